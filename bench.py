@@ -10,10 +10,12 @@ predecessors and vector map stay resident in HBM (mnav_set_resident_outputs), th
 the host.  Mesh and costs are resident before the timed region.  For N > 1 every rank (one per GPU) runs its own
 batches on its own replica of the mesh: the path shards by plan, there is no data-path collective (weak scaling).
 
-Prints ONE JSON line (see the task contract).  `value` = plans/s of the whole job (C2).  The settled-vertex count that
-feeds the algorithmic-bytes figure is instrumentation: it is read after the timed region (the batches are replayed
-untimed for the roofline object).  Rank 0 then measures, outside the timed region, the other BASELINE configurations on
-the same GPU and reports them under "configs", each with its own roofline and cpu_baseline objects:
+Prints ONE JSON line.  `value` = plans/s of the whole job (C2), `ms_per_step` = milliseconds of one timed batch.  The
+settled-vertex count that feeds the algorithmic-bytes figure comes from the timed batches' own statistics.  A plain run
+sets up, warms up, times the --steps batches, writes the last batch's outputs when --dump-outputs DIR is given, and
+prints the line.  With --full, rank 0 then measures, outside the timed region, the single-plan latencies, the CVP
+planner on the same mesh, the CPU baselines and the other BASELINE configurations on the same GPU, the latter under
+"configs", each with its own roofline and cpu_baseline objects:
   C2_paths_only  the same batches without finalize / vector map (vertex paths only), and with a larger batch
   C5  64 concurrent goals on the C2 mesh (one batch)
   C3  CVP wavefront on the 1M mesh (seed 3) with Steepness + Inflation costs, the whole cost stack built on the device
@@ -69,15 +71,22 @@ def main() -> None:
     ap.add_argument("--grid", type=int, default=int(os.environ.get("MNAV_BENCH_N", "1000")))
     ap.add_argument("--offset", type=float, default=float(os.environ.get("MNAV_BENCH_OFFSET", "0.3")),
                     help="goal_dist_offset (reference default 0.3; inf = full-field variant of SURVEY.md 8d)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline line's batches also measure the single-plan latencies, the CVP planner, the CPU baselines "
+                         "and the C2_paths_only / C5 / adapter / C3 / C4 legs (off: the headline figure only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, a fixed sample of the large outputs)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline legs")
     ap.add_argument("--cpu-all-cores-child", action="store_true", help=argparse.SUPPRESS)
-    ap.add_argument("--no-latency", action="store_true", help="skip the single-plan latency runs (profiling)")
+    ap.add_argument("--no-latency", action="store_true", help="--full: skip the single-plan latency runs")
     ap.add_argument("--config", default="C2", choices=["C2", "C4"], help="C2: the headline batch bench; C4: one sharded plan on the 10M mesh")
-    ap.add_argument("--no-configs", action="store_true", help="skip the C3/C4/C5 legs (profiling the headline kernel)")
-    ap.add_argument("--skip-c4", action="store_true", help="skip the 10M-vertex leg")
+    ap.add_argument("--no-configs", action="store_true", help="--full: skip the C2_paths_only / C5 / adapter / C3 / C4 legs")
+    ap.add_argument("--skip-c4", action="store_true", help="--full: skip the 10M-vertex leg")
     ap.add_argument("--c4-grid", type=int, default=int(os.environ.get("MNAV_BENCH_C4_N", "3163")))
     ap.add_argument("--c4-batch", type=int, default=int(os.environ.get("MNAV_BENCH_C4_BATCH", "4096")))   # tile-batch engine: 52 MB of blocked distances per plan at 10M = 213 GB (1536 plans on the per-plan engine: 831 plans/s; 4096 here: 1132)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.cpu_all_cores_child:
         return cpu_all_cores_child(args)
 
@@ -137,11 +146,11 @@ def main() -> None:
 
     # every plan leaves potential, predecessors and vector map behind, like the reference's dijkstra() (:380): resident in HBM
     ctx.set_resident_outputs(True)
-    first = None
+    first = None                                                        # (kept by a --full run only)
     for _ in range(max(args.warmup, 0)):
         g, t = batch_goals()
         r = ctx.plan_dijkstra_batch(g, t, goal_dist_offset=args.offset, want_fields=False, path_cap=16384)
-        if first is None:
+        if args.full and first is None:
             first = first_of(g, t, r)
     r = None                                                            # (a result keeps its path buffer of the binding's pool busy)
     prop_ms = kern_ms = launches = algo = vec_ms = 0.0
@@ -155,18 +164,20 @@ def main() -> None:
         st = r["stats"]                                                 # event timings + the finalize pass's settled count (already on the host)
         prop_ms += st["ms_propagation"]; kern_ms += st["ms_step_kernels"]; launches += st["launches"]; vec_ms += st["ms_vector_map"]
         algo += st["algorithmic_bytes"]; settled += st["settled"]
-        if first is None:
+        if args.full and first is None:
             first = first_of(g, t, r)
     barrier()
     elapsed = time.perf_counter() - t0
     headline_kernel = ctx.last_engine()                                 # which engine / kernel `auto` ran the batches on
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ctx, r, mesh.V)
     from mesh_navigation_amd import multi
     total_plans, elapsed = multi.aggregate_throughput(B * args.steps, elapsed, dist)   # sum of plans, MAX time over ranks
     ctx.set_resident_outputs(False)
 
     # single-plan latency (ms/makePlan, device part) -- rank 0 only, outside the timed region
     single_ms = single_p95 = None
-    if rank == 0 and not args.no_latency:
+    if rank == 0 and args.full and not args.no_latency:
         # SURVEY.md §8d protocol: 3 warm-ups, 20 timed plans (different goals), median and p95
         lat = []
         for k in range(23):
@@ -179,7 +190,7 @@ def main() -> None:
     # the second planner on the same mesh (CVP / FMM wavefront, cvp_mesh_planner.cpp:651-918): single-plan
     # latency and a batch of 128 -- reported next to the headline metric, not part of `value`
     cvp = None
-    if rank == 0 and not args.no_latency:
+    if rank == 0 and args.full and not args.no_latency:
         first_face = np.full(mesh.V, -1, np.int64)
         fl = mesh.faces.ravel()
         first_face[fl[::-1]] = (np.arange(fl.size)[::-1] // 3)           # some face of every vertex
@@ -264,9 +275,9 @@ def main() -> None:
                          "avg_launch_us": per_launch_s * 1e6, "propagation_ms_per_step": prop_ms / args.steps,
                          "settled_vertices_per_plan": settled / max(args.steps * B, 1)},
         }
-        if not args.no_cpu and world >= 1:
+        if args.full and not args.no_cpu:
             out["cpu_baseline"] = cpu_baseline(mesh, edge_w, costs, first, B, args.offset)
-        if not args.no_configs:
+        if args.full and not args.no_configs:
             cfgs = {}
             t_cfg = time.perf_counter()
             for name, leg in (("C2_paths_only", lambda: leg_paths_only(ctx, mesh, robot, rng, args)),
@@ -286,6 +297,46 @@ def main() -> None:
         dist.barrier()
         dist.destroy_process_group()
 
+
+
+DUMP_LIMIT = 64 << 20           # --dump-outputs writes at most this many bytes
+
+
+def write_npy(dirname, arrays):
+    os.makedirs(dirname, exist_ok=True)
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_LIMIT
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        assert np.isfinite(a).all(), f"{name}: not finite"
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
+def dump_outputs(dirname, ctx, r, V):
+    """--dump-outputs: what a caller of the timed path holds after its last batch.  Codes and path lengths of every plan;
+    the vertex paths of a fixed sample of plans; potential, predecessors and vector map (resident in HBM, read back per
+    plan) of the first two plans of that sample, on a fixed sample of the vertices when they would exceed 24 MB.
+    Vertex ids are float32 while they are exact in it, float64 above; everything else keeps its bits or is exact.
+    The potential is +inf where a plan did not reach a vertex: `reached` says where it is finite, and `dist` holds -1
+    there (a potential is never negative), so that every array is finite."""
+    sel = np.random.default_rng(20261016)
+    B = len(r["codes"])
+    plans = np.sort(sel.choice(B, size=min(B, 512), replace=False))
+    ids = np.float32 if V < (1 << 24) else np.float64
+    out = {"codes": r["codes"].astype(np.float64), "path_len": r["path_len"].astype(np.float64),
+           "sample_plans": plans.astype(np.float64),
+           "sample_paths": np.concatenate([r["paths"][int(k)] for k in plans]).astype(ids)}     # path_len[k] entries per sampled plan k
+    fields = plans[:2]
+    nv = min(V, (24 << 20) // (len(fields) * (4 + 8 + 12)))
+    verts = np.arange(V) if nv == V else np.sort(sel.choice(V, size=nv, replace=False))
+    out["field_plans"] = fields.astype(np.float64)
+    out["field_vertices"] = verts.astype(ids)
+    dist = np.stack([ctx.download_output("dist", int(k))[verts] for k in fields])
+    reached = np.isfinite(dist)
+    out["reached"] = reached.astype(np.float32)
+    out["dist"] = np.where(reached, dist, np.float32(-1.0)).astype(np.float32)
+    out["pred"] = np.stack([ctx.download_output("pred", int(k))[verts] for k in fields]).astype(np.float64)
+    out["vecmap"] = np.stack([ctx.download_output("vecmap", int(k))[verts] for k in fields])
+    write_npy(dirname, out)
 
 
 def run_leg(fn):
@@ -629,6 +680,9 @@ def sharded_c4(args, torch, dist, rank, local_rank, world):
         exch += res.exchanges
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        write_npy(args.dump_outputs, {"code": np.array([res.code], np.float64),
+                                      "path": res.path.astype(np.float32 if mesh.V < (1 << 24) else np.float64)})
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)

@@ -1,12 +1,13 @@
 #!/bin/bash
 # shader-core counters of the bench command (what bounds k_plan_persistent), one group per pass
+R="$(cd "$(dirname "$0")/.." && pwd)"                    # the repository root
 cd /tmp && export TMPDIR=/tmp
 i=0
 for grp in "LdsUtil LdsBankConflict" "SQ_INSTS_LDS SQ_INSTS_VALU SQ_INSTS_SALU SQ_ACTIVE_INST_LDS" "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_BUSY_CYCLES SQ_WAIT_INST_ANY" "SQ_WAVE_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_VMEM"; do
   i=$((i+1))
   OUT=$GRAFT_REPO_ROOT/gpurun_out/pmc_sq_$i
   rm -rf $OUT
-  rocprofv3 --pmc $grp --kernel-trace --output-format csv -d $OUT -o pmc -- python $GRAFT_REPO_ROOT/bench.py --steps 1 --warmup 1 --no-cpu --no-latency > $GRAFT_REPO_ROOT/gpurun_out/pmc_sq_$i.log 2>&1
+  rocprofv3 --pmc $grp --kernel-trace --output-format csv -d $OUT -o pmc -- python "$R/bench.py" --full --steps 1 --warmup 1 --no-cpu --no-latency > "$OUT.log" 2>&1
 done
 python - <<'PY'
 import csv, glob, os, collections

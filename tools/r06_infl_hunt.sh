@@ -4,7 +4,7 @@
 cd $GRAFT_REPO_ROOT; O=gpurun_out/r06/infl_hunt; rm -rf $O; mkdir -p $O
 for i in $(seq 1 ${HUNT_N:-18}); do
   SPIN=0; [ $i -gt ${HUNT_SPIN_AFTER:-999} ] && SPIN=1                  # (the second half with the host polling instead of blocking: MNAV_SPIN_WAIT)
-  MNAV_SPIN_WAIT=$SPIN MNAV_TRACE=1 timeout 300 python bench.py --skip-c4 --no-cpu > $O/line.json 2> $O/err.txt
+  MNAV_SPIN_WAIT=$SPIN MNAV_TRACE=1 timeout 300 python bench.py --full --skip-c4 --no-cpu > $O/line.json 2> $O/err.txt
   python - <<PY
 import json
 d = json.loads(open("$O/line.json").read().strip().splitlines()[-1])

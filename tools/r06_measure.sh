@@ -6,7 +6,7 @@
 #    tools/summarize_r06.py turns them into profiles/r06_*)  4. the soak (tools/gpu_soak.py) and the inflation fuzz
 cd $GRAFT_REPO_ROOT; O=gpurun_out/r06; mkdir -p $O
 timeout 2400 python -m pytest tests -m gpu -x -q > $O/gputest.log 2>&1; echo "suite rc=$?"; tail -4 $O/gputest.log
-MNAV_TRACE=1 timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_line.json 2> $O/bench_line.err; echo "bench rc=$?"; tail -c 300 $O/bench_line.json; echo
+MNAV_TRACE=1 timeout 1200 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_line.json 2> $O/bench_line.err; echo "bench rc=$?"; tail -c 300 $O/bench_line.json; echo
 grep -h "inflation it" $O/bench_line.err | tail -3 | cut -c1-200
 bash tools/prof_r06.sh c2 > $O/prof_c2.log 2>&1
 bash tools/prof_r06.sh c2sq > $O/prof_c2sq.log 2>&1
