@@ -175,8 +175,9 @@ int mnav_download_costs(mnav_ctx* ctx, float* vertex_costs_out, float* edge_weig
 /* -- cost layers on the device (mesh_layers) ------------------------------------------------------
  * The reference's layer plugins compute per-vertex costs on the CPU (AbstractLayer::computeLayer) and MeshMap
  * combines them.  These entry points keep that stack in HBM: layer `k` (0..63) is a resident cost array + lethal set.
- *   mnav_layer_upload      a layer computed elsewhere (ObstacleLayer, a costs file ...): costs V floats, lethal V bytes
- *                          or NULL
+ *   mnav_layer_upload      a layer computed elsewhere (a costs file, a layer plugin without a device version ...): costs
+ *                          V floats, lethal V bytes or NULL
+ *   mnav_layer_obstacle    ObstacleLayer::processPointCloud (obstacle_layer.cpp:216-290) from a point cloud: see below
  *   mnav_layer_steepness   SteepnessLayer::computeLayer (steepness_layer.cpp:157-166) from the resident vertex normals:
  *                          cost = acos(n.z) in float, lethal when > threshold (:82-93)
  *   mnav_layer_inflation   InflationLayer::computeLayer (inflation_layer.cpp:96-178): the lethal set of `input_layer`
@@ -215,6 +216,30 @@ int mnav_combine_layers_update(mnav_ctx* ctx, int mode, uint32_t n_layers, const
  * verification sweeps that were needed, device milliseconds of the wave alone.  Any pointer may be NULL. */
 int mnav_layer_stats(const mnav_ctx* ctx, uint32_t* steps, uint32_t* bands, uint64_t* evals, float* ms, uint32_t* verify_sweeps,
                      float* ms_wave);
+/* ObstacleLayer::processPointCloud (obstacle_layer.cpp:216-290) on the device: n_points points of point_step bytes each
+ * (x, y, z float32 at offsets 0, 4, 8, as PointCloud2 lays them out) are copied in, and layer `layer` becomes the
+ * obstacle layer of that cloud.  Per point p (sensor frame):
+ *   kept iff (double)sqrtf((x*x + y*y) + z*z) <= max_obstacle_dist (NaN points are dropped);
+ *   origin o = R p + t, sensor_to_map a row-major 3x4 float matrix (NULL = identity), each row ((m0 x + m1 y) + m2 z) + m3;
+ *   ray along down_axis (3 floats, already in the map frame, used as given: not re-normalised; must be finite, non-zero);
+ *   cast with the watertight ray/triangle test of Woop, Benthin & Wald 2013 (mesh_navigation_amd/csrc/mnav_ray.h),
+ *   two-sided, t >= 0, closest hit, equal t to the smallest face id, degenerate faces (det == 0) never hit, over a linear
+ *   BVH of the resident faces that is built on the first call after mnav_upload_mesh;
+ *   a hit with (double)t <= robot_height makes the face's three vertices lethal (both limits: +inf = no limit).
+ * The layer's costs become +inf on lethal vertices and 0 elsewhere; its lethal flags become the new set.  changed_out
+ * (capacity V, or NULL) receives the ascending ids whose lethal flag differs from the layer's flags before the call (a slot
+ * that held no layer counts as empty): the `changed` set of the reference's notifyChange (:265-278), ready for
+ * mnav_layer_inflation (with this layer as input) and mnav_combine_layers_update.  An empty cloud clears the layer.
+ * Departures from the reference: the reference's raycaster is Embree or lvr2's BVH (mesh_map.cpp:312-324), neither of which
+ * pins edge / tie behaviour; Eigen's summation order of R p is not pinned; a ray whose origin is not finite hits nothing.
+ * Returns 0 / <0 (mnav_last_error). */
+int mnav_layer_obstacle(mnav_ctx* ctx, uint32_t layer, uint32_t n_points, const void* points, uint32_t point_step,
+                        const float* sensor_to_map, const float* down_axis, double robot_height, double max_obstacle_dist,
+                        uint32_t* changed_out, uint32_t* n_changed, uint32_t* n_lethal);
+/* Counters of the last mnav_layer_obstacle: rays kept by the distance filter, rays that hit a face, rays that made a face
+ * lethal, device milliseconds of the last BVH build, of the ray cast kernel and of the whole call.  Any pointer may be NULL. */
+int mnav_obstacle_stats(const mnav_ctx* ctx, uint32_t* rays_kept, uint32_t* hits, uint32_t* lethal_rays, float* ms_bvh_build,
+                        float* ms_cast, float* ms_total);
 
 /* -- one plan over several GPUs (BASELINE config 4) ---------------------------------------------
  * The reference's loop (dijkstra_mesh_planner.cpp:287-348) on a mesh that is range-partitioned over `world`

@@ -27,6 +27,7 @@ SYMBOLS = [
     "mnav_shard_finalize", "mnav_update_costs", "mnav_update_edge_weights", "mnav_download_costs", "mnav_set_resident_outputs", "mnav_download_output",
     "mnav_vector_at", "mnav_backtrack_cvp", "mnav_backtrack_cvp_batch", "mnav_layer_upload", "mnav_layer_steepness", "mnav_layer_inflation", "mnav_layer_download",
     "mnav_combine_layers", "mnav_layer_stats", "mnav_layer_download_vectors", "mnav_combine_layers_update",
+    "mnav_layer_obstacle", "mnav_obstacle_stats",
     "mnav_set_option", "mnav_get_option", "mnav_shard_set_goal_tie", "mnav_last_engine",
 ]
 
@@ -149,6 +150,10 @@ def load(path: str | None = None):
     L.mnav_combine_layers.argtypes = [vp, C.c_int, u32, vp, vp, f64, vp]
     L.mnav_layer_stats.restype = C.c_int
     L.mnav_layer_stats.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(C.c_uint64), C.POINTER(C.c_float), C.POINTER(u32), C.POINTER(C.c_float)]
+    L.mnav_layer_obstacle.restype = C.c_int
+    L.mnav_layer_obstacle.argtypes = [vp, u32, u32, vp, u32, vp, vp, f64, f64, vp, C.POINTER(u32), C.POINTER(u32)]
+    L.mnav_obstacle_stats.restype = C.c_int
+    L.mnav_obstacle_stats.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.mnav_shard_setup.restype = C.c_int
     L.mnav_shard_setup.argtypes = [vp, u32, u32]
     L.mnav_shard_setup_partition.restype = C.c_int
@@ -190,6 +195,24 @@ def _f32(a):
 
 def _u32(a):
     return np.ascontiguousarray(a, dtype=np.uint32)
+
+
+def quat_to_matrix(q_wxyz, translation) -> np.ndarray:
+    """Row-major 3x4 float32 [R | t]: R = Eigen::Quaternionf(w, x, y, z).normalized().toRotationMatrix(), restated in
+    float32 with Eigen's formula (Quaternion.h toRotationMatrix); bit equality with Eigen's build is not pinned."""
+    f = np.float32
+    q = np.asarray(q_wxyz, f).reshape(4)
+    nrm = np.sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3], dtype=f)
+    w, x, y, z = (q / nrm).astype(f)
+    tx, ty, tz = f(2) * x, f(2) * y, f(2) * z
+    twx, twy, twz = tx * w, ty * w, tz * w
+    txx, txy, txz = tx * x, ty * x, tz * x
+    tyy, tyz, tzz = ty * y, tz * y, tz * z
+    one = f(1)
+    R = np.array([[one - (tyy + tzz), txy - twz, txz + twy],
+                  [txy + twz, one - (txx + tzz), tyz - twx],
+                  [txz - twy, tyz + twx, one - (txx + tyy)]], f)
+    return np.ascontiguousarray(np.concatenate([R, np.asarray(translation, f).reshape(3, 1)], axis=1), f)
 
 
 @dataclass
@@ -390,6 +413,48 @@ class MnavContext:
         a, b, e, ms, vs, mw = C.c_uint32(), C.c_uint32(), C.c_uint64(), C.c_float(), C.c_uint32(), C.c_float()
         self._L.mnav_layer_stats(self._h, C.byref(a), C.byref(b), C.byref(e), C.byref(ms), C.byref(vs), C.byref(mw))
         return dict(steps=a.value, bands=b.value, evals=e.value, ms=ms.value, ms_wave=mw.value, verify_sweeps=vs.value)
+
+    def layer_obstacle(self, layer: int, points, sensor_to_map=None, rotation_wxyz=None, translation=None,
+                       down_axis=(0.0, 0.0, -1.0), robot_height: float = np.inf, max_obstacle_dist: float = np.inf) -> dict:
+        """ObstacleLayer::processPointCloud on the device (mnav_layer_obstacle, include/mnav.h).
+
+        points: an (n, 3) float32 array, or a structured array whose float32 fields x, y, z sit at byte offsets 0, 4, 8
+        (any itemsize: it is the point_step).  The sensor-to-map transform is either `sensor_to_map`, a row-major 3x4
+        matrix, or `rotation_wxyz` + `translation`, turned into one here with Eigen's Quaternion::toRotationMatrix formula
+        after normalising the quaternion, in float32 (the reference does that conversion with Eigen; that the two agree
+        bit for bit is not pinned).  Neither = identity.  down_axis is already in the map frame and used as given.
+        Returns dict(changed = ascending uint32 ids whose lethal flag changed, n_lethal, stats = the call's counters)."""
+        pts = np.asarray(points)
+        if pts.dtype.names:
+            f = pts.dtype.fields
+            if any(k not in f or f[k][0] != np.float32 or f[k][1] != o for k, o in (("x", 0), ("y", 4), ("z", 8))):
+                raise ValueError("structured points need float32 fields x, y, z at byte offsets 0, 4, 8")
+            pts = np.ascontiguousarray(pts.reshape(-1))
+            step = pts.dtype.itemsize
+        else:
+            pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 3)
+            step = 12
+        n = int(pts.shape[0])
+        if sensor_to_map is not None and rotation_wxyz is not None:
+            raise ValueError("give sensor_to_map or rotation_wxyz / translation, not both")
+        m = None
+        if sensor_to_map is not None:
+            m = _f32(sensor_to_map).reshape(3, 4)
+        elif rotation_wxyz is not None:
+            m = quat_to_matrix(rotation_wxyz, (0.0, 0.0, 0.0) if translation is None else translation)
+        d = _f32(down_axis).reshape(3)
+        changed = np.empty(max(self.V, 1), np.uint32)
+        nc, nl = C.c_uint32(), C.c_uint32()
+        rc = self._L.mnav_layer_obstacle(self._h, int(layer), n, _p(pts) if n else None, int(step), _p(m), _p(d),
+                                         float(robot_height), float(max_obstacle_dist), _p(changed), C.byref(nc), C.byref(nl))
+        if rc != 0:
+            raise RuntimeError(f"mnav_layer_obstacle failed: {self._err()}")
+        return dict(changed=changed[:nc.value].copy(), n_lethal=nl.value, stats=self.obstacle_stats())
+
+    def obstacle_stats(self) -> dict:
+        k, h, lr, mb, mc, mt = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_float(), C.c_float(), C.c_float()
+        self._L.mnav_obstacle_stats(self._h, C.byref(k), C.byref(h), C.byref(lr), C.byref(mb), C.byref(mc), C.byref(mt))
+        return dict(rays_kept=k.value, hits=h.value, lethal_rays=lr.value, ms_bvh_build=mb.value, ms_cast=mc.value, ms_total=mt.value)
 
     def layer_download(self, layer: int, distances: bool = False):
         c = np.empty(self.V, np.float32)

@@ -76,6 +76,7 @@ constexpr int kChunk = 96;  // step launches per graph replay; multiple of 6 (sl
 #include "mnav_tb_finalize.h"
 #include "mnav_tbv.h"
 #include "mnav_walk.h"
+#include "mnav_obstacle.h"   // obstacle layer: LBVH build, ray cast, change list (mnav_obs::)
 
 // One back-tracking job: the plan's resident vector map and the two ends of the walk.
 struct WalkJob { const float* vecmap; float seed[3]; uint32_t seed_face; float target[3]; uint32_t target_face; };
@@ -207,6 +208,7 @@ struct mnav_ctx {
   Corner* d_crn_infl = nullptr; bool crn_infl_valid = false;       // corners over the edge distances (inflation wave)
   uint8_t *d_infl_mask = nullptr, *d_zero_u8 = nullptr;
   float* d_infl_keyd = nullptr;
+  mnav_obs::Bvh obs;                                               // obstacle layer: BVH built by the first mnav_layer_obstacle after an upload
   uint32_t infl_steps = 0, infl_bands = 0; uint64_t infl_evals = 0; float infl_ms = 0.f, infl_ms_wave = 0.f;   // last inflation wave
   TilePlan* d_tplans = nullptr; uint32_t tplans_cap = 0;
   TCtl* h_tctl = nullptr;
@@ -626,6 +628,7 @@ void mnav_destroy(mnav_ctx* ctx)
   tb_free(ctx);
   for (auto& s : ctx->slots) free_slot(s);
   drop_layers(ctx);
+  mnav_obs::bvh_free(ctx->obs);
   (void)hipFree(ctx->d_row_ptr); (void)hipFree(ctx->d_nbr_u); (void)hipFree(ctx->d_nbr_e); (void)hipFree(ctx->d_crn_ptr);
   (void)hipFree(ctx->d_edge_vtx); (void)hipFree(ctx->d_crn_idx); (void)hipFree(ctx->d_crn_walk); (void)hipFree(ctx->d_xyz); (void)hipFree(ctx->d_nrm);
   (void)hipFree(ctx->d_cost); (void)hipFree(ctx->d_w); (void)hipFree(ctx->d_edge_dist); (void)hipFree(ctx->d_invalid);
@@ -694,6 +697,7 @@ int mnav_upload_mesh(mnav_ctx* ctx, uint32_t V, uint32_t F, uint32_t E, const fl
   for (auto& s : ctx->slots) free_slot(s);
   ctx->slots.clear();
   drop_layers(ctx);
+  mnav_obs::bvh_free(ctx->obs);                                      // belongs to the old mesh; rebuilt lazily
   if (ctx->d_edge_dist) { ctx->alloc_bytes.erase((void*)ctx->d_edge_dist); (void)hipFree(ctx->d_edge_dist); ctx->d_edge_dist = nullptr; }   // belongs to the old mesh
   drop_graphs(ctx);
   (void)hipFree(ctx->d_paths); ctx->d_paths = nullptr; ctx->paths_words = 0;
@@ -1656,6 +1660,7 @@ uint32_t mnav_plan_cvp_batch(mnav_ctx* ctx, uint32_t n, const float* seed_pos, c
 }
 
 #include "mnav_shard_capi.h"   // mnav_shard_* (one plan over several GPUs)
+#include "mnav_obstacle_capi.h"   // mnav_layer_obstacle, mnav_obstacle_stats
 
 void mnav_cancel(mnav_ctx* ctx)
 {

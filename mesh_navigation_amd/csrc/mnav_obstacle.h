@@ -1,0 +1,343 @@
+// mnav_obstacle.h -- kernels of the obstacle layer (mnav_layer_obstacle; ObstacleLayer::processPointCloud,
+// obstacle_layer.cpp:134-290): a linear BVH over the resident faces (Karras 2012: Morton codes of the face centroids,
+// radix sort, hierarchy emission, bottom-up refit with one arrival counter per node), one lane per ray for the
+// closest-hit traversal (mnav_ray.h), then the new lethal set is diffed against the layer's old one and compacted into
+// the ascending change list.  Included by mnav.hip after the anonymous namespace of the planner kernels; the C ABI
+// is in mnav_obstacle_capi.h.
+#pragma once
+
+#include <rocprim/device/device_radix_sort.hpp>
+
+#include "mnav_ray.h"
+
+namespace mnav_obs {
+
+constexpr uint32_t kLeaf = 0x80000000u;   // child reference: leaf (sorted position) | kLeaf, else an internal node
+constexpr int kStack = 64;                // traversal stack per lane (LDS): a root-to-leaf path has <= 62 internal nodes
+constexpr int kCastBlock = 64;            // one wave per workgroup: 16 KiB of LDS stack
+constexpr int kOutBlock = 256;            // output passes: 4 vertices per lane
+constexpr int kOutPer = 4;
+// counters of one call (device words)
+enum { kKept = 0, kHits, kLethalRays, kOverflow, kChanged, kLethal, kCounters };
+
+// Resident acceleration structure + per-call scratch of the obstacle layer; built on the first call after a mesh
+// upload, dropped by the next upload and by mnav_destroy.
+struct Bvh {
+  bool valid = false;
+  uint32_t F = 0, root = kNone;
+  float4* nodes = nullptr;     // F-1 internal nodes x 4 float4: left box (6 floats), right box (6), left ref, right ref
+  float4* tris = nullptr;      // F leaves in Morton order x 3 float4: a.xyz b.xyz c.xyz, original face id (bits)
+  uint32_t* fvtx = nullptr;    // 3F vertex ids, original face order
+  uint8_t* flags = nullptr;    // V: lethal flags of the current call
+  uint32_t* ids = nullptr;     // V: change list
+  uint32_t* blk = nullptr;     // 3 x blocks: changed per block, lethal per block, exclusive offsets
+  uint32_t* cnt = nullptr;     // kCounters words
+  uint8_t* pts = nullptr; size_t pts_cap = 0;
+  float ms_build = 0.f, ms_cast = 0.f, ms_total = 0.f;
+  uint32_t kept = 0, hits = 0, lethal_rays = 0;
+};
+
+inline void bvh_free(Bvh& b)
+{
+  (void)hipFree(b.nodes); (void)hipFree(b.tris); (void)hipFree(b.fvtx); (void)hipFree(b.flags); (void)hipFree(b.ids);
+  (void)hipFree(b.blk); (void)hipFree(b.cnt); (void)hipFree(b.pts);
+  b = Bvh{};
+}
+
+__device__ __forceinline__ uint32_t f2ord(float f)
+{
+  const uint32_t u = __float_as_uint(f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float ord2f(uint32_t u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u); }
+
+// mesh bounds: bnd[0..2] = ordered min, bnd[3..5] = ordered max (pre-set to 0xFFFFFFFF / 0)
+__global__ __launch_bounds__(256) void k_obs_bounds(uint32_t V, const float* __restrict__ xyz, uint32_t* __restrict__ bnd)
+{
+  float lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
+  for (uint32_t v = blockIdx.x * 256 + threadIdx.x; v < V; v += gridDim.x * 256)
+    for (int k = 0; k < 3; ++k) { const float x = xyz[3 * (size_t)v + k]; lo[k] = fminf(lo[k], x); hi[k] = fmaxf(hi[k], x); }
+  for (int k = 0; k < 3; ++k)
+    for (int off = 32; off > 0; off >>= 1) { lo[k] = fminf(lo[k], __shfl_xor(lo[k], off)); hi[k] = fmaxf(hi[k], __shfl_xor(hi[k], off)); }
+  if ((threadIdx.x & 63) == 0 && lo[0] <= hi[0])
+    for (int k = 0; k < 3; ++k) { atomicMin(&bnd[k], f2ord(lo[k])); atomicMax(&bnd[3 + k], f2ord(hi[k])); }
+}
+
+__device__ __forceinline__ uint32_t expand10(uint32_t v)
+{
+  v = (v * 0x00010001u) & 0xFF0000FFu;
+  v = (v * 0x00000101u) & 0x0F00F00Fu;
+  v = (v * 0x00000011u) & 0xC30C30C3u;
+  v = (v * 0x00000005u) & 0x49249249u;
+  return v;
+}
+
+// 30-bit Morton code of every face centroid; ids = 0..F-1
+__global__ __launch_bounds__(256) void k_obs_morton(uint32_t F, const uint32_t* __restrict__ fv, const float* __restrict__ xyz,
+                                                     const uint32_t* __restrict__ bnd, uint32_t* __restrict__ keys, uint32_t* __restrict__ ids)
+{
+  const uint32_t f = blockIdx.x * 256 + threadIdx.x;
+  if (f >= F) return;
+  uint32_t code = 0;
+  for (int k = 0; k < 3; ++k) {
+    const float c = (xyz[3 * (size_t)fv[3 * (size_t)f] + k] + xyz[3 * (size_t)fv[3 * (size_t)f + 1] + k] + xyz[3 * (size_t)fv[3 * (size_t)f + 2] + k]) * (1.0f / 3.0f);
+    const float lo = ord2f(bnd[k]), ext = ord2f(bnd[3 + k]) - lo;
+    float u = ext > 0.f ? (c - lo) / ext : 0.f;
+    u = fminf(fmaxf(u * 1024.f, 0.f), 1023.f);          // NaN-free: fmaxf(NaN, 0) = 0
+    code |= expand10((uint32_t)u) << (2 - k);
+  }
+  keys[f] = code;
+  ids[f] = f;
+}
+
+// Karras 2012 common-prefix length of sorted keys i and j (index as tie-break), -1 outside [0, F)
+__device__ __forceinline__ int obs_delta(const uint32_t* __restrict__ keys, int64_t F, int64_t i, int64_t j)
+{
+  if (j < 0 || j >= F) return -1;
+  const uint32_t a = keys[i], b = keys[j];
+  if (a == b) return 32 + __clz((uint32_t)i ^ (uint32_t)j);
+  return __clz(a ^ b);
+}
+
+// internal node i covers a key range; its split is where the common prefix grows (Karras 2012, Fig. 4)
+__global__ __launch_bounds__(256) void k_obs_hierarchy(uint32_t F, const uint32_t* __restrict__ keys, float4* __restrict__ nodes,
+                                                       uint32_t* __restrict__ par_int, uint32_t* __restrict__ par_leaf)
+{
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t n = F;
+  if (i >= n - 1) return;
+  const int d = obs_delta(keys, n, i, i + 1) - obs_delta(keys, n, i, i - 1) >= 0 ? 1 : -1;
+  const int dmin = obs_delta(keys, n, i, i - d);
+  int64_t lmax = 2;
+  while (obs_delta(keys, n, i, i + lmax * d) > dmin) lmax *= 2;
+  int64_t l = 0;
+  for (int64_t t = lmax / 2; t >= 1; t /= 2)
+    if (obs_delta(keys, n, i, i + (l + t) * d) > dmin) l += t;
+  const int64_t j = i + l * d;
+  const int dnode = obs_delta(keys, n, i, j);
+  int64_t s = 0, t = l;
+  do {
+    t = (t + 1) >> 1;
+    if (obs_delta(keys, n, i, i + (s + t) * d) > dnode) s += t;
+  } while (t > 1);
+  const int64_t gamma = i + s * d + (d < 0 ? -1 : 0);
+  if (gamma < 0 || gamma > n - 2) return;                // cannot happen for sorted keys; keeps every write in bounds
+  const int64_t lo = i < j ? i : j, hi = i < j ? j : i;
+  const uint32_t left = lo == gamma ? ((uint32_t)gamma | kLeaf) : (uint32_t)gamma;
+  const uint32_t right = hi == gamma + 1 ? ((uint32_t)(gamma + 1) | kLeaf) : (uint32_t)(gamma + 1);
+  uint32_t* w = (uint32_t*)(nodes + 4 * i);
+  w[12] = left; w[13] = right; w[14] = 0; w[15] = 0;
+  if (left & kLeaf) par_leaf[left & ~kLeaf] = (uint32_t)i; else par_int[left] = (uint32_t)i;
+  if (right & kLeaf) par_leaf[right & ~kLeaf] = (uint32_t)i; else par_int[right] = (uint32_t)i;
+  if (i == 0) par_int[0] = kNone;
+}
+
+// Leaf k: the triangle in Morton order, its box padded by 1e-4 (1 + max |coordinate|) on every side, so that no
+// rounding of the slab test or of the watertight test can cull a face the test hits (brute force == BVH, bit for bit);
+// then up the tree: the second lane to arrive at a node owns its union (agent-scope release / acquire around the counter).
+__global__ __launch_bounds__(256) void k_obs_leaves(uint32_t F, const uint32_t* __restrict__ ids, const uint32_t* __restrict__ fv,
+                                                    const float* __restrict__ xyz, float4* __restrict__ tris, float4* nodes,
+                                                    const uint32_t* __restrict__ par_int, const uint32_t* __restrict__ par_leaf,
+                                                    uint32_t* arrive)
+{
+  const uint32_t k = blockIdx.x * 256 + threadIdx.x;
+  if (k >= F) return;
+  const uint32_t f = ids[k];
+  float p[9];
+  for (int c = 0; c < 3; ++c)
+    for (int a = 0; a < 3; ++a) p[3 * c + a] = xyz[3 * (size_t)fv[3 * (size_t)f + c] + a];
+  tris[3 * (size_t)k + 0] = make_float4(p[0], p[1], p[2], p[3]);
+  tris[3 * (size_t)k + 1] = make_float4(p[4], p[5], p[6], p[7]);
+  tris[3 * (size_t)k + 2] = make_float4(p[8], __uint_as_float(f), 0.f, 0.f);
+  if (F == 1) return;
+  float box[6];
+  float m = 0.f;
+  for (int a = 0; a < 3; ++a) {
+    box[a] = fminf(fminf(p[a], p[3 + a]), p[6 + a]);
+    box[3 + a] = fmaxf(fmaxf(p[a], p[3 + a]), p[6 + a]);
+    m = fmaxf(m, fmaxf(fabsf(box[a]), fabsf(box[3 + a])));
+  }
+  const float pad = 1e-4f * (1.f + m);
+  for (int a = 0; a < 3; ++a) { box[a] -= pad; box[3 + a] += pad; }
+  uint32_t child = k | kLeaf;
+  uint32_t node = par_leaf[k];
+  while (node < F - 1) {                                // the root's parent is kNone
+    float* w = (float*)(nodes + 4 * (size_t)node);
+    const uint32_t side = __float_as_uint(w[12]) == child ? 0 : 6;
+    for (int a = 0; a < 6; ++a) w[side + a] = box[a];
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const uint32_t old = __hip_atomic_fetch_add(&arrive[node], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (old == 0) return;                                 // the sibling's lane finishes this node
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const volatile float* r = w;
+    for (int a = 0; a < 3; ++a) {
+      box[a] = fminf(r[a], r[6 + a]);
+      box[3 + a] = fmaxf(r[3 + a], r[9 + a]);
+    }
+    child = node;
+    node = par_int[node];
+  }
+}
+
+// slab test of a padded box; the far bound is widened by 1 + 2 gamma_3 (Ize 2013) against the test's own rounding
+__device__ __forceinline__ bool obs_box(const float* b, const float o[3], const float inv[3], float best, float* tnear)
+{
+  float tn = 0.f, tf = INFINITY;
+  for (int a = 0; a < 3; ++a) {
+    const float t0 = (b[a] - o[a]) * inv[a], t1 = (b[3 + a] - o[a]) * inv[a];
+    tn = fmaxf(tn, fminf(t0, t1));
+    tf = fminf(tf, fmaxf(t0, t1));
+  }
+  *tnear = tn;
+  return tn <= tf * 1.000001f && tn <= best;
+}
+
+struct CastArgs {
+  uint32_t n, step, F, root;
+  float m[12];
+  float inv[3];
+  RaySetup rs;
+  double max_dist, robot_height;
+};
+
+// One lane per ray: gather the point (byte stride), filter, transform, closest hit over the BVH (ties: smallest face id),
+// lethal -> the face's three vertices are flagged (plain byte stores of 1: no race that matters).
+__global__ __launch_bounds__(kCastBlock) void k_obs_cast(CastArgs A, const uint8_t* __restrict__ pts, const float4* __restrict__ nodes,
+                                                         const float4* __restrict__ tris, const uint32_t* __restrict__ fvtx,
+                                                         uint8_t* __restrict__ flags, uint32_t* __restrict__ cnt)
+{
+  __shared__ uint32_t stack[kStack * kCastBlock];
+  const uint32_t lane = threadIdx.x;
+  const uint32_t i = blockIdx.x * kCastBlock + lane;
+  bool kept = false, hit = false, leth = false, over = false;
+  if (i < A.n) {
+    const uint8_t* p = pts + (size_t)i * A.step;
+    float x, y, z;
+    if ((A.step & 3u) == 0) { const float* q = (const float*)p; x = q[0]; y = q[1]; z = q[2]; }
+    else { __builtin_memcpy(&x, p, 4); __builtin_memcpy(&y, p + 4, 4); __builtin_memcpy(&z, p + 8, 4); }
+    kept = ray_point_kept(x, y, z, A.max_dist);
+    float o[3];
+    ray_transform(A.m, x, y, z, o);
+    if (kept && A.F && ray_origin_finite(o)) {
+      float best = INFINITY;
+      uint32_t best_f = kNone, sp = 0, node = A.root;
+      for (;;) {
+        if ((node & kLeaf) ? (node & ~kLeaf) >= A.F : node + 1 >= A.F) {
+          // not a node of this tree (cannot happen): nothing to test
+        } else if (node & kLeaf) {
+          const size_t k = node & ~kLeaf;
+          const float4 t0 = tris[3 * k], t1 = tris[3 * k + 1], t2 = tris[3 * k + 2];
+          const float a[3] = { t0.x, t0.y, t0.z }, b[3] = { t0.w, t1.x, t1.y }, c[3] = { t1.z, t1.w, t2.x };
+          const uint32_t f = __float_as_uint(t2.y);
+          float t;
+          if (ray_triangle(A.rs, o, a, b, c, &t) && (t < best || (t == best && f < best_f))) { best = t; best_f = f; }
+        } else {
+          const float4 q0 = nodes[4 * (size_t)node], q1 = nodes[4 * (size_t)node + 1], q2 = nodes[4 * (size_t)node + 2], q3 = nodes[4 * (size_t)node + 3];
+          const float bl[6] = { q0.x, q0.y, q0.z, q0.w, q1.x, q1.y }, br[6] = { q1.z, q1.w, q2.x, q2.y, q2.z, q2.w };
+          float tl, tr;
+          const bool hl = obs_box(bl, o, A.inv, best, &tl), hr = obs_box(br, o, A.inv, best, &tr);
+          const uint32_t cl = __float_as_uint(q3.x), cr = __float_as_uint(q3.y);
+          if (hl && hr) {
+            const uint32_t nearc = tl <= tr ? cl : cr, farc = tl <= tr ? cr : cl;
+            if (sp < (uint32_t)kStack) stack[sp++ * kCastBlock + lane] = farc;
+            else over = true;
+            node = nearc;
+            continue;
+          }
+          if (hl) { node = cl; continue; }
+          if (hr) { node = cr; continue; }
+        }
+        if (sp == 0) break;
+        node = stack[--sp * kCastBlock + lane];
+      }
+      if (best_f != kNone) {
+        hit = true;
+        if ((double)best <= A.robot_height) {
+          leth = true;
+          for (int c = 0; c < 3; ++c) flags[fvtx[3 * (size_t)best_f + c]] = 1;
+        }
+      }
+    }
+  }
+  const uint64_t bk = __ballot(kept), bh = __ballot(hit), bl = __ballot(leth), bo = __ballot(over);
+  if (lane == 0) {
+    if (bk) atomicAdd(&cnt[kKept], (uint32_t)__popcll(bk));
+    if (bh) atomicAdd(&cnt[kHits], (uint32_t)__popcll(bh));
+    if (bl) atomicAdd(&cnt[kLethalRays], (uint32_t)__popcll(bl));
+    if (bo) atomicAdd(&cnt[kOverflow], 1u);
+  }
+}
+
+// exclusive scan of one value per lane over a block of kOutBlock lanes; *total = the block's sum
+__device__ __forceinline__ uint32_t obs_block_scan(uint32_t v, uint32_t* lds, uint32_t* total)
+{
+  const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  uint32_t s = v;
+  for (int off = 1; off < 64; off <<= 1) { const uint32_t u = __shfl_up(s, off); if (lane >= (uint32_t)off) s += u; }
+  if (lane == 63) lds[w] = s;
+  __syncthreads();
+  uint32_t base = 0, all = 0;
+  for (uint32_t k = 0; k < kOutBlock / 64; ++k) { if (k < w) base += lds[k]; all += lds[k]; }
+  __syncthreads();
+  *total = all;
+  return base + s - v;
+}
+
+// per block of kOutBlock * kOutPer vertices: how many flags change, how many are lethal
+__global__ __launch_bounds__(kOutBlock) void k_obs_count(uint32_t V, const uint8_t* __restrict__ flags, const uint8_t* __restrict__ old,
+                                                         uint32_t* __restrict__ blk, uint32_t nblk)
+{
+  __shared__ uint32_t lds[kOutBlock / 64];
+  const size_t v0 = ((size_t)blockIdx.x * kOutBlock + threadIdx.x) * kOutPer;
+  uint32_t c = 0, l = 0;
+  for (int k = 0; k < kOutPer; ++k)
+    if (v0 + k < V) { const uint8_t f = flags[v0 + k]; c += f != old[v0 + k]; l += f; }
+  uint32_t tc, tl;
+  (void)obs_block_scan(c, lds, &tc);
+  (void)obs_block_scan(l, lds, &tl);
+  if (threadIdx.x == 0) { blk[blockIdx.x] = tc; blk[nblk + blockIdx.x] = tl; }
+}
+
+// one workgroup: exclusive offsets of the per-block change counts, totals into cnt
+__global__ __launch_bounds__(kOutBlock) void k_obs_scan(uint32_t nblk, uint32_t* __restrict__ blk, uint32_t* __restrict__ cnt)
+{
+  __shared__ uint32_t lds[kOutBlock / 64];
+  uint32_t carry = 0, lethal = 0;
+  for (uint32_t b0 = 0; b0 < nblk; b0 += kOutBlock) {
+    const uint32_t b = b0 + threadIdx.x;
+    const uint32_t c = b < nblk ? blk[b] : 0, l = b < nblk ? blk[nblk + b] : 0;
+    uint32_t tc, tl;
+    const uint32_t ex = obs_block_scan(c, lds, &tc);
+    (void)obs_block_scan(l, lds, &tl);
+    if (b < nblk) blk[2 * nblk + b] = carry + ex;
+    carry += tc; lethal += tl;
+  }
+  if (threadIdx.x == 0) { cnt[kChanged] = carry; cnt[kLethal] = lethal; }
+}
+
+// the changed ids in ascending order (block offset + lane prefix), then the layer's flags and costs (+inf / 0)
+__global__ __launch_bounds__(kOutBlock) void k_obs_emit(uint32_t V, const uint8_t* __restrict__ flags, uint8_t* __restrict__ lethal,
+                                                        float* __restrict__ cost, const uint32_t* __restrict__ blk, uint32_t nblk,
+                                                        uint32_t* __restrict__ ids)
+{
+  __shared__ uint32_t lds[kOutBlock / 64];
+  const size_t v0 = ((size_t)blockIdx.x * kOutBlock + threadIdx.x) * kOutPer;
+  uint8_t f[kOutPer], ch[kOutPer];
+  uint32_t c = 0;
+  for (int k = 0; k < kOutPer; ++k) {
+    f[k] = 0; ch[k] = 0;
+    if (v0 + k < V) { f[k] = flags[v0 + k]; ch[k] = f[k] != lethal[v0 + k]; c += ch[k]; }
+  }
+  uint32_t tot;
+  uint32_t pos = blk[2 * nblk + blockIdx.x] + obs_block_scan(c, lds, &tot);
+  for (int k = 0; k < kOutPer; ++k) {
+    if (v0 + k >= V) break;
+    if (ch[k]) ids[pos++] = (uint32_t)(v0 + k);
+    lethal[v0 + k] = f[k];
+    cost[v0 + k] = f[k] ? INFINITY : 0.f;
+  }
+}
+
+}  // namespace mnav_obs
