@@ -240,6 +240,31 @@ int mnav_layer_obstacle(mnav_ctx* ctx, uint32_t layer, uint32_t n_points, const 
  * lethal, device milliseconds of the last BVH build, of the ray cast kernel and of the whole call.  Any pointer may be NULL. */
 int mnav_obstacle_stats(const mnav_ctx* ctx, uint32_t* rays_kept, uint32_t* hits, uint32_t* lethal_rays, float* ms_bvh_build,
                         float* ms_cast, float* ms_total);
+/* The local-neighbourhood layers on the device: HeightDiffLayer (height_diff_layer.cpp:103-110), RoughnessLayer
+ * (roughness_layer.cpp:144) and RidgeLayer (ridge_layer.cpp:155-184).  Per vertex v:
+ *   N(v)       the vertices reachable from v over mesh edges along a path whose every vertex u has (double)d2(u) < radius *
+ *              radius (radius * radius in double, strict); d2 = (dx*dx + dy*dy) + dz*dz in float, d = p_u - p_v, no
+ *              contraction (lvr2 BaseVector::squaredDistanceFrom).  v is always a member; a vertex without edges has
+ *              N(v) = {v}.  N(v) is a set: each member counts once, whatever order the visit takes.
+ *   height     max z - min z over N(v), world z, subtracted in float (no normals needed)
+ *   roughness  the mean over N(v) of acos(clamp(dot(n_v, n_u), -1, 1)), dot = (ax*bx + ay*by) + az*bz in float, acos = the
+ *              host libm's acosf (the restatement used by mnav_layer_steepness)
+ *   ridge      the mean over N(v) of sqrtf(|(p_u + n_u) - (p_v + n_v)|^2), additions in float, squared length as d2
+ *   mean       each float term t becomes llrint((double)t * 2^32) (half to even); the int64 sum S gives
+ *              (float)(((double)S * 2^-32) / (double)|N(v)|): order-free, so the result is deterministic bit for bit
+ * The layer's costs become the values, its lethal flags (double)value > threshold (computeLethals).  Roughness and ridge
+ * read the resident vertex normals and fail without them.  radius must be finite and >= 0; a ridge call needs
+ * V * (2 * radius + 2) < 2^31 (the int64 sum cannot overflow).  Layer slots as for mnav_layer_steepness.  Departures from
+ * lvr2 (whose sources the spec could not be checked against: INTEGRATION.md): a vertex met twice by lvr2's DFS would count
+ * twice there; the mean is summed in fixed point, not in float in DFS order; the clamp of the dot product.
+ * Reference defaults: height_diff threshold 0.185, radius 0.3; roughness and ridge threshold 0.3, radius 0.3.
+ * Returns 0 / <0 (mnav_last_error); on error the layer is left untouched. */
+int mnav_layer_height_diff(mnav_ctx* ctx, uint32_t layer, double radius, double threshold);
+int mnav_layer_roughness(mnav_ctx* ctx, uint32_t layer, double radius, double threshold);
+int mnav_layer_ridge(mnav_ctx* ctx, uint32_t layer, double radius, double threshold);
+/* last call: centres, sum of |N(v)|, largest |N(v)|, centres that left the LDS path, device ms; NULL to skip */
+int mnav_neighbourhood_stats(const mnav_ctx* ctx, uint32_t* centres, uint64_t* visits, uint32_t* max_size,
+                             uint32_t* spilled, float* ms);
 
 /* -- one plan over several GPUs (BASELINE config 4) ---------------------------------------------
  * The reference's loop (dijkstra_mesh_planner.cpp:287-348) on a mesh that is range-partitioned over `world`

@@ -28,6 +28,7 @@ SYMBOLS = [
     "mnav_vector_at", "mnav_backtrack_cvp", "mnav_backtrack_cvp_batch", "mnav_layer_upload", "mnav_layer_steepness", "mnav_layer_inflation", "mnav_layer_download",
     "mnav_combine_layers", "mnav_layer_stats", "mnav_layer_download_vectors", "mnav_combine_layers_update",
     "mnav_layer_obstacle", "mnav_obstacle_stats",
+    "mnav_layer_height_diff", "mnav_layer_roughness", "mnav_layer_ridge", "mnav_neighbourhood_stats",
     "mnav_set_option", "mnav_get_option", "mnav_shard_set_goal_tie", "mnav_last_engine",
 ]
 
@@ -154,6 +155,11 @@ def load(path: str | None = None):
     L.mnav_layer_obstacle.argtypes = [vp, u32, u32, vp, u32, vp, vp, f64, f64, vp, C.POINTER(u32), C.POINTER(u32)]
     L.mnav_obstacle_stats.restype = C.c_int
     L.mnav_obstacle_stats.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    for name in ("mnav_layer_height_diff", "mnav_layer_roughness", "mnav_layer_ridge"):
+        getattr(L, name).restype = C.c_int
+        getattr(L, name).argtypes = [vp, u32, f64, f64]
+    L.mnav_neighbourhood_stats.restype = C.c_int
+    L.mnav_neighbourhood_stats.argtypes = [vp, C.POINTER(u32), C.POINTER(C.c_uint64), C.POINTER(u32), C.POINTER(u32), C.POINTER(C.c_float)]
     L.mnav_shard_setup.restype = C.c_int
     L.mnav_shard_setup.argtypes = [vp, u32, u32]
     L.mnav_shard_setup_partition.restype = C.c_int
@@ -455,6 +461,28 @@ class MnavContext:
         k, h, lr, mb, mc, mt = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_float(), C.c_float(), C.c_float()
         self._L.mnav_obstacle_stats(self._h, C.byref(k), C.byref(h), C.byref(lr), C.byref(mb), C.byref(mc), C.byref(mt))
         return dict(rays_kept=k.value, hits=h.value, lethal_rays=lr.value, ms_bvh_build=mb.value, ms_cast=mc.value, ms_total=mt.value)
+
+    # local-neighbourhood layers (mnav_layer_height_diff / _roughness / _ridge, include/mnav.h); defaults: the reference's
+    # height_diff_layer.h:132-133, roughness_layer.h:133-134, ridge_layer.h:135-136.  Each returns neighbourhood_stats().
+    def layer_height_diff(self, layer: int, radius: float = 0.3, threshold: float = 0.185) -> dict:
+        return self._nbhd("mnav_layer_height_diff", layer, radius, threshold)
+
+    def layer_roughness(self, layer: int, radius: float = 0.3, threshold: float = 0.3) -> dict:
+        return self._nbhd("mnav_layer_roughness", layer, radius, threshold)
+
+    def layer_ridge(self, layer: int, radius: float = 0.3, threshold: float = 0.3) -> dict:
+        return self._nbhd("mnav_layer_ridge", layer, radius, threshold)
+
+    def _nbhd(self, name: str, layer: int, radius: float, threshold: float) -> dict:
+        if getattr(self._L, name)(self._h, int(layer), float(radius), float(threshold)) != 0:
+            raise RuntimeError(f"{name} failed: {self._err()}")
+        return self.neighbourhood_stats()
+
+    def neighbourhood_stats(self) -> dict:
+        """The last neighbourhood layer call: centres, sum and maximum of |N(v)|, centres that left the LDS path, device ms."""
+        c, v, m, s, ms = C.c_uint32(), C.c_uint64(), C.c_uint32(), C.c_uint32(), C.c_float()
+        self._L.mnav_neighbourhood_stats(self._h, C.byref(c), C.byref(v), C.byref(m), C.byref(s), C.byref(ms))
+        return dict(centres=c.value, visits=v.value, max_size=m.value, spilled=s.value, ms=ms.value)
 
     def layer_download(self, layer: int, distances: bool = False):
         c = np.empty(self.V, np.float32)

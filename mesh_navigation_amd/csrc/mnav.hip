@@ -77,6 +77,7 @@ constexpr int kChunk = 96;  // step launches per graph replay; multiple of 6 (sl
 #include "mnav_tbv.h"
 #include "mnav_walk.h"
 #include "mnav_obstacle.h"   // obstacle layer: LBVH build, ray cast, change list (mnav_obs::)
+#include "mnav_nbhd.h"       // height-difference / roughness / ridge layers: neighbourhood visits (mnav_nb::)
 
 // One back-tracking job: the plan's resident vector map and the two ends of the walk.
 struct WalkJob { const float* vecmap; float seed[3]; uint32_t seed_face; float target[3]; uint32_t target_face; };
@@ -209,6 +210,7 @@ struct mnav_ctx {
   uint8_t *d_infl_mask = nullptr, *d_zero_u8 = nullptr;
   float* d_infl_keyd = nullptr;
   mnav_obs::Bvh obs;                                               // obstacle layer: BVH built by the first mnav_layer_obstacle after an upload
+  mnav_nb::State nbhd;                                             // neighbourhood layers: counters, spill lists and scratch of the last call
   uint32_t infl_steps = 0, infl_bands = 0; uint64_t infl_evals = 0; float infl_ms = 0.f, infl_ms_wave = 0.f;   // last inflation wave
   TilePlan* d_tplans = nullptr; uint32_t tplans_cap = 0;
   TCtl* h_tctl = nullptr;
@@ -629,6 +631,7 @@ void mnav_destroy(mnav_ctx* ctx)
   for (auto& s : ctx->slots) free_slot(s);
   drop_layers(ctx);
   mnav_obs::bvh_free(ctx->obs);
+  mnav_nb::nb_free(ctx->nbhd);
   (void)hipFree(ctx->d_row_ptr); (void)hipFree(ctx->d_nbr_u); (void)hipFree(ctx->d_nbr_e); (void)hipFree(ctx->d_crn_ptr);
   (void)hipFree(ctx->d_edge_vtx); (void)hipFree(ctx->d_crn_idx); (void)hipFree(ctx->d_crn_walk); (void)hipFree(ctx->d_xyz); (void)hipFree(ctx->d_nrm);
   (void)hipFree(ctx->d_cost); (void)hipFree(ctx->d_w); (void)hipFree(ctx->d_edge_dist); (void)hipFree(ctx->d_invalid);
@@ -698,6 +701,7 @@ int mnav_upload_mesh(mnav_ctx* ctx, uint32_t V, uint32_t F, uint32_t E, const fl
   ctx->slots.clear();
   drop_layers(ctx);
   mnav_obs::bvh_free(ctx->obs);                                      // belongs to the old mesh; rebuilt lazily
+  mnav_nb::nb_free(ctx->nbhd);                                       // V-sized spill lists
   if (ctx->d_edge_dist) { ctx->alloc_bytes.erase((void*)ctx->d_edge_dist); (void)hipFree(ctx->d_edge_dist); ctx->d_edge_dist = nullptr; }   // belongs to the old mesh
   drop_graphs(ctx);
   (void)hipFree(ctx->d_paths); ctx->d_paths = nullptr; ctx->paths_words = 0;
@@ -1661,6 +1665,7 @@ uint32_t mnav_plan_cvp_batch(mnav_ctx* ctx, uint32_t n, const float* seed_pos, c
 
 #include "mnav_shard_capi.h"   // mnav_shard_* (one plan over several GPUs)
 #include "mnav_obstacle_capi.h"   // mnav_layer_obstacle, mnav_obstacle_stats
+#include "mnav_nbhd_capi.h"       // mnav_layer_height_diff / _roughness / _ridge, mnav_neighbourhood_stats
 
 void mnav_cancel(mnav_ctx* ctx)
 {

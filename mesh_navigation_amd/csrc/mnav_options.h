@@ -27,7 +27,8 @@
   X(async_wg_per_cu) X(async_wg_per_plan) X(async_max_s)                                                                                 \
   X(async_band_mult)     /* band of the asynchronous engine in tile widths of potential (default 4; <= 0: no bands) */                         \
   X(async_max_batch)     /* auto: batches of up to this many plans take the asynchronous engine */                                      \
-  X(async_ring_cap)      /* ticket slots of the asynchronous engine (default 16 per tile and plan; tests force the overflow path) */
+  X(async_ring_cap)      /* ticket slots of the asynchronous engine (default 16 per tile and plan; tests force the overflow path) */       \
+  X(nbhd_lds_cap)        /* neighbourhood layers: members per centre in LDS (default 128, 32..512; tests force the spill path) */
 
 struct Options {
 #define X(name) double name = NAN;
