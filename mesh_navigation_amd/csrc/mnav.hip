@@ -34,6 +34,7 @@
 #include <unistd.h>
 
 #include "../../include/mnav.h"
+#include "mnav_buf.h"
 #include "mnav_build.h"
 #include "mnav_eval.h"
 #include "mnav_options.h"
@@ -104,18 +105,18 @@ __global__ __launch_bounds__(64) void k_backtrack(WalkMesh M, WalkInflation L, c
 namespace {
 
 struct Slot {
-  float *dist = nullptr, *dirn = nullptr, *vecmap = nullptr;
-  PopKey* tkey = nullptr;
-  uint32_t *pred = nullptr, *cutf = nullptr, *stamp = nullptr, *dirty = nullptr, *list0 = nullptr, *list1 = nullptr;
-  uint32_t *wlist0 = nullptr, *wlist1 = nullptr, *wstamp = nullptr;
-  Ctl* ctl = nullptr;
-  Cnt* cnt = nullptr;
+  DevBuf<float> dist, dirn, vecmap;
+  DevBuf<PopKey> tkey;
+  DevBuf<uint32_t> pred, cutf, stamp, dirty, list0, list1;
+  DevBuf<uint32_t> wlist0, wlist1, wstamp;
+  Ctl* ctl = nullptr;                  // (into d_ctl_pool)
+  DevBuf<Cnt> cnt;
   bool cvp_ready = false, band_ready = false;
   // tiled engine
-  uint32_t *tpend0 = nullptr, *tpend1 = nullptr;
-  float* tlast = nullptr;
-  TCtl* tctl = nullptr;
-  TCnt* tcnt = nullptr;
+  DevBuf<uint32_t> tpend0, tpend1;
+  DevBuf<float> tlast;
+  TCtl* tctl = nullptr;                // (into d_tctl_pool)
+  DevBuf<TCnt> tcnt;
   bool tile_ready = false;
 };
 
@@ -123,12 +124,12 @@ struct Slot {
 
 struct mnav_ctx {
   int device = 0;
-  hipStream_t stream = nullptr;
+  Stream stream;
   std::string err;
   std::atomic<int> cancel{ 0 };
-  uint32_t* d_cancel = nullptr;            // the same flag in device memory: long-running kernels poll it (agent-scope load)
-  uint32_t* h_one = nullptr;               // pinned source word (1) for the copy mnav_cancel issues on its own stream
-  hipStream_t cancel_stream = nullptr;
+  DevBuf<uint32_t> d_cancel;               // the same flag in device memory: long-running kernels poll it (agent-scope load)
+  PinnedBuf<uint32_t> h_one;               // pinned source word (1) for the copy mnav_cancel issues on its own stream
+  Stream cancel_stream;
   // host copies needed for seeding
   uint32_t V = 0, F = 0, E = 0;
   std::vector<float> h_xyz, h_cost;
@@ -140,38 +141,37 @@ struct mnav_ctx {
   std::vector<uint32_t> caller_slot;   // plan index of the caller's batch -> device slot of the last call (kNone: never ran)
   std::vector<uint32_t> h_faces;
   std::vector<uint32_t> h_vf_ptr, h_vf;    // getFacesOfVertex rows (host copy; uploaded on the first device back-tracking call)
-  uint32_t *d_faces = nullptr, *d_vf_ptr = nullptr, *d_vf = nullptr; bool walk_mesh_valid = false;
-  float* d_walk_pos = nullptr; uint32_t* d_walk_face = nullptr; size_t walk_cap = 0;   // k_backtrack outputs: rows of `cap` entries
-  hipEvent_t ev_link[2]{};                 // stream links of the asynchronous shard calls (caller's stream <-> ours)
-  struct WalkJob* d_walk_jobs = nullptr; int32_t* d_walk_ctl = nullptr; uint32_t walk_jobs_cap = 0;
+  DevBuf<uint32_t> d_faces, d_vf_ptr, d_vf; bool walk_mesh_valid = false;
+  DevBuf<float> d_walk_pos; DevBuf<uint32_t> d_walk_face; size_t walk_cap = 0;   // k_backtrack outputs: rows of `cap` entries
+  Event ev_link[2];                        // stream links of the asynchronous shard calls (caller's stream <-> ours)
+  DevBuf<WalkJob> d_walk_jobs; DevBuf<int32_t> d_walk_ctl; uint32_t walk_jobs_cap = 0;
   std::vector<uint8_t> h_invalid;
   bool have_mesh = false, have_costs = false, have_normals = false;
   // device mesh
-  uint32_t *d_row_ptr = nullptr, *d_nbr_u = nullptr, *d_nbr_e = nullptr, *d_crn_ptr = nullptr, *d_edge_vtx = nullptr;
-  CornerIdx* d_crn_idx = nullptr;
-  uint32_t* d_crn_walk = nullptr;                                   // HostTopology::crn_walk (inflation vector field)
-  float *d_xyz = nullptr, *d_nrm = nullptr, *d_cost = nullptr, *d_w = nullptr, *d_edge_dist = nullptr;
-  uint8_t* d_invalid = nullptr;
+  DevBuf<uint32_t> d_row_ptr, d_nbr_u, d_nbr_e, d_crn_ptr, d_edge_vtx;
+  DevBuf<CornerIdx> d_crn_idx;
+  DevBuf<uint32_t> d_crn_walk;                                      // HostTopology::crn_walk (inflation vector field)
+  DevBuf<float> d_xyz, d_nrm, d_cost, d_w, d_edge_dist;
+  DevBuf<uint8_t> d_invalid;
   // materialised per cost_limit
-  Nbr* d_nbr = nullptr; double nbr_limit = NAN; bool nbr_valid = false;
-  Corner* d_crn = nullptr; uint8_t* d_blocked = nullptr; double crn_limit = NAN; bool crn_valid = false;
+  DevBuf<Nbr> d_nbr; double nbr_limit = NAN; bool nbr_valid = false;
+  DevBuf<Corner> d_crn; DevBuf<uint8_t> d_blocked; double crn_limit = NAN; bool crn_valid = false;
   FaceCirculation circ;                                            // caller-supplied getFacesOfVertex rows (optional)
-  uint32_t* d_verify_any = nullptr; uint32_t verify_sweeps_used = 0;
+  DevBuf<uint32_t> d_verify_any; uint32_t verify_sweeps_used = 0;
   bool cvp_verify = true;                                          // k_cvp_verify after every CVP plan (MNAV_CVP_VERIFY=0 to skip)
   int walk_max = kKeyWalkMax, descend_max = kDescendWalkMax;       // cascade-tree walk bounds (MNAV_KEY_WALK_MAX / MNAV_DESCEND_WALK_MAX: tests)
   // plans
   std::vector<Slot> slots;
-  Plan* d_plans = nullptr; uint32_t plans_cap = 0;
-  PlanResult* d_res = nullptr; PlanResult* h_res = nullptr;
-  float** d_vecptrs = nullptr;
-  uint32_t* d_paths = nullptr; size_t paths_words = 0; uint32_t path_stride = 0;   // n plans x path_stride vertex ids
-  uint32_t* d_over = nullptr; unsigned long long* d_over_off = nullptr; uint32_t* d_over_cap = nullptr;   // exact rows of the paths that did not fit
-  uint32_t *d_pack = nullptr, *h_pack = nullptr, *d_pack_meta = nullptr; size_t pack_words = 0, pack_meta_n = 0;   // packed paths (device, pinned host), offsets + lengths
-  std::unordered_map<void*, size_t> alloc_bytes;                   // sizes of the dev_upload buffers (re-used when unchanged)
-  Ctl* h_ctl = nullptr;       // pinned, 2 per plan
+  DevBuf<Plan> d_plans; uint32_t plans_cap = 0;
+  DevBuf<PlanResult> d_res; PinnedBuf<PlanResult> h_res;
+  DevBuf<float*> d_vecptrs;
+  DevBuf<uint32_t> d_paths; size_t paths_words = 0; uint32_t path_stride = 0;   // n plans x path_stride vertex ids
+  DevBuf<uint32_t> d_over; DevBuf<unsigned long long> d_over_off; DevBuf<uint32_t> d_over_cap;   // exact rows of the paths that did not fit
+  DevBuf<uint32_t> d_pack; PinnedBuf<uint32_t> h_pack; DevBuf<uint32_t> d_pack_meta; size_t pack_words = 0, pack_meta_n = 0;   // packed paths (device, pinned host), offsets + lengths
+  PinnedBuf<Ctl> h_ctl;       // 2 per plan
   uint32_t infl_exact_bands = 0;   // bands of the last inflation wave that went through the exact band routine (k_exact_band)
-  float* d_seed_pos = nullptr; uint32_t seed_pos_cap = 1;
-  std::map<uint64_t, hipGraphExec_t> graphs;
+  DevBuf<float> d_seed_pos; uint32_t seed_pos_cap = 1;
+  std::map<uint64_t, GraphExec> graphs;
   // tiled SSSP engine
   int dij_engine = 3;          // 0 tiled rounds, 1 band steps, 3 auto, 5 tile-batch, 6 asynchronous tiles (2: the per-plan persistent kernel, retired round 5)
   int last_engine = 0;
@@ -182,57 +182,56 @@ struct mnav_ctx {
   uint32_t tile_size = 512;    // 4 workgroups of the tile kernels per CU (36 KB LDS each)
   float rounds_band_mult = 4.0f;   // the round engine (latency) prefers wide bands
   float tile_band_user = 0.f, tile_band_auto = 1.f;
-  uint32_t* d_t_rptr = nullptr;
+  DevBuf<uint32_t> d_t_rptr;
   HostTiles tiles_meta;        // only the small per-tile vectors are kept (vert_tile, sizes)
-  uint32_t *d_t_vptr = nullptr, *d_t_verts = nullptr, *d_t_hptr = nullptr, *d_t_halo_verts = nullptr, *d_t_halo_tile = nullptr,
-           *d_t_eptr = nullptr, *d_t_src = nullptr, *d_vert_tile = nullptr, *d_mismatch = nullptr;
-  uint16_t *d_t_rowptr = nullptr, *d_t_col = nullptr;
-  float* d_t_tw = nullptr; bool tw_valid = false; uint32_t t_nnz = 0;
+  DevBuf<uint32_t> d_t_vptr, d_t_verts, d_t_hptr, d_t_halo_verts, d_t_halo_tile, d_t_eptr, d_t_src, d_vert_tile, d_mismatch;
+  DevBuf<uint16_t> d_t_rowptr, d_t_col;
+  DevBuf<float> d_t_tw; bool tw_valid = false; uint32_t t_nnz = 0;
   // sharded single plan (mnav_shard_*)
   struct Shard {
     bool ready = false, active = false, finalized = false;   // finalized: slot 0 holds the predecessors of the last sharded plan (mnav_shard_walk)
     uint32_t rank = 0, world = 1, t_lo = 0, t_hi = 0, n_iface = 0, rounds_per_exchange = 8, j = 0;
     uint32_t seed = 0, target = 0; double offset = 0.3; uint32_t goal_tie1 = 0;
-    uint32_t *d_iface_vert = nullptr, *d_wake_ptr = nullptr, *d_wake_tile = nullptr, *d_changed = nullptr, *d_minpend = nullptr;
-    uint8_t* d_iface_owner = nullptr;
+    DevBuf<uint32_t> d_iface_vert, d_wake_ptr, d_wake_tile, d_changed, d_minpend;
+    DevBuf<uint8_t> d_iface_owner;
     std::vector<uint32_t> iface_vert;
-    bool partition = false; uint8_t* d_owned = nullptr;              // mnav_shard_setup_partition
-    uint32_t* d_walk = nullptr; uint32_t walk_cap = 0;               // mnav_shard_walk
-    std::map<std::array<uint64_t, 3>, hipGraphExec_t> graphs;        // captured exchange sequences (shard_replay)
+    bool partition = false; DevBuf<uint8_t> d_owned;                 // mnav_shard_setup_partition
+    DevBuf<uint32_t> d_walk; uint32_t walk_cap = 0;                  // mnav_shard_walk
+    std::map<std::array<uint64_t, 3>, GraphExec> graphs;             // captured exchange sequences (shard_replay)
   } shard;
   double edge_cost_factor = 0.0;                                   // factor of the resident edge weights (mnav_update_costs)
   // layers computed / kept on the device (mnav_layer_*)
-  struct Layer { float* cost = nullptr; uint8_t* lethal = nullptr; float* dist = nullptr; float* vec = nullptr; uint8_t* vstate = nullptr;   // vstate: 3 x V (two state arrays + the accumulate flags)
+  struct Layer { DevBuf<float> cost; DevBuf<uint8_t> lethal; DevBuf<float> dist, vec; DevBuf<uint8_t> vstate;   // vstate: 3 x V (two state arrays + the accumulate flags)
                  bool ready = false, have_vec = false;
                  double inflation_radius = 0, inscribed_radius = 0, inscribed_value = 0, lethal_value = 0; };   // InflationLayer config (vectorAt reads it)
   std::vector<Layer> layers;
-  Corner* d_crn_infl = nullptr; bool crn_infl_valid = false;       // corners over the edge distances (inflation wave)
-  uint8_t *d_infl_mask = nullptr, *d_zero_u8 = nullptr;
-  float* d_infl_keyd = nullptr;
+  DevBuf<Corner> d_crn_infl; bool crn_infl_valid = false;          // corners over the edge distances (inflation wave)
+  DevBuf<uint8_t> d_infl_mask, d_zero_u8;
+  DevBuf<float> d_infl_keyd;
   mnav_obs::Bvh obs;                                               // obstacle layer: BVH built by the first mnav_layer_obstacle after an upload
   mnav_nb::State nbhd;                                             // neighbourhood layers: counters, spill lists and scratch of the last call
   uint32_t infl_steps = 0, infl_bands = 0; uint64_t infl_evals = 0; float infl_ms = 0.f, infl_ms_wave = 0.f;   // last inflation wave
-  TilePlan* d_tplans = nullptr; uint32_t tplans_cap = 0;
-  TCtl* h_tctl = nullptr;
+  DevBuf<TilePlan> d_tplans; uint32_t tplans_cap = 0;
+  PinnedBuf<TCtl> h_tctl;
   size_t tile_lds = 0, fin_lds = 0;
   bool use_graph = true;
-  uint32_t* d_wide_prefix = nullptr; WideSched* d_wide_sched = nullptr; uint32_t wide_cap = 0;   // k_cvp_ctl -> k_step_wide
-  float* d_vec3 = nullptr;                                           // mnav_vector_at after a paths-only batch
-  uint32_t wide_groups = 1; hipStream_t stream_g[kWideGroupsMax] = {}; hipEvent_t ev_fork[kWideGroupsMax] = {};   // CVP batches in groups on their own streams ([0] unused / fork event)
+  DevBuf<uint32_t> d_wide_prefix; DevBuf<WideSched> d_wide_sched; uint32_t wide_cap = 0;   // k_cvp_ctl -> k_step_wide
+  DevBuf<float> d_vec3;                                              // mnav_vector_at after a paths-only batch
+  uint32_t wide_groups = 1; Stream stream_g[kWideGroupsMax]; Event ev_fork[kWideGroupsMax];   // CVP batches in groups on their own streams ([0] unused / fork event)
   uint32_t cvp_wide_min_batch = 32;                                  // CVP batches of at least this many plans run k_step_wide
   float delta_user = 0.f, delta_auto = 0.f;
   Options opt;                                                       // mnav_options.h: read from the environment once, by mnav_create
   uint32_t max_steps_auto = 1u << 20;
-  uint32_t* d_ring = nullptr; uint32_t ring_cap = 0; size_t ring_words = 0; struct AsyncCtl* h_actl = nullptr; uint32_t* d_parked = nullptr; size_t parked_words = 0;   // asynchronous tile engine: ticket ring, pinned copy of its control words
+  DevBuf<uint32_t> d_ring; uint32_t ring_cap = 0; size_t ring_words = 0; PinnedBuf<AsyncCtl> h_actl; DevBuf<uint32_t> d_parked; size_t parked_words = 0;   // asynchronous tile engine: ticket ring, pinned copy of its control words
   uint32_t last_planner = 0, last_n = 0;
   std::vector<uint32_t> last_target; double last_offset = 0.0;   // Dijkstra: robot vertex per device slot, goal_dist_offset of the last call
   mnav_stats stats{};
   uint64_t algo_bytes = 0;
-  hipEvent_t ev[8]{};
-  hipEvent_t evc[2]{};         // bracket one graph replay (chunk of step/round launches)
+  Event ev[8];
+  Event evc[2];                // bracket one graph replay (chunk of step/round launches)
   double ms_chunks = 0.0;      // sum of the bracketed chunk durations of the last call
-  Ctl* d_ctl_pool = nullptr; uint32_t ctl_pool_cap = 0;      // contiguous control blocks: one D2H copy per chunk
-  TCtl* d_tctl_pool = nullptr; uint32_t tctl_pool_cap = 0;
+  DevBuf<Ctl> d_ctl_pool; uint32_t ctl_pool_cap = 0;         // contiguous control blocks: one D2H copy per chunk
+  DevBuf<TCtl> d_tctl_pool; uint32_t tctl_pool_cap = 0;
 };
 
 namespace {
@@ -247,57 +246,11 @@ namespace {
     }                                                                                              \
   } while (0)
 
-// temporary device buffer of one call: freed on every way out (the HIPCHK early returns included)
-template <class T>
-struct DevTmp {
-  T* p = nullptr;
-  DevTmp() = default;
-  DevTmp(const DevTmp&) = delete;
-  DevTmp& operator=(const DevTmp&) = delete;
-  ~DevTmp() { if (p) (void)hipFree(p); }
-  operator T*() const { return p; }
-  void** out() { return (void**)&p; }
-};
-
-template <class T>
-int dev_upload(mnav_ctx* ctx, T** dptr, const T* host, size_t n)
-{
-  const size_t bytes = sizeof(T) * (n ? n : 1) + 64;               // tail slack: clamped vector loads may touch element 0 of an empty tile
-  auto it = *dptr ? ctx->alloc_bytes.find((void*)*dptr) : ctx->alloc_bytes.end();
-  if (!*dptr || it == ctx->alloc_bytes.end() || it->second != bytes) {   // same size as last time (cost re-uploads): keep the buffer
-    if (*dptr) { ctx->alloc_bytes.erase((void*)*dptr); (void)hipFree(*dptr); *dptr = nullptr; }
-    HIPCHK(hipMalloc((void**)dptr, bytes));
-    ctx->alloc_bytes[(void*)*dptr] = bytes;
-  }
-  if (n && host) HIPCHK(hipMemcpyAsync(*dptr, host, sizeof(T) * n, hipMemcpyHostToDevice, ctx->stream));
-  return 0;
-}
-
 float ev_ms(hipEvent_t a, hipEvent_t b);
-
-void drop_layers(mnav_ctx* ctx)
-{
-  for (auto& L : ctx->layers) { (void)hipFree(L.cost); (void)hipFree(L.lethal); (void)hipFree(L.dist); (void)hipFree(L.vec); (void)hipFree(L.vstate); }
-  ctx->layers.clear();
-  (void)hipFree(ctx->d_crn_infl); (void)hipFree(ctx->d_infl_mask); (void)hipFree(ctx->d_zero_u8); (void)hipFree(ctx->d_infl_keyd);
-  ctx->d_crn_infl = nullptr; ctx->d_infl_mask = nullptr; ctx->d_zero_u8 = nullptr; ctx->d_infl_keyd = nullptr; ctx->crn_infl_valid = false;
-}
-
-void free_slot(Slot& s)
-{
-  (void)hipFree(s.dist); (void)hipFree(s.tkey); (void)hipFree(s.dirn); (void)hipFree(s.vecmap);
-  (void)hipFree(s.pred); (void)hipFree(s.cutf); (void)hipFree(s.stamp); (void)hipFree(s.dirty); (void)hipFree(s.list0); (void)hipFree(s.list1);
-  (void)hipFree(s.wlist0); (void)hipFree(s.wlist1); (void)hipFree(s.wstamp);
-  (void)hipFree(s.cnt);
-  (void)hipFree(s.tpend0); (void)hipFree(s.tpend1); (void)hipFree(s.tlast); (void)hipFree(s.tcnt);
-  s = Slot{};
-}
 
 void drop_graphs(mnav_ctx* ctx)
 {
-  for (auto& kv : ctx->graphs) (void)hipGraphExecDestroy(kv.second);
   ctx->graphs.clear();
-  for (auto& kv : ctx->shard.graphs) (void)hipGraphExecDestroy(kv.second);
   ctx->shard.graphs.clear();
 }
 
@@ -325,33 +278,28 @@ int ensure_slots(mnav_ctx* ctx, uint32_t n, bool cvp, bool band, bool vec)
   const size_t V = ctx->V ? ctx->V : 1;
   while (ctx->slots.size() < n) {
     Slot s;
-    HIPCHK(hipMalloc((void**)&s.dist, 4 * V)); HIPCHK(hipMalloc((void**)&s.pred, 4 * V));   // 8 B per vertex and plan ...
-    HIPCHK(hipMalloc((void**)&s.cnt, 4 * sizeof(Cnt)));                                       // 3 rotating + sticky flags
-    ctx->slots.push_back(s);
+    HIPCHK(s.dist.alloc(4 * V)); HIPCHK(s.pred.alloc(4 * V));          // 8 B per vertex and plan ...
+    HIPCHK(s.cnt.alloc(4 * sizeof(Cnt)));                              // 3 rotating + sticky flags
+    ctx->slots.push_back(std::move(s));
   }
   for (uint32_t i = 0; i < n; ++i) {                                   // ... the rest only for the paths that use it
     Slot& s = ctx->slots[i];
     if (band && !s.band_ready) {                                       // work lists of the band/gather steps
-      HIPCHK(hipMalloc((void**)&s.stamp, 4 * V)); HIPCHK(hipMalloc((void**)&s.dirty, 4 * V));
-      HIPCHK(hipMalloc((void**)&s.list0, 4 * V)); HIPCHK(hipMalloc((void**)&s.list1, 4 * V));
-      HIPCHK(hipMalloc((void**)&s.wlist0, 4 * V)); HIPCHK(hipMalloc((void**)&s.wlist1, 4 * V)); HIPCHK(hipMalloc((void**)&s.wstamp, 4 * V));
+      HIPCHK(alloc_group(s.stamp, 4 * V, s.dirty, 4 * V, s.list0, 4 * V, s.list1, 4 * V, s.wlist0, 4 * V, s.wlist1, 4 * V, s.wstamp, 4 * V));
       s.band_ready = true;
     }
-    if (vec && !s.vecmap) HIPCHK(hipMalloc((void**)&s.vecmap, 12 * V));
+    if (vec && !s.vecmap) HIPCHK(s.vecmap.alloc(12 * V));
   }
   if (cvp)
     for (uint32_t i = 0; i < n; ++i) {
       Slot& s = ctx->slots[i];
       if (!s.cvp_ready) {
-        HIPCHK(hipMalloc((void**)&s.tkey, sizeof(PopKey) * V)); HIPCHK(hipMalloc((void**)&s.dirn, 4 * V));
-        HIPCHK(hipMalloc((void**)&s.cutf, 4 * V));
+        HIPCHK(alloc_group(s.tkey, sizeof(PopKey) * V, s.dirn, 4 * V, s.cutf, 4 * V));
         s.cvp_ready = true;
       }
     }
   if (ctx->ctl_pool_cap < n) {
-    if (ctx->d_ctl_pool) (void)hipFree(ctx->d_ctl_pool);
-    ctx->d_ctl_pool = nullptr;
-    HIPCHK(hipMalloc((void**)&ctx->d_ctl_pool, 2 * sizeof(Ctl) * n));
+    HIPCHK(ctx->d_ctl_pool.alloc(2 * sizeof(Ctl) * n));
     ctx->ctl_pool_cap = n;
   }
   for (uint32_t i = 0; i < n; ++i) ctx->slots[i].ctl = ctx->d_ctl_pool + 2 * i;
@@ -362,18 +310,13 @@ int ensure_slots(mnav_ctx* ctx, uint32_t n, bool cvp, bool band, bool vec)
 int ensure_plan_tables(mnav_ctx* ctx, uint32_t n)
 {
   if (ctx->plans_cap < n) {
-    if (ctx->d_plans) (void)hipFree(ctx->d_plans);
-    if (ctx->d_res) (void)hipFree(ctx->d_res);
-    if (ctx->h_res) (void)hipHostFree(ctx->h_res);
-    if (ctx->h_ctl) (void)hipHostFree(ctx->h_ctl);
-    if (ctx->d_vecptrs) (void)hipFree(ctx->d_vecptrs);
-    ctx->d_plans = nullptr; ctx->d_res = nullptr; ctx->h_res = nullptr; ctx->h_ctl = nullptr; ctx->d_vecptrs = nullptr;
+    ctx->d_plans.reset(); ctx->d_res.reset(); ctx->h_res.reset(); ctx->h_ctl.reset(); ctx->d_vecptrs.reset();
     drop_graphs(ctx);   // graphs captured the old d_plans pointer
-    HIPCHK(hipMalloc((void**)&ctx->d_plans, sizeof(Plan) * n));
-    HIPCHK(hipMalloc((void**)&ctx->d_res, sizeof(PlanResult) * n));
-    HIPCHK(hipHostMalloc((void**)&ctx->h_res, sizeof(PlanResult) * n, hipHostMallocDefault));
-    HIPCHK(hipHostMalloc((void**)&ctx->h_ctl, sizeof(Ctl) * 2 * n, hipHostMallocDefault));
-    HIPCHK(hipMalloc((void**)&ctx->d_vecptrs, sizeof(float*) * n));
+    HIPCHK(ctx->d_plans.alloc(sizeof(Plan) * n));
+    HIPCHK(ctx->d_res.alloc(sizeof(PlanResult) * n));
+    HIPCHK(ctx->h_res.alloc(sizeof(PlanResult) * n));
+    HIPCHK(ctx->h_ctl.alloc(sizeof(Ctl) * 2 * n));
+    HIPCHK(ctx->d_vecptrs.alloc(sizeof(float*) * n));
     ctx->plans_cap = n;
   }
   return 0;
@@ -392,9 +335,8 @@ int ensure_paths(mnav_ctx* ctx, uint32_t n, uint32_t stride)
 {
   const size_t words = (size_t)n * (stride ? stride : 1);
   if (ctx->paths_words < words) {
-    if (ctx->d_paths) (void)hipFree(ctx->d_paths);
-    ctx->d_paths = nullptr; ctx->paths_words = 0;
-    HIPCHK(hipMalloc((void**)&ctx->d_paths, sizeof(uint32_t) * words));
+    ctx->paths_words = 0;
+    HIPCHK(ctx->d_paths.alloc(sizeof(uint32_t) * words));
     ctx->paths_words = words;
   }
   ctx->path_stride = stride;
@@ -467,10 +409,10 @@ int run_chunk(mnav_ctx* ctx, uint32_t n, uint32_t G, bool wide)
     const int rc = launch_steps<PLANNER>(ctx, n, G, kChunk, wide);
     hipError_t e = hipStreamEndCapture(ctx->stream, &g);
     if (rc != 0 || e != hipSuccess) { ctx->err = "graph capture failed"; return -1; }
-    hipGraphExec_t ge = nullptr;
-    HIPCHK(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
+    GraphExec ge;
+    HIPCHK(hipGraphInstantiate(ge.out(), g, nullptr, nullptr, 0));
     (void)hipGraphDestroy(g);
-    it = ctx->graphs.emplace(key, ge).first;
+    it = ctx->graphs.emplace(key, std::move(ge)).first;
   }
   HIPCHK(hipGraphLaunch(it->second, ctx->stream));
   return 0;
@@ -482,15 +424,15 @@ int materialize(mnav_ctx* ctx, bool cvp, double cost_limit)
   const uint32_t gb = (V + kBlock - 1) / kBlock;
   if (!cvp) {
     if (ctx->nbr_valid && ctx->nbr_limit == cost_limit) return 0;
-    if (!ctx->d_nbr) HIPCHK(hipMalloc((void**)&ctx->d_nbr, sizeof(Nbr) * (size_t)(ctx->E ? 2 * (size_t)ctx->E : 1)));
+    if (!ctx->d_nbr) HIPCHK(ctx->d_nbr.alloc(sizeof(Nbr) * (size_t)(ctx->E ? 2 * (size_t)ctx->E : 1)));
     hipLaunchKernelGGL(k_build_nbr, dim3(gb ? gb : 1), dim3(kBlock), 0, ctx->stream, V, ctx->d_row_ptr, ctx->d_nbr_u,
                        ctx->d_nbr_e, ctx->d_w, ctx->d_cost, ctx->d_invalid, cost_limit, ctx->d_nbr);
     HIPCHK(hipGetLastError());
     ctx->nbr_limit = cost_limit; ctx->nbr_valid = true; ctx->tw_valid = false; ctx->tb.w_valid = false;
   } else {
     if (ctx->crn_valid && ctx->crn_limit == cost_limit) return 0;
-    if (!ctx->d_crn) HIPCHK(hipMalloc((void**)&ctx->d_crn, sizeof(Corner) * (size_t)(ctx->F ? 3 * (size_t)ctx->F : 1)));
-    if (!ctx->d_blocked) HIPCHK(hipMalloc((void**)&ctx->d_blocked, V ? V : 1));
+    if (!ctx->d_crn) HIPCHK(ctx->d_crn.alloc(sizeof(Corner) * (size_t)(ctx->F ? 3 * (size_t)ctx->F : 1)));
+    if (!ctx->d_blocked) HIPCHK(ctx->d_blocked.alloc(V ? V : 1));
     hipLaunchKernelGGL(k_build_crn, dim3(gb ? gb : 1), dim3(kBlock), 0, ctx->stream, V, ctx->d_crn_ptr, ctx->d_crn_idx,
                        ctx->d_w, ctx->d_cost, ctx->d_invalid, cost_limit, ctx->d_crn, ctx->d_blocked);
     HIPCHK(hipGetLastError());
@@ -503,7 +445,7 @@ int materialize(mnav_ctx* ctx, bool cvp, double cost_limit)
 // the re-evaluated state (verify_entry) and are followed by another one; the last allowed sweep only checks.
 int verify_sweeps(mnav_ctx* ctx, uint32_t n)
 {
-  if (!ctx->d_verify_any) HIPCHK(hipMalloc((void**)&ctx->d_verify_any, 4));
+  if (!ctx->d_verify_any) HIPCHK(ctx->d_verify_any.alloc(4));
   uint32_t gv = (ctx->V / kGroupsPerWave + 3) / 4;                  // ~4 vertices per 8-lane group
   if (gv < 1) gv = 1;
   if (gv > 8192) gv = 8192;
@@ -605,17 +547,16 @@ mnav_ctx* mnav_create(int device)
   if (hipSetDevice(device) != hipSuccess) return nullptr;
   mnav_ctx* ctx = new mnav_ctx();
   ctx->device = device;
-  if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) { delete ctx; return nullptr; }
+  if (hipStreamCreateWithFlags(ctx->stream.out(), hipStreamNonBlocking) != hipSuccess) { delete ctx; return nullptr; }
   for (auto& e : ctx->ev)
-    if (hipEventCreate(&e) != hipSuccess) { delete ctx; return nullptr; }
+    if (hipEventCreate(e.out()) != hipSuccess) { delete ctx; return nullptr; }
   for (auto& e : ctx->evc)
-    if (hipEventCreate(&e) != hipSuccess) { delete ctx; return nullptr; }
-  if (hipMalloc((void**)&ctx->d_seed_pos, 3 * sizeof(float)) != hipSuccess) { delete ctx; return nullptr; }
-  if (hipMalloc((void**)&ctx->d_cancel, 64) != hipSuccess || hipMemset(ctx->d_cancel, 0, 64) != hipSuccess ||
-      hipHostMalloc((void**)&ctx->h_one, 64, hipHostMallocDefault) != hipSuccess ||
-      hipStreamCreateWithFlags(&ctx->cancel_stream, hipStreamNonBlocking) != hipSuccess) { delete ctx; return nullptr; }
+    if (hipEventCreate(e.out()) != hipSuccess) { delete ctx; return nullptr; }
+  if (ctx->d_seed_pos.alloc(3 * sizeof(float)) != hipSuccess) { delete ctx; return nullptr; }
+  if (ctx->d_cancel.alloc(64) != hipSuccess || hipMemset(ctx->d_cancel, 0, 64) != hipSuccess || ctx->h_one.alloc(64) != hipSuccess ||
+      hipStreamCreateWithFlags(ctx->cancel_stream.out(), hipStreamNonBlocking) != hipSuccess) { delete ctx; return nullptr; }
   *ctx->h_one = 1u;
-  if (hipHostMalloc((void**)&ctx->h_actl, sizeof(AsyncCtl), hipHostMallocDefault) != hipSuccess) { delete ctx; return nullptr; }
+  if (ctx->h_actl.alloc(sizeof(AsyncCtl)) != hipSuccess) { delete ctx; return nullptr; }
   ctx->opt.from_environment();                                        // the ONLY look at the environment (mnav_options.h)
   apply_options(ctx);
   return ctx;
@@ -626,42 +567,10 @@ void mnav_destroy(mnav_ctx* ctx)
   if (!ctx) return;
   (void)hipSetDevice(ctx->device);
   (void)hipStreamSynchronize(ctx->stream);
-  drop_graphs(ctx);
-  tb_free(ctx);
-  for (auto& s : ctx->slots) free_slot(s);
-  drop_layers(ctx);
-  mnav_obs::bvh_free(ctx->obs);
-  mnav_nb::nb_free(ctx->nbhd);
-  (void)hipFree(ctx->d_row_ptr); (void)hipFree(ctx->d_nbr_u); (void)hipFree(ctx->d_nbr_e); (void)hipFree(ctx->d_crn_ptr);
-  (void)hipFree(ctx->d_edge_vtx); (void)hipFree(ctx->d_crn_idx); (void)hipFree(ctx->d_crn_walk); (void)hipFree(ctx->d_xyz); (void)hipFree(ctx->d_nrm);
-  (void)hipFree(ctx->d_cost); (void)hipFree(ctx->d_w); (void)hipFree(ctx->d_edge_dist); (void)hipFree(ctx->d_invalid);
-  (void)hipFree(ctx->d_nbr); (void)hipFree(ctx->d_crn); (void)hipFree(ctx->d_blocked); (void)hipFree(ctx->d_plans);
-  (void)hipFree(ctx->d_res); (void)hipFree(ctx->d_vecptrs); (void)hipFree(ctx->d_paths); (void)hipFree(ctx->d_seed_pos);
-  (void)hipFree(ctx->d_t_vptr); (void)hipFree(ctx->d_t_verts); (void)hipFree(ctx->d_t_hptr); (void)hipFree(ctx->d_t_halo_verts);
-  (void)hipFree(ctx->d_t_halo_tile); (void)hipFree(ctx->d_t_eptr); (void)hipFree(ctx->d_t_src); (void)hipFree(ctx->d_vert_tile);
-  (void)hipFree(ctx->d_t_rptr); (void)hipFree(ctx->d_mismatch); (void)hipFree(ctx->d_t_rowptr); (void)hipFree(ctx->d_t_col); (void)hipFree(ctx->d_t_tw);
-  (void)hipFree(ctx->d_tplans);
-  (void)hipFree(ctx->shard.d_iface_vert); (void)hipFree(ctx->shard.d_iface_owner); (void)hipFree(ctx->shard.d_wake_ptr); (void)hipFree(ctx->shard.d_wake_tile);
-  (void)hipFree(ctx->d_wide_prefix); (void)hipFree(ctx->d_wide_sched); (void)hipFree(ctx->d_vec3);
-  for (auto& st : ctx->stream_g) if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
-  for (auto& e : ctx->ev_fork) if (e) (void)hipEventDestroy(e);
-  (void)hipFree(ctx->shard.d_owned); (void)hipFree(ctx->shard.d_changed); (void)hipFree(ctx->shard.d_minpend); (void)hipFree(ctx->shard.d_walk);
-  if (ctx->cancel_stream) { (void)hipStreamSynchronize(ctx->cancel_stream); (void)hipStreamDestroy(ctx->cancel_stream); }
-  if (ctx->h_one) (void)hipHostFree(ctx->h_one);
-  (void)hipFree(ctx->d_cancel); (void)hipFree(ctx->d_verify_any); (void)hipFree(ctx->d_ring); (void)hipFree(ctx->d_parked); if (ctx->h_actl) (void)hipHostFree(ctx->h_actl);
-  (void)hipFree(ctx->d_over); (void)hipFree(ctx->d_over_off); (void)hipFree(ctx->d_over_cap);
-  (void)hipFree(ctx->d_pack); (void)hipFree(ctx->d_pack_meta); if (ctx->h_pack) (void)hipHostFree(ctx->h_pack);
-  if (ctx->h_tctl) (void)hipHostFree(ctx->h_tctl);
-  if (ctx->h_res) (void)hipHostFree(ctx->h_res);
-  if (ctx->h_ctl) (void)hipHostFree(ctx->h_ctl);
-  for (auto& e : ctx->ev) if (e) (void)hipEventDestroy(e);
-  for (auto& e : ctx->evc) if (e) (void)hipEventDestroy(e);
-  for (auto& e : ctx->ev_link) if (e) (void)hipEventDestroy(e);
-  (void)hipFree(ctx->d_ctl_pool); (void)hipFree(ctx->d_tctl_pool);
-  (void)hipFree(ctx->d_faces); (void)hipFree(ctx->d_vf_ptr); (void)hipFree(ctx->d_vf); (void)hipFree(ctx->d_walk_pos); (void)hipFree(ctx->d_walk_face);
-  (void)hipFree(ctx->d_walk_jobs); (void)hipFree(ctx->d_walk_ctl);
-  if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-  delete ctx;
+  if (ctx->cancel_stream) (void)hipStreamSynchronize(ctx->cancel_stream);
+  for (auto& st : ctx->stream_g) if (st) (void)hipStreamSynchronize(st);
+  if (ctx->tb.fill_stream) (void)hipStreamSynchronize(ctx->tb.fill_stream);
+  delete ctx;                                                         // the owners free the rest
 }
 
 const char* mnav_last_error(const mnav_ctx* ctx) { return ctx ? ctx->err.c_str() : "null context"; }
@@ -697,18 +606,17 @@ int mnav_upload_mesh(mnav_ctx* ctx, uint32_t V, uint32_t F, uint32_t E, const fl
   }
   catch (const std::exception& ex) { ctx->err = ex.what(); return -2; }
   (void)hipStreamSynchronize(ctx->stream);
-  for (auto& s : ctx->slots) free_slot(s);
+  // V-, E- and F-sized state of the old mesh
   ctx->slots.clear();
-  drop_layers(ctx);
-  mnav_obs::bvh_free(ctx->obs);                                      // belongs to the old mesh; rebuilt lazily
-  mnav_nb::nb_free(ctx->nbhd);                                       // V-sized spill lists
-  if (ctx->d_edge_dist) { ctx->alloc_bytes.erase((void*)ctx->d_edge_dist); (void)hipFree(ctx->d_edge_dist); ctx->d_edge_dist = nullptr; }   // belongs to the old mesh
+  ctx->layers.clear();
+  ctx->d_crn_infl.reset(); ctx->d_infl_mask.reset(); ctx->d_zero_u8.reset(); ctx->d_infl_keyd.reset(); ctx->crn_infl_valid = false;
+  ctx->obs = {};                                                     // rebuilt lazily
+  ctx->nbhd = {};                                                    // V-sized spill lists
+  ctx->d_edge_dist.reset();
   drop_graphs(ctx);
-  (void)hipFree(ctx->d_paths); ctx->d_paths = nullptr; ctx->paths_words = 0;
-  (void)hipFree(ctx->d_nbr); ctx->d_nbr = nullptr; (void)hipFree(ctx->d_crn); ctx->d_crn = nullptr;
-  (void)hipFree(ctx->d_blocked); ctx->d_blocked = nullptr;
-  (void)hipFree(ctx->d_cost); ctx->d_cost = nullptr; (void)hipFree(ctx->d_w); ctx->d_w = nullptr;
-  (void)hipFree(ctx->d_invalid); ctx->d_invalid = nullptr; (void)hipFree(ctx->d_edge_dist); ctx->d_edge_dist = nullptr;
+  ctx->d_paths.reset(); ctx->paths_words = 0;
+  ctx->d_nbr.reset(); ctx->d_crn.reset(); ctx->d_blocked.reset();
+  ctx->d_cost.reset(); ctx->d_w.reset(); ctx->d_invalid.reset();
   ctx->nbr_valid = ctx->crn_valid = false; ctx->have_costs = false;
   ctx->V = V; ctx->F = F; ctx->E = E;
   {
@@ -723,18 +631,18 @@ int mnav_upload_mesh(mnav_ctx* ctx, uint32_t V, uint32_t F, uint32_t E, const fl
   ctx->h_row_ptr = t.row_ptr; ctx->h_nbr_u = t.nbr_u;
   ctx->h_vf_ptr = std::move(t.vf_ptr); ctx->h_vf = std::move(t.vf); ctx->walk_mesh_valid = false;
   tb_free(ctx);
-  if (dev_upload(ctx, &ctx->d_row_ptr, t.row_ptr.data(), t.row_ptr.size())) return -1;
-  if (dev_upload(ctx, &ctx->d_nbr_u, t.nbr_u.data(), t.nbr_u.size())) return -1;
-  if (dev_upload(ctx, &ctx->d_nbr_e, t.nbr_e.data(), t.nbr_e.size())) return -1;
-  if (dev_upload(ctx, &ctx->d_crn_ptr, t.crn_ptr.data(), t.crn_ptr.size())) return -1;
-  if (dev_upload(ctx, &ctx->d_edge_vtx, edge_vtx, 2 * (size_t)E)) return -1;
+  HIPCHK(ctx->d_row_ptr.upload(ctx->stream, t.row_ptr.data(), t.row_ptr.size()));
+  HIPCHK(ctx->d_nbr_u.upload(ctx->stream, t.nbr_u.data(), t.nbr_u.size()));
+  HIPCHK(ctx->d_nbr_e.upload(ctx->stream, t.nbr_e.data(), t.nbr_e.size()));
+  HIPCHK(ctx->d_crn_ptr.upload(ctx->stream, t.crn_ptr.data(), t.crn_ptr.size()));
+  HIPCHK(ctx->d_edge_vtx.upload(ctx->stream, edge_vtx, 2 * (size_t)E));
   std::vector<CornerIdx> ci(t.crn_v1.size());
   for (size_t i = 0; i < ci.size(); ++i) ci[i] = CornerIdx{ t.crn_v1[i], t.crn_v2[i], t.crn_ea[i], t.crn_eb[i], t.crn_ec[i], t.crn_face[i] };
-  if (dev_upload(ctx, &ctx->d_crn_walk, t.crn_walk.data(), t.crn_walk.size())) return -1;
-  if (dev_upload(ctx, &ctx->d_crn_idx, ci.data(), ci.size())) return -1;
-  if (dev_upload(ctx, &ctx->d_xyz, xyz, 3 * (size_t)V)) return -1;
+  HIPCHK(ctx->d_crn_walk.upload(ctx->stream, t.crn_walk.data(), t.crn_walk.size()));
+  HIPCHK(ctx->d_crn_idx.upload(ctx->stream, ci.data(), ci.size()));
+  HIPCHK(ctx->d_xyz.upload(ctx->stream, xyz, 3 * (size_t)V));
   ctx->have_normals = vertex_normals != nullptr;
-  if (dev_upload(ctx, &ctx->d_nrm, vertex_normals, vertex_normals ? 3 * (size_t)V : 0)) return -1;
+  HIPCHK(ctx->d_nrm.upload(ctx->stream, vertex_normals, vertex_normals ? 3 * (size_t)V : 0));
   // LDS tiles of the SSSP engine
   {
     ctx->tile_size = opt_u32(ctx->opt.tile_size, 512u);
@@ -762,20 +670,20 @@ int mnav_upload_mesh(mnav_ctx* ctx, uint32_t V, uint32_t F, uint32_t E, const fl
     if (opt_on(ctx->opt.verbose))
       fprintf(stderr, "[mnav] tiles: size %u, %u tiles, max owned %u, halo %u, edges %u -> LDS %zu B (solve), %zu B (finalize)\n",
               ctx->tile_size, T.ntiles, T.max_nv, T.max_nh, T.max_ne, ctx->tile_lds, ctx->fin_lds);
-    (void)hipFree(ctx->d_t_tw); ctx->d_t_tw = nullptr; ctx->tw_valid = false;
+    ctx->d_t_tw.reset(); ctx->tw_valid = false;
     ctx->t_nnz = (uint32_t)T.col.size();
-    if (dev_upload(ctx, &ctx->d_t_vptr, T.vptr.data(), T.vptr.size())) return -1;
-    if (dev_upload(ctx, &ctx->d_t_verts, T.verts.data(), T.verts.size())) return -1;
-    if (dev_upload(ctx, &ctx->d_t_hptr, T.hptr.data(), T.hptr.size())) return -1;
-    if (dev_upload(ctx, &ctx->d_t_halo_verts, T.halo_verts.data(), T.halo_verts.size())) return -1;
-    if (dev_upload(ctx, &ctx->d_t_halo_tile, T.halo_tile.data(), T.halo_tile.size())) return -1;
-    if (dev_upload(ctx, &ctx->d_t_eptr, T.eptr.data(), T.eptr.size())) return -1;
-    if (dev_upload(ctx, &ctx->d_t_rptr, T.rptr.data(), T.rptr.size())) return -1;
-    if (dev_upload(ctx, &ctx->d_t_rowptr, T.rowptr.data(), T.rowptr.size())) return -1;
-    if (dev_upload(ctx, &ctx->d_t_col, T.col.data(), T.col.size())) return -1;
-    if (dev_upload(ctx, &ctx->d_t_src, T.src.data(), T.src.size())) return -1;
-    if (dev_upload(ctx, &ctx->d_vert_tile, T.vert_tile.data(), T.vert_tile.size())) return -1;
-    if (dev_upload(ctx, &ctx->d_t_tw, (const float*)nullptr, T.col.size())) return -1;
+    HIPCHK(ctx->d_t_vptr.upload(ctx->stream, T.vptr.data(), T.vptr.size()));
+    HIPCHK(ctx->d_t_verts.upload(ctx->stream, T.verts.data(), T.verts.size()));
+    HIPCHK(ctx->d_t_hptr.upload(ctx->stream, T.hptr.data(), T.hptr.size()));
+    HIPCHK(ctx->d_t_halo_verts.upload(ctx->stream, T.halo_verts.data(), T.halo_verts.size()));
+    HIPCHK(ctx->d_t_halo_tile.upload(ctx->stream, T.halo_tile.data(), T.halo_tile.size()));
+    HIPCHK(ctx->d_t_eptr.upload(ctx->stream, T.eptr.data(), T.eptr.size()));
+    HIPCHK(ctx->d_t_rptr.upload(ctx->stream, T.rptr.data(), T.rptr.size()));
+    HIPCHK(ctx->d_t_rowptr.upload(ctx->stream, T.rowptr.data(), T.rowptr.size()));
+    HIPCHK(ctx->d_t_col.upload(ctx->stream, T.col.data(), T.col.size()));
+    HIPCHK(ctx->d_t_src.upload(ctx->stream, T.src.data(), T.src.size()));
+    HIPCHK(ctx->d_vert_tile.upload(ctx->stream, T.vert_tile.data(), T.vert_tile.size()));
+    HIPCHK(ctx->d_t_tw.upload(ctx->stream, nullptr, T.col.size()));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     // keep the sizes, and the small per-vertex maps the partitioner of mnav_shard_setup needs, on the host
     T.halo_tile.clear(); T.halo_tile.shrink_to_fit(); T.rowptr.clear(); T.rowptr.shrink_to_fit();
@@ -805,11 +713,11 @@ int mnav_upload_costs(mnav_ctx* ctx, const float* vertex_costs, const float* edg
   if (!ctx->have_mesh) { ctx->err = "mnav_upload_mesh has not been called"; return -1; }
   if ((ctx->V && !vertex_costs) || (ctx->E && !edge_weights)) { ctx->err = "null cost array"; return -1; }
   if (hipSetDevice(ctx->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return -1; }
-  if (dev_upload(ctx, &ctx->d_cost, vertex_costs, ctx->V)) return -1;
-  if (dev_upload(ctx, &ctx->d_w, edge_weights, ctx->E)) return -1;
+  HIPCHK(ctx->d_cost.upload(ctx->stream, vertex_costs, ctx->V));
+  HIPCHK(ctx->d_w.upload(ctx->stream, edge_weights, ctx->E));
   std::vector<uint8_t> zero;
   if (!invalid) { zero.assign(ctx->V ? ctx->V : 1, 0); invalid = zero.data(); }
-  if (dev_upload(ctx, &ctx->d_invalid, invalid, ctx->V)) return -1;
+  HIPCHK(ctx->d_invalid.upload(ctx->stream, invalid, ctx->V));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   ctx->h_cost.assign(vertex_costs, vertex_costs + ctx->V);
   ctx->h_invalid.assign(invalid, invalid + ctx->V);
@@ -824,10 +732,10 @@ int mnav_upload_costs(mnav_ctx* ctx, const float* vertex_costs, const float* edg
 // (re)computed; host mirrors (cost for the seed cut-offs, mean weight for the band widths) are refreshed
 static int edge_weight_pass(mnav_ctx* ctx, double edge_cost_factor, const uint8_t* invalid, float* vertex_costs_out, float* edge_weights_out)
 {
-  if (dev_upload(ctx, &ctx->d_w, (const float*)nullptr, ctx->E)) return -1;
+  HIPCHK(ctx->d_w.upload(ctx->stream, nullptr, ctx->E));
   std::vector<uint8_t> zero;
   if (!invalid) { zero.assign(ctx->V ? ctx->V : 1, 0); invalid = zero.data(); }
-  if (dev_upload(ctx, &ctx->d_invalid, invalid, ctx->V)) return -1;
+  HIPCHK(ctx->d_invalid.upload(ctx->stream, invalid, ctx->V));
   const uint32_t gb = (ctx->E + kBlock - 1) / kBlock;
   hipLaunchKernelGGL(k_edge_weights, dim3(gb ? gb : 1), dim3(kBlock), 0, ctx->stream, ctx->E, ctx->d_edge_vtx, ctx->d_edge_dist,
                      ctx->d_cost, edge_cost_factor, ctx->d_w);
@@ -855,8 +763,8 @@ int mnav_compute_edge_weights(mnav_ctx* ctx, const float* vertex_costs, const fl
   if (!ctx->have_mesh) { ctx->err = "mnav_upload_mesh has not been called"; return -1; }
   if ((ctx->V && !vertex_costs) || (ctx->E && !edge_distances)) { ctx->err = "null cost array"; return -1; }
   if (hipSetDevice(ctx->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return -1; }
-  if (dev_upload(ctx, &ctx->d_cost, vertex_costs, ctx->V)) return -1;
-  if (dev_upload(ctx, &ctx->d_edge_dist, edge_distances, ctx->E)) return -1;
+  HIPCHK(ctx->d_cost.upload(ctx->stream, vertex_costs, ctx->V));
+  HIPCHK(ctx->d_edge_dist.upload(ctx->stream, edge_distances, ctx->E));
   ctx->crn_infl_valid = false;
   return edge_weight_pass(ctx, edge_cost_factor, invalid, nullptr, edge_weights_out);
 }
@@ -872,9 +780,9 @@ int mnav_combine_costs(mnav_ctx* ctx, int mode, uint32_t n_layers, const float* 
   if ((n_layers && !layer_costs) || (mode == 1 && n_layers && !weights) || (ctx->E && !edge_distances && !ctx->d_edge_dist)) { ctx->err = "null input array"; return -1; }
   if (hipSetDevice(ctx->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return -1; }
   const uint32_t V = ctx->V;
-  DevTmp<float> d_layers, d_wts;
-  HIPCHK(hipMalloc(d_layers.out(), sizeof(float) * ((size_t)n_layers * V + 1)));
-  HIPCHK(hipMalloc(d_wts.out(), sizeof(float) * (n_layers + 1)));
+  DevBuf<float> d_layers, d_wts;
+  HIPCHK(d_layers.alloc(sizeof(float) * ((size_t)n_layers * V + 1)));
+  HIPCHK(d_wts.alloc(sizeof(float) * (n_layers + 1)));
   int rc = 0;
   for (uint32_t l = 0; l < n_layers && rc == 0; ++l) {
     if (!layer_costs[l]) { ctx->err = "null layer"; rc = -1; break; }
@@ -882,8 +790,11 @@ int mnav_combine_costs(mnav_ctx* ctx, int mode, uint32_t n_layers, const float* 
   }
   if (rc == 0 && mode == 1 && n_layers &&
       hipMemcpyAsync(d_wts, weights, sizeof(float) * n_layers, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) { ctx->err = "weight upload failed"; rc = -1; }
-  if (rc == 0 && dev_upload(ctx, &ctx->d_cost, (const float*)nullptr, V)) rc = -1;
-  if (rc == 0 && edge_distances) { ctx->crn_infl_valid = false; if (dev_upload(ctx, &ctx->d_edge_dist, edge_distances, ctx->E)) rc = -1; }   // NULL: keep the resident ones
+  if (rc == 0 && ctx->d_cost.upload(ctx->stream, nullptr, V) != hipSuccess) { ctx->err = "cost buffer allocation failed"; rc = -1; }
+  if (rc == 0 && edge_distances) {                                   // NULL: keep the resident ones
+    ctx->crn_infl_valid = false;
+    if (ctx->d_edge_dist.upload(ctx->stream, edge_distances, ctx->E) != hipSuccess) { ctx->err = "edge distance upload failed"; rc = -1; }
+  }
   if (rc == 0) {
     const uint32_t gb = (V + kBlock - 1) / kBlock;
     hipLaunchKernelGGL(k_combine, dim3(gb ? gb : 1), dim3(kBlock), 0, ctx->stream, V, mode, n_layers, d_layers, d_wts, ctx->d_cost);
@@ -904,9 +815,9 @@ int mnav_update_costs(mnav_ctx* ctx, uint32_t n, const uint32_t* vertex_ids, con
   if (!vertex_ids || !values) { ctx->err = "null input array"; return -1; }
   for (uint32_t i = 0; i < n; ++i) if (vertex_ids[i] >= ctx->V) { ctx->err = "vertex id out of range"; return -1; }
   if (hipSetDevice(ctx->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return -1; }
-  DevTmp<uint32_t> d_ids; DevTmp<float> d_vals;
-  HIPCHK(hipMalloc(d_ids.out(), sizeof(uint32_t) * n));
-  HIPCHK(hipMalloc(d_vals.out(), sizeof(float) * n));
+  DevBuf<uint32_t> d_ids; DevBuf<float> d_vals;
+  HIPCHK(d_ids.alloc(sizeof(uint32_t) * n));
+  HIPCHK(d_vals.alloc(sizeof(float) * n));
   int rc = 0;
   if (hipMemcpyAsync(d_ids, vertex_ids, sizeof(uint32_t) * n, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
       hipMemcpyAsync(d_vals, values, sizeof(float) * n, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) { ctx->err = "upload failed"; rc = -1; }
@@ -936,9 +847,9 @@ int mnav_update_edge_weights(mnav_ctx* ctx, uint32_t n, const uint32_t* edge_ids
   if (!edge_ids || !values) { ctx->err = "null input array"; return -1; }
   for (uint32_t i = 0; i < n; ++i) if (edge_ids[i] >= ctx->E) { ctx->err = "edge id out of range"; return -1; }
   if (hipSetDevice(ctx->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return -1; }
-  DevTmp<uint32_t> d_ids; DevTmp<float> d_vals;
-  HIPCHK(hipMalloc(d_ids.out(), sizeof(uint32_t) * n));
-  HIPCHK(hipMalloc(d_vals.out(), sizeof(float) * n));
+  DevBuf<uint32_t> d_ids; DevBuf<float> d_vals;
+  HIPCHK(d_ids.alloc(sizeof(uint32_t) * n));
+  HIPCHK(d_vals.alloc(sizeof(float) * n));
   int rc = 0;
   if (hipMemcpyAsync(d_ids, edge_ids, sizeof(uint32_t) * n, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
       hipMemcpyAsync(d_vals, values, sizeof(float) * n, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) { ctx->err = "upload failed"; rc = -1; }
@@ -971,16 +882,16 @@ static int layer_slot(mnav_ctx* ctx, uint32_t layer, bool want_dist)
   if (ctx->layers.size() <= layer) ctx->layers.resize(layer + 1);
   mnav_ctx::Layer& L = ctx->layers[layer];
   const size_t V = ctx->V ? ctx->V : 1;
-  if (!L.cost) HIPCHK(hipMalloc((void**)&L.cost, 4 * V));
-  if (!L.lethal) HIPCHK(hipMalloc((void**)&L.lethal, V));
-  if (want_dist && !L.dist) HIPCHK(hipMalloc((void**)&L.dist, 4 * V));
+  if (!L.cost) HIPCHK(L.cost.alloc(4 * V));
+  if (!L.lethal) HIPCHK(L.lethal.alloc(V));
+  if (want_dist && !L.dist) HIPCHK(L.dist.alloc(4 * V));
   return 0;
 }
 
 static int ensure_edge_distances(mnav_ctx* ctx)
 {
   if (ctx->d_edge_dist) return 0;
-  if (dev_upload(ctx, &ctx->d_edge_dist, (const float*)nullptr, ctx->E)) return -1;
+  HIPCHK(ctx->d_edge_dist.upload(ctx->stream, nullptr, ctx->E));
   const uint32_t gb = (ctx->E + kBlock - 1) / kBlock;
   hipLaunchKernelGGL(k_edge_dist, dim3(gb ? gb : 1), dim3(kBlock), 0, ctx->stream, ctx->E, ctx->d_edge_vtx, ctx->d_xyz, ctx->d_edge_dist);
   HIPCHK(hipGetLastError());
@@ -1031,18 +942,18 @@ int mnav_layer_inflation(mnav_ctx* ctx, uint32_t layer, uint32_t input_layer, do
   if (ensure_edge_distances(ctx)) return -1;
   const uint32_t V = ctx->V;
   const uint32_t gb = (V + kBlock - 1) / kBlock ? (V + kBlock - 1) / kBlock : 1;
-  if (!ctx->d_crn_infl) HIPCHK(hipMalloc((void**)&ctx->d_crn_infl, sizeof(Corner) * (size_t)(ctx->F ? 3 * (size_t)ctx->F : 1)));
+  if (!ctx->d_crn_infl) HIPCHK(ctx->d_crn_infl.alloc(sizeof(Corner) * (size_t)(ctx->F ? 3 * (size_t)ctx->F : 1)));
   if (!ctx->crn_infl_valid) {
     hipLaunchKernelGGL(k_build_crn_infl, dim3(gb), dim3(kBlock), 0, ctx->stream, V, ctx->d_crn_ptr, ctx->d_crn_idx, ctx->d_edge_dist, ctx->d_crn_infl);
     HIPCHK(hipGetLastError());
     ctx->crn_infl_valid = true;
   }
   const size_t Vn = V ? V : 1;
-  if (!ctx->d_infl_mask) HIPCHK(hipMalloc((void**)&ctx->d_infl_mask, Vn));
-  if (!ctx->d_zero_u8) { HIPCHK(hipMalloc((void**)&ctx->d_zero_u8, Vn)); HIPCHK(hipMemsetAsync(ctx->d_zero_u8, 0, Vn, ctx->stream)); }
-  if (!ctx->d_infl_keyd) HIPCHK(hipMalloc((void**)&ctx->d_infl_keyd, 4 * Vn));
-  DevTmp<uint8_t> d_inv;
-  if (invalid) { HIPCHK(hipMalloc(d_inv.out(), Vn)); HIPCHK(hipMemcpyAsync(d_inv, invalid, V, hipMemcpyHostToDevice, ctx->stream)); }
+  if (!ctx->d_infl_mask) HIPCHK(ctx->d_infl_mask.alloc(Vn));
+  if (!ctx->d_zero_u8) { HIPCHK(ctx->d_zero_u8.alloc(Vn)); HIPCHK(hipMemsetAsync(ctx->d_zero_u8, 0, Vn, ctx->stream)); }
+  if (!ctx->d_infl_keyd) HIPCHK(ctx->d_infl_keyd.alloc(4 * Vn));
+  DevBuf<uint8_t> d_inv;
+  if (invalid) { HIPCHK(d_inv.alloc(Vn)); HIPCHK(hipMemcpyAsync(d_inv, invalid, V, hipMemcpyHostToDevice, ctx->stream)); }
   mnav_ctx::Layer& L = ctx->layers[layer];
   mnav_ctx::Layer& In = ctx->layers[input_layer];
   L.inflation_radius = inflation_radius; L.inscribed_radius = inscribed_radius; L.inscribed_value = inscribed_value; L.lethal_value = lethal_value;
@@ -1055,15 +966,15 @@ int mnav_layer_inflation(mnav_ctx* ctx, uint32_t layer, uint32_t input_layer, do
   Plan P;
   memset(&P, 0, sizeof(P));
   P.planner = kPlannerCvp; P.V = V;
-  P.row_ptr = ctx->d_row_ptr; P.nbr = nullptr; P.crn_ptr = ctx->d_crn_ptr; P.crn = ctx->d_crn_infl; P.blocked = ctx->d_zero_u8;
-  P.dist = L.dist; P.tkey = s.tkey; P.pred = s.pred; P.dirn = s.dirn; P.cutf = s.cutf; P.stamp = s.stamp; P.dirty = s.dirty;
-  P.list[0] = s.list0; P.list[1] = s.list1; P.wlist[0] = s.wlist0; P.wlist[1] = s.wlist1; P.wstamp = s.wstamp; P.cap = V; P.ctl = s.ctl; P.cnt = s.cnt;
+  P.row_ptr = ctx->d_row_ptr.get(); P.nbr = nullptr; P.crn_ptr = ctx->d_crn_ptr.get(); P.crn = ctx->d_crn_infl.get(); P.blocked = ctx->d_zero_u8.get();
+  P.dist = L.dist.get(); P.tkey = s.tkey.get(); P.pred = s.pred.get(); P.dirn = s.dirn.get(); P.cutf = s.cutf.get(); P.stamp = s.stamp.get(); P.dirty = s.dirty.get();
+  P.list[0] = s.list0.get(); P.list[1] = s.list1.get(); P.wlist[0] = s.wlist0.get(); P.wlist[1] = s.wlist1.get(); P.wstamp = s.wstamp.get(); P.cap = V; P.ctl = s.ctl; P.cnt = s.cnt.get();
   const float maxd = (float)inflation_radius;                                               // :438 (const float&)
   P.delta = maxd > 0.f ? maxd : 1.0f;                                                       // one band per radius: the wave dies out within ~2
   P.offset = 0.0; P.max_steps = ctx->max_steps; P.walk_max = ctx->walk_max; P.descend_max = ctx->descend_max;
   for (int k = 0; k < 3; ++k) { P.seed[k] = kNone; P.target[k] = kNone; P.seed_d[k] = 0.f; P.seed_expands[k] = 1; P.target_expands[k] = 0; }
   P.seed_face = kNone;
-  P.seed_mask = ctx->d_infl_mask; P.keyd = ctx->d_infl_keyd; P.infl_max = maxd;
+  P.seed_mask = ctx->d_infl_mask.get(); P.keyd = ctx->d_infl_keyd.get(); P.infl_max = maxd;
   HIPCHK(hipMemcpyAsync(ctx->d_plans, &P, sizeof(Plan), hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
   uint32_t gi = (V + kBlock * 4 - 1) / (kBlock * 4);
@@ -1085,7 +996,7 @@ int mnav_layer_inflation(mnav_ctx* ctx, uint32_t layer, uint32_t input_layer, do
     }
     const auto t_c0 = std::chrono::steady_clock::now();
     const bool tr = opt_on(ctx->opt.trace);
-    unsigned long long* const stamps = reinterpret_cast<unsigned long long*>(ctx->h_res);   // (trace: two device clock stamps in the pinned result record, unused during a wave)
+    unsigned long long* const stamps = reinterpret_cast<unsigned long long*>(ctx->h_res.get());   // (trace: two device clock stamps in the pinned result record, unused during a wave)
     if (tr) { HIPCHK(hipEventRecord(ctx->ev[4], ctx->stream)); hipLaunchKernelGGL(k_stamp_to_host, dim3(1), dim3(1), 0, ctx->stream, stamps); }   // (trace: the chunk's time on the DEVICE, apart from the host's wait for it)
     if (run_chunk<kPlannerCvp>(ctx, 1, G, false)) return -1;
     if (tr) HIPCHK(hipEventRecord(ctx->ev[5], ctx->stream));
@@ -1119,11 +1030,11 @@ int mnav_layer_inflation(mnav_ctx* ctx, uint32_t layer, uint32_t input_layer, do
   HIPCHK(hipGetLastError());
   // vector_map_ (:277-309): accumulation over the lethal contours, then assignments in pop order (launches until settled)
   L.have_vec = false;
-  if (!L.vec) HIPCHK(hipMalloc((void**)&L.vec, 12 * Vn));
-  if (!L.vstate) HIPCHK(hipMalloc((void**)&L.vstate, 3 * Vn));
-  if (!ctx->d_verify_any) HIPCHK(hipMalloc((void**)&ctx->d_verify_any, 4));
-  uint32_t* d_vctl = nullptr;
-  HIPCHK(hipMalloc((void**)&d_vctl, 16));
+  if (!L.vec) HIPCHK(L.vec.alloc(12 * Vn));
+  if (!L.vstate) HIPCHK(L.vstate.alloc(3 * Vn));
+  if (!ctx->d_verify_any) HIPCHK(ctx->d_verify_any.alloc(4));
+  DevBuf<uint32_t> d_vctl;
+  HIPCHK(d_vctl.alloc(16));
   HIPCHK(hipMemsetAsync(d_vctl, 0, 16, ctx->stream));
   uint8_t *st0 = L.vstate, *st1 = L.vstate + Vn, *acc = L.vstate + 2 * Vn;
   hipLaunchKernelGGL(k_infl_accum, dim3(gb), dim3(kBlock), 0, ctx->stream, ctx->d_plans, ctx->d_crn_walk, ctx->d_xyz, L.vec, st0, acc, d_vctl);
@@ -1140,7 +1051,7 @@ int mnav_layer_inflation(mnav_ctx* ctx, uint32_t layer, uint32_t input_layer, do
     if (vctl[1] == 0) { vec_ok = false; break; }                     // nothing moved although something waits: not on a verified state
   }
   if (st0 != L.vstate) HIPCHK(hipMemcpyAsync(L.vstate, st0, Vn, hipMemcpyDeviceToDevice, ctx->stream));   // final states in the first array
-  (void)hipFree(d_vctl);
+  d_vctl.reset();
   L.have_vec = vec_ok;
   HIPCHK(hipEventRecord(ctx->ev[3], ctx->stream));
   Cnt flags{};
@@ -1218,13 +1129,13 @@ int mnav_combine_layers(mnav_ctx* ctx, int mode, uint32_t n_layers, const uint32
     ptrs[l] = ctx->layers[layers[l]].cost;
   }
   if (ensure_edge_distances(ctx)) return -1;
-  DevTmp<const float*> d_ptrs; DevTmp<float> d_wts;
-  HIPCHK(hipMalloc(d_ptrs.out(), sizeof(float*) * (n_layers + 1)));
-  HIPCHK(hipMalloc(d_wts.out(), sizeof(float) * (n_layers + 1)));
+  DevBuf<const float*> d_ptrs; DevBuf<float> d_wts;
+  HIPCHK(d_ptrs.alloc(sizeof(float*) * (n_layers + 1)));
+  HIPCHK(d_wts.alloc(sizeof(float) * (n_layers + 1)));
   int rc = 0;
   if (n_layers && hipMemcpyAsync(d_ptrs, ptrs.data(), sizeof(float*) * n_layers, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = -1;
   if (rc == 0 && mode == 1 && n_layers && hipMemcpyAsync(d_wts, weights, sizeof(float) * n_layers, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = -1;
-  if (rc == 0 && dev_upload(ctx, &ctx->d_cost, (const float*)nullptr, ctx->V)) rc = -1;
+  if (rc == 0 && ctx->d_cost.upload(ctx->stream, nullptr, ctx->V) != hipSuccess) { ctx->err = "cost buffer allocation failed"; rc = -1; }
   if (rc == 0) {
     const uint32_t gb = (ctx->V + kBlock - 1) / kBlock;
     hipLaunchKernelGGL(k_combine_resident, dim3(gb ? gb : 1), dim3(kBlock), 0, ctx->stream, ctx->V, mode, n_layers, d_ptrs, d_wts, ctx->d_cost);
@@ -1256,11 +1167,11 @@ int mnav_combine_layers_update(mnav_ctx* ctx, int mode, uint32_t n_layers, const
     if (layers[l] >= ctx->layers.size() || !ctx->layers[layers[l]].ready) { ctx->err = "layer is not resident"; return -1; }
     ptrs[l] = ctx->layers[layers[l]].cost;
   }
-  DevTmp<const float*> d_ptrs; DevTmp<float> d_wts, d_vals; DevTmp<uint32_t> d_ids;
-  HIPCHK(hipMalloc(d_ptrs.out(), sizeof(float*) * (n_layers + 1)));
-  HIPCHK(hipMalloc(d_wts.out(), sizeof(float) * (n_layers + 1)));
-  HIPCHK(hipMalloc(d_vals.out(), sizeof(float) * n));
-  HIPCHK(hipMalloc(d_ids.out(), sizeof(uint32_t) * n));
+  DevBuf<const float*> d_ptrs; DevBuf<float> d_wts, d_vals; DevBuf<uint32_t> d_ids;
+  HIPCHK(d_ptrs.alloc(sizeof(float*) * (n_layers + 1)));
+  HIPCHK(d_wts.alloc(sizeof(float) * (n_layers + 1)));
+  HIPCHK(d_vals.alloc(sizeof(float) * n));
+  HIPCHK(d_ids.alloc(sizeof(uint32_t) * n));
   std::vector<float> vals(n);
   int rc = 0;
   if (n_layers && hipMemcpyAsync(d_ptrs, ptrs.data(), sizeof(float*) * n_layers, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = -1;
@@ -1427,11 +1338,9 @@ static uint32_t dijkstra_impl(mnav_ctx* ctx, uint32_t n, const uint32_t* seeds, 
       for (uint32_t k = 0; k < m; ++k)
         if (ctx->h_res[k].code == kPathOverflow) { ooff[k] = over_words; ocap[k] = ctx->h_res[k].path_len; over_words += ctx->h_res[k].path_len; }
       if (over_words) {
-        std::vector<PlanResult> keep(ctx->h_res, ctx->h_res + m);   // settled / evals were accumulated by other kernels
-        (void)hipFree(ctx->d_over); (void)hipFree(ctx->d_over_off); (void)hipFree(ctx->d_over_cap);
-        ctx->d_over = nullptr; ctx->d_over_off = nullptr; ctx->d_over_cap = nullptr;
-        if (hipMalloc((void**)&ctx->d_over, 4 * over_words) != hipSuccess || hipMalloc((void**)&ctx->d_over_off, 8 * (size_t)m) != hipSuccess ||
-            hipMalloc((void**)&ctx->d_over_cap, 4 * (size_t)m) != hipSuccess ||
+        std::vector<PlanResult> keep(ctx->h_res.get(), ctx->h_res + m);   // settled / evals were accumulated by other kernels
+        ctx->d_over.reset(); ctx->d_over_off.reset(); ctx->d_over_cap.reset();
+        if (ctx->d_over.alloc(4 * over_words) != hipSuccess || ctx->d_over_off.alloc(8 * (size_t)m) != hipSuccess || ctx->d_over_cap.alloc(4 * (size_t)m) != hipSuccess ||
             hipMemcpyAsync(ctx->d_over_off, ooff.data(), 8 * (size_t)m, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
             hipMemcpyAsync(ctx->d_over_cap, ocap.data(), 4 * (size_t)m, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
           { ctx->err = "path buffers: out of memory"; return MNAV_INTERNAL_ERROR; }
@@ -1461,18 +1370,15 @@ static uint32_t dijkstra_impl(mnav_ctx* ctx, uint32_t n, const uint32_t* seeds, 
     const size_t total = offs[m];
     if (total && path_out && path_cap) {
       if (ctx->pack_words < total) {
-        if (ctx->d_pack) (void)hipFree(ctx->d_pack);
-        if (ctx->h_pack) (void)hipHostFree(ctx->h_pack);
-        ctx->d_pack = nullptr; ctx->h_pack = nullptr; ctx->pack_words = 0;
+        ctx->d_pack.reset(); ctx->h_pack.reset(); ctx->pack_words = 0;
         const size_t want = total + total / 4 + 1024;
-        if (hipMalloc((void**)&ctx->d_pack, 4 * want) != hipSuccess || hipHostMalloc((void**)&ctx->h_pack, 4 * want, hipHostMallocDefault) != hipSuccess)
+        if (ctx->d_pack.alloc(4 * want) != hipSuccess || ctx->h_pack.alloc(4 * want) != hipSuccess)
           { ctx->err = "path buffers: out of memory"; return MNAV_INTERNAL_ERROR; }
         ctx->pack_words = want;
       }
       if (ctx->pack_meta_n < 2 * (size_t)m) {
-        if (ctx->d_pack_meta) (void)hipFree(ctx->d_pack_meta);
-        ctx->d_pack_meta = nullptr; ctx->pack_meta_n = 0;
-        if (hipMalloc((void**)&ctx->d_pack_meta, 4 * 2 * (size_t)m) != hipSuccess) { ctx->err = "path buffers: out of memory"; return MNAV_INTERNAL_ERROR; }
+        ctx->pack_meta_n = 0;
+        if (ctx->d_pack_meta.alloc(4 * 2 * (size_t)m) != hipSuccess) { ctx->err = "path buffers: out of memory"; return MNAV_INTERNAL_ERROR; }
         ctx->pack_meta_n = 2 * (size_t)m;
       }
       if (hipMemcpyAsync(ctx->d_pack_meta, offs.data(), 4 * (size_t)m, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
@@ -1592,8 +1498,7 @@ static uint32_t cvp_impl(mnav_ctx* ctx, uint32_t n, const float* seed_pos, const
   if (m) {
     if (materialize(ctx, true, cost_limit)) return MNAV_INTERNAL_ERROR;
     if (ctx->seed_pos_cap < m) {
-      (void)hipFree(ctx->d_seed_pos); ctx->d_seed_pos = nullptr;
-      if (hipMalloc((void**)&ctx->d_seed_pos, 12 * (size_t)m) != hipSuccess) { ctx->err = "alloc failed"; return MNAV_INTERNAL_ERROR; }
+      if (ctx->d_seed_pos.alloc(12 * (size_t)m) != hipSuccess) { ctx->err = "alloc failed"; return MNAV_INTERNAL_ERROR; }
       ctx->seed_pos_cap = m;
     }
     if (hipMemcpyAsync(ctx->d_seed_pos, sp.data(), 12 * (size_t)m, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
@@ -1780,15 +1685,15 @@ int mnav_download_output(mnav_ctx* ctx, uint32_t slot, int what, void* host_out)
     if (slot < ctx->caller_slot.size()) slot = ctx->caller_slot[slot];
     if (slot >= ctx->last_n) { ctx->err = "output not resident"; return -1; }
     if (hipSetDevice(ctx->device) != hipSuccess) return -1;
-    float* tmp = nullptr;
-    HIPCHK(hipMalloc((void**)&tmp, 4 * (size_t)(ctx->V ? ctx->V : 1)));
+    DevBuf<float> tmp;
+    HIPCHK(tmp.alloc(4 * (size_t)(ctx->V ? ctx->V : 1)));
     const uint32_t g = std::min<uint32_t>((ctx->V + kBlock - 1) / kBlock + 1, 4096);
-    if (ctx->last_engine == 5 && ctx->lazy_paths && !ctx->tb_args_valid) { (void)hipFree(tmp); ctx->err = "output not resident"; return -1; }
+    if (ctx->last_engine == 5 && ctx->lazy_paths && !ctx->tb_args_valid) { ctx->err = "output not resident"; return -1; }
     if (ctx->last_engine == 5 && ctx->lazy_paths) hipLaunchKernelGGL(k_tb_popped, dim3(g), dim3(kBlock), 0, ctx->stream, ctx->tb_args, slot, ctx->V, tmp);
     else hipLaunchKernelGGL(k_popped, dim3(g), dim3(kBlock), 0, ctx->stream, ctx->slots[slot].dist, ctx->last_target[slot], ctx->last_offset, ctx->V, tmp);
     const hipError_t e1 = hipMemcpyAsync(host_out, tmp, 4 * (size_t)ctx->V, hipMemcpyDeviceToHost, ctx->stream);
     const hipError_t e2 = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(tmp);
+    tmp.reset();
     if (e1 != hipSuccess || e2 != hipSuccess) { ctx->err = "popped potential: copy failed"; return -1; }
     return 0;
   }
@@ -1815,7 +1720,7 @@ int mnav_vector_at(mnav_ctx* ctx, uint32_t slot, const uint32_t vs[3], const flo
     if (p < ctx->caller_slot.size()) p = ctx->caller_slot[p];
     if (p >= ctx->last_n) { ctx->err = "output not resident"; return -1; }
     if (hipSetDevice(ctx->device) != hipSuccess) return -1;
-    if (!ctx->d_vec3) HIPCHK(hipMalloc((void**)&ctx->d_vec3, 64));
+    if (!ctx->d_vec3) HIPCHK(ctx->d_vec3.alloc(64));
     hipLaunchKernelGGL(k_tb_vector3, dim3(3), dim3(kWave), 0, ctx->stream, ctx->tb_args, ctx->d_row_ptr, ctx->d_nbr, ctx->d_xyz, p,
                        make_uint3(vs[0], vs[1], vs[2]), ctx->d_vec3);
     HIPCHK(hipGetLastError());
@@ -1878,20 +1783,20 @@ int mnav_backtrack_cvp_batch(mnav_ctx* ctx, uint32_t n, const float* seed_pos, c
     L.repulsive_field = 1;
   }
   if (!ctx->walk_mesh_valid) {
-    if (dev_upload(ctx, &ctx->d_faces, ctx->h_faces.data(), ctx->h_faces.size())) return -1;
-    if (dev_upload(ctx, &ctx->d_vf_ptr, ctx->h_vf_ptr.data(), ctx->h_vf_ptr.size())) return -1;
-    if (dev_upload(ctx, &ctx->d_vf, ctx->h_vf.data(), ctx->h_vf.size())) return -1;
+    HIPCHK(ctx->d_faces.upload(ctx->stream, ctx->h_faces.data(), ctx->h_faces.size()));
+    HIPCHK(ctx->d_vf_ptr.upload(ctx->stream, ctx->h_vf_ptr.data(), ctx->h_vf_ptr.size()));
+    HIPCHK(ctx->d_vf.upload(ctx->stream, ctx->h_vf.data(), ctx->h_vf.size()));
     ctx->walk_mesh_valid = true;
   }
   const size_t need = (size_t)cap * n;
   if (need > ctx->walk_cap) {
-    (void)hipFree(ctx->d_walk_pos); (void)hipFree(ctx->d_walk_face); ctx->d_walk_pos = nullptr; ctx->d_walk_face = nullptr; ctx->walk_cap = 0;
-    HIPCHK(hipMalloc((void**)&ctx->d_walk_pos, 12 * need)); HIPCHK(hipMalloc((void**)&ctx->d_walk_face, 4 * need));
+    ctx->d_walk_pos.reset(); ctx->d_walk_face.reset(); ctx->walk_cap = 0;
+    HIPCHK(ctx->d_walk_pos.alloc(12 * need)); HIPCHK(ctx->d_walk_face.alloc(4 * need));
     ctx->walk_cap = need;
   }
   if (n > ctx->walk_jobs_cap) {
-    (void)hipFree(ctx->d_walk_jobs); (void)hipFree(ctx->d_walk_ctl); ctx->d_walk_jobs = nullptr; ctx->d_walk_ctl = nullptr; ctx->walk_jobs_cap = 0;
-    HIPCHK(hipMalloc((void**)&ctx->d_walk_jobs, sizeof(WalkJob) * (size_t)n)); HIPCHK(hipMalloc((void**)&ctx->d_walk_ctl, 8 * (size_t)n));
+    ctx->d_walk_jobs.reset(); ctx->d_walk_ctl.reset(); ctx->walk_jobs_cap = 0;
+    HIPCHK(ctx->d_walk_jobs.alloc(sizeof(WalkJob) * (size_t)n)); HIPCHK(ctx->d_walk_ctl.alloc(8 * (size_t)n));
     ctx->walk_jobs_cap = n;
   }
   HIPCHK(hipMemcpyAsync(ctx->d_walk_jobs, jobs.data(), sizeof(WalkJob) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));

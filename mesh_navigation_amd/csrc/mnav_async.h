@@ -274,7 +274,7 @@ __global__ __launch_bounds__(kTileBlock) void k_plan_async(const TilePlan* __res
       MNAV_GLOBAL const uint32_t* g_halo_tile = as_global(P.halo_tile);
       // The ids, then the distances: every load unconditional at a clamped index, so that all of a level are in flight together
       // (a load under `if (i < nv)` is waited for before the next branch: six ids and six distances were twelve round trips).
-      const uint32_t nvm = nv ? nv - 1u : 0u, nhm = nh ? nh - 1u : 0u;   // (an empty halo reads the slack behind the array: dev_upload)
+      const uint32_t nvm = nv ? nv - 1u : 0u, nhm = nh ? nh - 1u : 0u;   // (an empty halo reads the slack behind the array: DevBuf::upload)
       uint32_t gi[VPT];
 #pragma unroll
       for (int k2 = 0; k2 < VPT; ++k2) gi[k2] = g_verts[v0 + min((uint32_t)tid + k2 * kTileBlock, nvm)];

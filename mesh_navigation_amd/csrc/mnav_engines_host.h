@@ -28,9 +28,9 @@ int run_plans(mnav_ctx* ctx, uint32_t n, const std::vector<PlanIn>& in, double o
     Plan& P = hp[i];
     memset(&P, 0, sizeof(P));
     P.planner = PLANNER; P.V = ctx->V;
-    P.row_ptr = ctx->d_row_ptr; P.nbr = ctx->d_nbr; P.crn_ptr = ctx->d_crn_ptr; P.crn = ctx->d_crn; P.blocked = ctx->d_blocked;
-    P.dist = s.dist; P.tkey = cvp ? s.tkey : nullptr; P.pred = s.pred; P.dirn = s.dirn; P.cutf = s.cutf; P.stamp = s.stamp; P.dirty = s.dirty;
-    P.list[0] = s.list0; P.list[1] = s.list1; P.wlist[0] = s.wlist0; P.wlist[1] = s.wlist1; P.wstamp = s.wstamp; P.cap = ctx->V; P.ctl = s.ctl; P.cnt = s.cnt;
+    P.row_ptr = ctx->d_row_ptr.get(); P.nbr = ctx->d_nbr.get(); P.crn_ptr = ctx->d_crn_ptr.get(); P.crn = ctx->d_crn.get(); P.blocked = ctx->d_blocked.get();
+    P.dist = s.dist.get(); P.tkey = cvp ? s.tkey.get() : nullptr; P.pred = s.pred.get(); P.dirn = s.dirn.get(); P.cutf = s.cutf.get(); P.stamp = s.stamp.get(); P.dirty = s.dirty.get();
+    P.list[0] = s.list0.get(); P.list[1] = s.list1.get(); P.wlist[0] = s.wlist0.get(); P.wlist[1] = s.wlist1.get(); P.wstamp = s.wstamp.get(); P.cap = ctx->V; P.ctl = s.ctl; P.cnt = s.cnt.get();
     P.delta = delta; P.offset = offset; P.max_steps = ctx->max_steps; P.walk_max = ctx->walk_max; P.descend_max = ctx->descend_max;
     for (int k = 0; k < 3; ++k) {
       P.seed[k] = in[i].seed[k]; P.target[k] = in[i].target[k]; P.seed_d[k] = in[i].seed_d[k];
@@ -67,15 +67,14 @@ int run_plans(mnav_ctx* ctx, uint32_t n, const std::vector<PlanIn>& in, double o
     if (opt_set(ctx->opt.cvp_groups)) ctx->wide_groups = std::min(std::max(1u, opt_u32(ctx->opt.cvp_groups, 1u)), (uint32_t)kWideGroupsMax);
     if (ctx->wide_groups > n) ctx->wide_groups = 1;
     if (ctx->wide_cap < n + 1u) {
-      (void)hipFree(ctx->d_wide_prefix); ctx->d_wide_prefix = nullptr;
-      HIPCHK(hipMalloc((void**)&ctx->d_wide_prefix, 4 * (size_t)(2u * n + 2u * kWideGroupsMax + 8u)));   // per group: prefix sums [ng + 1], then the list of plans in a band cut [ng]
+      HIPCHK(ctx->d_wide_prefix.alloc(4 * (size_t)(2u * n + 2u * kWideGroupsMax + 8u)));   // per group: prefix sums [ng + 1], then the list of plans in a band cut [ng]
       ctx->wide_cap = n + 1u;
       drop_graphs(ctx);                                               // (captured with the old pointer)
     }
-    if (!ctx->d_wide_sched) HIPCHK(hipMalloc((void**)&ctx->d_wide_sched, kWideGroupsMax * sizeof(WideSched)));
+    if (!ctx->d_wide_sched) HIPCHK(ctx->d_wide_sched.alloc(kWideGroupsMax * sizeof(WideSched)));
     if (!ctx->stream_g[1]) {
-      for (uint32_t g = 1; g < kWideGroupsMax; ++g) HIPCHK(hipStreamCreateWithFlags(&ctx->stream_g[g], hipStreamNonBlocking));
-      for (auto& e : ctx->ev_fork) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+      for (uint32_t g = 1; g < kWideGroupsMax; ++g) HIPCHK(hipStreamCreateWithFlags(ctx->stream_g[g].out(), hipStreamNonBlocking));
+      for (auto& e : ctx->ev_fork) HIPCHK(hipEventCreateWithFlags(e.out(), hipEventDisableTiming));
     }
   }
   uint32_t launches = 0;
@@ -119,29 +118,23 @@ int ensure_tile_state(mnav_ctx* ctx, uint32_t n)
   for (uint32_t i = 0; i < n; ++i) {
     Slot& s = ctx->slots[i];
     if (!s.tile_ready) {
-      HIPCHK(hipMalloc((void**)&s.tpend0, 4 * nt)); HIPCHK(hipMalloc((void**)&s.tpend1, 4 * nt));
-      HIPCHK(hipMalloc((void**)&s.tlast, 4 * nt));
-      HIPCHK(hipMalloc((void**)&s.tcnt, 3 * sizeof(TCnt)));
+      HIPCHK(alloc_group(s.tpend0, 4 * nt, s.tpend1, 4 * nt, s.tlast, 4 * nt, s.tcnt, 3 * sizeof(TCnt)));
       s.tile_ready = true;
     }
   }
   if (ctx->tctl_pool_cap < n) {
-    if (ctx->d_tctl_pool) (void)hipFree(ctx->d_tctl_pool);
-    ctx->d_tctl_pool = nullptr;
-    HIPCHK(hipMalloc((void**)&ctx->d_tctl_pool, 2 * sizeof(TCtl) * n));
+    HIPCHK(ctx->d_tctl_pool.alloc(2 * sizeof(TCtl) * n));
     ctx->tctl_pool_cap = n;
   }
   for (uint32_t i = 0; i < n; ++i) ctx->slots[i].tctl = ctx->d_tctl_pool + 2 * i;
   if (ctx->tplans_cap < n) {
-    if (ctx->d_tplans) (void)hipFree(ctx->d_tplans);
-    if (ctx->h_tctl) (void)hipHostFree(ctx->h_tctl);
-    ctx->d_tplans = nullptr; ctx->h_tctl = nullptr;
+    ctx->d_tplans.reset(); ctx->h_tctl.reset();
     drop_graphs(ctx);
-    HIPCHK(hipMalloc((void**)&ctx->d_tplans, sizeof(TilePlan) * n));
-    HIPCHK(hipHostMalloc((void**)&ctx->h_tctl, sizeof(TCtl) * 2 * n, hipHostMallocDefault));
+    HIPCHK(ctx->d_tplans.alloc(sizeof(TilePlan) * n));
+    HIPCHK(ctx->h_tctl.alloc(sizeof(TCtl) * 2 * n));
     ctx->tplans_cap = n;
   }
-  if (!ctx->d_mismatch) HIPCHK(hipMalloc((void**)&ctx->d_mismatch, 4));
+  if (!ctx->d_mismatch) HIPCHK(ctx->d_mismatch.alloc(4));
   return 0;
 }
 
@@ -192,10 +185,10 @@ int run_tile_chunk(mnav_ctx* ctx, uint32_t n, uint32_t G)
     const int rc = launch_tile_rounds(ctx, n, G, kTileChunk);
     hipError_t e = hipStreamEndCapture(ctx->stream, &g);
     if (rc != 0 || e != hipSuccess) { ctx->err = "graph capture failed"; return -1; }
-    hipGraphExec_t ge = nullptr;
-    HIPCHK(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
+    GraphExec ge;
+    HIPCHK(hipGraphInstantiate(ge.out(), g, nullptr, nullptr, 0));
     (void)hipGraphDestroy(g);
-    it = ctx->graphs.emplace(key, ge).first;
+    it = ctx->graphs.emplace(key, std::move(ge)).first;
   }
   HIPCHK(hipGraphLaunch(it->second, ctx->stream));
   return 0;
@@ -217,9 +210,9 @@ int run_dijkstra_tiled(mnav_ctx* ctx, uint32_t n, const std::vector<PlanIn>& in,
     Plan& P = hp[i];
     memset(&P, 0, sizeof(P));
     P.planner = kPlannerDijkstra; P.V = ctx->V;
-    P.row_ptr = ctx->d_row_ptr; P.nbr = ctx->d_nbr; P.crn_ptr = ctx->d_crn_ptr; P.crn = ctx->d_crn; P.blocked = ctx->d_blocked;
-    P.dist = s.dist; P.tkey = nullptr; P.pred = s.pred; P.dirn = s.dirn; P.cutf = s.cutf; P.stamp = s.stamp; P.dirty = s.dirty;
-    P.list[0] = s.list0; P.list[1] = s.list1; P.wlist[0] = s.wlist0; P.wlist[1] = s.wlist1; P.wstamp = s.wstamp; P.cap = ctx->V; P.ctl = s.ctl; P.cnt = s.cnt;
+    P.row_ptr = ctx->d_row_ptr.get(); P.nbr = ctx->d_nbr.get(); P.crn_ptr = ctx->d_crn_ptr.get(); P.crn = ctx->d_crn.get(); P.blocked = ctx->d_blocked.get();
+    P.dist = s.dist.get(); P.tkey = nullptr; P.pred = s.pred.get(); P.dirn = s.dirn.get(); P.cutf = s.cutf.get(); P.stamp = s.stamp.get(); P.dirty = s.dirty.get();
+    P.list[0] = s.list0.get(); P.list[1] = s.list1.get(); P.wlist[0] = s.wlist0.get(); P.wlist[1] = s.wlist1.get(); P.wstamp = s.wstamp.get(); P.cap = ctx->V; P.ctl = s.ctl; P.cnt = s.cnt.get();
     P.delta = 0.f; P.offset = offset; P.max_steps = 0x7FFFFFF0u; P.walk_max = kKeyWalkMax; P.descend_max = kDescendWalkMax;
     for (int k = 0; k < 3; ++k) {
       P.seed[k] = in[i].seed[k]; P.target[k] = in[i].target[k]; P.seed_d[k] = 0.f; P.seed_expands[k] = 1; P.target_expands[k] = 1;
@@ -229,9 +222,9 @@ int run_dijkstra_tiled(mnav_ctx* ctx, uint32_t n, const std::vector<PlanIn>& in,
     TilePlan& T = tp[i];
     memset(&T, 0, sizeof(T));
     T.V = ctx->V; T.ntiles = M.ntiles;
-    T.vptr = ctx->d_t_vptr; T.verts = ctx->d_t_verts; T.hptr = ctx->d_t_hptr; T.halo_verts = ctx->d_t_halo_verts;
-    T.halo_tile = ctx->d_t_halo_tile; T.eptr = ctx->d_t_eptr; T.rptr = ctx->d_t_rptr; T.rowptr = ctx->d_t_rowptr; T.col = ctx->d_t_col; T.tw = ctx->d_t_tw;
-    T.dist = s.dist; T.pend[0] = s.tpend0; T.pend[1] = s.tpend1; T.tlast = s.tlast; T.ctl = s.tctl; T.cnt = s.tcnt;
+    T.vptr = ctx->d_t_vptr.get(); T.verts = ctx->d_t_verts.get(); T.hptr = ctx->d_t_hptr.get(); T.halo_verts = ctx->d_t_halo_verts.get();
+    T.halo_tile = ctx->d_t_halo_tile.get(); T.eptr = ctx->d_t_eptr.get(); T.rptr = ctx->d_t_rptr.get(); T.rowptr = ctx->d_t_rowptr.get(); T.col = ctx->d_t_col.get(); T.tw = ctx->d_t_tw.get();
+    T.dist = s.dist.get(); T.pend[0] = s.tpend0.get(); T.pend[1] = s.tpend1.get(); T.tlast = s.tlast.get(); T.ctl = s.tctl; T.cnt = s.tcnt.get();
     T.seed = in[i].seed[0]; T.target = in[i].target[0]; T.offset = offset; T.max_rounds = ctx->max_steps;
     T.band = ctx->tile_band_user > 0.f ? ctx->tile_band_user : ctx->tile_band_auto * ctx->rounds_band_mult;
     T.max_nv = M.max_nv; T.max_nh = M.max_nh; T.max_ne = M.max_ne;
@@ -312,9 +305,9 @@ int run_dijkstra_async(mnav_ctx* ctx, uint32_t n, const std::vector<PlanIn>& in,
     Plan& P = hp[i];
     memset(&P, 0, sizeof(P));
     P.planner = kPlannerDijkstra; P.V = ctx->V;
-    P.row_ptr = ctx->d_row_ptr; P.nbr = ctx->d_nbr; P.crn_ptr = ctx->d_crn_ptr; P.crn = ctx->d_crn; P.blocked = ctx->d_blocked;
-    P.dist = s.dist; P.tkey = nullptr; P.pred = s.pred; P.dirn = s.dirn; P.cutf = s.cutf; P.stamp = s.stamp; P.dirty = s.dirty;
-    P.list[0] = s.list0; P.list[1] = s.list1; P.wlist[0] = s.wlist0; P.wlist[1] = s.wlist1; P.wstamp = s.wstamp; P.cap = ctx->V; P.ctl = s.ctl; P.cnt = s.cnt;
+    P.row_ptr = ctx->d_row_ptr.get(); P.nbr = ctx->d_nbr.get(); P.crn_ptr = ctx->d_crn_ptr.get(); P.crn = ctx->d_crn.get(); P.blocked = ctx->d_blocked.get();
+    P.dist = s.dist.get(); P.tkey = nullptr; P.pred = s.pred.get(); P.dirn = s.dirn.get(); P.cutf = s.cutf.get(); P.stamp = s.stamp.get(); P.dirty = s.dirty.get();
+    P.list[0] = s.list0.get(); P.list[1] = s.list1.get(); P.wlist[0] = s.wlist0.get(); P.wlist[1] = s.wlist1.get(); P.wstamp = s.wstamp.get(); P.cap = ctx->V; P.ctl = s.ctl; P.cnt = s.cnt.get();
     P.delta = 0.f; P.offset = offset; P.max_steps = ctx->max_steps;
     for (int k = 0; k < 3; ++k) { P.seed[k] = in[i].seed[k]; P.target[k] = in[i].target[k]; P.seed_d[k] = 0.f; P.seed_expands[k] = 1; P.target_expands[k] = 1; }
     P.seed_face = kNone;
@@ -322,12 +315,12 @@ int run_dijkstra_async(mnav_ctx* ctx, uint32_t n, const std::vector<PlanIn>& in,
     TilePlan& T = tp[i];
     memset(&T, 0, sizeof(T));
     T.V = ctx->V; T.ntiles = M.ntiles;
-    T.vptr = ctx->d_t_vptr; T.verts = ctx->d_t_verts; T.hptr = ctx->d_t_hptr; T.halo_verts = ctx->d_t_halo_verts;
-    T.halo_tile = ctx->d_t_halo_tile; T.eptr = ctx->d_t_eptr; T.rptr = ctx->d_t_rptr; T.rowptr = ctx->d_t_rowptr; T.col = ctx->d_t_col; T.tw = ctx->d_t_tw;
-    T.dist = s.dist; T.pend[0] = s.tpend0; T.pend[1] = s.tpend1; T.tlast = s.tlast; T.ctl = s.tctl; T.cnt = s.tcnt;
+    T.vptr = ctx->d_t_vptr.get(); T.verts = ctx->d_t_verts.get(); T.hptr = ctx->d_t_hptr.get(); T.halo_verts = ctx->d_t_halo_verts.get();
+    T.halo_tile = ctx->d_t_halo_tile.get(); T.eptr = ctx->d_t_eptr.get(); T.rptr = ctx->d_t_rptr.get(); T.rowptr = ctx->d_t_rowptr.get(); T.col = ctx->d_t_col.get(); T.tw = ctx->d_t_tw.get();
+    T.dist = s.dist.get(); T.pend[0] = s.tpend0.get(); T.pend[1] = s.tpend1.get(); T.tlast = s.tlast.get(); T.ctl = s.tctl; T.cnt = s.tcnt.get();
     T.seed = in[i].seed[0]; T.target = in[i].target[0]; T.offset = offset;
     T.max_rounds = 0x7FFFFFF0u;
-    T.cancel = ctx->d_cancel;
+    T.cancel = ctx->d_cancel.get();
     T.pend1_is_state = 1u;
     // band of the plan in tile widths (<= 0: one band, every solve runs to its tile's fixed point); measured round 5, ms per call at
     // 1 / 8 / 47 / 64 plans on the 1M mesh: 2 widths 7.1 / 11.1 / 20.8 / 25.4, 3: 6.9 / 10.8 / 21.9 / 26.8, 4: 6.8 / 9.9 / 23.2 / 27.7, 6: 7.2 / 10.3 / 25.7 / 31.8, 8: 7.1 / 10.6 / 28.2 / 34.8
@@ -344,16 +337,16 @@ int run_dijkstra_async(mnav_ctx* ctx, uint32_t n, const std::vector<PlanIn>& in,
   const bool ring_forced = opt_set(ctx->opt.async_ring_cap);
   const uint32_t cap1 = ring_forced ? std::max(2u, opt_u32(ctx->opt.async_ring_cap, 0u)) : std::max(1024u, std::min(M.ntiles * 16u, 1u << 24));
   if (ctx->ring_words < (size_t)cap1 * n) {
-    (void)hipFree(ctx->d_ring); ctx->d_ring = nullptr; ctx->ring_words = 0;
-    HIPCHK(hipMalloc((void**)&ctx->d_ring, 4 * (size_t)cap1 * n));
+    ctx->ring_words = 0;
+    HIPCHK(ctx->d_ring.alloc(4 * (size_t)cap1 * n));
     ctx->ring_words = (size_t)cap1 * n;
   }
   ctx->ring_cap = cap1;
   {
     const size_t per_plan = 2u * (size_t)aq::kParkedLists * M.ntiles;   // the two parked lists of a plan
     if (ctx->parked_words < per_plan * n) {
-      (void)hipFree(ctx->d_parked); ctx->d_parked = nullptr; ctx->parked_words = 0;
-      HIPCHK(hipMalloc((void**)&ctx->d_parked, 4 * per_plan * n));
+      ctx->parked_words = 0;
+      HIPCHK(ctx->d_parked.alloc(4 * per_plan * n));
       ctx->parked_words = per_plan * n;
     }
     for (uint32_t i = 0; i < n; ++i) tp[i].parked = ctx->d_parked + per_plan * i;

@@ -115,16 +115,11 @@ enum { kSpilled = 0, kOverflow = 1, kMaxSize = 2, kCounters32 = 4 };
 
 // Per-context state: the device counters, spill lists and scratch; dropped by mnav_upload_mesh and mnav_destroy.
 struct State {
-  uint32_t* cnt = nullptr;                    // kCounters32 words + one 64-bit visit sum
-  uint32_t* list[2] = { nullptr, nullptr };   // spill list / overflow list (V entries each)
-  uint32_t* scratch = nullptr; size_t scratch_words = 0;
+  DevBuf<uint32_t> cnt;                       // kCounters32 words + one 64-bit visit sum
+  DevBuf<uint32_t> list[2];                   // spill list / overflow list (V entries each)
+  DevBuf<uint32_t> scratch; size_t scratch_words = 0;
   uint32_t centres = 0, max_size = 0, spilled = 0; uint64_t visits = 0; float ms = 0.f;
 };
-inline void nb_free(State& s)
-{
-  (void)hipFree(s.cnt); (void)hipFree(s.list[0]); (void)hipFree(s.list[1]); (void)hipFree(s.scratch);
-  s = State{};
-}
 
 struct Mesh {
   const uint32_t* __restrict__ row_ptr; const uint32_t* __restrict__ nbr; const float* __restrict__ xyz; const float* __restrict__ nrm;

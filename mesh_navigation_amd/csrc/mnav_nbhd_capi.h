@@ -10,11 +10,8 @@ static int nbhd_launch(mnav_ctx* ctx, mnav_ctx::Layer& L, const mnav_nb::Mesh& M
   using namespace mnav_nb;
   State& S = ctx->nbhd;
   const uint32_t V = ctx->V;
-  if (!S.cnt) {
-    HIPCHK(hipMalloc((void**)&S.cnt, sizeof(uint32_t) * (kCounters32 + 2)));
-    HIPCHK(hipMalloc((void**)&S.list[0], sizeof(uint32_t) * (V ? V : 1)));
-    HIPCHK(hipMalloc((void**)&S.list[1], sizeof(uint32_t) * (V ? V : 1)));
-  }
+  if (!S.cnt)
+    HIPCHK(alloc_group(S.cnt, sizeof(uint32_t) * (kCounters32 + 2), S.list[0], sizeof(uint32_t) * (V ? V : 1), S.list[1], sizeof(uint32_t) * (V ? V : 1)));
   // LDS passes: all centres with `cap` members per group, then (default only) the spill list with kWideLdsCap; an
   // explicit nbhd_lds_cap makes its pass the only LDS pass (tests reach the global spill path with it)
   const bool wide = !opt_set(ctx->opt.nbhd_lds_cap);
@@ -52,8 +49,8 @@ static int nbhd_launch(mnav_ctx* ctx, mnav_ctx::Layer& L, const mnav_nb::Mesh& M
     const size_t budget = (size_t)64 << 20;                        // words of scratch (256 MiB) shared by the pass's waves
     const uint32_t waves = (uint32_t)std::max<size_t>(1, std::min<size_t>(std::min<size_t>(n, budget / per), 8192));
     if (S.scratch_words < per * waves) {
-      (void)hipFree(S.scratch); S.scratch = nullptr; S.scratch_words = 0;
-      HIPCHK(hipMalloc((void**)&S.scratch, sizeof(uint32_t) * per * waves));
+      S.scratch_words = 0;
+      HIPCHK(S.scratch.alloc(sizeof(uint32_t) * per * waves));
       S.scratch_words = per * waves;
     }
     HIPCHK(hipMemsetAsync(S.cnt + kOverflow, 0, sizeof(uint32_t), ctx->stream));
@@ -100,7 +97,7 @@ static int nbhd_layer(mnav_ctx* ctx, int op, uint32_t layer, double radius, doub
   if (rc) return rc;
   // the slot now holds a neighbourhood layer: no wave distances / vector field of an earlier inflation layer survive
   L.have_vec = false;
-  if (L.dist) { (void)hipFree(L.dist); L.dist = nullptr; }
+  L.dist.reset();
   L.ready = true;
   ctx->nbhd.centres = ctx->V;
   ctx->nbhd.spilled = spilled;

@@ -25,24 +25,17 @@ enum { kKept = 0, kHits, kLethalRays, kOverflow, kChanged, kLethal, kCounters };
 struct Bvh {
   bool valid = false;
   uint32_t F = 0, root = kNone;
-  float4* nodes = nullptr;     // F-1 internal nodes x 4 float4: left box (6 floats), right box (6), left ref, right ref
-  float4* tris = nullptr;      // F leaves in Morton order x 3 float4: a.xyz b.xyz c.xyz, original face id (bits)
-  uint32_t* fvtx = nullptr;    // 3F vertex ids, original face order
-  uint8_t* flags = nullptr;    // V: lethal flags of the current call
-  uint32_t* ids = nullptr;     // V: change list
-  uint32_t* blk = nullptr;     // 3 x blocks: changed per block, lethal per block, exclusive offsets
-  uint32_t* cnt = nullptr;     // kCounters words
-  uint8_t* pts = nullptr; size_t pts_cap = 0;
+  DevBuf<float4> nodes;        // F-1 internal nodes x 4 float4: left box (6 floats), right box (6), left ref, right ref
+  DevBuf<float4> tris;         // F leaves in Morton order x 3 float4: a.xyz b.xyz c.xyz, original face id (bits)
+  DevBuf<uint32_t> fvtx;       // 3F vertex ids, original face order
+  DevBuf<uint8_t> flags;       // V: lethal flags of the current call
+  DevBuf<uint32_t> ids;        // V: change list
+  DevBuf<uint32_t> blk;        // 3 x blocks: changed per block, lethal per block, exclusive offsets
+  DevBuf<uint32_t> cnt;        // kCounters words
+  DevBuf<uint8_t> pts; size_t pts_cap = 0;
   float ms_build = 0.f, ms_cast = 0.f, ms_total = 0.f;
   uint32_t kept = 0, hits = 0, lethal_rays = 0;
 };
-
-inline void bvh_free(Bvh& b)
-{
-  (void)hipFree(b.nodes); (void)hipFree(b.tris); (void)hipFree(b.fvtx); (void)hipFree(b.flags); (void)hipFree(b.ids);
-  (void)hipFree(b.blk); (void)hipFree(b.cnt); (void)hipFree(b.pts);
-  b = Bvh{};
-}
 
 __device__ __forceinline__ uint32_t f2ord(float f)
 {

@@ -9,18 +9,18 @@ static int obstacle_build_bvh(mnav_ctx* ctx)
   Bvh& B = ctx->obs;
   const uint32_t F = ctx->F, V = ctx->V;
   HIPCHK(hipEventRecord(ctx->ev[4], ctx->stream));
-  HIPCHK(hipMalloc((void**)&B.fvtx, sizeof(uint32_t) * 3 * (size_t)(F ? F : 1)));
+  HIPCHK(B.fvtx.alloc(sizeof(uint32_t) * 3 * (size_t)(F ? F : 1)));
   if (F) HIPCHK(hipMemcpyAsync(B.fvtx, ctx->h_faces.data(), sizeof(uint32_t) * 3 * (size_t)F, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMalloc((void**)&B.tris, sizeof(float4) * 3 * (size_t)(F ? F : 1)));
-  HIPCHK(hipMalloc((void**)&B.nodes, sizeof(float4) * 4 * (size_t)(F > 1 ? F - 1 : 1)));
+  HIPCHK(B.tris.alloc(sizeof(float4) * 3 * (size_t)(F ? F : 1)));
+  HIPCHK(B.nodes.alloc(sizeof(float4) * 4 * (size_t)(F > 1 ? F - 1 : 1)));
   if (F) {
-    DevTmp<uint32_t> bnd, keys, keys2, ids, ids2, par_int, par_leaf, arrive;
-    DevTmp<uint8_t> tmp;
-    HIPCHK(hipMalloc(bnd.out(), 6 * sizeof(uint32_t)));
-    HIPCHK(hipMalloc(keys.out(), sizeof(uint32_t) * F)); HIPCHK(hipMalloc(keys2.out(), sizeof(uint32_t) * F));
-    HIPCHK(hipMalloc(ids.out(), sizeof(uint32_t) * F)); HIPCHK(hipMalloc(ids2.out(), sizeof(uint32_t) * F));
-    HIPCHK(hipMalloc(par_int.out(), sizeof(uint32_t) * F)); HIPCHK(hipMalloc(par_leaf.out(), sizeof(uint32_t) * F));
-    HIPCHK(hipMalloc(arrive.out(), sizeof(uint32_t) * F));
+    DevBuf<uint32_t> bnd, keys, keys2, ids, ids2, par_int, par_leaf, arrive;
+    DevBuf<uint8_t> tmp;
+    HIPCHK(bnd.alloc(6 * sizeof(uint32_t)));
+    HIPCHK(keys.alloc(sizeof(uint32_t) * F)); HIPCHK(keys2.alloc(sizeof(uint32_t) * F));
+    HIPCHK(ids.alloc(sizeof(uint32_t) * F)); HIPCHK(ids2.alloc(sizeof(uint32_t) * F));
+    HIPCHK(par_int.alloc(sizeof(uint32_t) * F)); HIPCHK(par_leaf.alloc(sizeof(uint32_t) * F));
+    HIPCHK(arrive.alloc(sizeof(uint32_t) * F));
     HIPCHK(hipMemsetAsync(bnd, 0xFF, 3 * sizeof(uint32_t), ctx->stream));
     HIPCHK(hipMemsetAsync((uint32_t*)bnd + 3, 0, 3 * sizeof(uint32_t), ctx->stream));
     HIPCHK(hipMemsetAsync(arrive, 0, sizeof(uint32_t) * F, ctx->stream));
@@ -33,7 +33,7 @@ static int obstacle_build_bvh(mnav_ctx* ctx)
     HIPCHK(hipGetLastError());
     size_t tmp_bytes = 0;
     HIPCHK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, (uint32_t*)keys, (uint32_t*)keys2, (uint32_t*)ids, (uint32_t*)ids2, F, 0, 30, ctx->stream));
-    HIPCHK(hipMalloc(tmp.out(), tmp_bytes ? tmp_bytes : 1));
+    HIPCHK(tmp.alloc(tmp_bytes ? tmp_bytes : 1));
     HIPCHK(rocprim::radix_sort_pairs((void*)tmp, tmp_bytes, (uint32_t*)keys, (uint32_t*)keys2, (uint32_t*)ids, (uint32_t*)ids2, F, 0, 30, ctx->stream));
     if (F > 1)
       hipLaunchKernelGGL(k_obs_hierarchy, dim3((F - 1 + 255) / 256), dim3(256), 0, ctx->stream, F, keys2, B.nodes, par_int, par_leaf);
@@ -68,18 +68,15 @@ int mnav_layer_obstacle(mnav_ctx* ctx, uint32_t layer, uint32_t n_points, const 
   mnav_ctx::Layer& L = ctx->layers[layer];
   Bvh& B = ctx->obs;
   const uint32_t V = ctx->V;
-  if (!B.valid && obstacle_build_bvh(ctx)) { bvh_free(B); return -1; }
+  if (!B.valid && obstacle_build_bvh(ctx)) { B = Bvh{}; return -1; }
   const uint32_t nblk = (uint32_t)(((size_t)V + kOutBlock * kOutPer - 1) / (kOutBlock * kOutPer));
-  if (!B.flags) {
-    HIPCHK(hipMalloc((void**)&B.flags, V ? V : 1));
-    HIPCHK(hipMalloc((void**)&B.ids, sizeof(uint32_t) * (V ? V : 1)));
-    HIPCHK(hipMalloc((void**)&B.blk, sizeof(uint32_t) * 3 * (nblk ? nblk : 1)));
-    HIPCHK(hipMalloc((void**)&B.cnt, sizeof(uint32_t) * kCounters));
-  }
+  if (!B.flags)
+    HIPCHK(alloc_group(B.flags, V ? V : 1, B.ids, sizeof(uint32_t) * (V ? V : 1), B.blk, sizeof(uint32_t) * 3 * (nblk ? nblk : 1),
+                       B.cnt, sizeof(uint32_t) * kCounters));
   const size_t bytes = (size_t)n_points * point_step;
   if (bytes > B.pts_cap) {
-    (void)hipFree(B.pts); B.pts = nullptr; B.pts_cap = 0;
-    HIPCHK(hipMalloc((void**)&B.pts, bytes));
+    B.pts_cap = 0;
+    HIPCHK(B.pts.alloc(bytes));
     B.pts_cap = bytes;
   }
   CastArgs A{};
@@ -117,7 +114,7 @@ int mnav_layer_obstacle(mnav_ctx* ctx, uint32_t layer, uint32_t n_points, const 
   }
   // the slot now holds an obstacle layer: no wave distances / vector field of an earlier inflation layer survive
   L.have_vec = false;
-  if (L.dist) { (void)hipFree(L.dist); L.dist = nullptr; }
+  L.dist.reset();
   L.ready = true;
   B.kept = c[kKept]; B.hits = c[kHits]; B.lethal_rays = c[kLethalRays];
   B.ms_cast = ev_ms(ctx->ev[1], ctx->ev[2]);

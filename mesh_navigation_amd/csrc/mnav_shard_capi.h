@@ -48,15 +48,14 @@ int mnav_shard_setup(mnav_ctx* ctx, uint32_t rank, uint32_t world)
       }
     if (pass == 0) { for (uint32_t i = 0; i < S.n_iface; ++i) wptr[i + 1] += wptr[i]; wtile.assign(wptr[S.n_iface] ? wptr[S.n_iface] : 1, 0); }
   }
-  if (dev_upload(ctx, &S.d_iface_vert, S.iface_vert.data(), S.iface_vert.size())) return -1;
-  if (dev_upload(ctx, &S.d_iface_owner, owner.data(), S.n_iface)) return -1;
-  if (dev_upload(ctx, &S.d_wake_ptr, wptr.data(), wptr.size())) return -1;
-  if (dev_upload(ctx, &S.d_wake_tile, wtile.data(), wtile.size())) return -1;
-  if (!S.d_changed) HIPCHK(hipMalloc((void**)&S.d_changed, 64));
-  if (!S.d_minpend) HIPCHK(hipMalloc((void**)&S.d_minpend, 64));
+  HIPCHK(S.d_iface_vert.upload(ctx->stream, S.iface_vert.data(), S.iface_vert.size()));
+  HIPCHK(S.d_iface_owner.upload(ctx->stream, owner.data(), S.n_iface));
+  HIPCHK(S.d_wake_ptr.upload(ctx->stream, wptr.data(), wptr.size()));
+  HIPCHK(S.d_wake_tile.upload(ctx->stream, wtile.data(), wtile.size()));
+  if (!S.d_changed) HIPCHK(S.d_changed.alloc(64));
+  if (!S.d_minpend) HIPCHK(S.d_minpend.alloc(64));
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  for (auto& kv : S.graphs) (void)hipGraphExecDestroy(kv.second);   // the captured exchanges hold the old lists
-  S.graphs.clear();
+  S.graphs.clear();                                                   // the captured exchanges hold the old lists
   S.ready = true; S.active = false;
   return (int)S.n_iface + 1;                                          // floats in the exchange buffer (interface + robot vertex)
 }
@@ -100,16 +99,15 @@ int mnav_shard_setup_partition(mnav_ctx* ctx, uint32_t n_exchange, const uint32_
     if (pass == 0) { for (uint32_t i = 0; i < n_exchange; ++i) wptr[i + 1] += wptr[i]; wtile.assign(wptr[n_exchange] ? wptr[n_exchange] : 1, 0); }
   }
   std::vector<uint8_t> zero(n_exchange ? n_exchange : 1, 0);
-  if (dev_upload(ctx, &S.d_iface_vert, S.iface_vert.data(), S.iface_vert.size())) return -1;
-  if (dev_upload(ctx, &S.d_iface_owner, zero.data(), n_exchange)) return -1;
-  if (dev_upload(ctx, &S.d_wake_ptr, wptr.data(), wptr.size())) return -1;
-  if (dev_upload(ctx, &S.d_wake_tile, wtile.data(), wtile.size())) return -1;
-  if (dev_upload(ctx, &S.d_owned, owned, (size_t)ctx->V)) return -1;
-  if (!S.d_changed) HIPCHK(hipMalloc((void**)&S.d_changed, 64));
-  if (!S.d_minpend) HIPCHK(hipMalloc((void**)&S.d_minpend, 64));
+  HIPCHK(S.d_iface_vert.upload(ctx->stream, S.iface_vert.data(), S.iface_vert.size()));
+  HIPCHK(S.d_iface_owner.upload(ctx->stream, zero.data(), n_exchange));
+  HIPCHK(S.d_wake_ptr.upload(ctx->stream, wptr.data(), wptr.size()));
+  HIPCHK(S.d_wake_tile.upload(ctx->stream, wtile.data(), wtile.size()));
+  HIPCHK(S.d_owned.upload(ctx->stream, owned, (size_t)ctx->V));
+  if (!S.d_changed) HIPCHK(S.d_changed.alloc(64));
+  if (!S.d_minpend) HIPCHK(S.d_minpend.alloc(64));
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  for (auto& kv : S.graphs) (void)hipGraphExecDestroy(kv.second);   // the captured exchanges hold the old lists
-  S.graphs.clear();
+  S.graphs.clear();                                                   // the captured exchanges hold the old lists
   S.ready = true; S.active = false;
   return (int)S.n_iface + 1;                                          // floats in the exchange buffer (interface + robot vertex)
 }
@@ -117,8 +115,19 @@ int mnav_shard_setup_partition(mnav_ctx* ctx, uint32_t n_exchange, const uint32_
 uint64_t mnav_device_bytes(const mnav_ctx* ctx)
 {
   if (!ctx) return 0;
-  uint64_t n = 0;
-  for (const auto& kv : ctx->alloc_bytes) n += kv.second;             // mesh tables, tiles, costs, shard lists (dev_upload)
+  // the buffers filled by upload(): mesh tables (with the face rows of the back-tracking walk), tiles, costs, edge distances,
+  // shard lists and the tile-batch engine's streams
+  const auto bytes = [](const auto&... b) { return (uint64_t{ 0 } + ... + (uint64_t)b.bytes()); };
+  const auto& S = ctx->shard;
+  const TbState& B = ctx->tb;
+  uint64_t n = bytes(ctx->d_row_ptr, ctx->d_nbr_u, ctx->d_nbr_e, ctx->d_crn_ptr, ctx->d_edge_vtx, ctx->d_crn_walk, ctx->d_crn_idx, ctx->d_xyz,
+                     ctx->d_nrm, ctx->d_faces, ctx->d_vf_ptr, ctx->d_vf) +
+               bytes(ctx->d_t_vptr, ctx->d_t_verts, ctx->d_t_hptr, ctx->d_t_halo_verts, ctx->d_t_halo_tile, ctx->d_t_eptr, ctx->d_t_rptr,
+                     ctx->d_t_rowptr, ctx->d_t_col, ctx->d_t_src, ctx->d_vert_tile, ctx->d_t_tw) +
+               bytes(ctx->d_cost, ctx->d_w, ctx->d_invalid, ctx->d_edge_dist) +
+               bytes(S.d_iface_vert, S.d_iface_owner, S.d_wake_ptr, S.d_wake_tile, S.d_owned) +
+               bytes(B.d_tiles, B.d_stream, B.d_wsrc, B.d_exps, B.d_vstream, B.d_vwsrc, B.d_vtile, B.d_vgroups, B.d_vexps, B.d_vaddr,
+                     B.d_vert_tile, B.d_verts, B.d_fin_src, B.d_fin_wsrc, B.d_fin_ovf, B.d_fin_ovf_wsrc, B.d_ghost_gid, B.d_fin_order);
   const uint64_t V = ctx->V ? ctx->V : 1;
   for (const Slot& s : ctx->slots) {                                  // per-plan state (ensure_slots, ensure_tile_state)
     n += 8 * V;
@@ -180,17 +189,17 @@ int mnav_shard_begin(mnav_ctx* ctx, uint32_t seed_vertex, uint32_t target_vertex
   Slot& s = ctx->slots[0];
   Plan P; memset(&P, 0, sizeof(P));
   P.planner = kPlannerDijkstra; P.V = ctx->V;
-  P.row_ptr = ctx->d_row_ptr; P.nbr = ctx->d_nbr; P.crn_ptr = ctx->d_crn_ptr; P.crn = ctx->d_crn; P.blocked = ctx->d_blocked;
-  P.dist = s.dist; P.pred = s.pred; P.dirn = s.dirn; P.cutf = s.cutf; P.stamp = s.stamp; P.dirty = s.dirty;
-  P.list[0] = s.list0; P.list[1] = s.list1; P.wlist[0] = s.wlist0; P.wlist[1] = s.wlist1; P.wstamp = s.wstamp; P.cap = ctx->V; P.ctl = s.ctl; P.cnt = s.cnt;
+  P.row_ptr = ctx->d_row_ptr.get(); P.nbr = ctx->d_nbr.get(); P.crn_ptr = ctx->d_crn_ptr.get(); P.crn = ctx->d_crn.get(); P.blocked = ctx->d_blocked.get();
+  P.dist = s.dist.get(); P.pred = s.pred.get(); P.dirn = s.dirn.get(); P.cutf = s.cutf.get(); P.stamp = s.stamp.get(); P.dirty = s.dirty.get();
+  P.list[0] = s.list0.get(); P.list[1] = s.list1.get(); P.wlist[0] = s.wlist0.get(); P.wlist[1] = s.wlist1.get(); P.wstamp = s.wstamp.get(); P.cap = ctx->V; P.ctl = s.ctl; P.cnt = s.cnt.get();
   P.offset = goal_dist_offset; P.goal_tie1 = goal_tie1; P.max_steps = 0x7FFFFFF0u; P.walk_max = kKeyWalkMax; P.descend_max = kDescendWalkMax;
   for (int k = 0; k < 3; ++k) { P.seed[k] = kNone; P.target[k] = kNone; P.seed_expands[k] = 1; P.target_expands[k] = 1; }
   P.seed[0] = seed_vertex; P.target[0] = target_vertex; P.seed_face = kNone;
   TilePlan T; memset(&T, 0, sizeof(T));
   T.V = ctx->V; T.ntiles = M.ntiles;
-  T.vptr = ctx->d_t_vptr; T.verts = ctx->d_t_verts; T.hptr = ctx->d_t_hptr; T.halo_verts = ctx->d_t_halo_verts;
-  T.halo_tile = ctx->d_t_halo_tile; T.eptr = ctx->d_t_eptr; T.rptr = ctx->d_t_rptr; T.rowptr = ctx->d_t_rowptr; T.col = ctx->d_t_col; T.tw = ctx->d_t_tw;
-  T.dist = s.dist; T.pend[0] = s.tpend0; T.pend[1] = s.tpend1; T.tlast = s.tlast; T.ctl = s.tctl; T.cnt = s.tcnt;
+  T.vptr = ctx->d_t_vptr.get(); T.verts = ctx->d_t_verts.get(); T.hptr = ctx->d_t_hptr.get(); T.halo_verts = ctx->d_t_halo_verts.get();
+  T.halo_tile = ctx->d_t_halo_tile.get(); T.eptr = ctx->d_t_eptr.get(); T.rptr = ctx->d_t_rptr.get(); T.rowptr = ctx->d_t_rowptr.get(); T.col = ctx->d_t_col.get(); T.tw = ctx->d_t_tw.get();
+  T.dist = s.dist.get(); T.pend[0] = s.tpend0.get(); T.pend[1] = s.tpend1.get(); T.tlast = s.tlast.get(); T.ctl = s.tctl; T.cnt = s.tcnt.get();
   T.seed = seed_vertex; T.target = target_vertex; T.offset = goal_dist_offset; T.max_rounds = 0x7FFFFFF0u;
   T.band = ctx->tile_band_user > 0.f ? ctx->tile_band_user : ctx->tile_band_auto * ctx->rounds_band_mult;
   T.max_nv = M.max_nv; T.max_nh = M.max_nh; T.max_ne = M.max_ne;
@@ -261,8 +270,8 @@ int mnav_shard_apply(mnav_ctx* ctx, const float* iface_buf_dev, float* local_min
 // changes nothing).
 static int shard_link(mnav_ctx* ctx, hipStream_t caller, bool in)
 {
-  hipEvent_t& e = ctx->ev_link[in ? 0 : 1];
-  if (!e && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { ctx->err = "event creation failed"; return -1; }
+  Event& e = ctx->ev_link[in ? 0 : 1];
+  if (!e && hipEventCreateWithFlags(e.out(), hipEventDisableTiming) != hipSuccess) { ctx->err = "event creation failed"; return -1; }
   if (in) { HIPCHK(hipEventRecord(e, caller)); HIPCHK(hipStreamWaitEvent(ctx->stream, e, 0)); }
   else { HIPCHK(hipEventRecord(e, ctx->stream)); HIPCHK(hipStreamWaitEvent(caller, e, 0)); }
   return 0;
@@ -285,10 +294,10 @@ static int shard_replay(mnav_ctx* ctx, const std::array<uint64_t, 3>& key, const
     const int rc = enqueue();
     const hipError_t e = hipStreamEndCapture(ctx->stream, &g);
     if (rc != 0 || e != hipSuccess) { ctx->err = "graph capture failed"; return -1; }
-    hipGraphExec_t ge = nullptr;
-    HIPCHK(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
+    GraphExec ge;
+    HIPCHK(hipGraphInstantiate(ge.out(), g, nullptr, nullptr, 0));
     (void)hipGraphDestroy(g);
-    it = S.graphs.emplace(key, ge).first;
+    it = S.graphs.emplace(key, std::move(ge)).first;
   }
   HIPCHK(hipGraphLaunch(it->second, ctx->stream));
   return 0;
@@ -383,8 +392,8 @@ int mnav_shard_walk(mnav_ctx* ctx, uint32_t start_vertex, uint32_t seed_vertex, 
   if (hipSetDevice(ctx->device) != hipSuccess) return -1;
   auto& S = ctx->shard;
   if (S.walk_cap < cap + 3u) {
-    (void)hipFree(S.d_walk); S.d_walk = nullptr; S.walk_cap = 0;
-    HIPCHK(hipMalloc((void**)&S.d_walk, 4 * (size_t)(cap + 3u)));
+    S.walk_cap = 0;
+    HIPCHK(S.d_walk.alloc(4 * (size_t)(cap + 3u)));
     S.walk_cap = cap + 3u;
   }
   hipLaunchKernelGGL(k_shard_walk, dim3(1), dim3(64), 0, ctx->stream, ctx->slots[0].pred, S.partition ? S.d_owned : nullptr, start_vertex, seed_vertex, cap, S.d_walk);

@@ -884,34 +884,43 @@ __global__ __launch_bounds__(kBlock) void k_popped(const float* __restrict__ dis
   for (uint32_t v = blockIdx.x * kBlock + threadIdx.x; v < V; v += stride) { const float d = dist[v]; out[v] = (d <= goal_dist) ? d : inf_f(); }
 }
 
-// host-side state of the engine (device arrays of the mesh-dependent streams, and of the running batch)
-struct TbState {
+// host-side state of the engine: the mesh-dependent streams (tb_build; dropped by tb_free) ...
+struct TbTables {
   bool built = false, w_valid = false;
-  uint32_t T = 120, ntiles = 0, max_nh = 0;   // 120 rows x 256 B + staging = 31 232 B of LDS: five waves per CU (128 rows: four)
+  uint32_t ntiles = 0, max_nh = 0;
   uint64_t S = 0;                       // words per plan
   size_t nrec = 0, nexp = 0;
   std::vector<uint32_t> vert_tile;      // host copy: plans are ordered by the tile of their wave source
-  uint32_t* d_verts = nullptr;          // tile order -> vertex id
-  TbTile* d_tiles = nullptr; uint32_t* d_stream = nullptr; uint32_t* d_wsrc = nullptr; TbExp* d_exps = nullptr;
-  uint32_t *d_vstream = nullptr, *d_vwsrc = nullptr, *d_vtile = nullptr, *d_vgroups = nullptr; TbvExp* d_vexps = nullptr; size_t nvrec = 0;   // the streams in the V layout (k_tbv_solve, mnav_tbv.h)
-  int kernel = 0;                       // solve kernel of the running batch: 0 = k_tb_solve_q (quarters, distances in LDS), 1 = k_tbv_solve (waves, distances in registers)
-  uint2* d_vaddr = nullptr; uint32_t* d_vert_tile = nullptr;
+  DevBuf<uint32_t> d_verts;             // tile order -> vertex id
+  DevBuf<TbTile> d_tiles; DevBuf<uint32_t> d_stream, d_wsrc; DevBuf<TbExp> d_exps;
+  DevBuf<uint32_t> d_vstream, d_vwsrc, d_vtile, d_vgroups; DevBuf<TbvExp> d_vexps; size_t nvrec = 0;   // the streams in the V layout (k_tbv_solve, mnav_tbv.h)
+  DevBuf<uint2> d_vaddr; DevBuf<uint32_t> d_vert_tile;
   // finalize tables (mnav_tb_finalize.h)
-  uint16_t* d_fin_src = nullptr; uint32_t* d_fin_wsrc = nullptr; float* d_fin_w = nullptr; TbFinOvf* d_fin_ovf = nullptr; uint32_t* d_fin_ovf_wsrc = nullptr; float* d_fin_ovf_w = nullptr;
-  uint32_t* d_ghost_gid = nullptr; uint32_t* d_fin_order = nullptr; unsigned long long* wstat = nullptr; struct FinRec* d_recs = nullptr; size_t fin_n = 0, fin_novf = 0; bool fin_w_valid = false; uint32_t max_sl = 0;
-  // batch state, sized for cap_np plans
+  DevBuf<uint16_t> d_fin_src; DevBuf<uint32_t> d_fin_wsrc; DevBuf<float> d_fin_w; DevBuf<TbFinOvf> d_fin_ovf; DevBuf<uint32_t> d_fin_ovf_wsrc; DevBuf<float> d_fin_ovf_w;
+  DevBuf<uint32_t> d_ghost_gid, d_fin_order; size_t fin_n = 0, fin_novf = 0; bool fin_w_valid = false; uint32_t max_sl = 0;
+};
+
+// ... and the batch state, sized for cap_np plans (tb_ensure_batch; dropped by tb_free_batch)
+struct TbBatch {
   uint32_t cap_np = 0;
-  float* D = nullptr; uint32_t* pend = nullptr; uint8_t* pflag = nullptr; uint32_t* pairs = nullptr; uint16_t* bucket = nullptr; uint32_t* bcnt = nullptr; uint2* items = nullptr;
-  tb::Ctl* ctl = nullptr; tb::Ctl* h_ctl = nullptr;
-  uint32_t* marr[2] = { nullptr, nullptr };
-  float *thr = nullptr, *bnd = nullptr; uint32_t *seed = nullptr, *target = nullptr;
+  DevBuf<float> D; DevBuf<uint32_t> pend; DevBuf<uint8_t> pflag; DevBuf<uint32_t> pairs; DevBuf<uint16_t> bucket; DevBuf<uint32_t> bcnt; DevBuf<uint2> items;
+  DevBuf<tb::Ctl> ctl; PinnedBuf<tb::Ctl> h_ctl;
+  DevBuf<unsigned long long> wstat; DevBuf<struct FinRec> d_recs;
+  DevBuf<uint32_t> marr[2];
+  DevBuf<float> thr, bnd; DevBuf<uint32_t> seed, target;
+  GraphExec graph[2]; tb::Args graph_args[2]{};   // one per distance buffer
+  // second distance buffer, filled with +inf on its own stream behind the previous call (the fill of 6 B x slots x plans is
+  // otherwise 2 % of a batch); only when both fit comfortably
+  DevBuf<float> D2; bool d2_clean = false; uint32_t d2_clean_np = 0, d2_wanted_np = 0;
+};
+
+struct TbState : TbTables, TbBatch {
+  uint32_t T = 120;                     // 120 rows x 256 B + staging = 31 232 B of LDS: five waves per CU (128 rows: four)
+  int kernel = 0;                       // solve kernel of the running batch: 0 = k_tb_solve_q (quarters, distances in LDS), 1 = k_tbv_solve (waves, distances in registers)
   uint32_t min_batch = 48;              // auto engine: batches of at least this many plans (and of tiles / 1000: mnav.hip dijkstra_impl)
   float band_mult = 2.0f;               // band = band_mult * mean edge weight * sqrt(T)  (measured on C2: 1 -> 236 ms, 2 -> 218 ms per 5120 plans)
   int iters_per_replay = 16, waves_per_cu = 0;
-  hipGraphExec_t graph[2] = { nullptr, nullptr }; tb::Args graph_args[2]{};   // one per distance buffer
-  // second distance buffer, filled with +inf on its own stream behind the previous call (the fill of 6 B x slots x plans is
-  // otherwise 2 % of a batch); only when both fit comfortably
-  float* D2 = nullptr; bool d2_clean = false; uint32_t d2_clean_np = 0, d2_wanted_np = 0; hipStream_t fill_stream = nullptr; hipEvent_t fill_done = nullptr;
+  Stream fill_stream; Event fill_done;  // (the fill of D2)
   tb::Ctl last{};                       // counters of the last batch
   bool count_pending = false;           // the settled-vertex count of the last (paths-only) batch has not been taken yet
 };

@@ -1,37 +1,19 @@
 // mnav_tb_host.h -- host driver of the tile-batch SSSP engine (mnav_tb.h).  Included by mnav.hip inside its anonymous
-// namespace, after mnav_ctx and the helpers (HIPCHK, dev_upload, ev_ms, PlanIn) are defined.
+// namespace, after mnav_ctx and the helpers (HIPCHK, ev_ms, PlanIn) are defined.
 #pragma once
 
 void tb_free_batch(mnav_ctx* ctx)
 {
   TbState& S = ctx->tb;
-  (void)hipFree(S.D); (void)hipFree(S.pend); (void)hipFree(S.pflag); (void)hipFree(S.pairs); S.pairs = nullptr; (void)hipFree(S.bucket); (void)hipFree(S.bcnt); (void)hipFree(S.items); (void)hipFree(S.ctl); (void)hipFree(S.wstat); S.wstat = nullptr;
-  (void)hipFree(S.marr[0]); (void)hipFree(S.marr[1]);
-  (void)hipFree(S.thr); (void)hipFree(S.bnd); (void)hipFree(S.seed); (void)hipFree(S.target); (void)hipFree(S.d_recs); S.d_recs = nullptr;
-  if (S.h_ctl) (void)hipHostFree(S.h_ctl);
-  for (int k = 0; k < 2; ++k) { if (S.graph[k]) (void)hipGraphExecDestroy(S.graph[k]); S.graph[k] = nullptr; }
-  if (S.fill_stream) (void)hipStreamSynchronize(S.fill_stream);
-  (void)hipFree(S.D2); S.D2 = nullptr; S.d2_clean = false; S.d2_wanted_np = 0u;
-  S.D = nullptr; S.pend = nullptr; S.pflag = nullptr; S.bucket = nullptr; S.bcnt = nullptr; S.items = nullptr; S.ctl = nullptr; S.h_ctl = nullptr;
-  S.marr[0] = S.marr[1] = nullptr; S.thr = S.bnd = nullptr; S.seed = S.target = nullptr;
-  S.cap_np = 0;
+  if (S.fill_stream) (void)hipStreamSynchronize(S.fill_stream);      // (its fill may still be writing D2)
+  static_cast<TbBatch&>(S) = TbBatch{};
   S.count_pending = false; ctx->tb_args_valid = false;               // the last batch's arguments point into freed memory now
 }
 
 void tb_free(mnav_ctx* ctx)
 {
-  TbState& S = ctx->tb;
   tb_free_batch(ctx);
-  for (void* p : { (void*)S.d_tiles, (void*)S.d_stream, (void*)S.d_wsrc, (void*)S.d_exps, (void*)S.d_vaddr, (void*)S.d_vert_tile, (void*)S.d_verts,
-                   (void*)S.d_vstream, (void*)S.d_vwsrc, (void*)S.d_vtile, (void*)S.d_vgroups, (void*)S.d_vexps,
-                   (void*)S.d_fin_src, (void*)S.d_fin_wsrc, (void*)S.d_fin_ovf, (void*)S.d_fin_ovf_wsrc, (void*)S.d_ghost_gid, (void*)S.d_fin_order })
-    if (p) { ctx->alloc_bytes.erase(p); (void)hipFree(p); }
-  S.d_tiles = nullptr; S.d_stream = nullptr; S.d_wsrc = nullptr; S.d_exps = nullptr; S.d_vaddr = nullptr; S.d_vert_tile = nullptr; S.d_verts = nullptr;
-  S.d_vstream = nullptr; S.d_vwsrc = nullptr; S.d_vtile = nullptr; S.d_vgroups = nullptr; S.d_vexps = nullptr;
-  S.d_fin_src = nullptr; S.d_fin_wsrc = nullptr; S.d_fin_ovf = nullptr; S.d_fin_ovf_wsrc = nullptr; S.d_ghost_gid = nullptr; S.d_fin_order = nullptr;
-  (void)hipFree(S.d_fin_w); S.d_fin_w = nullptr; (void)hipFree(S.d_fin_ovf_w); S.d_fin_ovf_w = nullptr; S.fin_w_valid = false;
-  S.built = false; S.w_valid = false; S.vert_tile.clear();
-  S.count_pending = false; ctx->tb_args_valid = false;
+  static_cast<TbTables&>(ctx->tb) = TbTables{};
 }
 
 // mesh-dependent streams: built on the first batch that takes this engine (a few seconds of host work at 1M vertices)
@@ -53,29 +35,29 @@ int tb_build(mnav_ctx* ctx)
     if (W.sl >= (1u << 24)) { ctx->err = "tile-batch engine: a tile has too many ghosts"; return -1; }
     vaddr[v] = make_uint2(W.soff, (W.sl << 8) | H.vert_local[v]);
   }
-  if (dev_upload(ctx, &S.d_tiles, H.tiles.data(), H.tiles.size())) return -1;
-  if (dev_upload(ctx, &S.d_stream, H.stream.data(), H.stream.size())) return -1;
-  if (dev_upload(ctx, &S.d_wsrc, H.wsrc.data(), H.wsrc.size())) return -1;
-  if (dev_upload(ctx, &S.d_exps, H.exps.data(), H.exps.size())) return -1;
-  if (dev_upload(ctx, &S.d_vstream, H.vstream.data(), H.vstream.size())) return -1;
-  if (dev_upload(ctx, &S.d_vwsrc, H.vwsrc.data(), H.vwsrc.size())) return -1;
-  if (dev_upload(ctx, &S.d_vtile, H.vtile.data(), H.vtile.size())) return -1;
+  HIPCHK(S.d_tiles.upload(ctx->stream, H.tiles.data(), H.tiles.size()));
+  HIPCHK(S.d_stream.upload(ctx->stream, H.stream.data(), H.stream.size()));
+  HIPCHK(S.d_wsrc.upload(ctx->stream, H.wsrc.data(), H.wsrc.size()));
+  HIPCHK(S.d_exps.upload(ctx->stream, H.exps.data(), H.exps.size()));
+  HIPCHK(S.d_vstream.upload(ctx->stream, H.vstream.data(), H.vstream.size()));
+  HIPCHK(S.d_vwsrc.upload(ctx->stream, H.vwsrc.data(), H.vwsrc.size()));
+  HIPCHK(S.d_vtile.upload(ctx->stream, H.vtile.data(), H.vtile.size()));
   if (H.vgroups.empty()) H.vgroups.push_back(0u);
-  if (dev_upload(ctx, &S.d_vgroups, H.vgroups.data(), H.vgroups.size())) return -1;
-  if (dev_upload(ctx, &S.d_vexps, H.vexps.data(), H.vexps.size())) return -1;
-  if (dev_upload(ctx, &S.d_vaddr, vaddr.data(), vaddr.size())) return -1;
-  if (dev_upload(ctx, &S.d_vert_tile, H.vert_tile.data(), H.vert_tile.size())) return -1;
-  if (dev_upload(ctx, &S.d_verts, H.verts.data(), H.verts.size())) return -1;
+  HIPCHK(S.d_vgroups.upload(ctx->stream, H.vgroups.data(), H.vgroups.size()));
+  HIPCHK(S.d_vexps.upload(ctx->stream, H.vexps.data(), H.vexps.size()));
+  HIPCHK(S.d_vaddr.upload(ctx->stream, vaddr.data(), vaddr.size()));
+  HIPCHK(S.d_vert_tile.upload(ctx->stream, H.vert_tile.data(), H.vert_tile.size()));
+  HIPCHK(S.d_verts.upload(ctx->stream, H.verts.data(), H.verts.size()));
   // finalize tables (mnav_tb_finalize.h)
-  if (dev_upload(ctx, &S.d_fin_src, H.fin_src.data(), H.fin_src.size())) return -1;
-  if (dev_upload(ctx, &S.d_fin_wsrc, H.fin_wsrc.data(), H.fin_wsrc.size())) return -1;
-  if (dev_upload(ctx, &S.d_fin_ovf, H.fin_ovf.data(), H.fin_ovf.size())) return -1;
+  HIPCHK(S.d_fin_src.upload(ctx->stream, H.fin_src.data(), H.fin_src.size()));
+  HIPCHK(S.d_fin_wsrc.upload(ctx->stream, H.fin_wsrc.data(), H.fin_wsrc.size()));
+  HIPCHK(S.d_fin_ovf.upload(ctx->stream, H.fin_ovf.data(), H.fin_ovf.size()));
   {
     std::vector<uint32_t> ow(H.fin_ovf.size());
     for (size_t i = 0; i < ow.size(); ++i) ow[i] = H.fin_ovf[i].wsrc;
-    if (dev_upload(ctx, &S.d_fin_ovf_wsrc, ow.data(), ow.size())) return -1;
+    HIPCHK(S.d_fin_ovf_wsrc.upload(ctx->stream, ow.data(), ow.size()));
   }
-  if (dev_upload(ctx, &S.d_ghost_gid, H.ghost_gid.data(), H.ghost_gid.size())) return -1;
+  HIPCHK(S.d_ghost_gid.upload(ctx->stream, H.ghost_gid.data(), H.ghost_gid.size()));
   {
     // k_tb_finalize's workgroups take the tiles in the order of their smallest vertex id: the tiles of a workgroup -- and of the
     // workgroups running next to it -- then write neighbouring pieces of the vertex-order output arrays (on a row-major grid: a
@@ -87,12 +69,12 @@ int tb_build(mnav_ctx* ctx)
     }
     std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return key[a] < key[b]; });
     if (order.empty()) order.push_back(0u);
-    if (dev_upload(ctx, &S.d_fin_order, order.data(), order.size())) return -1;
+    HIPCHK(S.d_fin_order.upload(ctx->stream, order.data(), order.size()));
   }
-  (void)hipFree(S.d_fin_w); S.d_fin_w = nullptr; (void)hipFree(S.d_fin_ovf_w); S.d_fin_ovf_w = nullptr;
+  S.d_fin_w.reset(); S.d_fin_ovf_w.reset();
   S.fin_n = H.fin_src.size(); S.fin_novf = H.fin_ovf.size(); S.fin_w_valid = false; S.max_sl = H.max_sl;
-  HIPCHK(hipMalloc((void**)&S.d_fin_w, 4 * std::max<size_t>(S.fin_n, 1)));
-  HIPCHK(hipMalloc((void**)&S.d_fin_ovf_w, 4 * std::max<size_t>(S.fin_novf, 1)));
+  HIPCHK(S.d_fin_w.alloc(4 * std::max<size_t>(S.fin_n, 1)));
+  HIPCHK(S.d_fin_ovf_w.alloc(4 * std::max<size_t>(S.fin_novf, 1)));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   S.nvrec = H.vstream.size();
   S.ntiles = H.ntiles; S.S = H.S; S.nrec = H.stream.size(); S.nexp = H.exps.size(); S.max_nh = H.max_nh;
@@ -133,26 +115,24 @@ int tb_ensure_batch(mnav_ctx* ctx, uint32_t np)
   if (np <= S.cap_np) return 0;
   tb_free_batch(ctx);
   const size_t nt = S.ntiles ? S.ntiles : 1, pairs = nt * (size_t)np;
-  HIPCHK(hipMalloc((void**)&S.D, 4 * (size_t)S.S * np + 64));
+  HIPCHK(S.D.alloc(4 * (size_t)S.S * np + 64));
   if (8 * (size_t)S.S * np <= ((size_t)96 << 30) && !opt_on(ctx->opt.tb_no_prefill)) {
-    if (hipMalloc((void**)&S.D2, 4 * (size_t)S.S * np + 64) != hipSuccess) { S.D2 = nullptr; (void)hipGetLastError(); }
-    if (S.D2 && !S.fill_stream) { HIPCHK(hipStreamCreateWithFlags(&S.fill_stream, hipStreamNonBlocking)); HIPCHK(hipEventCreateWithFlags(&S.fill_done, hipEventDisableTiming)); }
+    if (S.D2.alloc(4 * (size_t)S.S * np + 64) != hipSuccess) (void)hipGetLastError();   // (optional: the batch runs without it)
+    if (S.D2 && !S.fill_stream) { HIPCHK(hipStreamCreateWithFlags(S.fill_stream.out(), hipStreamNonBlocking)); HIPCHK(hipEventCreateWithFlags(S.fill_done.out(), hipEventDisableTiming)); }
   }
-  HIPCHK(hipMalloc((void**)&S.pend, 4 * pairs + 64));
-  HIPCHK(hipMalloc((void**)&S.pflag, nt * (((size_t)np + 63) / 64) + 64));
-  HIPCHK(hipMalloc((void**)&S.pairs, 4 * (nt * (((size_t)np + 63) / 64) + 64)));   // worst case: every (tile, block) flagged
-  HIPCHK(hipMalloc((void**)&S.bucket, 2 * pairs + 64));
-  HIPCHK(hipMalloc((void**)&S.bcnt, 4 * nt));
-  HIPCHK(hipMalloc((void**)&S.items, 8 * (nt + pairs / kTbItemPlans + 64)));
-  HIPCHK(hipMalloc((void**)&S.ctl, sizeof(tb::Ctl)));
-  if (!S.wstat) HIPCHK(hipMalloc((void**)&S.wstat, 32 * (size_t)kTbStatSlots));
-  HIPCHK(hipHostMalloc((void**)&S.h_ctl, sizeof(tb::Ctl), hipHostMallocDefault));
-  for (int k = 0; k < 2; ++k) {
-    HIPCHK(hipMalloc((void**)&S.marr[k], 4 * (size_t)np));
-  }
-  HIPCHK(hipMalloc((void**)&S.thr, 4 * (size_t)np)); HIPCHK(hipMalloc((void**)&S.bnd, 4 * (size_t)np));
-  HIPCHK(hipMalloc((void**)&S.seed, 4 * (size_t)np)); HIPCHK(hipMalloc((void**)&S.target, 4 * (size_t)np));
-  HIPCHK(hipMalloc((void**)&S.d_recs, sizeof(FinRec) * (size_t)np));
+  HIPCHK(S.pend.alloc(4 * pairs + 64));
+  HIPCHK(S.pflag.alloc(nt * (((size_t)np + 63) / 64) + 64));
+  HIPCHK(S.pairs.alloc(4 * (nt * (((size_t)np + 63) / 64) + 64)));   // worst case: every (tile, block) flagged
+  HIPCHK(S.bucket.alloc(2 * pairs + 64));
+  HIPCHK(S.bcnt.alloc(4 * nt));
+  HIPCHK(S.items.alloc(8 * (nt + pairs / kTbItemPlans + 64)));
+  HIPCHK(S.ctl.alloc(sizeof(tb::Ctl)));
+  HIPCHK(S.wstat.alloc(32 * (size_t)kTbStatSlots));
+  HIPCHK(S.h_ctl.alloc(sizeof(tb::Ctl)));
+  for (int k = 0; k < 2; ++k) HIPCHK(S.marr[k].alloc(4 * (size_t)np));
+  HIPCHK(S.thr.alloc(4 * (size_t)np)); HIPCHK(S.bnd.alloc(4 * (size_t)np));
+  HIPCHK(S.seed.alloc(4 * (size_t)np)); HIPCHK(S.target.alloc(4 * (size_t)np));
+  HIPCHK(S.d_recs.alloc(sizeof(FinRec) * (size_t)np));
   S.cap_np = np;
   return 0;
 }
@@ -200,8 +180,8 @@ int tb_fields(mnav_ctx* ctx, uint32_t n, const std::vector<PlanIn>& in, double o
     Plan& P = hp[i];
     memset(&P, 0, sizeof(P));
     P.planner = kPlannerDijkstra; P.V = ctx->V;
-    P.row_ptr = ctx->d_row_ptr; P.nbr = ctx->d_nbr; P.crn_ptr = ctx->d_crn_ptr; P.crn = ctx->d_crn; P.blocked = ctx->d_blocked;
-    P.dist = s.dist; P.pred = s.pred; P.cap = ctx->V; P.ctl = s.ctl; P.cnt = s.cnt;
+    P.row_ptr = ctx->d_row_ptr.get(); P.nbr = ctx->d_nbr.get(); P.crn_ptr = ctx->d_crn_ptr.get(); P.crn = ctx->d_crn.get(); P.blocked = ctx->d_blocked.get();
+    P.dist = s.dist.get(); P.pred = s.pred.get(); P.cap = ctx->V; P.ctl = s.ctl; P.cnt = s.cnt.get();
     P.offset = offset; P.max_steps = ctx->max_steps;
     for (int k = 0; k < 3; ++k) { P.seed[k] = in[i].seed[k]; P.target[k] = in[i].target[k]; P.seed_d[k] = 0.f; P.seed_expands[k] = 1; P.target_expands[k] = 1; }
     P.seed_face = kNone;
@@ -249,7 +229,7 @@ int tb_clean_other(mnav_ctx* ctx)
   S.d2_wanted_np = 0u;
   const size_t n16 = (4 * (size_t)S.S * n + 15) / 16;
   const uint32_t g = (uint32_t)std::max<size_t>(std::min<size_t>((n16 + kBlock - 1) / kBlock, 256 * 32), 1);
-  hipLaunchKernelGGL(k_tb_fill, dim3(g), dim3(kBlock), 0, S.fill_stream, (u32x4*)S.D2, n16, kTbInfBits);
+  hipLaunchKernelGGL(k_tb_fill, dim3(g), dim3(kBlock), 0, S.fill_stream, (u32x4*)S.D2.get(), n16, kTbInfBits);
   HIPCHK(hipEventRecord(S.fill_done, S.fill_stream));
   S.d2_clean = true; S.d2_clean_np = n;
   return 0;
@@ -264,7 +244,7 @@ int run_dijkstra_tb(mnav_ctx* ctx, uint32_t n, const std::vector<PlanIn>& in, do
   if (tb_ensure_batch(ctx, n)) return -1;
   if (ensure_plan_tables(ctx, n)) return -1;
   if (ensure_paths(ctx, n)) return -1;
-  if (!ctx->d_mismatch) HIPCHK(hipMalloc((void**)&ctx->d_mismatch, 4));
+  if (!ctx->d_mismatch) HIPCHK(ctx->d_mismatch.alloc(4));
   std::vector<uint32_t> seeds(n), targets(n);
   for (uint32_t i = 0; i < n; ++i) { seeds[i] = in[i].seed[0]; targets[i] = in[i].target[0]; }
   HIPCHK(hipMemcpyAsync(S.seed, seeds.data(), 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
@@ -334,13 +314,13 @@ int run_dijkstra_tb(mnav_ctx* ctx, uint32_t n, const std::vector<PlanIn>& in, do
   for (int k = 0; k < 2; ++k) if (S.graph[k] && memcmp(&S.graph_args[k], &A, sizeof(A)) == 0) gi = k + 2;
   if (ctx->use_graph && gi < 2) {
     gi = (S.graph[0] && S.graph_args[0].D != A.D) ? 1 : 0;
-    if (S.graph[gi]) { (void)hipGraphExecDestroy(S.graph[gi]); S.graph[gi] = nullptr; }
+    S.graph[gi].reset();
     hipGraph_t g = nullptr;
     HIPCHK(hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
     const int rc = tb_launch_iterations(ctx, A, chunk, waves);
     const hipError_t e = hipStreamEndCapture(ctx->stream, &g);
     if (rc != 0 || e != hipSuccess) { ctx->err = "graph capture failed"; return -1; }
-    HIPCHK(hipGraphInstantiate(&S.graph[gi], g, nullptr, nullptr, 0));
+    HIPCHK(hipGraphInstantiate(S.graph[gi].out(), g, nullptr, nullptr, 0));
     (void)hipGraphDestroy(g);
     memcpy(&S.graph_args[gi], &A, sizeof(A));
   } else gi -= 2;

@@ -476,14 +476,14 @@ void k_tbv_micro(const uint32_t* __restrict__ stream, uint32_t nch, uint32_t fir
 extern "C" int mnav_debug_tbv_sweeps(const uint32_t* stream_host, uint32_t nch, uint32_t first_order, uint32_t cap, uint32_t force, uint32_t reps,
                                      uint32_t waves, uint32_t* img_host, uint32_t* out_host, float* ms_out)
 {
-  uint32_t *d_s = nullptr, *d_i = nullptr, *d_o = nullptr;
+  DevBuf<uint32_t> d_s, d_i, d_o;
   const size_t ns = (size_t)4 * nch * 64 + 8 * 64, ni = (size_t)waves * tbv::kRows * 64;
-  if (hipMalloc((void**)&d_s, 4 * ns) != hipSuccess || hipMalloc((void**)&d_i, 4 * ni) != hipSuccess || hipMalloc((void**)&d_o, 8 * (size_t)waves) != hipSuccess) return -1;
+  if (d_s.alloc(4 * ns) != hipSuccess || d_i.alloc(4 * ni) != hipSuccess || d_o.alloc(8 * (size_t)waves) != hipSuccess) return -1;
   (void)hipMemset(d_s, 0, 4 * ns);
   (void)hipMemcpy(d_s, stream_host, (size_t)4 * 4 * nch * 64, hipMemcpyHostToDevice);
   (void)hipMemcpy(d_i, img_host, 4 * ni, hipMemcpyHostToDevice);
-  hipEvent_t e0, e1;
-  (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
+  Event e0, e1;
+  (void)hipEventCreate(e0.out()); (void)hipEventCreate(e1.out());
   (void)hipEventRecord(e0, 0);
   hipLaunchKernelGGL(k_tbv_micro, dim3(waves), dim3(64), 0, 0, d_s, nch, first_order, cap, force, reps, d_i, d_o);
   (void)hipEventRecord(e1, 0);
@@ -493,8 +493,6 @@ extern "C" int mnav_debug_tbv_sweeps(const uint32_t* stream_host, uint32_t nch, 
   if (ms_out) *ms_out = ms;
   (void)hipMemcpy(img_host, d_i, 4 * ni, hipMemcpyDeviceToHost);
   (void)hipMemcpy(out_host, d_o, 8 * (size_t)waves, hipMemcpyDeviceToHost);
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-  (void)hipFree(d_s); (void)hipFree(d_i); (void)hipFree(d_o);
   return e == hipSuccess ? 0 : -2;
 }
 #pragma clang diagnostic pop

@@ -247,3 +247,51 @@ def test_negative_goal_dist_offset_matches_the_reference(gpu_ctx_factory):
         with pytest.raises(RuntimeError, match="goal_dist_offset"):
             ctx.plan_dijkstra_batch(seeds, targets, goal_dist_offset=float("nan"))
         assert ctx.plan_dijkstra(int(seeds[0]), int(targets[0]), goal_dist_offset=0.0).code == 0
+
+
+def test_mesh_reupload_gives_the_same_results_and_device_bytes(gpu_ctx_factory):
+    """One context: a mesh and its costs, a tile-batch Dijkstra batch, a CVP batch with back-tracking, an obstacle layer
+    and a neighbourhood layer; then a different mesh (with a batch of its own), the first mesh again and the same calls.
+    The second round's results equal the first round's bit for bit, and mnav_device_bytes counts the same memory: nothing
+    the re-uploads freed is still counted, nothing of the other mesh is left behind."""
+    case, other = terrain_case(96, 7), terrain_case(64, 3)
+    mesh = case.mesh
+    rng = np.random.default_rng(11)
+    seeds = rng.choice(mesh.V, 64, replace=False).astype(np.uint32)
+    targets = rng.choice(mesh.V, 64, replace=False).astype(np.uint32)
+    sf = rng.choice(mesh.F, 6, replace=False).astype(np.uint32)
+    tf = rng.choice(mesh.F, 6, replace=False).astype(np.uint32)
+    sp = np.stack([centroid(mesh, int(f)) for f in sf])
+    tp = np.stack([centroid(mesh, int(f)) for f in tf])
+    pts = mesh.xyz[rng.choice(mesh.V, 500, replace=False)] + np.float32([0.0, 0.0, 0.5])
+    pts = pts.astype(np.float32)
+    ctx = gpu_ctx_factory()
+    ctx.set_dijkstra_engine("tile_batch")
+
+    def one_round():
+        case.upload(ctx)
+        out = {}
+        b = ctx.plan_dijkstra_batch(seeds, targets, want_fields=True)
+        assert ctx.last_engine().startswith("k_tb")
+        out.update(codes=b["codes"], dist=b["dist"].view(np.uint32), pred=b["pred"], paths=np.concatenate(list(b["paths"])))
+        c = ctx.plan_cvp_batch(sp, sf, tf, want_fields=True, want_vecmap=True)
+        out.update(cvp_codes=c["codes"], cvp_dist=c["dist"].view(np.uint32), cvp_pred=c["pred"], cvp_vec=c["vecmap"].view(np.uint32))
+        walks = ctx.backtrack_cvp_batch(sp, sf, tp, tf)
+        out.update(walk_status=np.array([w[0] for w in walks]), walk_pos=np.concatenate([w[1] for w in walks]).view(np.uint32),
+                   walk_faces=np.concatenate([w[2] for w in walks]))
+        o = ctx.layer_obstacle(0, pts)
+        cost, lethal = ctx.layer_download(0)
+        out.update(obs_changed=o["changed"], obs_cost=cost.view(np.uint32), obs_lethal=lethal)
+        ctx.layer_height_diff(1)
+        cost, lethal = ctx.layer_download(1)
+        out.update(hd_cost=cost.view(np.uint32), hd_lethal=lethal)
+        return ctx.device_bytes(), out
+
+    bytes1, first = one_round()
+    assert (first["codes"] == 0).all() and first["obs_lethal"].any()
+    other.upload(ctx)
+    ctx.plan_dijkstra_batch(rng.choice(other.mesh.V, 64).astype(np.uint32), rng.choice(other.mesh.V, 64).astype(np.uint32))
+    bytes2, second = one_round()
+    for k in first:
+        assert np.array_equal(first[k], second[k]), k
+    assert bytes2 == bytes1
