@@ -8,6 +8,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import sys
+import time
 import weakref
 from dataclasses import dataclass
 
@@ -29,6 +30,7 @@ SYMBOLS = [
     "mnav_combine_layers", "mnav_layer_stats", "mnav_layer_download_vectors", "mnav_combine_layers_update",
     "mnav_layer_obstacle", "mnav_obstacle_stats",
     "mnav_layer_height_diff", "mnav_layer_roughness", "mnav_layer_ridge", "mnav_neighbourhood_stats",
+    "mnav_layer_border", "mnav_layer_clearance", "mnav_clearance_download", "mnav_clearance_stats",
     "mnav_set_option", "mnav_get_option", "mnav_shard_set_goal_tie", "mnav_last_engine",
 ]
 
@@ -160,6 +162,13 @@ def load(path: str | None = None):
         getattr(L, name).argtypes = [vp, u32, f64, f64]
     L.mnav_neighbourhood_stats.restype = C.c_int
     L.mnav_neighbourhood_stats.argtypes = [vp, C.POINTER(u32), C.POINTER(C.c_uint64), C.POINTER(u32), C.POINTER(u32), C.POINTER(C.c_float)]
+    for name in ("mnav_layer_border", "mnav_layer_clearance"):
+        getattr(L, name).restype = C.c_int
+        getattr(L, name).argtypes = [vp, u32, f64, f64, vp, C.POINTER(u32), C.POINTER(u32)]
+    L.mnav_clearance_download.restype = C.c_int
+    L.mnav_clearance_download.argtypes = [vp, vp]
+    L.mnav_clearance_stats.restype = C.c_int
+    L.mnav_clearance_stats.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.mnav_shard_setup.restype = C.c_int
     L.mnav_shard_setup.argtypes = [vp, u32, u32]
     L.mnav_shard_setup_partition.restype = C.c_int
@@ -483,6 +492,44 @@ class MnavContext:
         c, v, m, s, ms = C.c_uint32(), C.c_uint64(), C.c_uint32(), C.c_uint32(), C.c_float()
         self._L.mnav_neighbourhood_stats(self._h, C.byref(c), C.byref(v), C.byref(m), C.byref(s), C.byref(ms))
         return dict(centres=c.value, visits=v.value, max_size=m.value, spilled=s.value, ms=ms.value)
+
+    # border and clearance layers (mnav_layer_border / mnav_layer_clearance, include/mnav.h); defaults: the reference's
+    # border_layer.h:132-133 and clearance_layer.h:135-136.  Both return dict(changed = ascending uint32 ids whose lethal
+    # flag or cost bits changed, n_lethal, stats).
+    def layer_border(self, layer: int, border_cost: float = 1.0, threshold: float = 0.5) -> dict:
+        """stats: the host wall-clock milliseconds of the call (ms_wall)"""
+        t0 = time.perf_counter()
+        out = self._change_layer("mnav_layer_border", layer, border_cost, threshold)
+        out["stats"] = dict(ms_wall=(time.perf_counter() - t0) * 1e3)
+        return out
+
+    def layer_clearance(self, layer: int, robot_height: float = 0.5, height_inflation: float = 0.3) -> dict:
+        """the first call after upload_mesh casts the rays (and builds the BVH if no obstacle call did); later calls only
+        recompute the costs from the cached clearance.  stats: clearance_stats()"""
+        out = self._change_layer("mnav_layer_clearance", layer, robot_height, height_inflation)
+        out["stats"] = self.clearance_stats()
+        return out
+
+    def _change_layer(self, name: str, layer: int, a: float, b: float) -> dict:
+        changed = np.empty(max(self.V, 1), np.uint32)
+        nc, nl = C.c_uint32(), C.c_uint32()
+        if getattr(self._L, name)(self._h, int(layer), float(a), float(b), _p(changed), C.byref(nc), C.byref(nl)) != 0:
+            raise RuntimeError(f"{name} failed: {self._err()}")
+        return dict(changed=changed[:nc.value].copy(), n_lethal=nl.value)
+
+    def clearance(self) -> np.ndarray:
+        """the cached clearance: float32[V], +inf where the vertex's ray hit nothing"""
+        c = np.empty(max(self.V, 1), np.float32)
+        if self._L.mnav_clearance_download(self._h, _p(c)) != 0:
+            raise RuntimeError(f"mnav_clearance_download failed: {self._err()}")
+        return c[:self.V]
+
+    def clearance_stats(self) -> dict:
+        """the last clearance call: cast (1) or reused the cache (0), rays cast and rays that hit by it, device ms of its BVH
+        build (0 if none), of the cast (0 if reused) and of the whole call"""
+        cast, r, h, mb, mc, mt = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_float(), C.c_float(), C.c_float()
+        self._L.mnav_clearance_stats(self._h, C.byref(cast), C.byref(r), C.byref(h), C.byref(mb), C.byref(mc), C.byref(mt))
+        return dict(cast=cast.value, rays=r.value, hits=h.value, ms_bvh_build=mb.value, ms_cast=mc.value, ms_total=mt.value)
 
     def layer_download(self, layer: int, distances: bool = False):
         c = np.empty(self.V, np.float32)

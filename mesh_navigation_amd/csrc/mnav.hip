@@ -79,6 +79,7 @@ constexpr int kChunk = 96;  // step launches per graph replay; multiple of 6 (sl
 #include "mnav_walk.h"
 #include "mnav_obstacle.h"   // obstacle layer: LBVH build, ray cast, change list (mnav_obs::)
 #include "mnav_nbhd.h"       // height-difference / roughness / ridge layers: neighbourhood visits (mnav_nb::)
+#include "mnav_clearance.h"  // clearance / border layers: normal ray casts over the obstacle BVH, border test (mnav_clr::)
 
 // One back-tracking job: the plan's resident vector map and the two ends of the walk.
 struct WalkJob { const float* vecmap; float seed[3]; uint32_t seed_face; float target[3]; uint32_t target_face; };
@@ -210,6 +211,7 @@ struct mnav_ctx {
   DevBuf<float> d_infl_keyd;
   mnav_obs::Bvh obs;                                               // obstacle layer: BVH built by the first mnav_layer_obstacle after an upload
   mnav_nb::State nbhd;                                             // neighbourhood layers: counters, spill lists and scratch of the last call
+  mnav_clr::State clr;                                             // clearance / border layers: cached clearance (first clearance call after an upload)
   uint32_t infl_steps = 0, infl_bands = 0; uint64_t infl_evals = 0; float infl_ms = 0.f, infl_ms_wave = 0.f;   // last inflation wave
   DevBuf<TilePlan> d_tplans; uint32_t tplans_cap = 0;
   PinnedBuf<TCtl> h_tctl;
@@ -612,6 +614,7 @@ int mnav_upload_mesh(mnav_ctx* ctx, uint32_t V, uint32_t F, uint32_t E, const fl
   ctx->d_crn_infl.reset(); ctx->d_infl_mask.reset(); ctx->d_zero_u8.reset(); ctx->d_infl_keyd.reset(); ctx->crn_infl_valid = false;
   ctx->obs = {};                                                     // rebuilt lazily
   ctx->nbhd = {};                                                    // V-sized spill lists
+  ctx->clr = {};                                                     // cached clearance: recast lazily
   ctx->d_edge_dist.reset();
   drop_graphs(ctx);
   ctx->d_paths.reset(); ctx->paths_words = 0;
@@ -1571,6 +1574,7 @@ uint32_t mnav_plan_cvp_batch(mnav_ctx* ctx, uint32_t n, const float* seed_pos, c
 #include "mnav_shard_capi.h"   // mnav_shard_* (one plan over several GPUs)
 #include "mnav_obstacle_capi.h"   // mnav_layer_obstacle, mnav_obstacle_stats
 #include "mnav_nbhd_capi.h"       // mnav_layer_height_diff / _roughness / _ridge, mnav_neighbourhood_stats
+#include "mnav_clearance_capi.h"  // mnav_layer_clearance, mnav_layer_border, mnav_clearance_download, mnav_clearance_stats
 
 void mnav_cancel(mnav_ctx* ctx)
 {
