@@ -458,13 +458,10 @@ class MnavContext:
         elif rotation_wxyz is not None:
             m = quat_to_matrix(rotation_wxyz, (0.0, 0.0, 0.0) if translation is None else translation)
         d = _f32(down_axis).reshape(3)
-        changed = np.empty(max(self.V, 1), np.uint32)
-        nc, nl = C.c_uint32(), C.c_uint32()
-        rc = self._L.mnav_layer_obstacle(self._h, int(layer), n, _p(pts) if n else None, int(step), _p(m), _p(d),
-                                         float(robot_height), float(max_obstacle_dist), _p(changed), C.byref(nc), C.byref(nl))
-        if rc != 0:
-            raise RuntimeError(f"mnav_layer_obstacle failed: {self._err()}")
-        return dict(changed=changed[:nc.value].copy(), n_lethal=nl.value, stats=self.obstacle_stats())
+        out = self._change_layer("mnav_layer_obstacle", layer, n, _p(pts) if n else None, int(step), _p(m), _p(d),
+                                 float(robot_height), float(max_obstacle_dist))
+        out["stats"] = self.obstacle_stats()
+        return out
 
     def obstacle_stats(self) -> dict:
         k, h, lr, mb, mc, mt = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_float(), C.c_float(), C.c_float()
@@ -499,21 +496,22 @@ class MnavContext:
     def layer_border(self, layer: int, border_cost: float = 1.0, threshold: float = 0.5) -> dict:
         """stats: the host wall-clock milliseconds of the call (ms_wall)"""
         t0 = time.perf_counter()
-        out = self._change_layer("mnav_layer_border", layer, border_cost, threshold)
+        out = self._change_layer("mnav_layer_border", layer, float(border_cost), float(threshold))
         out["stats"] = dict(ms_wall=(time.perf_counter() - t0) * 1e3)
         return out
 
     def layer_clearance(self, layer: int, robot_height: float = 0.5, height_inflation: float = 0.3) -> dict:
         """the first call after upload_mesh casts the rays (and builds the BVH if no obstacle call did); later calls only
         recompute the costs from the cached clearance.  stats: clearance_stats()"""
-        out = self._change_layer("mnav_layer_clearance", layer, robot_height, height_inflation)
+        out = self._change_layer("mnav_layer_clearance", layer, float(robot_height), float(height_inflation))
         out["stats"] = self.clearance_stats()
         return out
 
-    def _change_layer(self, name: str, layer: int, a: float, b: float) -> dict:
+    def _change_layer(self, name: str, layer: int, *args) -> dict:
+        """a layer call whose C signature ends in (changed_out, n_changed, n_lethal): dict(changed, n_lethal)"""
         changed = np.empty(max(self.V, 1), np.uint32)
         nc, nl = C.c_uint32(), C.c_uint32()
-        if getattr(self._L, name)(self._h, int(layer), float(a), float(b), _p(changed), C.byref(nc), C.byref(nl)) != 0:
+        if getattr(self._L, name)(self._h, int(layer), *args, _p(changed), C.byref(nc), C.byref(nl)) != 0:
             raise RuntimeError(f"{name} failed: {self._err()}")
         return dict(changed=changed[:nc.value].copy(), n_lethal=nl.value)
 

@@ -77,7 +77,7 @@ constexpr int kChunk = 96;  // step launches per graph replay; multiple of 6 (sl
 #include "mnav_tb_finalize.h"
 #include "mnav_tbv.h"
 #include "mnav_walk.h"
-#include "mnav_obstacle.h"   // obstacle layer: LBVH build, ray cast, change list (mnav_obs::)
+#include "mnav_obstacle.h"   // obstacle layer: LBVH build, ray cast (mnav_obs::); the change list of mnav_changelist.h (mnav_chg::)
 #include "mnav_nbhd.h"       // height-difference / roughness / ridge layers: neighbourhood visits (mnav_nb::)
 #include "mnav_clearance.h"  // clearance / border layers: normal ray casts over the obstacle BVH, border test (mnav_clr::)
 
@@ -212,6 +212,7 @@ struct mnav_ctx {
   mnav_obs::Bvh obs;                                               // obstacle layer: BVH built by the first mnav_layer_obstacle after an upload
   mnav_nb::State nbhd;                                             // neighbourhood layers: counters, spill lists and scratch of the last call
   mnav_clr::State clr;                                             // clearance / border layers: cached clearance (first clearance call after an upload)
+  mnav_chg::Scratch chg;                                           // obstacle / clearance / border layers: change list and counters of the last call
   uint32_t infl_steps = 0, infl_bands = 0; uint64_t infl_evals = 0; float infl_ms = 0.f, infl_ms_wave = 0.f;   // last inflation wave
   DevBuf<TilePlan> d_tplans; uint32_t tplans_cap = 0;
   PinnedBuf<TCtl> h_tctl;
@@ -615,6 +616,7 @@ int mnav_upload_mesh(mnav_ctx* ctx, uint32_t V, uint32_t F, uint32_t E, const fl
   ctx->obs = {};                                                     // rebuilt lazily
   ctx->nbhd = {};                                                    // V-sized spill lists
   ctx->clr = {};                                                     // cached clearance: recast lazily
+  ctx->chg = {};                                                     // V-sized change list
   ctx->d_edge_dist.reset();
   drop_graphs(ctx);
   ctx->d_paths.reset(); ctx->paths_words = 0;
@@ -891,6 +893,59 @@ static int layer_slot(mnav_ctx* ctx, uint32_t layer, bool want_dist)
   return 0;
 }
 
+// Every writer of a slot but the inflation wave ends here: the slot holds a plain layer, and no wave distances / vector
+// field of an earlier inflation layer survive in it.
+static void layer_commit_plain(mnav_ctx::Layer& L)
+{
+  L.have_vec = false;
+  L.dist.reset();
+  L.ready = true;
+}
+
+// the scratch of the change-list pass: V ids, 3 words per block, the counters (once per mesh)
+static int change_scratch(mnav_ctx* ctx)
+{
+  using namespace mnav_chg;
+  Scratch& S = ctx->chg;
+  const size_t V = ctx->V ? ctx->V : 1, nblk = blocks(ctx->V) ? blocks(ctx->V) : 1;
+  if (!S.cnt) HIPCHK(alloc_group(S.ids, sizeof(uint32_t) * V, S.blk, sizeof(uint32_t) * 3 * nblk, S.cnt, sizeof(uint32_t) * kCounters));
+  return 0;
+}
+
+extern "C++" {
+// The pass that ends the obstacle, clearance and border layers (mnav_changelist.h): new costs and flags from `rule`, diffed
+// against the slot, written into it, `done` recorded; then the counters of the call (those of its ray cast included)
+// into `c`, the ascending change list into `changed_out` and the two totals into `n_changed` / `n_lethal` (each may be null).
+template <class Rule>
+static int layer_change_list(mnav_ctx* ctx, mnav_ctx::Layer& L, const Rule& rule, hipEvent_t done, uint32_t (&c)[mnav_chg::kCounters],
+                             uint32_t* changed_out, uint32_t* n_changed, uint32_t* n_lethal)
+{
+  using namespace mnav_chg;
+  if (change_scratch(ctx)) return -1;
+  Scratch& S = ctx->chg;
+  const uint32_t V = ctx->V, nblk = blocks(V), fresh = L.ready ? 0u : 1u;
+  if (nblk) {
+    hipLaunchKernelGGL(k_chg_count<Rule>, dim3(nblk), dim3(kChgBlock), 0, ctx->stream, V, rule, fresh, L.cost, L.lethal, S.blk, nblk);
+    hipLaunchKernelGGL(k_chg_scan, dim3(1), dim3(kChgBlock), 0, ctx->stream, nblk, S.blk, S.cnt);
+    hipLaunchKernelGGL(k_chg_emit<Rule>, dim3(nblk), dim3(kChgBlock), 0, ctx->stream, V, rule, fresh, L.cost, L.lethal, S.blk, nblk, S.ids);
+  } else {
+    HIPCHK(hipMemsetAsync(S.cnt + kChanged, 0, sizeof(uint32_t) * 2, ctx->stream));   // no vertex: k_chg_scan sets no totals
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(done, ctx->stream));
+  HIPCHK(hipMemcpyAsync(c, S.cnt, sizeof(c), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (changed_out && c[kChanged]) {
+    HIPCHK(hipMemcpyAsync(changed_out, S.ids, sizeof(uint32_t) * c[kChanged], hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+  }
+  layer_commit_plain(L);
+  if (n_changed) *n_changed = c[kChanged];
+  if (n_lethal) *n_lethal = c[kLethal];
+  return 0;
+}
+}  // extern "C++"
+
 static int ensure_edge_distances(mnav_ctx* ctx)
 {
   if (ctx->d_edge_dist) return 0;
@@ -913,7 +968,7 @@ int mnav_layer_upload(mnav_ctx* ctx, uint32_t layer, const float* costs, const u
   if (lethal) HIPCHK(hipMemcpyAsync(L.lethal, lethal, ctx->V, hipMemcpyHostToDevice, ctx->stream));
   else HIPCHK(hipMemsetAsync(L.lethal, 0, ctx->V ? ctx->V : 1, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  L.ready = true;
+  layer_commit_plain(L);
   return 0;
 }
 
@@ -927,7 +982,7 @@ int mnav_layer_steepness(mnav_ctx* ctx, uint32_t layer, double threshold)
   const uint32_t gb = (ctx->V + kBlock - 1) / kBlock;
   hipLaunchKernelGGL(k_steepness, dim3(gb ? gb : 1), dim3(kBlock), 0, ctx->stream, ctx->V, ctx->d_nrm, threshold, L.cost, L.lethal);
   HIPCHK(hipGetLastError());
-  L.ready = true;
+  layer_commit_plain(L);
   return 0;
 }
 

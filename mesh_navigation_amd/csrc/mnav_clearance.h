@@ -5,8 +5,8 @@
 // Clearance: one ray per vertex from p_v along its resident normal, closest hit over the obstacle layer's LBVH
 // (mnav_obstacle.h) with the faces that have v as a corner left out; the array is cached on the context and the cost
 // pass (computeLethalsAndCosts) runs on every call.  Border: v is a border vertex iff an edge of its CSR row has fewer
-// than two incident faces, counted over v's corner table.  Both end in the obstacle layer's diff + compaction scheme,
-// extended to compare the cost bits as well as the lethal flag.
+// than two incident faces, counted over v's corner table.  Both end in the diff + compaction pass of mnav_changelist.h,
+// comparing the cost bits as well as the lethal flag.
 //
 // The per-vertex rules (self-exclusion, usable normal, border predicate, the two cost mappings) are MNAV_HD functions
 // that g++ compiles too (tests/test_clearance_model.py); clr_vertex_host is the brute-force cast of one vertex on the
@@ -99,29 +99,11 @@ inline float clr_vertex_host(uint32_t v, const float* xyz, const float* nrm, con
 #if defined(__HIPCC__)
 namespace mnav_clr {
 
-using mnav_obs::kLeaf;
-using mnav_obs::kStack;
-using mnav_obs::kCastBlock;
-using mnav_obs::kOutBlock;
-using mnav_obs::kOutPer;
-
-// counters of one call (device words), in the obstacle layer's layout so that k_obs_scan fills kChanged / kLethal:
-// kKept = rays cast, kHits = rays that hit, kOverflow = waves whose traversal stack overflowed
-using mnav_obs::kKept;
-using mnav_obs::kHits;
-using mnav_obs::kOverflow;
-using mnav_obs::kChanged;
-using mnav_obs::kLethal;
-using mnav_obs::kCounters;
-
-// Per-context state: the cached clearance, the border flags and the scratch of the diff; dropped by mnav_upload_mesh.
+// Per-context state: the cached clearance and the border flags; dropped by mnav_upload_mesh.
 struct State {
   bool valid = false;            // clr holds the clearance of the resident mesh and normals
   DevBuf<float> clr;             // V
   DevBuf<uint8_t> border;        // V: border flags of the last mnav_layer_border
-  DevBuf<uint32_t> ids;          // V: change list
-  DevBuf<uint32_t> blk;          // 3 x blocks: changed per block, lethal per block, exclusive offsets
-  DevBuf<uint32_t> cnt;          // kCounters words
   uint32_t cast = 0, rays = 0, hits = 0;
   float ms_build = 0.f, ms_cast = 0.f, ms_total = 0.f;
 };
@@ -132,14 +114,14 @@ struct CastArgs {
   const float* __restrict__ nrm;
 };
 
-// One lane per vertex, in vertex order: the obstacle kernel's closest-hit traversal with the LDS stack, each lane with
-// its own RaySetup and slab inverses; faces with v as a corner are skipped at the leaves (Bvh::fvtx).
-__global__ __launch_bounds__(kCastBlock) void k_clr_cast(CastArgs A, const float4* __restrict__ nodes, const float4* __restrict__ tris,
+// One lane per vertex, in vertex order: the obstacle layer's closest-hit traversal (bvh_closest_hit) with the LDS stack,
+// each lane with its own RaySetup and slab inverses; faces with v as a corner are skipped at the leaves (Bvh::fvtx).
+__global__ __launch_bounds__(mnav_obs::kCastBlock) void k_clr_cast(CastArgs A, const float4* __restrict__ nodes, const float4* __restrict__ tris,
                                                          const uint32_t* __restrict__ fvtx, float* __restrict__ clr, uint32_t* __restrict__ cnt)
 {
-  __shared__ uint32_t stack[kStack * kCastBlock];
+  __shared__ uint32_t stack[mnav_obs::kStack * mnav_obs::kCastBlock];
   const uint32_t lane = threadIdx.x;
-  const uint32_t v = blockIdx.x * kCastBlock + lane;
+  const uint32_t v = blockIdx.x * mnav_obs::kCastBlock + lane;
   bool cast = false, hit = false, over = false;
   if (v < A.V) {
     const float n[3] = { A.nrm[3 * (size_t)v], A.nrm[3 * (size_t)v + 1], A.nrm[3 * (size_t)v + 2] };
@@ -150,48 +132,18 @@ __global__ __launch_bounds__(kCastBlock) void k_clr_cast(CastArgs A, const float
       const float o[3] = { A.xyz[3 * (size_t)v], A.xyz[3 * (size_t)v + 1], A.xyz[3 * (size_t)v + 2] };
       const mnav::RaySetup rs = mnav::ray_setup(n[0], n[1], n[2]);
       float inv[3];
-      for (int a = 0; a < 3; ++a) inv[a] = fabsf(n[a]) < 1e-30f ? copysignf(1e30f, n[a]) : 1.0f / n[a];
-      uint32_t sp = 0, node = A.root;
-      for (;;) {
-        if ((node & kLeaf) ? (node & ~kLeaf) >= A.F : node + 1 >= A.F) {
-          // not a node of this tree (cannot happen): nothing to test
-        } else if (node & kLeaf) {
-          const size_t k = node & ~kLeaf;
-          const float4 t0 = tris[3 * k], t1 = tris[3 * k + 1], t2 = tris[3 * k + 2];
-          const uint32_t f = __float_as_uint(t2.y);
-          if (!clr_excluded(v, fvtx[3 * (size_t)f], fvtx[3 * (size_t)f + 1], fvtx[3 * (size_t)f + 2])) {
-            const float a[3] = { t0.x, t0.y, t0.z }, b[3] = { t0.w, t1.x, t1.y }, c[3] = { t1.z, t1.w, t2.x };
-            float t;
-            if (mnav::ray_triangle(rs, o, a, b, c, &t) && (t < best || (t == best && f < best_f))) { best = t; best_f = f; }
-          }
-        } else {
-          const float4 q0 = nodes[4 * (size_t)node], q1 = nodes[4 * (size_t)node + 1], q2 = nodes[4 * (size_t)node + 2], q3 = nodes[4 * (size_t)node + 3];
-          const float bl[6] = { q0.x, q0.y, q0.z, q0.w, q1.x, q1.y }, br[6] = { q1.z, q1.w, q2.x, q2.y, q2.z, q2.w };
-          float tl, tr;
-          const bool hl = mnav_obs::obs_box(bl, o, inv, best, &tl), hr = mnav_obs::obs_box(br, o, inv, best, &tr);
-          const uint32_t cl = __float_as_uint(q3.x), cr = __float_as_uint(q3.y);
-          if (hl && hr) {
-            const uint32_t nearc = tl <= tr ? cl : cr, farc = tl <= tr ? cr : cl;
-            if (sp < (uint32_t)kStack) stack[sp++ * kCastBlock + lane] = farc;
-            else over = true;
-            node = nearc;
-            continue;
-          }
-          if (hl) { node = cl; continue; }
-          if (hr) { node = cr; continue; }
-        }
-        if (sp == 0) break;
-        node = stack[--sp * kCastBlock + lane];
-      }
+      for (int a = 0; a < 3; ++a) inv[a] = mnav::ray_slab_inverse(n[a]);
+      over = mnav_obs::bvh_closest_hit(A.F, A.root, nodes, tris, rs, o, inv, stack, lane,
+        [&](uint32_t f) { return clr_excluded(v, fvtx[3 * (size_t)f], fvtx[3 * (size_t)f + 1], fvtx[3 * (size_t)f + 2]); }, &best, &best_f);
       hit = best_f != kNone;
     }
     clr[v] = hit ? best : INFINITY;
   }
   const uint64_t bc = __ballot(cast), bh = __ballot(hit), bo = __ballot(over);
   if (lane == 0) {
-    if (bc) atomicAdd(&cnt[kKept], (uint32_t)__popcll(bc));
-    if (bh) atomicAdd(&cnt[kHits], (uint32_t)__popcll(bh));
-    if (bo) atomicAdd(&cnt[kOverflow], 1u);
+    if (bc) atomicAdd(&cnt[mnav_chg::kKept], (uint32_t)__popcll(bc));
+    if (bh) atomicAdd(&cnt[mnav_chg::kHits], (uint32_t)__popcll(bh));
+    if (bo) atomicAdd(&cnt[mnav_chg::kOverflow], 1u);
   }
 }
 
@@ -204,71 +156,20 @@ __global__ __launch_bounds__(256) void k_border(uint32_t V, const uint32_t* __re
   border[v] = border_vertex(nbr_e, row_ptr[v], row_ptr[v + 1], crn, crn_ptr[v], crn_ptr[v + 1]) ? 1 : 0;
 }
 
-enum : int { kModeClearance = 0, kModeBorder = 1 };
-
-// where the new cost of a vertex comes from: the cached clearance or the border flags, and the two parameters
-struct CostArgs {
+// change-list rules: a vertex changed iff its lethal flag or its cost bits did, and every vertex of a fresh slot
+struct ClearanceRule {
+  static constexpr bool kCostBits = true;
   const float* __restrict__ clr;
-  const uint8_t* __restrict__ border;
-  double p0, p1;                 // robot_height, height_inflation / border_cost, threshold
-  uint32_t fresh;                // the slot held no layer: every vertex counts as changed
+  double robot_height, height_inflation;
+  __device__ __forceinline__ float operator()(size_t v, uint8_t* lethal) const { return clr_cost(clr[v], robot_height, height_inflation, lethal); }
 };
 
-template <int MODE>
-__device__ __forceinline__ float clr_new(const CostArgs& A, size_t v, uint8_t* lethal)
-{
-  if (MODE == kModeClearance) return clr_cost(A.clr[v], A.p0, A.p1, lethal);
-  return border_cost_of(A.border[v] != 0, A.p0, A.p1, lethal);
-}
-
-// per block of kOutBlock * kOutPer vertices: how many vertices change (lethal flag or cost bits), how many are lethal
-template <int MODE>
-__global__ __launch_bounds__(kOutBlock) void k_clr_count(uint32_t V, CostArgs A, const float* __restrict__ cost, const uint8_t* __restrict__ lethal,
-                                                         uint32_t* __restrict__ blk, uint32_t nblk)
-{
-  __shared__ uint32_t lds[kOutBlock / 64];
-  const size_t v0 = ((size_t)blockIdx.x * kOutBlock + threadIdx.x) * kOutPer;
-  uint32_t c = 0, l = 0;
-  for (int k = 0; k < kOutPer; ++k)
-    if (v0 + k < V) {
-      uint8_t f;
-      const float x = clr_new<MODE>(A, v0 + k, &f);
-      c += A.fresh || f != lethal[v0 + k] || __float_as_uint(x) != __float_as_uint(cost[v0 + k]);
-      l += f;
-    }
-  uint32_t tc, tl;
-  (void)mnav_obs::obs_block_scan(c, lds, &tc);
-  (void)mnav_obs::obs_block_scan(l, lds, &tl);
-  if (threadIdx.x == 0) { blk[blockIdx.x] = tc; blk[nblk + blockIdx.x] = tl; }
-}
-
-// the changed ids in ascending order (block offset from k_obs_scan + lane prefix), then the layer's costs and flags
-template <int MODE>
-__global__ __launch_bounds__(kOutBlock) void k_clr_emit(uint32_t V, CostArgs A, float* __restrict__ cost, uint8_t* __restrict__ lethal,
-                                                        const uint32_t* __restrict__ blk, uint32_t nblk, uint32_t* __restrict__ ids)
-{
-  __shared__ uint32_t lds[kOutBlock / 64];
-  const size_t v0 = ((size_t)blockIdx.x * kOutBlock + threadIdx.x) * kOutPer;
-  float x[kOutPer];
-  uint8_t f[kOutPer], ch[kOutPer];
-  uint32_t c = 0;
-  for (int k = 0; k < kOutPer; ++k) {
-    x[k] = 0.f; f[k] = 0; ch[k] = 0;
-    if (v0 + k < V) {
-      x[k] = clr_new<MODE>(A, v0 + k, &f[k]);
-      ch[k] = A.fresh || f[k] != lethal[v0 + k] || __float_as_uint(x[k]) != __float_as_uint(cost[v0 + k]);
-      c += ch[k];
-    }
-  }
-  uint32_t tot;
-  uint32_t pos = blk[2 * nblk + blockIdx.x] + mnav_obs::obs_block_scan(c, lds, &tot);
-  for (int k = 0; k < kOutPer; ++k) {
-    if (v0 + k >= V) break;
-    if (ch[k]) ids[pos++] = (uint32_t)(v0 + k);
-    lethal[v0 + k] = f[k];
-    cost[v0 + k] = x[k];
-  }
-}
+struct BorderRule {
+  static constexpr bool kCostBits = true;
+  const uint8_t* __restrict__ border;
+  double border_cost, threshold;
+  __device__ __forceinline__ float operator()(size_t v, uint8_t* lethal) const { return border_cost_of(border[v] != 0, border_cost, threshold, lethal); }
+};
 
 }  // namespace mnav_clr
 #endif

@@ -3,60 +3,12 @@
 // after mnav_ctx, the host helpers and mnav_obstacle_capi.h (obstacle_build_bvh).
 #pragma once
 
-// the scratch of the diff + compaction: V ids, 3 words per output block, the counters (once per mesh)
-static int clr_scratch(mnav_ctx* ctx)
-{
-  using namespace mnav_clr;
-  State& S = ctx->clr;
-  const uint32_t V = ctx->V;
-  const uint32_t nblk = (uint32_t)(((size_t)V + kOutBlock * kOutPer - 1) / (kOutBlock * kOutPer));
-  if (!S.cnt)
-    HIPCHK(alloc_group(S.ids, sizeof(uint32_t) * (V ? V : 1), S.blk, sizeof(uint32_t) * 3 * (nblk ? nblk : 1), S.cnt, sizeof(uint32_t) * kCounters));
-  return 0;
-}
-
-extern "C++" {
-// The cost pass of both layers: new costs and flags from `A`, diffed against the slot, ascending change list.  The slot is
-// written only here, after every check has passed.
-template <int MODE>
-static int clr_emit(mnav_ctx* ctx, mnav_ctx::Layer& L, mnav_clr::CostArgs A, uint32_t* changed_out, uint32_t* n_changed, uint32_t* n_lethal)
-{
-  using namespace mnav_clr;
-  State& S = ctx->clr;
-  const uint32_t V = ctx->V;
-  const uint32_t nblk = (uint32_t)(((size_t)V + kOutBlock * kOutPer - 1) / (kOutBlock * kOutPer));
-  if (clr_scratch(ctx)) return -1;
-  A.fresh = L.ready ? 0u : 1u;
-  HIPCHK(hipMemsetAsync(S.cnt + kChanged, 0, sizeof(uint32_t) * 2, ctx->stream));
-  if (nblk) {
-    hipLaunchKernelGGL(k_clr_count<MODE>, dim3(nblk), dim3(kOutBlock), 0, ctx->stream, V, A, L.cost, L.lethal, S.blk, nblk);
-    hipLaunchKernelGGL(mnav_obs::k_obs_scan, dim3(1), dim3(kOutBlock), 0, ctx->stream, nblk, S.blk, S.cnt);
-    hipLaunchKernelGGL(k_clr_emit<MODE>, dim3(nblk), dim3(kOutBlock), 0, ctx->stream, V, A, L.cost, L.lethal, S.blk, nblk, S.ids);
-  }
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(ctx->ev[7], ctx->stream));
-  uint32_t c[kCounters];
-  HIPCHK(hipMemcpyAsync(c, S.cnt, sizeof(c), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  if (changed_out && c[kChanged]) {
-    HIPCHK(hipMemcpyAsync(changed_out, S.ids, sizeof(uint32_t) * c[kChanged], hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-  }
-  // the slot now holds this layer: no wave distances / vector field of an earlier inflation layer survive
-  L.have_vec = false;
-  L.dist.reset();
-  L.ready = true;
-  if (n_changed) *n_changed = c[kChanged];
-  if (n_lethal) *n_lethal = c[kLethal];
-  return 0;
-}
-}  // extern "C++"
-
 // the clearance of every vertex into the cache: the BVH (unless an obstacle call built it), then one ray per vertex.  On
 // any failure the cache stays invalid.
 static int clr_cast(mnav_ctx* ctx)
 {
   using namespace mnav_clr;
+  using namespace mnav_chg;
   State& S = ctx->clr;
   mnav_obs::Bvh& B = ctx->obs;
   const uint32_t V = ctx->V;
@@ -67,16 +19,17 @@ static int clr_cast(mnav_ctx* ctx)
     S.ms_build = B.ms_build;
   }
   if (!S.clr) HIPCHK(S.clr.alloc(sizeof(float) * (V ? V : 1)));
-  if (clr_scratch(ctx)) return -1;
+  if (change_scratch(ctx)) return -1;
+  uint32_t* const cnt = ctx->chg.cnt;
   const CastArgs A{ V, B.F, B.root, ctx->d_xyz, ctx->d_nrm };
-  HIPCHK(hipMemsetAsync(S.cnt, 0, sizeof(uint32_t) * kCounters, ctx->stream));
+  HIPCHK(hipMemsetAsync(cnt, 0, sizeof(uint32_t) * kCounters, ctx->stream));
   HIPCHK(hipEventRecord(ctx->ev[0], ctx->stream));
-  if (V) hipLaunchKernelGGL(k_clr_cast, dim3((V + kCastBlock - 1) / kCastBlock), dim3(kCastBlock), 0, ctx->stream, A, B.nodes, B.tris, B.fvtx,
-                            S.clr, S.cnt);
+  const uint32_t wave = mnav_obs::kCastBlock;
+  if (V) hipLaunchKernelGGL(k_clr_cast, dim3((V + wave - 1) / wave), dim3(wave), 0, ctx->stream, A, B.nodes, B.tris, B.fvtx, S.clr, cnt);
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
   uint32_t c[kCounters];
-  HIPCHK(hipMemcpyAsync(c, S.cnt, sizeof(c), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(c, cnt, sizeof(c), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   S.rays = c[kKept]; S.hits = c[kHits];
   S.ms_cast = ev_ms(ctx->ev[0], ctx->ev[1]);
@@ -109,8 +62,9 @@ int mnav_layer_clearance(mnav_ctx* ctx, uint32_t layer, double robot_height, dou
     S.ms_build = S.ms_cast = 0.f;
   }
   if (layer_slot(ctx, layer, false)) return -1;
-  const CostArgs A{ S.clr, nullptr, robot_height, height_inflation, 0u };
-  if (clr_emit<kModeClearance>(ctx, ctx->layers[layer], A, changed_out, n_changed, n_lethal)) return -1;
+  uint32_t c[mnav_chg::kCounters];
+  const ClearanceRule rule{ S.clr, robot_height, height_inflation };
+  if (layer_change_list(ctx, ctx->layers[layer], rule, ctx->ev[7], c, changed_out, n_changed, n_lethal)) return -1;
   S.ms_total = ev_ms(ctx->ev[6], ctx->ev[7]);
   return 0;
 }
@@ -131,8 +85,8 @@ int mnav_layer_border(mnav_ctx* ctx, uint32_t layer, double border_cost, double 
   if (V) hipLaunchKernelGGL(k_border, dim3((V + 255) / 256), dim3(256), 0, ctx->stream, V, ctx->d_row_ptr, ctx->d_nbr_e, ctx->d_crn_ptr,
                             ctx->d_crn_idx, S.border);
   HIPCHK(hipGetLastError());
-  const CostArgs A{ nullptr, S.border, border_cost, threshold, 0u };
-  return clr_emit<kModeBorder>(ctx, ctx->layers[layer], A, changed_out, n_changed, n_lethal);
+  uint32_t c[mnav_chg::kCounters];
+  return layer_change_list(ctx, ctx->layers[layer], BorderRule{ S.border, border_cost, threshold }, ctx->ev[7], c, changed_out, n_changed, n_lethal);
 }
 
 int mnav_clearance_download(const mnav_ctx* cctx, float* clearance_out)

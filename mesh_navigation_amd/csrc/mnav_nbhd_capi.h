@@ -95,10 +95,7 @@ static int nbhd_layer(mnav_ctx* ctx, int op, uint32_t layer, double radius, doub
   const int rc = op == kHeight ? nbhd_launch<kHeight>(ctx, L, M, &spilled)
                : op == kRough ? nbhd_launch<kRough>(ctx, L, M, &spilled) : nbhd_launch<kRidge>(ctx, L, M, &spilled);
   if (rc) return rc;
-  // the slot now holds a neighbourhood layer: no wave distances / vector field of an earlier inflation layer survive
-  L.have_vec = false;
-  L.dist.reset();
-  L.ready = true;
+  layer_commit_plain(L);
   ctx->nbhd.centres = ctx->V;
   ctx->nbhd.spilled = spilled;
   return 0;

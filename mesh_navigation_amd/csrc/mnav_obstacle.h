@@ -1,13 +1,14 @@
 // mnav_obstacle.h -- kernels of the obstacle layer (mnav_layer_obstacle; ObstacleLayer::processPointCloud,
 // obstacle_layer.cpp:134-290): a linear BVH over the resident faces (Karras 2012: Morton codes of the face centroids,
 // radix sort, hierarchy emission, bottom-up refit with one arrival counter per node), one lane per ray for the
-// closest-hit traversal (mnav_ray.h), then the new lethal set is diffed against the layer's old one and compacted into
-// the ascending change list.  Included by mnav.hip after the anonymous namespace of the planner kernels; the C ABI
-// is in mnav_obstacle_capi.h.
+// closest-hit traversal (mnav_ray.h; bvh_closest_hit, which the clearance layer casts with too), then the new lethal set
+// is diffed against the layer's old one and compacted into the ascending change list (mnav_changelist.h).  Included by
+// mnav.hip after the anonymous namespace of the planner kernels; the C ABI is in mnav_obstacle_capi.h.
 #pragma once
 
 #include <rocprim/device/device_radix_sort.hpp>
 
+#include "mnav_changelist.h"
 #include "mnav_ray.h"
 
 namespace mnav_obs {
@@ -15,10 +16,6 @@ namespace mnav_obs {
 constexpr uint32_t kLeaf = 0x80000000u;   // child reference: leaf (sorted position) | kLeaf, else an internal node
 constexpr int kStack = 64;                // traversal stack per lane (LDS): a root-to-leaf path has <= 62 internal nodes
 constexpr int kCastBlock = 64;            // one wave per workgroup: 16 KiB of LDS stack
-constexpr int kOutBlock = 256;            // output passes: 4 vertices per lane
-constexpr int kOutPer = 4;
-// counters of one call (device words)
-enum { kKept = 0, kHits, kLethalRays, kOverflow, kChanged, kLethal, kCounters };
 
 // Resident acceleration structure + per-call scratch of the obstacle layer; built on the first call after a mesh
 // upload, dropped by the next upload and by mnav_destroy.
@@ -29,9 +26,6 @@ struct Bvh {
   DevBuf<float4> tris;         // F leaves in Morton order x 3 float4: a.xyz b.xyz c.xyz, original face id (bits)
   DevBuf<uint32_t> fvtx;       // 3F vertex ids, original face order
   DevBuf<uint8_t> flags;       // V: lethal flags of the current call
-  DevBuf<uint32_t> ids;        // V: change list
-  DevBuf<uint32_t> blk;        // 3 x blocks: changed per block, lethal per block, exclusive offsets
-  DevBuf<uint32_t> cnt;        // kCounters words
   DevBuf<uint8_t> pts; size_t pts_cap = 0;
   float ms_build = 0.f, ms_cast = 0.f, ms_total = 0.f;
   uint32_t kept = 0, hits = 0, lethal_rays = 0;
@@ -187,6 +181,50 @@ __device__ __forceinline__ bool obs_box(const float* b, const float o[3], const 
   return tn <= tf * 1.000001f && tn <= best;
 }
 
+// closest hit of one ray over the BVH (ties: smallest face id); `skip(f)` leaves face f out.  Returns true on a stack overflow.
+template <class Skip>
+__device__ __forceinline__ bool bvh_closest_hit(uint32_t F, uint32_t root, const float4* __restrict__ nodes, const float4* __restrict__ tris,
+                                                const RaySetup& rs, const float* o, const float* inv, uint32_t* stack, uint32_t lane, Skip skip,
+                                                float* best_out, uint32_t* best_f_out)
+{
+  bool over = false;
+  float best = INFINITY;
+  uint32_t best_f = kNone, sp = 0, node = root;
+  for (;;) {
+    if ((node & kLeaf) ? (node & ~kLeaf) >= F : node + 1 >= F) {
+      // not a node of this tree (cannot happen): nothing to test
+    } else if (node & kLeaf) {
+      const size_t k = node & ~kLeaf;
+      const float4 t0 = tris[3 * k], t1 = tris[3 * k + 1], t2 = tris[3 * k + 2];
+      const uint32_t f = __float_as_uint(t2.y);
+      if (!skip(f)) {
+        const float a[3] = { t0.x, t0.y, t0.z }, b[3] = { t0.w, t1.x, t1.y }, c[3] = { t1.z, t1.w, t2.x };
+        float t;
+        if (ray_triangle(rs, o, a, b, c, &t) && (t < best || (t == best && f < best_f))) { best = t; best_f = f; }
+      }
+    } else {
+      const float4 q0 = nodes[4 * (size_t)node], q1 = nodes[4 * (size_t)node + 1], q2 = nodes[4 * (size_t)node + 2], q3 = nodes[4 * (size_t)node + 3];
+      const float bl[6] = { q0.x, q0.y, q0.z, q0.w, q1.x, q1.y }, br[6] = { q1.z, q1.w, q2.x, q2.y, q2.z, q2.w };
+      float tl, tr;
+      const bool hl = obs_box(bl, o, inv, best, &tl), hr = obs_box(br, o, inv, best, &tr);
+      const uint32_t cl = __float_as_uint(q3.x), cr = __float_as_uint(q3.y);
+      if (hl && hr) {
+        const uint32_t nearc = tl <= tr ? cl : cr, farc = tl <= tr ? cr : cl;
+        if (sp < (uint32_t)kStack) stack[sp++ * kCastBlock + lane] = farc;
+        else over = true;
+        node = nearc;
+        continue;
+      }
+      if (hl) { node = cl; continue; }
+      if (hr) { node = cr; continue; }
+    }
+    if (sp == 0) break;
+    node = stack[--sp * kCastBlock + lane];
+  }
+  *best_out = best; *best_f_out = best_f;
+  return over;
+}
+
 struct CastArgs {
   uint32_t n, step, F, root;
   float m[12];
@@ -214,37 +252,8 @@ __global__ __launch_bounds__(kCastBlock) void k_obs_cast(CastArgs A, const uint8
     float o[3];
     ray_transform(A.m, x, y, z, o);
     if (kept && A.F && ray_origin_finite(o)) {
-      float best = INFINITY;
-      uint32_t best_f = kNone, sp = 0, node = A.root;
-      for (;;) {
-        if ((node & kLeaf) ? (node & ~kLeaf) >= A.F : node + 1 >= A.F) {
-          // not a node of this tree (cannot happen): nothing to test
-        } else if (node & kLeaf) {
-          const size_t k = node & ~kLeaf;
-          const float4 t0 = tris[3 * k], t1 = tris[3 * k + 1], t2 = tris[3 * k + 2];
-          const float a[3] = { t0.x, t0.y, t0.z }, b[3] = { t0.w, t1.x, t1.y }, c[3] = { t1.z, t1.w, t2.x };
-          const uint32_t f = __float_as_uint(t2.y);
-          float t;
-          if (ray_triangle(A.rs, o, a, b, c, &t) && (t < best || (t == best && f < best_f))) { best = t; best_f = f; }
-        } else {
-          const float4 q0 = nodes[4 * (size_t)node], q1 = nodes[4 * (size_t)node + 1], q2 = nodes[4 * (size_t)node + 2], q3 = nodes[4 * (size_t)node + 3];
-          const float bl[6] = { q0.x, q0.y, q0.z, q0.w, q1.x, q1.y }, br[6] = { q1.z, q1.w, q2.x, q2.y, q2.z, q2.w };
-          float tl, tr;
-          const bool hl = obs_box(bl, o, A.inv, best, &tl), hr = obs_box(br, o, A.inv, best, &tr);
-          const uint32_t cl = __float_as_uint(q3.x), cr = __float_as_uint(q3.y);
-          if (hl && hr) {
-            const uint32_t nearc = tl <= tr ? cl : cr, farc = tl <= tr ? cr : cl;
-            if (sp < (uint32_t)kStack) stack[sp++ * kCastBlock + lane] = farc;
-            else over = true;
-            node = nearc;
-            continue;
-          }
-          if (hl) { node = cl; continue; }
-          if (hr) { node = cr; continue; }
-        }
-        if (sp == 0) break;
-        node = stack[--sp * kCastBlock + lane];
-      }
+      float best; uint32_t best_f;
+      over = bvh_closest_hit(A.F, A.root, nodes, tris, A.rs, o, A.inv, stack, lane, [](uint32_t) { return false; }, &best, &best_f);
       if (best_f != kNone) {
         hit = true;
         if ((double)best <= A.robot_height) {
@@ -256,81 +265,22 @@ __global__ __launch_bounds__(kCastBlock) void k_obs_cast(CastArgs A, const uint8
   }
   const uint64_t bk = __ballot(kept), bh = __ballot(hit), bl = __ballot(leth), bo = __ballot(over);
   if (lane == 0) {
-    if (bk) atomicAdd(&cnt[kKept], (uint32_t)__popcll(bk));
-    if (bh) atomicAdd(&cnt[kHits], (uint32_t)__popcll(bh));
-    if (bl) atomicAdd(&cnt[kLethalRays], (uint32_t)__popcll(bl));
-    if (bo) atomicAdd(&cnt[kOverflow], 1u);
+    if (bk) atomicAdd(&cnt[mnav_chg::kKept], (uint32_t)__popcll(bk));
+    if (bh) atomicAdd(&cnt[mnav_chg::kHits], (uint32_t)__popcll(bh));
+    if (bl) atomicAdd(&cnt[mnav_chg::kLethalRays], (uint32_t)__popcll(bl));
+    if (bo) atomicAdd(&cnt[mnav_chg::kOverflow], 1u);
   }
 }
 
-// exclusive scan of one value per lane over a block of kOutBlock lanes; *total = the block's sum
-__device__ __forceinline__ uint32_t obs_block_scan(uint32_t v, uint32_t* lds, uint32_t* total)
-{
-  const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  uint32_t s = v;
-  for (int off = 1; off < 64; off <<= 1) { const uint32_t u = __shfl_up(s, off); if (lane >= (uint32_t)off) s += u; }
-  if (lane == 63) lds[w] = s;
-  __syncthreads();
-  uint32_t base = 0, all = 0;
-  for (uint32_t k = 0; k < kOutBlock / 64; ++k) { if (k < w) base += lds[k]; all += lds[k]; }
-  __syncthreads();
-  *total = all;
-  return base + s - v;
-}
-
-// per block of kOutBlock * kOutPer vertices: how many flags change, how many are lethal
-__global__ __launch_bounds__(kOutBlock) void k_obs_count(uint32_t V, const uint8_t* __restrict__ flags, const uint8_t* __restrict__ old,
-                                                         uint32_t* __restrict__ blk, uint32_t nblk)
-{
-  __shared__ uint32_t lds[kOutBlock / 64];
-  const size_t v0 = ((size_t)blockIdx.x * kOutBlock + threadIdx.x) * kOutPer;
-  uint32_t c = 0, l = 0;
-  for (int k = 0; k < kOutPer; ++k)
-    if (v0 + k < V) { const uint8_t f = flags[v0 + k]; c += f != old[v0 + k]; l += f; }
-  uint32_t tc, tl;
-  (void)obs_block_scan(c, lds, &tc);
-  (void)obs_block_scan(l, lds, &tl);
-  if (threadIdx.x == 0) { blk[blockIdx.x] = tc; blk[nblk + blockIdx.x] = tl; }
-}
-
-// one workgroup: exclusive offsets of the per-block change counts, totals into cnt
-__global__ __launch_bounds__(kOutBlock) void k_obs_scan(uint32_t nblk, uint32_t* __restrict__ blk, uint32_t* __restrict__ cnt)
-{
-  __shared__ uint32_t lds[kOutBlock / 64];
-  uint32_t carry = 0, lethal = 0;
-  for (uint32_t b0 = 0; b0 < nblk; b0 += kOutBlock) {
-    const uint32_t b = b0 + threadIdx.x;
-    const uint32_t c = b < nblk ? blk[b] : 0, l = b < nblk ? blk[nblk + b] : 0;
-    uint32_t tc, tl;
-    const uint32_t ex = obs_block_scan(c, lds, &tc);
-    (void)obs_block_scan(l, lds, &tl);
-    if (b < nblk) blk[2 * nblk + b] = carry + ex;
-    carry += tc; lethal += tl;
+// change-list rule: the flags of this call are the slot's new lethal set, cost +inf / 0; a vertex changed iff its flag did
+struct FlagRule {
+  static constexpr bool kCostBits = false;
+  const uint8_t* __restrict__ flags;
+  __device__ __forceinline__ float operator()(size_t v, uint8_t* lethal) const
+  {
+    *lethal = flags[v];
+    return *lethal ? INFINITY : 0.f;
   }
-  if (threadIdx.x == 0) { cnt[kChanged] = carry; cnt[kLethal] = lethal; }
-}
-
-// the changed ids in ascending order (block offset + lane prefix), then the layer's flags and costs (+inf / 0)
-__global__ __launch_bounds__(kOutBlock) void k_obs_emit(uint32_t V, const uint8_t* __restrict__ flags, uint8_t* __restrict__ lethal,
-                                                        float* __restrict__ cost, const uint32_t* __restrict__ blk, uint32_t nblk,
-                                                        uint32_t* __restrict__ ids)
-{
-  __shared__ uint32_t lds[kOutBlock / 64];
-  const size_t v0 = ((size_t)blockIdx.x * kOutBlock + threadIdx.x) * kOutPer;
-  uint8_t f[kOutPer], ch[kOutPer];
-  uint32_t c = 0;
-  for (int k = 0; k < kOutPer; ++k) {
-    f[k] = 0; ch[k] = 0;
-    if (v0 + k < V) { f[k] = flags[v0 + k]; ch[k] = f[k] != lethal[v0 + k]; c += ch[k]; }
-  }
-  uint32_t tot;
-  uint32_t pos = blk[2 * nblk + blockIdx.x] + obs_block_scan(c, lds, &tot);
-  for (int k = 0; k < kOutPer; ++k) {
-    if (v0 + k >= V) break;
-    if (ch[k]) ids[pos++] = (uint32_t)(v0 + k);
-    lethal[v0 + k] = f[k];
-    cost[v0 + k] = f[k] ? INFINITY : 0.f;
-  }
-}
+};
 
 }  // namespace mnav_obs

@@ -57,6 +57,7 @@ int mnav_layer_obstacle(mnav_ctx* ctx, uint32_t layer, uint32_t n_points, const 
                         uint32_t* changed_out, uint32_t* n_changed, uint32_t* n_lethal)
 {
   using namespace mnav_obs;
+  using namespace mnav_chg;
   if (!ctx) return -1;
   ctx->err.clear();
   if (point_step < 12) { ctx->err = "point_step must be at least 12 bytes (x, y, z floats at offsets 0, 4, 8)"; return -1; }
@@ -69,10 +70,9 @@ int mnav_layer_obstacle(mnav_ctx* ctx, uint32_t layer, uint32_t n_points, const 
   Bvh& B = ctx->obs;
   const uint32_t V = ctx->V;
   if (!B.valid && obstacle_build_bvh(ctx)) { B = Bvh{}; return -1; }
-  const uint32_t nblk = (uint32_t)(((size_t)V + kOutBlock * kOutPer - 1) / (kOutBlock * kOutPer));
-  if (!B.flags)
-    HIPCHK(alloc_group(B.flags, V ? V : 1, B.ids, sizeof(uint32_t) * (V ? V : 1), B.blk, sizeof(uint32_t) * 3 * (nblk ? nblk : 1),
-                       B.cnt, sizeof(uint32_t) * kCounters));
+  if (!B.flags) HIPCHK(B.flags.alloc(V ? V : 1));
+  if (change_scratch(ctx)) return -1;
+  uint32_t* const cnt = ctx->chg.cnt;
   const size_t bytes = (size_t)n_points * point_step;
   if (bytes > B.pts_cap) {
     B.pts_cap = 0;
@@ -84,43 +84,22 @@ int mnav_layer_obstacle(mnav_ctx* ctx, uint32_t layer, uint32_t n_points, const 
   static const float kIdentity[12] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0 };
   std::memcpy(A.m, sensor_to_map ? sensor_to_map : kIdentity, sizeof(A.m));
   A.rs = ray_setup(down_axis[0], down_axis[1], down_axis[2]);
-  for (int a = 0; a < 3; ++a) {                                 // finite slab slopes: a zero component never makes 0 * inf
-    const float d = down_axis[a];
-    A.inv[a] = std::fabs(d) < 1e-30f ? std::copysign(1e30f, d) : 1.0f / d;
-  }
+  for (int a = 0; a < 3; ++a) A.inv[a] = ray_slab_inverse(down_axis[a]);
   A.max_dist = max_obstacle_dist; A.robot_height = robot_height;
   HIPCHK(hipEventRecord(ctx->ev[0], ctx->stream));
   if (!L.ready) HIPCHK(hipMemsetAsync(L.lethal, 0, V ? V : 1, ctx->stream));   // a fresh slot: the old set is empty
   HIPCHK(hipMemsetAsync(B.flags, 0, V ? V : 1, ctx->stream));
-  HIPCHK(hipMemsetAsync(B.cnt, 0, sizeof(uint32_t) * kCounters, ctx->stream));
+  HIPCHK(hipMemsetAsync(cnt, 0, sizeof(uint32_t) * kCounters, ctx->stream));
   if (bytes) HIPCHK(hipMemcpyAsync(B.pts, points, bytes, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
   if (n_points) hipLaunchKernelGGL(k_obs_cast, dim3((n_points + kCastBlock - 1) / kCastBlock), dim3(kCastBlock), 0, ctx->stream, A, B.pts,
-                                   B.nodes, B.tris, B.fvtx, B.flags, B.cnt);
+                                   B.nodes, B.tris, B.fvtx, B.flags, cnt);
   HIPCHK(hipEventRecord(ctx->ev[2], ctx->stream));
-  if (nblk) {
-    hipLaunchKernelGGL(k_obs_count, dim3(nblk), dim3(kOutBlock), 0, ctx->stream, V, B.flags, L.lethal, B.blk, nblk);
-    hipLaunchKernelGGL(k_obs_scan, dim3(1), dim3(kOutBlock), 0, ctx->stream, nblk, B.blk, B.cnt);
-    hipLaunchKernelGGL(k_obs_emit, dim3(nblk), dim3(kOutBlock), 0, ctx->stream, V, B.flags, L.lethal, L.cost, B.blk, nblk, B.ids);
-  }
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(ctx->ev[3], ctx->stream));
   uint32_t c[kCounters];
-  HIPCHK(hipMemcpyAsync(c, B.cnt, sizeof(c), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  if (changed_out && c[kChanged]) {
-    HIPCHK(hipMemcpyAsync(changed_out, B.ids, sizeof(uint32_t) * c[kChanged], hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-  }
-  // the slot now holds an obstacle layer: no wave distances / vector field of an earlier inflation layer survive
-  L.have_vec = false;
-  L.dist.reset();
-  L.ready = true;
+  if (layer_change_list(ctx, L, FlagRule{ B.flags }, ctx->ev[3], c, changed_out, n_changed, n_lethal)) return -1;
   B.kept = c[kKept]; B.hits = c[kHits]; B.lethal_rays = c[kLethalRays];
   B.ms_cast = ev_ms(ctx->ev[1], ctx->ev[2]);
   B.ms_total = ev_ms(ctx->ev[0], ctx->ev[3]);
-  if (n_changed) *n_changed = c[kChanged];
-  if (n_lethal) *n_lethal = c[kLethal];
   if (c[kOverflow]) { ctx->err = "obstacle ray cast: BVH traversal stack overflow"; return -1; }
   return 0;
 }

@@ -48,6 +48,10 @@ MNAV_RAY_HD RaySetup ray_setup(float dx, float dy, float dz)
   return s;
 }
 
+// The slope of the BVH's slab test along one axis of the direction: 1 / d, kept finite so that a zero component never
+// makes 0 * inf.
+MNAV_RAY_HD float ray_slab_inverse(float d) { return fabsf(d) < 1e-30f ? copysignf(1e30f, d) : 1.0f / d; }
+
 // Ray (origin o, direction of `s`) against triangle (a, b, c), each a float[3].  Returns 1 and *t_out = T / det on a
 // hit with t >= 0 (either side of the face), 0 otherwise.  A face with det == 0 (degenerate in the ray's shear
 // space: repeated or collinear vertices) never hits; neither does anything that produces a NaN t.

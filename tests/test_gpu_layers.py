@@ -187,3 +187,49 @@ def test_isolated_lethal_vertices_with_tied_pop_times_settle(gpu_ctx_factory, i)
     assert np.array_equal(bits(d), bits(dist)), int((bits(d) != bits(dist)).sum())
     assert np.array_equal(bits(c), bits(cost))
     assert st["steps"] < 20000                                         # (a band that goes through the exact band routine idles through the rest of its chunk of steps)
+
+
+@pytest.mark.parametrize("writer", ["upload", "steepness"])
+def test_a_plain_layer_written_over_an_inflation_layer_drops_its_wave_state(gpu_ctx_factory, writer):
+    """A slot that held an inflation layer and is then overwritten by mnav_layer_upload / mnav_layer_steepness holds a plain
+    layer: its costs and flags are the new ones bit for bit, and the old wave's distances and vector field are gone -- they
+    cannot be downloaded, and the back-tracking does not steer on them."""
+    rng = np.random.default_rng(11)
+    mesh = meshgen.terrain(44, 0.1, 12, amplitude=0.3)
+    N = mesh.N
+    lethal = np.zeros(mesh.V, np.uint8)
+    i, j = np.meshgrid(np.arange(N), np.arange(N))
+    lethal[(((j == 18) | (j == 25)) & (i > 3) & (i < N - 4)).ravel()] = 1            # a corridor between two lethal walls
+    case = Case(mesh)
+    goal = mesh.xyz[21 * N + 6] + np.array([0.02, 0.03, 0.0], np.float32)
+    robot = mesh.xyz[22 * N + N - 8] + np.array([0.03, 0.01, 0.0], np.float32)
+    sf, _ = case.om.containing_face(goal)
+    tf, _ = case.om.containing_face(robot)
+    ctx = gpu_ctx_factory()
+    upload(ctx, case)
+    ctx.layer_upload(0, np.zeros(mesh.V, np.float32), lethal)
+    ctx.layer_inflation(1, 0)
+    ctx.combine_layers([1], [1.0], mode="max", edge_cost_factor=1.0)
+    ctx.set_resident_outputs(True)
+    assert ctx.plan_cvp(goal, sf, tf, want_fields=False, want_vecmap=False).code == 0
+    # the inflation layer: distances, a vector field, and the walk takes it
+    ctx.layer_download(1, distances=True)
+    ctx.layer_vectors(1)
+    assert ctx.backtrack_cvp(goal, sf, robot, tf, step_width=0.2, inflation_layer=1)[0] == 1
+    if writer == "upload":
+        want_c = rng.uniform(0, 1.4, mesh.V).astype(np.float32)
+        want_l = (rng.random(mesh.V) < 0.1).astype(np.uint8)
+        ctx.layer_upload(1, want_c, want_l)
+    else:
+        ctx.layer_steepness(2, 0.3)                              # the device's own steepness, in a slot that never held a wave
+        want_c, want_l = ctx.layer_download(2)
+        ctx.layer_steepness(1, 0.3)
+    c, le = ctx.layer_download(1)
+    assert np.array_equal(bits(c), bits(want_c)) and np.array_equal(le, want_l)
+    with pytest.raises(RuntimeError, match="this layer keeps no distances"):
+        ctx.layer_download(1, distances=True)
+    with pytest.raises(RuntimeError, match="this layer has no vector field"):
+        ctx.layer_vectors(1)
+    with pytest.raises(RuntimeError, match="back-tracking: not a resident inflation layer with a vector field"):
+        ctx.backtrack_cvp(goal, sf, robot, tf, step_width=0.2, inflation_layer=1)
+    assert ctx.backtrack_cvp(goal, sf, robot, tf, step_width=0.2)[0] == 1           # the plan's own field is untouched
