@@ -202,3 +202,43 @@ def fan_field(spokes: int = 40, rings: int = 6, seed: int = 0) -> TerrainMesh:
             c, d = vid(r + 1, s), vid(r + 1, s + 1)
             faces.append((a, c, b)); faces.append((b, c, d))
     return from_faces(xyz, np.asarray(faces, np.uint32))
+
+
+def union_jack(N: int, h: float = 0.1, seed: int = 0, amplitude: float = 0.5, flat: bool = False) -> TerrainMesh:
+    """The terrain's vertices with the cell diagonal alternating with (i + j) % 2: interior vertices alternate between
+    valence 8 ((i + j) even) and valence 4.  `flat` takes flat_grid's vertices instead (terrain jitters x and y, so
+    amplitude 0 alone leaves every potential distinct): many equal potentials."""
+    xyz = flat_grid(N, h).xyz if flat else terrain(N, h, seed, amplitude=amplitude).xyz
+    n = N - 1
+    i, j = np.meshgrid(np.arange(n, dtype=np.int64), np.arange(n, dtype=np.int64))
+    v00 = (j * N + i).ravel()
+    v10, v01, v11 = v00 + 1, v00 + N, v00 + N + 1
+    even = ((i + j) % 2 == 0).ravel()
+    faces = np.empty((n * n, 6), np.int64)            # even cell: (v00, v10, v11), (v00, v11, v01); odd: (v00, v10, v01), (v10, v11, v01)
+    faces[:, 0], faces[:, 1], faces[:, 2] = v00, v10, np.where(even, v11, v01)
+    faces[:, 3], faces[:, 4], faces[:, 5] = np.where(even, v00, v10), v11, v01
+    return from_faces(xyz, faces.reshape(-1, 3).astype(np.uint32), N=N, h=h)
+
+
+def hub_terrain(N: int, hubs, h: float = 0.1, seed: int = 0, amplitude: float = 0.5) -> TerrainMesh:
+    """Terrain with hubs: for every (ci, cj, k) the 2k x 2k block of cells around grid vertex (ci, cj) is removed and
+    re-triangulated as a fan from that vertex to the block's boundary ring -- a hub of valence 8k, its former interior
+    neighbours left without any face.  Blocks lie inside the grid and share no cell; the mesh stays manifold."""
+    t = terrain(N, h, seed, amplitude=amplitude)
+    n = N - 1
+    taken = np.zeros((n, n), bool)                    # [cell row j, cell column i]
+    fans = []
+    for ci, cj, k in hubs:
+        if k < 1 or ci - k < 0 or cj - k < 0 or ci + k > n or cj + k > n:
+            raise ValueError(f"hub {(ci, cj, k)} leaves the grid")
+        if taken[cj - k:cj + k, ci - k:ci + k].any():
+            raise ValueError(f"hub {(ci, cj, k)} overlaps another hub")
+        taken[cj - k:cj + k, ci - k:ci + k] = True
+        ring = [(ci - k + s, cj - k) for s in range(2 * k)] + [(ci + k, cj - k + s) for s in range(2 * k)] \
+             + [(ci + k - s, cj + k) for s in range(2 * k)] + [(ci - k, cj + k - s) for s in range(2 * k)]   # counter-clockwise
+        ids = [j * N + i for i, j in ring]
+        c = cj * N + ci
+        fans += [(c, ids[s], ids[(s + 1) % len(ids)]) for s in range(len(ids))]
+    keep = np.repeat(~taken.ravel(), 2)               # two faces per cell, cell-major
+    faces = np.concatenate([t.faces[keep], np.asarray(fans, np.uint32).reshape(-1, 3)])
+    return from_faces(t.xyz, faces, N=N, h=h)

@@ -33,7 +33,7 @@ def test_auto_takes_the_async_engine_for_single_plans_and_small_batches(gpu_ctx_
                 o = ctx.plan_dijkstra(int(g), robot, goal_dist_offset=off)
                 assert o.stats["launches"] == 1                          # ONE launch: the asynchronous engine, not rounds
                 assert_dijkstra_equal(o, case.om.dijkstra(case.weights, case.costs, int(g), robot, goal_dist_offset=off))
-        nb = 8 if engine == "auto" else goals.shape[0]                 # ('auto' gives the engine batches of up to 8 plans)
+        nb = 8 if engine == "auto" else goals.shape[0]                 # ('auto' gives the engine batches of up to 160 plans: below)
         targets = np.full(nb, robot, np.uint32)
         refs = [case.om.dijkstra(case.weights, case.costs, int(g), robot) for g in goals[:nb]]
         for fields in (True, False):
@@ -46,6 +46,26 @@ def test_auto_takes_the_async_engine_for_single_plans_and_small_batches(gpu_ctx_
                     assert np.array_equal(b["dist"][k].view(np.uint32), ref.dist.view(np.uint32)), k
                     assert np.array_equal(b["pred"][k], ref.pred), k
     ctx.set_dijkstra_engine("auto")
+
+
+def test_auto_switches_to_the_tile_batch_engine_above_160_plans(gpu_ctx_factory):
+    """`auto` keeps batches of up to 160 plans (async_max_batch) on the asynchronous engine and hands 161 to the tile-batch engine:
+    every path of both batches against the oracle, the engine that ran by name."""
+    case = terrain_case(128, 3)
+    ctx = gpu_ctx_factory()
+    case.upload(ctx)
+    m = case.mesh
+    robot = m.vertex_at(0.85, 0.8)
+    goals = np.random.default_rng(4).choice(np.setdiff1d(np.arange(m.V), [robot]), 161, replace=False).astype(np.uint32)
+    refs = [case.om.dijkstra(case.weights, case.costs, int(g), robot) for g in goals]
+    for nb, want in ((160, "k_plan_async"), (161, "tile-batch engine")):
+        b = ctx.plan_dijkstra_batch(goals[:nb], np.full(nb, robot, np.uint32), want_fields=False)
+        assert want in ctx.last_engine(), (nb, ctx.last_engine())
+        assert b["stats"]["n_plans"] == nb
+        for k in range(nb):
+            assert b["codes"][k] == refs[k].code == 0
+            assert np.array_equal(b["paths"][k], refs[k].path), (nb, k)
+    ctx.close()
 
 
 def test_async_banded_solves_and_few_workgroups_give_the_same_bits(gpu_ctx_factory):

@@ -2,7 +2,7 @@
 
   (a) the tile-batch engine on the C4 mesh (10M vertices) with a batch large enough to take it (>= 1024 plans):
       vertex paths and popped potential of a sample against the oracle (dijkstra_mesh_planner.cpp:287-348, :358-373);
-  (b) V-sized outputs of a batch at C2 scale through `k_dij_finalize<8, true>` with FULL groups of eight plans:
+  (b) V-sized outputs of a 64-plan batch at C2 scale through the tile-batch engine's own finalize pass (`k_tb_finalize`):
       potential / predecessors / vector map bits of >= 8 plans against the oracle (:189-209, :293-300);
   (c) `mnav_cancel` during a large tile-batch run: every plan CANCELED (:287, :350-354), a later batch unaffected (:238).
 """
@@ -25,28 +25,53 @@ def _popped(full, t, offset):
     return full <= gd
 
 
-def test_c4_tile_batch_1024_plans_paths_and_popped_potential(gpu_ctx_factory):
-    mesh = meshgen.terrain(3163, 0.1, 4)
-    w = meshgen.edge_lengths(mesh)
-    costs = np.zeros(mesh.V, np.float32)
-    ctx = gpu_ctx_factory()
-    ctx.upload_mesh(mesh.xyz, mesh.faces, mesh.edges, None)
-    ctx.upload_costs(costs, w)
-    ctx.set_dijkstra_engine("tile_batch")
-    rng = np.random.default_rng(41)
-    n = 1024
-    seeds = rng.choice(mesh.V, n, replace=False).astype(np.uint32)
-    targets = rng.choice(mesh.V, n, replace=False).astype(np.uint32)
-    targets[: n // 2] = mesh.vertex_at(0.9, 0.9)                      # the bench's common robot vertex and scattered ones
+class C4:
+    """The 10M-vertex mesh of config C4, its oracle, one batch of 1024 plans and the oracle's answers to the plans the tests of this
+    module sample: generated once per process."""
+
+    def __init__(self):
+        self.mesh = mesh = meshgen.terrain(3163, 0.1, 4)
+        self.w = meshgen.edge_lengths(mesh)
+        self.costs = np.zeros(mesh.V, np.float32)
+        self.om = O.OracleMesh(mesh.xyz, mesh.faces)
+        rng = np.random.default_rng(41)
+        self.n = n = 1024
+        self.seeds = rng.choice(mesh.V, n, replace=False).astype(np.uint32)
+        self.targets = rng.choice(mesh.V, n, replace=False).astype(np.uint32)
+        self.targets[: n // 2] = mesh.vertex_at(0.9, 0.9)             # the bench's common robot vertex and scattered ones
+        self._refs = {}
+
+    def oracle(self, k):
+        """(the plan at offset 0.3, the full-field potential) of plan k"""
+        if k not in self._refs:
+            ref = self.om.dijkstra(self.w, self.costs, int(self.seeds[k]), int(self.targets[k]))
+            full = self.om.dijkstra(self.w, self.costs, int(self.seeds[k]), int(self.targets[k]), goal_dist_offset=np.inf).dist
+            self._refs[k] = (ref, full)
+        return self._refs[k]
+
+    def context(self, gpu_ctx_factory):
+        ctx = gpu_ctx_factory()
+        ctx.upload_mesh(self.mesh.xyz, self.mesh.faces, self.mesh.edges, None)
+        ctx.upload_costs(self.costs, self.w)
+        ctx.set_dijkstra_engine("tile_batch")
+        return ctx
+
+
+@pytest.fixture(scope="module")
+def c4():
+    return C4()
+
+
+def test_c4_tile_batch_1024_plans_paths_and_popped_potential(gpu_ctx_factory, c4):
+    mesh, n, seeds, targets = c4.mesh, c4.n, c4.seeds, c4.targets
+    ctx = c4.context(gpu_ctx_factory)
     b = ctx.plan_dijkstra_batch(seeds, targets, want_fields=False, path_cap=32768)
     assert b["rc"] == 0 and (b["codes"] == 0).all()
     assert b["stats"]["n_plans"] == n
-    om = O.OracleMesh(mesh.xyz, mesh.faces)
     for k in (0, 511, 777, 1023):
-        ref = om.dijkstra(w, costs, int(seeds[k]), int(targets[k]))
+        ref, full = c4.oracle(k)
         assert ref.code == 0
         assert np.array_equal(b["paths"][k], ref.path), k
-        full = om.dijkstra(w, costs, int(seeds[k]), int(targets[k]), goal_dist_offset=np.inf).dist
         pot = ctx.download_output("popped", k)
         m = _popped(full, int(targets[k]), 0.3)
         assert np.array_equal(pot[m].view(np.uint32), full[m].view(np.uint32)), k
@@ -63,8 +88,34 @@ def test_c4_tile_batch_1024_plans_paths_and_popped_potential(gpu_ctx_factory):
     ctx.close()
 
 
+def test_c4_register_resident_kernel_band_4(gpu_ctx_factory, c4):
+    """The same batch on k_tbv_solve (`tb_kernel` 1): 1024 plans on ~92 600 tiles are 3.4 plans per tile and iteration, so the band is
+    the 4 tile widths `auto` gives the C4 bench leg (4096 plans) -- at a quarter of its memory.  Paths and popped potential of the
+    first and last plan and of the two either side of the first 64-plan boundary."""
+    n, seeds, targets = c4.n, c4.seeds, c4.targets
+    ctx = c4.context(gpu_ctx_factory)
+    ctx.set_option("tb_kernel", 1)
+    try:
+        b = ctx.plan_dijkstra_batch(seeds, targets, want_fields=False, path_cap=32768)
+        print("kernel that ran:", ctx.last_engine())
+        assert "k_tbv_solve" in ctx.last_engine(), ctx.last_engine()
+        assert b["rc"] == 0 and (b["codes"] == 0).all()
+        assert b["stats"]["n_plans"] == n
+        for k in (0, 63, 64, 1023):
+            ref, full = c4.oracle(k)
+            assert ref.code == 0
+            assert np.array_equal(b["paths"][k], ref.path), k
+            pot = ctx.download_output("popped", k)
+            m = _popped(full, int(targets[k]), 0.3)
+            assert np.array_equal(pot[m].view(np.uint32), full[m].view(np.uint32)), k
+            assert np.isinf(pot[~m]).all()
+    finally:
+        ctx.close()
+
+
 def test_c2_tile_batch_fields_and_vector_map_full_groups(gpu_ctx_factory):
-    """64 plans with V-sized outputs on the 1M mesh: eight full groups of `k_dij_finalize<8, true>`."""
+    """64 plans with V-sized outputs on the 1M mesh, written by the tile-batch engine's finalize pass (`k_tb_finalize`: with this
+    engine the V-sized outputs never go through `k_dij_finalize`): exactly one full plan range of 64."""
     case = terrain_case(1000, 2)
     ctx = gpu_ctx_factory()
     case.upload(ctx)

@@ -32,3 +32,57 @@ def test_grid_edges_closed_form_matches_first_appearance_order():
         e1, fe1 = meshgen.edges_from_faces(meshgen.grid_faces(N))
         e2, fe2 = meshgen.grid_edges(N)
         assert np.array_equal(e1, e2) and np.array_equal(fe1, fe2)
+
+
+def _valences(mesh):
+    deg = np.bincount(mesh.edges.ravel(), minlength=mesh.V)
+    return {int(k): int(v) for k, v in zip(*np.unique(deg, return_counts=True))}
+
+
+def _checked(mesh):
+    om = O.OracleMesh(mesh.xyz, mesh.faces)
+    assert om.manifold                                               # every edge in at most two faces
+    assert np.array_equal(om.edges(), mesh.edges) and np.array_equal(om.face_edges(), mesh.face_edges)
+    assert (om.face_normals()[:, 2] > 0).all()                       # counter-clockwise seen from +z
+    assert mesh.V - mesh.E + mesh.F == 1 + int((np.bincount(mesh.edges.ravel(), minlength=mesh.V) == 0).sum())   # a disc + its face-less vertices
+    return om
+
+
+def test_union_jack_alternates_valence_4_and_8():
+    m = meshgen.union_jack(96, 0.1, 3, 0.5)
+    _checked(m)
+    assert (m.V, m.F, m.E) == (9216, 18050, 27265)
+    assert _valences(m) == {2: 2, 3: 190, 4: 4418, 5: 188, 8: 4418}
+    assert np.array_equal(m.xyz, meshgen.terrain(96, 0.1, 3, amplitude=0.5).xyz)
+    deg = np.bincount(m.edges.ravel(), minlength=m.V).reshape(96, 96)
+    j, i = np.mgrid[1:95, 1:95]
+    assert np.array_equal(deg[1:95, 1:95], np.where((i + j) % 2 == 0, 8, 4))
+    f = meshgen.union_jack(48, 1.0, flat=True)                       # flat: the vertices of flat_grid, many equal potentials
+    _checked(f)
+    assert (f.V, f.F, f.E) == (2304, 4418, 6721)
+    assert _valences(f) == {2: 2, 3: 94, 4: 1058, 5: 92, 8: 1058}
+    assert np.array_equal(f.xyz, meshgen.flat_grid(48, 1.0).xyz)
+    om = O.OracleMesh(f.xyz, f.faces)
+    w = om.edge_distances()
+    d = om.dijkstra(w, np.zeros(f.V, np.float32), f.vertex_at(0.5, 0.5), f.vertex_at(0.9, 0.9), goal_dist_offset=np.inf).dist
+    assert np.isfinite(d).all() and len(np.unique(d)) == 325          # 2304 vertices, 325 distinct potentials from the centre
+
+
+def test_hub_terrain_valences_and_faceless_vertices():
+    hubs = [(20, 20, 1), (60, 30, 2), (40, 90, 3), (100, 100, 5), (64, 64, 1), (90, 40, 2)]
+    m = meshgen.hub_terrain(128, hubs, 0.1, 3)
+    _checked(m)
+    assert (m.V, m.F, m.E) == (16384, 32018, 48281)
+    assert _valences(m) == {0: 120, 2: 2, 3: 2, 4: 504, 5: 88, 6: 15650, 7: 12, 8: 2, 16: 2, 24: 1, 40: 1}
+    deg = np.bincount(m.edges.ravel(), minlength=m.V)
+    for ci, cj, k in hubs:
+        assert deg[cj * 128 + ci] == 8 * k
+        inner = [(cj + dj) * 128 + ci + di for dj in range(-k + 1, k) for di in range(-k + 1, k) if (di, dj) != (0, 0)]
+        assert (deg[inner] == 0).all() and len(inner) == (2 * k - 1) ** 2 - 1      # the hub's former interior neighbours
+    assert np.array_equal(m.xyz, meshgen.terrain(128, 0.1, 3, amplitude=0.5).xyz)
+    for bad in ([(1, 5, 2)], [(20, 20, 2), (22, 22, 1)]):                         # a block leaving the grid, two blocks sharing cells
+        try:
+            meshgen.hub_terrain(32, bad)
+        except ValueError:
+            continue
+        raise AssertionError(bad)

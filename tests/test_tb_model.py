@@ -141,6 +141,37 @@ def test_v_layout_streams_of_the_register_resident_kernel():
     assert r["max_sweeps"] <= 40
 
 
+TBV_PARITY_MESHES = {                                                   # the meshes of tests/test_gpu_tbv_parity.py: (mesh, tiles, most ghosts of a tile)
+    "union_jack": (lambda: meshgen.union_jack(96, 0.1, 3, 0.5), 86, 49),
+    "hub": (lambda: meshgen.hub_terrain(128, [(20, 20, 1), (60, 30, 2), (40, 90, 3), (100, 100, 5), (64, 64, 1), (90, 40, 2)], 0.1, 3), 152, 54),
+    "flat_union_jack": (lambda: meshgen.union_jack(48, 1.0, flat=True), 22, 46),
+    "punched": (lambda: meshgen.punched(96, 0.1, 5, drop=0.30, cut_column=60), 86, 48),
+    "fan": (lambda: meshgen.fan_field(40, 6, 1), 3, 34),
+}
+
+
+@pytest.mark.parametrize("name", sorted(TBV_PARITY_MESHES))
+def test_meshes_of_the_gpu_parity_tests_fit_the_register_resident_kernel(name):
+    """k_tbv_solve holds 64 ghost rows; the host keeps a mesh with a fuller tile on k_tb_solve_q.  The GPU parity tests mean to run
+    k_tbv_solve on these meshes, so their tilings (T = 120) are pinned here -- and the V layout of their streams (continuation
+    blocks of the valence-8 .. 40 rows, tiles with few or no ghosts, face-less vertices) gives the oracle's popped potential bit for
+    bit at a positive and a negative offset."""
+    make, tiles, ghosts = TBV_PARITY_MESHES[name]
+    m = make()
+    case = Case(m)
+    deg = np.bincount(m.edges.ravel(), minlength=m.V)
+    ok = np.flatnonzero(deg > 0)
+    rng = np.random.default_rng(8)
+    seeds = rng.choice(ok, 4, replace=False)
+    targets = rng.choice(ok, 4, replace=False)
+    seeds[0] = np.flatnonzero(deg == deg.max())[0]                    # the highest valence as a wave source and as a target
+    targets[1] = seeds[0]
+    for offset in (0.3, -0.2):
+        r = check(case, seeds, targets, offset=offset, tile=120, jacobi=3)
+        assert r["max_ghosts"] <= 64
+        assert (r["tiles"], r["max_ghosts"]) == (tiles, ghosts)
+
+
 def test_pair_division_by_multiply_high():
     """k_tb_scan splits a listed pair (tile * blocks + block) by one multiply-high and a shift (mnav::tb_div_magic): exact for
     every numerator below 2^31 -- the host refuses a flag matrix beyond that -- and every number of blocks a batch can have."""
