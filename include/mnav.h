@@ -306,6 +306,44 @@ int mnav_clearance_download(const mnav_ctx* ctx, float* clearance_out);
 int mnav_clearance_stats(const mnav_ctx* ctx, uint32_t* cast, uint32_t* rays, uint32_t* hits, float* ms_bvh_build, float* ms_cast,
                          float* ms_total);
 
+/* -- pose lookup on the device ---------------------------------------------------------------------
+ * MeshMap::getNearestVertexHandle (mesh_map.cpp:1161-1174) and MeshMap::getContainingFace / searchContainingFace
+ * (:1120-1159) for n positions (pos: n*3 floats) in one call; only the positions go up and the results come down.
+ *   vertex   the minimum over ALL uploaded vertices (isolated ones included) of the pair (d, id), d = (dx*dx + dy*dy) + dz*dz
+ *            in float with dx = pos.x - x_v, no contraction: the exact nearest vertex, equal d to the smallest id.  A vertex
+ *            whose d is +inf or NaN never wins (so a vertex with a non-finite coordinate never does), and a position with a
+ *            NaN, an infinite or an overflowing coordinate finds MNAV_NONE.
+ *   face     among the faces of that vertex, in the getFacesOfVertex row order (mnav_set_face_circulation, or the library's
+ *            own replay), those that pass the inside test of projectedBarycentricCoords (util.cpp:320-347, EPSILON 0.01);
+ *            the smallest SIGNED plane distance wins, the first row entry on a tie; a degenerate face (NaN barycentrics) is
+ *            never inside.  MNAV_NONE if there is none.
+ *   bary     the three barycentric coordinates in that face, dist the signed distance; zeros without a face.
+ * Any output pointer may be NULL; n = 0 does nothing.  The search structure, a linear BVH over the vertex positions of
+ * O(V) bytes whatever the extent of the mesh, is built by the first call after mnav_upload_mesh and dropped by the next
+ * upload; pruning compares exact lower bounds, so the result never depends on it.
+ * Returns 0 / <0 (mnav_last_error; e.g. before a mesh was uploaded).  No plan output and no layer is touched. */
+int mnav_locate(mnav_ctx* ctx, uint32_t n, const float* pos, uint32_t* vertex_out, uint32_t* face_out, float* bary_out,
+                float* dist_out);
+/* The last lookup (mnav_locate or a plan call that starts from positions): built = 1 if that call built the search
+ * structure; device milliseconds of the last build and of the last query kernel; vertex distances the last call
+ * evaluated, over all its positions.  Any pointer may be NULL. */
+int mnav_locate_stats(const mnav_ctx* ctx, uint32_t* built, float* ms_build, float* ms_query, uint64_t* candidates);
+/* MeshPlanner::makePlan's resolution (dijkstra_mesh_planner.cpp:235-236) followed by mnav_plan_dijkstra_batch: plan i runs
+ * from the nearest vertex of goal_pos[i] (the wave seed) to the nearest vertex of start_pos[i] (the robot), both n*3
+ * floats.  A goal without a vertex gives MNAV_INVALID_START, a start without one MNAV_INVALID_GOAL, as out-of-range ids do
+ * there.  seeds_out / targets_out (n each, may be NULL) receive the resolved ids; every other argument and every output is
+ * that of mnav_plan_dijkstra_batch called with those ids, bit for bit.  Only 2n ids pass through the host. */
+uint32_t mnav_plan_dijkstra_batch_at(mnav_ctx* ctx, uint32_t n, const float* goal_pos, const float* start_pos,
+                                     double goal_dist_offset, double cost_limit, uint32_t* codes_out, uint32_t* seeds_out,
+                                     uint32_t* targets_out, float* dist_out, uint32_t* pred_out, uint32_t* path_out,
+                                     uint32_t path_cap, uint32_t* path_len);
+/* The same for mnav_plan_cvp_batch: seed_pos = goal_pos as given (the reference does not project it), seed face / target
+ * face = the containing faces of goal_pos[i] / start_pos[i]; a position without a face gets the code an out-of-range face
+ * gets there.  seed_faces_out / target_faces_out (n each, may be NULL) receive the faces. */
+uint32_t mnav_plan_cvp_batch_at(mnav_ctx* ctx, uint32_t n, const float* goal_pos, const float* start_pos,
+                                double goal_dist_offset, double cost_limit, uint32_t* codes_out, uint32_t* seed_faces_out,
+                                uint32_t* target_faces_out, float* dist_out, uint32_t* pred_out, float* vecmap_out);
+
 /* -- one plan over several GPUs (BASELINE config 4) ---------------------------------------------
  * The reference's loop (dijkstra_mesh_planner.cpp:287-348) on a mesh that is range-partitioned over `world`
  * processes, one per GPU: the LDS tiles are in Morton order and process `rank` owns a contiguous range of them.

@@ -31,6 +31,7 @@ SYMBOLS = [
     "mnav_layer_obstacle", "mnav_obstacle_stats",
     "mnav_layer_height_diff", "mnav_layer_roughness", "mnav_layer_ridge", "mnav_neighbourhood_stats",
     "mnav_layer_border", "mnav_layer_clearance", "mnav_clearance_download", "mnav_clearance_stats",
+    "mnav_locate", "mnav_locate_stats", "mnav_plan_dijkstra_batch_at", "mnav_plan_cvp_batch_at",
     "mnav_set_option", "mnav_get_option", "mnav_shard_set_goal_tie", "mnav_last_engine",
 ]
 
@@ -104,6 +105,14 @@ def load(path: str | None = None):
     L.mnav_plan_dijkstra_batch.argtypes = [vp, u32, vp, vp, f64, f64, vp, vp, vp, vp, u32, vp]
     L.mnav_plan_cvp_batch.restype = u32
     L.mnav_plan_cvp_batch.argtypes = [vp, u32, vp, vp, vp, f64, f64, vp, vp, vp, vp]
+    L.mnav_locate.restype = C.c_int
+    L.mnav_locate.argtypes = [vp, u32, vp, vp, vp, vp, vp]
+    L.mnav_locate_stats.restype = C.c_int
+    L.mnav_locate_stats.argtypes = [vp, C.POINTER(u32), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint64)]
+    L.mnav_plan_dijkstra_batch_at.restype = u32
+    L.mnav_plan_dijkstra_batch_at.argtypes = [vp, u32, vp, vp, f64, f64, vp, vp, vp, vp, vp, vp, u32, vp]
+    L.mnav_plan_cvp_batch_at.restype = u32
+    L.mnav_plan_cvp_batch_at.argtypes = [vp, u32, vp, vp, f64, f64, vp, vp, vp, vp, vp, vp]
     L.mnav_cancel.argtypes = [vp]
     L.mnav_get_stats.restype = C.c_int
     L.mnav_get_stats.argtypes = [vp, C.POINTER(Stats)]
@@ -667,15 +676,8 @@ class MnavContext:
             raise RuntimeError(f"mnav_plan_dijkstra internal error: {self._err()}")
         return DijkstraOut(code, dist, pred, path[: n.value].copy(), vm, self.stats())
 
-    def plan_dijkstra_batch(self, seeds, targets, goal_dist_offset: float = 0.3, cost_limit: float = 1.0,
-                            want_fields: bool = False, path_cap: int | None = None, want_stats: bool = True):
-        seeds, targets = _u32(seeds), _u32(targets)
-        n = seeds.shape[0]
-        V = self.V
-        cap = int(path_cap if path_cap is not None else V)
-        codes = np.empty(n, np.uint32)
-        dist = np.empty((n, V), np.float32) if want_fields else None
-        pred = np.empty((n, V), np.uint32) if want_fields else None
+    def _lease_paths(self, n: int, cap: int):
+        """An (n, cap) path buffer that no result handed out earlier still refers to, and the lease list a new result signs."""
         # the rows of the path buffer are only touched where a path lands: keep the (mostly untouched) buffers between calls --
         # a fresh 335 MB buffer per call costs one page fault per row (12 ms per 5120-plan batch).  A small pool, because the
         # caller usually still holds the previous call's result (which refers to its buffer) while the next call runs.
@@ -696,6 +698,18 @@ class MnavContext:
             lease = []
             if len(self._path_pool) < 3:
                 self._path_pool.append([paths, lease])
+        return paths, lease
+
+    def plan_dijkstra_batch(self, seeds, targets, goal_dist_offset: float = 0.3, cost_limit: float = 1.0,
+                            want_fields: bool = False, path_cap: int | None = None, want_stats: bool = True):
+        seeds, targets = _u32(seeds), _u32(targets)
+        n = seeds.shape[0]
+        V = self.V
+        cap = int(path_cap if path_cap is not None else V)
+        codes = np.empty(n, np.uint32)
+        dist = np.empty((n, V), np.float32) if want_fields else None
+        pred = np.empty((n, V), np.uint32) if want_fields else None
+        paths, lease = self._lease_paths(n, cap)
         lens = np.zeros(n, np.uint32)
         rc = self._L.mnav_plan_dijkstra_batch(self._h, n, _p(seeds), _p(targets), float(goal_dist_offset),
                                               float(cost_limit), _p(codes), _p(dist), _p(pred), _p(paths), cap, _p(lens))
@@ -720,6 +734,69 @@ class MnavContext:
         if rc == INTERNAL_ERROR:
             raise RuntimeError(f"mnav_plan_cvp_batch internal error: {self._err()}")
         return dict(rc=rc, codes=codes, dist=dist, pred=pred, vecmap=vm, stats=self.stats())
+
+    def locate(self, points, want_vertex: bool = True, want_face: bool = True, want_bary: bool = True, want_dist: bool = True) -> dict:
+        """MeshMap::getNearestVertexHandle and searchContainingFace for an (n, 3) batch of positions (mnav_locate,
+        include/mnav.h).  Returns dict(vertex, face, bary, dist): uint32 ids (NONE = 0xFFFFFFFF where there is none), the
+        barycentric coordinates and the signed distance to the face's plane (zeros without a face); an output that was not
+        asked for is None."""
+        pts = _f32(points).reshape(-1, 3)
+        n = int(pts.shape[0])
+        vtx = np.empty(n, np.uint32) if want_vertex else None
+        face = np.empty(n, np.uint32) if want_face else None
+        bary = np.empty((n, 3), np.float32) if want_bary else None
+        dist = np.empty(n, np.float32) if want_dist else None
+        if self._L.mnav_locate(self._h, n, _p(pts) if n else None, _p(vtx), _p(face), _p(bary), _p(dist)) != 0:
+            raise RuntimeError(f"mnav_locate failed: {self._err()}")
+        return dict(vertex=vtx, face=face, bary=bary, dist=dist)
+
+    def locate_stats(self) -> dict:
+        b, mb, mq, c = C.c_uint32(), C.c_float(), C.c_float(), C.c_uint64()
+        self._L.mnav_locate_stats(self._h, C.byref(b), C.byref(mb), C.byref(mq), C.byref(c))
+        return dict(built=b.value, ms_build=mb.value, ms_query=mq.value, candidates=c.value)
+
+    def plan_dijkstra_batch_at(self, goal_pos, start_pos, goal_dist_offset: float = 0.3, cost_limit: float = 1.0,
+                               want_fields: bool = False, path_cap: int | None = None, want_stats: bool = True):
+        """plan_dijkstra_batch from positions: goal -> seed vertex, start -> target vertex on the device (`seeds`, `targets`
+        in the result)."""
+        gp, sp = _f32(goal_pos).reshape(-1, 3), _f32(start_pos).reshape(-1, 3)
+        n, V = int(gp.shape[0]), self.V
+        if sp.shape[0] != n:
+            raise ValueError("goal_pos and start_pos differ in length")
+        cap = int(path_cap if path_cap is not None else V)
+        codes = np.empty(n, np.uint32)
+        seeds, targets = np.empty(n, np.uint32), np.empty(n, np.uint32)
+        dist = np.empty((n, V), np.float32) if want_fields else None
+        pred = np.empty((n, V), np.uint32) if want_fields else None
+        paths, lease = self._lease_paths(n, cap)
+        lens = np.zeros(n, np.uint32)
+        rc = self._L.mnav_plan_dijkstra_batch_at(self._h, n, _p(gp), _p(sp), float(goal_dist_offset), float(cost_limit), _p(codes),
+                                                 _p(seeds), _p(targets), _p(dist), _p(pred), _p(paths), cap, _p(lens))
+        if rc == INTERNAL_ERROR:
+            raise RuntimeError(f"mnav_plan_dijkstra_batch_at internal error: {self._err()}")
+        rows = _PathRows(paths, lens, cap)
+        lease.append(weakref.ref(rows))
+        return dict(rc=rc, codes=codes, seeds=seeds, targets=targets, dist=dist, pred=pred, paths=rows, path_len=lens,
+                    stats=self.stats() if want_stats else self.timing())
+
+    def plan_cvp_batch_at(self, goal_pos, start_pos, goal_dist_offset: float = 0.3, cost_limit: float = 1.0,
+                          want_fields: bool = False, want_vecmap: bool = False):
+        """plan_cvp_batch from positions: the wave seed is the goal position as given, the two faces are the containing
+        faces found on the device (`seed_faces`, `target_faces` in the result)."""
+        gp, sp = _f32(goal_pos).reshape(-1, 3), _f32(start_pos).reshape(-1, 3)
+        n, V = int(gp.shape[0]), self.V
+        if sp.shape[0] != n:
+            raise ValueError("goal_pos and start_pos differ in length")
+        codes = np.empty(n, np.uint32)
+        sf, tf = np.empty(n, np.uint32), np.empty(n, np.uint32)
+        dist = np.empty((n, V), np.float32) if want_fields else None
+        pred = np.empty((n, V), np.uint32) if want_fields else None
+        vm = np.empty((n, V, 3), np.float32) if want_vecmap else None
+        rc = self._L.mnav_plan_cvp_batch_at(self._h, n, _p(gp), _p(sp), float(goal_dist_offset), float(cost_limit), _p(codes), _p(sf), _p(tf),
+                                            _p(dist), _p(pred), _p(vm))
+        if rc == INTERNAL_ERROR:
+            raise RuntimeError(f"mnav_plan_cvp_batch_at internal error: {self._err()}")
+        return dict(rc=rc, codes=codes, seed_faces=sf, target_faces=tf, dist=dist, pred=pred, vecmap=vm, stats=self.stats())
 
     def plan_cvp(self, seed_pos, seed_face: int, target_face: int, goal_dist_offset: float = 0.3,
                  cost_limit: float = 1.0, want_fields: bool = True, want_vecmap: bool = True) -> CvpOut:

@@ -80,6 +80,7 @@ constexpr int kChunk = 96;  // step launches per graph replay; multiple of 6 (sl
 #include "mnav_obstacle.h"   // obstacle layer: LBVH build, ray cast (mnav_obs::); the change list of mnav_changelist.h (mnav_chg::)
 #include "mnav_nbhd.h"       // height-difference / roughness / ridge layers: neighbourhood visits (mnav_nb::)
 #include "mnav_clearance.h"  // clearance / border layers: normal ray casts over the obstacle BVH, border test (mnav_clr::)
+#include "mnav_locate.h"     // pose lookup: point LBVH over the vertices, exact nearest vertex, containing face (mnav_loc::)
 
 // One back-tracking job: the plan's resident vector map and the two ends of the walk.
 struct WalkJob { const float* vecmap; float seed[3]; uint32_t seed_face; float target[3]; uint32_t target_face; };
@@ -212,6 +213,7 @@ struct mnav_ctx {
   mnav_obs::Bvh obs;                                               // obstacle layer: BVH built by the first mnav_layer_obstacle after an upload
   mnav_nb::State nbhd;                                             // neighbourhood layers: counters, spill lists and scratch of the last call
   mnav_clr::State clr;                                             // clearance / border layers: cached clearance (first clearance call after an upload)
+  mnav_loc::State loc;                                             // pose lookup: vertex index built by the first mnav_locate after an upload
   mnav_chg::Scratch chg;                                           // obstacle / clearance / border layers: change list and counters of the last call
   uint32_t infl_steps = 0, infl_bands = 0; uint64_t infl_evals = 0; float infl_ms = 0.f, infl_ms_wave = 0.f;   // last inflation wave
   DevBuf<TilePlan> d_tplans; uint32_t tplans_cap = 0;
@@ -536,6 +538,17 @@ int check_ready(mnav_ctx* ctx)
   return 0;
 }
 
+// the face tables that the device back-tracking and the containing-face search walk: uploaded by whichever comes first
+int upload_walk_mesh(mnav_ctx* ctx)
+{
+  if (ctx->walk_mesh_valid) return 0;
+  HIPCHK(ctx->d_faces.upload(ctx->stream, ctx->h_faces.data(), ctx->h_faces.size()));
+  HIPCHK(ctx->d_vf_ptr.upload(ctx->stream, ctx->h_vf_ptr.data(), ctx->h_vf_ptr.size()));
+  HIPCHK(ctx->d_vf.upload(ctx->stream, ctx->h_vf.data(), ctx->h_vf.size()));
+  ctx->walk_mesh_valid = true;
+  return 0;
+}
+
 }  // namespace
 
 // =============================================================================================
@@ -617,6 +630,7 @@ int mnav_upload_mesh(mnav_ctx* ctx, uint32_t V, uint32_t F, uint32_t E, const fl
   ctx->nbhd = {};                                                    // V-sized spill lists
   ctx->clr = {};                                                     // cached clearance: recast lazily
   ctx->chg = {};                                                     // V-sized change list
+  ctx->loc = {};                                                     // vertex index: rebuilt lazily
   ctx->d_edge_dist.reset();
   drop_graphs(ctx);
   ctx->d_paths.reset(); ctx->paths_words = 0;
@@ -1630,6 +1644,7 @@ uint32_t mnav_plan_cvp_batch(mnav_ctx* ctx, uint32_t n, const float* seed_pos, c
 #include "mnav_obstacle_capi.h"   // mnav_layer_obstacle, mnav_obstacle_stats
 #include "mnav_nbhd_capi.h"       // mnav_layer_height_diff / _roughness / _ridge, mnav_neighbourhood_stats
 #include "mnav_clearance_capi.h"  // mnav_layer_clearance, mnav_layer_border, mnav_clearance_download, mnav_clearance_stats
+#include "mnav_locate_capi.h"     // mnav_locate, mnav_locate_stats, mnav_plan_dijkstra_batch_at, mnav_plan_cvp_batch_at
 
 void mnav_cancel(mnav_ctx* ctx)
 {
@@ -1841,12 +1856,7 @@ int mnav_backtrack_cvp_batch(mnav_ctx* ctx, uint32_t n, const float* seed_pos, c
     L.inflation_radius = Ly.inflation_radius; L.inscribed_radius = Ly.inscribed_radius; L.inscribed_value = Ly.inscribed_value; L.lethal_value = Ly.lethal_value;
     L.repulsive_field = 1;
   }
-  if (!ctx->walk_mesh_valid) {
-    HIPCHK(ctx->d_faces.upload(ctx->stream, ctx->h_faces.data(), ctx->h_faces.size()));
-    HIPCHK(ctx->d_vf_ptr.upload(ctx->stream, ctx->h_vf_ptr.data(), ctx->h_vf_ptr.size()));
-    HIPCHK(ctx->d_vf.upload(ctx->stream, ctx->h_vf.data(), ctx->h_vf.size()));
-    ctx->walk_mesh_valid = true;
-  }
+  if (upload_walk_mesh(ctx)) return -1;
   const size_t need = (size_t)cap * n;
   if (need > ctx->walk_cap) {
     ctx->d_walk_pos.reset(); ctx->d_walk_face.reset(); ctx->walk_cap = 0;

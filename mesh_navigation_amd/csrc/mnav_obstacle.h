@@ -77,17 +77,21 @@ __global__ __launch_bounds__(256) void k_obs_morton(uint32_t F, const uint32_t* 
   ids[f] = f;
 }
 
-// Karras 2012 common-prefix length of sorted keys i and j (index as tie-break), -1 outside [0, F)
-__device__ __forceinline__ int obs_delta(const uint32_t* __restrict__ keys, int64_t F, int64_t i, int64_t j)
+// Karras 2012 common-prefix length of sorted keys i and j (index as tie-break), -1 outside [0, F).  Key = uint32_t (the
+// faces here) or uint64_t (the vertex index of mnav_locate.h).
+template <class Key>
+__device__ __forceinline__ int obs_delta(const Key* __restrict__ keys, int64_t F, int64_t i, int64_t j)
 {
   if (j < 0 || j >= F) return -1;
-  const uint32_t a = keys[i], b = keys[j];
-  if (a == b) return 32 + __clz((uint32_t)i ^ (uint32_t)j);
-  return __clz(a ^ b);
+  const Key a = keys[i], b = keys[j];
+  if (a == b) return 8 * (int)sizeof(Key) + __clz((uint32_t)i ^ (uint32_t)j);
+  if constexpr (sizeof(Key) == 8) return __clzll((long long)(a ^ b));
+  else return __clz((uint32_t)(a ^ b));
 }
 
 // internal node i covers a key range; its split is where the common prefix grows (Karras 2012, Fig. 4)
-__global__ __launch_bounds__(256) void k_obs_hierarchy(uint32_t F, const uint32_t* __restrict__ keys, float4* __restrict__ nodes,
+template <class Key>
+__global__ __launch_bounds__(256) void k_obs_hierarchy(uint32_t F, const Key* __restrict__ keys, float4* __restrict__ nodes,
                                                        uint32_t* __restrict__ par_int, uint32_t* __restrict__ par_leaf)
 {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;

@@ -36,7 +36,7 @@ static int obstacle_build_bvh(mnav_ctx* ctx)
     HIPCHK(tmp.alloc(tmp_bytes ? tmp_bytes : 1));
     HIPCHK(rocprim::radix_sort_pairs((void*)tmp, tmp_bytes, (uint32_t*)keys, (uint32_t*)keys2, (uint32_t*)ids, (uint32_t*)ids2, F, 0, 30, ctx->stream));
     if (F > 1)
-      hipLaunchKernelGGL(k_obs_hierarchy, dim3((F - 1 + 255) / 256), dim3(256), 0, ctx->stream, F, keys2, B.nodes, par_int, par_leaf);
+      hipLaunchKernelGGL(k_obs_hierarchy<uint32_t>, dim3((F - 1 + 255) / 256), dim3(256), 0, ctx->stream, F, keys2, B.nodes, par_int, par_leaf);
     hipLaunchKernelGGL(k_obs_leaves, dim3(gf), dim3(256), 0, ctx->stream, F, ids2, B.fvtx, ctx->d_xyz, B.tris, B.nodes, par_int, par_leaf, arrive);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(ctx->ev[5], ctx->stream));

@@ -126,6 +126,7 @@ uint64_t mnav_device_bytes(const mnav_ctx* ctx)
                      ctx->d_t_rowptr, ctx->d_t_col, ctx->d_t_src, ctx->d_vert_tile, ctx->d_t_tw) +
                bytes(ctx->d_cost, ctx->d_w, ctx->d_invalid, ctx->d_edge_dist) +
                bytes(ctx->clr.clr, ctx->clr.border, ctx->chg.ids, ctx->chg.blk, ctx->chg.cnt) +
+               bytes(ctx->loc.nodes, ctx->loc.pts) +
                bytes(S.d_iface_vert, S.d_iface_owner, S.d_wake_ptr, S.d_wake_tile, S.d_owned) +
                bytes(B.d_tiles, B.d_stream, B.d_wsrc, B.d_exps, B.d_vstream, B.d_vwsrc, B.d_vtile, B.d_vgroups, B.d_vexps, B.d_vaddr,
                      B.d_vert_tile, B.d_verts, B.d_fin_src, B.d_fin_wsrc, B.d_fin_ovf, B.d_fin_ovf_wsrc, B.d_ghost_gid, B.d_fin_order);
