@@ -344,6 +344,61 @@ uint32_t mnav_plan_cvp_batch_at(mnav_ctx* ctx, uint32_t n, const float* goal_pos
                                 double goal_dist_offset, double cost_limit, uint32_t* codes_out, uint32_t* seed_faces_out,
                                 uint32_t* target_faces_out, float* dist_out, uint32_t* pred_out, float* vecmap_out);
 
+/* -- vector-field follower on the device -------------------------------------------------------------
+ * One tick of mesh_controller::MeshController (computeVelocityCommands, mesh_controller.cpp:67-170, and naiveControl,
+ * :225-242) for n robots over the vector maps the last plan call left resident (a single plan or a batch, Dijkstra or CVP;
+ * resident through mnav_set_resident_outputs or through a vecmap_out buffer): only 44 bytes per robot go up (48 with seed_faces) and the
+ * commands come down, no V-sized field crosses PCIe.  The eight parameters of mesh_controller.h:193-200: */
+typedef struct mnav_follow_config {
+  double max_lin_velocity;     /* 1.0 */
+  double max_ang_velocity;     /* 0.5 */
+  double arrival_fading;       /* 0.5; unused, as in the reference */
+  double ang_vel_factor;       /* 1.0 */
+  double lin_vel_factor;       /* 1.0 */
+  double max_angle;            /* 20 (degrees) */
+  double max_search_radius;    /* 0.4 */
+  double max_search_distance;  /* 0.4 */
+} mnav_follow_config;
+#define MNAV_FOLLOW_CONFIG_DEFAULTS { 1.0, 0.5, 0.5, 1.0, 1.0, 20.0, 0.4, 0.4 }
+/* Outcome of one robot's tick.  The ROS plugin maps them to mbf_msgs ExePath results (SUCCESS, OUT_OF_MAP, FAILURE). */
+enum { MNAV_FOLLOW_OK = 0, MNAV_FOLLOW_OUT_OF_MAP = 1, MNAV_FOLLOW_NO_FIELD = 2 };
+/* Robot i: position pos[i], heading dir[i] and up vector up[i] (3 floats each, in the map frame, used as given), the face
+ * it was on at the last tick face_in[i] (MNAV_NONE: none yet), the plan whose field it follows slots[i] (plan index of the
+ * last plan call; robots may share one) and, if seed_faces is not NULL, that plan's seed face seed_faces[i] (MNAV_NONE:
+ * none), whose three vertices always count as having a vector, as in the back-tracking walk.
+ *   face   in the reference's order; how_out[i] tells which step found it:
+ *            1  no face_in: searchContainingFace, the rule of mnav_locate (max_search_distance is ignored there, :82-83)
+ *            2  face_in still holds the position: inside and the SIGNED plane distance < max_search_distance (:109-111,
+ *               no fabs: a robot far below its face stays on it); the position is kept
+ *            3  searchNeighbourFaces around face_in with max_search_radius / max_search_distance (mesh_map.cpp:999-1068)
+ *            4  searchContainingFace
+ *            0  none: code MNAV_FOLLOW_OUT_OF_MAP (also for a position with a non-finite coordinate)
+ *          in steps 1, 3 and 4 pos_out[i] is the projection v0*b0 + v1*b1 + v2*b2 (util.h:182-183), else pos[i]
+ *   field  directionAtPosition (mesh_map.cpp:625-650) on the vector map; no vector at the three vertices, or a
+ *          non-finite sum: code MNAV_FOLLOW_NO_FIELD (face, bary, pos and how are set, the rest is zero)
+ *   mesh_dir_out  that vector divided by its float length; cost_out = c0*b0 + c1*b1 + c2*b2 over the resident vertex costs
+ *   cmd_out       2 doubles per robot: linear x and angular z velocity, naiveControl in its mix of float and double, then
+ *                 the two std::min saturations in double (:161-162)
+ * All arithmetic is the reference's in type and order: every output equals the host's bit for bit, whichever pass of the
+ * device produced it.  Not pinned (lvr2 / tf2 sources are not part of the reference): whether mesh_map::Normal's
+ * constructor normalises mesh_dir a second time (here: once), and the quaternion-to-basis product of
+ * poseToDirectionVector (dir / up arrive as vectors).  A neighbour search that would list more than 1024 faces goes on
+ * with step 4.  Any output pointer may be NULL; n = 0 does nothing.
+ * Returns 0, or -1 with mnav_last_error set and NOTHING touched: no mesh, no costs, a slot that is not a plan of the last
+ * call, a slot whose vector map is not resident (also after a paths-only batch, which mnav_vector_at still serves), a
+ * face id >= F that is not MNAV_NONE, a non-finite or non-positive search radius or distance.  The call changes no plan
+ * output, no layer and no statistic of another entry point; it builds the lookup index of mnav_locate when a robot
+ * reaches step 1 or 4 and none exists yet (mnav_locate_stats then reports built = 1).  DESIGN.md section 3.8. */
+int mnav_follow_batch(mnav_ctx* ctx, uint32_t n, const float* pos, const float* dir, const float* up, const uint32_t* face_in,
+                      const uint32_t* slots, const uint32_t* seed_faces, const mnav_follow_config* config, int32_t* code_out,
+                      uint32_t* face_out, float* bary_out, float* pos_out, float* mesh_dir_out, float* cost_out, double* cmd_out,
+                      int32_t* how_out);
+/* The last mnav_follow_batch: robots that stayed on their face (how 2), found a neighbour face (3), were found by a global
+ * search (1 or 4), are out of the map, have no field; built_index = 1 if the call built the lookup index; device
+ * milliseconds of its kernels and host milliseconds of the whole call.  Any pointer may be NULL. */
+int mnav_follow_stats(const mnav_ctx* ctx, uint32_t* stayed, uint32_t* neighbour, uint32_t* global, uint32_t* lost,
+                      uint32_t* no_field, uint32_t* built_index, float* ms_kernels, float* ms_total);
+
 /* -- one plan over several GPUs (BASELINE config 4) ---------------------------------------------
  * The reference's loop (dijkstra_mesh_planner.cpp:287-348) on a mesh that is range-partitioned over `world`
  * processes, one per GPU: the LDS tiles are in Morton order and process `rank` owns a contiguous range of them.

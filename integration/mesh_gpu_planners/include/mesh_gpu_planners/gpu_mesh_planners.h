@@ -29,6 +29,7 @@
 #include <rclcpp/rclcpp.hpp>
 
 #include "mnav.h"
+#include "mnav_controller_host.hpp"
 #include "mesh_gpu_planners/cost_observer_layer.h"
 
 namespace mesh_gpu_planners
@@ -43,6 +44,9 @@ public:
   DeviceMap(const DeviceMap&) = delete;
   DeviceMap& operator=(const DeviceMap&) = delete;
   mnav_ctx* ctx() const { return ctx_; }
+  // the context with its lock (mnav_controller_host.hpp): makePlan holds the lock around its device calls, the
+  // GpuMeshController of the same map around its tick; the handle outlives this object without dangling
+  const mnav_host::ContextHandle& handle() const { return handle_; }
   bool ok() const { return ctx_ != nullptr; }
   uint32_t numVertices() const { return V_; }
   bool uploadMesh(const std::shared_ptr<mesh_map::MeshMap>& map_ptr, std::string& err);
@@ -54,6 +58,7 @@ public:
 private:
   bool static_costs_ = false;
   mnav_ctx* ctx_ = nullptr;
+  mnav_host::ContextHandle handle_;
   uint32_t V_ = 0, F_ = 0, E_ = 0;
   uint64_t cost_hash_ = 0;
   uint32_t probe_v_ = 0, probe_e_ = 0;   // rotating windows of the backstop check behind the change signal (syncCosts)

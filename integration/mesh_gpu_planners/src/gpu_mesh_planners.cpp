@@ -33,11 +33,11 @@ extern "C" void mesh_gpu_planners_cost_sync_counts(uint64_t* full_uploads, uint6
   if (signing_passes) *signing_passes = g_signing_passes.load();
 }
 
-DeviceMap::DeviceMap(int device) : ctx_(mnav_create(device)) {}
+DeviceMap::DeviceMap(int device) : ctx_(mnav_create(device)), handle_(std::make_shared<mnav_host::SharedContext>(ctx_)) {}
 DeviceMap::~DeviceMap()
 {
   if (log_ && log_id_ >= 0) log_->unsubscribe(log_id_);
-  if (ctx_) mnav_destroy(ctx_);
+  handle_->destroy();   // under the context's lock; a GpuMeshController that still holds the handle finds ctx == nullptr and refuses
 }
 
 // The half-edge mesh as flat arrays, in the reference's own ids (handle indices), once per map.
@@ -268,6 +268,7 @@ uint32_t GpuDijkstraMeshPlanner::plan(const mesh_map::Vector& wave_seed, const m
   if (!target_opt) return Result::INVALID_GOAL;                                                    // :242
   path.clear();
   std::string err;
+  std::lock_guard<std::recursive_mutex> device_lock(dev_->handle()->mutex);   // a controller tick on this context waits (and the other way round)
   if (!dev_->syncCosts(*mesh_map_, err, reload_costs_.exchange(false))) { RCLCPP_ERROR_STREAM(node_->get_logger(), name_ << ": " << err); return Result::INTERNAL_ERROR; }
   std::vector<uint32_t> ids;
   const uint32_t code = mnav_host::dijkstra_vertex_path(dev_->ctx(), seed_opt.unwrap().idx(), target_opt.unwrap().idx(), config_.goal_dist_offset,
@@ -276,9 +277,10 @@ uint32_t GpuDijkstraMeshPlanner::plan(const mesh_map::Vector& wave_seed, const m
   for (const uint32_t id : ids) path.push_back(lvr2::VertexHandle(id));
   // computeVectorMap ends with mesh_map_->setVectorMap(vector_map_) (:208): the controller copies the map's field in
   // setPlan (mesh_controller.cpp:182), so a drop-in has to leave it there after every successful plan.  16 bytes per
-  // vertex cross PCIe for it; a deployment whose controller samples the resident field instead (mnav_vector_at) turns
-  // `sync_vector_map` off.
+  // vertex cross PCIe for it; a deployment whose controller follows the resident field instead (GpuMeshController,
+  // mnav_follow_batch) turns `sync_vector_map` off.
   if (config_.sync_vector_map || config_.publish_vector_field) exportVectorMap();
+  mnav_host::publish_field(mesh_map_.get(), dev_->handle(), 0, MNAV_NONE);   // where mesh_gpu_planners/GpuMeshController finds the resident field
   return Result::SUCCESS;
 }
 
@@ -288,6 +290,7 @@ void GpuDijkstraMeshPlanner::exportVectorMap()
   const uint32_t V = dev_->numVertices();
   std::vector<float> vm((size_t)V * 3);
   std::vector<uint32_t> pred(V);
+  std::lock_guard<std::recursive_mutex> device_lock(dev_->handle()->mutex);
   if (mnav_download_output(dev_->ctx(), 0, 4, vm.data()) != 0 || mnav_download_output(dev_->ctx(), 0, 1, pred.data()) != 0) return;
   vector_map_.clear();
   for (uint32_t v = 0; v < V; ++v)
@@ -298,6 +301,7 @@ void GpuDijkstraMeshPlanner::exportVectorMap()
 bool GpuDijkstraMeshPlanner::potential(std::vector<float>& out)
 {
   out.assign(dev_->numVertices(), 0.f);
+  std::lock_guard<std::recursive_mutex> device_lock(dev_->handle()->mutex);
   return mnav_download_output(dev_->ctx(), 0, 0, out.data()) == 0;
 }
 
@@ -411,6 +415,7 @@ bool GpuCVPMeshPlanner::cancel()                                                
 bool GpuCVPMeshPlanner::potential(std::vector<float>& out)
 {
   out.assign(dev_->numVertices(), 0.f);
+  std::lock_guard<std::recursive_mutex> device_lock(dev_->handle()->mutex);
   return mnav_download_output(dev_->ctx(), 0, 0, out.data()) == 0;
 }
 
@@ -429,6 +434,7 @@ uint32_t GpuCVPMeshPlanner::plan(const mesh_map::Vector& wave_seed, const mesh_m
   const lvr2::FaceHandle seed_face = seed_opt.unwrap(), target_face = target_opt.unwrap();
   path.clear();
   std::string err;
+  std::lock_guard<std::recursive_mutex> device_lock(dev_->handle()->mutex);   // a controller tick on this context waits (and the other way round)
   if (!dev_->syncCosts(*mesh_map_, err, reload_costs_.exchange(false))) { message = err; return Result::INTERNAL_ERROR; }
   const uint32_t V = dev_->numVertices();
   // the V-sized field crosses PCIe only when someone on the host reads it: the map (setVectorMap, the controller's
@@ -470,15 +476,18 @@ uint32_t GpuCVPMeshPlanner::plan(const mesh_map::Vector& wave_seed, const mesh_m
     if (st == -1) { message = "Could not find a valid path, while back-tracking from the goal: HalfEdgeMesh panicked!"; return Result::NO_PATH_FOUND; }
     if (st != 1) { message = "Could not find a valid path, while back-tracking from the goal"; return Result::NO_PATH_FOUND; }
     if (cancel_planning_) return Result::CANCELED;
+    mnav_host::publish_field(mesh_map_.get(), dev_->handle(), 0, seed_face.idx());   // where mesh_gpu_planners/GpuMeshController finds the resident field
     return Result::SUCCESS;
   }
   // :920-966 on the host: the map's own meshAhead over the field just handed to it
-  return mnav_host::backtrack_on_host(seed, seed_face, target, target_face, config_.step_width, [&] { return cancel_planning_.load(); },
-                                      [&](mesh_map::Vector& pos, lvr2::FaceHandle& face, double width) {
-                                        try { return mesh_map_->meshAhead(pos, face, width) ? 1 : 0; }
-                                        catch (lvr2::PanicException&) { return -1; }
-                                      },
-                                      0, path, message);
+  const uint32_t walked = mnav_host::backtrack_on_host(seed, seed_face, target, target_face, config_.step_width, [&] { return cancel_planning_.load(); },
+                                                      [&](mesh_map::Vector& pos, lvr2::FaceHandle& face, double width) {
+                                                        try { return mesh_map_->meshAhead(pos, face, width) ? 1 : 0; }
+                                                        catch (lvr2::PanicException&) { return -1; }
+                                                      },
+                                                      0, path, message);
+  if (walked == Result::SUCCESS) mnav_host::publish_field(mesh_map_.get(), dev_->handle(), 0, seed_face.idx());
+  return walked;
 }
 
 uint32_t GpuCVPMeshPlanner::makePlan(const PoseStamped& start, const PoseStamped& goal, double /*tolerance*/,

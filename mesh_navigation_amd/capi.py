@@ -32,6 +32,7 @@ SYMBOLS = [
     "mnav_layer_height_diff", "mnav_layer_roughness", "mnav_layer_ridge", "mnav_neighbourhood_stats",
     "mnav_layer_border", "mnav_layer_clearance", "mnav_clearance_download", "mnav_clearance_stats",
     "mnav_locate", "mnav_locate_stats", "mnav_plan_dijkstra_batch_at", "mnav_plan_cvp_batch_at",
+    "mnav_follow_batch", "mnav_follow_stats",
     "mnav_set_option", "mnav_get_option", "mnav_shard_set_goal_tie", "mnav_last_engine",
 ]
 
@@ -65,6 +66,34 @@ class Stats(C.Structure):
 
     def as_dict(self) -> dict:
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class FollowConfig(C.Structure):
+    """mnav_follow_config (include/mnav.h): the parameters of mesh_controller.h:193-200 with their defaults."""
+    _fields_ = [("max_lin_velocity", C.c_double), ("max_ang_velocity", C.c_double), ("arrival_fading", C.c_double),
+                ("ang_vel_factor", C.c_double), ("lin_vel_factor", C.c_double), ("max_angle", C.c_double),
+                ("max_search_radius", C.c_double), ("max_search_distance", C.c_double)]
+    DEFAULTS = dict(max_lin_velocity=1.0, max_ang_velocity=0.5, arrival_fading=0.5, ang_vel_factor=1.0, lin_vel_factor=1.0,
+                    max_angle=20.0, max_search_radius=0.4, max_search_distance=0.4)
+
+    def __init__(self, **kw):
+        super().__init__(**{**self.DEFAULTS, **kw})
+
+
+FOLLOW_OK, FOLLOW_OUT_OF_MAP, FOLLOW_NO_FIELD = 0, 1, 2
+
+
+@dataclass
+class FollowOut:
+    """One mnav_follow_batch call: an array per output, one row per robot (None where the output was not asked for)."""
+    code: np.ndarray | None
+    face: np.ndarray | None
+    bary: np.ndarray | None
+    pos: np.ndarray | None
+    mesh_dir: np.ndarray | None
+    cost: np.ndarray | None
+    cmd: np.ndarray | None        # (n, 2) float64: linear x, angular z
+    how: np.ndarray | None
 
 
 _lib = None
@@ -113,6 +142,10 @@ def load(path: str | None = None):
     L.mnav_plan_dijkstra_batch_at.argtypes = [vp, u32, vp, vp, f64, f64, vp, vp, vp, vp, vp, vp, u32, vp]
     L.mnav_plan_cvp_batch_at.restype = u32
     L.mnav_plan_cvp_batch_at.argtypes = [vp, u32, vp, vp, f64, f64, vp, vp, vp, vp, vp, vp]
+    L.mnav_follow_batch.restype = C.c_int
+    L.mnav_follow_batch.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, C.POINTER(FollowConfig), vp, vp, vp, vp, vp, vp, vp, vp]
+    L.mnav_follow_stats.restype = C.c_int
+    L.mnav_follow_stats.argtypes = [vp] + [C.POINTER(u32)] * 6 + [C.POINTER(C.c_float)] * 2
     L.mnav_cancel.argtypes = [vp]
     L.mnav_get_stats.restype = C.c_int
     L.mnav_get_stats.argtypes = [vp, C.POINTER(Stats)]
@@ -754,6 +787,37 @@ class MnavContext:
         b, mb, mq, c = C.c_uint32(), C.c_float(), C.c_float(), C.c_uint64()
         self._L.mnav_locate_stats(self._h, C.byref(b), C.byref(mb), C.byref(mq), C.byref(c))
         return dict(built=b.value, ms_build=mb.value, ms_query=mq.value, candidates=c.value)
+
+    def follow(self, pos, direction, up, face_in, slots, seed_faces=None, config: FollowConfig | None = None, outputs=None) -> FollowOut:
+        """One controller tick of mesh_controller::MeshController for n robots over the resident vector maps of the last
+        plan call (mnav_follow_batch, include/mnav.h).  pos / direction / up: (n, 3); face_in: the face of the last tick
+        or NONE; slots: the plan each robot follows; seed_faces: that plan's seed face per robot (optional).  `outputs`:
+        the names of the FollowOut fields to fetch (default: all)."""
+        p, d, u = (_f32(a).reshape(-1, 3) for a in (pos, direction, up))
+        fi, sl = _u32(face_in).reshape(-1), _u32(slots).reshape(-1)
+        n = int(p.shape[0])
+        if not (d.shape[0] == u.shape[0] == fi.shape[0] == sl.shape[0] == n):
+            raise ValueError("follow: the per-robot arrays differ in length")
+        sf = None if seed_faces is None else _u32(seed_faces).reshape(-1)
+        if sf is not None and sf.shape[0] != n:
+            raise ValueError("follow: seed_faces needs one entry per robot")
+        cfg = config if config is not None else FollowConfig()
+        want = set(FollowOut.__dataclass_fields__) if outputs is None else set(outputs)
+        shapes = dict(code=((n,), np.int32), face=((n,), np.uint32), bary=((n, 3), np.float32), pos=((n, 3), np.float32),
+                      mesh_dir=((n, 3), np.float32), cost=((n,), np.float32), cmd=((n, 2), np.float64), how=((n,), np.int32))
+        o = {k: (np.zeros(*shapes[k]) if k in want else None) for k in shapes}
+        rc = self._L.mnav_follow_batch(self._h, n, _p(p), _p(d), _p(u), _p(fi), _p(sl), _p(sf), C.byref(cfg), _p(o["code"]), _p(o["face"]),
+                                       _p(o["bary"]), _p(o["pos"]), _p(o["mesh_dir"]), _p(o["cost"]), _p(o["cmd"]), _p(o["how"]))
+        if rc != 0:
+            raise RuntimeError(f"mnav_follow_batch failed: {self._err()}")
+        return FollowOut(**o)
+
+    def follow_stats(self) -> dict:
+        v = [C.c_uint32() for _ in range(6)]
+        mk, mt = C.c_float(), C.c_float()
+        self._L.mnav_follow_stats(self._h, *[C.byref(x) for x in v], C.byref(mk), C.byref(mt))
+        names = ("stayed", "neighbour", "global", "lost", "no_field", "built_index")
+        return dict(**{k: x.value for k, x in zip(names, v)}, ms_kernels=mk.value, ms_total=mt.value)
 
     def plan_dijkstra_batch_at(self, goal_pos, start_pos, goal_dist_offset: float = 0.3, cost_limit: float = 1.0,
                                want_fields: bool = False, path_cap: int | None = None, want_stats: bool = True):

@@ -1,10 +1,12 @@
 // adapter_capi.cpp -- tiny C harness around the C++ planner adapter so that the (Python) parity tests
 // can drive makePlan()/cancel()/initialize() exactly like mbf_mesh_nav does
 // (mbf_mesh_nav/src/mesh_navigation_server.cpp:185-212, mesh_planner_execution.cpp:55-66).
+#include <cmath>
 #include <cstring>
 #include <memory>
 #include <string>
 
+#include "gpu_mesh_controller.h"
 #include "gpu_mesh_planners.h"
 
 struct mnav_adapter_planner {
@@ -13,6 +15,11 @@ struct mnav_adapter_planner {
   std::shared_ptr<mbf_mesh_core::MeshPlanner> planner;
   bool is_cvp = false;
   std::string message;
+};
+
+struct mnav_adapter_controller {
+  mnav_host::ContextHandle dev;                             // the planner's device context (its handle outlives the planner)
+  mesh_controller::MeshController controller;
 };
 
 extern "C" {
@@ -206,6 +213,91 @@ static uint32_t host_backtrack(mesh_map::MeshMap& m, uint32_t V, const float* ve
   }
   *path_len = n;
   return code;
+}
+
+// -- mesh_controller::MeshController over the planner's map and device context, driven like mbf_mesh_nav drives a
+// controller plugin (mesh_controller_execution.cpp): setPlan, computeVelocityCommands per tick, isGoalReached, cancel.
+// cfg: the eight parameters of mesh_controller.h:193-200 in that order, or null for the defaults.
+mnav_adapter_controller* mnav_adapter_controller_create(mnav_adapter_planner* a, const double* cfg)
+{
+  static const char* names[8] = { "max_lin_velocity", "max_ang_velocity", "arrival_fading", "ang_vel_factor", "lin_vel_factor", "max_angle",
+                                  "max_search_radius", "max_search_distance" };
+  if (!a) return nullptr;
+  auto* c = new mnav_adapter_controller();
+  c->dev = a->is_cvp ? static_cast<cvp_mesh_planner::CVPMeshPlanner*>(a->planner.get())->deviceContext()
+                     : static_cast<dijkstra_mesh_planner::DijkstraMeshPlanner*>(a->planner.get())->deviceContext();
+  auto node = std::make_shared<rclcpp::Node>();
+  if (cfg) for (int k = 0; k < 8; ++k) node->set_override(std::string("mesh_controller.") + names[k], cfg[k]);
+  if (!c->controller.initialize("mesh_controller", a->map, node)) { delete c; return nullptr; }
+  return c;
+}
+
+void mnav_adapter_controller_destroy(mnav_adapter_controller* c) { delete c; }
+
+// poses: x y z qx qy qz qw per pose (the plan makePlan produced); slot: the plan's index in the planner's last call;
+// seed_face: the plan's seed face or 0xFFFFFFFF
+int mnav_adapter_controller_set_plan(mnav_adapter_controller* c, const double* poses, uint32_t n, uint32_t slot, uint32_t seed_face)
+{
+  std::vector<geometry_msgs::msg::PoseStamped> plan(n);
+  for (uint32_t i = 0; i < n; ++i) {
+    const double* v = poses + 7 * (size_t)i;
+    auto& p = plan[i].pose;
+    p.position.x = v[0]; p.position.y = v[1]; p.position.z = v[2];
+    p.orientation.x = v[3]; p.orientation.y = v[4]; p.orientation.z = v[5]; p.orientation.w = v[6];
+  }
+  return c->controller.setPlan(plan, c->dev, slot, seed_face) ? 1 : 0;
+}
+
+// one tick.  Returns the controller's Outcome (0 SUCCESS, 1 OUT_OF_MAP, 2 FAILURE, 3 CANCELED, 4 INTERNAL_ERROR);
+// cmd = linear x, angular z; face / pos = what the controller keeps for the next tick
+uint32_t mnav_adapter_controller_compute(mnav_adapter_controller* c, const double pose[7], double cmd[2], uint32_t* face, float pos[3], char* message,
+                                         uint32_t message_cap)
+{
+  geometry_msgs::msg::PoseStamped p;
+  p.pose.position.x = pose[0]; p.pose.position.y = pose[1]; p.pose.position.z = pose[2];
+  p.pose.orientation.x = pose[3]; p.pose.orientation.y = pose[4]; p.pose.orientation.z = pose[5]; p.pose.orientation.w = pose[6];
+  mesh_controller::MeshController::Twist t;
+  std::string msg;
+  const uint32_t code = c->controller.computeVelocityCommands(p, t, msg);
+  cmd[0] = t.linear_x; cmd[1] = t.angular_z;
+  *face = c->controller.currentFace();
+  const mesh_map::Vector r = c->controller.robotPosition();
+  pos[0] = r.x; pos[1] = r.y; pos[2] = r.z;
+  if (message && message_cap) { std::strncpy(message, msg.c_str(), message_cap - 1); message[message_cap - 1] = 0; }
+  return code;
+}
+
+int mnav_adapter_controller_goal_reached(mnav_adapter_controller* c, double dist_tolerance, double angle_tolerance)
+{
+  return c->controller.isGoalReached(dist_tolerance, angle_tolerance) ? 1 : 0;
+}
+
+int mnav_adapter_controller_cancel(mnav_adapter_controller* c) { return c->controller.cancel() ? 1 : 0; }
+
+// heading (axis 0: x) or up vector (axis 2: z) of a pose, as the controller derives it from the quaternion
+void mnav_adapter_controller_direction(const double pose[7], int axis, float out[3])
+{
+  geometry_msgs::msg::PoseStamped p;
+  p.pose.orientation.x = pose[3]; p.pose.orientation.y = pose[4]; p.pose.orientation.z = pose[5]; p.pose.orientation.w = pose[6];
+  const double a[3] = { axis == 0 ? 1.0 : 0.0, axis == 1 ? 1.0 : 0.0, axis == 2 ? 1.0 : 0.0 };
+  const mesh_map::Normal v = mesh_controller::MeshController::poseToDirectionVector(p, a);
+  out[0] = v.x; out[1] = v.y; out[2] = v.z;
+}
+
+// What the reference's controller reads: MeshMap::directionAtPosition (mesh_map.cpp:625-650) over the vector map the
+// planner's setVectorMap left in the HOST map.  1 + out = the direction, 0 = none (no field on the host).
+int mnav_adapter_host_direction(mnav_adapter_planner* a, uint32_t face, const float bary[3], float out[3])
+{
+  const mesh_map::MeshMap& m = *a->map;
+  if (face >= m.F || m.vector_map_set.size() != m.V) return 0;
+  const uint32_t* vs = &m.faces[3 * (size_t)face];
+  if (!(m.vector_map_set[vs[0]] || m.vector_map_set[vs[1]] || m.vector_map_set[vs[2]])) return 0;   // :633
+  mesh_map::Vector vec(0, 0, 0);
+  for (int k = 0; k < 3; ++k)
+    if (m.vector_map_set[vs[k]]) vec = vec + mesh_map::Vector(m.vector_map[3 * (size_t)vs[k]], m.vector_map[3 * (size_t)vs[k] + 1], m.vector_map[3 * (size_t)vs[k] + 2]) * bary[k];   // :636-638
+  if (!(std::isfinite(vec.x) && std::isfinite(vec.y) && std::isfinite(vec.z))) return 0;           // :639
+  out[0] = vec.x; out[1] = vec.y; out[2] = vec.z;
+  return 1;
 }
 
 }  // extern "C"

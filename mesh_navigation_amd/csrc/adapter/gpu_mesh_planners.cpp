@@ -30,8 +30,8 @@ static uint64_t hash_words(const void* p, size_t n, uint64_t h)
   return h ^ (h >> 29);
 }
 
-MeshMapDevice::MeshMapDevice(int device) { ctx_ = mnav_create(device); }
-MeshMapDevice::~MeshMapDevice() { if (ctx_) mnav_destroy(ctx_); }
+MeshMapDevice::MeshMapDevice(int device) { ctx_ = mnav_create(device); handle_ = std::make_shared<mnav_host::SharedContext>(ctx_); }
+MeshMapDevice::~MeshMapDevice() { handle_->destroy(); }             // under the context's lock; a controller that holds the handle refuses from now on
 
 bool MeshMapDevice::sync(const mesh_map::MeshMap& map, std::string& err)
 {
@@ -125,7 +125,9 @@ uint32_t DijkstraMeshPlanner::dijkstra(const mesh_map::Vector& original_start, c
   if (goal_vertex == mesh_map::kNoHandle) return Result::INVALID_GOAL;        // :242
   path.clear();
   std::string err;
-  if (!dev_ || !dev_->sync(*mesh_map_, err)) return Result::INTERNAL_ERROR;
+  if (!dev_) return Result::INTERNAL_ERROR;
+  std::lock_guard<std::recursive_mutex> device_lock(dev_->handle()->mutex);   // a controller tick on this context waits (and the other way round)
+  if (!dev_->sync(*mesh_map_, err)) return Result::INTERNAL_ERROR;
   fields_on_host_ = false;
   // potential, predecessors and the vector map (computeVectorMap :380) are computed and kept on the device; only
   // the vertex path comes back.  They are fetched when somebody reads them (potential(), the controller's
@@ -143,6 +145,7 @@ uint32_t DijkstraMeshPlanner::dijkstra(const mesh_map::Vector& original_start, c
 void DijkstraMeshPlanner::fetchFields()
 {
   if (fields_on_host_ || !dev_ || !dev_->ok()) return;
+  std::lock_guard<std::recursive_mutex> device_lock(dev_->handle()->mutex);
   const uint32_t V = mesh_map_->V;
   potential_.assign(V, 0.f); predecessors_.assign(V, 0u); vector_map_.assign((size_t)V * 3, 0.f);
   if (mnav_download_output(dev_->ctx(), 0, 0, potential_.data()) != 0 || mnav_download_output(dev_->ctx(), 0, 1, predecessors_.data()) != 0 ||
@@ -221,7 +224,9 @@ uint32_t CVPMeshPlanner::waveFrontPropagation(const mesh_map::Vector& original_s
   if (goal_face == mesh_map::kNoHandle) { message = "Could not find a face close enough to the given goal pose"; return Result::INVALID_GOAL; }      // :686-690
   path.clear();
   std::string err;
-  if (!dev_ || !dev_->sync(*mesh_map_, err)) { message = err; return Result::INTERNAL_ERROR; }
+  if (!dev_) { message = "no device"; return Result::INTERNAL_ERROR; }
+  std::lock_guard<std::recursive_mutex> device_lock(dev_->handle()->mutex);   // a controller tick on this context waits (and the other way round)
+  if (!dev_->sync(*mesh_map_, err)) { message = err; return Result::INTERNAL_ERROR; }
   const uint32_t V = mesh_map_->V;
   fields_on_host_ = false;
   vector_map_.assign((size_t)V * 3, 0.f);
@@ -252,6 +257,7 @@ uint32_t CVPMeshPlanner::waveFrontPropagation(const mesh_map::Vector& original_s
 void CVPMeshPlanner::fetchFields()
 {
   if (fields_on_host_ || !dev_ || !dev_->ok()) return;
+  std::lock_guard<std::recursive_mutex> device_lock(dev_->handle()->mutex);
   const uint32_t V = mesh_map_->V;
   potential_.assign(V, 0.f); predecessors_.assign(V, 0u); cutting_faces_.assign(V, mesh_map::kNoHandle); direction_.assign(V, 0.f);
   if (mnav_download_output(dev_->ctx(), 0, 0, potential_.data()) != 0 || mnav_download_output(dev_->ctx(), 0, 1, predecessors_.data()) != 0 ||

@@ -10,6 +10,7 @@
 #include <utility>
 
 #include "../../../include/mnav.h"
+#include "../../../include/mnav_controller_host.hpp"
 #include "mesh_planner.h"
 
 namespace mnav_adapter {
@@ -20,11 +21,14 @@ public:
   ~MeshMapDevice();
   bool ok() const { return ctx_ != nullptr; }
   mnav_ctx* ctx() const { return ctx_; }
+  // the context with its lock (mnav_controller_host.hpp): a plan and a controller tick on it exclude each other
+  const mnav_host::ContextHandle& handle() const { return handle_; }
   // uploads the mesh on first use and the cost arrays whenever their content changed (the reference
   // re-reads vertex_costs / edge_weights by const-ref on every plan, dijkstra_mesh_planner.cpp:214)
   bool sync(const mesh_map::MeshMap& map, std::string& err);
 private:
   mnav_ctx* ctx_ = nullptr;
+  mnav_host::ContextHandle handle_;
   const mesh_map::MeshMap* uploaded_ = nullptr;
   uint64_t cost_hash_ = 0;
   bool have_costs_ = false;
@@ -48,6 +52,7 @@ public:
   const std::vector<float>& getVectorMap() { fetchFields(); return vector_map_; }   // dijkstra_mesh_planner.h:126
   void fetchFields();
   void setEagerFields(bool on) { eager_fields_ = on; }                // download after every plan, like the reference's host maps
+  mnav_host::ContextHandle deviceContext() const { return dev_ ? dev_->handle() : nullptr; }   // where the last plan's fields are resident (MeshController::setPlan)
 protected:
   // dijkstra_mesh_planner.cpp:211-215 (the 3-arg overload): wave from `start` towards `goal`
   uint32_t dijkstra(const mesh_map::Vector& start, const mesh_map::Vector& goal, std::list<uint32_t>& path);
@@ -78,6 +83,7 @@ public:
   const std::vector<float>& potential() { fetchFields(); return potential_; }
   void fetchFields();
   void setEagerFields(bool on) { eager_fields_ = on; }
+  mnav_host::ContextHandle deviceContext() const { return dev_ ? dev_->handle() : nullptr; }
 protected:
   // cvp_mesh_planner.cpp:241-247 (the 4-arg overload)
   uint32_t waveFrontPropagation(const mesh_map::Vector& start, const mesh_map::Vector& goal,

@@ -89,6 +89,9 @@ public:
   bool meshAhead(Vector& pos, uint32_t& face, float step_size) const;               // :1070-1108
   struct MapPanic { };                                                              // lvr2::PanicException stand-in
   void setVectorMap(const std::vector<float>& vm, const std::vector<uint8_t>& set) { vector_map = vm; vector_map_set = set; }
+  // searchNeighbourFaces for callers outside the map (the controller's host baseline, tools/follow_perf.py)
+  bool findNeighbourFace(const Vector& pos, uint32_t face, float max_radius, float max_dist, uint32_t& found, std::array<float, 3>& bary) const
+  { return searchNeighbourFaces(pos, face, max_radius, max_dist, found, bary); }
 
 private:
   bool searchNeighbourFaces(const Vector& pos, uint32_t face, float max_radius, float max_dist, uint32_t& found,

@@ -81,6 +81,7 @@ constexpr int kChunk = 96;  // step launches per graph replay; multiple of 6 (sl
 #include "mnav_nbhd.h"       // height-difference / roughness / ridge layers: neighbourhood visits (mnav_nb::)
 #include "mnav_clearance.h"  // clearance / border layers: normal ray casts over the obstacle BVH, border test (mnav_clr::)
 #include "mnav_locate.h"     // pose lookup: point LBVH over the vertices, exact nearest vertex, containing face (mnav_loc::)
+#include "mnav_follow.h"     // vector-field follower: one controller tick for a batch of robots over the resident fields (mnav_fol::)
 
 // One back-tracking job: the plan's resident vector map and the two ends of the walk.
 struct WalkJob { const float* vecmap; float seed[3]; uint32_t seed_face; float target[3]; uint32_t target_face; };
@@ -214,6 +215,7 @@ struct mnav_ctx {
   mnav_nb::State nbhd;                                             // neighbourhood layers: counters, spill lists and scratch of the last call
   mnav_clr::State clr;                                             // clearance / border layers: cached clearance (first clearance call after an upload)
   mnav_loc::State loc;                                             // pose lookup: vertex index built by the first mnav_locate after an upload
+  mnav_fol::State fol;                                             // vector-field follower: buffers and counters of the last mnav_follow_batch
   mnav_chg::Scratch chg;                                           // obstacle / clearance / border layers: change list and counters of the last call
   uint32_t infl_steps = 0, infl_bands = 0; uint64_t infl_evals = 0; float infl_ms = 0.f, infl_ms_wave = 0.f;   // last inflation wave
   DevBuf<TilePlan> d_tplans; uint32_t tplans_cap = 0;
@@ -1645,6 +1647,7 @@ uint32_t mnav_plan_cvp_batch(mnav_ctx* ctx, uint32_t n, const float* seed_pos, c
 #include "mnav_nbhd_capi.h"       // mnav_layer_height_diff / _roughness / _ridge, mnav_neighbourhood_stats
 #include "mnav_clearance_capi.h"  // mnav_layer_clearance, mnav_layer_border, mnav_clearance_download, mnav_clearance_stats
 #include "mnav_locate_capi.h"     // mnav_locate, mnav_locate_stats, mnav_plan_dijkstra_batch_at, mnav_plan_cvp_batch_at
+#include "mnav_follow_capi.h"     // mnav_follow_batch, mnav_follow_stats
 
 void mnav_cancel(mnav_ctx* ctx)
 {

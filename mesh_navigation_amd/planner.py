@@ -37,6 +37,20 @@ def _load():
         L.mnav_adapter_fetch.restype = C.c_int
         L.mnav_adapter_fetch.argtypes = [vp, C.c_int, vp]
         L.mnav_adapter_add_layer_field.argtypes = [vp, vp, vp, vp, vp, f64, f64, f64, f64, C.c_int]
+        L.mnav_adapter_controller_create.restype = vp
+        L.mnav_adapter_controller_create.argtypes = [vp, vp]
+        L.mnav_adapter_controller_destroy.argtypes = [vp]
+        L.mnav_adapter_controller_set_plan.restype = C.c_int
+        L.mnav_adapter_controller_set_plan.argtypes = [vp, vp, u32, u32, u32]
+        L.mnav_adapter_controller_compute.restype = u32
+        L.mnav_adapter_controller_compute.argtypes = [vp, vp, vp, C.POINTER(u32), vp, C.c_char_p, u32]
+        L.mnav_adapter_controller_goal_reached.restype = C.c_int
+        L.mnav_adapter_controller_goal_reached.argtypes = [vp, f64, f64]
+        L.mnav_adapter_controller_cancel.restype = C.c_int
+        L.mnav_adapter_controller_cancel.argtypes = [vp]
+        L.mnav_adapter_controller_direction.argtypes = [vp, C.c_int, vp]
+        L.mnav_adapter_host_direction.restype = C.c_int
+        L.mnav_adapter_host_direction.argtypes = [vp, u32, vp, vp]
         _lib = L
     return _lib
 
@@ -118,6 +132,13 @@ class _MeshPlanner:
         _load().mnav_adapter_add_layer_field(self._h, _p(a[0]), _p(a[1]), _p(a[2]), _p(a[3]), float(inscribed_radius),
                                              float(inflation_radius), float(lethal_value), float(inscribed_value), int(repulsive_field))
 
+    def host_direction(self, face: int, bary):
+        """MeshMap::directionAtPosition over the vector map in the HOST map (what the reference's controller reads after
+        the planner's setVectorMap): the direction, or None when the host map holds no field there."""
+        out = np.zeros(3, np.float32)
+        ok = _load().mnav_adapter_host_direction(self._h, int(face), _p(np.ascontiguousarray(bary, np.float32)), _p(out))
+        return out if ok else None
+
     def close(self):
         if self._h:
             _load().mnav_adapter_destroy(self._h)
@@ -138,3 +159,60 @@ class DijkstraMeshPlanner(_MeshPlanner):
 class CVPMeshPlanner(_MeshPlanner):
     """cvp_mesh_planner/CVPMeshPlanner (cvp_mesh_planner.xml:1-8)."""
     KIND = 1
+
+
+class MeshController:
+    """mesh_controller/MeshController (mesh_controller.xml) over a planner's map and device context: the C++ adapter class
+    of that name (csrc/adapter/gpu_mesh_controller.h), which follows the vector field the planner left on the device."""
+    SUCCESS, OUT_OF_MAP, FAILURE, CANCELED, INTERNAL_ERROR = 0, 1, 2, 3, 4
+    PARAMS = ("max_lin_velocity", "max_ang_velocity", "arrival_fading", "ang_vel_factor", "lin_vel_factor", "max_angle",
+              "max_search_radius", "max_search_distance")
+
+    def __init__(self):
+        self._h = None
+        self._planner = None
+
+    def initialize(self, name: str, planner: _MeshPlanner, params: dict | None = None) -> bool:
+        cfg = None
+        if params:
+            defaults = dict(zip(self.PARAMS, (1.0, 0.5, 0.5, 1.0, 1.0, 20.0, 0.4, 0.4)))      # mesh_controller.h:193-200
+            cfg = np.array([float(params.get(k, defaults[k])) for k in self.PARAMS], np.float64)
+        self._planner = planner                                       # keeps the map and the device context alive
+        self._h = _load().mnav_adapter_controller_create(planner._h, _p(cfg))
+        return bool(self._h)
+
+    def setPlan(self, plan, slot: int = 0, seed_face: int = 0xFFFFFFFF) -> bool:
+        poses = np.ascontiguousarray(plan, np.float64).reshape(-1, 7)
+        return bool(_load().mnav_adapter_controller_set_plan(self._h, _p(poses), poses.shape[0], int(slot), int(seed_face) & 0xFFFFFFFF))
+
+    def computeVelocityCommands(self, pose):
+        """Returns (code, (linear x, angular z), current face, robot position, message)."""
+        p = np.ascontiguousarray(pose, np.float64)
+        cmd, face, pos = np.zeros(2, np.float64), C.c_uint32(0), np.zeros(3, np.float32)
+        msg = C.create_string_buffer(256)
+        code = _load().mnav_adapter_controller_compute(self._h, _p(p), _p(cmd), C.byref(face), _p(pos), msg, 256)
+        return int(code), cmd, int(face.value), pos, msg.value.decode()
+
+    def isGoalReached(self, dist_tolerance: float, angle_tolerance: float) -> bool:
+        return bool(_load().mnav_adapter_controller_goal_reached(self._h, float(dist_tolerance), float(angle_tolerance)))
+
+    def cancel(self) -> bool:
+        return bool(_load().mnav_adapter_controller_cancel(self._h))
+
+    @staticmethod
+    def direction(pose, axis: int = 0) -> np.ndarray:
+        """heading (axis 0) or up vector (axis 2) the controller derives from the pose's quaternion"""
+        out = np.zeros(3, np.float32)
+        _load().mnav_adapter_controller_direction(_p(np.ascontiguousarray(pose, np.float64)), int(axis), _p(out))
+        return out
+
+    def close(self):
+        if self._h:
+            _load().mnav_adapter_controller_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
