@@ -306,6 +306,80 @@ int mnav_clearance_download(const mnav_ctx* ctx, float* clearance_out);
 int mnav_clearance_stats(const mnav_ctx* ctx, uint32_t* cast, uint32_t* rays, uint32_t* hits, float* ms_bvh_build, float* ms_cast,
                          float* ms_total);
 
+/* -- the resident layer graph ------------------------------------------------------------------------
+ * mesh_map::LayerManager (layer_manager.cpp:153-263) + MeshMap::layerChanged (mesh_map.cpp:454-493) on the device: the
+ * layer stack is declared once; after that one call per event brings every dependent layer, the resident vertex costs and
+ * the edge weights to the state the reference's notification chain (notifyChange -> LayerManager::layer_changed ->
+ * MeshMap::layerChanged -> updateEdgeWeights(changed), plus onInputChanged of every dependent layer) would leave.  Between
+ * the stages only counters cross PCIe; the change lists stay on the device.
+ *
+ * A node is a layer slot.  An INPUT node is a slot the caller fills with any writer (mnav_layer_upload, _steepness,
+ * _height_diff, _roughness, _ridge, _border, _clearance, _obstacle).  Derived nodes are owned by the graph:
+ *   INFLATION     mnav_layer_inflation of its one input with the node's five parameters
+ *   COMBINE_MAX   cost = max over the inputs, from 0.0f, in input order (combination_layer.cpp:44-85)
+ *   COMBINE_AVG   cost = sum of weights[k] * input k, from 0.0f, in input order, float multiply then float add (:185-248)
+ *                 both: lethal flag = OR of the inputs' flags (:73-79, :122-139); a NaN cost never replaces the running max
+ * so a combination is a layer like any other: it can feed an inflation or another combination. */
+enum { MNAV_NODE_INPUT = 0, MNAV_NODE_INFLATION = 1, MNAV_NODE_COMBINE_MAX = 2, MNAV_NODE_COMBINE_AVG = 3 };
+typedef struct {
+  uint32_t layer;            /* slot 0..63 */
+  uint32_t kind;
+  uint32_t n_inputs;         /* INPUT: 0; INFLATION: exactly 1; COMBINE_*: 1..8 */
+  uint32_t inputs[8];        /* slots of other nodes */
+  float    weights[8];       /* COMBINE_AVG: combinationWeight of each input, in input order */
+  double   inflation_radius, inscribed_radius, inscribed_value, lethal_value, cost_scaling_factor;  /* INFLATION */
+} mnav_map_node;
+/* Declares the graph (after mnav_upload_mesh; the next mnav_upload_mesh drops it).  default_layer is the node whose costs
+ * become the vertex costs the planners read (any kind); edge_cost_factor and invalid (V bytes or NULL: the map's
+ * non-manifold flags, read by the inflation waves and the planners) are those of mnav_combine_layers.  Returns <0 with a
+ * mnav_last_error text, and leaves a previous configuration in place and usable, for: a slot out of range or listed
+ * twice, an input that is not a node, a wrong n_inputs for the kind, a cycle, a default layer that is not a node.  The
+ * order of evaluation is a dependency order (inputs before users; among ready nodes, the order of `nodes`). */
+int mnav_map_configure(mnav_ctx* ctx, uint32_t n_nodes, const mnav_map_node* nodes, uint32_t default_layer, double edge_cost_factor,
+                       const uint8_t* invalid);
+/* The layer part of MeshMap::readMap (mesh_map.cpp:427-448): every INPUT slot must be resident; the derived nodes are
+ * computed in order, the default layer is copied into the resident vertex costs (copyVertexCostsFromDefaultLayer) and the
+ * full edge-weight pass runs (as mnav_combine_layers).  An inflation node works in the first plan slot, as
+ * mnav_layer_inflation does: the resident outputs of the last plan are gone afterwards.  That holds for the three update
+ * calls below whenever they re-run a wave. */
+int mnav_map_compute(mnav_ctx* ctx);
+/* The run-time chain, after a successful mnav_map_compute.  Each call names an INPUT node (a derived node is refused):
+ *   mnav_map_update_layer   vertex_ids[i] takes costs[i] and, unless lethal is NULL, the flag lethal[i] (the harness's
+ *                           ArrayLayer::update: duplicates allowed, of equal ids the last one counts); the layer's change
+ *                           list is the given ids.  An id >= V is an error raised before anything is written.
+ *   mnav_map_layer_changed  the caller rewrote the slot through one of the writers above and reports the vertices that
+ *                           changed (e.g. the changed_out of mnav_layer_border); which lethal flags flipped is not known
+ *                           here, so an inflation node on this input re-runs its wave whenever n > 0
+ *   mnav_map_obstacle       mnav_layer_obstacle on the slot (same arguments from n_points to max_obstacle_dist); its change
+ *                           list never leaves the device
+ * Then every dependent node is visited in dependency order with the union of the change lists of its inputs that changed
+ * in this call.  A combination recombines those vertices (cost and flag); its own list is the subset whose cost bits or
+ * flag now differ.  An inflation node whose input had no lethal flag flipped on the list is left alone and emits nothing
+ * (waveCostInflation is a function of the lethal set only); otherwise the wave is re-run whole, as the reference does
+ * (inflation_layer.cpp:143), and its list is the vertices whose cost bits or flag differ from before.  Finally, for the
+ * default layer's list D: the resident vertex costs take the layer's values on D, the edges around D are re-weighted if
+ * edge_cost_factor != 0 (mesh_map.cpp:568-572), the host's cost mirror takes the |D| (id, value) pairs -- the only id-sized
+ * download of the call -- and the cost-limit folded planner tables are rebuilt by the next plan.  changed_out (capacity V,
+ * or NULL) receives D ascending, n_changed (or NULL) its length.
+ * Departure from the reference: it forwards larger sets (a combination its whole incoming set, an inflation every vertex
+ * either wave reached); recombining and re-weighting are idempotent, so every layer's costs and flags, the inflation
+ * distances and vector field, the vertex costs and the edge weights are the same bit for bit, but the list reported here
+ * is the tighter one: the vertices whose default-layer cost bits (or flag) changed.
+ * A wave that fails its verification sweep, or any other failure after the first write, returns <0 and marks the graph
+ * stale: the update calls then fail until a mnav_map_compute succeeds.  Writers used on an INPUT slot without a following
+ * mnav_map_layer_changed, and mnav_upload_costs / mnav_combine_* on a context with a graph, leave the graph's state behind;
+ * mnav_map_compute brings it back. */
+int mnav_map_layer_changed(mnav_ctx* ctx, uint32_t layer, uint32_t n, const uint32_t* vertex_ids, uint32_t* changed_out, uint32_t* n_changed);
+int mnav_map_update_layer(mnav_ctx* ctx, uint32_t layer, uint32_t n, const uint32_t* vertex_ids, const float* costs, const uint8_t* lethal,
+                          uint32_t* changed_out, uint32_t* n_changed);
+int mnav_map_obstacle(mnav_ctx* ctx, uint32_t layer, uint32_t n_points, const void* points, uint32_t point_step, const float* sensor_to_map,
+                      const float* down_axis, double robot_height, double max_obstacle_dist, uint32_t* changed_out, uint32_t* n_changed);
+/* The last update call: inflation waves re-run, vertices recombined (summed over the combination nodes), |D|, incident
+ * edges visited by the re-weighting (an edge between two vertices of D counts twice; 0 when edge_cost_factor == 0), device
+ * milliseconds of the whole call and of its waves.  Any pointer may be NULL. */
+int mnav_map_stats(const mnav_ctx* ctx, uint32_t* waves, uint32_t* recombined, uint32_t* default_changed, uint32_t* edges_reweighted,
+                   float* ms_total, float* ms_wave);
+
 /* -- pose lookup on the device ---------------------------------------------------------------------
  * MeshMap::getNearestVertexHandle (mesh_map.cpp:1161-1174) and MeshMap::getContainingFace / searchContainingFace
  * (:1120-1159) for n positions (pos: n*3 floats) in one call; only the positions go up and the results come down.

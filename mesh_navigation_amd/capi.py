@@ -33,6 +33,7 @@ SYMBOLS = [
     "mnav_layer_border", "mnav_layer_clearance", "mnav_clearance_download", "mnav_clearance_stats",
     "mnav_locate", "mnav_locate_stats", "mnav_plan_dijkstra_batch_at", "mnav_plan_cvp_batch_at",
     "mnav_follow_batch", "mnav_follow_stats",
+    "mnav_map_configure", "mnav_map_compute", "mnav_map_layer_changed", "mnav_map_update_layer", "mnav_map_obstacle", "mnav_map_stats",
     "mnav_set_option", "mnav_get_option", "mnav_shard_set_goal_tie", "mnav_last_engine",
 ]
 
@@ -81,6 +82,16 @@ class FollowConfig(C.Structure):
 
 
 FOLLOW_OK, FOLLOW_OUT_OF_MAP, FOLLOW_NO_FIELD = 0, 1, 2
+
+
+class MapNode(C.Structure):
+    """mnav_map_node (include/mnav.h): one node of the resident layer graph"""
+    _fields_ = [("layer", C.c_uint32), ("kind", C.c_uint32), ("n_inputs", C.c_uint32), ("inputs", C.c_uint32 * 8),
+                ("weights", C.c_float * 8), ("inflation_radius", C.c_double), ("inscribed_radius", C.c_double),
+                ("inscribed_value", C.c_double), ("lethal_value", C.c_double), ("cost_scaling_factor", C.c_double)]
+
+
+NODE_KINDS = {"input": 0, "inflation": 1, "max": 2, "avg": 3}
 
 
 @dataclass
@@ -146,6 +157,18 @@ def load(path: str | None = None):
     L.mnav_follow_batch.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, C.POINTER(FollowConfig), vp, vp, vp, vp, vp, vp, vp, vp]
     L.mnav_follow_stats.restype = C.c_int
     L.mnav_follow_stats.argtypes = [vp] + [C.POINTER(u32)] * 6 + [C.POINTER(C.c_float)] * 2
+    L.mnav_map_configure.restype = C.c_int
+    L.mnav_map_configure.argtypes = [vp, u32, C.POINTER(MapNode), u32, f64, vp]
+    L.mnav_map_compute.restype = C.c_int
+    L.mnav_map_compute.argtypes = [vp]
+    L.mnav_map_layer_changed.restype = C.c_int
+    L.mnav_map_layer_changed.argtypes = [vp, u32, u32, vp, vp, C.POINTER(u32)]
+    L.mnav_map_update_layer.restype = C.c_int
+    L.mnav_map_update_layer.argtypes = [vp, u32, u32, vp, vp, vp, vp, C.POINTER(u32)]
+    L.mnav_map_obstacle.restype = C.c_int
+    L.mnav_map_obstacle.argtypes = [vp, u32, u32, vp, u32, vp, vp, f64, f64, vp, C.POINTER(u32)]
+    L.mnav_map_stats.restype = C.c_int
+    L.mnav_map_stats.argtypes = [vp] + [C.POINTER(u32)] * 4 + [C.POINTER(C.c_float)] * 2
     L.mnav_cancel.argtypes = [vp]
     L.mnav_get_stats.restype = C.c_int
     L.mnav_get_stats.argtypes = [vp, C.POINTER(Stats)]
@@ -481,6 +504,14 @@ class MnavContext:
         after normalising the quaternion, in float32 (the reference does that conversion with Eigen; that the two agree
         bit for bit is not pinned).  Neither = identity.  down_axis is already in the map frame and used as given.
         Returns dict(changed = ascending uint32 ids whose lethal flag changed, n_lethal, stats = the call's counters)."""
+        args = self._obstacle_args(points, sensor_to_map, rotation_wxyz, translation, down_axis, robot_height, max_obstacle_dist)
+        out = self._change_layer("mnav_layer_obstacle", layer, *args[1:])
+        out["stats"] = self.obstacle_stats()
+        return out
+
+    @staticmethod
+    def _obstacle_args(points, sensor_to_map, rotation_wxyz, translation, down_axis, robot_height, max_obstacle_dist):
+        """the arguments of mnav_layer_obstacle from n_points to max_obstacle_dist, behind the arrays they point into"""
         pts = np.asarray(points)
         if pts.dtype.names:
             f = pts.dtype.fields
@@ -500,10 +531,7 @@ class MnavContext:
         elif rotation_wxyz is not None:
             m = quat_to_matrix(rotation_wxyz, (0.0, 0.0, 0.0) if translation is None else translation)
         d = _f32(down_axis).reshape(3)
-        out = self._change_layer("mnav_layer_obstacle", layer, n, _p(pts) if n else None, int(step), _p(m), _p(d),
-                                 float(robot_height), float(max_obstacle_dist))
-        out["stats"] = self.obstacle_stats()
-        return out
+        return (pts, m, d), n, _p(pts) if n else None, int(step), _p(m), _p(d), float(robot_height), float(max_obstacle_dist)
 
     def obstacle_stats(self) -> dict:
         k, h, lr, mb, mc, mt = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_float(), C.c_float(), C.c_float()
@@ -601,6 +629,67 @@ class MnavContext:
         ii = np.ascontiguousarray(ids, np.uint32)
         if self._L.mnav_combine_layers_update(self._h, 0 if mode == "max" else 1, len(ls), _p(ls), _p(w), ii.shape[0], _p(ii)) != 0:
             raise RuntimeError(f"mnav_combine_layers_update failed: {self._err()}")
+
+    # ---- the resident layer graph (mnav_map_*, include/mnav.h) ----
+    def map_configure(self, nodes, default_layer: int, edge_cost_factor: float = 0.0, invalid=None):
+        """nodes: dicts with layer, kind ("input" | "inflation" | "max" | "avg"), inputs (slots), weights (avg), and for an
+        inflation node any of inflation_radius, inscribed_radius, inscribed_value, lethal_value, cost_scaling_factor
+        (defaults: layer_inflation's)."""
+        arr = (MapNode * max(len(nodes), 1))()
+        for a, n in zip(arr, nodes):
+            ins = list(n.get("inputs", ()))
+            if len(ins) > 8:
+                raise ValueError("a node takes at most 8 inputs")
+            ws = list(n.get("weights", [1.0] * len(ins)))
+            a.layer, a.kind, a.n_inputs = int(n["layer"]), NODE_KINDS[n["kind"]], len(ins)
+            for k, i in enumerate(ins):
+                a.inputs[k] = int(i)
+            for k, w in enumerate(ws[:8]):
+                a.weights[k] = float(w)
+            a.inflation_radius = float(n.get("inflation_radius", 0.4))
+            a.inscribed_radius = float(n.get("inscribed_radius", 0.25))
+            a.inscribed_value = float(n.get("inscribed_value", 0.99))
+            a.lethal_value = float(n.get("lethal_value", 1.0))
+            a.cost_scaling_factor = float(n.get("cost_scaling_factor", 1.0))
+        inv = None if invalid is None else np.ascontiguousarray(invalid, np.uint8)
+        if self._L.mnav_map_configure(self._h, len(nodes), arr, int(default_layer), float(edge_cost_factor),
+                                      None if inv is None else _p(inv)) != 0:
+            raise RuntimeError(f"mnav_map_configure failed: {self._err()}")
+
+    def map_compute(self):
+        if self._L.mnav_map_compute(self._h) != 0:
+            raise RuntimeError(f"mnav_map_compute failed: {self._err()}")
+
+    def _map_call(self, name: str, layer: int, *args) -> dict:
+        """an update call of the graph: dict(changed = D ascending, stats = map_stats())"""
+        changed = np.empty(max(self.V, 1), np.uint32)
+        nc = C.c_uint32()
+        if getattr(self._L, name)(self._h, int(layer), *args, _p(changed), C.byref(nc)) != 0:
+            raise RuntimeError(f"{name} failed: {self._err()}")
+        return dict(changed=changed[:nc.value].copy(), stats=self.map_stats())
+
+    def map_layer_changed(self, layer: int, ids) -> dict:
+        ii = np.ascontiguousarray(ids, np.uint32).reshape(-1)
+        return self._map_call("mnav_map_layer_changed", layer, ii.shape[0], _p(ii))
+
+    def map_update_layer(self, layer: int, ids, costs, lethal=None) -> dict:
+        ii = np.ascontiguousarray(ids, np.uint32).reshape(-1)
+        cc = np.ascontiguousarray(costs, np.float32).reshape(-1)
+        le = None if lethal is None else np.ascontiguousarray(lethal, np.uint8).reshape(-1)
+        if cc.shape[0] != ii.shape[0] or (le is not None and le.shape[0] != ii.shape[0]):
+            raise ValueError("ids, costs and lethal must have one length")
+        return self._map_call("mnav_map_update_layer", layer, ii.shape[0], _p(ii), _p(cc), None if le is None else _p(le))
+
+    def map_obstacle(self, layer: int, points, sensor_to_map=None, rotation_wxyz=None, translation=None,
+                     down_axis=(0.0, 0.0, -1.0), robot_height: float = np.inf, max_obstacle_dist: float = np.inf) -> dict:
+        """layer_obstacle on an input node of the graph, then the propagation; same keyword arguments"""
+        args = self._obstacle_args(points, sensor_to_map, rotation_wxyz, translation, down_axis, robot_height, max_obstacle_dist)
+        return self._map_call("mnav_map_obstacle", layer, *args[1:])
+
+    def map_stats(self) -> dict:
+        w, r, d, e, mt, mw = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_float(), C.c_float()
+        self._L.mnav_map_stats(self._h, C.byref(w), C.byref(r), C.byref(d), C.byref(e), C.byref(mt), C.byref(mw))
+        return dict(waves=w.value, recombined=r.value, default_changed=d.value, edges_reweighted=e.value, ms_total=mt.value, ms_wave=mw.value)
 
     # ---- one plan over several GPUs (mesh_navigation_amd/sharded.py drives these) ----
     def shard_setup(self, rank: int, world: int) -> int:

@@ -19,6 +19,7 @@
 // This file never computes a plan on the CPU: every entry point fails when no GPU is usable.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <array>
 #include <atomic>
 #include <chrono>
@@ -82,6 +83,7 @@ constexpr int kChunk = 96;  // step launches per graph replay; multiple of 6 (sl
 #include "mnav_clearance.h"  // clearance / border layers: normal ray casts over the obstacle BVH, border test (mnav_clr::)
 #include "mnav_locate.h"     // pose lookup: point LBVH over the vertices, exact nearest vertex, containing face (mnav_loc::)
 #include "mnav_follow.h"     // vector-field follower: one controller tick for a batch of robots over the resident fields (mnav_fol::)
+#include "mnav_graph.h"      // resident layer graph: node passes with change lists, id-list union, combination into a slot (mnav_map::)
 
 // One back-tracking job: the plan's resident vector map and the two ends of the walk.
 struct WalkJob { const float* vecmap; float seed[3]; uint32_t seed_face; float target[3]; uint32_t target_face; };
@@ -217,6 +219,7 @@ struct mnav_ctx {
   mnav_loc::State loc;                                             // pose lookup: vertex index built by the first mnav_locate after an upload
   mnav_fol::State fol;                                             // vector-field follower: buffers and counters of the last mnav_follow_batch
   mnav_chg::Scratch chg;                                           // obstacle / clearance / border layers: change list and counters of the last call
+  mnav_map::State map;                                             // resident layer graph (mnav_map_*): nodes, tables, change lists of the last update
   uint32_t infl_steps = 0, infl_bands = 0; uint64_t infl_evals = 0; float infl_ms = 0.f, infl_ms_wave = 0.f;   // last inflation wave
   DevBuf<TilePlan> d_tplans; uint32_t tplans_cap = 0;
   PinnedBuf<TCtl> h_tctl;
@@ -632,6 +635,7 @@ int mnav_upload_mesh(mnav_ctx* ctx, uint32_t V, uint32_t F, uint32_t E, const fl
   ctx->nbhd = {};                                                    // V-sized spill lists
   ctx->clr = {};                                                     // cached clearance: recast lazily
   ctx->chg = {};                                                     // V-sized change list
+  ctx->map = {};                                                     // the layer graph: its slots are gone
   ctx->loc = {};                                                     // vertex index: rebuilt lazily
   ctx->d_edge_dist.reset();
   drop_graphs(ctx);
@@ -1004,11 +1008,13 @@ int mnav_layer_steepness(mnav_ctx* ctx, uint32_t layer, double threshold)
 
 // InflationLayer::computeLayer (inflation_layer.cpp:96-178 / :577-600): lethals of the input layer -> distances_
 // (multi-source wave) -> riskiness.  Runs the wave on the band engine with plan slot 0's work arrays.
-int mnav_layer_inflation(mnav_ctx* ctx, uint32_t layer, uint32_t input_layer, double inflation_radius, double inscribed_radius,
-                         double inscribed_value, double lethal_value, double cost_scaling_factor, const uint8_t* invalid)
+// `invalid` is a host array, `d_invalid` the same flags already on the device (the layer graph's); either or neither.
+// With `diff` (the layer graph's update path) the slot's costs and flags are not stored plainly: they are diffed against
+// the slot while being written (mnav_map::InflRule), and diff->h_cnt holds the counters of that pass on return.
+static int layer_inflation_impl(mnav_ctx* ctx, uint32_t layer, uint32_t input_layer, double inflation_radius, double inscribed_radius,
+                                double inscribed_value, double lethal_value, double cost_scaling_factor, const uint8_t* invalid,
+                                const uint8_t* d_invalid, const mnav_map::Diff* diff)
 {
-  if (!ctx) return -1;
-  ctx->err.clear();
   if (input_layer >= ctx->layers.size() || !ctx->layers[input_layer].ready) { ctx->err = "input layer is not resident"; return -1; }
   if (layer == input_layer) { ctx->err = "a layer cannot inflate itself"; return -1; }
   if (layer_slot(ctx, layer, true)) return -1;
@@ -1027,12 +1033,12 @@ int mnav_layer_inflation(mnav_ctx* ctx, uint32_t layer, uint32_t input_layer, do
   if (!ctx->d_zero_u8) { HIPCHK(ctx->d_zero_u8.alloc(Vn)); HIPCHK(hipMemsetAsync(ctx->d_zero_u8, 0, Vn, ctx->stream)); }
   if (!ctx->d_infl_keyd) HIPCHK(ctx->d_infl_keyd.alloc(4 * Vn));
   DevBuf<uint8_t> d_inv;
-  if (invalid) { HIPCHK(d_inv.alloc(Vn)); HIPCHK(hipMemcpyAsync(d_inv, invalid, V, hipMemcpyHostToDevice, ctx->stream)); }
+  if (invalid) { HIPCHK(d_inv.alloc(Vn)); HIPCHK(hipMemcpyAsync(d_inv, invalid, V, hipMemcpyHostToDevice, ctx->stream)); d_invalid = d_inv; }
   mnav_ctx::Layer& L = ctx->layers[layer];
   mnav_ctx::Layer& In = ctx->layers[input_layer];
   L.inflation_radius = inflation_radius; L.inscribed_radius = inscribed_radius; L.inscribed_value = inscribed_value; L.lethal_value = lethal_value;
-  hipLaunchKernelGGL(k_infl_mask, dim3(gb), dim3(kBlock), 0, ctx->stream, V, In.lethal, d_inv, ctx->d_infl_mask);
-  HIPCHK(hipMemcpyAsync(L.lethal, In.lethal, V, hipMemcpyDeviceToDevice, ctx->stream));    // lethal_vertices_ = input->lethals() :170,:584
+  hipLaunchKernelGGL(k_infl_mask, dim3(gb), dim3(kBlock), 0, ctx->stream, V, In.lethal, d_invalid, ctx->d_infl_mask);
+  if (!diff) HIPCHK(hipMemcpyAsync(L.lethal, In.lethal, V, hipMemcpyDeviceToDevice, ctx->stream));    // lethal_vertices_ = input->lethals() :170,:584
   if (ensure_slots(ctx, 1, true, true, false)) return -1;
   Slot& s = ctx->slots[0];
   ctx->caller_slot.assign(1, kNone);                                // the wave works in plan slot 0: the last plan's resident outputs are gone
@@ -1099,8 +1105,17 @@ int mnav_layer_inflation(mnav_ctx* ctx, uint32_t layer, uint32_t input_layer, do
   HIPCHK(hipEventRecord(ctx->ev[2], ctx->stream));
   // verification: every vertex must be a fixed point of the replay rule on the converged state (k_cvp_verify)
   if (verify_sweeps(ctx, 1)) return -1;
-  hipLaunchKernelGGL(k_infl_cost, dim3(gb), dim3(kBlock), 0, ctx->stream, V, L.dist, inflation_radius, inscribed_radius, inscribed_value,
-                     lethal_value, cost_scaling_factor, L.cost);
+  if (diff) {
+    using namespace mnav_map;
+    const InflRule rule{ L.dist, In.lethal, inflation_radius, inscribed_radius, inscribed_value, lethal_value, cost_scaling_factor };
+    const uint32_t nblk = blocks(V) ? blocks(V) : 1, fresh = L.ready ? 0u : 1u;
+    hipLaunchKernelGGL(k_node_count<InflRule>, dim3(nblk), dim3(kChgBlock), 0, ctx->stream, V, rule, fresh, L.cost, L.lethal, diff->blk, nblk);
+    hipLaunchKernelGGL(k_node_scan, dim3(1), dim3(kChgBlock), 0, ctx->stream, nblk, diff->blk, diff->cnt);
+    hipLaunchKernelGGL(k_node_emit<InflRule>, dim3(nblk), dim3(kChgBlock), 0, ctx->stream, V, rule, fresh, L.cost, L.lethal, diff->blk, nblk, diff->ids);
+  } else {
+    hipLaunchKernelGGL(k_infl_cost, dim3(gb), dim3(kBlock), 0, ctx->stream, V, L.dist, inflation_radius, inscribed_radius, inscribed_value,
+                       lethal_value, cost_scaling_factor, L.cost);
+  }
   HIPCHK(hipGetLastError());
   // vector_map_ (:277-309): accumulation over the lethal contours, then assignments in pop order (launches until settled)
   L.have_vec = false;
@@ -1130,6 +1145,7 @@ int mnav_layer_inflation(mnav_ctx* ctx, uint32_t layer, uint32_t input_layer, do
   HIPCHK(hipEventRecord(ctx->ev[3], ctx->stream));
   Cnt flags{};
   HIPCHK(hipMemcpyAsync(&flags, s.cnt + 3, sizeof(Cnt), hipMemcpyDeviceToHost, ctx->stream));
+  if (diff) HIPCHK(hipMemcpyAsync(diff->h_cnt, diff->cnt, sizeof(uint32_t) * mnav_map::kCounters, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   ctx->infl_steps = (uint32_t)(last.it < 0 ? 0 : last.it); ctx->infl_bands = last.bands; ctx->infl_evals = last.evals;
   ctx->infl_ms = ev_ms(ctx->ev[1], ctx->ev[3]); ctx->infl_ms_wave = ev_ms(ctx->ev[1], ctx->ev[2]);
@@ -1138,6 +1154,15 @@ int mnav_layer_inflation(mnav_ctx* ctx, uint32_t layer, uint32_t input_layer, do
   if (flags.changed) { ctx->err = "inflation wave: the converged state is not a fixed point of the replay rule"; return -1; }
   L.ready = true;
   return 0;
+}
+
+int mnav_layer_inflation(mnav_ctx* ctx, uint32_t layer, uint32_t input_layer, double inflation_radius, double inscribed_radius,
+                         double inscribed_value, double lethal_value, double cost_scaling_factor, const uint8_t* invalid)
+{
+  if (!ctx) return -1;
+  ctx->err.clear();
+  return layer_inflation_impl(ctx, layer, input_layer, inflation_radius, inscribed_radius, inscribed_value, lethal_value, cost_scaling_factor,
+                              invalid, nullptr, nullptr);
 }
 
 int mnav_layer_download(mnav_ctx* ctx, uint32_t layer, float* costs_out, uint8_t* lethal_out, float* distances_out)
@@ -1648,6 +1673,7 @@ uint32_t mnav_plan_cvp_batch(mnav_ctx* ctx, uint32_t n, const float* seed_pos, c
 #include "mnav_clearance_capi.h"  // mnav_layer_clearance, mnav_layer_border, mnav_clearance_download, mnav_clearance_stats
 #include "mnav_locate_capi.h"     // mnav_locate, mnav_locate_stats, mnav_plan_dijkstra_batch_at, mnav_plan_cvp_batch_at
 #include "mnav_follow_capi.h"     // mnav_follow_batch, mnav_follow_stats
+#include "mnav_graph_capi.h"      // mnav_map_configure / _compute / _layer_changed / _update_layer / _obstacle / _stats
 
 void mnav_cancel(mnav_ctx* ctx)
 {

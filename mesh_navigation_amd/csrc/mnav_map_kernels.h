@@ -291,13 +291,9 @@ __global__ __launch_bounds__(kBlock) void k_infl_assign(const Plan* __restrict__
 
 // riskiness from the distances: fading() :315-339; vertices the wave never reached keep the default 0
 // (inflation_layer.h:74-77).  The exponential runs in float64 and is rounded to float32 (:326).
-__global__ __launch_bounds__(kBlock) void k_infl_cost(uint32_t V, const float* __restrict__ dist, double inflation_radius,
-                                                      double inscribed_radius, double inscribed_value, double lethal_value,
-                                                      double cost_scaling_factor, float* __restrict__ cost)
+__device__ __forceinline__ float infl_fading(float d, double inflation_radius, double inscribed_radius, double inscribed_value,
+                                             double lethal_value, double cost_scaling_factor)
 {
-  const uint32_t v = blockIdx.x * kBlock + threadIdx.x;
-  if (v >= V) return;
-  const float d = dist[v];
   float c;
   if (!(d < inf_f())) c = 0.0f;
   else if ((double)d > inflation_radius) c = 0.0f;                                        // :317-320
@@ -307,7 +303,16 @@ __global__ __launch_bounds__(kBlock) void k_infl_cost(uint32_t V, const float* _
   }
   else if (d > 0) c = (float)inscribed_value;                                             // :332-335
   else c = (float)lethal_value;                                                           // :338
-  cost[v] = c;
+  return c;
+}
+
+__global__ __launch_bounds__(kBlock) void k_infl_cost(uint32_t V, const float* __restrict__ dist, double inflation_radius,
+                                                      double inscribed_radius, double inscribed_value, double lethal_value,
+                                                      double cost_scaling_factor, float* __restrict__ cost)
+{
+  const uint32_t v = blockIdx.x * kBlock + threadIdx.x;
+  if (v >= V) return;
+  cost[v] = infl_fading(dist[v], inflation_radius, inscribed_radius, inscribed_value, lethal_value, cost_scaling_factor);
 }
 
 __global__ __launch_bounds__(kBlock) void k_combine_resident(uint32_t V, int mode, uint32_t n_layers, const float* const* __restrict__ layers,

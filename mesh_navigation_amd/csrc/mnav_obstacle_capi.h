@@ -52,6 +52,17 @@ static int obstacle_build_bvh(mnav_ctx* ctx)
   return 0;
 }
 
+// the argument errors of mnav_layer_obstacle (and mnav_map_obstacle): refused before anything is touched
+static int obstacle_check_args(mnav_ctx* ctx, uint32_t n_points, const void* points, uint32_t point_step, const float* down_axis)
+{
+  if (point_step < 12) { ctx->err = "point_step must be at least 12 bytes (x, y, z floats at offsets 0, 4, 8)"; return -1; }
+  if (n_points && !points) { ctx->err = "null point buffer with n_points > 0"; return -1; }
+  if (!down_axis) { ctx->err = "null down_axis"; return -1; }
+  if (!std::isfinite(down_axis[0]) || !std::isfinite(down_axis[1]) || !std::isfinite(down_axis[2]) ||
+      (down_axis[0] == 0.f && down_axis[1] == 0.f && down_axis[2] == 0.f)) { ctx->err = "down_axis must be finite and non-zero"; return -1; }
+  return 0;
+}
+
 int mnav_layer_obstacle(mnav_ctx* ctx, uint32_t layer, uint32_t n_points, const void* points, uint32_t point_step,
                         const float* sensor_to_map, const float* down_axis, double robot_height, double max_obstacle_dist,
                         uint32_t* changed_out, uint32_t* n_changed, uint32_t* n_lethal)
@@ -60,11 +71,7 @@ int mnav_layer_obstacle(mnav_ctx* ctx, uint32_t layer, uint32_t n_points, const 
   using namespace mnav_chg;
   if (!ctx) return -1;
   ctx->err.clear();
-  if (point_step < 12) { ctx->err = "point_step must be at least 12 bytes (x, y, z floats at offsets 0, 4, 8)"; return -1; }
-  if (n_points && !points) { ctx->err = "null point buffer with n_points > 0"; return -1; }
-  if (!down_axis) { ctx->err = "null down_axis"; return -1; }
-  if (!std::isfinite(down_axis[0]) || !std::isfinite(down_axis[1]) || !std::isfinite(down_axis[2]) ||
-      (down_axis[0] == 0.f && down_axis[1] == 0.f && down_axis[2] == 0.f)) { ctx->err = "down_axis must be finite and non-zero"; return -1; }
+  if (obstacle_check_args(ctx, n_points, points, point_step, down_axis)) return -1;
   if (layer_slot(ctx, layer, false)) return -1;
   mnav_ctx::Layer& L = ctx->layers[layer];
   Bvh& B = ctx->obs;
