@@ -473,6 +473,60 @@ int mnav_follow_batch(mnav_ctx* ctx, uint32_t n, const float* pos, const float* 
 int mnav_follow_stats(const mnav_ctx* ctx, uint32_t* stayed, uint32_t* neighbour, uint32_t* global, uint32_t* lost,
                       uint32_t* no_field, uint32_t* built_index, float* ms_kernels, float* ms_total);
 
+/* -- device rollouts: many controller ticks per call -------------------------------------------------
+ * Move Base Flex's controller loop (computeVelocityCommands, then isGoalReached, at the controller frequency until the robot
+ * arrives) for n robots over `ticks` ticks, the robots' state resident and the tick loop on the device: the inputs of
+ * mnav_follow_batch go up once, only the final state comes down (plus an optional strided trace of positions).  For fleets,
+ * rollouts and arrival estimates over fields that cannot leave the device; a controller plugin that serves one robot keeps
+ * ticking once per call through mnav_follow_batch.  Final state of a robot: */
+enum { MNAV_ROLLOUT_RUNNING = 0, MNAV_ROLLOUT_REACHED = 1, MNAV_ROLLOUT_OUT_OF_MAP = 2, MNAV_ROLLOUT_NO_FIELD = 3 };
+typedef struct mnav_rollout_config {
+  double   dt;               /* seconds per tick */
+  double   dist_tolerance;   /* isGoalReached (mesh_controller.cpp:172-177); unused without goals */
+  double   angle_tolerance;
+  uint32_t ticks;            /* ticks of this call, 1 .. 100000 */
+  uint32_t trace_stride;     /* 0: no trace; else a position row after every trace_stride-th tick */
+} mnav_rollout_config;
+/* Every robot starts RUNNING with ticks = 0, travel = cost_integral = 0 and min_goal_dist = +inf.  One tick of a RUNNING
+ * robot, in this order and these types (float32 / double as written, no contraction):
+ *   1  R = one mnav_follow_batch tick of (pos, dir, up, face), bit for bit; ticks += 1
+ *   2  R is MNAV_FOLLOW_OUT_OF_MAP: status OUT_OF_MAP, face = MNAV_NONE, pos unchanged, the robot stops
+ *   3  pos = R.pos, face = R.face
+ *   4  with goals: gd = |goal_pos - pos|, ang = acosf(goal_dir . dir) (the host libm's bits); min_goal_dist = min(min_goal_dist,
+ *      gd); gd <= (float)dist_tolerance && ang <= (float)angle_tolerance: status REACHED, the robot stops (a NaN angle, from
+ *      a dot product rounded above 1, is not reached, as in the reference)
+ *   5  R is MNAV_FOLLOW_NO_FIELD: status NO_FIELD, the robot stops
+ *   6  the unicycle: step = R.lin * dt (double); travel += step; cost_integral += (double)R.cost * dt;
+ *      pos.c = (float)((double)pos.c + (double)dir.c * step); th = (float)(R.ang * dt); dir = the float Rodrigues rotation
+ *      of dir about up by th (the host libm's cosf / sinf bits), normalised
+ * A robot that is not RUNNING is left untouched by later ticks.  seed_faces may be NULL; goal_pos / goal_dir (n * 3 each) are
+ * both given or both NULL (no goal test).  Outputs (any may be NULL): the final status, ticks run, position, heading and
+ * face per robot, the distance travelled and the integral of the cost over time (both sums of THIS call), the smallest
+ * goal distance seen, and trace_out: n * (ticks / trace_stride) * 3 floats, robot-major, row k = the position after tick
+ * (k + 1) * trace_stride (a stopped robot repeats its last position).  n = 0 does nothing.
+ * Resuming: pos_out, dir_out and face_out of the RUNNING robots fed back as the inputs of a second call continue the
+ * rollout exactly: a + b ticks in one call or in two give the same status, position, heading and face bits.
+ * mnav_cancel is honoured between blocks of at most 256 ticks (one stream synchronise and one look at the flag per block;
+ * the flag is cleared at entry, as the plan calls do): the call then returns 1 and the outputs hold the state reached
+ * (ticks_out tells how far; trace rows beyond it are unspecified).
+ * Returns 0, 1 when cancelled, or -1 with mnav_last_error set and NOTHING touched: every refusal of mnav_follow_batch, a dt
+ * that is not finite and positive, ticks outside 1 .. 100000, a trace_stride without trace_out or larger than ticks, only one
+ * of goal_pos / goal_dir, a NaN tolerance, |max_ang_velocity| * max(1, |ang_vel_factor|) * dt >= 100 (the restated sinf /
+ * cosf are pinned for |x| < 120 only).  The call changes no plan output, no layer and no statistic of another entry point;
+ * it builds the lookup index of mnav_locate at its start if none exists yet (mnav_locate_stats then reports built = 1).
+ * DESIGN.md section 3.10. */
+int mnav_follow_rollout(mnav_ctx* ctx, uint32_t n, const float* pos, const float* dir, const float* up, const uint32_t* face_in,
+                        const uint32_t* slots, const uint32_t* seed_faces, const float* goal_pos, const float* goal_dir,
+                        const mnav_follow_config* config, const mnav_rollout_config* rollout, int32_t* status_out,
+                        uint32_t* ticks_out, float* pos_out, float* dir_out, uint32_t* face_out, double* travel_out,
+                        double* cost_integral_out, float* min_goal_dist_out, float* trace_out);
+/* The last mnav_follow_rollout: status_counts[4] = robots per final status (indexed by MNAV_ROLLOUT_*), the robot-ticks run,
+ * how they were resolved summed over all ticks (stayed on the face, neighbour search, global search; a tick that lost the
+ * map is in none), built_index = 1 if the call built the lookup index, device milliseconds of its kernels and host
+ * milliseconds of the whole call.  Any pointer may be NULL. */
+int mnav_rollout_stats(const mnav_ctx* ctx, uint32_t* status_counts, uint64_t* robot_ticks, uint64_t* stayed, uint64_t* neighbour,
+                       uint64_t* global, uint32_t* built_index, float* ms_kernels, float* ms_total);
+
 /* -- one plan over several GPUs (BASELINE config 4) ---------------------------------------------
  * The reference's loop (dijkstra_mesh_planner.cpp:287-348) on a mesh that is range-partitioned over `world`
  * processes, one per GPU: the LDS tiles are in Morton order and process `rank` owns a contiguous range of them.

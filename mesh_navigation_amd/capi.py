@@ -32,7 +32,7 @@ SYMBOLS = [
     "mnav_layer_height_diff", "mnav_layer_roughness", "mnav_layer_ridge", "mnav_neighbourhood_stats",
     "mnav_layer_border", "mnav_layer_clearance", "mnav_clearance_download", "mnav_clearance_stats",
     "mnav_locate", "mnav_locate_stats", "mnav_plan_dijkstra_batch_at", "mnav_plan_cvp_batch_at",
-    "mnav_follow_batch", "mnav_follow_stats",
+    "mnav_follow_batch", "mnav_follow_stats", "mnav_follow_rollout", "mnav_rollout_stats",
     "mnav_map_configure", "mnav_map_compute", "mnav_map_layer_changed", "mnav_map_update_layer", "mnav_map_obstacle", "mnav_map_stats",
     "mnav_set_option", "mnav_get_option", "mnav_shard_set_goal_tie", "mnav_last_engine",
 ]
@@ -84,6 +84,20 @@ class FollowConfig(C.Structure):
 FOLLOW_OK, FOLLOW_OUT_OF_MAP, FOLLOW_NO_FIELD = 0, 1, 2
 
 
+class RolloutConfig(C.Structure):
+    """mnav_rollout_config (include/mnav.h): the tick length, isGoalReached's tolerances, the ticks of the call and the
+    stride of the optional trace."""
+    _fields_ = [("dt", C.c_double), ("dist_tolerance", C.c_double), ("angle_tolerance", C.c_double), ("ticks", C.c_uint32),
+                ("trace_stride", C.c_uint32)]
+    DEFAULTS = dict(dt=0.1, dist_tolerance=0.2, angle_tolerance=0.8, ticks=1, trace_stride=0)
+
+    def __init__(self, **kw):
+        super().__init__(**{**self.DEFAULTS, **kw})
+
+
+ROLLOUT_RUNNING, ROLLOUT_REACHED, ROLLOUT_OUT_OF_MAP, ROLLOUT_NO_FIELD = 0, 1, 2, 3
+
+
 class MapNode(C.Structure):
     """mnav_map_node (include/mnav.h): one node of the resident layer graph"""
     _fields_ = [("layer", C.c_uint32), ("kind", C.c_uint32), ("n_inputs", C.c_uint32), ("inputs", C.c_uint32 * 8),
@@ -105,6 +119,22 @@ class FollowOut:
     cost: np.ndarray | None
     cmd: np.ndarray | None        # (n, 2) float64: linear x, angular z
     how: np.ndarray | None
+
+
+@dataclass
+class RolloutOut:
+    """One mnav_follow_rollout call: an array per output, one row per robot (None where the output was not asked for).
+    `cancelled`: mnav_cancel ended the call early (`ticks` tells how far each robot came)."""
+    status: np.ndarray | None
+    ticks: np.ndarray | None
+    pos: np.ndarray | None
+    dir: np.ndarray | None
+    face: np.ndarray | None
+    travel: np.ndarray | None
+    cost_integral: np.ndarray | None
+    min_goal_dist: np.ndarray | None
+    trace: np.ndarray | None      # (n, ticks // trace_stride, 3) float32, or None without a trace
+    cancelled: bool = False
 
 
 _lib = None
@@ -157,6 +187,10 @@ def load(path: str | None = None):
     L.mnav_follow_batch.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, C.POINTER(FollowConfig), vp, vp, vp, vp, vp, vp, vp, vp]
     L.mnav_follow_stats.restype = C.c_int
     L.mnav_follow_stats.argtypes = [vp] + [C.POINTER(u32)] * 6 + [C.POINTER(C.c_float)] * 2
+    L.mnav_follow_rollout.restype = C.c_int
+    L.mnav_follow_rollout.argtypes = [vp, u32] + [vp] * 8 + [C.POINTER(FollowConfig), C.POINTER(RolloutConfig)] + [vp] * 9
+    L.mnav_rollout_stats.restype = C.c_int
+    L.mnav_rollout_stats.argtypes = [vp, C.POINTER(u32 * 4)] + [C.POINTER(C.c_uint64)] * 4 + [C.POINTER(u32)] + [C.POINTER(C.c_float)] * 2
     L.mnav_map_configure.restype = C.c_int
     L.mnav_map_configure.argtypes = [vp, u32, C.POINTER(MapNode), u32, f64, vp]
     L.mnav_map_compute.restype = C.c_int
@@ -907,6 +941,48 @@ class MnavContext:
         self._L.mnav_follow_stats(self._h, *[C.byref(x) for x in v], C.byref(mk), C.byref(mt))
         names = ("stayed", "neighbour", "global", "lost", "no_field", "built_index")
         return dict(**{k: x.value for k, x in zip(names, v)}, ms_kernels=mk.value, ms_total=mt.value)
+
+    def rollout(self, pos, direction, up, face_in, slots, seed_faces=None, goal_pos=None, goal_dir=None, config: FollowConfig | None = None,
+                rollout: RolloutConfig | None = None, outputs=None) -> RolloutOut:
+        """`rollout.ticks` controller ticks of n robots over the resident vector maps of the last plan call, the robots'
+        state resident and the loop on the device (mnav_follow_rollout, include/mnav.h).  The per-robot arrays are those
+        of follow(); goal_pos / goal_dir: (n, 3) each, both or neither.  `outputs`: the names of the RolloutOut fields to
+        fetch (default: all; the trace whenever rollout.trace_stride is set)."""
+        p, d, u = (_f32(a).reshape(-1, 3) for a in (pos, direction, up))
+        fi, sl = _u32(face_in).reshape(-1), _u32(slots).reshape(-1)
+        n = int(p.shape[0])
+        if not (d.shape[0] == u.shape[0] == fi.shape[0] == sl.shape[0] == n):
+            raise ValueError("rollout: the per-robot arrays differ in length")
+        sf = None if seed_faces is None else _u32(seed_faces).reshape(-1)
+        if sf is not None and sf.shape[0] != n:
+            raise ValueError("rollout: seed_faces needs one entry per robot")
+        gp = None if goal_pos is None else _f32(goal_pos).reshape(-1, 3)
+        gd = None if goal_dir is None else _f32(goal_dir).reshape(-1, 3)
+        if any(g is not None and g.shape[0] != n for g in (gp, gd)):
+            raise ValueError("rollout: goal_pos / goal_dir need one row per robot")
+        cfg = config if config is not None else FollowConfig()
+        ro = rollout if rollout is not None else RolloutConfig()
+        rows = int(ro.ticks) // int(ro.trace_stride) if ro.trace_stride else 0
+        shapes = dict(status=((n,), np.int32), ticks=((n,), np.uint32), pos=((n, 3), np.float32), dir=((n, 3), np.float32), face=((n,), np.uint32),
+                      travel=((n,), np.float64), cost_integral=((n,), np.float64), min_goal_dist=((n,), np.float32))
+        want = set(shapes) if outputs is None else set(outputs)
+        o = {k: (np.zeros(*shapes[k]) if k in want else None) for k in shapes}
+        o["trace"] = np.zeros((n, rows, 3), np.float32) if ro.trace_stride else None
+        rc = self._L.mnav_follow_rollout(self._h, n, _p(p), _p(d), _p(u), _p(fi), _p(sl), _p(sf), _p(gp), _p(gd), C.byref(cfg), C.byref(ro),
+                                         _p(o["status"]), _p(o["ticks"]), _p(o["pos"]), _p(o["dir"]), _p(o["face"]), _p(o["travel"]),
+                                         _p(o["cost_integral"]), _p(o["min_goal_dist"]), _p(o["trace"]))
+        if rc < 0:
+            raise RuntimeError(f"mnav_follow_rollout failed: {self._err()}")
+        return RolloutOut(**o, cancelled=rc == 1)
+
+    def rollout_stats(self) -> dict:
+        sc = (C.c_uint32 * 4)()
+        v = [C.c_uint64() for _ in range(4)]
+        b, mk, mt = C.c_uint32(), C.c_float(), C.c_float()
+        self._L.mnav_rollout_stats(self._h, C.byref(sc), *[C.byref(x) for x in v], C.byref(b), C.byref(mk), C.byref(mt))
+        names = ("robot_ticks", "stayed", "neighbour", "global")
+        return dict(running=sc[0], reached=sc[1], out_of_map=sc[2], no_field=sc[3], **{k: x.value for k, x in zip(names, v)},
+                    built_index=b.value, ms_kernels=mk.value, ms_total=mt.value)
 
     def plan_dijkstra_batch_at(self, goal_pos, start_pos, goal_dist_offset: float = 0.3, cost_limit: float = 1.0,
                                want_fields: bool = False, path_cap: int | None = None, want_stats: bool = True):

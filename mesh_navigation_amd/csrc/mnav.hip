@@ -83,6 +83,7 @@ constexpr int kChunk = 96;  // step launches per graph replay; multiple of 6 (sl
 #include "mnav_clearance.h"  // clearance / border layers: normal ray casts over the obstacle BVH, border test (mnav_clr::)
 #include "mnav_locate.h"     // pose lookup: point LBVH over the vertices, exact nearest vertex, containing face (mnav_loc::)
 #include "mnav_follow.h"     // vector-field follower: one controller tick for a batch of robots over the resident fields (mnav_fol::)
+#include "mnav_rollout.h"    // device rollouts: many controller ticks per call over resident robot state (mnav_rol::)
 #include "mnav_graph.h"      // resident layer graph: node passes with change lists, id-list union, combination into a slot (mnav_map::)
 
 // One back-tracking job: the plan's resident vector map and the two ends of the walk.
@@ -218,6 +219,7 @@ struct mnav_ctx {
   mnav_clr::State clr;                                             // clearance / border layers: cached clearance (first clearance call after an upload)
   mnav_loc::State loc;                                             // pose lookup: vertex index built by the first mnav_locate after an upload
   mnav_fol::State fol;                                             // vector-field follower: buffers and counters of the last mnav_follow_batch
+  mnav_rol::Dev rol;                                               // device rollout: resident robot state and statistics of the last mnav_follow_rollout
   mnav_chg::Scratch chg;                                           // obstacle / clearance / border layers: change list and counters of the last call
   mnav_map::State map;                                             // resident layer graph (mnav_map_*): nodes, tables, change lists of the last update
   uint32_t infl_steps = 0, infl_bands = 0; uint64_t infl_evals = 0; float infl_ms = 0.f, infl_ms_wave = 0.f;   // last inflation wave
@@ -1673,6 +1675,7 @@ uint32_t mnav_plan_cvp_batch(mnav_ctx* ctx, uint32_t n, const float* seed_pos, c
 #include "mnav_clearance_capi.h"  // mnav_layer_clearance, mnav_layer_border, mnav_clearance_download, mnav_clearance_stats
 #include "mnav_locate_capi.h"     // mnav_locate, mnav_locate_stats, mnav_plan_dijkstra_batch_at, mnav_plan_cvp_batch_at
 #include "mnav_follow_capi.h"     // mnav_follow_batch, mnav_follow_stats
+#include "mnav_rollout_capi.h"    // mnav_follow_rollout, mnav_rollout_stats
 #include "mnav_graph_capi.h"      // mnav_map_configure / _compute / _layer_changed / _update_layer / _obstacle / _stats
 
 void mnav_cancel(mnav_ctx* ctx)

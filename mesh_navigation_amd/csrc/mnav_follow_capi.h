@@ -6,6 +6,34 @@
 static_assert(sizeof(mnav_follow_config) == sizeof(mnav_fol::Config) && offsetof(mnav_follow_config, max_search_distance) == offsetof(mnav_fol::Config, max_search_distance),
               "mnav_follow_config and mnav_fol::Config are one layout");
 
+// The argument checks of a follower call (mnav_follow_batch, mnav_follow_rollout), all on the host: -1 with ctx->err set, or
+// 0 and maps[s] = the resident vector map of every slot a robot uses (null for the others).
+static int follow_check(mnav_ctx* ctx, uint32_t n, const float* pos, const float* dir, const float* up, const uint32_t* face_in, const uint32_t* slots,
+                        const uint32_t* seed_faces, const mnav_follow_config* config, std::vector<const float*>& maps)
+{
+  using mnav_fol::kNone;
+  if (!pos || !dir || !up || !face_in || !slots || !config) { ctx->err = "follow: null argument"; return -1; }
+  if (check_ready(ctx)) return -1;
+  if (n > 0x7FFFFFFFu) { ctx->err = "follow: too many robots in one call"; return -1; }
+  if (!(config->max_search_radius > 0.0) || !std::isfinite(config->max_search_radius)) { ctx->err = "follow: max_search_radius must be positive and finite"; return -1; }
+  if (!(config->max_search_distance > 0.0) || !std::isfinite(config->max_search_distance)) { ctx->err = "follow: max_search_distance must be positive and finite"; return -1; }
+  const size_t n_slots = ctx->caller_slot.size();
+  maps.assign(n_slots ? n_slots : 1, nullptr);
+  std::vector<uint8_t> used(n_slots ? n_slots : 1, 0);
+  for (uint32_t i = 0; i < n; ++i) {
+    if (slots[i] >= n_slots) { ctx->err = "follow: slot out of range (not a plan of the last call)"; return -1; }
+    if (face_in[i] != kNone && face_in[i] >= ctx->F) { ctx->err = "follow: face id out of range"; return -1; }
+    if (seed_faces && seed_faces[i] != kNone && seed_faces[i] >= ctx->F) { ctx->err = "follow: seed face id out of range"; return -1; }
+    used[slots[i]] = 1;
+  }
+  for (size_t s = 0; s < n_slots; ++s) {
+    if (!used[s]) continue;
+    maps[s] = static_cast<const float*>(mnav_device_output(ctx, (uint32_t)s, 4));
+    if (!maps[s]) { ctx->err = "follow: vector map of slot " + std::to_string(s) + " not resident (mnav_set_resident_outputs, or pass vecmap_out to the plan call)"; return -1; }
+  }
+  return 0;
+}
+
 static int follow_reserve(mnav_ctx* ctx, size_t n, size_t n_slots)
 {
   mnav_fol::State& S = ctx->fol;
@@ -39,25 +67,9 @@ int mnav_follow_batch(mnav_ctx* ctx, uint32_t n, const float* pos, const float* 
   if (!n) return 0;
   const auto t0 = std::chrono::steady_clock::now();
   // every refusal comes before the first device call: a refused call touches nothing
-  if (!pos || !dir || !up || !face_in || !slots || !config) { ctx->err = "follow: null argument"; return -1; }
-  if (check_ready(ctx)) return -1;
-  if (n > 0x7FFFFFFFu) { ctx->err = "follow: too many robots in one call"; return -1; }
-  if (!(config->max_search_radius > 0.0) || !std::isfinite(config->max_search_radius)) { ctx->err = "follow: max_search_radius must be positive and finite"; return -1; }
-  if (!(config->max_search_distance > 0.0) || !std::isfinite(config->max_search_distance)) { ctx->err = "follow: max_search_distance must be positive and finite"; return -1; }
+  std::vector<const float*> maps;
+  if (follow_check(ctx, n, pos, dir, up, face_in, slots, seed_faces, config, maps)) return -1;
   const size_t n_slots = ctx->caller_slot.size();
-  std::vector<const float*> maps(n_slots ? n_slots : 1, nullptr);
-  std::vector<uint8_t> used(n_slots ? n_slots : 1, 0);
-  for (uint32_t i = 0; i < n; ++i) {
-    if (slots[i] >= n_slots) { ctx->err = "follow: slot out of range (not a plan of the last call)"; return -1; }
-    if (face_in[i] != kNone && face_in[i] >= ctx->F) { ctx->err = "follow: face id out of range"; return -1; }
-    if (seed_faces && seed_faces[i] != kNone && seed_faces[i] >= ctx->F) { ctx->err = "follow: seed face id out of range"; return -1; }
-    used[slots[i]] = 1;
-  }
-  for (size_t s = 0; s < n_slots; ++s) {
-    if (!used[s]) continue;
-    maps[s] = static_cast<const float*>(mnav_device_output(ctx, (uint32_t)s, 4));
-    if (!maps[s]) { ctx->err = "follow: vector map of slot " + std::to_string(s) + " not resident (mnav_set_resident_outputs, or pass vecmap_out to the plan call)"; return -1; }
-  }
   if (hipSetDevice(ctx->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return -1; }
   if (upload_walk_mesh(ctx)) return -1;
   if (follow_reserve(ctx, n, n_slots)) return -1;
