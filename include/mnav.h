@@ -380,6 +380,35 @@ int mnav_map_obstacle(mnav_ctx* ctx, uint32_t layer, uint32_t n_points, const vo
 int mnav_map_stats(const mnav_ctx* ctx, uint32_t* waves, uint32_t* recombined, uint32_t* default_changed, uint32_t* edges_reweighted,
                    float* ms_total, float* ms_wave);
 
+/* -- replan on the resident potentials ---------------------------------------------------------
+ * Brings the n plans of the last Dijkstra call (mnav_plan_dijkstra, _batch, _batch_at) up to date with the resident costs and
+ * with new robot vertices (targets: n ids in the caller's order, NULL = unchanged).  Seeds and cost_limit are those of that
+ * call.  Outputs, codes and the path order are those of mnav_plan_dijkstra_batch, bit for bit what a fresh plan on the
+ * resident map returns; the finalize pass always runs, so dist, pred and (with mnav_set_resident_outputs) the vector maps are
+ * resident afterwards and mnav_follow_batch, mnav_follow_rollout, mnav_download_output and a further replan work on them.
+ * The context logs which vertices mnav_update_costs, mnav_update_edge_weights (both endpoints) and the mnav_map_* update
+ * calls (the default layer's change list) touched since the last Dijkstra or replan call.  A plan keeps every value strictly
+ * below its rewind level L = min(old cut, smallest old value over the closed one-ring of the logged vertices); the rest goes
+ * back to +inf and the tile rounds continue from the kept part.  mnav_cancel is honoured between
+ * chunks of rounds (the flag is cleared at entry); a cancelled call leaves nothing to replan.
+ * Refused with MNAV_INTERNAL_ERROR, mnav_last_error set and outputs, log and replan state untouched: no mesh or costs, a NaN
+ * offset, no Dijkstra call before, n different from that call's. */
+uint32_t mnav_replan_dijkstra_batch(mnav_ctx* ctx, uint32_t n, const uint32_t* targets, double goal_dist_offset, uint32_t* codes_out,
+                                    float* dist_out, uint32_t* pred_out, uint32_t* path_out, uint32_t path_cap, uint32_t* path_len);
+/* The n a replan call must pass: the plans of the last Dijkstra call (0: none recorded, a replan is refused). */
+uint32_t mnav_replan_plans(const mnav_ctx* ctx);
+/* The last mnav_replan_dijkstra_batch.  reason: 0 the fields were repaired; otherwise the call planned afresh from the recorded
+ * seeds (always a correct answer): 1 no usable resident field (the last call ran the band steps, was sharded, a CVP call,
+ * failed or was cancelled, or a paths-only tile-batch call), 2 the change log ran over (option replan_log_cap, default V
+ * entries) or a writer replaced whole arrays (mnav_upload_costs, mnav_compute_edge_weights, mnav_combine_*, mnav_map_compute),
+ * 3 a plan of the last call never reached the device or a new target is out of range or equals its seed, 4 the option
+ * replan_fresh_below = f > 0 (default 0.25, 0: never) and min over the plans with a finite old cut of L / cut < f.  log_len: logged ids at entry.
+ * For reason 0: levels_out (n floats, caller's order) the rewind levels; owned vertices kept and rewound from a finite value,
+ * tiles woken, summed over the plans; round launches; device milliseconds of the level kernels, the rewind, the rounds and the
+ * finalize pass.  Zero otherwise (levels_out untouched).  Any pointer may be NULL. */
+int mnav_replan_stats(const mnav_ctx* ctx, uint32_t* reason, uint32_t* log_len, float* levels_out, uint64_t* kept, uint64_t* rewound,
+                      uint32_t* tiles_woken, uint32_t* rounds, float* ms_level, float* ms_rewind, float* ms_rounds, float* ms_finalize);
+
 /* -- pose lookup on the device ---------------------------------------------------------------------
  * MeshMap::getNearestVertexHandle (mesh_map.cpp:1161-1174) and MeshMap::getContainingFace / searchContainingFace
  * (:1120-1159) for n positions (pos: n*3 floats) in one call; only the positions go up and the results come down.

@@ -34,6 +34,7 @@ SYMBOLS = [
     "mnav_locate", "mnav_locate_stats", "mnav_plan_dijkstra_batch_at", "mnav_plan_cvp_batch_at",
     "mnav_follow_batch", "mnav_follow_stats", "mnav_follow_rollout", "mnav_rollout_stats",
     "mnav_map_configure", "mnav_map_compute", "mnav_map_layer_changed", "mnav_map_update_layer", "mnav_map_obstacle", "mnav_map_stats",
+    "mnav_replan_dijkstra_batch", "mnav_replan_plans", "mnav_replan_stats",
     "mnav_set_option", "mnav_get_option", "mnav_shard_set_goal_tie", "mnav_last_engine",
 ]
 
@@ -203,6 +204,12 @@ def load(path: str | None = None):
     L.mnav_map_obstacle.argtypes = [vp, u32, u32, vp, u32, vp, vp, f64, f64, vp, C.POINTER(u32)]
     L.mnav_map_stats.restype = C.c_int
     L.mnav_map_stats.argtypes = [vp] + [C.POINTER(u32)] * 4 + [C.POINTER(C.c_float)] * 2
+    L.mnav_replan_dijkstra_batch.restype = u32
+    L.mnav_replan_dijkstra_batch.argtypes = [vp, u32, vp, f64, vp, vp, vp, vp, u32, vp]
+    L.mnav_replan_plans.restype = u32
+    L.mnav_replan_plans.argtypes = [vp]
+    L.mnav_replan_stats.restype = C.c_int
+    L.mnav_replan_stats.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), vp] + [C.POINTER(C.c_uint64)] * 2 + [C.POINTER(u32)] * 2 + [C.POINTER(C.c_float)] * 4
     L.mnav_cancel.argtypes = [vp]
     L.mnav_get_stats.restype = C.c_int
     L.mnav_get_stats.argtypes = [vp, C.POINTER(Stats)]
@@ -875,6 +882,42 @@ class MnavContext:
         lease.append(weakref.ref(rows))
         return dict(rc=rc, codes=codes, dist=dist, pred=pred, paths=rows, path_len=lens,
                     stats=self.stats() if want_stats else self.timing())
+
+    def replan_dijkstra(self, targets=None, goal_dist_offset: float = 0.3, want_dist: bool = False, want_pred: bool = False,
+                        path_cap: int | None = None, want_stats: bool = True):
+        """Brings the plans of the last Dijkstra call up to date with the resident costs and, when `targets` is given, with new
+        robot vertices (mnav_replan_dijkstra_batch, include/mnav.h): the result of plan_dijkstra_batch on the resident map, from
+        the part of the resident fields the changes cannot have touched.  Adds `replan` = replan_stats() to the dict (want_stats
+        False: None, and `stats` is timing() as in plan_dijkstra_batch -- the two calls then do the same work around the C call)."""
+        n = int(self._L.mnav_replan_plans(self._h)) if targets is None else int(_u32(targets).shape[0])
+        tg = None if targets is None else _u32(targets)
+        V = self.V
+        cap = int(path_cap if path_cap is not None else V)
+        codes = np.empty(n, np.uint32)
+        dist = np.empty((n, V), np.float32) if want_dist else None
+        pred = np.empty((n, V), np.uint32) if want_pred else None
+        paths, lease = self._lease_paths(n, cap)
+        lens = np.zeros(n, np.uint32)
+        rc = self._L.mnav_replan_dijkstra_batch(self._h, n, _p(tg), float(goal_dist_offset), _p(codes), _p(dist), _p(pred), _p(paths), cap, _p(lens))
+        if rc == INTERNAL_ERROR:
+            raise RuntimeError(f"mnav_replan_dijkstra_batch internal error: {self._err()}")
+        rows = _PathRows(paths, lens, cap)
+        lease.append(weakref.ref(rows))
+        return dict(rc=rc, codes=codes, dist=dist, pred=pred, paths=rows, path_len=lens, stats=self.stats() if want_stats else self.timing(),
+                    replan=self.replan_stats(n) if want_stats else None)
+
+    def replan_stats(self, n: int = 0) -> dict:
+        """The last replan_dijkstra call (mnav_replan_stats); n: its plan count, for the rewind levels (reason 0 only)."""
+        r, ll, tw, rd = (C.c_uint32() for _ in range(4))
+        k, w = C.c_uint64(), C.c_uint64()
+        ms = [C.c_float() for _ in range(4)]
+        self._L.mnav_replan_stats(self._h, C.byref(r), C.byref(ll), None, C.byref(k), C.byref(w), C.byref(tw), C.byref(rd), *[C.byref(x) for x in ms])
+        lv = None
+        if r.value == 0 and n:
+            lv = np.zeros(n, np.float32)
+            self._L.mnav_replan_stats(self._h, None, None, _p(lv), *([None] * 8))
+        return dict(reason=r.value, log_len=ll.value, levels=lv, kept=k.value, rewound=w.value, tiles_woken=tw.value, rounds=rd.value,
+                    ms_level=ms[0].value, ms_rewind=ms[1].value, ms_rounds=ms[2].value, ms_finalize=ms[3].value)
 
     def plan_cvp_batch(self, seed_pos, seed_faces, target_faces, goal_dist_offset: float = 0.3, cost_limit: float = 1.0,
                        want_fields: bool = False, want_vecmap: bool = False):

@@ -84,6 +84,7 @@ constexpr int kChunk = 96;  // step launches per graph replay; multiple of 6 (sl
 #include "mnav_locate.h"     // pose lookup: point LBVH over the vertices, exact nearest vertex, containing face (mnav_loc::)
 #include "mnav_follow.h"     // vector-field follower: one controller tick for a batch of robots over the resident fields (mnav_fol::)
 #include "mnav_rollout.h"    // device rollouts: many controller ticks per call over resident robot state (mnav_rol::)
+#include "mnav_replan.h"     // replan on a resident potential: rewind level from the change log, rewind with the tiles' wake-up words (k_replan_*)
 #include "mnav_graph.h"      // resident layer graph: node passes with change lists, id-list union, combination into a slot (mnav_map::)
 
 // One back-tracking job: the plan's resident vector map and the two ends of the walk.
@@ -235,6 +236,20 @@ struct mnav_ctx {
   Options opt;                                                       // mnav_options.h: read from the environment once, by mnav_create
   uint32_t max_steps_auto = 1u << 20;
   DevBuf<uint32_t> d_ring; uint32_t ring_cap = 0; size_t ring_words = 0; PinnedBuf<AsyncCtl> h_actl; DevBuf<uint32_t> d_parked; size_t parked_words = 0;   // asynchronous tile engine: ticket ring, pinned copy of its control words
+  // replan on the resident potentials (mnav_replan_dijkstra_batch)
+  struct Replan {
+    // change log: vertices whose cost, blocked status or incident edge weights may have changed since the last Dijkstra call.
+    // Every writer knows its count on the host, so the length lives there; `all`: a writer replaced whole arrays, or the log ran over
+    DevBuf<uint32_t> log; uint32_t len = 0; bool all = false;
+    // the last Dijkstra call, in the caller's order; which device slot each plan ran in; whether slots[k].dist holds a field to rewind
+    std::vector<uint32_t> seeds, targets, caller_slot; double cost_limit = 1.0, offset = 0.0; bool have_call = false, usable = false;
+    bool partial = false;            // the last Dijkstra call went through, but a plan of it never reached the device (rejected ids, seed == target)
+    DevBuf<uint32_t> d_level, d_old_target; DevBuf<float> d_cut; DevBuf<ReplanCnt> d_cnt; uint32_t cap = 0;
+    Event ev[5]; bool have_ev = false;
+    // statistics of the last replan call (mnav_replan_stats)
+    uint32_t reason = 0, stat_log_len = 0, tiles_woken = 0, rounds = 0; uint64_t kept = 0, rewound = 0; std::vector<float> levels;
+    float ms_level = 0.f, ms_rewind = 0.f, ms_rounds = 0.f, ms_finalize = 0.f;
+  } rp;
   uint32_t last_planner = 0, last_n = 0;
   std::vector<uint32_t> last_target; double last_offset = 0.0;   // Dijkstra: robot vertex per device slot, goal_dist_offset of the last call
   mnav_stats stats{};
@@ -545,6 +560,35 @@ int check_ready(mnav_ctx* ctx)
   return 0;
 }
 
+// -- change log of the replan -----------------------------------------------------------------------
+// Nothing is logged before the first Dijkstra call, and nothing once "everything changed" is set: both are decided here.
+uint32_t replan_log_room(mnav_ctx* ctx, uint32_t n)
+{
+  mnav_ctx::Replan& R = ctx->rp;
+  if (!R.have_call || R.all || n == 0) return 0;
+  const uint32_t cap = std::min(opt_u32(ctx->opt.replan_log_cap, ctx->V), ctx->V);
+  if (n > cap || R.len > cap - n) { R.all = true; return 0; }        // overflow: the next replan plans afresh
+  if (!R.log && R.log.alloc(sizeof(uint32_t) * (size_t)(ctx->V ? ctx->V : 1)) != hipSuccess) { R.all = true; return 0; }
+  return n;
+}
+// n vertex ids that are already on the device (enqueued on the context's stream, before the writer's synchronisation)
+void replan_log_vertices(mnav_ctx* ctx, const uint32_t* d_ids, uint32_t n)
+{
+  mnav_ctx::Replan& R = ctx->rp;
+  if (!replan_log_room(ctx, n)) return;
+  if (hipMemcpyAsync(R.log + R.len, d_ids, sizeof(uint32_t) * n, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) { R.all = true; return; }
+  R.len += n;
+}
+// both endpoints of n edges
+void replan_log_edges(mnav_ctx* ctx, const uint32_t* d_edge_ids, uint32_t n)
+{
+  mnav_ctx::Replan& R = ctx->rp;
+  if (n > 0x7FFFFFFFu || !replan_log_room(ctx, 2u * n)) { if (n > 0x7FFFFFFFu) R.all = true; return; }
+  hipLaunchKernelGGL(k_replan_log_edges, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, n, d_edge_ids, ctx->d_edge_vtx, R.log + R.len);
+  if (hipGetLastError() != hipSuccess) { R.all = true; return; }
+  R.len += 2u * n;
+}
+
 // the face tables that the device back-tracking and the containing-face search walk: uploaded by whichever comes first
 int upload_walk_mesh(mnav_ctx* ctx)
 {
@@ -631,6 +675,7 @@ int mnav_upload_mesh(mnav_ctx* ctx, uint32_t V, uint32_t F, uint32_t E, const fl
   (void)hipStreamSynchronize(ctx->stream);
   // V-, E- and F-sized state of the old mesh
   ctx->slots.clear();
+  ctx->rp.log.reset(); ctx->rp.len = 0; ctx->rp.all = false; ctx->rp.have_call = ctx->rp.usable = ctx->rp.partial = false;   // (the log is V-sized; the recorded seeds are the old mesh's)
   ctx->layers.clear();
   ctx->d_crn_infl.reset(); ctx->d_infl_mask.reset(); ctx->d_zero_u8.reset(); ctx->d_infl_keyd.reset(); ctx->crn_infl_valid = false;
   ctx->obs = {};                                                     // rebuilt lazily
@@ -639,6 +684,7 @@ int mnav_upload_mesh(mnav_ctx* ctx, uint32_t V, uint32_t F, uint32_t E, const fl
   ctx->chg = {};                                                     // V-sized change list
   ctx->map = {};                                                     // the layer graph: its slots are gone
   ctx->loc = {};                                                     // vertex index: rebuilt lazily
+  ctx->rp = {};                                                      // change log and replan state: the fields are gone with the slots
   ctx->d_edge_dist.reset();
   drop_graphs(ctx);
   ctx->d_paths.reset(); ctx->paths_words = 0;
@@ -740,6 +786,7 @@ int mnav_upload_costs(mnav_ctx* ctx, const float* vertex_costs, const float* edg
   if (!ctx->have_mesh) { ctx->err = "mnav_upload_mesh has not been called"; return -1; }
   if ((ctx->V && !vertex_costs) || (ctx->E && !edge_weights)) { ctx->err = "null cost array"; return -1; }
   if (hipSetDevice(ctx->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return -1; }
+  ctx->rp.all = true;                                                // whole arrays replaced: a replan plans afresh, also after a failure half way
   HIPCHK(ctx->d_cost.upload(ctx->stream, vertex_costs, ctx->V));
   HIPCHK(ctx->d_w.upload(ctx->stream, edge_weights, ctx->E));
   std::vector<uint8_t> zero;
@@ -759,6 +806,7 @@ int mnav_upload_costs(mnav_ctx* ctx, const float* vertex_costs, const float* edg
 // (re)computed; host mirrors (cost for the seed cut-offs, mean weight for the band widths) are refreshed
 static int edge_weight_pass(mnav_ctx* ctx, double edge_cost_factor, const uint8_t* invalid, float* vertex_costs_out, float* edge_weights_out)
 {
+  ctx->rp.all = true;                                                // whole arrays replaced: a replan plans afresh
   HIPCHK(ctx->d_w.upload(ctx->stream, nullptr, ctx->E));
   std::vector<uint8_t> zero;
   if (!invalid) { zero.assign(ctx->V ? ctx->V : 1, 0); invalid = zero.data(); }
@@ -790,6 +838,7 @@ int mnav_compute_edge_weights(mnav_ctx* ctx, const float* vertex_costs, const fl
   if (!ctx->have_mesh) { ctx->err = "mnav_upload_mesh has not been called"; return -1; }
   if ((ctx->V && !vertex_costs) || (ctx->E && !edge_distances)) { ctx->err = "null cost array"; return -1; }
   if (hipSetDevice(ctx->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return -1; }
+  ctx->rp.all = true;                                                // whole arrays replaced: a replan plans afresh, also after a failure half way
   HIPCHK(ctx->d_cost.upload(ctx->stream, vertex_costs, ctx->V));
   HIPCHK(ctx->d_edge_dist.upload(ctx->stream, edge_distances, ctx->E));
   ctx->crn_infl_valid = false;
@@ -806,6 +855,7 @@ int mnav_combine_costs(mnav_ctx* ctx, int mode, uint32_t n_layers, const float* 
   if (mode != 0 && mode != 1) { ctx->err = "combination mode must be 0 (max) or 1 (weighted sum)"; return -1; }
   if ((n_layers && !layer_costs) || (mode == 1 && n_layers && !weights) || (ctx->E && !edge_distances && !ctx->d_edge_dist)) { ctx->err = "null input array"; return -1; }
   if (hipSetDevice(ctx->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return -1; }
+  ctx->rp.all = true;                                                // whole arrays replaced: a replan plans afresh, also after a failure half way
   const uint32_t V = ctx->V;
   DevBuf<float> d_layers, d_wts;
   HIPCHK(d_layers.alloc(sizeof(float) * ((size_t)n_layers * V + 1)));
@@ -857,7 +907,9 @@ int mnav_update_costs(mnav_ctx* ctx, uint32_t n, const uint32_t* vertex_ids, con
                               ctx->d_nbr_u, ctx->d_nbr_e, ctx->d_edge_dist, ctx->d_cost, ctx->edge_cost_factor, ctx->d_w);
     }
     if (rc == 0 && hipGetLastError() != hipSuccess) { ctx->err = "cost update failed"; rc = -1; }
+    if (rc == 0) replan_log_vertices(ctx, d_ids, n);
   }
+  if (rc) ctx->rp.all = true;                                        // (how far a failed update got is unknown)
   (void)hipStreamSynchronize(ctx->stream);
   if (rc) return rc;
   for (uint32_t i = 0; i < n; ++i) ctx->h_cost[vertex_ids[i]] = values[i];
@@ -883,7 +935,9 @@ int mnav_update_edge_weights(mnav_ctx* ctx, uint32_t n, const uint32_t* edge_ids
   if (rc == 0) {
     hipLaunchKernelGGL(k_scatter_costs, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, n, d_ids, d_vals, ctx->d_w);   // (a scatter of floats by index)
     if (hipGetLastError() != hipSuccess) { ctx->err = "edge weight update failed"; rc = -1; }
+    if (rc == 0) replan_log_edges(ctx, d_ids, n);
   }
+  if (rc) ctx->rp.all = true;                                        // (how far a failed update got is unknown)
   (void)hipStreamSynchronize(ctx->stream);
   if (rc) return rc;
   ctx->nbr_valid = ctx->crn_valid = false;                          // the cost-limit folded copies (and the tiles' weights behind them) are rebuilt on the next plan
@@ -1229,6 +1283,7 @@ int mnav_combine_layers(mnav_ctx* ctx, int mode, uint32_t n_layers, const uint32
     if (layers[l] >= ctx->layers.size() || !ctx->layers[layers[l]].ready) { ctx->err = "layer is not resident"; return -1; }
     ptrs[l] = ctx->layers[layers[l]].cost;
   }
+  ctx->rp.all = true;                                                // whole arrays replaced: a replan plans afresh, also after a failure half way
   if (ensure_edge_distances(ctx)) return -1;
   DevBuf<const float*> d_ptrs; DevBuf<float> d_wts;
   HIPCHK(d_ptrs.alloc(sizeof(float*) * (n_layers + 1)));
@@ -1268,6 +1323,7 @@ int mnav_combine_layers_update(mnav_ctx* ctx, int mode, uint32_t n_layers, const
     if (layers[l] >= ctx->layers.size() || !ctx->layers[layers[l]].ready) { ctx->err = "layer is not resident"; return -1; }
     ptrs[l] = ctx->layers[layers[l]].cost;
   }
+  ctx->rp.all = true;                                                // (not one of the logging writers: a replan plans afresh)
   DevBuf<const float*> d_ptrs; DevBuf<float> d_wts, d_vals; DevBuf<uint32_t> d_ids;
   HIPCHK(d_ptrs.alloc(sizeof(float*) * (n_layers + 1)));
   HIPCHK(d_wts.alloc(sizeof(float) * (n_layers + 1)));
@@ -1294,6 +1350,116 @@ int mnav_combine_layers_update(mnav_ctx* ctx, int mode, uint32_t n_layers, const
   return 0;
 }
 
+// The tail of a Dijkstra call whose engine (and, unless the call is paths-only, finalize pass) has run: vertex paths, result
+// records, the vector map, the downloads and the statistics of m device plans; map: device plan -> caller's index.
+// Returns 0 or -1 (ctx->err set).
+static int dijkstra_tail(mnav_ctx* ctx, uint32_t m, int engine, const std::vector<uint32_t>& map, std::vector<uint32_t>& codes, float* dist_out,
+                         uint32_t* pred_out, uint32_t* path_out, uint32_t path_cap, uint32_t* path_len, float* vecmap_out, bool want_vecmap)
+{
+  const uint32_t V = ctx->V;
+  const PathRows rows1{ ctx->d_paths, ctx->path_stride, nullptr, nullptr };
+  PathRows rows2{ nullptr, 0u, nullptr, nullptr };
+  const uint32_t gc = (V + kBlock * 4 - 1) / (kBlock * 4);
+  if (engine == 5 && ctx->lazy_paths) {
+    hipLaunchKernelGGL(k_tb_path, dim3(m), dim3(kWave), 0, ctx->stream, ctx->tb_args, ctx->d_row_ptr, ctx->d_nbr, V, ctx->d_res, rows1, ctx->d_mismatch);
+    ctx->tb.count_pending = true;                                  // settled vertices (a statistic): counted when somebody asks, mnav_get_stats
+  } else if (ctx->lazy_paths) {
+    hipLaunchKernelGGL(k_path_lazy, dim3(m), dim3(kWave), 0, ctx->stream, ctx->d_plans, ctx->d_tplans, ctx->d_res, rows1, ctx->d_mismatch);
+    hipLaunchKernelGGL(k_count_goal, dim3(gc ? gc : 1, m), dim3(kBlock), 0, ctx->stream, ctx->d_plans, ctx->d_res);
+  } else
+  hipLaunchKernelGGL(k_finish<kPlannerDijkstra>, dim3(m), dim3(64), 0, ctx->stream, ctx->d_plans, ctx->d_res, rows1);
+  if (engine == 1)   // the tile engines count the settled vertices in k_dij_finalize
+    hipLaunchKernelGGL(k_count, dim3(gc ? gc : 1, m), dim3(kBlock), 0, ctx->stream, ctx->d_plans, ctx->d_res);
+  (void)hipEventRecord(ctx->ev[4], ctx->stream);
+  if (want_vecmap && !(engine == 5 && !ctx->lazy_paths))            // (the tile-batch engine's finalize pass writes the vector map itself)
+    hipLaunchKernelGGL(k_vecmap_dijkstra, dim3(gc ? gc : 1, m), dim3(kBlock), 0, ctx->stream, ctx->d_plans, ctx->d_xyz, ctx->d_vecptrs);
+  (void)hipEventRecord(ctx->ev[5], ctx->stream);
+  if (hipMemcpyAsync(ctx->h_res, ctx->d_res, sizeof(PlanResult) * m, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+      hipStreamSynchronize(ctx->stream) != hipSuccess) { ctx->err = "result download failed"; return -1; }
+  {
+    // paths longer than the default rows (corridors, mazes): ONLY those plans are walked again, into rows of exactly their
+    // length (the first walk counted it) in one packed buffer
+    size_t over_words = 0;
+    std::vector<unsigned long long> ooff(m, 0ull); std::vector<uint32_t> ocap(m, 0u);
+    for (uint32_t k = 0; k < m; ++k)
+      if (ctx->h_res[k].code == kPathOverflow) { ooff[k] = over_words; ocap[k] = ctx->h_res[k].path_len; over_words += ctx->h_res[k].path_len; }
+    if (over_words) {
+      std::vector<PlanResult> keep(ctx->h_res.get(), ctx->h_res + m);   // settled / evals were accumulated by other kernels
+      ctx->d_over.reset(); ctx->d_over_off.reset(); ctx->d_over_cap.reset();
+      if (ctx->d_over.alloc(4 * over_words) != hipSuccess || ctx->d_over_off.alloc(8 * (size_t)m) != hipSuccess || ctx->d_over_cap.alloc(4 * (size_t)m) != hipSuccess ||
+          hipMemcpyAsync(ctx->d_over_off, ooff.data(), 8 * (size_t)m, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+          hipMemcpyAsync(ctx->d_over_cap, ocap.data(), 4 * (size_t)m, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+        { ctx->err = "path buffers: out of memory"; return -1; }
+      rows2 = PathRows{ ctx->d_over, 0u, ctx->d_over_off, ctx->d_over_cap };
+      if (engine == 5 && ctx->lazy_paths) hipLaunchKernelGGL(k_tb_path, dim3(m), dim3(kWave), 0, ctx->stream, ctx->tb_args, ctx->d_row_ptr, ctx->d_nbr, V, ctx->d_res, rows2, ctx->d_mismatch);
+      else if (ctx->lazy_paths) hipLaunchKernelGGL(k_path_lazy, dim3(m), dim3(kWave), 0, ctx->stream, ctx->d_plans, ctx->d_tplans, ctx->d_res, rows2, ctx->d_mismatch);
+      else hipLaunchKernelGGL(k_finish<kPlannerDijkstra>, dim3(m), dim3(64), 0, ctx->stream, ctx->d_plans, ctx->d_res, rows2);
+      if (hipMemcpyAsync(ctx->h_res, ctx->d_res, sizeof(PlanResult) * m, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+          hipStreamSynchronize(ctx->stream) != hipSuccess) { ctx->err = "result download failed"; return -1; }
+      for (uint32_t k = 0; k < m; ++k) ctx->h_res[k].settled = keep[k].settled;
+    }
+  }
+  if (ctx->last_engine != 1) {
+    uint32_t mism = 0;
+    if (hipMemcpy(&mism, ctx->d_mismatch, 4, hipMemcpyDeviceToHost) != hipSuccess || mism != 0) {
+      ctx->err = "tiled SSSP did not reach its fixed point (" + std::to_string(mism) + " vertices)";
+      return -1;
+    }
+  }
+  MTRACE("results downloaded");
+  // all vertex paths: packed and reversed on the device (k_pack_paths), one dense copy into a pinned buffer
+  std::vector<uint32_t> offs(m + 1, 0), lens(m, 0);
+  for (uint32_t k = 0; k < m; ++k) {
+    lens[k] = (ctx->h_res[k].code == MNAV_SUCCESS) ? ctx->h_res[k].path_len : 0u;
+    offs[k + 1] = offs[k] + lens[k];
+  }
+  const size_t total = offs[m];
+  if (total && path_out && path_cap) {
+    if (ctx->pack_words < total) {
+      ctx->d_pack.reset(); ctx->h_pack.reset(); ctx->pack_words = 0;
+      const size_t want = total + total / 4 + 1024;
+      if (ctx->d_pack.alloc(4 * want) != hipSuccess || ctx->h_pack.alloc(4 * want) != hipSuccess)
+        { ctx->err = "path buffers: out of memory"; return -1; }
+      ctx->pack_words = want;
+    }
+    if (ctx->pack_meta_n < 2 * (size_t)m) {
+      ctx->pack_meta_n = 0;
+      if (ctx->d_pack_meta.alloc(4 * 2 * (size_t)m) != hipSuccess) { ctx->err = "path buffers: out of memory"; return -1; }
+      ctx->pack_meta_n = 2 * (size_t)m;
+    }
+    if (hipMemcpyAsync(ctx->d_pack_meta, offs.data(), 4 * (size_t)m, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+        hipMemcpyAsync(ctx->d_pack_meta + m, lens.data(), 4 * (size_t)m, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+      { ctx->err = "path download failed"; return -1; }
+    hipLaunchKernelGGL(k_pack_paths, dim3(m), dim3(kBlock), 0, ctx->stream, rows1, rows2, ctx->d_pack_meta, ctx->d_pack_meta + m, ctx->d_pack);
+    if (hipMemcpyAsync(ctx->h_pack, ctx->d_pack, 4 * total, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+        hipStreamSynchronize(ctx->stream) != hipSuccess) { ctx->err = "path download failed"; return -1; }
+  }
+  MTRACE("paths downloaded");
+  for (uint32_t k = 0; k < m; ++k) {
+    const uint32_t i = map[k];
+    const PlanResult& r = ctx->h_res[k];
+    codes[i] = r.code;
+    if (r.code == MNAV_SUCCESS) {
+      if (path_len) path_len[i] = r.path_len;
+      if (path_out && path_cap && r.path_len)                         // reference list order: seed ... pred[target]
+        memcpy(path_out + (size_t)i * path_cap, ctx->h_pack + offs[k], 4 * (size_t)std::min(r.path_len, path_cap));
+    }
+    if (dist_out && hipMemcpyAsync(dist_out + (size_t)i * V, ctx->slots[k].dist, 4 * (size_t)V, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+      { ctx->err = "dist download failed"; return -1; }
+    if (pred_out && hipMemcpyAsync(pred_out + (size_t)i * V, ctx->slots[k].pred, 4 * (size_t)V, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+      { ctx->err = "pred download failed"; return -1; }
+    if (vecmap_out && want_vecmap && hipMemcpyAsync(vecmap_out + (size_t)i * 3 * V, ctx->slots[k].vecmap, 12 * (size_t)V, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+      { ctx->err = "vecmap download failed"; return -1; }
+  }
+  MTRACE("paths copied out");
+  (void)hipEventRecord(ctx->ev[6], ctx->stream);
+  if (hipStreamSynchronize(ctx->stream) != hipSuccess) { ctx->err = "sync failed"; return -1; }
+  if (engine == 5 && tb_clean_other(ctx)) return -1;   // (the next call's distance buffer, in the gap between the calls)
+  finish_stats(ctx, m, false);
+  MTRACE("stats done");
+  return 0;
+}
+
 static uint32_t dijkstra_impl(mnav_ctx* ctx, uint32_t n, const uint32_t* seeds, const uint32_t* targets, double offset,
                               double cost_limit, uint32_t* codes_out, float* dist_out, uint32_t* pred_out, uint32_t* path_out,
                               uint32_t path_cap, uint32_t* path_len, float* vecmap_out, bool want_vecmap)
@@ -1313,6 +1479,13 @@ static uint32_t dijkstra_impl(mnav_ctx* ctx, uint32_t n, const uint32_t* seeds, 
   MTRACE("start");
   const uint32_t V = ctx->V;
   uint32_t worst = MNAV_SUCCESS;
+  {
+    // what a replan needs of this call (the caller's arrays may be the record's own: mnav_replan_dijkstra_batch); its fields
+    // count once the call has gone through
+    mnav_ctx::Replan& R = ctx->rp;
+    const std::vector<uint32_t> s_(seeds, seeds + n), t_(targets, targets + n);
+    R.seeds = s_; R.targets = t_; R.cost_limit = cost_limit; R.offset = offset; R.have_call = true; R.usable = false; R.partial = false;
+  }
   // id checks stand in for the optional-handle tests of dijkstra :240-243
   std::vector<PlanIn> in; std::vector<uint32_t> map;   // map: device plan -> caller index
   std::vector<uint32_t> codes(n, MNAV_SUCCESS);
@@ -1412,107 +1585,13 @@ static uint32_t dijkstra_impl(mnav_ctx* ctx, uint32_t n, const uint32_t* seeds, 
     if (rc == 1) { for (uint32_t i = 0; i < n; ++i) if (codes_out) codes_out[i] = MNAV_CANCELED; return MNAV_CANCELED; }   // :350-354
     ctx->last_engine = engine; ctx->last_n = m;                       // only a call whose engine succeeded leaves outputs behind
     if (engine == 1) ctx->lazy_paths = false;                         // the band steps keep their predecessors as they go
-    const PathRows rows1{ ctx->d_paths, ctx->path_stride, nullptr, nullptr };
-    PathRows rows2{ nullptr, 0u, nullptr, nullptr };
-    const uint32_t gc = (V + kBlock * 4 - 1) / (kBlock * 4);
-    if (engine == 5 && ctx->lazy_paths) {
-      hipLaunchKernelGGL(k_tb_path, dim3(m), dim3(kWave), 0, ctx->stream, ctx->tb_args, ctx->d_row_ptr, ctx->d_nbr, V, ctx->d_res, rows1, ctx->d_mismatch);
-      ctx->tb.count_pending = true;                                  // settled vertices (a statistic): counted when somebody asks, mnav_get_stats
-    } else if (ctx->lazy_paths) {
-      hipLaunchKernelGGL(k_path_lazy, dim3(m), dim3(kWave), 0, ctx->stream, ctx->d_plans, ctx->d_tplans, ctx->d_res, rows1, ctx->d_mismatch);
-      hipLaunchKernelGGL(k_count_goal, dim3(gc ? gc : 1, m), dim3(kBlock), 0, ctx->stream, ctx->d_plans, ctx->d_res);
-    } else
-    hipLaunchKernelGGL(k_finish<kPlannerDijkstra>, dim3(m), dim3(64), 0, ctx->stream, ctx->d_plans, ctx->d_res, rows1);
-    if (engine == 1)   // the tile engines count the settled vertices in k_dij_finalize
-      hipLaunchKernelGGL(k_count, dim3(gc ? gc : 1, m), dim3(kBlock), 0, ctx->stream, ctx->d_plans, ctx->d_res);
-    (void)hipEventRecord(ctx->ev[4], ctx->stream);
-    if (want_vecmap && !(engine == 5 && !ctx->lazy_paths))            // (the tile-batch engine's finalize pass writes the vector map itself)
-      hipLaunchKernelGGL(k_vecmap_dijkstra, dim3(gc ? gc : 1, m), dim3(kBlock), 0, ctx->stream, ctx->d_plans, ctx->d_xyz, ctx->d_vecptrs);
-    (void)hipEventRecord(ctx->ev[5], ctx->stream);
-    if (hipMemcpyAsync(ctx->h_res, ctx->d_res, sizeof(PlanResult) * m, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-        hipStreamSynchronize(ctx->stream) != hipSuccess) { ctx->err = "result download failed"; return MNAV_INTERNAL_ERROR; }
-    {
-      // paths longer than the default rows (corridors, mazes): ONLY those plans are walked again, into rows of exactly their
-      // length (the first walk counted it) in one packed buffer
-      size_t over_words = 0;
-      std::vector<unsigned long long> ooff(m, 0ull); std::vector<uint32_t> ocap(m, 0u);
-      for (uint32_t k = 0; k < m; ++k)
-        if (ctx->h_res[k].code == kPathOverflow) { ooff[k] = over_words; ocap[k] = ctx->h_res[k].path_len; over_words += ctx->h_res[k].path_len; }
-      if (over_words) {
-        std::vector<PlanResult> keep(ctx->h_res.get(), ctx->h_res + m);   // settled / evals were accumulated by other kernels
-        ctx->d_over.reset(); ctx->d_over_off.reset(); ctx->d_over_cap.reset();
-        if (ctx->d_over.alloc(4 * over_words) != hipSuccess || ctx->d_over_off.alloc(8 * (size_t)m) != hipSuccess || ctx->d_over_cap.alloc(4 * (size_t)m) != hipSuccess ||
-            hipMemcpyAsync(ctx->d_over_off, ooff.data(), 8 * (size_t)m, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
-            hipMemcpyAsync(ctx->d_over_cap, ocap.data(), 4 * (size_t)m, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-          { ctx->err = "path buffers: out of memory"; return MNAV_INTERNAL_ERROR; }
-        rows2 = PathRows{ ctx->d_over, 0u, ctx->d_over_off, ctx->d_over_cap };
-        if (engine == 5 && ctx->lazy_paths) hipLaunchKernelGGL(k_tb_path, dim3(m), dim3(kWave), 0, ctx->stream, ctx->tb_args, ctx->d_row_ptr, ctx->d_nbr, V, ctx->d_res, rows2, ctx->d_mismatch);
-        else if (ctx->lazy_paths) hipLaunchKernelGGL(k_path_lazy, dim3(m), dim3(kWave), 0, ctx->stream, ctx->d_plans, ctx->d_tplans, ctx->d_res, rows2, ctx->d_mismatch);
-        else hipLaunchKernelGGL(k_finish<kPlannerDijkstra>, dim3(m), dim3(64), 0, ctx->stream, ctx->d_plans, ctx->d_res, rows2);
-        if (hipMemcpyAsync(ctx->h_res, ctx->d_res, sizeof(PlanResult) * m, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-            hipStreamSynchronize(ctx->stream) != hipSuccess) { ctx->err = "result download failed"; return MNAV_INTERNAL_ERROR; }
-        for (uint32_t k = 0; k < m; ++k) ctx->h_res[k].settled = keep[k].settled;
-      }
-    }
-    if (ctx->last_engine != 1) {
-      uint32_t mism = 0;
-      if (hipMemcpy(&mism, ctx->d_mismatch, 4, hipMemcpyDeviceToHost) != hipSuccess || mism != 0) {
-        ctx->err = "tiled SSSP did not reach its fixed point (" + std::to_string(mism) + " vertices)";
-        return MNAV_INTERNAL_ERROR;
-      }
-    }
-    MTRACE("results downloaded");
-    // all vertex paths: packed and reversed on the device (k_pack_paths), one dense copy into a pinned buffer
-    std::vector<uint32_t> offs(m + 1, 0), lens(m, 0);
-    for (uint32_t k = 0; k < m; ++k) {
-      lens[k] = (ctx->h_res[k].code == MNAV_SUCCESS) ? ctx->h_res[k].path_len : 0u;
-      offs[k + 1] = offs[k] + lens[k];
-    }
-    const size_t total = offs[m];
-    if (total && path_out && path_cap) {
-      if (ctx->pack_words < total) {
-        ctx->d_pack.reset(); ctx->h_pack.reset(); ctx->pack_words = 0;
-        const size_t want = total + total / 4 + 1024;
-        if (ctx->d_pack.alloc(4 * want) != hipSuccess || ctx->h_pack.alloc(4 * want) != hipSuccess)
-          { ctx->err = "path buffers: out of memory"; return MNAV_INTERNAL_ERROR; }
-        ctx->pack_words = want;
-      }
-      if (ctx->pack_meta_n < 2 * (size_t)m) {
-        ctx->pack_meta_n = 0;
-        if (ctx->d_pack_meta.alloc(4 * 2 * (size_t)m) != hipSuccess) { ctx->err = "path buffers: out of memory"; return MNAV_INTERNAL_ERROR; }
-        ctx->pack_meta_n = 2 * (size_t)m;
-      }
-      if (hipMemcpyAsync(ctx->d_pack_meta, offs.data(), 4 * (size_t)m, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
-          hipMemcpyAsync(ctx->d_pack_meta + m, lens.data(), 4 * (size_t)m, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-        { ctx->err = "path download failed"; return MNAV_INTERNAL_ERROR; }
-      hipLaunchKernelGGL(k_pack_paths, dim3(m), dim3(kBlock), 0, ctx->stream, rows1, rows2, ctx->d_pack_meta, ctx->d_pack_meta + m, ctx->d_pack);
-      if (hipMemcpyAsync(ctx->h_pack, ctx->d_pack, 4 * total, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-          hipStreamSynchronize(ctx->stream) != hipSuccess) { ctx->err = "path download failed"; return MNAV_INTERNAL_ERROR; }
-    }
-    MTRACE("paths downloaded");
-    for (uint32_t k = 0; k < m; ++k) {
-      const uint32_t i = map[k];
-      const PlanResult& r = ctx->h_res[k];
-      codes[i] = r.code;
-      if (r.code == MNAV_SUCCESS) {
-        if (path_len) path_len[i] = r.path_len;
-        if (path_out && path_cap && r.path_len)                         // reference list order: seed ... pred[target]
-          memcpy(path_out + (size_t)i * path_cap, ctx->h_pack + offs[k], 4 * (size_t)std::min(r.path_len, path_cap));
-      }
-      if (dist_out && hipMemcpyAsync(dist_out + (size_t)i * V, ctx->slots[k].dist, 4 * (size_t)V, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
-        { ctx->err = "dist download failed"; return MNAV_INTERNAL_ERROR; }
-      if (pred_out && hipMemcpyAsync(pred_out + (size_t)i * V, ctx->slots[k].pred, 4 * (size_t)V, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
-        { ctx->err = "pred download failed"; return MNAV_INTERNAL_ERROR; }
-      if (vecmap_out && want_vecmap && hipMemcpyAsync(vecmap_out + (size_t)i * 3 * V, ctx->slots[k].vecmap, 12 * (size_t)V, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
-        { ctx->err = "vecmap download failed"; return MNAV_INTERNAL_ERROR; }
-    }
-    MTRACE("paths copied out");
-    (void)hipEventRecord(ctx->ev[6], ctx->stream);
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess) { ctx->err = "sync failed"; return MNAV_INTERNAL_ERROR; }
-    if (engine == 5 && tb_clean_other(ctx)) return MNAV_INTERNAL_ERROR;   // (the next call's distance buffer, in the gap between the calls)
-    finish_stats(ctx, m, false);
-    MTRACE("stats done");
+    if (dijkstra_tail(ctx, m, engine, map, codes, dist_out, pred_out, path_out, path_cap, path_len, vecmap_out, want_vecmap)) return MNAV_INTERNAL_ERROR;
+    // slots[k].dist is a field a replan can rewind: below the cut every value is final after the tile rounds and the
+    // asynchronous tiles (finalized or not) and after the tile-batch engine's finalize pass; the band steps keep other values
+    ctx->rp.usable = engine == 0 || engine == 6 || (engine == 5 && !ctx->lazy_paths);
   }
+  ctx->rp.caller_slot = ctx->caller_slot; ctx->rp.len = 0; ctx->rp.all = false;   // the change log starts over
+  ctx->rp.partial = m != n;
   // plans rejected before reaching the device: the reference has cleared its maps by then
   for (uint32_t i = 0; i < n; ++i) {
     if (codes[i] == MNAV_INVALID_START || codes[i] == MNAV_INVALID_GOAL || cleared[i]) {
@@ -1595,6 +1674,7 @@ static uint32_t cvp_impl(mnav_ctx* ctx, uint32_t n, const float* seed_pos, const
   (void)hipEventRecord(ctx->ev[0], ctx->stream);
   ctx->tb.count_pending = false; ctx->tb_args_valid = false;         // (a lazy settled-vertex count of an earlier Dijkstra batch is void now)
   ctx->last_planner = kPlannerCvp; ctx->last_n = 0; ctx->last_engine = 1;
+  ctx->rp.usable = ctx->rp.partial = false;                          // the slots' dist now holds CVP potentials
   uint32_t worst = MNAV_SUCCESS;
   if (m) {
     if (materialize(ctx, true, cost_limit)) return MNAV_INTERNAL_ERROR;
@@ -1677,6 +1757,7 @@ uint32_t mnav_plan_cvp_batch(mnav_ctx* ctx, uint32_t n, const float* seed_pos, c
 #include "mnav_follow_capi.h"     // mnav_follow_batch, mnav_follow_stats
 #include "mnav_rollout_capi.h"    // mnav_follow_rollout, mnav_rollout_stats
 #include "mnav_graph_capi.h"      // mnav_map_configure / _compute / _layer_changed / _update_layer / _obstacle / _stats
+#include "mnav_replan_capi.h"     // mnav_replan_dijkstra_batch, mnav_replan_stats
 
 void mnav_cancel(mnav_ctx* ctx)
 {

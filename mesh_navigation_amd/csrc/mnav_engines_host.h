@@ -194,17 +194,13 @@ int run_tile_chunk(mnav_ctx* ctx, uint32_t n, uint32_t G)
   return 0;
 }
 
-// Dijkstra through the tiled engine.  Returns 0, -1 (error) or 1 (cancelled).
-int run_dijkstra_tiled(mnav_ctx* ctx, uint32_t n, const std::vector<PlanIn>& in, double offset)
+// The plan and tile-plan records of n plans on the tile rounds, uploaded, with cleared results.  The caller owns the host
+// vectors: they must outlive the copies (its next stream synchronisation).
+int fill_tile_records(mnav_ctx* ctx, uint32_t n, const std::vector<PlanIn>& in, double offset, std::vector<Plan>& hp, std::vector<TilePlan>& tp,
+                      std::vector<float*>& vecs)
 {
-  if (ensure_slots(ctx, n, false, false, ctx->want_vec)) return -1;
-  if (ensure_paths(ctx, n)) return -1;
-  if (ensure_tile_state(ctx, n)) return -1;
-  if (tile_weights(ctx)) return -1;
   const HostTiles& M = ctx->tiles_meta;
-  std::vector<Plan> hp(n);
-  std::vector<TilePlan> tp(n);
-  std::vector<float*> vecs(n);
+  hp.assign(n, Plan{}); tp.assign(n, TilePlan{}); vecs.assign(n, nullptr);
   for (uint32_t i = 0; i < n; ++i) {
     Slot& s = ctx->slots[i];
     Plan& P = hp[i];
@@ -234,20 +230,13 @@ int run_dijkstra_tiled(mnav_ctx* ctx, uint32_t n, const std::vector<PlanIn>& in,
   HIPCHK(hipMemcpyAsync(ctx->d_vecptrs, vecs.data(), sizeof(float*) * n, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipMemsetAsync(ctx->d_res, 0, sizeof(PlanResult) * n, ctx->stream));
   HIPCHK(hipMemsetAsync(ctx->d_mismatch, 0, 4, ctx->stream));
+  return 0;
+}
 
-  HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
-  uint32_t gi = (ctx->V + kBlock * 4 - 1) / (kBlock * 4);
-  if (gi < 1) gi = 1;
-  if (gi > 4096) gi = 4096;
-  hipLaunchKernelGGL(k_init<kPlannerDijkstra>, dim3(gi, n), dim3(kBlock), 0, ctx->stream, ctx->d_plans);
-  {
-    uint32_t gt = (M.ntiles + kBlock - 1) / kBlock;
-    if (gt < 1) gt = 1;
-    hipLaunchKernelGGL(k_tile_init, dim3(gt, n), dim3(kBlock), 0, ctx->stream, ctx->d_tplans, ctx->d_vert_tile, -inf_f());
-  }
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(ctx->ev[2], ctx->stream));
-
+// The rounds of n plans whose tile state is set up, chunk by chunk, until every plan is done.  Returns 0, -1 (error) or 1 (cancelled).
+int run_tile_rounds(mnav_ctx* ctx, uint32_t n)
+{
+  const HostTiles& M = ctx->tiles_meta;
   // active tiles form a ring along the wavefront: O(sqrt(ntiles)); every workgroup scans a
   // strided share of the tile table, so any grid size is correct
   uint32_t G = (uint32_t)std::ceil(8.0 * std::sqrt((double)M.ntiles)) + 8;
@@ -280,6 +269,35 @@ int run_dijkstra_tiled(mnav_ctx* ctx, uint32_t n, const std::vector<PlanIn>& in,
     if (ctx->cancel.load(std::memory_order_relaxed)) { rc = 1; break; }
   }
   ctx->stats.launches = launches;
+  return rc;
+}
+
+// Dijkstra through the tiled engine.  Returns 0, -1 (error) or 1 (cancelled).
+int run_dijkstra_tiled(mnav_ctx* ctx, uint32_t n, const std::vector<PlanIn>& in, double offset)
+{
+  if (ensure_slots(ctx, n, false, false, ctx->want_vec)) return -1;
+  if (ensure_paths(ctx, n)) return -1;
+  if (ensure_tile_state(ctx, n)) return -1;
+  if (tile_weights(ctx)) return -1;
+  const HostTiles& M = ctx->tiles_meta;
+  std::vector<Plan> hp; std::vector<TilePlan> tp; std::vector<float*> vecs;
+  if (fill_tile_records(ctx, n, in, offset, hp, tp, vecs)) return -1;
+
+  HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
+  uint32_t gi = (ctx->V + kBlock * 4 - 1) / (kBlock * 4);
+  if (gi < 1) gi = 1;
+  if (gi > 4096) gi = 4096;
+  hipLaunchKernelGGL(k_init<kPlannerDijkstra>, dim3(gi, n), dim3(kBlock), 0, ctx->stream, ctx->d_plans);
+  {
+    uint32_t gt = (M.ntiles + kBlock - 1) / kBlock;
+    if (gt < 1) gt = 1;
+    hipLaunchKernelGGL(k_tile_init, dim3(gt, n), dim3(kBlock), 0, ctx->stream, ctx->d_tplans, ctx->d_vert_tile, -inf_f());
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(ctx->ev[2], ctx->stream));
+
+  const int rc = run_tile_rounds(ctx, n);
+  if (rc < 0) return -1;
   if (rc == 0 && !ctx->lazy_paths) {
     launch_finalize(ctx, n);
     HIPCHK(hipGetLastError());

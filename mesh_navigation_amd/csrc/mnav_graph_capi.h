@@ -121,6 +121,7 @@ int mnav_map_compute(mnav_ctx* ctx)
   for (const Node& n : S.order)
     if (n.kind == MNAV_NODE_INPUT && !ctx->layers[n.layer].ready) return map_fail(ctx, "layer graph: an input layer is not resident");
   S.computed = false; S.stale = true;                                // until the whole pass went through
+  ctx->rp.all = true;                                                // whole arrays replaced: a replan plans afresh, also after a failure half way
   const uint32_t V = ctx->V, gb = (V + kBlock - 1) / kBlock ? (V + kBlock - 1) / kBlock : 1;
   for (const Node& n : S.order) {
     if (n.kind == MNAV_NODE_INFLATION) {
@@ -204,6 +205,7 @@ static int map_propagate(mnav_ctx* ctx, uint32_t src, uint32_t* changed_out, uin
       hipLaunchKernelGGL(k_update_edge_weights, dim3((8 * (size_t)nd + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, nd, dn.out, ctx->d_row_ptr,
                          ctx->d_nbr_u, ctx->d_nbr_e, ctx->d_edge_dist, ctx->d_cost, ctx->edge_cost_factor, ctx->d_w);
     HIPCHK(hipGetLastError());
+    replan_log_vertices(ctx, dn.out, nd);                           // D is what a replan has to look at (mnav_replan.h)
     S.h_ids.resize(nd); S.h_vals.resize(nd);
     HIPCHK(hipMemcpyAsync(S.h_ids.data(), dn.out, sizeof(uint32_t) * nd, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipMemcpyAsync(S.h_vals.data(), S.vals, sizeof(float) * nd, hipMemcpyDeviceToHost, ctx->stream));
@@ -241,7 +243,7 @@ static int map_sorted_ids(mnav_ctx* ctx, uint32_t n, const uint32_t* vertex_ids,
 
 static int map_finish(mnav_ctx* ctx, int rc)
 {
-  if (rc) { ctx->map.stale = true; (void)hipStreamSynchronize(ctx->stream); }
+  if (rc) { ctx->map.stale = true; ctx->rp.all = true; (void)hipStreamSynchronize(ctx->stream); }   // (how far the update got is unknown: a replan plans afresh)
   return rc;
 }
 

@@ -28,7 +28,9 @@
   X(async_band_mult)     /* band of the asynchronous engine in tile widths of potential (default 4; <= 0: no bands) */                         \
   X(async_max_batch)     /* auto: batches of up to this many plans take the asynchronous engine */                                      \
   X(async_ring_cap)      /* ticket slots of the asynchronous engine (default 16 per tile and plan; tests force the overflow path) */       \
-  X(nbhd_lds_cap)        /* neighbourhood layers: members per centre in LDS (default 128, 32..512; tests force the spill path) */
+  X(nbhd_lds_cap)        /* neighbourhood layers: members per centre in LDS (default 128, 32..512; tests force the spill path) */ \
+  X(replan_log_cap)      /* replan: entries of the change log (default V; tests force the overflow) */                                    \
+  X(replan_fresh_below)  /* replan: plan afresh when the smallest rewind level / old cut of the batch lies below this fraction (default 0.25; 0: never) */
 
 struct Options {
 #define X(name) double name = NAN;

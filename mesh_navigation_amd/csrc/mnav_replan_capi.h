@@ -1,0 +1,185 @@
+// mnav_replan_capi.h -- the C ABI of the replan (include/mnav.h: mnav_replan_dijkstra_batch, mnav_replan_plans, mnav_replan_stats) over the
+// kernels of mnav_replan.h, the tile rounds and the finalize pass.  Included by mnav.hip inside its extern "C" block, after
+// dijkstra_impl (the fresh path) and its helpers.
+#pragma once
+
+// Default of the option replan_fresh_below.  Measured on the 1M-vertex mesh (profiles/replan_perf.json): below a smallest
+// L / cut_old of 0.25 the fresh plan won for one plan and for 64; one plan alone crosses at 0.50, 64 plans between 0.25 and 0.38.
+constexpr double kReplanFreshBelow = 0.25;
+
+static int replan_reserve(mnav_ctx* ctx, uint32_t m)
+{
+  mnav_ctx::Replan& R = ctx->rp;
+  if (!R.have_ev) {
+    for (auto& e : R.ev) HIPCHK(hipEventCreate(e.out()));
+    R.have_ev = true;
+  }
+  if (m > R.cap) {
+    R.cap = 0;
+    if (alloc_group(R.d_level, 4 * (size_t)m, R.d_old_target, 4 * (size_t)m, R.d_cut, 4 * (size_t)m, R.d_cnt, sizeof(ReplanCnt) * (size_t)m) != hipSuccess) {
+      ctx->err = "replan: out of device memory"; return -1;
+    }
+    R.cap = m;
+  }
+  return 0;
+}
+
+// The repair of the m = n resident fields.  tg: the new robot vertices in the caller's order.  Returns 0 (done, *code set),
+// -1 (error), 1 (cancelled) or 2 (policy: nothing was rewound yet, the caller plans afresh).
+static int replan_repair(mnav_ctx* ctx, uint32_t n, const std::vector<uint32_t>& tg, double offset, uint32_t* codes_out, float* dist_out,
+                         uint32_t* pred_out, uint32_t* path_out, uint32_t path_cap, uint32_t* path_len, uint32_t* code)
+{
+  mnav_ctx::Replan& R = ctx->rp;
+  const uint32_t m = n;
+  std::vector<PlanIn> in(m); std::vector<uint32_t> map(m), old_target(m);
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint32_t k = R.caller_slot[i];
+    PlanIn p{};
+    for (int q = 0; q < 3; ++q) { p.seed[q] = kNone; p.target[q] = kNone; p.seed_d[q] = 0.f; p.seed_expands[q] = 1; p.target_expands[q] = 1; }
+    p.seed[0] = R.seeds[i]; p.target[0] = tg[i]; p.seed_face = kNone;
+    in[k] = p; map[k] = i; old_target[k] = R.targets[i];
+  }
+  ctx->want_vec = ctx->resident_vecmap;
+  ctx->lazy_paths = false;                                            // the finalize pass always runs: predecessors and vector maps are re-derived
+  if (replan_reserve(ctx, m)) return -1;
+  if (materialize(ctx, false, R.cost_limit)) return -1;
+  if (ensure_slots(ctx, m, false, false, ctx->want_vec)) return -1;
+  if (ensure_paths(ctx, m)) return -1;
+  if (ensure_tile_state(ctx, m)) return -1;
+  if (tile_weights(ctx)) return -1;
+  std::vector<Plan> hp; std::vector<TilePlan> tp; std::vector<float*> vecs;
+  (void)hipEventRecord(ctx->ev[0], ctx->stream);
+  if (fill_tile_records(ctx, m, in, offset, hp, tp, vecs)) return -1;
+  HIPCHK(hipMemcpyAsync(R.d_old_target, old_target.data(), 4 * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
+  HIPCHK(hipEventRecord(R.ev[0], ctx->stream));
+  hipLaunchKernelGGL(k_replan_begin, dim3((m + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, ctx->d_tplans, m, R.d_old_target, R.offset,
+                     R.d_level, R.d_cut, R.d_cnt);
+  if (R.len)
+    hipLaunchKernelGGL(k_replan_level, dim3((R.len + kBlock - 1) / kBlock, m), dim3(kBlock), 0, ctx->stream, ctx->d_tplans, R.log, R.len,
+                       ctx->d_row_ptr, ctx->d_nbr_u, R.d_level);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(R.ev[1], ctx->stream));
+  std::vector<float> cut(m);
+  R.levels.assign(m, 0.f);
+  HIPCHK(hipMemcpyAsync(R.levels.data(), R.d_level, 4 * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(cut.data(), R.d_cut, 4 * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));                          // (hp, tp, vecs, old_target are on the device now)
+  const double f = opt_set(ctx->opt.replan_fresh_below) ? ctx->opt.replan_fresh_below : kReplanFreshBelow;
+  if (f > 0.0) {
+    double share = INFINITY;                                          // plans with an infinite old cut do not vote
+    for (uint32_t k = 0; k < m; ++k) if (cut[k] < INFINITY && cut[k] > 0.f) share = std::min(share, (double)R.levels[k] / (double)cut[k]);
+    if (share < f) return 2;
+  }
+  // from here on the fields change: the record of the last call follows
+  ctx->caller_slot = R.caller_slot;                                   // (an inflation wave in between took slot 0's bookkeeping, not its dist)
+  ctx->shard.finalized = false; ctx->tb.count_pending = false; ctx->tb_args_valid = false;
+  ctx->last_planner = kPlannerDijkstra; ctx->last_n = 0; R.usable = false;
+  ctx->last_target.resize(m); for (uint32_t k = 0; k < m; ++k) ctx->last_target[k] = in[k].target[0];
+  ctx->last_offset = offset;
+  hipLaunchKernelGGL(k_replan_rewind, dim3(ctx->tiles_meta.ntiles ? ctx->tiles_meta.ntiles : 1u, m), dim3(kTileBlock), 0, ctx->stream,
+                     ctx->d_tplans, ctx->d_plans, R.d_level, R.d_cnt);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(R.ev[2], ctx->stream));
+  HIPCHK(hipEventRecord(ctx->ev[2], ctx->stream));
+  const int rc = run_tile_rounds(ctx, m);
+  if (rc != 0) { (void)hipStreamSynchronize(ctx->stream); return rc < 0 ? -1 : 1; }
+  HIPCHK(hipEventRecord(R.ev[3], ctx->stream));
+  launch_finalize(ctx, m);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(R.ev[4], ctx->stream));
+  HIPCHK(hipEventRecord(ctx->ev[3], ctx->stream));
+  ctx->last_engine = 0; ctx->last_n = m;
+  std::vector<uint32_t> codes(n, MNAV_SUCCESS);
+  for (uint32_t i = 0; i < n; ++i) if (path_len) path_len[i] = 0;
+  if (dijkstra_tail(ctx, m, 0, map, codes, dist_out, pred_out, path_out, path_cap, path_len, nullptr, ctx->want_vec)) { ctx->last_n = 0; return -1; }
+  std::vector<ReplanCnt> cnt(m);
+  HIPCHK(hipMemcpy(cnt.data(), R.d_cnt, sizeof(ReplanCnt) * (size_t)m, hipMemcpyDeviceToHost));
+  R.kept = R.rewound = 0; R.tiles_woken = 0;
+  for (uint32_t k = 0; k < m; ++k) { R.kept += cnt[k].kept; R.rewound += cnt[k].rewound; R.tiles_woken += cnt[k].woken; }
+  {
+    std::vector<float> lv(m);                                         // levels in the caller's order
+    for (uint32_t k = 0; k < m; ++k) lv[map[k]] = R.levels[k];
+    R.levels.swap(lv);
+  }
+  R.rounds = ctx->stats.launches;
+  R.ms_level = ev_ms(R.ev[0], R.ev[1]); R.ms_rewind = ev_ms(R.ev[1], R.ev[2]); R.ms_rounds = (float)ctx->ms_chunks; R.ms_finalize = ev_ms(R.ev[3], R.ev[4]);
+  R.targets = tg; R.offset = offset; R.usable = true; R.len = 0; R.all = false;   // the change log starts over
+  uint32_t worst = MNAV_SUCCESS;
+  for (uint32_t i = 0; i < n; ++i) {
+    if (codes_out) codes_out[i] = codes[i];
+    if (codes[i] != MNAV_SUCCESS && worst == MNAV_SUCCESS) worst = codes[i];
+  }
+  *code = worst;
+  return 0;
+}
+
+uint32_t mnav_replan_dijkstra_batch(mnav_ctx* ctx, uint32_t n, const uint32_t* targets, double goal_dist_offset, uint32_t* codes_out, float* dist_out,
+                                    uint32_t* pred_out, uint32_t* path_out, uint32_t path_cap, uint32_t* path_len)
+{
+  if (!ctx) return MNAV_INTERNAL_ERROR;
+  mnav_ctx::Replan& R = ctx->rp;
+  // refusals: outputs, change log and replan state stay as they are
+  ctx->err.clear();
+  if (!ctx->have_mesh) { ctx->err = "mnav_upload_mesh has not been called"; return MNAV_INTERNAL_ERROR; }
+  if (goal_dist_offset != goal_dist_offset) { ctx->err = "goal_dist_offset is NaN"; return MNAV_INTERNAL_ERROR; }
+  if (!R.have_call) { ctx->err = "replan: no Dijkstra call to bring up to date (mnav_plan_dijkstra* first)"; return MNAV_INTERNAL_ERROR; }
+  if (n != R.seeds.size()) { ctx->err = "replan: n differs from the last Dijkstra call"; return MNAV_INTERNAL_ERROR; }
+  if (check_ready(ctx)) return MNAV_INTERNAL_ERROR;
+  if (n == 0) return MNAV_SUCCESS;
+  if (hipSetDevice(ctx->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return MNAV_INTERNAL_ERROR; }
+  ctx->cancel.store(0);                                               // a stale flag does not cancel (dijkstra :238)
+  if (ctx->d_cancel) { (void)hipStreamSynchronize(ctx->cancel_stream); (void)hipMemsetAsync(ctx->d_cancel, 0, 4, ctx->stream); }
+  const std::vector<uint32_t> seeds = R.seeds;
+  const std::vector<uint32_t> tg = targets ? std::vector<uint32_t>(targets, targets + n) : R.targets;
+  const uint32_t log_len = R.len;
+  uint32_t reason = 0;
+  if (R.partial && ctx->last_planner == kPlannerDijkstra) reason = 3; // a plan of the last call never reached the device (none of them: no field either)
+  else if (!R.usable || ctx->last_planner != kPlannerDijkstra || ctx->last_n != n || R.caller_slot.size() != n || ctx->slots.size() < n) reason = 1;
+  else if (R.all) reason = 2;
+  else
+    for (uint32_t i = 0; i < n; ++i)
+      if (R.caller_slot[i] >= n || tg[i] >= ctx->V || tg[i] == seeds[i]) { reason = 3; break; }
+  R.reason = reason; R.stat_log_len = log_len; R.kept = R.rewound = 0; R.tiles_woken = R.rounds = 0; R.levels.clear();
+  R.ms_level = R.ms_rewind = R.ms_rounds = R.ms_finalize = 0.f;
+  if (reason == 0) {
+    uint32_t code = MNAV_INTERNAL_ERROR;
+    const int rc = replan_repair(ctx, n, tg, goal_dist_offset, codes_out, dist_out, pred_out, path_out, path_cap, path_len, &code);
+    if (rc == 0) return code;
+    if (rc == 1) {                                                    // cancelled between two chunks of rounds: the fields are half rewound
+      R.usable = false; ctx->last_n = 0;
+      for (uint32_t i = 0; i < n; ++i) if (codes_out) codes_out[i] = MNAV_CANCELED;
+      return MNAV_CANCELED;
+    }
+    if (rc < 0) { R.usable = false; ctx->last_n = 0; (void)hipStreamSynchronize(ctx->stream); return MNAV_INTERNAL_ERROR; }
+    R.reason = 4; R.levels.clear();                                   // policy: plan afresh
+  }
+  // a fresh plan from the recorded seeds, finalize pass included: always a correct answer
+  const bool lazy = ctx->allow_lazy_paths;
+  ctx->allow_lazy_paths = false;
+  const uint32_t rc = dijkstra_impl(ctx, n, seeds.data(), tg.data(), goal_dist_offset, R.cost_limit, codes_out, dist_out, pred_out, path_out, path_cap,
+                                    path_len, nullptr, false);
+  ctx->allow_lazy_paths = lazy;
+  return rc;
+}
+
+uint32_t mnav_replan_plans(const mnav_ctx* ctx) { return ctx && ctx->rp.have_call ? (uint32_t)ctx->rp.seeds.size() : 0u; }
+
+int mnav_replan_stats(const mnav_ctx* ctx, uint32_t* reason, uint32_t* log_len, float* levels_out, uint64_t* kept, uint64_t* rewound,
+                      uint32_t* tiles_woken, uint32_t* rounds, float* ms_level, float* ms_rewind, float* ms_rounds, float* ms_finalize)
+{
+  if (!ctx) return -1;
+  const mnav_ctx::Replan& R = ctx->rp;
+  if (reason) *reason = R.reason;
+  if (log_len) *log_len = R.stat_log_len;
+  if (levels_out) for (size_t i = 0; i < R.levels.size(); ++i) levels_out[i] = R.levels[i];
+  if (kept) *kept = R.kept;
+  if (rewound) *rewound = R.rewound;
+  if (tiles_woken) *tiles_woken = R.tiles_woken;
+  if (rounds) *rounds = R.rounds;
+  if (ms_level) *ms_level = R.ms_level;
+  if (ms_rewind) *ms_rewind = R.ms_rewind;
+  if (ms_rounds) *ms_rounds = R.ms_rounds;
+  if (ms_finalize) *ms_finalize = R.ms_finalize;
+  return 0;
+}

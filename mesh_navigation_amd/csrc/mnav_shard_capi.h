@@ -181,6 +181,7 @@ int mnav_shard_begin(mnav_ctx* ctx, uint32_t seed_vertex, uint32_t target_vertex
   ctx->want_vec = false;
   ctx->tb.count_pending = false; ctx->tb_args_valid = false;         // slot 0 and d_res are taken over by the sharded plan
   ctx->last_planner = kPlannerDijkstra; ctx->last_engine = 0; ctx->last_n = 0; ctx->caller_slot.clear();
+  ctx->rp.usable = ctx->rp.partial = false;                          // slot 0 holds a part of a sharded plan: nothing a replan can rewind
   if (materialize(ctx, false, cost_limit)) return -1;
   if (ensure_slots(ctx, 1, false, false, false)) return -1;
   if (ensure_paths(ctx, 1)) return -1;

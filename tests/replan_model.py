@@ -1,0 +1,268 @@
+"""The replan rule of DESIGN.md §3.11 in numpy, and the scenarios the CPU and the GPU tests share.
+
+Rule: for one resident Dijkstra potential d with old cut `cut_old` (goal_cut of the old robot vertex: every value strictly
+below it is final) and the set C of vertices whose cost, blocked status or incident edge weights may have changed,
+    L = min(cut_old, min over v in C, u in N[v] + {v} of d[u]),
+a vertex is kept iff d < L (the seed always, at 0), everything else goes back to +inf, and float32 relaxations from the
+kept part reach the fixed point of the new map.  tests/test_replan_model.py pins the result to OracleMesh.dijkstra;
+tests/test_gpu_replan.py runs the same scenarios on the device."""
+from __future__ import annotations
+
+import functools
+import heapq
+from dataclasses import dataclass, field
+
+import numpy as np
+
+from mesh_navigation_amd import meshgen
+from oracle import oracle as O
+from tests.common import Case
+
+LIMIT = 1.0
+NONE = 0xFFFFFFFF
+f32 = np.float32
+INF = f32(np.inf)
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+@functools.lru_cache(maxsize=None)
+def terrain(N: int) -> Case:
+    return Case(meshgen.terrain(N, 0.1, N))
+
+
+@functools.lru_cache(maxsize=None)
+def adjacency(N: int):
+    """per vertex: (neighbour, edge id) pairs"""
+    m = terrain(N).mesh
+    adj = [[] for _ in range(m.V)]
+    for e, (a, b) in enumerate(np.asarray(m.edges).reshape(-1, 2)):
+        adj[a].append((int(b), e)); adj[b].append((int(a), e))
+    return adj
+
+
+class World:
+    """A terrain(N) with the cost state both contexts of a GPU test hold.  computed: the weights are derived from the costs
+    with edge_cost_factor 1 (mnav_compute_edge_weights; mnav_update_costs re-weights the incident edges); otherwise they
+    are the caller's (mnav_upload_costs; only mnav_update_edge_weights changes them)."""
+
+    def __init__(self, N: int, computed: bool):
+        self.N, self.computed = N, computed
+        self.case = terrain(N)
+        self.mesh, self.om = self.case.mesh, self.case.om
+        self.costs = (np.random.default_rng(N).random(self.mesh.V) * 0.8).astype(f32)
+        self.weights = self.om.edge_weights(self.case.edge_dist, self.costs, 1.0 if computed else 0.0)
+
+    def v(self, fx, fy):
+        return self.mesh.vertex_at(fx, fy)
+
+    def rect(self, fx, fy, r):
+        """ids of the (2r+1)^2 square around the vertex at (fx, fy), clipped"""
+        N = self.N
+        c = self.v(fx, fy)
+        cx, cy = c % N, c // N
+        return np.array([y * N + x for y in range(max(0, cy - r), min(N, cy + r + 1)) for x in range(max(0, cx - r), min(N, cx + r + 1))], np.uint32)
+
+    def ring(self, fx, fy, r):
+        inner = set(self.rect(fx, fy, r - 1).tolist())
+        return np.array([i for i in self.rect(fx, fy, r).tolist() if i not in inner], np.uint32)
+
+    def column(self, fx, fy0, fy1):
+        N = self.N
+        x = self.v(fx, 0.0) % N
+        return np.array([y * N + x for y in range(int(fy0 * N), int(fy1 * N))], np.uint32)
+
+    def edges_at(self, ids):
+        ids = set(int(i) for i in ids)
+        return np.array(sorted({e for v in ids for _, e in adjacency(self.N)[v]}), np.uint32)
+
+    def apply(self, ev):
+        """one event on the model's state; returns the vertex ids the context logs for it"""
+        kind, ids, vals = ev
+        ids = np.asarray(ids, np.uint32)
+        vals = np.broadcast_to(np.asarray(vals, f32), ids.shape)
+        if kind == "costs":
+            self.costs = self.costs.copy(); self.costs[ids] = vals
+            if self.computed:
+                self.weights = self.om.edge_weights(self.case.edge_dist, self.costs, 1.0)
+            return ids
+        assert kind == "edges"
+        self.weights = self.weights.copy(); self.weights[ids] = vals
+        return np.asarray(self.mesh.edges, np.uint32).reshape(-1, 2)[ids].ravel()
+
+    # -- the same state on a device context
+    def upload(self, ctx, tile=None):
+        if tile:
+            ctx.set_option("tile_size", tile)
+        ctx.upload_mesh(self.mesh.xyz, self.mesh.faces, self.mesh.edges, self.case.vn)
+        if self.computed:
+            ctx.compute_edge_weights(self.costs, self.case.edge_dist, 1.0)
+        else:
+            ctx.upload_costs(self.costs, self.weights)
+
+    @staticmethod
+    def send(ctx, ev):
+        kind, ids, vals = ev
+        ids = np.asarray(ids, np.uint32)
+        vals = np.ascontiguousarray(np.broadcast_to(np.asarray(vals, f32), ids.shape))
+        (ctx.update_costs if kind == "costs" else ctx.update_edge_weights)(ids, vals)
+
+
+# -- the rule ---------------------------------------------------------------------------------------------------------
+def old_cut(dist, target, offset) -> np.float32:
+    return f32(O.product_expanded_sources(dist, int(target), float(offset))[2])
+
+
+def level(N, dist, C, cut):
+    adj = adjacency(N)
+    L = f32(cut)
+    for v in np.asarray(C, np.int64):
+        L = min(L, dist[v], *[dist[u] for u, _ in adj[v]])
+    return f32(L)
+
+
+def keep_mask(dist, L, seed):
+    k = dist < L
+    k[seed] = True
+    return k
+
+
+def replan(world: World, dist_old, seed, target_old, offset_old, C, target, offset):
+    """(code, dist, pred, path, info) of the replan on world's CURRENT state from the old potential"""
+    N, adj, w, costs = world.N, adjacency(world.N), world.weights, world.costs
+    V = dist_old.shape[0]
+    cut0 = old_cut(dist_old, target_old, offset_old)
+    L = level(N, dist_old, C, cut0)
+    keep = keep_mask(dist_old, L, seed)
+    d = np.where(keep, dist_old, INF).astype(f32)
+    d[seed] = f32(0)
+    info = dict(level=L, cut_old=cut0, kept=int(keep.sum()), rewound=int((~keep & np.isfinite(dist_old)).sum()), reached=int(np.isfinite(dist_old).sum()))
+    # float32 relaxations from the kept part to the fixed point, under the running bound dist[target] + max(offset, 0)
+    heap = [(float(d[v]), int(v)) for v in np.flatnonzero(keep)]
+    heapq.heapify(heap)
+    while heap:
+        val, v = heapq.heappop(heap)
+        if f32(val) != d[v]:
+            continue
+        bound = f32(np.float64(d[target]) + max(offset, 0.0)) if np.isfinite(d[target]) else INF
+        if f32(val) > bound:
+            break
+        if float(costs[v]) > LIMIT:
+            continue                                                   # reached, never expanded (dijkstra :302)
+        for u, e in adj[v]:
+            s = f32(d[v] + w[e])
+            if s < d[u]:
+                d[u] = s
+                heapq.heappush(heap, (float(s), u))
+    # the reference's cut-off semantics: values beyond the cut come from expanded sources only; predecessor = the
+    # first-popped expanded neighbour that attains the value
+    exp, goal, cut = O.product_expanded_sources(d, int(target), float(offset))
+    exp = exp & ~(costs.astype(np.float64) > LIMIT)
+    out = d.copy()
+    pred = np.arange(V, dtype=np.uint32)
+    for v in range(V):
+        if v == seed:
+            continue
+        if not d[v] <= f32(cut):
+            out[v] = min([INF] + [f32(d[u] + w[e]) for u, e in adj[v] if exp[u]])
+        if np.isfinite(out[v]):
+            cand = [(d[u], u) for u, e in adj[v] if exp[u] and f32(d[u] + w[e]) == out[v]]
+            if cand:
+                pred[v] = min(cand)[1]
+    path = []
+    code = 54 if pred[target] == target else 0
+    if code == 0:
+        x = int(target)
+        while x != seed:
+            x = int(pred[x]); path.append(x)
+        path.reverse()
+    return code, out, pred, np.array(path, np.uint32), info
+
+
+# -- the scenarios ----------------------------------------------------------------------------------------------------
+@dataclass
+class Step:
+    events: list                     # ("costs", vertex ids, value(s)) | ("edges", edge ids, value(s))
+    targets: list | None             # new robot vertices, or None (unchanged)
+    offset: float
+    expect: str                      # "partial": 0 < rewound < reached; "cut": the level is the old cut; "all": only the seed is kept; "any"
+    codes: list | None = None        # expected codes (default: success)
+
+
+@dataclass
+class Scenario:
+    name: str
+    N: int
+    tile: int | None
+    computed: bool
+    seeds: list
+    targets: list
+    offset: float
+    steps: list = field(default_factory=list)
+    engine: str = "auto"
+    fields: bool = True              # the first call asks for dist / pred (False: a paths-only call)
+    reason: int = 0                  # what the first replan reports
+
+
+def _wall(W, name, N, tile, offset=0.3):
+    s, t = W.v(0.15, 0.5), W.v(0.7, 0.5)
+    wall = W.column(0.6, 0.3, 0.7)
+    back = W.costs[wall].copy()
+    return Scenario(name, N, tile, W.computed, [s], [t], offset, [
+        Step([("costs", wall, 1.5)], None, offset, "partial"),        # over the limit: the path goes round
+        Step([("costs", wall, back)], None, offset, "partial")])      # a decrease
+
+
+def scenarios():
+    out = []
+    A, B, U = World(48, True), World(96, True), World(48, False)
+    out.append(_wall(A, "wall48", 48, 64))
+    out.append(_wall(B, "wall96", 96, None))
+    for off in (0.0, -0.2, 1e9):
+        out.append(_wall(A, "wall48_offset%g" % off, 48, 64, off))
+    # 2: cost-only changes, weights derived on the device; uploaded weights changed by edge id
+    s, t = A.v(0.15, 0.5), A.v(0.7, 0.5)
+    patch = A.rect(0.55, 0.4, 3)
+    out.append(Scenario("costs48", 48, 64, True, [s], [t], 0.3, [Step([("costs", patch, 0.95)], None, 0.3, "partial"),
+                                                                Step([("costs", patch, 0.0)], None, 0.3, "partial")]))
+    eids = U.edges_at(U.rect(0.55, 0.4, 2))
+    out.append(Scenario("edges48", 48, 64, False, [s], [t], 0.3, [Step([("edges", eids, U.weights[eids] * f32(3))], None, 0.3, "partial"),
+                                                                 Step([("edges", eids, U.weights[eids] * f32(0.25))], None, 0.3, "partial")]))
+    # 3: an event wholly beyond the old cut; an event on a neighbour of the seed
+    s9, t9 = B.v(0.15, 0.5), B.v(0.5, 0.5)
+    out.append(Scenario("beyond96", 96, None, True, [s9], [t9], 0.3, [Step([("costs", B.rect(0.97, 0.97, 1), 1.5)], None, 0.3, "cut"),
+                                                                     Step([("costs", [s9 + 1], 0.9)], None, 0.3, "all")]))
+    # 4: the target alone -- nearer, farther, into the unreached region, the same again
+    out.append(Scenario("targets48", 48, 64, False, [s], [U.v(0.6, 0.5)], 0.3, [Step([], [U.v(0.4, 0.5)], 0.3, "cut"), Step([], [U.v(0.8, 0.5)], 0.3, "cut"),
+                                                                               Step([], [U.v(0.98, 0.98)], 0.3, "cut"), Step([], None, 0.3, "cut")]))
+    # 5: the target walled in, then freed
+    ring = A.ring(0.7, 0.5, 2)
+    out.append(Scenario("walled48", 48, 64, True, [s], [t], 0.3, [Step([("costs", ring, 1.5)], None, 0.3, "partial", [54]),
+                                                                 Step([("costs", ring, A.costs[ring].copy())], None, 0.3, "partial")]))
+    # 7: batches
+    sd = [B.v(0.1, 0.1), B.v(0.9, 0.2), B.v(0.5, 0.5), B.v(0.2, 0.8), B.v(0.85, 0.85)]
+    tg = [B.v(0.6, 0.5), B.v(0.4, 0.6), B.v(0.8, 0.3), B.v(0.6, 0.4), B.v(0.4, 0.5)]
+    tg2 = [B.v(0.65, 0.55), B.v(0.4, 0.6), B.v(0.7, 0.35), B.v(0.5, 0.5), B.v(0.45, 0.45)]
+    ev = [("costs", B.rect(0.55, 0.5, 2), 1.5)]
+    out.append(Scenario("batch5", 96, None, True, sd, tg, 0.3, [Step(ev, tg2, 0.3, "partial")]))
+    out.append(Scenario("shared3", 96, None, True, [sd[0]] * 3, tg[:3], 0.3, [Step(ev, tg2[:3], 0.3, "partial")]))
+    rng = np.random.default_rng(170)
+    s170, t170 = rng.integers(0, A.mesh.V, 170), rng.integers(0, A.mesh.V, 170)
+    t170 = np.where(t170 == s170, (t170 + 7) % A.mesh.V, t170)
+    ev48 = [("costs", A.rect(0.5, 0.5, 2), 1.5)]
+    out.append(Scenario("batch170", 48, 64, True, s170.tolist(), t170.tolist(), 0.3, [Step(ev48, None, 0.3, "any")], engine="tile_batch"))
+    out.append(Scenario("pathsonly_async", 96, None, True, sd, tg, 0.3, [Step(ev, tg2, 0.3, "partial")], engine="async", fields=False))
+    out.append(Scenario("pathsonly_tile_batch", 48, 64, True, s170.tolist(), t170.tolist(), 0.3, [Step(ev48, None, 0.3, "any")], engine="tile_batch",
+                        fields=False, reason=1))
+    # 9: a chain on terrain(160): four events, a replan after each
+    C = World(160, True)
+    sc, tc = C.v(0.2, 0.5), C.v(0.75, 0.5)
+    wall = C.column(0.6, 0.35, 0.65)
+    out.append(Scenario("chain160", 160, None, True, [sc], [tc], 0.3, [
+        Step([("costs", wall, 1.5)], None, 0.3, "partial"),
+        Step([], [C.v(0.7, 0.55)], 0.3, "cut"),
+        Step([("costs", C.rect(0.5, 0.45, 4), 0.0)], [C.v(0.65, 0.6)], 0.3, "partial"),
+        Step([("costs", wall, C.costs[wall].copy())], None, 0.0, "partial")]))
+    return out
