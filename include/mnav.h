@@ -556,6 +556,74 @@ int mnav_follow_rollout(mnav_ctx* ctx, uint32_t n, const float* pos, const float
 int mnav_rollout_stats(const mnav_ctx* ctx, uint32_t* status_counts, uint64_t* robot_ticks, uint64_t* stayed, uint64_t* neighbour,
                        uint64_t* global, uint32_t* built_index, float* ms_kernels, float* ms_total);
 
+/* -- fleet paths and walks: many robots per resident field ---------------------------------------------
+ * A Dijkstra call returns one vertex path per plan, from the plan's seed (the goal) to its one target.  The field is seeded
+ * at the goal, so it already holds the path of every robot inside it: mnav_fleet_paths hands Move Base Flex's setPlan a
+ * vertex path for n robots over the fields the last Dijkstra call (mnav_plan_dijkstra, _batch, _batch_at) or the last
+ * mnav_replan_dijkstra_batch left resident, without another wave and without a V-sized array crossing PCIe. */
+#define MNAV_BEYOND_FIELD 70u   /* not an mbf code: the resident field cannot answer for this robot; plan or replan */
+/* Robot i uses plan slots[i] (plan index of that call; robots may share one) and stands on vertex start_vertex[i] or, when
+ * start_vertex is NULL, on the vertex nearest to start_pos[i] by the rule of mnav_locate (the ids stay on the device).
+ * With d / p the plan's resident dist / pred, g its seed, t its target, offset and cost_limit those of the call and
+ * cut = float(d[t] + offset) (d[t] itself when that rounds below d[t]; +inf when d[t] is), the first match decides:
+ *   1  v >= V (an id out of range, MNAV_NONE, a position without a vertex): MNAV_INVALID_GOAL, as in mnav_plan_dijkstra_batch_at
+ *   2  the plan never reached the device (rejected ids, seed == target): the plan's own code, length 0
+ *      CAUTION: a plan whose seed is its target never runs and its own code is MNAV_SUCCESS, so EVERY robot on that slot gets
+ *      MNAV_SUCCESS with length 0 wherever it stands; only a robot on the seed has reached the goal.  Such a robot is told
+ *      apart by potential_out == +inf (rule 3 gives 0): check it, or put no robot other than the plan's own on such a slot
+ *   3  v == g: MNAV_SUCCESS, length 0, potential 0
+ *   4  d[v] < cut, or v == t: p[v] == v: MNAV_NO_PATH_FOUND; otherwise MNAV_SUCCESS, the path p[v], p[p[v]], ..., g written
+ *      in the reference's list order (seed first ... pred[v]) and potential_out[i] = d[v]; a chain that does not reach g
+ *      within V hops: MNAV_INTERNAL_ERROR
+ *   5  d[v] == +inf and the wave ran out (cut == +inf, or no vertex of the plan holds a finite value at or above the cut, so
+ *      every vertex the wave reached was expanded): MNAV_NO_PATH_FOUND, v is not connected to g
+ *   6  otherwise MNAV_BEYOND_FIELD, length 0: the tentative ring at or above the cut and the vertices the wave never
+ *      reached before it stopped; the caller plans for this robot, or replans with a larger offset
+ * For every robot that gets MNAV_SUCCESS or MNAV_NO_PATH_FOUND by rules 4 and 5 the code, the ids and the potential are bit
+ * for bit what mnav_plan_dijkstra_batch(seed = g, target = v) returns with the recorded offset and cost_limit on the
+ * resident map.  The call may say MNAV_BEYOND_FIELD where a fresh plan would succeed; it never
+ * returns another path than the fresh plan's.  potential_out is +inf wherever rules 3 and 4 do not set it.
+ * Output: paths packed back to back; offset_out (n + 1) = the exclusive prefix sum of len_out in robot order,
+ * offset_out[n] = *total_out; robot i's ids are ids_out[offset_out[i] .. offset_out[i] + len_out[i]).  vertex_out: the
+ * vertex each robot was given or found on.  Any output pointer may be NULL; n = 0 does nothing.
+ * Returns 0 when everything was written; 1 when *total_out > ids_cap or ids_out is NULL: all per-robot outputs and
+ * total_out are valid then and ids_out is untouched -- size the buffer and call again; -1 with mnav_last_error set and
+ * NOTHING touched: no mesh or costs, the last plan call was not a Dijkstra call or replan, a slot that is not a plan of
+ * it, a slot whose predecessors are not resident (a paths-only call: mnav_device_output(slot, 1) == NULL; a sharded,
+ * failed or cancelled call; the band-step engine, whose predecessors are not pinned), neither start_vertex nor
+ * start_pos, or a cost-changing call since the plan (the replan's change log is not empty, or a writer replaced whole
+ * arrays): the field no longer belongs to the resident map -- replan first.  The call changes no plan output, no layer
+ * and no statistic of another entry point; with positions it builds the lookup index of mnav_locate when none exists
+ * yet (mnav_locate_stats then reports built = 1). */
+int mnav_fleet_paths(mnav_ctx* ctx, uint32_t n, const uint32_t* slots, const uint32_t* start_vertex, const float* start_pos,
+                     uint32_t* code_out, uint32_t* vertex_out, float* potential_out, uint32_t* len_out, uint64_t* offset_out,
+                     uint32_t* ids_out, uint64_t ids_cap, uint64_t* total_out);
+/* The walk of mnav_backtrack_cvp_batch for many robots per field: robot i walks over the vector map resident for plan
+ * slots[i] of the last plan call (CVP or Dijkstra, the rule of mnav_follow_batch) from start_pos[i] on start_faces[i]
+ * (start_faces NULL: the containing face by the rule of mnav_locate; start_face_out receives the faces used) to
+ * seed_pos[slots[i]] on seed_faces[slots[i]].  n_plans must equal the plan count of the last call.  status_out[i]: 1, 0,
+ * -1, -2 as in mnav_backtrack_cvp_batch (reached; no path, also when walk_cap is hit; a vertex without an inflation
+ * entry; internal list overflow); -3: no face at the
+ * start (MNAV_NONE, or a position without one), length 0; 0 with length 0: a plan that never reached the device.  Rows
+ * come out seed first and packed (3 floats in positions_out and one id in faces_out per entry), offset_out / total_out
+ * and the return values 0 / 1 (entries_cap too small, or positions_out and faces_out both NULL) as in mnav_fleet_paths.
+ * Robots are walked in chunks whose scratch rows of walk_cap entries stay within the option fleet_scratch_mb (default
+ * 256 MiB); the result does not depend on it, and walk_cap * n is not bounded.
+ * Returns -1 with mnav_last_error set and NOTHING touched: no mesh, a null slots / seed / start_pos array, walk_cap
+ * outside 2 .. 2^24, a step_width that is not positive, n_plans different from the last call's, a slot out of range, a
+ * used slot whose vector map is not resident or whose seed face is out of range, a start face >= F that is not
+ * MNAV_NONE, an inflation_layer >= 0 that is no resident inflation layer with a vector field. */
+int mnav_fleet_walks(mnav_ctx* ctx, uint32_t n, const uint32_t* slots, uint32_t n_plans, const float* seed_pos,
+                     const uint32_t* seed_faces, const float* start_pos, const uint32_t* start_faces, double step_width,
+                     int32_t inflation_layer, uint32_t walk_cap, int32_t* status_out, uint32_t* start_face_out, uint32_t* len_out,
+                     uint64_t* offset_out, float* positions_out, uint32_t* faces_out, uint64_t entries_cap, uint64_t* total_out);
+/* The last mnav_fleet_paths or mnav_fleet_walks: robots served (MNAV_SUCCESS / status 1), beyond the field, without a path
+ * (MNAV_NO_PATH_FOUND / every other walk status but -3) and invalid (every other code / status -3); path ids or walk
+ * entries summed; built_index = 1 if the call built the lookup index; chunks of a walk call; device milliseconds of its
+ * kernels and host milliseconds of the whole call.  Any pointer may be NULL. */
+int mnav_fleet_stats(const mnav_ctx* ctx, uint32_t* served, uint32_t* beyond_field, uint32_t* no_path, uint32_t* invalid,
+                     uint64_t* entries, uint32_t* built_index, uint32_t* chunks, float* ms_kernels, float* ms_total);
+
 /* -- one plan over several GPUs (BASELINE config 4) ---------------------------------------------
  * The reference's loop (dijkstra_mesh_planner.cpp:287-348) on a mesh that is range-partitioned over `world`
  * processes, one per GPU: the LDS tiles are in Morton order and process `rank` owns a contiguous range of them.

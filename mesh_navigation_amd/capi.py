@@ -18,6 +18,8 @@ from . import build as _build
 
 NONE = 0xFFFFFFFF
 SUCCESS, CANCELED, INVALID_START, INVALID_GOAL, NO_PATH_FOUND, INTERNAL_ERROR = 0, 51, 52, 53, 54, 60
+BEYOND_FIELD = 70           # mnav_fleet_paths: the resident field cannot answer for this robot
+WALK_NO_FACE = -3           # mnav_fleet_walks: no face at the start
 
 # every symbol include/mnav.h declares
 SYMBOLS = [
@@ -35,6 +37,7 @@ SYMBOLS = [
     "mnav_follow_batch", "mnav_follow_stats", "mnav_follow_rollout", "mnav_rollout_stats",
     "mnav_map_configure", "mnav_map_compute", "mnav_map_layer_changed", "mnav_map_update_layer", "mnav_map_obstacle", "mnav_map_stats",
     "mnav_replan_dijkstra_batch", "mnav_replan_plans", "mnav_replan_stats",
+    "mnav_fleet_paths", "mnav_fleet_walks", "mnav_fleet_stats",
     "mnav_set_option", "mnav_get_option", "mnav_shard_set_goal_tie", "mnav_last_engine",
 ]
 
@@ -301,6 +304,12 @@ def load(path: str | None = None):
     L.mnav_algorithmic_bytes.argtypes = [vp]
     L.mnav_last_engine.restype = C.c_int
     L.mnav_last_engine.argtypes = [vp]
+    L.mnav_fleet_paths.restype = C.c_int
+    L.mnav_fleet_paths.argtypes = [vp, u32] + [vp] * 9 + [C.c_uint64, vp]
+    L.mnav_fleet_walks.restype = C.c_int
+    L.mnav_fleet_walks.argtypes = [vp, u32, vp, u32, vp, vp, vp, vp, f64, C.c_int32, u32] + [vp] * 6 + [C.c_uint64, vp]
+    L.mnav_fleet_stats.restype = C.c_int
+    L.mnav_fleet_stats.argtypes = [vp] + [C.POINTER(u32)] * 4 + [C.POINTER(C.c_uint64)] + [C.POINTER(u32)] * 2 + [C.POINTER(C.c_float)] * 2
     if path is None:
         _lib = L
     return L
@@ -918,6 +927,91 @@ class MnavContext:
             self._L.mnav_replan_stats(self._h, None, None, _p(lv), *([None] * 8))
         return dict(reason=r.value, log_len=ll.value, levels=lv, kept=k.value, rewound=w.value, tiles_woken=tw.value, rounds=rd.value,
                     ms_level=ms[0].value, ms_rewind=ms[1].value, ms_rounds=ms[2].value, ms_finalize=ms[3].value)
+
+    def fleet_paths(self, slots, start_vertex=None, start_pos=None, ids_cap: int | None = None) -> dict:
+        """Vertex paths of n robots out of the resident fields of the last Dijkstra call or replan (mnav_fleet_paths,
+        include/mnav.h): robot i stands on start_vertex[i] (or on the vertex nearest to start_pos[i]) of plan slots[i].
+        Returns dict(rc, codes, vertex, potential, path_len, offsets, ids, total): the ids of robot i are
+        ids[offsets[i]:offsets[i + 1]], seed first.  Without ids_cap the call sizes the buffer itself (two calls); with it,
+        rc = 1 and ids = None tell that `total` ids did not fit."""
+        sl = _u32(slots).reshape(-1)
+        n = int(sl.shape[0])
+        sv = None if start_vertex is None else _u32(start_vertex).reshape(-1)
+        sp = None if start_pos is None else _f32(start_pos).reshape(-1, 3)
+        if (sv is not None and sv.shape[0] != n) or (sv is None and sp is not None and sp.shape[0] != n):
+            raise ValueError("fleet_paths: the per-robot arrays differ in length")
+        codes, vtx, lens = (np.zeros(n, np.uint32) for _ in range(3))
+        pot = np.zeros(n, np.float32)
+        off = np.zeros(n + 1, np.uint64)
+        total = C.c_uint64(0)
+
+        def call(ids, cap):
+            rc = self._L.mnav_fleet_paths(self._h, n, _p(sl), _p(sv), _p(sp), _p(codes), _p(vtx), _p(pot), _p(lens), _p(off), _p(ids), int(cap), C.byref(total))
+            if rc < 0:
+                raise RuntimeError(f"mnav_fleet_paths failed: {self._err()}")
+            return rc
+
+        ids = None
+        if ids_cap is None:
+            rc = call(None, 0) if n else 0
+            ids = np.empty(int(total.value), np.uint32)
+            if n and ids.size:
+                rc = call(ids, ids.size)
+            elif n:
+                rc = 0
+        else:
+            ids = np.empty(int(ids_cap), np.uint32)
+            rc = call(ids, ids.size) if n else 0
+            ids = ids[: int(total.value)] if rc == 0 else None
+        return dict(rc=rc, codes=codes, vertex=vtx, potential=pot, path_len=lens, offsets=off, ids=ids, total=int(total.value))
+
+    def fleet_walks(self, slots, seed_pos, seed_faces, start_pos, start_faces=None, step_width: float = 0.4, inflation_layer: int = -1,
+                    walk_cap: int = 4096, entries_cap: int | None = None) -> dict:
+        """The back-tracking walk for n robots over the resident vector maps of the last plan call (mnav_fleet_walks,
+        include/mnav.h): robot i walks from start_pos[i] to the seed end of plan slots[i].  seed_pos / seed_faces: one row
+        per plan of that call.  Returns dict(rc, status, start_face, path_len, offsets, positions, faces, total), rows seed
+        first: positions[offsets[i]:offsets[i + 1]].  Without entries_cap a first call without row buffers sizes
+        them (the walks run twice; no buffer is larger than the result); with it, one call: rc = 1 and positions = None
+        tell that `total` entries did not fit."""
+        sl = _u32(slots).reshape(-1)
+        n = int(sl.shape[0])
+        sp, sf = _f32(seed_pos).reshape(-1, 3), _u32(seed_faces).reshape(-1)
+        tp = _f32(start_pos).reshape(-1, 3)
+        tf = None if start_faces is None else _u32(start_faces).reshape(-1)
+        if sp.shape[0] != sf.shape[0] or tp.shape[0] != n or (tf is not None and tf.shape[0] != n):
+            raise ValueError("fleet_walks: array lengths differ")
+        st = np.zeros(n, np.int32)
+        face0, lens = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        off = np.zeros(n + 1, np.uint64)
+        total = C.c_uint64(0)
+
+        def call(pos, face, cap):
+            rc = self._L.mnav_fleet_walks(self._h, n, _p(sl), int(sf.shape[0]), _p(sp), _p(sf), _p(tp), _p(tf), float(step_width), int(inflation_layer),
+                                          int(walk_cap), _p(st), _p(face0), _p(lens), _p(off), _p(pos), _p(face), int(cap), C.byref(total)) if n else 0
+            if rc < 0:
+                raise RuntimeError(f"mnav_fleet_walks failed: {self._err()}")
+            return rc
+
+        if entries_cap is None:
+            call(None, None, 0)                                              # sizing only: statuses, lengths, total
+            cap = int(total.value)
+        else:
+            cap = int(entries_cap)
+        pos, face = np.empty((max(cap, 1), 3), np.float32), np.empty(max(cap, 1), np.uint32)
+        rc = call(pos, face, cap)
+        t = int(total.value)
+        return dict(rc=rc, status=st, start_face=face0, path_len=lens, offsets=off, positions=pos[:t] if rc == 0 else None,
+                    faces=face[:t] if rc == 0 else None, total=t)
+
+    def fleet_stats(self) -> dict:
+        """The last fleet_paths / fleet_walks call (mnav_fleet_stats)."""
+        v = [C.c_uint32() for _ in range(4)]
+        e = C.c_uint64()
+        b, ch = C.c_uint32(), C.c_uint32()
+        mk, mt = C.c_float(), C.c_float()
+        self._L.mnav_fleet_stats(self._h, *[C.byref(x) for x in v], C.byref(e), C.byref(b), C.byref(ch), C.byref(mk), C.byref(mt))
+        names = ("served", "beyond_field", "no_path", "invalid")
+        return dict(**{k: x.value for k, x in zip(names, v)}, entries=e.value, built_index=b.value, chunks=ch.value, ms_kernels=mk.value, ms_total=mt.value)
 
     def plan_cvp_batch(self, seed_pos, seed_faces, target_faces, goal_dist_offset: float = 0.3, cost_limit: float = 1.0,
                        want_fields: bool = False, want_vecmap: bool = False):

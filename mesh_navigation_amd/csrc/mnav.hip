@@ -109,6 +109,7 @@ __global__ __launch_bounds__(64) void k_backtrack(WalkMesh M, WalkInflation L, c
                                 step_width, cap, pos_out + 3 * (size_t)cap * j, face_out + (size_t)cap * j, &n, list);
   ctl[2 * j] = st; ctl[2 * j + 1] = (int32_t)n;
 }
+#include "mnav_fleet.h"      // fleet paths and walks: many robots per resident field (mnav_fleet::; after the locate and follow headers, and after WalkJob)
 namespace {
 
 struct Slot {
@@ -220,6 +221,7 @@ struct mnav_ctx {
   mnav_clr::State clr;                                             // clearance / border layers: cached clearance (first clearance call after an upload)
   mnav_loc::State loc;                                             // pose lookup: vertex index built by the first mnav_locate after an upload
   mnav_fol::State fol;                                             // vector-field follower: buffers and counters of the last mnav_follow_batch
+  mnav_fleet::State fleet;                                         // fleet paths / walks: buffers and statistics of the last mnav_fleet_* call
   mnav_rol::Dev rol;                                               // device rollout: resident robot state and statistics of the last mnav_follow_rollout
   mnav_chg::Scratch chg;                                           // obstacle / clearance / border layers: change list and counters of the last call
   mnav_map::State map;                                             // resident layer graph (mnav_map_*): nodes, tables, change lists of the last update
@@ -1758,6 +1760,7 @@ uint32_t mnav_plan_cvp_batch(mnav_ctx* ctx, uint32_t n, const float* seed_pos, c
 #include "mnav_rollout_capi.h"    // mnav_follow_rollout, mnav_rollout_stats
 #include "mnav_graph_capi.h"      // mnav_map_configure / _compute / _layer_changed / _update_layer / _obstacle / _stats
 #include "mnav_replan_capi.h"     // mnav_replan_dijkstra_batch, mnav_replan_stats
+#include "mnav_fleet_capi.h"      // mnav_fleet_paths, mnav_fleet_walks, mnav_fleet_stats
 
 void mnav_cancel(mnav_ctx* ctx)
 {

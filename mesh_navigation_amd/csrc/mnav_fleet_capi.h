@@ -1,0 +1,290 @@
+// mnav_fleet_capi.h -- the C ABI of the fleet calls (include/mnav.h: mnav_fleet_paths, mnav_fleet_walks, mnav_fleet_stats)
+// over the kernels of mnav_fleet.h, the lookup of mnav_locate_capi.h and k_backtrack.  Included by mnav.hip inside its
+// extern "C" block, after mnav_replan_capi.h.
+#pragma once
+
+static_assert(mnav_fleet::kSuccess == MNAV_SUCCESS && mnav_fleet::kInvalidStart == MNAV_INVALID_START && mnav_fleet::kInvalidGoal == MNAV_INVALID_GOAL &&
+              mnav_fleet::kNoPath == MNAV_NO_PATH_FOUND && mnav_fleet::kInternal == MNAV_INTERNAL_ERROR && mnav_fleet::kBeyond == MNAV_BEYOND_FIELD,
+              "mnav_fleet.h restates the codes of include/mnav.h");
+
+constexpr double kFleetScratchMb = 256.0;   // default of the option fleet_scratch_mb
+
+static int fleet_reserve(mnav_ctx* ctx, size_t n, size_t n_slots)
+{
+  mnav_fleet::State& S = ctx->fleet;
+  if (!S.have_ev) {
+    for (auto& e : S.ev) HIPCHK(hipEventCreate(e.out()));
+    S.have_ev = true;
+  }
+  if (!S.cnt) HIPCHK(S.cnt.alloc(sizeof(uint32_t) * (mnav_fleet::kCounters + 1)));
+  if (n > S.cap) {
+    S.cap = 0;
+    const size_t nb = (n + mnav_fleet::kFleetBlock - 1) / mnav_fleet::kFleetBlock;
+    if (alloc_group(S.slot, 4 * n, S.vtx, 4 * n, S.code, 4 * n, S.len, 4 * n, S.face, 4 * n, S.potential, 4 * n, S.pos, 12 * n, S.status, 4 * n, S.bsum, 8 * nb,
+                    S.off, 8 * (n + 1)) != hipSuccess) { ctx->err = "fleet: out of device memory"; return -1; }
+    S.cap = n;
+  }
+  if (n_slots > S.slots_cap) {
+    S.slots_cap = 0;
+    if (alloc_group(S.fields, sizeof(mnav_fleet::Field) * n_slots, S.wslots, sizeof(mnav_fleet::WalkSlot) * n_slots, S.need, 8 * n_slots) !=
+        hipSuccess) {   // (need: a word per plan, then k_fleet_open's answers)
+      ctx->err = "fleet: out of device memory"; return -1;
+    }
+    S.slots_cap = n_slots;
+  }
+  return 0;
+}
+
+// the lookup of n positions for a fleet call: results stay in ctx->loc (q, vtx, face); of the lookup's own statistics only
+// `built` may change (the lazy index build is reported as the lookup's, as the follower does)
+static int fleet_locate(mnav_ctx* ctx, uint32_t n, const float* pos)
+{
+  mnav_loc::State& L = ctx->loc;
+  const uint32_t built = L.built; const float ms_query = L.ms_query; const uint64_t candidates = L.candidates;
+  if (locate_run(ctx, n, pos, 0, nullptr)) return -1;
+  ctx->fleet.built_index = L.built;
+  if (!L.built) L.built = built;
+  L.ms_query = ms_query; L.candidates = candidates;
+  return 0;
+}
+
+static void fleet_clear_stats(mnav_fleet::State& S)
+{
+  for (uint32_t& c : S.outcome) c = 0;
+  S.built_index = 0; S.chunks = 0; S.entries = 0; S.ms_kernels = S.ms_total = 0.f;
+}
+
+int mnav_fleet_paths(mnav_ctx* ctx, uint32_t n, const uint32_t* slots, const uint32_t* start_vertex, const float* start_pos, uint32_t* code_out,
+                     uint32_t* vertex_out, float* potential_out, uint32_t* len_out, uint64_t* offset_out, uint32_t* ids_out, uint64_t ids_cap,
+                     uint64_t* total_out)
+{
+  using namespace mnav_fleet;
+  if (!ctx) return -1;
+  ctx->err.clear();
+  if (!n) return 0;
+  const auto t0 = std::chrono::steady_clock::now();
+  // every refusal comes before the first device call: a refused call touches nothing
+  if (!slots) { ctx->err = "fleet paths: null slots"; return -1; }
+  if (!start_vertex && !start_pos) { ctx->err = "fleet paths: neither start vertices nor start positions"; return -1; }
+  if (check_ready(ctx)) return -1;
+  if (n > 0x7FFFFFFFu) { ctx->err = "fleet paths: too many robots in one call"; return -1; }
+  const mnav_ctx::Replan& R = ctx->rp;
+  const size_t n_slots = R.seeds.size();
+  if (!R.have_call || ctx->last_planner != kPlannerDijkstra || ctx->caller_slot != R.caller_slot || R.caller_slot.size() != n_slots || R.targets.size() != n_slots) {
+    ctx->err = "fleet paths: the last plan call was not a Dijkstra call or replan whose fields are resident"; return -1;
+  }
+  if (R.len || R.all) { ctx->err = "fleet paths: the costs changed since the plan (mnav_replan_dijkstra_batch first)"; return -1; }
+  std::vector<uint8_t> used(n_slots ? n_slots : 1, 0);
+  for (uint32_t i = 0; i < n; ++i) {
+    if (slots[i] >= n_slots) { ctx->err = "fleet paths: slot out of range (not a plan of the last call)"; return -1; }
+    used[slots[i]] = 1;
+  }
+  std::vector<Field> fields(n_slots);
+  for (size_t s = 0; s < n_slots; ++s) {
+    Field Fd; Fd.dist = nullptr; Fd.pred = nullptr; Fd.seed = R.seeds[s]; Fd.target = R.targets[s]; Fd.cut = INFINITY;
+    Fd.code = R.seeds[s] >= ctx->V ? MNAV_INVALID_START : R.targets[s] >= ctx->V ? MNAV_INVALID_GOAL : MNAV_SUCCESS;   // what the plan call gave a plan it did not run
+    if (used[s] && R.caller_slot[s] != kNone) {
+      // R.usable is the replan's record of "slots[k].dist is the reference's below the cut" (not after the band steps, a failed or cancelled
+      // call, a half-rewound replan); on top of it the predecessors must be resident, which a paths-only call does not leave
+      Fd.dist = static_cast<const float*>(mnav_device_output(ctx, (uint32_t)s, 0));
+      Fd.pred = static_cast<const uint32_t*>(mnav_device_output(ctx, (uint32_t)s, 1));
+      if (!R.usable || !Fd.dist || !Fd.pred) {
+        ctx->err = "fleet paths: predecessors of slot " + std::to_string(s) + " not resident (a paths-only, band-step, failed or cancelled call)"; return -1;
+      }
+    }
+    fields[s] = Fd;
+  }
+  if (hipSetDevice(ctx->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return -1; }
+  if (fleet_reserve(ctx, n, n_slots)) return -1;
+  State& S = ctx->fleet;
+  fleet_clear_stats(S);
+  const uint32_t* d_vtx = S.vtx;
+  if (start_vertex) HIPCHK(hipMemcpyAsync(S.vtx, start_vertex, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  else { if (fleet_locate(ctx, n, start_pos)) return -1; d_vtx = ctx->loc.vtx; }   // the ids stay on the device
+  HIPCHK(hipMemcpyAsync(S.slot, slots, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(S.fields, fields.data(), sizeof(Field) * n_slots, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemsetAsync(S.cnt, 0, sizeof(uint32_t) * (kCounters + 1), ctx->stream));
+  HIPCHK(hipMemsetAsync(S.need, 0, 8 * n_slots, ctx->stream));
+  Paths P{};
+  P.n = n; P.V = ctx->V; P.slot = S.slot; P.vtx = d_vtx; P.fields = S.fields; P.code = S.code; P.len = S.len; P.potential = S.potential; P.bsum = S.bsum; P.cnt = S.cnt;
+  P.mark = S.status; P.need = S.need;
+  const uint32_t nb = (n + kFleetBlock - 1) / kFleetBlock;
+  HIPCHK(hipEventRecord(S.ev[0], ctx->stream));
+  hipLaunchKernelGGL(k_fleet_cut, dim3(((uint32_t)n_slots + kFleetBlock - 1) / kFleetBlock), dim3(kFleetBlock), 0, ctx->stream, (uint32_t)n_slots, S.fields.get(), R.offset);
+  hipLaunchKernelGGL(k_fleet_len, dim3(nb), dim3(kFleetBlock), 0, ctx->stream, P);
+  hipLaunchKernelGGL(k_fleet_scan, dim3(1), dim3(kFleetBlock), 0, ctx->stream, nb, S.bsum.get(), (const unsigned long long*)nullptr, S.off + n);
+  hipLaunchKernelGGL(k_fleet_offsets, dim3(nb), dim3(kFleetBlock), 0, ctx->stream, n, S.len.get(), S.bsum.get(), S.off.get());
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(S.ev[1], ctx->stream));
+  unsigned long long total = 0; uint32_t cnt[kCounters + 1] = {};
+  HIPCHK(hipMemcpyAsync(&total, S.off + n, sizeof(total), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(cnt, S.cnt, sizeof(cnt), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  S.ms_kernels = ev_ms(S.ev[0], S.ev[1]);
+  if (cnt[kCounters]) {                                               // robots the wave never reached under a finite cut: did their plans' waves run out? (rule 5)
+    HIPCHK(hipEventRecord(S.ev[0], ctx->stream));
+    hipLaunchKernelGGL(k_fleet_open, dim3((uint32_t)n_slots * kOpenBlocks), dim3(kFleetBlock), 0, ctx->stream, (uint32_t)n_slots, ctx->V, S.fields.get(), S.need.get(),
+                       S.need + n_slots);
+    hipLaunchKernelGGL(k_fleet_resolve, dim3(nb), dim3(kFleetBlock), 0, ctx->stream, P, S.need + n_slots);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(S.ev[1], ctx->stream));
+    HIPCHK(hipMemcpyAsync(cnt, S.cnt, sizeof(cnt), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    S.ms_kernels += ev_ms(S.ev[0], S.ev[1]);
+  }
+  const bool fits = ids_out && total <= ids_cap;
+  if (fits && total) {
+    if (total > S.ids_cap) {
+      S.ids_cap = 0;
+      if (S.ids.alloc(4 * (size_t)total) != hipSuccess) { ctx->err = "fleet paths: out of device memory"; return -1; }
+      S.ids_cap = total;
+    }
+    HIPCHK(hipEventRecord(S.ev[0], ctx->stream));
+    hipLaunchKernelGGL(k_fleet_write, dim3(nb), dim3(kFleetBlock), 0, ctx->stream, P, S.off.get(), S.ids.get());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(S.ev[1], ctx->stream));
+    HIPCHK(hipMemcpyAsync(ids_out, S.ids, 4 * (size_t)total, hipMemcpyDeviceToHost, ctx->stream));   // one dense copy
+  }
+  if (code_out) HIPCHK(hipMemcpyAsync(code_out, S.code, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  if (vertex_out) HIPCHK(hipMemcpyAsync(vertex_out, d_vtx, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  if (potential_out) HIPCHK(hipMemcpyAsync(potential_out, S.potential, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  if (len_out) HIPCHK(hipMemcpyAsync(len_out, S.len, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  if (offset_out) HIPCHK(hipMemcpyAsync(offset_out, S.off, 8 * ((size_t)n + 1), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (fits && total) S.ms_kernels += ev_ms(S.ev[0], S.ev[1]);
+  if (total_out) *total_out = total;
+  for (int k = 0; k < kCounters; ++k) S.outcome[k] = cnt[k];
+  S.entries = total;
+  S.ms_total = (float)(1e-3 * (double)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count());
+  return fits ? 0 : 1;
+}
+
+int mnav_fleet_walks(mnav_ctx* ctx, uint32_t n, const uint32_t* slots, uint32_t n_plans, const float* seed_pos, const uint32_t* seed_faces,
+                     const float* start_pos, const uint32_t* start_faces, double step_width, int32_t inflation_layer, uint32_t walk_cap,
+                     int32_t* status_out, uint32_t* start_face_out, uint32_t* len_out, uint64_t* offset_out, float* positions_out, uint32_t* faces_out,
+                     uint64_t entries_cap, uint64_t* total_out)
+{
+  using namespace mnav_fleet;
+  if (!ctx) return -1;
+  ctx->err.clear();
+  if (!n) return 0;
+  const auto t0 = std::chrono::steady_clock::now();
+  // every refusal comes before the first device call: a refused call touches nothing
+  if (!slots || !seed_pos || !seed_faces || !start_pos) { ctx->err = "fleet walks: null argument"; return -1; }
+  if (!ctx->have_mesh) { ctx->err = "mnav_upload_mesh has not been called"; return -1; }
+  if (n > 0x7FFFFFFFu) { ctx->err = "fleet walks: too many robots in one call"; return -1; }
+  if (walk_cap < 2 || walk_cap > (1u << 24)) { ctx->err = "fleet walks: walk_cap out of range (2 .. 2^24)"; return -1; }
+  if (!(step_width > 0.0)) { ctx->err = "step_width must be positive"; return -1; }   // a zero step never leaves the start
+  if (n_plans != ctx->caller_slot.size()) { ctx->err = "fleet walks: n_plans differs from the last plan call"; return -1; }
+  std::vector<uint8_t> used(n_plans ? n_plans : 1, 0);
+  for (uint32_t i = 0; i < n; ++i) {
+    if (slots[i] >= n_plans) { ctx->err = "fleet walks: slot out of range (not a plan of the last call)"; return -1; }
+    if (start_faces && start_faces[i] != kNone && start_faces[i] >= ctx->F) { ctx->err = "fleet walks: face id out of range"; return -1; }
+    used[slots[i]] = 1;
+  }
+  std::vector<WalkSlot> ws(n_plans);
+  for (uint32_t s = 0; s < n_plans; ++s) {
+    WalkSlot W{};
+    W.vecmap = nullptr; W.seed_face = kNone;
+    if (used[s] && ctx->caller_slot[s] != kNone) {                    // (a plan rejected before it reached the device: status 0, no entries)
+      W.vecmap = static_cast<const float*>(mnav_device_output(ctx, s, 4));
+      if (!W.vecmap) { ctx->err = "fleet walks: vector map of slot " + std::to_string(s) + " not resident (mnav_set_resident_outputs, or pass vecmap_out to the plan call)"; return -1; }
+      if (seed_faces[s] >= ctx->F) { ctx->err = "fleet walks: seed face id out of range"; return -1; }
+      W.seed_face = seed_faces[s];
+      for (int k = 0; k < 3; ++k) W.seed[k] = seed_pos[3 * (size_t)s + k];
+    }
+    ws[s] = W;
+  }
+  WalkInflation L{};
+  if (inflation_layer >= 0) {
+    if ((size_t)inflation_layer >= ctx->layers.size() || !ctx->layers[inflation_layer].ready || !ctx->layers[inflation_layer].dist || !ctx->layers[inflation_layer].have_vec) {
+      ctx->err = "fleet walks: not a resident inflation layer with a vector field"; return -1;
+    }
+    const mnav_ctx::Layer& Ly = ctx->layers[inflation_layer];
+    L.distances = Ly.dist; L.vectors = Ly.vec; L.has_vector = Ly.vstate;
+    L.inflation_radius = Ly.inflation_radius; L.inscribed_radius = Ly.inscribed_radius; L.inscribed_value = Ly.inscribed_value; L.lethal_value = Ly.lethal_value;
+    L.repulsive_field = 1;
+  }
+  if (hipSetDevice(ctx->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return -1; }
+  if (upload_walk_mesh(ctx)) return -1;
+  if (fleet_reserve(ctx, n, n_plans)) return -1;
+  State& S = ctx->fleet;
+  fleet_clear_stats(S);
+  // scratch rows of walk_cap entries (16 bytes each) for one chunk of robots
+  const double mb = opt_set(ctx->opt.fleet_scratch_mb) && ctx->opt.fleet_scratch_mb > 0.0 ? ctx->opt.fleet_scratch_mb : kFleetScratchMb;
+  const double fit = std::floor(mb * 1048576.0 / (16.0 * (double)walk_cap));
+  const uint32_t chunk = (uint32_t)std::min<double>((double)n, std::max(1.0, fit));
+  if (chunk > S.rows || walk_cap > S.row_entries) {
+    S.rows = S.row_entries = 0;
+    if (alloc_group(S.jobs, sizeof(WalkJob) * (size_t)chunk, S.ctl, 8 * (size_t)chunk, S.row_pos, 12 * (size_t)chunk * walk_cap, S.row_face, 4 * (size_t)chunk * walk_cap) !=
+        hipSuccess) { ctx->err = "fleet walks: out of device memory"; return -1; }
+    S.rows = chunk; S.row_entries = walk_cap;
+  }
+  const bool want = positions_out || faces_out;
+  const unsigned long long out_cap = want ? std::min<unsigned long long>(entries_cap, (unsigned long long)n * walk_cap) : 0ull;
+  if (out_cap > S.out_cap) {
+    S.out_cap = 0;
+    if (alloc_group(S.out_pos, 12 * (size_t)out_cap, S.out_face, 4 * (size_t)out_cap) != hipSuccess) { ctx->err = "fleet walks: out of device memory"; return -1; }
+    S.out_cap = out_cap;
+  }
+  const float* d_pos = S.pos; const uint32_t* d_face = S.face;
+  if (start_faces) {
+    HIPCHK(hipMemcpyAsync(S.pos, start_pos, 12 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(S.face, start_faces, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  } else { if (fleet_locate(ctx, n, start_pos)) return -1; d_pos = ctx->loc.q; d_face = ctx->loc.face; }   // positions and faces stay on the device
+  HIPCHK(hipMemcpyAsync(S.slot, slots, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(S.wslots, ws.data(), sizeof(WalkSlot) * (size_t)n_plans, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemsetAsync(S.cnt, 0, sizeof(uint32_t) * kCounters, ctx->stream));
+  const WalkMesh M{ ctx->d_xyz, ctx->d_faces, ctx->d_vf_ptr, ctx->d_vf, ctx->V, ctx->F };
+  HIPCHK(hipEventRecord(S.ev[0], ctx->stream));
+  for (uint32_t a = 0; a < n; a += chunk) {                           // the chunks follow each other in stream order: one set of scratch rows
+    const uint32_t c = std::min(chunk, n - a), nb = (c + kFleetBlock - 1) / kFleetBlock;
+    hipLaunchKernelGGL(k_fleet_jobs, dim3(nb), dim3(kFleetBlock), 0, ctx->stream, c, ctx->F, S.slot + a, S.wslots.get(), d_pos + 3 * (size_t)a, d_face + a, S.jobs.get());
+    hipLaunchKernelGGL(k_backtrack, dim3(c), dim3(64), 0, ctx->stream, M, L, S.jobs.get(), step_width, walk_cap, S.row_pos.get(), S.row_face.get(), S.ctl.get());
+    hipLaunchKernelGGL(k_fleet_walk_len, dim3(nb), dim3(kFleetBlock), 0, ctx->stream, c, ctx->F, d_face + a, S.ctl.get(), S.status + a, S.len + a, S.bsum.get(), S.cnt.get());
+    hipLaunchKernelGGL(k_fleet_scan, dim3(1), dim3(kFleetBlock), 0, ctx->stream, nb, S.bsum.get(), a ? S.off + a : (const unsigned long long*)nullptr, S.off + a + c);
+    hipLaunchKernelGGL(k_fleet_offsets, dim3(nb), dim3(kFleetBlock), 0, ctx->stream, c, S.len + a, S.bsum.get(), S.off + a);
+    if (out_cap)
+      hipLaunchKernelGGL(k_fleet_pack, dim3(c), dim3(64), 0, ctx->stream, walk_cap, S.row_pos.get(), S.row_face.get(), S.len + a, S.off + a, S.out_pos.get(), S.out_face.get(), out_cap);
+    HIPCHK(hipGetLastError());
+    ++S.chunks;
+  }
+  HIPCHK(hipEventRecord(S.ev[1], ctx->stream));
+  unsigned long long total = 0; uint32_t cnt[kCounters] = {};
+  HIPCHK(hipMemcpyAsync(&total, S.off + n, sizeof(total), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(cnt, S.cnt, sizeof(cnt), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  S.ms_kernels = ev_ms(S.ev[0], S.ev[1]);
+  const bool fits = want && total <= entries_cap;
+  if (fits && total) {                                                // two dense copies
+    if (positions_out) HIPCHK(hipMemcpyAsync(positions_out, S.out_pos, 12 * (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
+    if (faces_out) HIPCHK(hipMemcpyAsync(faces_out, S.out_face, 4 * (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  if (status_out) HIPCHK(hipMemcpyAsync(status_out, S.status, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  if (start_face_out) HIPCHK(hipMemcpyAsync(start_face_out, d_face, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  if (len_out) HIPCHK(hipMemcpyAsync(len_out, S.len, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  if (offset_out) HIPCHK(hipMemcpyAsync(offset_out, S.off, 8 * ((size_t)n + 1), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (total_out) *total_out = total;
+  for (int k = 0; k < kCounters; ++k) S.outcome[k] = cnt[k];
+  S.entries = total;
+  S.ms_total = (float)(1e-3 * (double)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count());
+  return fits ? 0 : 1;
+}
+
+int mnav_fleet_stats(const mnav_ctx* ctx, uint32_t* served, uint32_t* beyond_field, uint32_t* no_path, uint32_t* invalid, uint64_t* entries,
+                     uint32_t* built_index, uint32_t* chunks, float* ms_kernels, float* ms_total)
+{
+  if (!ctx) return -1;
+  const mnav_fleet::State& S = ctx->fleet;
+  if (served) *served = S.outcome[0];
+  if (beyond_field) *beyond_field = S.outcome[1];
+  if (no_path) *no_path = S.outcome[2];
+  if (invalid) *invalid = S.outcome[3];
+  if (entries) *entries = S.entries;
+  if (built_index) *built_index = S.built_index;
+  if (chunks) *chunks = S.chunks;
+  if (ms_kernels) *ms_kernels = S.ms_kernels;
+  if (ms_total) *ms_total = S.ms_total;
+  return 0;
+}
