@@ -220,9 +220,10 @@ struct mnav_ctx {
   mnav_nb::State nbhd;                                             // neighbourhood layers: counters, spill lists and scratch of the last call
   mnav_clr::State clr;                                             // clearance / border layers: cached clearance (first clearance call after an upload)
   mnav_loc::State loc;                                             // pose lookup: vertex index built by the first mnav_locate after an upload
-  mnav_fol::State fol;                                             // vector-field follower: buffers and counters of the last mnav_follow_batch
+  mnav_fol::Staging stage;                                         // follower and rollout: the per-robot inputs of the running call, the two work lists
+  mnav_fol::State fol;                                             // vector-field follower: outputs and counters of the last mnav_follow_batch
   mnav_fleet::State fleet;                                         // fleet paths / walks: buffers and statistics of the last mnav_fleet_* call
-  mnav_rol::Dev rol;                                               // device rollout: resident robot state and statistics of the last mnav_follow_rollout
+  mnav_rol::Dev rol;                                               // device rollout: the rest of the resident robot state and statistics of the last mnav_follow_rollout
   mnav_chg::Scratch chg;                                           // obstacle / clearance / border layers: change list and counters of the last call
   mnav_map::State map;                                             // resident layer graph (mnav_map_*): nodes, tables, change lists of the last update
   uint32_t infl_steps = 0, infl_bands = 0; uint64_t infl_evals = 0; float infl_ms = 0.f, infl_ms_wave = 0.f;   // last inflation wave

@@ -27,12 +27,14 @@
 //     plan's seed face always count as having one (mnav::WalkField, as for the back-tracking walk).
 //
 // Device shape: the common tick is a robot still on its face -- one barycentric test and a dozen loads -- so pass A
-// (k_follow_stay) gives every robot ONE LANE: step 2 and the whole tail.  Robots that need a search are compacted into
-// two work lists with wave-aggregated atomics.  Pass B (k_follow_search) gives each listed robot a WAVE for the
+// (fol_pass_stay) gives every robot ONE LANE: step 2 and the whole tail.  Robots that need a search are compacted into
+// two work lists with wave-aggregated atomics.  Pass B (fol_pass_search) gives each listed robot a WAVE for the
 // breadth-first neighbour search (mnav_walk.h's wave version, list in LDS) and hands failures on to the second list.
-// Pass C (k_follow_global) runs the exact nearest-vertex descent of mnav_locate.h, one lane per listed robot, and is the
-// only pass that needs the lookup index: the host reads the two list lengths once after pass B and builds the index
-// only if the second list is not empty.  A robot's outputs are written by exactly one pass, to its own row.
+// Pass C (fol_pass_global) runs the exact nearest-vertex descent of mnav_locate.h, one lane per listed robot, and is the
+// only pass that needs the lookup index.  A robot's row is written by exactly one pass.  The three passes are written
+// once, as templates over the robots they serve, for two callers: this file's one-tick call (k_follow_*: the Result is
+// stored as the robot's output row; the host reads the two list lengths once after pass B and builds the index only if
+// the second list is not empty) and the rollout's tick (mnav_rollout.h, k_rollout_*).
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -156,32 +158,47 @@ inline Result fol_tick(const WalkMesh& M, const mnav_loc::Index& I, Stack& st, c
 
 #if defined(__HIPCC__)
 
-// one batch on the device: inputs, the per-slot vector maps, one output row per robot, the two work lists and
-// cnt[0] / cnt[1] = their lengths, cnt[2..6] = robots that stayed / found a neighbour face / were found by a global
-// search / are out of the map / have no field
-struct Batch {
+// Both callers run the three passes below: the one-tick call (Batch, this file) and the rollout's tick (mnav_rol::Tick).
+// What a pass knows of its robots is a small policy struct Q, passed by value.  Its base is Robots; beside that it has
+//   bool first(ic, face, pos)   the first loads of row ic (a clamped index: see pass A); false: the robot has no tick
+//   void idle(i, pos)           what a robot without a tick still gets
+//   Row load(i, face, pos)      the whole row, given its first loads: pos, dir, up, face and whatever finish needs beside them
+//   int finish(i, row, R)       what becomes of the tick's Result; returns how the tick ended (kEnd*)
+// Nothing in a pass branches on the caller: the policy is the only difference.
+struct Robots {
   uint32_t n;
-  const float* pos; const float* dir; const float* up; const uint32_t* face_in; const uint32_t* slot; const uint32_t* seed_face;   // seed_face: may be null
+  const uint32_t* slot; const uint32_t* seed_face;                    // seed_face: may be null
   const float* const* vecmaps; const float* costs;
-  int32_t* code; uint32_t* face; float* bary; float* pos_out; float* mesh_dir; float* cost; double* cmd; int32_t* how;
-  uint32_t* nb_list; uint32_t* gl_list; uint32_t* cnt;
+  uint32_t* nb_list; uint32_t* gl_list; uint32_t* cnt;                // the two work lists; cnt: this tick's counter row
 };
+// A counter row: the two lists' lengths, then the robots that stayed / found a neighbour face / were found by a global
+// search, and those whose tick ended reached / out of the map / without a field (1 + kEnd*)
 constexpr int kCounters = 8;
 constexpr int kStayBlock = 256;
+enum : int { kEndRunning = 0, kEndReached = 1, kEndOutOfMap = 2, kEndNoField = 3 };   // = MNAV_ROLLOUT_*; the one-tick call never reaches
 
-__device__ __forceinline__ WalkField fol_field_of(const Batch& B, const WalkMesh& M, uint32_t i)
-{
-  return fol_field(M, B.vecmaps[B.slot[i]], B.seed_face ? B.seed_face[i] : kNone);
-}
+// one batch of the one-tick call: inputs and one output row per robot
+struct Batch : Robots {
+  const float* pos; const float* dir; const float* up; const uint32_t* face_in;
+  int32_t* code; uint32_t* face; float* bary; float* pos_out; float* mesh_dir; float* cost; double* cmd; int32_t* how;
 
-__device__ __forceinline__ void fol_store(const Batch& B, uint32_t i, const Result& R)
-{
-  B.code[i] = R.code; B.how[i] = R.how; B.face[i] = R.face; B.cost[i] = R.cost;
-  for (int k = 0; k < 3; ++k) B.bary[3 * (size_t)i + k] = R.bary[k];
-  B.pos_out[3 * (size_t)i] = R.pos.x; B.pos_out[3 * (size_t)i + 1] = R.pos.y; B.pos_out[3 * (size_t)i + 2] = R.pos.z;
-  B.mesh_dir[3 * (size_t)i] = R.mesh_dir.x; B.mesh_dir[3 * (size_t)i + 1] = R.mesh_dir.y; B.mesh_dir[3 * (size_t)i + 2] = R.mesh_dir.z;
-  B.cmd[2 * (size_t)i] = R.lin; B.cmd[2 * (size_t)i + 1] = R.ang;
-}
+  struct Row { W3 pos, dir, up; uint32_t face; };
+  __device__ __forceinline__ bool first(uint32_t ic, uint32_t& f, W3& p) const { f = face_in[ic]; p = mnav::w3_load(pos + 3 * (size_t)ic); return true; }
+  __device__ __forceinline__ void idle(uint32_t, W3) const {}
+  __device__ __forceinline__ Row load(uint32_t i, uint32_t f, W3 p) const
+  {
+    return Row{ p, mnav::w3_load(dir + 3 * (size_t)i), mnav::w3_load(up + 3 * (size_t)i), f };
+  }
+  __device__ __forceinline__ int finish(uint32_t i, const Row&, const Result& R) const
+  {
+    code[i] = R.code; how[i] = R.how; face[i] = R.face; cost[i] = R.cost;
+    for (int k = 0; k < 3; ++k) bary[3 * (size_t)i + k] = R.bary[k];
+    pos_out[3 * (size_t)i] = R.pos.x; pos_out[3 * (size_t)i + 1] = R.pos.y; pos_out[3 * (size_t)i + 2] = R.pos.z;
+    mesh_dir[3 * (size_t)i] = R.mesh_dir.x; mesh_dir[3 * (size_t)i + 1] = R.mesh_dir.y; mesh_dir[3 * (size_t)i + 2] = R.mesh_dir.z;
+    cmd[2 * (size_t)i] = R.lin; cmd[2 * (size_t)i + 1] = R.ang;
+    return R.code == kOk ? kEndRunning : 1 + R.code;
+  }
+};
 
 // append i to a work list for the lanes that `want`: one atomic per wave (the whole wave must call this)
 __device__ __forceinline__ void fol_push(uint32_t* list, uint32_t* len, bool want, uint32_t i)
@@ -196,90 +213,127 @@ __device__ __forceinline__ void fol_push(uint32_t* list, uint32_t* len, bool wan
 }
 
 // the outcome counters of the robots a wave finished (the whole wave must call this)
-__device__ __forceinline__ void fol_count(uint32_t* cnt, bool done, int code, int how)
+__device__ __forceinline__ void fol_count(uint32_t* cnt, bool done, int how, int end)
 {
-  const unsigned long long b[5] = { __ballot(done && how == kHowStay), __ballot(done && how == kHowNeighbour),
-                                    __ballot(done && (how == kHowFirst || how == kHowGlobal)), __ballot(done && code == kOutOfMap),
-                                    __ballot(done && code == kNoField) };
+  const unsigned long long b[6] = { __ballot(done && how == kHowStay), __ballot(done && how == kHowNeighbour),
+                                    __ballot(done && (how == kHowFirst || how == kHowGlobal)), __ballot(done && end == kEndReached),
+                                    __ballot(done && end == kEndOutOfMap), __ballot(done && end == kEndNoField) };
   if ((threadIdx.x & 63u) == 0)
-    for (int k = 0; k < 5; ++k) if (b[k]) atomicAdd(&cnt[2 + k], (uint32_t)__popcll(b[k]));
+    for (int k = 0; k < 6; ++k) if (b[k]) atomicAdd(&cnt[2 + k], (uint32_t)__popcll(b[k]));
 }
 
-// Pass A: one lane per robot
-__global__ __launch_bounds__(kStayBlock) void k_follow_stay(Batch B, WalkMesh M, Config C)
+// the tail on robot i's row (f0, p: its first loads) once its face is known, and what the caller makes of it; returns how
+// the tick ended
+template <class Q>
+__device__ __forceinline__ int fol_resolve(const Q& B, const WalkMesh& M, const Config& C, uint32_t i, uint32_t f0, W3 p, uint32_t face, const float bary[3],
+                                           int how, bool project)
+{
+  auto S = B.load(i, f0, p);
+  const WalkField Fd = fol_field(M, B.vecmaps[B.slot[i]], B.seed_face ? B.seed_face[i] : kNone);
+  return B.finish(i, S, fol_finish(M, Fd, B.costs, C, S.pos, S.dir, S.up, face, bary, how, project));
+}
+
+// Pass A: one lane per robot (kStayBlock per workgroup).  The row's first loads are written at a clamped index, outside
+// the bounds test; the row is completed from them, so nothing is read twice.
+template <class Q>
+__device__ __forceinline__ void fol_pass_stay(const Q& B, const WalkMesh& M, const Config& C)
 {
   const uint32_t i = blockIdx.x * kStayBlock + threadIdx.x;
-  int route = 0, code = kOk, how = kHowNone;                          // route 1: neighbour search, 2: global search
+  uint32_t f; W3 p;
+  const bool live = B.first(i < B.n ? i : B.n - 1, f, p);
+  int route = 0, end = kEndRunning;                                   // route 1: neighbour search, 2: global search
+  bool done = false;
   if (i < B.n) {
-    const uint32_t f = B.face_in[i];
-    if (f == kNone) route = 2;
-    else {
-      const W3 p = mnav::w3_load(B.pos + 3 * (size_t)i);
-      float bary[3];
-      if (fol_stay(M, p, f, C.max_search_distance, bary)) {
-        const Result R = fol_finish(M, fol_field_of(B, M, i), B.costs, C, p, mnav::w3_load(B.dir + 3 * (size_t)i), mnav::w3_load(B.up + 3 * (size_t)i), f,
-                                    bary, kHowStay, false);
-        fol_store(B, i, R);
-        code = R.code; how = R.how;
-      } else route = 1;
-    }
+    float bary[3];
+    if (!live) B.idle(i, p);
+    else if (f == kNone) route = 2;
+    else if (fol_stay(M, p, f, C.max_search_distance, bary)) { end = fol_resolve(B, M, C, i, f, p, f, bary, kHowStay, false); done = true; }
+    else route = 1;
   }
   fol_push(B.nb_list, &B.cnt[0], route == 1, i);
   fol_push(B.gl_list, &B.cnt[1], route == 2, i);
-  fol_count(B.cnt, i < B.n && route == 0, code, how);
+  fol_count(B.cnt, done, kHowStay, end);
 }
 
-// Pass B: one wave per listed robot (grid-stride over the list, whose length pass A left in cnt[0])
-__global__ __launch_bounds__(64) void k_follow_search(Batch B, WalkMesh M, Config C)
+// Pass B: one wave per listed robot (grid-stride over the list, whose length pass A left in cnt[0]); list: kWalkScratchWords of LDS
+template <class Q>
+__device__ __forceinline__ void fol_pass_search(const Q& B, const WalkMesh& M, const Config& C, uint32_t* list)
 {
-  __shared__ uint32_t list[mnav::kWalkScratchWords];
   const uint32_t n_nb = B.cnt[0] < B.n ? B.cnt[0] : B.n;
   for (uint32_t j = blockIdx.x; j < n_nb; j += gridDim.x) {
     const uint32_t i = B.nb_list[j];
-    const W3 p = mnav::w3_load(B.pos + 3 * (size_t)i);
+    uint32_t f; W3 p;
+    B.first(i, f, p);                                                 // (its answer is not needed: a listed robot has a tick)
     float bary[3];
     int status = mnav::kWalkLost;
-    const uint32_t nf = mnav::walk_search_faces(M, p, B.face_in[i], (float)C.max_search_radius, (float)C.max_search_distance, bary, list, &status);
+    const uint32_t nf = mnav::walk_search_faces(M, p, f, (float)C.max_search_radius, (float)C.max_search_distance, bary, list, &status);
     if (threadIdx.x == 0) {
-      if (nf == kNone) B.gl_list[atomicAdd(&B.cnt[1], 1u)] = i;       // (a robot is listed at most once: the list holds n)
+      if (nf == kNone) B.gl_list[atomicAdd(&B.cnt[1], 1u)] = i;       // (a robot is listed at most once per tick: the list holds n)
       else {
-        const Result R = fol_finish(M, fol_field_of(B, M, i), B.costs, C, p, mnav::w3_load(B.dir + 3 * (size_t)i), mnav::w3_load(B.up + 3 * (size_t)i), nf,
-                                    bary, kHowNeighbour, true);
-        fol_store(B, i, R);
+        const int end = fol_resolve(B, M, C, i, f, p, nf, bary, kHowNeighbour, true);
         atomicAdd(&B.cnt[3], 1u);
-        if (R.code == kNoField) atomicAdd(&B.cnt[6], 1u);
+        if (end != kEndRunning) atomicAdd(&B.cnt[4 + end], 1u);       // (a face was found: reached or no field)
       }
     }
     __syncthreads();                                                  // the next search reuses the list
   }
 }
 
-// Pass C: one lane per robot of the second list (n_gl: its length, read by the host after pass B)
+// Pass C: one lane per robot of the second list, whose length n_gl is final when pass B has ended: grid-stride in whole
+// waves, so that the counters' ballots see every lane; s_node / s_bound: the lookup's LDS stacks
+template <class Q>
+__device__ __forceinline__ void fol_pass_global(const Q& B, const WalkMesh& M, const Config& C, const mnav_loc::Index& I, uint32_t n_gl, uint32_t* s_node,
+                                                float* s_bound)
+{
+  const uint32_t lane = threadIdx.x;
+  for (uint32_t base = blockIdx.x * mnav_loc::kLocBlock; base < n_gl; base += gridDim.x * mnav_loc::kLocBlock) {
+    const uint32_t j = base + lane;
+    int how = kHowNone, end = kEndRunning;
+    if (j < n_gl) {
+      uint64_t cand = 0;                                              // (distances evaluated: the lookup's statistic, not kept here)
+      const uint32_t i = B.gl_list[j];
+      uint32_t f; W3 p;
+      B.first(i, f, p);                                               // (as in pass B)
+      auto S = B.load(i, f, p);
+      mnav_loc::LdsStack st{ s_node, s_bound, lane, 0 };
+      const WalkField Fd = fol_field(M, B.vecmaps[B.slot[i]], B.seed_face ? B.seed_face[i] : kNone);
+      const Result R = fol_global(M, I, st, Fd, B.costs, C, S.pos, S.dir, S.up, S.face == kNone ? kHowFirst : kHowGlobal, &cand);
+      end = B.finish(i, S, R);
+      how = R.how;
+    }
+    fol_count(B.cnt, j < n_gl, how, end);
+  }
+}
+
+__global__ __launch_bounds__(kStayBlock) void k_follow_stay(Batch B, WalkMesh M, Config C) { fol_pass_stay(B, M, C); }
+
+__global__ __launch_bounds__(64) void k_follow_search(Batch B, WalkMesh M, Config C)
+{
+  __shared__ uint32_t list[mnav::kWalkScratchWords];
+  fol_pass_search(B, M, C, list);
+}
+
+// (n_gl: the second list's length, read by the host after pass B; the grid is exact, so the loop runs once)
 __global__ __launch_bounds__(mnav_loc::kLocBlock) void k_follow_global(Batch B, WalkMesh M, Config C, mnav_loc::Index I, uint32_t n_gl)
 {
   __shared__ uint32_t s_node[mnav_loc::kStack * mnav_loc::kLocBlock];
   __shared__ float s_bound[mnav_loc::kStack * mnav_loc::kLocBlock];
-  const uint32_t lane = threadIdx.x;
-  const uint32_t j = blockIdx.x * mnav_loc::kLocBlock + lane;
-  int code = kOk, how = kHowNone;
-  if (j < n_gl) {
-    uint64_t cand = 0;                                                // (distances evaluated: the lookup's statistic, not kept here)
-    const uint32_t i = B.gl_list[j];
-    mnav_loc::LdsStack st{ s_node, s_bound, lane, 0 };
-    const Result R = fol_global(M, I, st, fol_field_of(B, M, i), B.costs, C, mnav::w3_load(B.pos + 3 * (size_t)i), mnav::w3_load(B.dir + 3 * (size_t)i),
-                                mnav::w3_load(B.up + 3 * (size_t)i), B.face_in[i] == kNone ? kHowFirst : kHowGlobal, &cand);
-    fol_store(B, i, R);
-    code = R.code; how = R.how;
-  }
-  fol_count(B.cnt, j < n_gl, code, how);
+  fol_pass_global(B, M, C, I, n_gl, s_node, s_bound);
 }
 
-// buffers of the last call (grown on demand, kept between calls) and its counters
-struct State {
-  mnav::DevBuf<float> pos, dir, up, bary, pos_out, mesh_dir, cost; mnav::DevBuf<double> cmd;
-  mnav::DevBuf<uint32_t> face_in, slot, seed_face, face, nb_list, gl_list, cnt; mnav::DevBuf<int32_t> code, how;
-  mnav::DevBuf<const float*> vecmaps; size_t cap = 0, slots_cap = 0;
+// The per-robot inputs of a follower call or a rollout on the device, the two work lists and the events around the
+// passes: grown on demand, kept between calls, owned once by the context.  The two calls may share them because each
+// uploads every input at entry, and a rollout is continued through the caller's arrays, never through what a call left
+// here (the rollout advances pos, dir and face in place).
+struct Staging {
+  mnav::DevBuf<float> pos, dir, up; mnav::DevBuf<uint32_t> face, slot, seed_face, nb_list, gl_list; mnav::DevBuf<const float*> vecmaps;
+  size_t cap = 0, slots_cap = 0;
   mnav::Event ev[4]; bool have_ev = false;
+};
+
+// outputs of the last call (grown on demand, kept between calls) and its counters
+struct State {
+  mnav::DevBuf<float> bary, pos_out, mesh_dir, cost; mnav::DevBuf<double> cmd; mnav::DevBuf<uint32_t> face, cnt; mnav::DevBuf<int32_t> code, how; size_t cap = 0;
   uint32_t stayed = 0, neighbour = 0, global = 0, lost = 0, no_field = 0, built_index = 0; float ms_kernels = 0.f, ms_total = 0.f;
 };
 

@@ -34,25 +34,54 @@ static int follow_check(mnav_ctx* ctx, uint32_t n, const float* pos, const float
   return 0;
 }
 
-static int follow_reserve(mnav_ctx* ctx, size_t n, size_t n_slots)
+// the context's staging for n robots over n_slots plans (mnav_fol::Staging); `what`: the caller's name in the refusal
+static int staging_reserve(mnav_ctx* ctx, size_t n, size_t n_slots, const char* what)
+{
+  mnav_fol::Staging& G = ctx->stage;
+  if (!G.have_ev) {
+    for (auto& e : G.ev) HIPCHK(hipEventCreate(e.out()));
+    G.have_ev = true;
+  }
+  if (n > G.cap) {
+    G.cap = 0;
+    if (alloc_group(G.pos, 12 * n, G.dir, 12 * n, G.up, 12 * n, G.face, 4 * n, G.slot, 4 * n, G.seed_face, 4 * n, G.nb_list, 4 * n, G.gl_list, 4 * n) !=
+        hipSuccess) { ctx->err = std::string(what) + ": out of device memory"; return -1; }
+    G.cap = n;
+  }
+  if (n_slots > G.slots_cap) {
+    G.slots_cap = 0;
+    HIPCHK(G.vecmaps.alloc(sizeof(const float*) * n_slots));
+    G.slots_cap = n_slots;
+  }
+  return 0;
+}
+
+// every input of a call into the staging (on the context's stream), and the part of the passes' view that points into it
+static int staging_upload(mnav_ctx* ctx, uint32_t n, const float* pos, const float* dir, const float* up, const uint32_t* face_in, const uint32_t* slots,
+                          const uint32_t* seed_faces, const std::vector<const float*>& maps, mnav_fol::Robots& R)
+{
+  mnav_fol::Staging& G = ctx->stage;
+  HIPCHK(hipMemcpyAsync(G.pos, pos, 12 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(G.dir, dir, 12 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(G.up, up, 12 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(G.face, face_in, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(G.slot, slots, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  if (seed_faces) HIPCHK(hipMemcpyAsync(G.seed_face, seed_faces, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(G.vecmaps, maps.data(), sizeof(const float*) * ctx->caller_slot.size(), hipMemcpyHostToDevice, ctx->stream));
+  R.n = n; R.slot = G.slot; R.seed_face = seed_faces ? G.seed_face.get() : nullptr; R.vecmaps = G.vecmaps; R.costs = ctx->d_cost;
+  R.nb_list = G.nb_list; R.gl_list = G.gl_list;
+  return 0;
+}
+
+static int follow_reserve(mnav_ctx* ctx, size_t n)
 {
   mnav_fol::State& S = ctx->fol;
-  if (!S.have_ev) {
-    for (auto& e : S.ev) HIPCHK(hipEventCreate(e.out()));
-    S.have_ev = true;
-  }
   if (!S.cnt) HIPCHK(S.cnt.alloc(sizeof(uint32_t) * mnav_fol::kCounters));
   if (n > S.cap) {
     S.cap = 0;
-    if (alloc_group(S.pos, 12 * n, S.dir, 12 * n, S.up, 12 * n, S.face_in, 4 * n, S.slot, 4 * n, S.seed_face, 4 * n, S.code, 4 * n, S.face, 4 * n,
-                    S.bary, 12 * n, S.pos_out, 12 * n, S.mesh_dir, 12 * n, S.cost, 4 * n, S.cmd, 16 * n, S.how, 4 * n, S.nb_list, 4 * n,
-                    S.gl_list, 4 * n) != hipSuccess) { ctx->err = "follow: out of device memory"; return -1; }
+    if (alloc_group(S.code, 4 * n, S.face, 4 * n, S.bary, 12 * n, S.pos_out, 12 * n, S.mesh_dir, 12 * n, S.cost, 4 * n, S.cmd, 16 * n, S.how, 4 * n) !=
+        hipSuccess) { ctx->err = "follow: out of device memory"; return -1; }
     S.cap = n;
-  }
-  if (n_slots > S.slots_cap) {
-    S.slots_cap = 0;
-    HIPCHK(S.vecmaps.alloc(sizeof(const float*) * n_slots));
-    S.slots_cap = n_slots;
   }
   return 0;
 }
@@ -69,51 +98,40 @@ int mnav_follow_batch(mnav_ctx* ctx, uint32_t n, const float* pos, const float* 
   // every refusal comes before the first device call: a refused call touches nothing
   std::vector<const float*> maps;
   if (follow_check(ctx, n, pos, dir, up, face_in, slots, seed_faces, config, maps)) return -1;
-  const size_t n_slots = ctx->caller_slot.size();
   if (hipSetDevice(ctx->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return -1; }
   if (upload_walk_mesh(ctx)) return -1;
-  if (follow_reserve(ctx, n, n_slots)) return -1;
+  if (staging_reserve(ctx, n, ctx->caller_slot.size(), "follow") || follow_reserve(ctx, n)) return -1;
   State& S = ctx->fol;
+  Staging& G = ctx->stage;
   S.stayed = S.neighbour = S.global = S.lost = S.no_field = S.built_index = 0; S.ms_kernels = S.ms_total = 0.f;
-  HIPCHK(hipMemcpyAsync(S.pos, pos, 12 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(S.dir, dir, 12 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(S.up, up, 12 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(S.face_in, face_in, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(S.slot, slots, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-  if (seed_faces) HIPCHK(hipMemcpyAsync(S.seed_face, seed_faces, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(S.vecmaps, maps.data(), sizeof(const float*) * n_slots, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemsetAsync(S.cnt, 0, sizeof(uint32_t) * kCounters, ctx->stream));
   Batch B{};
-  B.n = n; B.pos = S.pos; B.dir = S.dir; B.up = S.up; B.face_in = S.face_in; B.slot = S.slot; B.seed_face = seed_faces ? S.seed_face.get() : nullptr;
-  B.vecmaps = S.vecmaps; B.costs = ctx->d_cost;
+  if (staging_upload(ctx, n, pos, dir, up, face_in, slots, seed_faces, maps, B)) return -1;
+  HIPCHK(hipMemsetAsync(S.cnt, 0, sizeof(uint32_t) * kCounters, ctx->stream));
+  B.pos = G.pos; B.dir = G.dir; B.up = G.up; B.face_in = G.face; B.cnt = S.cnt;
   B.code = S.code; B.face = S.face; B.bary = S.bary; B.pos_out = S.pos_out; B.mesh_dir = S.mesh_dir; B.cost = S.cost; B.cmd = S.cmd; B.how = S.how;
-  B.nb_list = S.nb_list; B.gl_list = S.gl_list; B.cnt = S.cnt;
   Config C;
   std::memcpy(&C, config, sizeof(C));
   const WalkMesh M{ ctx->d_xyz, ctx->d_faces, ctx->d_vf_ptr, ctx->d_vf, ctx->V, ctx->F };
-  HIPCHK(hipEventRecord(S.ev[0], ctx->stream));
+  HIPCHK(hipEventRecord(G.ev[0], ctx->stream));
   hipLaunchKernelGGL(k_follow_stay, dim3((n + kStayBlock - 1) / kStayBlock), dim3(kStayBlock), 0, ctx->stream, B, M, C);
   hipLaunchKernelGGL(k_follow_search, dim3(n < 2048u ? n : 2048u), dim3(64), 0, ctx->stream, B, M, C);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(S.ev[1], ctx->stream));
+  HIPCHK(hipEventRecord(G.ev[1], ctx->stream));
   uint32_t cnt[kCounters] = {};
   HIPCHK(hipMemcpyAsync(cnt, S.cnt, sizeof(cnt), hipMemcpyDeviceToHost, ctx->stream));   // the one look at the list lengths
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  S.ms_kernels = ev_ms(S.ev[0], S.ev[1]);
+  S.ms_kernels = ev_ms(G.ev[0], G.ev[1]);
   const uint32_t n_gl = cnt[1];
   if (n_gl > n) { ctx->err = "follow: work list out of range"; return -1; }
   if (n_gl) {
-    mnav_loc::State& L = ctx->loc;
-    if (!L.valid) {                                                   // the index mnav_locate would build, and reports as its own
-      if (locate_build(ctx)) { L.nodes.reset(); L.pts.reset(); L.valid = false; return -1; }
-      L.built = 1; S.built_index = 1;
-    }
+    if (locate_ensure(ctx, &S.built_index)) return -1;                // the index mnav_locate would build, and reports as its own
+    const mnav_loc::State& L = ctx->loc;
     const mnav_loc::Index I{ L.nodes, L.pts, L.n_pts, L.n_leaves, mnav_loc::loc_root(L.n_leaves) };
-    HIPCHK(hipEventRecord(S.ev[2], ctx->stream));
+    HIPCHK(hipEventRecord(G.ev[2], ctx->stream));
     hipLaunchKernelGGL(k_follow_global, dim3((n_gl + mnav_loc::kLocBlock - 1) / mnav_loc::kLocBlock), dim3(mnav_loc::kLocBlock), 0, ctx->stream, B, M, C, I,
                        n_gl);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(S.ev[3], ctx->stream));
+    HIPCHK(hipEventRecord(G.ev[3], ctx->stream));
     HIPCHK(hipMemcpyAsync(cnt, S.cnt, sizeof(cnt), hipMemcpyDeviceToHost, ctx->stream));
   }
   if (code_out) HIPCHK(hipMemcpyAsync(code_out, S.code, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
@@ -125,8 +143,8 @@ int mnav_follow_batch(mnav_ctx* ctx, uint32_t n, const float* pos, const float* 
   if (cmd_out) HIPCHK(hipMemcpyAsync(cmd_out, S.cmd, 16 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
   if (how_out) HIPCHK(hipMemcpyAsync(how_out, S.how, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  if (n_gl) S.ms_kernels += ev_ms(S.ev[2], S.ev[3]);
-  S.stayed = cnt[2]; S.neighbour = cnt[3]; S.global = cnt[4]; S.lost = cnt[5]; S.no_field = cnt[6];
+  if (n_gl) S.ms_kernels += ev_ms(G.ev[2], G.ev[3]);
+  S.stayed = cnt[2]; S.neighbour = cnt[3]; S.global = cnt[4]; S.lost = cnt[6]; S.no_field = cnt[7];   // (cnt[5], reached: the rollout's)
   S.ms_total = (float)(1e-3 * (double)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count());
   return 0;
 }

@@ -60,6 +60,17 @@ static int locate_build(mnav_ctx* ctx)
   return 0;
 }
 
+// The index for a call that needs one: built if the context has none (nothing is kept of a build that failed) and then
+// reported by mnav_locate_stats as the lookup's own; *built = 1 when this call built it.
+static int locate_ensure(mnav_ctx* ctx, uint32_t* built)
+{
+  mnav_loc::State& S = ctx->loc;
+  if (S.valid) return 0;
+  if (locate_build(ctx)) { S.nodes.reset(); S.pts.reset(); S.valid = false; return -1; }
+  S.built = 1; *built = 1;
+  return 0;
+}
+
 // n_a + n_b queries (two host arrays, either may be empty) through the index; the results stay in S.vtx / face / bary / dist
 static int locate_run(mnav_ctx* ctx, uint32_t n_a, const float* pos_a, uint32_t n_b, const float* pos_b)
 {
@@ -71,10 +82,7 @@ static int locate_run(mnav_ctx* ctx, uint32_t n_a, const float* pos_a, uint32_t 
   const size_t n = (size_t)n_a + n_b;
   if (n > 0x7FFFFFFFu) { ctx->err = "too many positions in one call"; return -1; }
   if (hipSetDevice(ctx->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return -1; }
-  if (!S.valid) {
-    if (locate_build(ctx)) { S.nodes.reset(); S.pts.reset(); S.valid = false; return -1; }
-    S.built = 1;
-  }
+  if (locate_ensure(ctx, &S.built)) return -1;
   if (!n) return 0;
   if (n > S.cap) {
     S.cap = 0;

@@ -3,7 +3,7 @@
 // mnav_follow_batch call), then isGoalReached (mesh_controller.cpp:172-177), then the robot moves -- here a unicycle
 // integrated with the host libm's float cos / sin (mnav_eval.h cosf_ref / sinf_ref), so that device, host mirror and the
 // Python model of the tests agree by bits.  Everything is built from the MNAV_HD pieces that already exist; the one new
-// rule is rol_after_tick, which every device pass and the host mirror rol_run call.
+// rule is rol_after_tick, which the device passes (through Tick::finish) and the host mirror rol_run call.
 //
 // One tick of a RUNNING robot, in this order and these types, no contraction:
 //   1  R = fol_tick(pos, dir, up, face); ticks += 1
@@ -18,13 +18,13 @@
 //      dir = normalized(dir * cos th + (up x dir) * sin th + up * ((up . dir) * (1 - cos th)))   (Rodrigues, float)
 // A robot that is not RUNNING is left untouched by later ticks.
 //
-// Device shape: tick-synchronous over the resident state, three kernels per tick on the context's stream that mirror
-// passes A, B and C of mnav_follow.h (k_rollout_stay: one lane per robot, stay test + tail + rol_after_tick fused;
-// k_rollout_search: one wave per listed robot; k_rollout_global: one lane per listed robot).  Unlike the one-tick call
-// nothing goes to the host between ticks: both list passes size themselves from the list lengths on the device
-// (grid-stride), the lookup index exists before the first tick, and every tick has its own row of 8 counters (cleared
-// once up front), which are the lists' lengths and the statistics at once.  A robot's row is written by exactly one pass
-// per tick; passes hand over through vector stores and vector atomics at kernel boundaries.
+// Device shape: tick-synchronous over the resident state, three kernels per tick on the context's stream, which are
+// passes A, B and C of mnav_follow.h over another policy (Tick): a robot has a tick while it is RUNNING, and the tick's
+// Result goes through rol_after_tick into its row instead of into an output row.  Unlike the one-tick call nothing goes
+// to the host between ticks: both list passes size themselves from the list lengths on the device (grid-stride), the
+// lookup index exists before the first tick, and every tick has its own row of 8 counters (cleared once up front), which
+// are the lists' lengths and the statistics at once.  A robot's row is written by exactly one pass per tick; passes hand
+// over through vector stores and vector atomics at kernel boundaries.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -121,151 +121,91 @@ inline int rol_blocks(uint32_t ticks, RunBlock run_block, Cancelled cancelled, u
 
 #if defined(__HIPCC__)
 
-constexpr int kCounters = 8;   // per tick: neighbour list length, global list length, stayed, neighbour, global, reached, out of map, no field
-constexpr int kStayBlock = 256;
+using mnav_fol::kCounters;
+using mnav_fol::kStayBlock;
 
-// the resident state (one row per robot, read and written in place), the per-slot vector maps, the two work lists, the
-// counter rows of the call and the optional trace (robot-major, trace_rows rows per robot)
-struct Batch {
-  uint32_t n;
-  float* pos; float* dir; const float* up; uint32_t* face; const uint32_t* slot; const uint32_t* seed_face;   // seed_face: may be null
+// the resident state (one row per robot, read and written in place; pos, dir, up, face: the context's staging), the
+// counter rows of the call (Robots::cnt: the first row) and the optional trace (robot-major, trace_rows rows per robot)
+struct Batch : mnav_fol::Robots {
+  float* pos; float* dir; const float* up; uint32_t* face;
   int32_t* status; uint32_t* ticks; double* travel; double* cost_integral; float* min_goal_dist;
   const float* goal_pos; const float* goal_dir;                                                                 // null without goals
-  const float* const* vecmaps; const float* costs;
-  uint32_t* nb_list; uint32_t* gl_list; uint32_t* cnt;
   float* trace; uint32_t trace_rows;
 };
 
-__device__ __forceinline__ State rol_load(const Batch& B, uint32_t i)
-{
-  State S;
-  S.pos = mnav::w3_load(B.pos + 3 * (size_t)i); S.dir = mnav::w3_load(B.dir + 3 * (size_t)i); S.up = mnav::w3_load(B.up + 3 * (size_t)i);
-  S.face = B.face[i]; S.status = B.status[i]; S.ticks = B.ticks[i]; S.travel = B.travel[i]; S.cost_integral = B.cost_integral[i];
-  S.min_goal_dist = B.min_goal_dist[i];
-  return S;
-}
+// The robots of one tick as the passes of mnav_follow.h see them: a robot has a tick while it is RUNNING, a stopped one
+// repeats its position in the trace, and the tick's Result goes through rol_after_tick into the row (`up` and the plan
+// never change).  A status is a kEnd* of mnav_follow.h.
+struct Tick : Batch {
+  Params P; uint32_t trace_row;                                       // trace_row kNone: this tick leaves no row
 
-__device__ __forceinline__ void rol_trace(const Batch& B, uint32_t i, uint32_t trace_row, W3 pos)
-{
-  if (trace_row == kNone) return;
-  float* row = B.trace + 3 * ((size_t)i * B.trace_rows + trace_row);
-  row[0] = pos.x; row[1] = pos.y; row[2] = pos.z;
-}
+  __device__ __forceinline__ Tick(const Batch& B, const Params& P_, uint32_t tick, uint32_t trace_row_) : Batch(B), P(P_), trace_row(trace_row_)
+  {
+    cnt += (size_t)kCounters * tick;
+  }
+  __device__ __forceinline__ bool first(uint32_t ic, uint32_t& f, W3& p) const
+  {
+    const int32_t st = status[ic];
+    f = face[ic]; p = mnav::w3_load(pos + 3 * (size_t)ic);
+    return st == kRunning;
+  }
+  __device__ __forceinline__ void trace_at(uint32_t i, W3 p) const
+  {
+    if (trace_row == kNone) return;
+    float* row = trace + 3 * ((size_t)i * trace_rows + trace_row);
+    row[0] = p.x; row[1] = p.y; row[2] = p.z;
+  }
+  __device__ __forceinline__ void idle(uint32_t i, W3 p) const { trace_at(i, p); }   // a stopped robot repeats its position
+  __device__ __forceinline__ State load(uint32_t i, uint32_t f, W3 p) const
+  {
+    State S;
+    S.pos = p; S.dir = mnav::w3_load(dir + 3 * (size_t)i); S.up = mnav::w3_load(up + 3 * (size_t)i);
+    S.face = f; S.status = status[i]; S.ticks = ticks[i]; S.travel = travel[i]; S.cost_integral = cost_integral[i];
+    S.min_goal_dist = min_goal_dist[i];
+    return S;
+  }
+  __device__ __forceinline__ int finish(uint32_t i, State& S, const mnav_fol::Result& R) const
+  {
+    const W3 zero = mnav::w3(0, 0, 0);
+    rol_after_tick(S, R, P, P.have_goal ? mnav::w3_load(goal_pos + 3 * (size_t)i) : zero, P.have_goal ? mnav::w3_load(goal_dir + 3 * (size_t)i) : zero);
+    pos[3 * (size_t)i] = S.pos.x; pos[3 * (size_t)i + 1] = S.pos.y; pos[3 * (size_t)i + 2] = S.pos.z;
+    dir[3 * (size_t)i] = S.dir.x; dir[3 * (size_t)i + 1] = S.dir.y; dir[3 * (size_t)i + 2] = S.dir.z;
+    face[i] = S.face; status[i] = S.status; ticks[i] = S.ticks; travel[i] = S.travel; cost_integral[i] = S.cost_integral;
+    min_goal_dist[i] = S.min_goal_dist;
+    trace_at(i, S.pos);
+    return S.status;
+  }
+};
+static_assert(kRunning == mnav_fol::kEndRunning && kReached == mnav_fol::kEndReached && kOutOfMap == mnav_fol::kEndOutOfMap && kNoField == mnav_fol::kEndNoField,
+              "a rollout status is how a tick ended");
 
-// rol_after_tick on robot i's row, the row and its trace entry written back (`up` and the plan never change)
-__device__ __forceinline__ int rol_finish(const Batch& B, const Params& P, uint32_t i, State& S, const mnav_fol::Result& R, uint32_t trace_row)
-{
-  const W3 zero = mnav::w3(0, 0, 0);
-  rol_after_tick(S, R, P, P.have_goal ? mnav::w3_load(B.goal_pos + 3 * (size_t)i) : zero, P.have_goal ? mnav::w3_load(B.goal_dir + 3 * (size_t)i) : zero);
-  B.pos[3 * (size_t)i] = S.pos.x; B.pos[3 * (size_t)i + 1] = S.pos.y; B.pos[3 * (size_t)i + 2] = S.pos.z;
-  B.dir[3 * (size_t)i] = S.dir.x; B.dir[3 * (size_t)i + 1] = S.dir.y; B.dir[3 * (size_t)i + 2] = S.dir.z;
-  B.face[i] = S.face; B.status[i] = S.status; B.ticks[i] = S.ticks; B.travel[i] = S.travel; B.cost_integral[i] = S.cost_integral;
-  B.min_goal_dist[i] = S.min_goal_dist;
-  rol_trace(B, i, trace_row, S.pos);
-  return S.status;
-}
-
-// the counters of the robots a wave finished this tick (the whole wave must call this)
-__device__ __forceinline__ void rol_count(uint32_t* cnt, bool done, int how, int status)
-{
-  const unsigned long long b[6] = { __ballot(done && how == mnav_fol::kHowStay), __ballot(done && how == mnav_fol::kHowNeighbour),
-                                    __ballot(done && (how == mnav_fol::kHowFirst || how == mnav_fol::kHowGlobal)), __ballot(done && status == kReached),
-                                    __ballot(done && status == kOutOfMap), __ballot(done && status == kNoField) };
-  if ((threadIdx.x & 63u) == 0)
-    for (int k = 0; k < 6; ++k) if (b[k]) atomicAdd(&cnt[2 + k], (uint32_t)__popcll(b[k]));
-}
-
-// Pass A: one lane per robot.  The row's first loads go to a clamped index, unconditionally.
 __global__ __launch_bounds__(kStayBlock) void k_rollout_stay(Batch B, WalkMesh M, mnav_fol::Config C, Params P, uint32_t tick, uint32_t trace_row)
 {
-  const uint32_t i = blockIdx.x * kStayBlock + threadIdx.x;
-  const uint32_t ic = i < B.n ? i : B.n - 1;
-  uint32_t* cnt = B.cnt + (size_t)kCounters * tick;
-  const int32_t status = B.status[ic];
-  const uint32_t f = B.face[ic];
-  const W3 p = mnav::w3_load(B.pos + 3 * (size_t)ic);
-  int route = 0, how = mnav_fol::kHowNone, after = kRunning;                // route 1: neighbour search, 2: global search
-  bool done = false;
-  if (i < B.n) {
-    if (status != kRunning) rol_trace(B, i, trace_row, p);              // a stopped robot repeats its position
-    else if (f == kNone) route = 2;
-    else {
-      float bary[3];
-      if (mnav_fol::fol_stay(M, p, f, C.max_search_distance, bary)) {
-        State S = rol_load(B, i);
-        const WalkField Fd = mnav_fol::fol_field(M, B.vecmaps[B.slot[i]], B.seed_face ? B.seed_face[i] : kNone);
-        const mnav_fol::Result R = mnav_fol::fol_finish(M, Fd, B.costs, C, S.pos, S.dir, S.up, f, bary, mnav_fol::kHowStay, false);
-        after = rol_finish(B, P, i, S, R, trace_row);
-        how = R.how; done = true;
-      } else route = 1;
-    }
-  }
-  mnav_fol::fol_push(B.nb_list, &cnt[0], route == 1, i);
-  mnav_fol::fol_push(B.gl_list, &cnt[1], route == 2, i);
-  rol_count(cnt, done, how, after);
+  mnav_fol::fol_pass_stay(Tick(B, P, tick, trace_row), M, C);
 }
 
-// Pass B: one wave per listed robot (grid-stride over the list, whose length pass A left in the tick's cnt[0])
 __global__ __launch_bounds__(64) void k_rollout_search(Batch B, WalkMesh M, mnav_fol::Config C, Params P, uint32_t tick, uint32_t trace_row)
 {
   __shared__ uint32_t list[mnav::kWalkScratchWords];
-  uint32_t* cnt = B.cnt + (size_t)kCounters * tick;
-  const uint32_t n_nb = cnt[0] < B.n ? cnt[0] : B.n;
-  for (uint32_t j = blockIdx.x; j < n_nb; j += gridDim.x) {
-    const uint32_t i = B.nb_list[j];
-    const W3 p = mnav::w3_load(B.pos + 3 * (size_t)i);
-    float bary[3];
-    int status = mnav::kWalkLost;
-    const uint32_t nf = mnav::walk_search_faces(M, p, B.face[i], (float)C.max_search_radius, (float)C.max_search_distance, bary, list, &status);
-    if (threadIdx.x == 0) {
-      if (nf == kNone) B.gl_list[atomicAdd(&cnt[1], 1u)] = i;           // (a robot is listed at most once per tick: the list holds n)
-      else {
-        State S = rol_load(B, i);
-        const WalkField Fd = mnav_fol::fol_field(M, B.vecmaps[B.slot[i]], B.seed_face ? B.seed_face[i] : kNone);
-        const mnav_fol::Result R = mnav_fol::fol_finish(M, Fd, B.costs, C, S.pos, S.dir, S.up, nf, bary, mnav_fol::kHowNeighbour, true);
-        const int after = rol_finish(B, P, i, S, R, trace_row);
-        atomicAdd(&cnt[3], 1u);
-        if (after == kReached) atomicAdd(&cnt[5], 1u);
-        if (after == kNoField) atomicAdd(&cnt[7], 1u);
-      }
-    }
-    __syncthreads();                                                    // the next search reuses the list
-  }
+  mnav_fol::fol_pass_search(Tick(B, P, tick, trace_row), M, C, list);
 }
 
-// Pass C: one lane per robot of the second list, whose length (the tick's cnt[1]) is final when pass B has ended:
-// grid-stride in whole waves, so that the counters' ballots see every lane
+// (the second list's length is the tick's cnt[1], final when pass B has ended: nothing goes to the host)
 __global__ __launch_bounds__(mnav_loc::kLocBlock) void k_rollout_global(Batch B, WalkMesh M, mnav_fol::Config C, Params P, mnav_loc::Index I, uint32_t tick,
                                                                        uint32_t trace_row)
 {
   __shared__ uint32_t s_node[mnav_loc::kStack * mnav_loc::kLocBlock];
   __shared__ float s_bound[mnav_loc::kStack * mnav_loc::kLocBlock];
-  uint32_t* cnt = B.cnt + (size_t)kCounters * tick;
-  const uint32_t lane = threadIdx.x;
-  const uint32_t n_gl = cnt[1] < B.n ? cnt[1] : B.n;
-  for (uint32_t base = blockIdx.x * mnav_loc::kLocBlock; base < n_gl; base += gridDim.x * mnav_loc::kLocBlock) {
-    const uint32_t j = base + lane;
-    int how = mnav_fol::kHowNone, after = kRunning;
-    if (j < n_gl) {
-      uint64_t cand = 0;                                                // (distances evaluated: the lookup's statistic, not kept here)
-      const uint32_t i = B.gl_list[j];
-      State S = rol_load(B, i);
-      mnav_loc::LdsStack st{ s_node, s_bound, lane, 0 };
-      const WalkField Fd = mnav_fol::fol_field(M, B.vecmaps[B.slot[i]], B.seed_face ? B.seed_face[i] : kNone);
-      const mnav_fol::Result R = mnav_fol::fol_global(M, I, st, Fd, B.costs, C, S.pos, S.dir, S.up, S.face == kNone ? mnav_fol::kHowFirst : mnav_fol::kHowGlobal, &cand);
-      after = rol_finish(B, P, i, S, R, trace_row);
-      how = R.how;
-    }
-    rol_count(cnt, j < n_gl, how, after);
-  }
+  const Tick T(B, P, tick, trace_row);
+  mnav_fol::fol_pass_global(T, M, C, I, T.cnt[1] < T.n ? T.cnt[1] : T.n, s_node, s_bound);
 }
 
-// buffers of the last call (grown on demand, kept between calls) and its statistics
+// what a rollout keeps beside the context's staging (grown on demand, kept between calls): the rest of the robots' rows,
+// goals, counter rows, trace, and the statistics of the last call
 struct Dev {
-  mnav::DevBuf<float> pos, dir, up, min_goal_dist, goal_pos, goal_dir, trace; mnav::DevBuf<double> travel, cost_integral;
-  mnav::DevBuf<uint32_t> face, slot, seed_face, ticks, nb_list, gl_list, cnt; mnav::DevBuf<int32_t> status;
-  mnav::DevBuf<const float*> vecmaps; size_t cap = 0, slots_cap = 0, cnt_cap = 0, trace_cap = 0;
-  mnav::Event ev[2]; bool have_ev = false;
+  mnav::DevBuf<float> min_goal_dist, goal_pos, goal_dir, trace; mnav::DevBuf<double> travel, cost_integral;
+  mnav::DevBuf<uint32_t> ticks, cnt; mnav::DevBuf<int32_t> status;
+  size_t cap = 0, cnt_cap = 0, trace_cap = 0;
   uint32_t final_status[4] = { 0, 0, 0, 0 }, built_index = 0; uint64_t robot_ticks = 0, stayed = 0, neighbour = 0, global = 0;
   float ms_kernels = 0.f, ms_total = 0.f;
 };

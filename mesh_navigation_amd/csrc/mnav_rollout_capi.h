@@ -3,27 +3,17 @@
 // checks are the follower's) and mnav_locate_capi.h (the index build is the lookup's own).
 #pragma once
 
-static int rollout_reserve(mnav_ctx* ctx, size_t n, size_t n_slots, bool goals, size_t ticks, size_t trace_floats)
+static int rollout_reserve(mnav_ctx* ctx, size_t n, bool goals, size_t ticks, size_t trace_floats)
 {
   mnav_rol::Dev& S = ctx->rol;
-  if (!S.have_ev) {
-    for (auto& e : S.ev) HIPCHK(hipEventCreate(e.out()));
-    S.have_ev = true;
-  }
   const char* oom = "rollout: out of device memory";
   if (n > S.cap) {
     S.cap = 0;
-    if (alloc_group(S.pos, 12 * n, S.dir, 12 * n, S.up, 12 * n, S.face, 4 * n, S.slot, 4 * n, S.seed_face, 4 * n, S.status, 4 * n, S.ticks, 4 * n,
-                    S.travel, 8 * n, S.cost_integral, 8 * n, S.min_goal_dist, 4 * n, S.nb_list, 4 * n, S.gl_list, 4 * n) != hipSuccess) { ctx->err = oom; return -1; }
+    if (alloc_group(S.status, 4 * n, S.ticks, 4 * n, S.travel, 8 * n, S.cost_integral, 8 * n, S.min_goal_dist, 4 * n) != hipSuccess) { ctx->err = oom; return -1; }
     S.goal_pos.reset(); S.goal_dir.reset();
     S.cap = n;
   }
   if (goals && !S.goal_pos && alloc_group(S.goal_pos, 12 * S.cap, S.goal_dir, 12 * S.cap) != hipSuccess) { ctx->err = oom; return -1; }
-  if (n_slots > S.slots_cap) {
-    S.slots_cap = 0;
-    HIPCHK(S.vecmaps.alloc(sizeof(const float*) * n_slots));
-    S.slots_cap = n_slots;
-  }
   if (ticks > S.cnt_cap) {
     S.cnt_cap = 0;
     if (S.cnt.alloc(sizeof(uint32_t) * mnav_rol::kCounters * ticks) != hipSuccess) { ctx->err = oom; return -1; }
@@ -60,43 +50,33 @@ int mnav_follow_rollout(mnav_ctx* ctx, uint32_t n, const float* pos, const float
   // the restated sinf / cosf are the host libm's on (-120, 120) only; NaN parameters give NaN commands, which std::min caps
   const double turn = std::fabs(config->max_ang_velocity) * std::fmax(1.0, std::fabs(config->ang_vel_factor)) * rollout->dt;   // bounds |ang * dt|
   if (!(turn < 100.0)) { ctx->err = "rollout: max_ang_velocity * max(1, ang_vel_factor) * dt must stay below 100 rad per tick"; return -1; }
-  const size_t n_slots = ctx->caller_slot.size();
   const uint32_t ticks = rollout->ticks, stride = rollout->trace_stride, rows = stride ? ticks / stride : 0;
   if (hipSetDevice(ctx->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return -1; }
   ctx->cancel.store(0);                                               // as the plan calls do
   if (ctx->d_cancel) { (void)hipStreamSynchronize(ctx->cancel_stream); (void)hipMemsetAsync(ctx->d_cancel, 0, 4, ctx->stream); }
   if (upload_walk_mesh(ctx)) return -1;
-  if (rollout_reserve(ctx, n, n_slots, goal_pos != nullptr, ticks, 3 * (size_t)n * rows)) return -1;
+  if (staging_reserve(ctx, n, ctx->caller_slot.size(), "rollout") || rollout_reserve(ctx, n, goal_pos != nullptr, ticks, 3 * (size_t)n * rows)) return -1;
   Dev& S = ctx->rol;
+  mnav_fol::Staging& G = ctx->stage;
   for (auto& c : S.final_status) c = 0;
   S.built_index = 0; S.robot_ticks = S.stayed = S.neighbour = S.global = 0; S.ms_kernels = S.ms_total = 0.f;
-  mnav_loc::State& L = ctx->loc;
-  if (!L.valid) {                                                     // no look at the lists between ticks: the index exists before the first one
-    if (locate_build(ctx)) { L.nodes.reset(); L.pts.reset(); L.valid = false; return -1; }
-    L.built = 1; S.built_index = 1;
-  }
-  HIPCHK(hipMemcpyAsync(S.pos, pos, 12 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(S.dir, dir, 12 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(S.up, up, 12 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(S.face, face_in, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(S.slot, slots, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-  if (seed_faces) HIPCHK(hipMemcpyAsync(S.seed_face, seed_faces, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  if (locate_ensure(ctx, &S.built_index)) return -1;                  // no look at the lists between ticks: the index exists before the first one
+  const mnav_loc::State& L = ctx->loc;
+  Batch B{};
+  if (staging_upload(ctx, n, pos, dir, up, face_in, slots, seed_faces, maps, B)) return -1;
   if (goal_pos) {
     HIPCHK(hipMemcpyAsync(S.goal_pos, goal_pos, 12 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(S.goal_dir, goal_dir, 12 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
   }
-  HIPCHK(hipMemcpyAsync(S.vecmaps, maps.data(), sizeof(const float*) * n_slots, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipMemsetAsync(S.status, 0, 4 * (size_t)n, ctx->stream));    // kRunning
   HIPCHK(hipMemsetAsync(S.ticks, 0, 4 * (size_t)n, ctx->stream));
   HIPCHK(hipMemsetAsync(S.travel, 0, 8 * (size_t)n, ctx->stream));
   HIPCHK(hipMemsetAsync(S.cost_integral, 0, 8 * (size_t)n, ctx->stream));
   HIPCHK(hipMemsetD32Async((hipDeviceptr_t)S.min_goal_dist.get(), 0x7F800000, n, ctx->stream));   // +inf
   HIPCHK(hipMemsetAsync(S.cnt, 0, sizeof(uint32_t) * kCounters * (size_t)ticks, ctx->stream));    // every tick's row, once
-  Batch B{};
-  B.n = n; B.pos = S.pos; B.dir = S.dir; B.up = S.up; B.face = S.face; B.slot = S.slot; B.seed_face = seed_faces ? S.seed_face.get() : nullptr;
+  B.pos = G.pos; B.dir = G.dir; B.up = G.up; B.face = G.face; B.cnt = S.cnt;
   B.status = S.status; B.ticks = S.ticks; B.travel = S.travel; B.cost_integral = S.cost_integral; B.min_goal_dist = S.min_goal_dist;
   B.goal_pos = goal_pos ? S.goal_pos.get() : nullptr; B.goal_dir = goal_pos ? S.goal_dir.get() : nullptr;
-  B.vecmaps = S.vecmaps; B.costs = ctx->d_cost; B.nb_list = S.nb_list; B.gl_list = S.gl_list; B.cnt = S.cnt;
   B.trace = rows ? S.trace.get() : nullptr; B.trace_rows = rows;
   mnav_fol::Config C;
   std::memcpy(&C, config, sizeof(C));
@@ -108,7 +88,7 @@ int mnav_follow_rollout(mnav_ctx* ctx, uint32_t n, const float* pos, const float
   float ms_kernels = 0.f;
   // one block: plain launches, no host look in between; then one synchronise
   const auto run_block = [&](uint32_t first, uint32_t nt) -> int {
-    HIPCHK(hipEventRecord(S.ev[0], ctx->stream));
+    HIPCHK(hipEventRecord(G.ev[0], ctx->stream));
     for (uint32_t t = first; t < first + nt; ++t) {
       const uint32_t row = stride && (t + 1) % stride == 0 ? (t + 1) / stride - 1 : kNone;
       hipLaunchKernelGGL(k_rollout_stay, dim3(g_stay), dim3(kStayBlock), 0, ctx->stream, B, M, C, P, t, row);
@@ -116,9 +96,9 @@ int mnav_follow_rollout(mnav_ctx* ctx, uint32_t n, const float* pos, const float
       hipLaunchKernelGGL(k_rollout_global, dim3(g_global), dim3(mnav_loc::kLocBlock), 0, ctx->stream, B, M, C, P, I, t, row);
     }
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(S.ev[1], ctx->stream));
+    HIPCHK(hipEventRecord(G.ev[1], ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    ms_kernels += ev_ms(S.ev[0], S.ev[1]);
+    ms_kernels += ev_ms(G.ev[0], G.ev[1]);
     return 0;
   };
   uint32_t done = 0;
@@ -128,9 +108,9 @@ int mnav_follow_rollout(mnav_ctx* ctx, uint32_t n, const float* pos, const float
   HIPCHK(hipMemcpyAsync(cnt.data(), S.cnt, sizeof(uint32_t) * cnt.size(), hipMemcpyDeviceToHost, ctx->stream));
   if (status_out) HIPCHK(hipMemcpyAsync(status_out, S.status, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
   if (ticks_out) HIPCHK(hipMemcpyAsync(ticks_out, S.ticks, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-  if (pos_out) HIPCHK(hipMemcpyAsync(pos_out, S.pos, 12 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-  if (dir_out) HIPCHK(hipMemcpyAsync(dir_out, S.dir, 12 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-  if (face_out) HIPCHK(hipMemcpyAsync(face_out, S.face, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  if (pos_out) HIPCHK(hipMemcpyAsync(pos_out, G.pos, 12 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  if (dir_out) HIPCHK(hipMemcpyAsync(dir_out, G.dir, 12 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  if (face_out) HIPCHK(hipMemcpyAsync(face_out, G.face, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
   if (travel_out) HIPCHK(hipMemcpyAsync(travel_out, S.travel, 8 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
   if (cost_integral_out) HIPCHK(hipMemcpyAsync(cost_integral_out, S.cost_integral, 8 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
   if (min_goal_dist_out) HIPCHK(hipMemcpyAsync(min_goal_dist_out, S.min_goal_dist, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));

@@ -1,7 +1,8 @@
 """The device rollout (mnav_follow_rollout, mnav_rollout_stats) against tests/rollout_model.py, the Python restatement of
 its specification with the host libm's cosf, sinf and acosf, over the resident fields of a single Dijkstra plan, an 8-plan
 batch of the asynchronous engine, a 168-plan batch of the tile-batch engine and a 4-plan CVP batch; against the loop of
-mnav_follow_batch calls it replaces; resumed in two calls; the index build at the start; refusals; the cancel flag.  Every
+mnav_follow_batch calls it replaces; resumed in two calls; the index build at the start; refusals; the cancel flag; and,
+against the compiled host mirror, a fleet large enough for a second trip of the list passes' grid-stride loops.  Every
 comparison is exact: integers equal, floats and doubles by their bits (any NaN equals any NaN)."""
 import ctypes as C
 
@@ -13,7 +14,7 @@ from tests import follow_model as FM
 from tests import locate_model as LM
 from tests import rollout_model as RM
 from tests.common import Case
-from tests.test_rollout_model import ANG_TOL, DIST_TOL, DT, TICKS, after_tick, build_shim, fleet, fresh_state
+from tests.test_rollout_model import ANG_TOL, DIST_TOL, DT, TICKS, Mirror, after_tick, build_shim, fleet, fresh_state
 
 pytestmark = pytest.mark.gpu
 
@@ -142,6 +143,62 @@ def test_equals_the_loop_of_calls_it_replaces(worlds, shim):
     assert got.trace is None
     RM.assert_same(got, S, "40 calls", keys=RM.KEYS)
     assert len(set(S["status"].tolist())) >= 3 and (S["ticks"] == T).any() and ((S["ticks"] > 1) & (S["ticks"] < T)).any()
+
+
+def big_fleet(model, seed=7, n_first=65537, n_moved=2049, n_stay=300):
+    """65 537 robots without a face (one more than the 1 024 x 64 lanes of the global pass), 2 049 with a face that does not
+    hold them (one more than the 2 048 workgroups of the search pass: three in four a face 5 to 30 cm away, the fourth one
+    across the mesh) and 300 on their own face; every robot stands inside a random face.  A goal per robot: the middle of
+    the mesh, heading +x."""
+    rng = np.random.default_rng(seed)
+    n = n_first + n_moved + n_stay
+    cen = model.xyz[model.faces].astype(np.float64).mean(axis=1)
+    f = rng.integers(0, model.F, n)
+    given = f.astype(np.uint32)
+    given[:n_first] = FM.NONE
+    for j in range(n_first, n_first + n_moved):
+        d = np.linalg.norm(cen - cen[f[j]], axis=1)
+        given[j] = rng.choice(np.nonzero((d > 0.05) & (d < 0.3) if j % 4 else d > 0.95)[0])
+    a = rng.uniform(0, 2 * np.pi, n)
+    pos = FM.face_points(model, f, rng)
+    k = n_first + n_moved                                            # those that may need searchContainingFace stand near a corner of their face: it looks
+    pos[:k] = 0.75 * model.xyz[model.faces[f[:k], rng.integers(0, 3, k)]].astype(np.float64) + 0.25 * pos[:k]   # around the nearest vertex only
+    robots = dict(pos=pos.astype(np.float32), dir=np.stack([np.cos(a), np.sin(a), np.zeros(n)], axis=1).astype(np.float32),
+                  up=np.tile(np.array([0, 0, 1], np.float32), (n, 1)), face_in=given, slot=np.zeros(n, np.uint32), seed_face=None)
+    mid = cen[int(np.argmin(np.linalg.norm(cen - cen.mean(axis=0), axis=1)))].astype(np.float32)
+    return robots, (np.tile(mid, (n, 1)), np.tile(np.array([1, 0, 0], np.float32), (n, 1)))
+
+
+def test_the_second_trip_of_the_list_passes(worlds, shim):
+    """Both grid-stride loops of the shared passes go round twice in tick 1: the global pass of the rollout (1 024 workgroups
+    of 64 lanes) and the search pass of either caller (2 048 workgroups).  The reference is the compiled host mirror (rol_run
+    of mnav_rollout.h through tests/test_rollout_model.py): the per-robot Python model would take minutes."""
+    w = worlds("single")
+    cfg = FM.config()
+    robots, goals = big_fleet(w.model)
+    n = robots["pos"].shape[0]
+    if 0 not in w.fields:
+        w.fields[0] = w.ctx.download_output("vecmap", 0)
+    mirror = Mirror(shim, w.model)
+    tick1 = mirror.run(cfg, [w.fields[0]], robots, goals, DT, 1, DIST_TOL, ANG_TOL, trace_stride=1)
+    want = mirror.run(cfg, [w.fields[0]], robots, goals, DT, 1, DIST_TOL, ANG_TOL, trace_stride=1, state=tick1)
+    mirror.close()
+    want["how"] = tick1["how"] + want["how"]
+    want["trace"] = np.concatenate([tick1["trace"], want["trace"]], axis=1)
+    print("tick 1 how:", tick1["how"], "both ticks:", want["how"], "status:", np.bincount(want["status"], minlength=4))
+    assert tick1["how"][1] >= 65537 and tick1["how"][3] + tick1["how"][4] >= 2049 and tick1["how"][2] > 0
+    got = w.device_run(cfg, robots, goals, 2)
+    RM.assert_same(got, want, "2 ticks")
+    check_stats(w.ctx, want, n)
+    # the follower on the same fleet: one call and rol_after_tick on the host equal one tick of the rollout
+    S = fresh_state(robots)
+    o = w.ctx.follow(S["pos"], S["dir"], robots["up"], S["face"], robots["slot"], None, capi.FollowConfig(**cfg))
+    fs = w.ctx.follow_stats()
+    assert (fs["stayed"], fs["neighbour"], fs["global"]) == (tick1["how"][2], tick1["how"][3], tick1["how"][1] + tick1["how"][4]), fs
+    after_tick(shim, S, robots["up"], goals, DT, DIST_TOL, ANG_TOL, dict(code=o.code, how=o.how, face=o.face, pos=o.pos, cost=o.cost, cmd=o.cmd))
+    one = w.device_run(cfg, robots, goals, 1, trace_stride=0)
+    RM.assert_same(one, S, "one call", keys=RM.KEYS)
+    RM.assert_same(one, tick1, "one tick", keys=RM.KEYS)
 
 
 def test_resume_and_a_call_that_spans_two_blocks(worlds):
