@@ -617,7 +617,51 @@ int mnav_fleet_walks(mnav_ctx* ctx, uint32_t n, const uint32_t* slots, uint32_t 
                      const uint32_t* seed_faces, const float* start_pos, const uint32_t* start_faces, double step_width,
                      int32_t inflation_layer, uint32_t walk_cap, int32_t* status_out, uint32_t* start_face_out, uint32_t* len_out,
                      uint64_t* offset_out, float* positions_out, uint32_t* faces_out, uint64_t entries_cap, uint64_t* total_out);
-/* The last mnav_fleet_paths or mnav_fleet_walks: robots served (MNAV_SUCCESS / status 1), beyond the field, without a path
+/* -- fleet plans: MeshPlanner::makePlan's pose list and cost for many robots per resident field ---------
+ * makePlan returns neither vertex ids nor (position, face) pairs but std::vector<PoseStamped> and a cost.  The two calls
+ * below turn the paths of mnav_fleet_paths and the walks of mnav_fleet_walks into exactly that on the device: 7 doubles per
+ * pose (x y z qx qy qz qw) by mesh_map::calculatePoseFromPosition (util.cpp:267-298: the basis in float, the tf2
+ * getRotation quaternion and its normalisation in double), bit for bit what the host loops of mnav_planner_host.hpp
+ * (vertex_path_poses, face_path_poses) compute.  A pose whose direction is zero or parallel to its normal has a NaN
+ * quaternion with an exact position and an exact length, as in the reference. */
+/* MeshMap::faceNormals(): F * 3 floats, resident until the next mnav_upload_mesh.  Only mnav_fleet_walk_plans needs them.
+ * Returns -1 with mnav_last_error set: no mesh, F different from the resident mesh's, a null array. */
+int mnav_upload_face_normals(mnav_ctx* ctx, uint32_t F, const float* face_normals);
+/* DijkstraMeshPlanner::makePlan's plan and cost (dijkstra_mesh_planner.cpp:83-116) for n robots over the resident fields.
+ * slots, start_vertex, code_out, vertex_out, potential_out: as in mnav_fleet_paths, with the same values for the same
+ * slots and vertices.  start_pos (n * 3, required): the robot position of the first pose; start_vertex may be NULL, the
+ * vertex then comes from start_pos by the rule of mnav_locate.  goal_pos (n_plans * 3): the goal position of every plan
+ * (the last pose looks at it); n_plans must equal the plan count of the recorded call.
+ * With u_0 .. u_{L-1} that robot's path, robot side first (the reverse of the ids of mnav_fleet_paths: u_0 = pred[v],
+ * u_{L-1} = the seed), xyz the vertex positions and vn the vertex normals of mnav_upload_mesh:
+ *   L == 0 (any code): no poses, cost 0
+ *   L > 0: L + 1 poses: pose 0 = pose_from(start_pos, xyz[u_0], vn[u_0]); pose k = pose_from(xyz[u_{k-1}], xyz[u_k],
+ *          vn[u_{k-1}]) for 1 <= k < L; pose L = pose_from(xyz[u_{L-1}], goal_pos[slot], vn[u_{L-1}])
+ * cost_out[i]: the double sum of the L + 1 float lengths in that order.  len_out counts poses; offset_out (n + 1) and
+ * total_out as in mnav_fleet_paths, in poses; poses_out: 7 doubles per pose, packed in robot order.
+ * Returns 0 when everything was written; 1 when *total_out > poses_cap or poses_out is NULL: all per-robot outputs (the
+ * costs too) and total_out are valid and poses_out is untouched; -1 with mnav_last_error set and NOTHING touched: every
+ * refusal of mnav_fleet_paths, vertex normals not resident, start_pos or goal_pos NULL, n_plans different from the
+ * recorded call's.  Path ids (4 bytes per hop) and lengths stay in device scratch; only the caller's outputs cross PCIe. */
+int mnav_fleet_plans(mnav_ctx* ctx, uint32_t n, const uint32_t* slots, const uint32_t* start_vertex, const float* start_pos,
+                     uint32_t n_plans, const float* goal_pos, uint32_t* code_out, uint32_t* vertex_out, float* potential_out,
+                     uint32_t* len_out, uint64_t* offset_out, double* cost_out, double* poses_out, uint64_t poses_cap,
+                     uint64_t* total_out);
+/* CVPMeshPlanner::makePlan's plan and cost (cvp_mesh_planner.cpp:93-124) over the walks of mnav_fleet_walks: arguments,
+ * statuses, chunking (fleet_scratch_mb) and refusals are that call's, plus two refusals: face normals not resident
+ * (mnav_upload_face_normals), goal_pose NULL.  goal_pose: n_plans * 7 doubles.  A row of m entries (p_0, f_0) ..
+ * (p_{m-1}, f_{m-1}), seed first, whatever its status (the reference poses a partial path too), with fn the face normals:
+ *   m == 0: no poses, cost 0
+ *   otherwise m poses: pose k = pose_from(p_{m-1-k}, p_{m-2-k}, fn[f_{m-1-k}]) for k < m - 1; pose m - 1 = the 7 doubles
+ *   of goal_pose[slot], bit for bit; cost_out[i] = the ordered double sum of the m - 1 lengths
+ * len_out, offset_out, total_out count poses; return values as in mnav_fleet_plans. */
+int mnav_fleet_walk_plans(mnav_ctx* ctx, uint32_t n, const uint32_t* slots, uint32_t n_plans, const float* seed_pos,
+                          const uint32_t* seed_faces, const double* goal_pose, const float* start_pos, const uint32_t* start_faces,
+                          double step_width, int32_t inflation_layer, uint32_t walk_cap, int32_t* status_out,
+                          uint32_t* start_face_out, uint32_t* len_out, uint64_t* offset_out, double* cost_out, double* poses_out,
+                          uint64_t poses_cap, uint64_t* total_out);
+/* The last mnav_fleet_paths, mnav_fleet_walks, mnav_fleet_plans or mnav_fleet_walk_plans (entries: poses for the last two);
+ * robots served (MNAV_SUCCESS / status 1), beyond the field, without a path
  * (MNAV_NO_PATH_FOUND / every other walk status but -3) and invalid (every other code / status -3); path ids or walk
  * entries summed; built_index = 1 if the call built the lookup index; chunks of a walk call; device milliseconds of its
  * kernels and host milliseconds of the whole call.  Any pointer may be NULL. */

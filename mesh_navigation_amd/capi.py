@@ -38,6 +38,7 @@ SYMBOLS = [
     "mnav_map_configure", "mnav_map_compute", "mnav_map_layer_changed", "mnav_map_update_layer", "mnav_map_obstacle", "mnav_map_stats",
     "mnav_replan_dijkstra_batch", "mnav_replan_plans", "mnav_replan_stats",
     "mnav_fleet_paths", "mnav_fleet_walks", "mnav_fleet_stats",
+    "mnav_upload_face_normals", "mnav_fleet_plans", "mnav_fleet_walk_plans",
     "mnav_set_option", "mnav_get_option", "mnav_shard_set_goal_tie", "mnav_last_engine",
 ]
 
@@ -308,6 +309,12 @@ def load(path: str | None = None):
     L.mnav_fleet_paths.argtypes = [vp, u32] + [vp] * 9 + [C.c_uint64, vp]
     L.mnav_fleet_walks.restype = C.c_int
     L.mnav_fleet_walks.argtypes = [vp, u32, vp, u32, vp, vp, vp, vp, f64, C.c_int32, u32] + [vp] * 6 + [C.c_uint64, vp]
+    L.mnav_upload_face_normals.restype = C.c_int
+    L.mnav_upload_face_normals.argtypes = [vp, u32, vp]
+    L.mnav_fleet_plans.restype = C.c_int
+    L.mnav_fleet_plans.argtypes = [vp, u32, vp, vp, vp, u32] + [vp] * 8 + [C.c_uint64, vp]
+    L.mnav_fleet_walk_plans.restype = C.c_int
+    L.mnav_fleet_walk_plans.argtypes = [vp, u32, vp, u32, vp, vp, vp, vp, vp, f64, C.c_int32, u32] + [vp] * 6 + [C.c_uint64, vp]
     L.mnav_fleet_stats.restype = C.c_int
     L.mnav_fleet_stats.argtypes = [vp] + [C.POINTER(u32)] * 4 + [C.POINTER(C.c_uint64)] + [C.POINTER(u32)] * 2 + [C.POINTER(C.c_float)] * 2
     if path is None:
@@ -1003,8 +1010,87 @@ class MnavContext:
         return dict(rc=rc, status=st, start_face=face0, path_len=lens, offsets=off, positions=pos[:t] if rc == 0 else None,
                     faces=face[:t] if rc == 0 else None, total=t)
 
+    def upload_face_normals(self, face_normals):
+        """MeshMap::faceNormals() for fleet_walk_plans (mnav_upload_face_normals): F x 3, resident until the next upload_mesh."""
+        fn = _f32(face_normals).reshape(-1, 3)
+        if self._L.mnav_upload_face_normals(self._h, int(fn.shape[0]), _p(fn)) != 0:
+            raise RuntimeError(f"mnav_upload_face_normals failed: {self._err()}")
+
+    def fleet_plans(self, slots, start_pos, goal_pos, start_vertex=None, poses_cap: int | None = None) -> dict:
+        """makePlan's pose list and cost of n robots out of the resident fields of the last Dijkstra call or replan
+        (mnav_fleet_plans, include/mnav.h): robot i stands at start_pos[i] on start_vertex[i] (None: the vertex nearest to
+        it) of plan slots[i]; goal_pos: one row per plan of that call.  Returns dict(rc, codes, vertex, potential, path_len,
+        offsets, cost, poses, total): the poses of robot i are poses[offsets[i]:offsets[i + 1]], 7 doubles each, robot side
+        first.  Without poses_cap the call sizes the buffer itself (two calls); with it, rc = 1 and poses = None tell that
+        `total` poses did not fit."""
+        sl = _u32(slots).reshape(-1)
+        n = int(sl.shape[0])
+        sv = None if start_vertex is None else _u32(start_vertex).reshape(-1)
+        sp = None if start_pos is None else _f32(start_pos).reshape(-1, 3)
+        gp = None if goal_pos is None else _f32(goal_pos).reshape(-1, 3)
+        if (sv is not None and sv.shape[0] != n) or (sp is not None and sp.shape[0] != n):
+            raise ValueError("fleet_plans: the per-robot arrays differ in length")
+        codes, vtx, lens = (np.zeros(n, np.uint32) for _ in range(3))
+        pot = np.zeros(n, np.float32)
+        off = np.zeros(n + 1, np.uint64)
+        cost = np.zeros(n, np.float64)
+        total = C.c_uint64(0)
+
+        def call(poses, cap):
+            rc = self._L.mnav_fleet_plans(self._h, n, _p(sl), _p(sv), _p(sp), 0 if gp is None else int(gp.shape[0]), _p(gp), _p(codes), _p(vtx), _p(pot), _p(lens),
+                                          _p(off), _p(cost), _p(poses), int(cap), C.byref(total)) if n else 0
+            if rc < 0:
+                raise RuntimeError(f"mnav_fleet_plans failed: {self._err()}")
+            return rc
+
+        if poses_cap is None:
+            rc = call(None, 0)
+            poses = np.empty((int(total.value), 7), np.float64)
+            rc = call(poses, poses.shape[0]) if poses.shape[0] else 0
+        else:
+            poses = np.empty((int(poses_cap), 7), np.float64)
+            rc = call(poses, poses.shape[0])
+            poses = poses[: int(total.value)] if rc == 0 else None
+        return dict(rc=rc, codes=codes, vertex=vtx, potential=pot, path_len=lens, offsets=off, cost=cost, poses=poses, total=int(total.value))
+
+    def fleet_walk_plans(self, slots, seed_pos, seed_faces, goal_pose, start_pos, start_faces=None, step_width: float = 0.4, inflation_layer: int = -1,
+                         walk_cap: int = 4096, poses_cap: int | None = None) -> dict:
+        """makePlan's pose list and cost over the walks of fleet_walks (mnav_fleet_walk_plans, include/mnav.h; face normals:
+        upload_face_normals).  goal_pose: 7 doubles per plan, the last pose of every row.  Returns dict(rc, status,
+        start_face, path_len, offsets, cost, poses, total), poses robot side first; sizing as in fleet_walks."""
+        sl = _u32(slots).reshape(-1)
+        n = int(sl.shape[0])
+        sp, sf = _f32(seed_pos).reshape(-1, 3), _u32(seed_faces).reshape(-1)
+        gp = None if goal_pose is None else np.ascontiguousarray(goal_pose, np.float64).reshape(-1, 7)
+        tp = _f32(start_pos).reshape(-1, 3)
+        tf = None if start_faces is None else _u32(start_faces).reshape(-1)
+        if sp.shape[0] != sf.shape[0] or (gp is not None and gp.shape[0] != sf.shape[0]) or tp.shape[0] != n or (tf is not None and tf.shape[0] != n):
+            raise ValueError("fleet_walk_plans: array lengths differ")
+        st = np.zeros(n, np.int32)
+        face0, lens = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        off = np.zeros(n + 1, np.uint64)
+        cost = np.zeros(n, np.float64)
+        total = C.c_uint64(0)
+
+        def call(poses, cap):
+            rc = self._L.mnav_fleet_walk_plans(self._h, n, _p(sl), int(sf.shape[0]), _p(sp), _p(sf), _p(gp), _p(tp), _p(tf), float(step_width), int(inflation_layer),
+                                               int(walk_cap), _p(st), _p(face0), _p(lens), _p(off), _p(cost), _p(poses), int(cap), C.byref(total)) if n else 0
+            if rc < 0:
+                raise RuntimeError(f"mnav_fleet_walk_plans failed: {self._err()}")
+            return rc
+
+        if poses_cap is None:
+            call(None, 0)                                                    # sizing only: statuses, lengths, costs, total
+            cap = int(total.value)
+        else:
+            cap = int(poses_cap)
+        poses = np.empty((max(cap, 1), 7), np.float64)
+        rc = call(poses, cap)
+        t = int(total.value)
+        return dict(rc=rc, status=st, start_face=face0, path_len=lens, offsets=off, cost=cost, poses=poses[:t] if rc == 0 else None, total=t)
+
     def fleet_stats(self) -> dict:
-        """The last fleet_paths / fleet_walks call (mnav_fleet_stats)."""
+        """The last fleet_paths / fleet_walks / fleet_plans / fleet_walk_plans call (mnav_fleet_stats; entries: ids, walk entries or poses)."""
         v = [C.c_uint32() for _ in range(4)]
         e = C.c_uint64()
         b, ch = C.c_uint32(), C.c_uint32()

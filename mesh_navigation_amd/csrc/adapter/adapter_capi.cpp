@@ -3,11 +3,14 @@
 // (mbf_mesh_nav/src/mesh_navigation_server.cpp:185-212, mesh_planner_execution.cpp:55-66).
 #include <cmath>
 #include <cstring>
+#include <iterator>
 #include <memory>
 #include <string>
+#include <vector>
 
 #include "gpu_mesh_controller.h"
 #include "gpu_mesh_planners.h"
+#include "mnav_planner_host.hpp"
 
 struct mnav_adapter_planner {
   std::shared_ptr<mesh_map::MeshMap> map;
@@ -83,6 +86,42 @@ uint32_t mnav_adapter_make_plan(mnav_adapter_planner* a, const double start_pose
   return code;
 }
 
+// DijkstraMeshPlanner::makeFleetPlans after a makePlan: n start poses (7 doubles each) -> codes, pose counts and costs per
+// robot; poses (7 doubles each, packed in robot order) when *total <= cap.  Returns the call's code, or 60 for a CVP planner.
+uint32_t mnav_adapter_make_fleet_plans(mnav_adapter_planner* a, uint32_t n, const double* start_poses, uint32_t* codes, uint32_t* lens, double* costs,
+                                       double* poses, uint64_t cap, uint64_t* total, char* message, uint32_t message_cap)
+{
+  if (a->is_cvp) return 60;
+  std::vector<geometry_msgs::msg::PoseStamped> starts(n);
+  for (uint32_t i = 0; i < n; ++i) {
+    const double* v = start_poses + 7 * (size_t)i;
+    auto& p = starts[i];
+    p.header.frame_id = "map";
+    p.pose.position.x = v[0]; p.pose.position.y = v[1]; p.pose.position.z = v[2];
+    p.pose.orientation.x = v[3]; p.pose.orientation.y = v[4]; p.pose.orientation.z = v[5]; p.pose.orientation.w = v[6];
+  }
+  std::vector<std::vector<geometry_msgs::msg::PoseStamped>> plans;
+  std::vector<double> c;
+  std::vector<uint32_t> k;
+  std::string msg;
+  const uint32_t code = static_cast<dijkstra_mesh_planner::DijkstraMeshPlanner*>(a->planner.get())->makeFleetPlans(starts, plans, c, k, msg);
+  uint64_t at = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    codes[i] = k[i]; lens[i] = (uint32_t)plans[i].size(); costs[i] = c[i];
+    for (const auto& ps : plans[i]) {
+      if (at < cap) {
+        double* o = poses + 7 * (size_t)at;
+        o[0] = ps.pose.position.x; o[1] = ps.pose.position.y; o[2] = ps.pose.position.z;
+        o[3] = ps.pose.orientation.x; o[4] = ps.pose.orientation.y; o[5] = ps.pose.orientation.z; o[6] = ps.pose.orientation.w;
+      }
+      ++at;
+    }
+  }
+  *total = at;
+  if (message && message_cap) { std::strncpy(message, msg.c_str(), message_cap - 1); message[message_cap - 1] = 0; }
+  return code;
+}
+
 int mnav_adapter_cancel(mnav_adapter_planner* a) { return a->planner->cancel() ? 1 : 0; }
 
 // change counter of the map's cost arrays (0 = unknown: the device mirror hashes them on every plan)
@@ -150,6 +189,67 @@ uint32_t mnav_adapter_host_containing_face(uint32_t V, uint32_t F, const float* 
   m.positions.assign(xyz, xyz + 3 * (size_t)V); m.faces.assign(faces, faces + 3 * (size_t)F);
   m.finalize();
   return m.getContainingFace(mesh_map::Vector(p[0], p[1], p[2]), 0.4f);
+}
+
+// The host pose loop (mnav_host::vertex_path_poses with mesh_map::calculatePoseFromPosition, what makePlan runs per plan) over
+// the packed ids of mnav_fleet_paths for n robots on one thread: robot i's ids are ids[offsets[i] .. offsets[i + 1]), seed
+// first; its poses (one more than its ids, none without ids) are packed in robot order.  No device involved: what a fleet
+// caller does without mnav_fleet_plans, for tools/fleet_plans_perf.py.  Returns the pose count.
+uint64_t mnav_adapter_host_vertex_path_poses(const float* xyz, const float* vertex_normals, uint32_t n, const uint32_t* ids, const uint64_t* offsets,
+                                             const uint32_t* slots, const float* start_pos, const float* goal_pos, double* poses, double* costs)
+{
+  uint64_t at = 0;
+  std::vector<uint32_t> path;
+  std::vector<geometry_msgs::msg::PoseStamped> plan;
+  const geometry_msgs::msg::PoseStamped stamped;
+  auto vec = [](const float* p, size_t i) { return mesh_map::Vector(p[3 * i], p[3 * i + 1], p[3 * i + 2]); };
+  for (uint32_t i = 0; i < n; ++i) {
+    path.assign(std::make_reverse_iterator(ids + offsets[i + 1]), std::make_reverse_iterator(ids + offsets[i]));   // robot side first (:83)
+    plan.clear();
+    mnav_host::vertex_path_poses(path, vec(start_pos, i), vec(goal_pos, slots[i]), stamped, [&](uint32_t v) { return vec(xyz, v); },
+                                 [&](uint32_t v) { return vec(vertex_normals, v); },
+                                 [](const mesh_map::Vector& from, const mesh_map::Vector& to, const mesh_map::Normal& up, float& len) {
+                                   return mesh_map::calculatePoseFromPosition(from, to, up, len);
+                                 },
+                                 plan, costs[i]);
+    for (const auto& ps : plan) {
+      double* o = poses + 7 * (size_t)at++;
+      o[0] = ps.pose.position.x; o[1] = ps.pose.position.y; o[2] = ps.pose.position.z;
+      o[3] = ps.pose.orientation.x; o[4] = ps.pose.orientation.y; o[5] = ps.pose.orientation.z; o[6] = ps.pose.orientation.w;
+    }
+  }
+  return at;
+}
+
+// The same for the packed rows of mnav_fleet_walks (mnav_host::face_path_poses): one pose per entry, the goal pose last.
+uint64_t mnav_adapter_host_face_path_poses(const float* face_normals, uint32_t n, const float* positions, const uint32_t* faces, const uint64_t* offsets,
+                                           const uint32_t* slots, const double* goal_pose, double* poses, double* costs)
+{
+  uint64_t at = 0;
+  std::vector<std::pair<mesh_map::Vector, uint32_t>> path;
+  std::vector<geometry_msgs::msg::PoseStamped> plan;
+  const geometry_msgs::msg::PoseStamped stamped;
+  for (uint32_t i = 0; i < n; ++i) {
+    path.clear();
+    for (uint64_t q = offsets[i + 1]; q-- > offsets[i];) path.push_back({ mesh_map::Vector(positions[3 * q], positions[3 * q + 1], positions[3 * q + 2]), faces[q] });   // robot side first (:93)
+    const double* g = goal_pose + 7 * (size_t)slots[i];
+    geometry_msgs::msg::Pose goal;
+    goal.position.x = g[0]; goal.position.y = g[1]; goal.position.z = g[2];
+    goal.orientation.x = g[3]; goal.orientation.y = g[4]; goal.orientation.z = g[5]; goal.orientation.w = g[6];
+    plan.clear();
+    mnav_host::face_path_poses(path, false, goal, stamped,
+                               [&](uint32_t f) { return mesh_map::Normal(face_normals[3 * (size_t)f], face_normals[3 * (size_t)f + 1], face_normals[3 * (size_t)f + 2]); },
+                               [](const mesh_map::Vector& from, const mesh_map::Vector& to, const mesh_map::Normal& up, float& len) {
+                                 return mesh_map::calculatePoseFromPosition(from, to, up, len);
+                               },
+                               plan, costs[i]);
+    for (const auto& ps : plan) {
+      double* o = poses + 7 * (size_t)at++;
+      o[0] = ps.pose.position.x; o[1] = ps.pose.position.y; o[2] = ps.pose.position.z;
+      o[3] = ps.pose.orientation.x; o[4] = ps.pose.orientation.y; o[5] = ps.pose.orientation.z; o[6] = ps.pose.orientation.w;
+    }
+  }
+  return at;
 }
 
 // cvp_mesh_planner.cpp:920-951 on a given vector field; path in reference list order (seed first)

@@ -72,6 +72,7 @@ uint32_t DijkstraMeshPlanner::makePlan(const PoseStamped& start, const PoseStamp
   mesh_map::Vector start_vec = mesh_map::toVector(start_in_map.pose.position);   // :72
   const mesh_map::Vector goal_vec = mesh_map::toVector(goal_in_map.pose.position);   // :73
   std::list<uint32_t> path;
+  last_goal_ = goal_vec;
   const uint32_t outcome = dijkstra(goal_vec, start_vec, path);               // :81 the wave starts at the goal pose
   path.reverse();                                                             // :83
   std_msgs::msg::Header header;
@@ -87,6 +88,48 @@ uint32_t DijkstraMeshPlanner::makePlan(const PoseStamped& start, const PoseStamp
                                plan, cost);
   // :118-131 publishing (path, "Potential" vertex costs, vector field) is ROS I/O and out of scope here
   return outcome;
+}
+
+uint32_t DijkstraMeshPlanner::makeFleetPlans(const std::vector<PoseStamped>& starts, std::vector<std::vector<PoseStamped>>& plans, std::vector<double>& costs,
+                                             std::vector<uint32_t>& codes, std::string& message)
+{
+  const uint32_t n = (uint32_t)starts.size();
+  plans.assign(n, {}); costs.assign(n, 0.0); codes.assign(n, Result::INTERNAL_ERROR);
+  if (!n) return Result::SUCCESS;
+  if (!dev_ || !dev_->ok()) { message = "no device"; return Result::INTERNAL_ERROR; }
+  // what makePlan does per robot on the host: frame transform, position, nearest vertex (:63-73, :236); the rest is one device call
+  std::vector<uint32_t> slots(n, 0u), vertex(n), lens(n);
+  std::vector<float> pos(3 * (size_t)n);
+  for (uint32_t i = 0; i < n; ++i) {
+    const mesh_map::Vector p = mesh_map::toVector(mesh_map_->transformToMapFrame(starts[i]).pose.position);
+    pos[3 * (size_t)i] = p.x; pos[3 * (size_t)i + 1] = p.y; pos[3 * (size_t)i + 2] = p.z;
+    vertex[i] = mesh_map_->getNearestVertexHandle(p);                         // (kNoHandle: MNAV_INVALID_GOAL, as dijkstra() :242)
+  }
+  const float goal[3] = { last_goal_.x, last_goal_.y, last_goal_.z };
+  std::vector<uint64_t> offsets((size_t)n + 1);
+  std::vector<double> poses;
+  uint64_t total = 0;
+  std::lock_guard<std::recursive_mutex> device_lock(dev_->handle()->mutex);
+  for (int pass = 0; pass < 2; ++pass) {                                      // the sizing call, then the call that fills the buffer
+    const int rc = mnav_fleet_plans(dev_->ctx(), n, slots.data(), vertex.data(), pos.data(), 1, goal, codes.data(), nullptr, nullptr, lens.data(), offsets.data(),
+                                    costs.data(), pass ? poses.data() : nullptr, pass ? total : 0, &total);
+    if (rc < 0) { message = mnav_last_error(dev_->ctx()); codes.assign(n, Result::INTERNAL_ERROR); return Result::INTERNAL_ERROR; }
+    if (rc == 0 || total == 0) break;
+    poses.resize(7 * (size_t)total);
+  }
+  PoseStamped stamped;
+  stamped.header.stamp = node_ ? node_->now() : builtin_interfaces::msg::Time();
+  stamped.header.frame_id = mesh_map_->mapFrame();                            // :87
+  for (uint32_t i = 0; i < n; ++i) {
+    plans[i].assign(lens[i], stamped);
+    for (uint32_t k = 0; k < lens[i]; ++k) {
+      const double* q = poses.data() + 7 * (size_t)(offsets[i] + k);
+      auto& p = plans[i][k].pose;
+      p.position.x = q[0]; p.position.y = q[1]; p.position.z = q[2];
+      p.orientation.x = q[3]; p.orientation.y = q[4]; p.orientation.z = q[5]; p.orientation.w = q[6];
+    }
+  }
+  return Result::SUCCESS;
 }
 
 bool DijkstraMeshPlanner::cancel()                                            // :136-140

@@ -46,6 +46,12 @@ public:
   bool cancel() override;
   bool initialize(const std::string& name, const std::shared_ptr<mesh_map::MeshMap>& mesh_map_ptr,
                   const rclcpp::Node::SharedPtr& node) override;
+  // After a makePlan(start, goal): for every pose of `starts` the plan and the cost makePlan(starts[i], goal) returns, out
+  // of the field that plan left resident (mnav_fleet_plans: no further wave, the pose lists are built on the device), or
+  // codes[i] == MNAV_BEYOND_FIELD where the field cannot answer (plan for that robot).  Returns MNAV_SUCCESS, or
+  // MNAV_INTERNAL_ERROR with `message` set when there is no such field (no plan yet, the costs changed since).
+  uint32_t makeFleetPlans(const std::vector<geometry_msgs::msg::PoseStamped>& starts, std::vector<std::vector<geometry_msgs::msg::PoseStamped>>& plans,
+                          std::vector<double>& costs, std::vector<uint32_t>& codes, std::string& message);
   // V-sized results live on the device; reading them fetches them (20 MB over PCIe at 1M vertices)
   const std::vector<float>& potential() { fetchFields(); return potential_; }
   const std::vector<uint32_t>& predecessors() { fetchFields(); return predecessors_; }
@@ -65,6 +71,7 @@ private:
   std::vector<uint32_t> predecessors_;
   std::vector<float> vector_map_, potential_;
   bool fields_on_host_ = false, eager_fields_ = false;
+  mesh_map::Vector last_goal_;                                        // the goal position of the last makePlan (makeFleetPlans: the last pose looks at it)
   std::unique_ptr<mnav_adapter::MeshMapDevice> dev_;
 };
 }  // namespace dijkstra_mesh_planner

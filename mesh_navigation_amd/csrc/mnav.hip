@@ -110,6 +110,7 @@ __global__ __launch_bounds__(64) void k_backtrack(WalkMesh M, WalkInflation L, c
   ctl[2 * j] = st; ctl[2 * j + 1] = (int32_t)n;
 }
 #include "mnav_fleet.h"      // fleet paths and walks: many robots per resident field (mnav_fleet::; after the locate and follow headers, and after WalkJob)
+#include "mnav_plans.h"      // fleet plans: makePlan's pose lists and costs over those paths and walks (mnav_fleet::, mnav_pose.h)
 namespace {
 
 struct Slot {
@@ -223,6 +224,8 @@ struct mnav_ctx {
   mnav_fol::Staging stage;                                         // follower and rollout: the per-robot inputs of the running call, the two work lists
   mnav_fol::State fol;                                             // vector-field follower: outputs and counters of the last mnav_follow_batch
   mnav_fleet::State fleet;                                         // fleet paths / walks: buffers and statistics of the last mnav_fleet_* call
+  mnav_fleet::PlanState plans;                                     // fleet plans: counts, costs, id / length scratch and packed poses of the last call
+  DevBuf<float> d_fnrm; bool have_face_normals = false;            // MeshMap::faceNormals() (mnav_upload_face_normals): F x 3, gone with the mesh
   mnav_rol::Dev rol;                                               // device rollout: the rest of the resident robot state and statistics of the last mnav_follow_rollout
   mnav_chg::Scratch chg;                                           // obstacle / clearance / border layers: change list and counters of the last call
   mnav_map::State map;                                             // resident layer graph (mnav_map_*): nodes, tables, change lists of the last update
@@ -718,6 +721,7 @@ int mnav_upload_mesh(mnav_ctx* ctx, uint32_t V, uint32_t F, uint32_t E, const fl
   HIPCHK(ctx->d_crn_idx.upload(ctx->stream, ci.data(), ci.size()));
   HIPCHK(ctx->d_xyz.upload(ctx->stream, xyz, 3 * (size_t)V));
   ctx->have_normals = vertex_normals != nullptr;
+  ctx->d_fnrm.reset(); ctx->have_face_normals = false;               // the old mesh's face normals
   HIPCHK(ctx->d_nrm.upload(ctx->stream, vertex_normals, vertex_normals ? 3 * (size_t)V : 0));
   // LDS tiles of the SSSP engine
   {
@@ -1762,6 +1766,7 @@ uint32_t mnav_plan_cvp_batch(mnav_ctx* ctx, uint32_t n, const float* seed_pos, c
 #include "mnav_graph_capi.h"      // mnav_map_configure / _compute / _layer_changed / _update_layer / _obstacle / _stats
 #include "mnav_replan_capi.h"     // mnav_replan_dijkstra_batch, mnav_replan_stats
 #include "mnav_fleet_capi.h"      // mnav_fleet_paths, mnav_fleet_walks, mnav_fleet_stats
+#include "mnav_plans_capi.h"      // mnav_upload_face_normals, mnav_fleet_plans, mnav_fleet_walk_plans
 
 void mnav_cancel(mnav_ctx* ctx)
 {

@@ -54,6 +54,97 @@ static void fleet_clear_stats(mnav_fleet::State& S)
   S.built_index = 0; S.chunks = 0; S.entries = 0; S.ms_kernels = S.ms_total = 0.f;
 }
 
+// The plans of the recorded Dijkstra call as the robots see them (`who` opens the error text).  Every refusal comes before
+// the first device call: a refused call touches nothing.
+static int fleet_fields_of(mnav_ctx* ctx, const std::string& who, uint32_t n, const uint32_t* slots, std::vector<mnav_fleet::Field>& fields)
+{
+  using namespace mnav_fleet;
+  if (check_ready(ctx)) return -1;
+  if (n > 0x7FFFFFFFu) { ctx->err = who + ": too many robots in one call"; return -1; }
+  const mnav_ctx::Replan& R = ctx->rp;
+  const size_t n_slots = R.seeds.size();
+  if (!R.have_call || ctx->last_planner != kPlannerDijkstra || ctx->caller_slot != R.caller_slot || R.caller_slot.size() != n_slots || R.targets.size() != n_slots) {
+    ctx->err = who + ": the last plan call was not a Dijkstra call or replan whose fields are resident"; return -1;
+  }
+  if (R.len || R.all) { ctx->err = who + ": the costs changed since the plan (mnav_replan_dijkstra_batch first)"; return -1; }
+  std::vector<uint8_t> used(n_slots ? n_slots : 1, 0);
+  for (uint32_t i = 0; i < n; ++i) {
+    if (slots[i] >= n_slots) { ctx->err = who + ": slot out of range (not a plan of the last call)"; return -1; }
+    used[slots[i]] = 1;
+  }
+  fields.resize(n_slots);
+  for (size_t s = 0; s < n_slots; ++s) {
+    Field Fd; Fd.dist = nullptr; Fd.pred = nullptr; Fd.seed = R.seeds[s]; Fd.target = R.targets[s]; Fd.cut = INFINITY;
+    Fd.code = R.seeds[s] >= ctx->V ? MNAV_INVALID_START : R.targets[s] >= ctx->V ? MNAV_INVALID_GOAL : MNAV_SUCCESS;   // what the plan call gave a plan it did not run
+    if (used[s] && R.caller_slot[s] != kNone) {
+      // R.usable is the replan's record of "slots[k].dist is the reference's below the cut" (not after the band steps, a failed or cancelled
+      // call, a half-rewound replan); on top of it the predecessors must be resident, which a paths-only call does not leave
+      Fd.dist = static_cast<const float*>(mnav_device_output(ctx, (uint32_t)s, 0));
+      Fd.pred = static_cast<const uint32_t*>(mnav_device_output(ctx, (uint32_t)s, 1));
+      if (!R.usable || !Fd.dist || !Fd.pred) {
+        ctx->err = who + ": predecessors of slot " + std::to_string(s) + " not resident (a paths-only, band-step, failed or cancelled call)"; return -1;
+      }
+    }
+    fields[s] = Fd;
+  }
+  return 0;
+}
+
+// The robots and the plan records go up, k_fleet_cut and k_fleet_len run (codes, hops, potentials, outcome counters, block
+// sums of the hops); ev[0] is recorded in front of the kernels.  *d_vtx: where the robots' vertices are resident.
+static int fleet_classify_robots(mnav_ctx* ctx, uint32_t n, const uint32_t* slots, const uint32_t* start_vertex, const float* start_pos,
+                                 const std::vector<mnav_fleet::Field>& fields, mnav_fleet::Paths& P, const uint32_t** d_vtx)
+{
+  using namespace mnav_fleet;
+  const size_t n_slots = fields.size();
+  if (hipSetDevice(ctx->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return -1; }
+  if (fleet_reserve(ctx, n, n_slots)) return -1;
+  State& S = ctx->fleet;
+  fleet_clear_stats(S);
+  *d_vtx = S.vtx;
+  if (start_vertex) HIPCHK(hipMemcpyAsync(S.vtx, start_vertex, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  else { if (fleet_locate(ctx, n, start_pos)) return -1; *d_vtx = ctx->loc.vtx; }   // the ids stay on the device
+  HIPCHK(hipMemcpyAsync(S.slot, slots, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(S.fields, fields.data(), sizeof(Field) * n_slots, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemsetAsync(S.cnt, 0, sizeof(uint32_t) * (kCounters + 1), ctx->stream));
+  HIPCHK(hipMemsetAsync(S.need, 0, 8 * n_slots, ctx->stream));
+  P = Paths{};
+  P.n = n; P.V = ctx->V; P.slot = S.slot; P.vtx = *d_vtx; P.fields = S.fields; P.code = S.code; P.len = S.len; P.potential = S.potential; P.bsum = S.bsum; P.cnt = S.cnt;
+  P.mark = S.status; P.need = S.need;
+  const uint32_t nb = (n + kFleetBlock - 1) / kFleetBlock;
+  HIPCHK(hipEventRecord(S.ev[0], ctx->stream));
+  hipLaunchKernelGGL(k_fleet_cut, dim3(((uint32_t)n_slots + kFleetBlock - 1) / kFleetBlock), dim3(kFleetBlock), 0, ctx->stream, (uint32_t)n_slots, S.fields.get(), ctx->rp.offset);
+  hipLaunchKernelGGL(k_fleet_len, dim3(nb), dim3(kFleetBlock), 0, ctx->stream, P);
+  return 0;
+}
+
+// After the scan: ev[1], the total and the counters come down; robots the wave never reached under a finite cut are settled
+// (did their plans' waves run out?  rule 5) and S.ms_kernels holds the time so far.
+static int fleet_finish_classify(mnav_ctx* ctx, const mnav_fleet::Paths& P, size_t n_slots, unsigned long long* total, uint32_t* cnt /* kCounters + 1 */)
+{
+  using namespace mnav_fleet;
+  State& S = ctx->fleet;
+  const uint32_t n = P.n, nb = (n + kFleetBlock - 1) / kFleetBlock;
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(S.ev[1], ctx->stream));
+  HIPCHK(hipMemcpyAsync(total, S.off + n, sizeof(*total), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(cnt, S.cnt, sizeof(uint32_t) * (kCounters + 1), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  S.ms_kernels = ev_ms(S.ev[0], S.ev[1]);
+  if (cnt[kCounters]) {
+    HIPCHK(hipEventRecord(S.ev[0], ctx->stream));
+    hipLaunchKernelGGL(k_fleet_open, dim3((uint32_t)n_slots * kOpenBlocks), dim3(kFleetBlock), 0, ctx->stream, (uint32_t)n_slots, ctx->V, S.fields.get(), S.need.get(),
+                       S.need + n_slots);
+    hipLaunchKernelGGL(k_fleet_resolve, dim3(nb), dim3(kFleetBlock), 0, ctx->stream, P, S.need + n_slots);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(S.ev[1], ctx->stream));
+    HIPCHK(hipMemcpyAsync(cnt, S.cnt, sizeof(uint32_t) * (kCounters + 1), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    S.ms_kernels += ev_ms(S.ev[0], S.ev[1]);
+  }
+  return 0;
+}
+
 int mnav_fleet_paths(mnav_ctx* ctx, uint32_t n, const uint32_t* slots, const uint32_t* start_vertex, const float* start_pos, uint32_t* code_out,
                      uint32_t* vertex_out, float* potential_out, uint32_t* len_out, uint64_t* offset_out, uint32_t* ids_out, uint64_t ids_cap,
                      uint64_t* total_out)
@@ -66,72 +157,17 @@ int mnav_fleet_paths(mnav_ctx* ctx, uint32_t n, const uint32_t* slots, const uin
   // every refusal comes before the first device call: a refused call touches nothing
   if (!slots) { ctx->err = "fleet paths: null slots"; return -1; }
   if (!start_vertex && !start_pos) { ctx->err = "fleet paths: neither start vertices nor start positions"; return -1; }
-  if (check_ready(ctx)) return -1;
-  if (n > 0x7FFFFFFFu) { ctx->err = "fleet paths: too many robots in one call"; return -1; }
-  const mnav_ctx::Replan& R = ctx->rp;
-  const size_t n_slots = R.seeds.size();
-  if (!R.have_call || ctx->last_planner != kPlannerDijkstra || ctx->caller_slot != R.caller_slot || R.caller_slot.size() != n_slots || R.targets.size() != n_slots) {
-    ctx->err = "fleet paths: the last plan call was not a Dijkstra call or replan whose fields are resident"; return -1;
-  }
-  if (R.len || R.all) { ctx->err = "fleet paths: the costs changed since the plan (mnav_replan_dijkstra_batch first)"; return -1; }
-  std::vector<uint8_t> used(n_slots ? n_slots : 1, 0);
-  for (uint32_t i = 0; i < n; ++i) {
-    if (slots[i] >= n_slots) { ctx->err = "fleet paths: slot out of range (not a plan of the last call)"; return -1; }
-    used[slots[i]] = 1;
-  }
-  std::vector<Field> fields(n_slots);
-  for (size_t s = 0; s < n_slots; ++s) {
-    Field Fd; Fd.dist = nullptr; Fd.pred = nullptr; Fd.seed = R.seeds[s]; Fd.target = R.targets[s]; Fd.cut = INFINITY;
-    Fd.code = R.seeds[s] >= ctx->V ? MNAV_INVALID_START : R.targets[s] >= ctx->V ? MNAV_INVALID_GOAL : MNAV_SUCCESS;   // what the plan call gave a plan it did not run
-    if (used[s] && R.caller_slot[s] != kNone) {
-      // R.usable is the replan's record of "slots[k].dist is the reference's below the cut" (not after the band steps, a failed or cancelled
-      // call, a half-rewound replan); on top of it the predecessors must be resident, which a paths-only call does not leave
-      Fd.dist = static_cast<const float*>(mnav_device_output(ctx, (uint32_t)s, 0));
-      Fd.pred = static_cast<const uint32_t*>(mnav_device_output(ctx, (uint32_t)s, 1));
-      if (!R.usable || !Fd.dist || !Fd.pred) {
-        ctx->err = "fleet paths: predecessors of slot " + std::to_string(s) + " not resident (a paths-only, band-step, failed or cancelled call)"; return -1;
-      }
-    }
-    fields[s] = Fd;
-  }
-  if (hipSetDevice(ctx->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return -1; }
-  if (fleet_reserve(ctx, n, n_slots)) return -1;
-  State& S = ctx->fleet;
-  fleet_clear_stats(S);
-  const uint32_t* d_vtx = S.vtx;
-  if (start_vertex) HIPCHK(hipMemcpyAsync(S.vtx, start_vertex, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-  else { if (fleet_locate(ctx, n, start_pos)) return -1; d_vtx = ctx->loc.vtx; }   // the ids stay on the device
-  HIPCHK(hipMemcpyAsync(S.slot, slots, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(S.fields, fields.data(), sizeof(Field) * n_slots, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemsetAsync(S.cnt, 0, sizeof(uint32_t) * (kCounters + 1), ctx->stream));
-  HIPCHK(hipMemsetAsync(S.need, 0, 8 * n_slots, ctx->stream));
+  std::vector<Field> fields;
+  if (fleet_fields_of(ctx, "fleet paths", n, slots, fields)) return -1;
   Paths P{};
-  P.n = n; P.V = ctx->V; P.slot = S.slot; P.vtx = d_vtx; P.fields = S.fields; P.code = S.code; P.len = S.len; P.potential = S.potential; P.bsum = S.bsum; P.cnt = S.cnt;
-  P.mark = S.status; P.need = S.need;
+  const uint32_t* d_vtx = nullptr;
+  if (fleet_classify_robots(ctx, n, slots, start_vertex, start_pos, fields, P, &d_vtx)) return -1;
+  State& S = ctx->fleet;
   const uint32_t nb = (n + kFleetBlock - 1) / kFleetBlock;
-  HIPCHK(hipEventRecord(S.ev[0], ctx->stream));
-  hipLaunchKernelGGL(k_fleet_cut, dim3(((uint32_t)n_slots + kFleetBlock - 1) / kFleetBlock), dim3(kFleetBlock), 0, ctx->stream, (uint32_t)n_slots, S.fields.get(), R.offset);
-  hipLaunchKernelGGL(k_fleet_len, dim3(nb), dim3(kFleetBlock), 0, ctx->stream, P);
   hipLaunchKernelGGL(k_fleet_scan, dim3(1), dim3(kFleetBlock), 0, ctx->stream, nb, S.bsum.get(), (const unsigned long long*)nullptr, S.off + n);
   hipLaunchKernelGGL(k_fleet_offsets, dim3(nb), dim3(kFleetBlock), 0, ctx->stream, n, S.len.get(), S.bsum.get(), S.off.get());
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(S.ev[1], ctx->stream));
   unsigned long long total = 0; uint32_t cnt[kCounters + 1] = {};
-  HIPCHK(hipMemcpyAsync(&total, S.off + n, sizeof(total), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipMemcpyAsync(cnt, S.cnt, sizeof(cnt), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  S.ms_kernels = ev_ms(S.ev[0], S.ev[1]);
-  if (cnt[kCounters]) {                                               // robots the wave never reached under a finite cut: did their plans' waves run out? (rule 5)
-    HIPCHK(hipEventRecord(S.ev[0], ctx->stream));
-    hipLaunchKernelGGL(k_fleet_open, dim3((uint32_t)n_slots * kOpenBlocks), dim3(kFleetBlock), 0, ctx->stream, (uint32_t)n_slots, ctx->V, S.fields.get(), S.need.get(),
-                       S.need + n_slots);
-    hipLaunchKernelGGL(k_fleet_resolve, dim3(nb), dim3(kFleetBlock), 0, ctx->stream, P, S.need + n_slots);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(S.ev[1], ctx->stream));
-    HIPCHK(hipMemcpyAsync(cnt, S.cnt, sizeof(cnt), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    S.ms_kernels += ev_ms(S.ev[0], S.ev[1]);
-  }
+  if (fleet_finish_classify(ctx, P, fields.size(), &total, cnt)) return -1;
   const bool fits = ids_out && total <= ids_cap;
   if (fits && total) {
     if (total > S.ids_cap) {
@@ -159,10 +195,40 @@ int mnav_fleet_paths(mnav_ctx* ctx, uint32_t n, const uint32_t* slots, const uin
   return fits ? 0 : 1;
 }
 
-int mnav_fleet_walks(mnav_ctx* ctx, uint32_t n, const uint32_t* slots, uint32_t n_plans, const float* seed_pos, const uint32_t* seed_faces,
-                     const float* start_pos, const uint32_t* start_faces, double step_width, int32_t inflation_layer, uint32_t walk_cap,
-                     int32_t* status_out, uint32_t* start_face_out, uint32_t* len_out, uint64_t* offset_out, float* positions_out, uint32_t* faces_out,
-                     uint64_t entries_cap, uint64_t* total_out)
+// buffers of the fleet plans calls: per robot, per plan, per pose of the scratch (ids and lengths), per pose of the output
+static int plans_reserve(mnav_ctx* ctx, size_t n, size_t n_plans, unsigned long long scratch, unsigned long long poses)
+{
+  mnav_fleet::PlanState& PS = ctx->plans;
+  const char* oom = "fleet plans: out of device memory";
+  if (n > PS.cap) {
+    PS.cap = 0;
+    if (alloc_group(PS.count, 4 * n, PS.cost, 8 * n) != hipSuccess) { ctx->err = oom; return -1; }
+    PS.cap = n;
+  }
+  if (n_plans > PS.slots_cap) {
+    PS.slots_cap = 0;
+    if (alloc_group(PS.goal, 12 * n_plans, PS.goal_pose, sizeof(double) * mnav_fleet::kPoseDoubles * n_plans) != hipSuccess) { ctx->err = oom; return -1; }
+    PS.slots_cap = n_plans;
+  }
+  if (scratch > PS.scratch_cap) {
+    PS.scratch_cap = 0;
+    if (alloc_group(PS.ids, 4 * (size_t)scratch, PS.lengths, 4 * (size_t)scratch) != hipSuccess) { ctx->err = oom; return -1; }
+    PS.scratch_cap = scratch;
+  }
+  if (poses > PS.poses_cap) {
+    PS.poses_cap = 0;
+    if (PS.poses.alloc(sizeof(double) * mnav_fleet::kPoseDoubles * (size_t)poses) != hipSuccess) { ctx->err = oom; return -1; }
+    PS.poses_cap = poses;
+  }
+  return 0;
+}
+
+// mnav_fleet_walks (plans == false: the packed rows go to positions_out / faces_out) and mnav_fleet_walk_plans (plans ==
+// true: their poses to poses_out, their costs to cost_out): one walk, two ways out
+static int fleet_walks_run(mnav_ctx* ctx, bool plans, uint32_t n, const uint32_t* slots, uint32_t n_plans, const float* seed_pos, const uint32_t* seed_faces,
+                           const double* goal_pose, const float* start_pos, const uint32_t* start_faces, double step_width, int32_t inflation_layer,
+                           uint32_t walk_cap, int32_t* status_out, uint32_t* start_face_out, uint32_t* len_out, uint64_t* offset_out, float* positions_out,
+                           uint32_t* faces_out, double* cost_out, double* poses_out, uint64_t entries_cap, uint64_t* total_out)
 {
   using namespace mnav_fleet;
   if (!ctx) return -1;
@@ -170,8 +236,9 @@ int mnav_fleet_walks(mnav_ctx* ctx, uint32_t n, const uint32_t* slots, uint32_t 
   if (!n) return 0;
   const auto t0 = std::chrono::steady_clock::now();
   // every refusal comes before the first device call: a refused call touches nothing
-  if (!slots || !seed_pos || !seed_faces || !start_pos) { ctx->err = "fleet walks: null argument"; return -1; }
+  if (!slots || !seed_pos || !seed_faces || !start_pos || (plans && !goal_pose)) { ctx->err = "fleet walks: null argument"; return -1; }
   if (!ctx->have_mesh) { ctx->err = "mnav_upload_mesh has not been called"; return -1; }
+  if (plans && !ctx->have_face_normals) { ctx->err = "fleet walk plans: face normals are not resident (mnav_upload_face_normals)"; return -1; }
   if (n > 0x7FFFFFFFu) { ctx->err = "fleet walks: too many robots in one call"; return -1; }
   if (walk_cap < 2 || walk_cap > (1u << 24)) { ctx->err = "fleet walks: walk_cap out of range (2 .. 2^24)"; return -1; }
   if (!(step_width > 0.0)) { ctx->err = "step_width must be positive"; return -1; }   // a zero step never leaves the start
@@ -220,12 +287,17 @@ int mnav_fleet_walks(mnav_ctx* ctx, uint32_t n, const uint32_t* slots, uint32_t 
         hipSuccess) { ctx->err = "fleet walks: out of device memory"; return -1; }
     S.rows = chunk; S.row_entries = walk_cap;
   }
-  const bool want = positions_out || faces_out;
+  const bool want = plans ? poses_out != nullptr : (positions_out || faces_out);
   const unsigned long long out_cap = want ? std::min<unsigned long long>(entries_cap, (unsigned long long)n * walk_cap) : 0ull;
-  if (out_cap > S.out_cap) {
+  if (!plans && out_cap > S.out_cap) {
     S.out_cap = 0;
     if (alloc_group(S.out_pos, 12 * (size_t)out_cap, S.out_face, 4 * (size_t)out_cap) != hipSuccess) { ctx->err = "fleet walks: out of device memory"; return -1; }
     S.out_cap = out_cap;
+  }
+  PlanState& PS = ctx->plans;
+  if (plans) {
+    if (plans_reserve(ctx, n, n_plans, 0, out_cap)) return -1;
+    HIPCHK(hipMemcpyAsync(PS.goal_pose, goal_pose, sizeof(double) * kPoseDoubles * (size_t)n_plans, hipMemcpyHostToDevice, ctx->stream));
   }
   const float* d_pos = S.pos; const uint32_t* d_face = S.face;
   if (start_faces) {
@@ -244,7 +316,12 @@ int mnav_fleet_walks(mnav_ctx* ctx, uint32_t n, const uint32_t* slots, uint32_t 
     hipLaunchKernelGGL(k_fleet_walk_len, dim3(nb), dim3(kFleetBlock), 0, ctx->stream, c, ctx->F, d_face + a, S.ctl.get(), S.status + a, S.len + a, S.bsum.get(), S.cnt.get());
     hipLaunchKernelGGL(k_fleet_scan, dim3(1), dim3(kFleetBlock), 0, ctx->stream, nb, S.bsum.get(), a ? S.off + a : (const unsigned long long*)nullptr, S.off + a + c);
     hipLaunchKernelGGL(k_fleet_offsets, dim3(nb), dim3(kFleetBlock), 0, ctx->stream, c, S.len + a, S.bsum.get(), S.off + a);
-    if (out_cap)
+    if (plans) {                                                      // the rows are robot first already: poses and costs straight from them
+      hipLaunchKernelGGL(k_walk_cost, dim3(nb), dim3(kFleetBlock), 0, ctx->stream, c, walk_cap, S.row_pos.get(), S.len + a, PS.cost + a);
+      if (out_cap)
+        hipLaunchKernelGGL(k_walk_poses, dim3(c), dim3(64), 0, ctx->stream, walk_cap, ctx->F, S.row_pos.get(), S.row_face.get(), S.slot + a, S.len + a, S.off + a,
+                           ctx->d_fnrm.get(), PS.goal_pose.get(), PS.poses.get(), out_cap);
+    } else if (out_cap)
       hipLaunchKernelGGL(k_fleet_pack, dim3(c), dim3(64), 0, ctx->stream, walk_cap, S.row_pos.get(), S.row_face.get(), S.len + a, S.off + a, S.out_pos.get(), S.out_face.get(), out_cap);
     HIPCHK(hipGetLastError());
     ++S.chunks;
@@ -256,7 +333,9 @@ int mnav_fleet_walks(mnav_ctx* ctx, uint32_t n, const uint32_t* slots, uint32_t 
   HIPCHK(hipStreamSynchronize(ctx->stream));
   S.ms_kernels = ev_ms(S.ev[0], S.ev[1]);
   const bool fits = want && total <= entries_cap;
-  if (fits && total) {                                                // two dense copies
+  if (fits && total && plans) HIPCHK(hipMemcpyAsync(poses_out, PS.poses, sizeof(double) * kPoseDoubles * (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
+  if (plans && cost_out) HIPCHK(hipMemcpyAsync(cost_out, PS.cost, 8 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  if (fits && total && !plans) {                                      // two dense copies
     if (positions_out) HIPCHK(hipMemcpyAsync(positions_out, S.out_pos, 12 * (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
     if (faces_out) HIPCHK(hipMemcpyAsync(faces_out, S.out_face, 4 * (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
   }
@@ -270,6 +349,15 @@ int mnav_fleet_walks(mnav_ctx* ctx, uint32_t n, const uint32_t* slots, uint32_t 
   S.entries = total;
   S.ms_total = (float)(1e-3 * (double)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count());
   return fits ? 0 : 1;
+}
+
+int mnav_fleet_walks(mnav_ctx* ctx, uint32_t n, const uint32_t* slots, uint32_t n_plans, const float* seed_pos, const uint32_t* seed_faces,
+                     const float* start_pos, const uint32_t* start_faces, double step_width, int32_t inflation_layer, uint32_t walk_cap,
+                     int32_t* status_out, uint32_t* start_face_out, uint32_t* len_out, uint64_t* offset_out, float* positions_out, uint32_t* faces_out,
+                     uint64_t entries_cap, uint64_t* total_out)
+{
+  return fleet_walks_run(ctx, false, n, slots, n_plans, seed_pos, seed_faces, nullptr, start_pos, start_faces, step_width, inflation_layer, walk_cap, status_out,
+                         start_face_out, len_out, offset_out, positions_out, faces_out, nullptr, nullptr, entries_cap, total_out);
 }
 
 int mnav_fleet_stats(const mnav_ctx* ctx, uint32_t* served, uint32_t* beyond_field, uint32_t* no_path, uint32_t* invalid, uint64_t* entries,

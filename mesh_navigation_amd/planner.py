@@ -30,6 +30,8 @@ def _load():
         L.mnav_adapter_destroy.argtypes = [vp]
         L.mnav_adapter_make_plan.restype = u32
         L.mnav_adapter_make_plan.argtypes = [vp, vp, vp, vp, u32, C.POINTER(u32), C.POINTER(f64), C.c_char_p, u32]
+        L.mnav_adapter_make_fleet_plans.restype = u32
+        L.mnav_adapter_make_fleet_plans.argtypes = [vp, u32, vp, vp, vp, vp, vp, C.c_uint64, C.POINTER(C.c_uint64), C.c_char_p, u32]
         L.mnav_adapter_cancel.restype = C.c_int
         L.mnav_adapter_cancel.argtypes = [vp]
         L.mnav_adapter_set_costs.argtypes = [vp, vp, vp]
@@ -154,6 +156,22 @@ class _MeshPlanner:
 class DijkstraMeshPlanner(_MeshPlanner):
     """dijkstra_mesh_planner/DijkstraMeshPlanner (dijkstra_mesh_planner.xml:1-8)."""
     KIND = 0
+
+    def makeFleetPlans(self, start_poses, poses_cap: int = 1 << 20):
+        """After a makePlan(start, goal): what makePlan(start_poses[i], goal) returns for every row of start_poses, out of the
+        field that plan left on the device.  Returns (code, codes, plans, costs, message): plans[i] is an (m, 7) array;
+        codes[i] == capi.BEYOND_FIELD where the field cannot answer."""
+        s = np.ascontiguousarray(start_poses, np.float64).reshape(-1, 7)
+        n = s.shape[0]
+        codes, lens, costs = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.float64)
+        poses = np.empty((int(poses_cap), 7), np.float64)
+        total = C.c_uint64(0)
+        msg = C.create_string_buffer(512)
+        code = _load().mnav_adapter_make_fleet_plans(self._h, n, _p(s), _p(codes), _p(lens), _p(costs), _p(poses), poses.shape[0], C.byref(total), msg, 512)
+        if total.value > poses.shape[0]:
+            raise ValueError("makeFleetPlans: poses_cap too small for %d poses" % total.value)
+        off = np.concatenate([[0], np.cumsum(lens.astype(np.int64))])
+        return int(code), codes, [poses[off[i]: off[i + 1]].copy() for i in range(n)], costs, msg.value.decode()
 
 
 class CVPMeshPlanner(_MeshPlanner):
