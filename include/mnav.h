@@ -409,6 +409,37 @@ uint32_t mnav_replan_plans(const mnav_ctx* ctx);
 int mnav_replan_stats(const mnav_ctx* ctx, uint32_t* reason, uint32_t* log_len, float* levels_out, uint64_t* kept, uint64_t* rewound,
                       uint32_t* tiles_woken, uint32_t* rounds, float* ms_level, float* ms_rewind, float* ms_rounds, float* ms_finalize);
 
+/* The replan plan by plan: arguments, outputs, refusals and the whole-call reasons 1, 2 and 3 of mnav_replan_dijkstra_batch, and
+ * every output -- codes, paths, dist_out, pred_out, the resident dist / pred / vector map of every slot, the settled count --
+ * is again bit for bit that of a fresh plan on the resident map.  What differs is how each plan gets there.  With L the
+ * plan's rewind level, cut its old cut and f the option replan_fresh_below, the first match decides, per plan, on the device:
+ *   KEPT (0)      no logged vertex has a value at or below the cut in its closed one-ring (L == cut, and no such value AT the
+ *                 cut: it may belong to an expanded source), the new target is the recorded one, the offset has the recorded
+ *                 bits and the resident field went through a finalize pass (the last call asked for fields or kept the
+ *                 vector maps resident, or was a replan; never slot 0 after an inflation wave worked in it).  Nothing of the
+ *                 plan is written; its path and settled count are read from what is resident.
+ *   FRESH (2)     f > 0, the cut is finite and positive and L / cut < f: planned afresh, all FRESH plans as one batch in their
+ *                 own slots, on the engine `auto` picks for their number.
+ *   REPAIRED (1)  everything else: the rewind, the tile rounds and the finalize pass of mnav_replan_dijkstra_batch, over
+ *                 these plans only.
+ * When more than the share replan_each_fresh_share of the plans is FRESH (default 0.004, measured; 1: never) the whole call plans afresh
+ * (reason 4), as it does for reasons 1 to 3.  After the call the change log starts over and mnav_follow_batch,
+ * mnav_follow_rollout, the mnav_fleet_* calls, mnav_download_output and a further replan work on every slot, KEPT ones
+ * included.  DESIGN.md section 3.14. */
+uint32_t mnav_replan_dijkstra_each(mnav_ctx* ctx, uint32_t n, const uint32_t* targets, double goal_dist_offset, uint32_t* codes_out,
+                                   float* dist_out, uint32_t* pred_out, uint32_t* path_out, uint32_t path_cap, uint32_t* path_len);
+/* The last mnav_replan_dijkstra_each.  reason: as in mnav_replan_stats (4: the share policy); whole_fresh: 1 when the whole
+ * call planned afresh; log_len: logged ids at entry.  Whenever the classes were taken (reason 0, and reason 4): classes_out
+ * (n bytes, caller's order: 0 KEPT, 1 REPAIRED, 2 FRESH), levels_out (n floats) and counts[3] (KEPT, REPAIRED, FRESH).  For
+ * reason 0: owned vertices kept and rewound from a finite value and tiles woken, summed over the REPAIRED plans; round
+ * launches; fresh_engine: the value mnav_last_engine would give for the FRESH batch, -1 without one; ms[5]: device
+ * milliseconds of level + classify + gather, the rewind, the rounds and the finalize pass, and host milliseconds of the FRESH
+ * batch.  Any pointer may be NULL.  mnav_last_engine after a reason-0 call: 256 + 128 (tile rounds ran) + the FRESH batch's
+ * engine (127: none). */
+int mnav_replan_each_stats(const mnav_ctx* ctx, uint32_t* reason, uint32_t* whole_fresh, uint32_t* log_len, uint8_t* classes_out,
+                           float* levels_out, uint32_t* counts, uint64_t* kept, uint64_t* rewound, uint32_t* tiles_woken, uint32_t* rounds,
+                           int32_t* fresh_engine, float* ms);
+
 /* -- pose lookup on the device ---------------------------------------------------------------------
  * MeshMap::getNearestVertexHandle (mesh_map.cpp:1161-1174) and MeshMap::getContainingFace / searchContainingFace
  * (:1120-1159) for n positions (pos: n*3 floats) in one call; only the positions go up and the results come down.

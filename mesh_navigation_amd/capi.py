@@ -36,7 +36,7 @@ SYMBOLS = [
     "mnav_locate", "mnav_locate_stats", "mnav_plan_dijkstra_batch_at", "mnav_plan_cvp_batch_at",
     "mnav_follow_batch", "mnav_follow_stats", "mnav_follow_rollout", "mnav_rollout_stats",
     "mnav_map_configure", "mnav_map_compute", "mnav_map_layer_changed", "mnav_map_update_layer", "mnav_map_obstacle", "mnav_map_stats",
-    "mnav_replan_dijkstra_batch", "mnav_replan_plans", "mnav_replan_stats",
+    "mnav_replan_dijkstra_batch", "mnav_replan_plans", "mnav_replan_stats", "mnav_replan_dijkstra_each", "mnav_replan_each_stats",
     "mnav_fleet_paths", "mnav_fleet_walks", "mnav_fleet_stats",
     "mnav_upload_face_normals", "mnav_fleet_plans", "mnav_fleet_walk_plans",
     "mnav_set_option", "mnav_get_option", "mnav_shard_set_goal_tie", "mnav_last_engine",
@@ -210,6 +210,11 @@ def load(path: str | None = None):
     L.mnav_map_stats.argtypes = [vp] + [C.POINTER(u32)] * 4 + [C.POINTER(C.c_float)] * 2
     L.mnav_replan_dijkstra_batch.restype = u32
     L.mnav_replan_dijkstra_batch.argtypes = [vp, u32, vp, f64, vp, vp, vp, vp, u32, vp]
+    L.mnav_replan_dijkstra_each.restype = u32
+    L.mnav_replan_dijkstra_each.argtypes = [vp, u32, vp, f64, vp, vp, vp, vp, u32, vp]
+    L.mnav_replan_each_stats.restype = C.c_int
+    L.mnav_replan_each_stats.argtypes = ([vp] + [C.POINTER(u32)] * 3 + [vp, vp, vp] + [C.POINTER(C.c_uint64)] * 2 + [C.POINTER(u32)] * 2
+                                         + [C.POINTER(C.c_int32), vp])
     L.mnav_replan_plans.restype = u32
     L.mnav_replan_plans.argtypes = [vp]
     L.mnav_replan_stats.restype = C.c_int
@@ -371,6 +376,11 @@ class CvpOut:
     cutface: np.ndarray | None
     vecmap: np.ndarray | None
     stats: dict
+
+
+def _engine_name(e: int) -> str:
+    return {0: "k_tile_round (tile rounds)", 1: "k_step (band steps)", 5: "k_tb_solve_q (tile-batch engine, quarters of a wave, distances in LDS)",
+            21: "k_tbv_solve (tile-batch engine, one wave per tile, distances in VGPRs)", 6: "k_plan_async (asynchronous tile engine)"}.get(e, "none")
 
 
 class MnavContext:
@@ -825,8 +835,10 @@ class MnavContext:
     def last_engine(self) -> str:
         """Engine / kernel of the last Dijkstra call, by name (mnav_last_engine)."""
         e = int(self._L.mnav_last_engine(self._h))
-        return {0: "k_tile_round (tile rounds)", 1: "k_step (band steps)", 5: "k_tb_solve_q (tile-batch engine, quarters of a wave, distances in LDS)",
-                21: "k_tbv_solve (tile-batch engine, one wave per tile, distances in VGPRs)", 6: "k_plan_async (asynchronous tile engine)"}.get(e, "none")
+        if e >= 256:                                                   # replan_dijkstra_each: the repair's rounds and / or the FRESH batch's engine
+            ran = (["k_tile_round (tile rounds)"] if e & 128 else []) + ([_engine_name(e & 127)] if (e & 127) != 127 else [])
+            return " + ".join(ran) if ran else "none (every plan kept)"
+        return _engine_name(e)
 
     def timing(self) -> dict:
         """Event timings of the last call; never triggers the (lazy) settled-vertex count of a tile-batch call."""
@@ -921,6 +933,47 @@ class MnavContext:
         lease.append(weakref.ref(rows))
         return dict(rc=rc, codes=codes, dist=dist, pred=pred, paths=rows, path_len=lens, stats=self.stats() if want_stats else self.timing(),
                     replan=self.replan_stats(n) if want_stats else None)
+
+    def replan_dijkstra_each(self, targets=None, goal_dist_offset: float = 0.3, want_dist: bool = False, want_pred: bool = False,
+                             path_cap: int | None = None, want_stats: bool = True):
+        """replan_dijkstra plan by plan (mnav_replan_dijkstra_each, include/mnav.h): every plan of the last Dijkstra call is kept
+        as it is, repaired or planned afresh, whatever its own field needs; the outputs are those of plan_dijkstra_batch on the
+        resident map.  The same dict as replan_dijkstra plus `each` = replan_each_stats()."""
+        n = int(self._L.mnav_replan_plans(self._h)) if targets is None else int(_u32(targets).shape[0])
+        tg = None if targets is None else _u32(targets)
+        V = self.V
+        cap = int(path_cap if path_cap is not None else V)
+        codes = np.empty(n, np.uint32)
+        dist = np.empty((n, V), np.float32) if want_dist else None
+        pred = np.empty((n, V), np.uint32) if want_pred else None
+        paths, lease = self._lease_paths(n, cap)
+        lens = np.zeros(n, np.uint32)
+        rc = self._L.mnav_replan_dijkstra_each(self._h, n, _p(tg), float(goal_dist_offset), _p(codes), _p(dist), _p(pred), _p(paths), cap, _p(lens))
+        if rc == INTERNAL_ERROR:
+            raise RuntimeError(f"mnav_replan_dijkstra_each internal error: {self._err()}")
+        rows = _PathRows(paths, lens, cap)
+        lease.append(weakref.ref(rows))
+        return dict(rc=rc, codes=codes, dist=dist, pred=pred, paths=rows, path_len=lens, stats=self.stats() if want_stats else self.timing(),
+                    replan=self.replan_stats(n) if want_stats else None, each=self.replan_each_stats(n) if want_stats else None)
+
+    def replan_each_stats(self, n: int = 0) -> dict:
+        """The last replan_dijkstra_each call (mnav_replan_each_stats); n: its plan count, for the classes (0 KEPT, 1 REPAIRED,
+        2 FRESH) and rewind levels in the caller's order."""
+        r, wf, ll, tw, rd = (C.c_uint32() for _ in range(5))
+        k, w = C.c_uint64(), C.c_uint64()
+        fe = C.c_int32()
+        counts = np.zeros(3, np.uint32)
+        ms = np.zeros(5, np.float32)
+        self._L.mnav_replan_each_stats(self._h, C.byref(r), C.byref(wf), C.byref(ll), None, None, _p(counts), C.byref(k), C.byref(w), C.byref(tw),
+                                       C.byref(rd), C.byref(fe), _p(ms))
+        cls = lv = None
+        if n and int(counts.sum()) == n:
+            cls, lv = np.zeros(n, np.uint8), np.zeros(n, np.float32)
+            self._L.mnav_replan_each_stats(self._h, None, None, None, _p(cls), _p(lv), *([None] * 7))
+        return dict(reason=r.value, whole_fresh=bool(wf.value), log_len=ll.value, classes=cls, levels=lv, kept_plans=int(counts[0]),
+                    repaired_plans=int(counts[1]), fresh_plans=int(counts[2]), kept=k.value, rewound=w.value, tiles_woken=tw.value,
+                    rounds=rd.value, fresh_engine=_engine_name(fe.value) if fe.value >= 0 else None, ms_classify=float(ms[0]),
+                    ms_rewind=float(ms[1]), ms_rounds=float(ms[2]), ms_finalize=float(ms[3]), ms_fresh=float(ms[4]))
 
     def replan_stats(self, n: int = 0) -> dict:
         """The last replan_dijkstra call (mnav_replan_stats); n: its plan count, for the rewind levels (reason 0 only)."""

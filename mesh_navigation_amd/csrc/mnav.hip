@@ -85,6 +85,7 @@ constexpr int kChunk = 96;  // step launches per graph replay; multiple of 6 (sl
 #include "mnav_follow.h"     // vector-field follower: one controller tick for a batch of robots over the resident fields (mnav_fol::)
 #include "mnav_rollout.h"    // device rollouts: many controller ticks per call over resident robot state (mnav_rol::)
 #include "mnav_replan.h"     // replan on a resident potential: rewind level from the change log, rewind with the tiles' wake-up words (k_replan_*)
+#include "mnav_replan_each.h"  // the per-plan replan: class of every plan, ordered lists, compacted records (k_replan_classify, k_replan_gather)
 #include "mnav_graph.h"      // resident layer graph: node passes with change lists, id-list union, combination into a slot (mnav_map::)
 
 // One back-tracking job: the plan's resident vector map and the two ends of the walk.
@@ -250,11 +251,25 @@ struct mnav_ctx {
     // the last Dijkstra call, in the caller's order; which device slot each plan ran in; whether slots[k].dist holds a field to rewind
     std::vector<uint32_t> seeds, targets, caller_slot; double cost_limit = 1.0, offset = 0.0; bool have_call = false, usable = false;
     bool partial = false;            // the last Dijkstra call went through, but a plan of it never reached the device (rejected ids, seed == target)
+    bool finalized = false;          // the fields of the last call went through a finalize pass (not a paths-only call): what mnav_replan_dijkstra_each may keep
+    bool slot0_taken = false;        // an inflation wave has worked in slot 0 since
+    bool vec_resident = false;       // ... and left the vector maps of its plans resident
+    int each_engines = 0;            // mnav_last_engine after mnav_replan_dijkstra_each repaired per plan: 256 + (128: tile rounds ran) + (engine of the FRESH sub-batch, 127: none)
     DevBuf<uint32_t> d_level, d_old_target; DevBuf<float> d_cut; DevBuf<ReplanCnt> d_cnt; uint32_t cap = 0;
     Event ev[5]; bool have_ev = false;
     // statistics of the last replan call (mnav_replan_stats)
     uint32_t reason = 0, stat_log_len = 0, tiles_woken = 0, rounds = 0; uint64_t kept = 0, rewound = 0; std::vector<float> levels;
     float ms_level = 0.f, ms_rewind = 0.f, ms_rounds = 0.f, ms_finalize = 0.f;
+    // mnav_replan_dijkstra_each: classes, lists and the compacted tables of the plans that go on; its statistics
+    struct Each {
+      DevBuf<uint8_t> d_cls; DevBuf<float> d_ratio; DevBuf<uint32_t> d_lists, d_counts, d_level;
+      DevBuf<Plan> d_plans; DevBuf<TilePlan> d_tplans; DevBuf<float*> d_vecptrs; DevBuf<ReplanCnt> d_cnt; DevBuf<TCtl> d_tctl; DevBuf<PlanResult> d_res;
+      uint32_t cap = 0;
+      Event ev[7]; bool have_ev = false;
+      uint32_t reason = 0, whole_fresh = 0, log_len = 0, counts[3] = { 0, 0, 0 }, tiles_woken = 0, rounds = 0; int fresh_engine = -1;
+      uint64_t kept = 0, rewound = 0; std::vector<uint8_t> cls; std::vector<float> levels;
+      float ms_classify = 0.f, ms_rewind = 0.f, ms_rounds = 0.f, ms_finalize = 0.f, ms_fresh = 0.f;
+    } each;
   } rp;
   uint32_t last_planner = 0, last_n = 0;
   std::vector<uint32_t> last_target; double last_offset = 0.0;   // Dijkstra: robot vertex per device slot, goal_dist_offset of the last call
@@ -1105,6 +1120,7 @@ static int layer_inflation_impl(mnav_ctx* ctx, uint32_t layer, uint32_t input_la
   if (ensure_slots(ctx, 1, true, true, false)) return -1;
   Slot& s = ctx->slots[0];
   ctx->caller_slot.assign(1, kNone);                                // the wave works in plan slot 0: the last plan's resident outputs are gone
+  ctx->rp.slot0_taken = true;                                       // (its predecessors: a replan re-derives them, and keeps no plan in slot 0 as it is)
   ctx->shard.finalized = false;
   Plan P;
   memset(&P, 0, sizeof(P));
@@ -1359,11 +1375,18 @@ int mnav_combine_layers_update(mnav_ctx* ctx, int mode, uint32_t n_layers, const
 
 // The tail of a Dijkstra call whose engine (and, unless the call is paths-only, finalize pass) has run: vertex paths, result
 // records, the vector map, the downloads and the statistics of m device plans; map: device plan -> caller's index.
+// sub (the per-plan replan, finalized plans only): the m plans are those of compacted tables -- the first n_vec of them get a
+// vector map, the rest (fields nobody rewound) have their settled vertices counted, and plan k lives in slot sub->slot[k].
 // Returns 0 or -1 (ctx->err set).
+struct TailSub { const Plan* plans; PlanResult* res; float* const* vecptrs; uint32_t n_vec; const uint32_t* slot; };
 static int dijkstra_tail(mnav_ctx* ctx, uint32_t m, int engine, const std::vector<uint32_t>& map, std::vector<uint32_t>& codes, float* dist_out,
-                         uint32_t* pred_out, uint32_t* path_out, uint32_t path_cap, uint32_t* path_len, float* vecmap_out, bool want_vecmap)
+                         uint32_t* pred_out, uint32_t* path_out, uint32_t path_cap, uint32_t* path_len, float* vecmap_out, bool want_vecmap,
+                         const TailSub* sub = nullptr)
 {
   const uint32_t V = ctx->V;
+  const Plan* const d_plans = sub ? sub->plans : ctx->d_plans.get();
+  PlanResult* const d_res = sub ? sub->res : ctx->d_res.get();
+  const uint32_t n_vec = sub ? sub->n_vec : m;
   const PathRows rows1{ ctx->d_paths, ctx->path_stride, nullptr, nullptr };
   PathRows rows2{ nullptr, 0u, nullptr, nullptr };
   const uint32_t gc = (V + kBlock * 4 - 1) / (kBlock * 4);
@@ -1374,14 +1397,16 @@ static int dijkstra_tail(mnav_ctx* ctx, uint32_t m, int engine, const std::vecto
     hipLaunchKernelGGL(k_path_lazy, dim3(m), dim3(kWave), 0, ctx->stream, ctx->d_plans, ctx->d_tplans, ctx->d_res, rows1, ctx->d_mismatch);
     hipLaunchKernelGGL(k_count_goal, dim3(gc ? gc : 1, m), dim3(kBlock), 0, ctx->stream, ctx->d_plans, ctx->d_res);
   } else
-  hipLaunchKernelGGL(k_finish<kPlannerDijkstra>, dim3(m), dim3(64), 0, ctx->stream, ctx->d_plans, ctx->d_res, rows1);
+  hipLaunchKernelGGL(k_finish<kPlannerDijkstra>, dim3(m), dim3(64), 0, ctx->stream, d_plans, d_res, rows1);
   if (engine == 1)   // the tile engines count the settled vertices in k_dij_finalize
-    hipLaunchKernelGGL(k_count, dim3(gc ? gc : 1, m), dim3(kBlock), 0, ctx->stream, ctx->d_plans, ctx->d_res);
+    hipLaunchKernelGGL(k_count, dim3(gc ? gc : 1, m), dim3(kBlock), 0, ctx->stream, d_plans, d_res);
+  if (sub && m > n_vec)
+    hipLaunchKernelGGL(k_count, dim3(gc ? gc : 1, m - n_vec), dim3(kBlock), 0, ctx->stream, d_plans + n_vec, d_res + n_vec);
   (void)hipEventRecord(ctx->ev[4], ctx->stream);
-  if (want_vecmap && !(engine == 5 && !ctx->lazy_paths))            // (the tile-batch engine's finalize pass writes the vector map itself)
-    hipLaunchKernelGGL(k_vecmap_dijkstra, dim3(gc ? gc : 1, m), dim3(kBlock), 0, ctx->stream, ctx->d_plans, ctx->d_xyz, ctx->d_vecptrs);
+  if (want_vecmap && n_vec && !(engine == 5 && !ctx->lazy_paths))   // (the tile-batch engine's finalize pass writes the vector map itself)
+    hipLaunchKernelGGL(k_vecmap_dijkstra, dim3(gc ? gc : 1, n_vec), dim3(kBlock), 0, ctx->stream, d_plans, ctx->d_xyz, sub ? sub->vecptrs : ctx->d_vecptrs.get());
   (void)hipEventRecord(ctx->ev[5], ctx->stream);
-  if (hipMemcpyAsync(ctx->h_res, ctx->d_res, sizeof(PlanResult) * m, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+  if (hipMemcpyAsync(ctx->h_res, d_res, sizeof(PlanResult) * m, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
       hipStreamSynchronize(ctx->stream) != hipSuccess) { ctx->err = "result download failed"; return -1; }
   {
     // paths longer than the default rows (corridors, mazes): ONLY those plans are walked again, into rows of exactly their
@@ -1400,8 +1425,8 @@ static int dijkstra_tail(mnav_ctx* ctx, uint32_t m, int engine, const std::vecto
       rows2 = PathRows{ ctx->d_over, 0u, ctx->d_over_off, ctx->d_over_cap };
       if (engine == 5 && ctx->lazy_paths) hipLaunchKernelGGL(k_tb_path, dim3(m), dim3(kWave), 0, ctx->stream, ctx->tb_args, ctx->d_row_ptr, ctx->d_nbr, V, ctx->d_res, rows2, ctx->d_mismatch);
       else if (ctx->lazy_paths) hipLaunchKernelGGL(k_path_lazy, dim3(m), dim3(kWave), 0, ctx->stream, ctx->d_plans, ctx->d_tplans, ctx->d_res, rows2, ctx->d_mismatch);
-      else hipLaunchKernelGGL(k_finish<kPlannerDijkstra>, dim3(m), dim3(64), 0, ctx->stream, ctx->d_plans, ctx->d_res, rows2);
-      if (hipMemcpyAsync(ctx->h_res, ctx->d_res, sizeof(PlanResult) * m, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+      else hipLaunchKernelGGL(k_finish<kPlannerDijkstra>, dim3(m), dim3(64), 0, ctx->stream, d_plans, d_res, rows2);
+      if (hipMemcpyAsync(ctx->h_res, d_res, sizeof(PlanResult) * m, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
           hipStreamSynchronize(ctx->stream) != hipSuccess) { ctx->err = "result download failed"; return -1; }
       for (uint32_t k = 0; k < m; ++k) ctx->h_res[k].settled = keep[k].settled;
     }
@@ -1445,17 +1470,18 @@ static int dijkstra_tail(mnav_ctx* ctx, uint32_t m, int engine, const std::vecto
   for (uint32_t k = 0; k < m; ++k) {
     const uint32_t i = map[k];
     const PlanResult& r = ctx->h_res[k];
+    const Slot& sl = ctx->slots[sub ? sub->slot[k] : k];
     codes[i] = r.code;
     if (r.code == MNAV_SUCCESS) {
       if (path_len) path_len[i] = r.path_len;
       if (path_out && path_cap && r.path_len)                         // reference list order: seed ... pred[target]
         memcpy(path_out + (size_t)i * path_cap, ctx->h_pack + offs[k], 4 * (size_t)std::min(r.path_len, path_cap));
     }
-    if (dist_out && hipMemcpyAsync(dist_out + (size_t)i * V, ctx->slots[k].dist, 4 * (size_t)V, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+    if (dist_out && hipMemcpyAsync(dist_out + (size_t)i * V, sl.dist, 4 * (size_t)V, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
       { ctx->err = "dist download failed"; return -1; }
-    if (pred_out && hipMemcpyAsync(pred_out + (size_t)i * V, ctx->slots[k].pred, 4 * (size_t)V, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+    if (pred_out && hipMemcpyAsync(pred_out + (size_t)i * V, sl.pred, 4 * (size_t)V, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
       { ctx->err = "pred download failed"; return -1; }
-    if (vecmap_out && want_vecmap && hipMemcpyAsync(vecmap_out + (size_t)i * 3 * V, ctx->slots[k].vecmap, 12 * (size_t)V, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+    if (vecmap_out && want_vecmap && hipMemcpyAsync(vecmap_out + (size_t)i * 3 * V, sl.vecmap, 12 * (size_t)V, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
       { ctx->err = "vecmap download failed"; return -1; }
   }
   MTRACE("paths copied out");
@@ -1465,6 +1491,80 @@ static int dijkstra_tail(mnav_ctx* ctx, uint32_t m, int engine, const std::vecto
   finish_stats(ctx, m, false);
   MTRACE("stats done");
   return 0;
+}
+
+// The engine `auto` picks for m plans of a Dijkstra call: 0 tile rounds, 5 tile-batch, 6 asynchronous tiles.
+static int dijkstra_auto_engine(mnav_ctx* ctx, uint32_t m0)
+{
+  // The tile-batch engine advances all plans tile by tile, 16 plans per quarter of a wave (k_tb_solve_q).  Its floor is one
+  // stream pass per iteration (~190 iterations x ~180 us on the 1M mesh, ~600 x 300 us at 10M), whatever the batch; above
+  // that it beats the per-plan engines at every size measured (round 4, plans/s, tiled / persistent / tile-batch --
+  // 1M: 64 plans 1084 / 496 / 1359, 256: 1879 / 1929 / 4392, 1024: 2223 / 7107 / 12871;
+  // 10M: 64 plans 196 / 41 / 189, 256: 252 / 163 / 409, 1024: 254 / 594 / 924).
+  const double tiles = std::max(1.0, (double)ctx->V / (0.9 * ctx->tb.T));
+  const bool fills = m0 >= ctx->tb.min_batch && m0 <= 65535u && (double)m0 >= tiles / 1000.0;
+  // Below that: the asynchronous tile engine (mnav_async.h: one launch, per-plan ticket queues of woken tiles; what a real
+  // makePlan call -- ONE plan -- runs on), up to async_max_batch plans.  Measured round 5, ms per call on the 1M mesh, rounds /
+  // tile-batch / asynchronous: 1 plan 10.1 / 20 / 6.8, 8 plans 28 / 29 / 9.7, 47 plans 55 / 38 / 22.9, 64 plans 65 / 46 / 27.5
+  // (10M mesh: 8 plans 83 / - / 45, 47 plans 243 / - / 182, 64 plans 330 / 340 / 224); it grows linearly with the batch
+  // where the tile-batch engine's iterations are shared by all plans: the engines cross at about a hundred plans.
+  // Round 6 (a ticket's round trips cut, mnav_async.h): ms per call, asynchronous / tile-batch, 1M mesh 96 plans 29 / 51,
+  // 128: 36 / 53, 192: 52 / 58, 256: 69 / 60; 10M mesh 96: 261 / 343, 128: 325 / 388, 192: 540 / 470
+  // (profiles/r06_async_crossover.json): the engines now cross at about 160 plans on both meshes.
+  return (m0 <= opt_u32(ctx->opt.async_max_batch, 160u)) ? 6 : fills ? 5 : 0;
+}
+
+// The plans of a batch in the order their engine wants them (results are mapped back through `map`).
+static int dijkstra_order(mnav_ctx* ctx, int engine, std::vector<PlanIn>& in, std::vector<uint32_t>& map)
+{
+  const uint32_t V = ctx->V;
+  if (engine == 5 && in.size() > 1) {
+    // plans whose waves start close to each other are neighbours in the batch: their slices of a tile are adjacent in memory
+    // and they tend to have work on the same tiles at the same time
+    if (tb_build(ctx)) return -1;
+    std::vector<uint32_t> ord(in.size());
+    std::iota(ord.begin(), ord.end(), 0u);
+    const std::vector<uint32_t>& vt = ctx->tb.vert_tile;
+    std::stable_sort(ord.begin(), ord.end(), [&](uint32_t x, uint32_t y) { return vt[in[x].seed[0]] < vt[in[y].seed[0]]; });
+    std::vector<PlanIn> in2(in.size()); std::vector<uint32_t> map2(in.size());
+    for (size_t i = 0; i < in.size(); ++i) { in2[i] = in[ord[i]]; map2[i] = map[ord[i]]; }
+    in.swap(in2); map.swap(map2);
+  } else
+  if (in.size() > 1 && ctx->h_xyz.size() == 3 * (size_t)V) {
+    std::vector<uint32_t> ord(in.size());
+    std::iota(ord.begin(), ord.end(), 0u);
+    std::vector<float> est(in.size());
+    for (size_t i = 0; i < in.size(); ++i) {
+      const float* a = &ctx->h_xyz[3 * (size_t)in[i].seed[0]];
+      const float* b = &ctx->h_xyz[3 * (size_t)in[i].target[0]];
+      est[i] = (a[0] - b[0]) * (a[0] - b[0]) + (a[1] - b[1]) * (a[1] - b[1]) + (a[2] - b[2]) * (a[2] - b[2]);
+    }
+    std::stable_sort(ord.begin(), ord.end(), [&](uint32_t x, uint32_t y) { return est[x] > est[y]; });
+    std::vector<PlanIn> in2(in.size()); std::vector<uint32_t> map2(in.size());
+    for (size_t i = 0; i < in.size(); ++i) { in2[i] = in[ord[i]]; map2[i] = map[ord[i]]; }
+    in.swap(in2); map.swap(map2);
+  }
+  return 0;
+}
+
+// The engine run of m plans in the first m slots.  Returns 0, -1 (error) or 1 (cancelled); nothing of a failed or cancelled
+// call stays in flight.  *engine: what ran (the asynchronous engine hands a call it cannot finish to the tile rounds).
+static int dijkstra_dispatch(mnav_ctx* ctx, uint32_t m, const std::vector<PlanIn>& in, double offset, bool engine_auto, int* engine_io)
+{
+  int engine = *engine_io;
+  const bool want_path = true;
+  int rc = (engine == 0) ? run_dijkstra_tiled(ctx, m, in, offset)
+         : (engine == 6) ? run_dijkstra_async(ctx, m, in, offset)
+         : (engine == 5) ? run_dijkstra_tb(ctx, m, in, offset)
+                         : run_plans<kPlannerDijkstra>(ctx, m, in, offset, want_path);
+  // ticket ring exhausted: the rounds start over.  So they do when the in-kernel watchdog gave up (rc 3) on an engine that `auto`
+  // picked: the rounds have the whole max_wall_s (a serialising profiler, a mesh far beyond the tuned sizes)
+  if (engine == 6 && (rc == 2 || (rc == 3 && engine_auto))) { ctx->err.clear(); engine = 0; rc = run_dijkstra_tiled(ctx, m, in, offset); }
+  if (rc == 3) rc = -1;
+  MTRACE("engine returned");
+  if (rc != 0) (void)hipStreamSynchronize(ctx->stream);             // nothing of a failed / cancelled call stays in flight
+  *engine_io = engine;
+  return rc;
 }
 
 static uint32_t dijkstra_impl(mnav_ctx* ctx, uint32_t n, const uint32_t* seeds, const uint32_t* targets, double offset,
@@ -1492,6 +1592,7 @@ static uint32_t dijkstra_impl(mnav_ctx* ctx, uint32_t n, const uint32_t* seeds, 
     mnav_ctx::Replan& R = ctx->rp;
     const std::vector<uint32_t> s_(seeds, seeds + n), t_(targets, targets + n);
     R.seeds = s_; R.targets = t_; R.cost_limit = cost_limit; R.offset = offset; R.have_call = true; R.usable = false; R.partial = false;
+    R.finalized = false; R.each_engines = 0;
   }
   // id checks stand in for the optional-handle tests of dijkstra :240-243
   std::vector<PlanIn> in; std::vector<uint32_t> map;   // map: device plan -> caller index
@@ -1519,53 +1620,11 @@ static uint32_t dijkstra_impl(mnav_ctx* ctx, uint32_t n, const uint32_t* seeds, 
   {
     const uint32_t m0 = (uint32_t)in.size();
     // auto: one wave per (tile, 64 plans) for large batches, one workgroup per plan for medium ones, tile rounds otherwise
-    if (engine == 3) {
-      // The tile-batch engine advances all plans tile by tile, 16 plans per quarter of a wave (k_tb_solve_q).  Its floor is one
-      // stream pass per iteration (~190 iterations x ~180 us on the 1M mesh, ~600 x 300 us at 10M), whatever the batch; above
-      // that it beats the per-plan engines at every size measured (round 4, plans/s, tiled / persistent / tile-batch --
-      // 1M: 64 plans 1084 / 496 / 1359, 256: 1879 / 1929 / 4392, 1024: 2223 / 7107 / 12871;
-      // 10M: 64 plans 196 / 41 / 189, 256: 252 / 163 / 409, 1024: 254 / 594 / 924).
-      const double tiles = std::max(1.0, (double)V / (0.9 * ctx->tb.T));
-      const bool fills = m0 >= ctx->tb.min_batch && m0 <= 65535u && (double)m0 >= tiles / 1000.0;
-      // Below that: the asynchronous tile engine (mnav_async.h: one launch, per-plan ticket queues of woken tiles; what a real
-      // makePlan call -- ONE plan -- runs on), up to async_max_batch plans.  Measured round 5, ms per call on the 1M mesh, rounds /
-      // tile-batch / asynchronous: 1 plan 10.1 / 20 / 6.8, 8 plans 28 / 29 / 9.7, 47 plans 55 / 38 / 22.9, 64 plans 65 / 46 / 27.5
-      // (10M mesh: 8 plans 83 / - / 45, 47 plans 243 / - / 182, 64 plans 330 / 340 / 224); it grows linearly with the batch
-      // where the tile-batch engine's iterations are shared by all plans: the engines cross at about a hundred plans.
-      // Round 6 (a ticket's round trips cut, mnav_async.h): ms per call, asynchronous / tile-batch, 1M mesh 96 plans 29 / 51,
-      // 128: 36 / 53, 192: 52 / 58, 256: 69 / 60; 10M mesh 96: 261 / 343, 128: 325 / 388, 192: 540 / 470
-      // (profiles/r06_async_crossover.json): the engines now cross at about 160 plans on both meshes.
-      engine = (m0 <= opt_u32(ctx->opt.async_max_batch, 160u)) ? 6 : fills ? 5 : 0;
-    }
+    if (engine == 3) engine = dijkstra_auto_engine(ctx, m0);
     if (engine == 5 && m0 > 65535u) engine = 0;                       // (plan ids are 16 bits in the tile-batch buckets)
     if (engine == 1 && offset < 0.0) engine = 0;                      // the band steps arm goal_dist inside the loop: tile rounds for a negative offset
   }
-  if (engine == 5 && in.size() > 1) {
-    // plans whose waves start close to each other are neighbours in the batch: their slices of a tile are adjacent in memory
-    // and they tend to have work on the same tiles at the same time
-    if (tb_build(ctx)) return MNAV_INTERNAL_ERROR;
-    std::vector<uint32_t> ord(in.size());
-    std::iota(ord.begin(), ord.end(), 0u);
-    const std::vector<uint32_t>& vt = ctx->tb.vert_tile;
-    std::stable_sort(ord.begin(), ord.end(), [&](uint32_t x, uint32_t y) { return vt[in[x].seed[0]] < vt[in[y].seed[0]]; });
-    std::vector<PlanIn> in2(in.size()); std::vector<uint32_t> map2(in.size());
-    for (size_t i = 0; i < in.size(); ++i) { in2[i] = in[ord[i]]; map2[i] = map[ord[i]]; }
-    in.swap(in2); map.swap(map2);
-  } else
-  if (in.size() > 1 && ctx->h_xyz.size() == 3 * (size_t)V) {
-    std::vector<uint32_t> ord(in.size());
-    std::iota(ord.begin(), ord.end(), 0u);
-    std::vector<float> est(in.size());
-    for (size_t i = 0; i < in.size(); ++i) {
-      const float* a = &ctx->h_xyz[3 * (size_t)in[i].seed[0]];
-      const float* b = &ctx->h_xyz[3 * (size_t)in[i].target[0]];
-      est[i] = (a[0] - b[0]) * (a[0] - b[0]) + (a[1] - b[1]) * (a[1] - b[1]) + (a[2] - b[2]) * (a[2] - b[2]);
-    }
-    std::stable_sort(ord.begin(), ord.end(), [&](uint32_t x, uint32_t y) { return est[x] > est[y]; });
-    std::vector<PlanIn> in2(in.size()); std::vector<uint32_t> map2(in.size());
-    for (size_t i = 0; i < in.size(); ++i) { in2[i] = in[ord[i]]; map2[i] = map[ord[i]]; }
-    in.swap(in2); map.swap(map2);
-  }
+  if (dijkstra_order(ctx, engine, in, map)) return MNAV_INTERNAL_ERROR;
   ctx->caller_slot.assign(n, kNone);
   ctx->shard.finalized = false;
   for (size_t i = 0; i < map.size(); ++i) ctx->caller_slot[map[i]] = (uint32_t)i;
@@ -1577,17 +1636,7 @@ static uint32_t dijkstra_impl(mnav_ctx* ctx, uint32_t n, const uint32_t* seeds, 
   ctx->last_offset = offset;
   if (m) {
     if (materialize(ctx, false, cost_limit)) return MNAV_INTERNAL_ERROR;
-    const bool want_path = true;
-    int rc = (engine == 0) ? run_dijkstra_tiled(ctx, m, in, offset)
-           : (engine == 6) ? run_dijkstra_async(ctx, m, in, offset)
-           : (engine == 5) ? run_dijkstra_tb(ctx, m, in, offset)
-                           : run_plans<kPlannerDijkstra>(ctx, m, in, offset, want_path);
-    // ticket ring exhausted: the rounds start over.  So they do when the in-kernel watchdog gave up (rc 3) on an engine that `auto`
-    // picked: the rounds have the whole max_wall_s (a serialising profiler, a mesh far beyond the tuned sizes)
-    if (engine == 6 && (rc == 2 || (rc == 3 && engine_auto))) { ctx->err.clear(); engine = 0; rc = run_dijkstra_tiled(ctx, m, in, offset); }
-    if (rc == 3) rc = -1;
-    MTRACE("engine returned");
-    if (rc != 0) (void)hipStreamSynchronize(ctx->stream);             // nothing of a failed / cancelled call stays in flight
+    const int rc = dijkstra_dispatch(ctx, m, in, offset, engine_auto, &engine);
     if (rc < 0) return MNAV_INTERNAL_ERROR;
     if (rc == 1) { for (uint32_t i = 0; i < n; ++i) if (codes_out) codes_out[i] = MNAV_CANCELED; return MNAV_CANCELED; }   // :350-354
     ctx->last_engine = engine; ctx->last_n = m;                       // only a call whose engine succeeded leaves outputs behind
@@ -1596,7 +1645,10 @@ static uint32_t dijkstra_impl(mnav_ctx* ctx, uint32_t n, const uint32_t* seeds, 
     // slots[k].dist is a field a replan can rewind: below the cut every value is final after the tile rounds and the
     // asynchronous tiles (finalized or not) and after the tile-batch engine's finalize pass; the band steps keep other values
     ctx->rp.usable = engine == 0 || engine == 6 || (engine == 5 && !ctx->lazy_paths);
+    ctx->rp.finalized = !ctx->lazy_paths;                             // (the per-plan replan keeps finalized fields only)
+    ctx->rp.vec_resident = want_vecmap;
   }
+  ctx->rp.slot0_taken = false; ctx->rp.each_engines = 0;
   ctx->rp.caller_slot = ctx->caller_slot; ctx->rp.len = 0; ctx->rp.all = false;   // the change log starts over
   ctx->rp.partial = m != n;
   // plans rejected before reaching the device: the reference has cleared its maps by then
@@ -1765,6 +1817,7 @@ uint32_t mnav_plan_cvp_batch(mnav_ctx* ctx, uint32_t n, const float* seed_pos, c
 #include "mnav_rollout_capi.h"    // mnav_follow_rollout, mnav_rollout_stats
 #include "mnav_graph_capi.h"      // mnav_map_configure / _compute / _layer_changed / _update_layer / _obstacle / _stats
 #include "mnav_replan_capi.h"     // mnav_replan_dijkstra_batch, mnav_replan_stats
+#include "mnav_replan_each_capi.h"   // mnav_replan_dijkstra_each, mnav_replan_each_stats
 #include "mnav_fleet_capi.h"      // mnav_fleet_paths, mnav_fleet_walks, mnav_fleet_stats
 #include "mnav_plans_capi.h"      // mnav_upload_face_normals, mnav_fleet_plans, mnav_fleet_walk_plans
 
@@ -2035,6 +2088,7 @@ uint64_t mnav_algorithmic_bytes(const mnav_ctx* ctx)
 int mnav_last_engine(const mnav_ctx* ctx)
 {
   if (!ctx || ctx->last_planner != kPlannerDijkstra || ctx->last_n == 0) return -1;
+  if (ctx->rp.each_engines) return ctx->rp.each_engines;
   return ctx->last_engine + ((ctx->last_engine == 5 && ctx->tb.kernel == 1) ? 16 : 0);
 }
 

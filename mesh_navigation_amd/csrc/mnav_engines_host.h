@@ -138,8 +138,12 @@ int ensure_tile_state(mnav_ctx* ctx, uint32_t n)
   return 0;
 }
 
+// The tables the tile rounds and the finalize pass of n plans work from when they are not the batch's own (the per-plan
+// replan: compacted records, their control pool and result records).
+struct TileTables { const Plan* plans; const TilePlan* tplans; const TCtl* tctl; PlanResult* res; };
+
 // one workgroup per (plan, chunk of tiles); small batches get more, smaller chunks to fill the chip
-void launch_finalize(mnav_ctx* ctx, uint32_t n, uint32_t ntiles_in = 0, size_t fin_lds_in = 0)
+void launch_finalize(mnav_ctx* ctx, uint32_t n, uint32_t ntiles_in = 0, size_t fin_lds_in = 0, const TileTables* alt = nullptr)
 {
   const uint32_t nt_ = ntiles_in ? ntiles_in : ctx->tiles_meta.ntiles;
   const size_t fin_lds = fin_lds_in ? fin_lds_in : ctx->fin_lds;
@@ -149,8 +153,8 @@ void launch_finalize(mnav_ctx* ctx, uint32_t n, uint32_t ntiles_in = 0, size_t f
   if (chunks < 1) chunks = 1;
   const uint32_t per = (ntiles + chunks - 1) / chunks;
   chunks = (ntiles + per - 1) / per;
-  hipLaunchKernelGGL(k_dij_finalize, dim3(n, chunks), dim3(kTileBlock), fin_lds, ctx->stream, ctx->d_plans, ctx->d_tplans,
-                     ctx->d_mismatch, ctx->d_res, per, n);
+  hipLaunchKernelGGL(k_dij_finalize, dim3(n, chunks), dim3(kTileBlock), fin_lds, ctx->stream, alt ? alt->plans : ctx->d_plans.get(),
+                     alt ? alt->tplans : ctx->d_tplans.get(), ctx->d_mismatch, alt ? alt->res : ctx->d_res.get(), per, n);
 }
 
 int tile_weights(mnav_ctx* ctx)
@@ -166,23 +170,25 @@ int tile_weights(mnav_ctx* ctx)
 
 constexpr int kTileChunk = 24;   // rounds per graph replay (multiple of 6)
 
-int launch_tile_rounds(mnav_ctx* ctx, uint32_t n, uint32_t G, int count)
+int launch_tile_rounds(mnav_ctx* ctx, uint32_t n, uint32_t G, int count, const TilePlan* tplans)
 {
   for (int j = 0; j < count; ++j)
-    hipLaunchKernelGGL(k_tile_round, dim3(G, n), dim3(kTileBlock), ctx->tile_lds, ctx->stream, ctx->d_tplans, j % 6);
+    hipLaunchKernelGGL(k_tile_round, dim3(G, n), dim3(kTileBlock), ctx->tile_lds, ctx->stream, tplans, j % 6);
   HIPCHK(hipGetLastError());
   return 0;
 }
 
-int run_tile_chunk(mnav_ctx* ctx, uint32_t n, uint32_t G)
+int run_tile_chunk(mnav_ctx* ctx, uint32_t n, uint32_t G, const TileTables* alt)
 {
-  if (!ctx->use_graph) return launch_tile_rounds(ctx, n, G, kTileChunk);
+  const TilePlan* const tplans = alt ? alt->tplans : ctx->d_tplans.get();
+  // (compacted tables: their plan count changes from call to call, and a captured graph is good for one count only)
+  if (!ctx->use_graph || alt) return launch_tile_rounds(ctx, n, G, kTileChunk, tplans);
   const uint64_t key = (7ull << 60) | ((uint64_t)n << 32) | G;
   auto it = ctx->graphs.find(key);
   if (it == ctx->graphs.end()) {
     hipGraph_t g = nullptr;
     HIPCHK(hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-    const int rc = launch_tile_rounds(ctx, n, G, kTileChunk);
+    const int rc = launch_tile_rounds(ctx, n, G, kTileChunk, tplans);
     hipError_t e = hipStreamEndCapture(ctx->stream, &g);
     if (rc != 0 || e != hipSuccess) { ctx->err = "graph capture failed"; return -1; }
     GraphExec ge;
@@ -234,7 +240,7 @@ int fill_tile_records(mnav_ctx* ctx, uint32_t n, const std::vector<PlanIn>& in, 
 }
 
 // The rounds of n plans whose tile state is set up, chunk by chunk, until every plan is done.  Returns 0, -1 (error) or 1 (cancelled).
-int run_tile_rounds(mnav_ctx* ctx, uint32_t n)
+int run_tile_rounds(mnav_ctx* ctx, uint32_t n, const TileTables* alt = nullptr)
 {
   const HostTiles& M = ctx->tiles_meta;
   // active tiles form a ring along the wavefront: O(sqrt(ntiles)); every workgroup scans a
@@ -252,10 +258,10 @@ int run_tile_rounds(mnav_ctx* ctx, uint32_t n)
       ctx->err = "tile rounds exceeded the wall-clock guard"; return -1;
     }
     HIPCHK(hipEventRecord(ctx->evc[0], ctx->stream));
-    if (run_tile_chunk(ctx, n, G)) return -1;
+    if (run_tile_chunk(ctx, n, G, alt)) return -1;
     HIPCHK(hipEventRecord(ctx->evc[1], ctx->stream));
     launches += kTileChunk;
-    HIPCHK(hipMemcpyAsync(ctx->h_tctl, ctx->d_tctl_pool, 2 * sizeof(TCtl) * n, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(ctx->h_tctl, alt ? alt->tctl : ctx->d_tctl_pool.get(), 2 * sizeof(TCtl) * n, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     ctx->ms_chunks += ev_ms(ctx->evc[0], ctx->evc[1]);
     bool all_done = true;

@@ -31,6 +31,7 @@
   X(nbhd_lds_cap)        /* neighbourhood layers: members per centre in LDS (default 128, 32..512; tests force the spill path) */ \
   X(replan_log_cap)      /* replan: entries of the change log (default V; tests force the overflow) */                                    \
   X(replan_fresh_below)  /* replan: plan afresh when the smallest rewind level / old cut of the batch lies below this fraction (default 0.25; 0: never) */ \
+  X(replan_each_fresh_share) /* per-plan replan: plan the whole call afresh when more than this share of its plans is FRESH (default 0.004, measured; 1: never) */ \
   X(fleet_scratch_mb)    /* fleet walks: MiB of scratch rows per chunk of robots (default 256; the result does not depend on it) */
 
 struct Options {

@@ -76,7 +76,7 @@ static int replan_repair(mnav_ctx* ctx, uint32_t n, const std::vector<uint32_t>&
   ctx->shard.finalized = false; ctx->tb.count_pending = false; ctx->tb_args_valid = false;
   ctx->last_planner = kPlannerDijkstra; ctx->last_n = 0; R.usable = false;
   ctx->last_target.resize(m); for (uint32_t k = 0; k < m; ++k) ctx->last_target[k] = in[k].target[0];
-  ctx->last_offset = offset;
+  ctx->last_offset = offset; R.each_engines = 0;
   hipLaunchKernelGGL(k_replan_rewind, dim3(ctx->tiles_meta.ntiles ? ctx->tiles_meta.ntiles : 1u, m), dim3(kTileBlock), 0, ctx->stream,
                      ctx->d_tplans, ctx->d_plans, R.d_level, R.d_cnt);
   HIPCHK(hipGetLastError());
@@ -105,6 +105,7 @@ static int replan_repair(mnav_ctx* ctx, uint32_t n, const std::vector<uint32_t>&
   R.rounds = ctx->stats.launches;
   R.ms_level = ev_ms(R.ev[0], R.ev[1]); R.ms_rewind = ev_ms(R.ev[1], R.ev[2]); R.ms_rounds = (float)ctx->ms_chunks; R.ms_finalize = ev_ms(R.ev[3], R.ev[4]);
   R.targets = tg; R.offset = offset; R.usable = true; R.len = 0; R.all = false;   // the change log starts over
+  R.finalized = true; R.vec_resident = ctx->want_vec; R.slot0_taken = false;
   uint32_t worst = MNAV_SUCCESS;
   for (uint32_t i = 0; i < n; ++i) {
     if (codes_out) codes_out[i] = codes[i];
@@ -114,8 +115,15 @@ static int replan_repair(mnav_ctx* ctx, uint32_t n, const std::vector<uint32_t>&
   return 0;
 }
 
-uint32_t mnav_replan_dijkstra_batch(mnav_ctx* ctx, uint32_t n, const uint32_t* targets, double goal_dist_offset, uint32_t* codes_out, float* dist_out,
-                                    uint32_t* pred_out, uint32_t* path_out, uint32_t path_cap, uint32_t* path_len)
+// mnav_replan_each_capi.h: the repair plan by plan; 2 = its share policy sends the whole call to a fresh plan
+static int replan_each_repair(mnav_ctx* ctx, uint32_t n, const std::vector<uint32_t>& tg, double offset, uint32_t* codes_out, float* dist_out,
+                              uint32_t* pred_out, uint32_t* path_out, uint32_t path_cap, uint32_t* path_len, uint32_t* code);
+static void replan_each_begin_stats(mnav_ctx* ctx, uint32_t reason, uint32_t log_len);
+
+// Both replan entry points: the refusals, the whole-call reasons and the fresh plan they end in are the same; `each` picks
+// the repair.
+static uint32_t replan_call(mnav_ctx* ctx, uint32_t n, const uint32_t* targets, double goal_dist_offset, uint32_t* codes_out, float* dist_out,
+                            uint32_t* pred_out, uint32_t* path_out, uint32_t path_cap, uint32_t* path_len, bool each)
 {
   if (!ctx) return MNAV_INTERNAL_ERROR;
   mnav_ctx::Replan& R = ctx->rp;
@@ -142,9 +150,11 @@ uint32_t mnav_replan_dijkstra_batch(mnav_ctx* ctx, uint32_t n, const uint32_t* t
       if (R.caller_slot[i] >= n || tg[i] >= ctx->V || tg[i] == seeds[i]) { reason = 3; break; }
   R.reason = reason; R.stat_log_len = log_len; R.kept = R.rewound = 0; R.tiles_woken = R.rounds = 0; R.levels.clear();
   R.ms_level = R.ms_rewind = R.ms_rounds = R.ms_finalize = 0.f;
+  if (each) replan_each_begin_stats(ctx, reason, log_len);
   if (reason == 0) {
     uint32_t code = MNAV_INTERNAL_ERROR;
-    const int rc = replan_repair(ctx, n, tg, goal_dist_offset, codes_out, dist_out, pred_out, path_out, path_cap, path_len, &code);
+    const int rc = each ? replan_each_repair(ctx, n, tg, goal_dist_offset, codes_out, dist_out, pred_out, path_out, path_cap, path_len, &code)
+                        : replan_repair(ctx, n, tg, goal_dist_offset, codes_out, dist_out, pred_out, path_out, path_cap, path_len, &code);
     if (rc == 0) return code;
     if (rc == 1) {                                                    // cancelled between two chunks of rounds: the fields are half rewound
       R.usable = false; ctx->last_n = 0;
@@ -153,6 +163,7 @@ uint32_t mnav_replan_dijkstra_batch(mnav_ctx* ctx, uint32_t n, const uint32_t* t
     }
     if (rc < 0) { R.usable = false; ctx->last_n = 0; (void)hipStreamSynchronize(ctx->stream); return MNAV_INTERNAL_ERROR; }
     R.reason = 4; R.levels.clear();                                   // policy: plan afresh
+    if (each) { R.each.reason = 4; R.each.whole_fresh = 1; }
   }
   // a fresh plan from the recorded seeds, finalize pass included: always a correct answer
   const bool lazy = ctx->allow_lazy_paths;
@@ -161,6 +172,12 @@ uint32_t mnav_replan_dijkstra_batch(mnav_ctx* ctx, uint32_t n, const uint32_t* t
                                     path_len, nullptr, false);
   ctx->allow_lazy_paths = lazy;
   return rc;
+}
+
+uint32_t mnav_replan_dijkstra_batch(mnav_ctx* ctx, uint32_t n, const uint32_t* targets, double goal_dist_offset, uint32_t* codes_out, float* dist_out,
+                                    uint32_t* pred_out, uint32_t* path_out, uint32_t path_cap, uint32_t* path_len)
+{
+  return replan_call(ctx, n, targets, goal_dist_offset, codes_out, dist_out, pred_out, path_out, path_cap, path_len, false);
 }
 
 uint32_t mnav_replan_plans(const mnav_ctx* ctx) { return ctx && ctx->rp.have_call ? (uint32_t)ctx->rp.seeds.size() : 0u; }
