@@ -389,7 +389,8 @@ int mnav_map_stats(const mnav_ctx* ctx, uint32_t* waves, uint32_t* recombined, u
  * The context logs which vertices mnav_update_costs, mnav_update_edge_weights (both endpoints) and the mnav_map_* update
  * calls (the default layer's change list) touched since the last Dijkstra or replan call.  A plan keeps every value strictly
  * below its rewind level L = min(old cut, smallest old value over the closed one-ring of the logged vertices); the rest goes
- * back to +inf and the tile rounds continue from the kept part.  mnav_cancel is honoured between
+ * back to +inf and the tile rounds -- or, by the option replan_repair_engine, the tile-batch engine (mnav_replan_warm_stats) --
+ * continue from the kept part.  mnav_cancel is honoured between
  * chunks of rounds (the flag is cleared at entry); a cancelled call leaves nothing to replan.
  * Refused with MNAV_INTERNAL_ERROR, mnav_last_error set and outputs, log and replan state untouched: no mesh or costs, a NaN
  * offset, no Dijkstra call before, n different from that call's. */
@@ -421,7 +422,8 @@ int mnav_replan_stats(const mnav_ctx* ctx, uint32_t* reason, uint32_t* log_len, 
  *   FRESH (2)     f > 0, the cut is finite and positive and L / cut < f: planned afresh, all FRESH plans as one batch in their
  *                 own slots, on the engine `auto` picks for their number.
  *   REPAIRED (1)  everything else: the rewind, the tile rounds and the finalize pass of mnav_replan_dijkstra_batch, over
- *                 these plans only.
+ *                 these plans only -- or, by the option replan_repair_engine, a warm start of the tile-batch engine
+ *                 (mnav_replan_warm_stats below).
  * When more than the share replan_each_fresh_share of the plans is FRESH (default 0.004, measured; 1: never) the whole call plans afresh
  * (reason 4), as it does for reasons 1 to 3.  After the call the change log starts over and mnav_follow_batch,
  * mnav_follow_rollout, the mnav_fleet_* calls, mnav_download_output and a further replan work on every slot, KEPT ones
@@ -439,6 +441,28 @@ uint32_t mnav_replan_dijkstra_each(mnav_ctx* ctx, uint32_t n, const uint32_t* ta
 int mnav_replan_each_stats(const mnav_ctx* ctx, uint32_t* reason, uint32_t* whole_fresh, uint32_t* log_len, uint8_t* classes_out,
                            float* levels_out, uint32_t* counts, uint64_t* kept, uint64_t* rewound, uint32_t* tiles_woken, uint32_t* rounds,
                            int32_t* fresh_engine, float* ms);
+
+/* The repaired plans on the tile-batch engine.  The plans a replan call repairs (all n of a reason-0
+ * mnav_replan_dijkstra_batch, the REPAIRED class of mnav_replan_dijkstra_each) are finished either on the tile rounds or on the
+ * tile-batch engine, started from the rewound fields instead of from +inf: the kernel k_tb_warm writes every slice and every
+ * pending word of the sub-batch from the resident potentials and the rewind levels (same rule: the seed, and every value
+ * strictly below L, is kept), and the engine's schedule, solve, finalize and path kernels run unchanged.  Outputs are the same
+ * bits either way.  Options: replan_repair_engine = 0 the tile rounds, 5 the tile-batch engine whenever a plan is repaired,
+ * unset automatic -- the tile-batch engine from replan_warm_min_plans repaired plans on (default 299, measured, DESIGN.md
+ * section 3.14; the built-in default is never below 161, under which a fresh plan does not take that engine either).  When the engine cannot be used the
+ * call falls back to the tile rounds and says so here; it never fails for that reason.
+ * The last replan call of either kind: plans repaired warm (0: none, the other outputs are zero); kernel: 0 k_tb_solve_q,
+ * 1 k_tbv_solve; iterations of the engine; (tile, plan) pairs woken by k_tb_warm; words: slice words it wrote; ms[3]: device
+ * milliseconds of k_tb_warm, of the engine run and of k_tb_finalize; fallback: 0 none, 1 more than 65535 repaired plans, 2 the
+ * engine's tables or batch state could not be allocated next to the resident outputs; live: 1 while no other planner call has
+ * run since a warm repair.  Any pointer may be NULL.
+ * For a warm repair mnav_replan_stats / mnav_replan_each_stats report: rounds = the engine's iterations, ms_rewind = k_tb_warm,
+ * ms_rounds = the engine run, ms_finalize = k_tb_finalize, kept / rewound as always, tiles_woken = the pairs woken (tiles of the
+ * tile-batch tiling).  mnav_last_engine after a per-plan call whose REPAIRED plans ran warm: 256 + 512 (+ 1024 with k_tbv_solve)
+ * + the FRESH batch's engine (127: none), without the 128; after a warm mnav_replan_dijkstra_batch the tile-batch engine's
+ * value (5, or 21 with k_tbv_solve). */
+int mnav_replan_warm_stats(const mnav_ctx* ctx, uint32_t* plans, uint32_t* kernel, uint32_t* iterations, uint64_t* pairs_woken, uint64_t* words,
+                           float* ms, uint32_t* fallback, uint32_t* live);
 
 /* -- pose lookup on the device ---------------------------------------------------------------------
  * MeshMap::getNearestVertexHandle (mesh_map.cpp:1161-1174) and MeshMap::getContainingFace / searchContainingFace

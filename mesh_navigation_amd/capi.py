@@ -37,6 +37,7 @@ SYMBOLS = [
     "mnav_follow_batch", "mnav_follow_stats", "mnav_follow_rollout", "mnav_rollout_stats",
     "mnav_map_configure", "mnav_map_compute", "mnav_map_layer_changed", "mnav_map_update_layer", "mnav_map_obstacle", "mnav_map_stats",
     "mnav_replan_dijkstra_batch", "mnav_replan_plans", "mnav_replan_stats", "mnav_replan_dijkstra_each", "mnav_replan_each_stats",
+    "mnav_replan_warm_stats",
     "mnav_fleet_paths", "mnav_fleet_walks", "mnav_fleet_stats",
     "mnav_upload_face_normals", "mnav_fleet_plans", "mnav_fleet_walk_plans",
     "mnav_set_option", "mnav_get_option", "mnav_shard_set_goal_tie", "mnav_last_engine",
@@ -215,6 +216,8 @@ def load(path: str | None = None):
     L.mnav_replan_each_stats.restype = C.c_int
     L.mnav_replan_each_stats.argtypes = ([vp] + [C.POINTER(u32)] * 3 + [vp, vp, vp] + [C.POINTER(C.c_uint64)] * 2 + [C.POINTER(u32)] * 2
                                          + [C.POINTER(C.c_int32), vp])
+    L.mnav_replan_warm_stats.restype = C.c_int
+    L.mnav_replan_warm_stats.argtypes = [vp] + [C.POINTER(u32)] * 3 + [C.POINTER(C.c_uint64)] * 2 + [vp] + [C.POINTER(u32)] * 2
     L.mnav_replan_plans.restype = u32
     L.mnav_replan_plans.argtypes = [vp]
     L.mnav_replan_stats.restype = C.c_int
@@ -381,6 +384,10 @@ class CvpOut:
 def _engine_name(e: int) -> str:
     return {0: "k_tile_round (tile rounds)", 1: "k_step (band steps)", 5: "k_tb_solve_q (tile-batch engine, quarters of a wave, distances in LDS)",
             21: "k_tbv_solve (tile-batch engine, one wave per tile, distances in VGPRs)", 6: "k_plan_async (asynchronous tile engine)"}.get(e, "none")
+
+
+def _warm_name(kernel: int) -> str:
+    return "k_tb_warm + %s (tile-batch engine started from the rewound fields)" % ("k_tbv_solve" if kernel == 1 else "k_tb_solve_q")
 
 
 class MnavContext:
@@ -835,9 +842,12 @@ class MnavContext:
     def last_engine(self) -> str:
         """Engine / kernel of the last Dijkstra call, by name (mnav_last_engine)."""
         e = int(self._L.mnav_last_engine(self._h))
-        if e >= 256:                                                   # replan_dijkstra_each: the repair's rounds and / or the FRESH batch's engine
-            ran = (["k_tile_round (tile rounds)"] if e & 128 else []) + ([_engine_name(e & 127)] if (e & 127) != 127 else [])
+        if e >= 256:                                                   # replan_dijkstra_each: the repair's rounds or warm start and / or the FRESH batch's engine
+            ran = (["k_tile_round (tile rounds)"] if e & 128 else []) + ([_warm_name(1 if e & 1024 else 0)] if e & 512 else [])
+            ran += [_engine_name(e & 127)] if (e & 127) != 127 else []
             return " + ".join(ran) if ran else "none (every plan kept)"
+        if e in (5, 21) and self.replan_warm_stats()["live"]:          # replan_dijkstra, all plans warm
+            return _warm_name(1 if e == 21 else 0)
         return _engine_name(e)
 
     def timing(self) -> dict:
@@ -932,7 +942,7 @@ class MnavContext:
         rows = _PathRows(paths, lens, cap)
         lease.append(weakref.ref(rows))
         return dict(rc=rc, codes=codes, dist=dist, pred=pred, paths=rows, path_len=lens, stats=self.stats() if want_stats else self.timing(),
-                    replan=self.replan_stats(n) if want_stats else None)
+                    replan=self.replan_stats(n) if want_stats else None, warm=self.replan_warm_stats() if want_stats else None)
 
     def replan_dijkstra_each(self, targets=None, goal_dist_offset: float = 0.3, want_dist: bool = False, want_pred: bool = False,
                              path_cap: int | None = None, want_stats: bool = True):
@@ -954,7 +964,21 @@ class MnavContext:
         rows = _PathRows(paths, lens, cap)
         lease.append(weakref.ref(rows))
         return dict(rc=rc, codes=codes, dist=dist, pred=pred, paths=rows, path_len=lens, stats=self.stats() if want_stats else self.timing(),
-                    replan=self.replan_stats(n) if want_stats else None, each=self.replan_each_stats(n) if want_stats else None)
+                    replan=self.replan_stats(n) if want_stats else None, each=self.replan_each_stats(n) if want_stats else None,
+                    warm=self.replan_warm_stats() if want_stats else None)
+
+    def replan_warm_stats(self) -> dict:
+        """The warm repair of the last replan call of either kind (mnav_replan_warm_stats): plans repaired on the tile-batch
+        engine from their rewound fields (0: none), its solve kernel, iterations, (tile, plan) pairs woken and slice words
+        written by k_tb_warm, device milliseconds, and whether (and why) the call fell back to the tile rounds."""
+        pl, kn, it, fb, lv = (C.c_uint32() for _ in range(5))
+        wk, wd = C.c_uint64(), C.c_uint64()
+        ms = np.zeros(3, np.float32)
+        self._L.mnav_replan_warm_stats(self._h, C.byref(pl), C.byref(kn), C.byref(it), C.byref(wk), C.byref(wd), _p(ms), C.byref(fb), C.byref(lv))
+        why = {0: None, 1: "more than 65535 repaired plans", 2: "the tile-batch engine could not be allocated"}.get(fb.value, str(fb.value))
+        return dict(plans=pl.value, kernel=("k_tbv_solve" if kn.value == 1 else "k_tb_solve_q") if pl.value else None, iterations=it.value,
+                    pairs_woken=wk.value, words=wd.value, ms_warm=float(ms[0]), ms_engine=float(ms[1]), ms_finalize=float(ms[2]),
+                    fallback=fb.value, fallback_reason=why, live=bool(lv.value))
 
     def replan_each_stats(self, n: int = 0) -> dict:
         """The last replan_dijkstra_each call (mnav_replan_each_stats); n: its plan count, for the classes (0 KEPT, 1 REPAIRED,

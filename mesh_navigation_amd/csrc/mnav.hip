@@ -86,6 +86,7 @@ constexpr int kChunk = 96;  // step launches per graph replay; multiple of 6 (sl
 #include "mnav_rollout.h"    // device rollouts: many controller ticks per call over resident robot state (mnav_rol::)
 #include "mnav_replan.h"     // replan on a resident potential: rewind level from the change log, rewind with the tiles' wake-up words (k_replan_*)
 #include "mnav_replan_each.h"  // the per-plan replan: class of every plan, ordered lists, compacted records (k_replan_classify, k_replan_gather)
+#include "mnav_tb_warm.h"    // warm start of the tile-batch engine from rewound fields: every slice and pending word of a sub-batch (k_tb_warm)
 #include "mnav_graph.h"      // resident layer graph: node passes with change lists, id-list union, combination into a slot (mnav_map::)
 
 // One back-tracking job: the plan's resident vector map and the two ends of the walk.
@@ -254,7 +255,15 @@ struct mnav_ctx {
     bool finalized = false;          // the fields of the last call went through a finalize pass (not a paths-only call): what mnav_replan_dijkstra_each may keep
     bool slot0_taken = false;        // an inflation wave has worked in slot 0 since
     bool vec_resident = false;       // ... and left the vector maps of its plans resident
-    int each_engines = 0;            // mnav_last_engine after mnav_replan_dijkstra_each repaired per plan: 256 + (128: tile rounds ran) + (engine of the FRESH sub-batch, 127: none)
+    int each_engines = 0;            // mnav_last_engine after mnav_replan_dijkstra_each repaired per plan: 256 + (128: tile rounds ran) + (512: the REPAIRED plans ran warm on the
+                                     // tile-batch engine, 1024: with k_tbv_solve) + (engine of the FRESH sub-batch, 127: none)
+    // the warm repair on the tile-batch engine (k_tb_warm): its device arrays in sub-batch order and the statistics of the last
+    // replan call of either kind (mnav_replan_warm_stats).  live: no other planner call has run since a warm repair
+    struct Warm {
+      DevBuf<uint32_t> d_level; DevBuf<const float*> d_dist; DevBuf<ReplanCnt> d_cnt; uint32_t cap = 0;
+      uint32_t plans = 0, kernel = 0, iters = 0, fallback = 0; uint64_t woken = 0, words = 0; bool live = false;
+      float ms_warm = 0.f, ms_engine = 0.f, ms_finalize = 0.f;
+    } warm;
     DevBuf<uint32_t> d_level, d_old_target; DevBuf<float> d_cut; DevBuf<ReplanCnt> d_cnt; uint32_t cap = 0;
     Event ev[5]; bool have_ev = false;
     // statistics of the last replan call (mnav_replan_stats)
@@ -1592,7 +1601,7 @@ static uint32_t dijkstra_impl(mnav_ctx* ctx, uint32_t n, const uint32_t* seeds, 
     mnav_ctx::Replan& R = ctx->rp;
     const std::vector<uint32_t> s_(seeds, seeds + n), t_(targets, targets + n);
     R.seeds = s_; R.targets = t_; R.cost_limit = cost_limit; R.offset = offset; R.have_call = true; R.usable = false; R.partial = false;
-    R.finalized = false; R.each_engines = 0;
+    R.finalized = false; R.each_engines = 0; R.warm.live = false;
   }
   // id checks stand in for the optional-handle tests of dijkstra :240-243
   std::vector<PlanIn> in; std::vector<uint32_t> map;   // map: device plan -> caller index
@@ -1648,7 +1657,7 @@ static uint32_t dijkstra_impl(mnav_ctx* ctx, uint32_t n, const uint32_t* seeds, 
     ctx->rp.finalized = !ctx->lazy_paths;                             // (the per-plan replan keeps finalized fields only)
     ctx->rp.vec_resident = want_vecmap;
   }
-  ctx->rp.slot0_taken = false; ctx->rp.each_engines = 0;
+  ctx->rp.slot0_taken = false; ctx->rp.each_engines = 0; ctx->rp.warm.live = false;
   ctx->rp.caller_slot = ctx->caller_slot; ctx->rp.len = 0; ctx->rp.all = false;   // the change log starts over
   ctx->rp.partial = m != n;
   // plans rejected before reaching the device: the reference has cleared its maps by then
@@ -1732,7 +1741,7 @@ static uint32_t cvp_impl(mnav_ctx* ctx, uint32_t n, const float* seed_pos, const
   for (size_t i = 0; i < map.size(); ++i) ctx->caller_slot[map[i]] = (uint32_t)i;
   (void)hipEventRecord(ctx->ev[0], ctx->stream);
   ctx->tb.count_pending = false; ctx->tb_args_valid = false;         // (a lazy settled-vertex count of an earlier Dijkstra batch is void now)
-  ctx->last_planner = kPlannerCvp; ctx->last_n = 0; ctx->last_engine = 1;
+  ctx->last_planner = kPlannerCvp; ctx->last_n = 0; ctx->last_engine = 1; ctx->rp.warm.live = false;
   ctx->rp.usable = ctx->rp.partial = false;                          // the slots' dist now holds CVP potentials
   uint32_t worst = MNAV_SUCCESS;
   if (m) {

@@ -32,6 +32,8 @@
   X(replan_log_cap)      /* replan: entries of the change log (default V; tests force the overflow) */                                    \
   X(replan_fresh_below)  /* replan: plan afresh when the smallest rewind level / old cut of the batch lies below this fraction (default 0.25; 0: never) */ \
   X(replan_each_fresh_share) /* per-plan replan: plan the whole call afresh when more than this share of its plans is FRESH (default 0.004, measured; 1: never) */ \
+  X(replan_repair_engine) /* replan: what finishes the repaired plans -- 0 the tile rounds, 5 the tile-batch engine started from the rewound fields (k_tb_warm); unset: by replan_warm_min_plans */ \
+  X(replan_warm_min_plans) /* replan, replan_repair_engine unset: the tile-batch warm start from this many repaired plans on (default 299, measured: DESIGN.md section 3.14) */ \
   X(fleet_scratch_mb)    /* fleet walks: MiB of scratch rows per chunk of robots (default 256; the result does not depend on it) */
 
 struct Options {

@@ -59,6 +59,10 @@ __global__ __launch_bounds__(kBlock) void k_replan_level(const TilePlan* __restr
   if ((threadIdx.x & 63) == 0 && m != kInfBits) atomicMin(&level[blockIdx.y], m);
 }
 
+// The rule of the rewind, for k_replan_rewind and for the warm start of the tile-batch engine (k_tb_warm, mnav_tb_warm.h): a
+// vertex keeps its value iff it is the plan's seed (at 0) or the value lies strictly below the plan's level L.
+__device__ __forceinline__ bool replan_keeps(bool is_seed, float d, float L) { return is_seed || d < L; }
+
 // The rewind: one workgroup per (tile, plan).  An owned vertex is kept iff its value lies strictly below the plan's level
 // (the seed always, at 0); every other one goes back to dist = +inf, pred = itself.  The halo is only read: its owners
 // rewind it, and whether a value is kept does not depend on who reads it first (kept values are never written).  The tile's
@@ -84,7 +88,7 @@ __global__ __launch_bounds__(kTileBlock) void k_replan_rewind(const TilePlan* __
     const uint32_t g = g_verts[v0 + i];
     const float d = g_dist[g];
     const bool is_seed = g == seed;
-    if (is_seed || d < L) {
+    if (replan_keeps(is_seed, d, L)) {
       if (is_seed && d != 0.0f) g_dist[g] = 0.0f;                     // dijkstra :276
       kmin = min(kmin, is_seed ? 0u : f2u(d)); ++nk;
     } else {
@@ -96,8 +100,8 @@ __global__ __launch_bounds__(kTileBlock) void k_replan_rewind(const TilePlan* __
   for (uint32_t i = tid; i < nh; i += kTileBlock) {
     const uint32_t g = g_halo_verts[h0 + i];
     const float d = g_dist[g];
-    if (g == seed) kmin = 0u;
-    else if (d < L) kmin = min(kmin, f2u(d));
+    const bool is_seed = g == seed;
+    if (replan_keeps(is_seed, d, L)) kmin = min(kmin, is_seed ? 0u : f2u(d));
     else open = 1u;
   }
 #pragma unroll

@@ -112,6 +112,7 @@ static int replan_each_repair(mnav_ctx* ctx, uint32_t n, const std::vector<uint3
   E.ms_classify = ev_ms(E.ev[0], E.ev[1]);
   const double share = opt_set(ctx->opt.replan_each_fresh_share) ? ctx->opt.replan_each_fresh_share : kReplanEachFreshShare;
   if (nf && (double)nf > share * (double)m) return 2;
+  const bool warm = replan_takes_warm(ctx, nr);                       // the REPAIRED plans from their rewound fields on the tile-batch engine
   // the lists on the host: ascending device plan, as k_replan_classify wrote them
   std::vector<uint32_t> tail, fresh;                                  // tail: the REPAIRED plans, then the KEPT ones
   tail.reserve(nr + nk); fresh.reserve(nf);
@@ -130,14 +131,14 @@ static int replan_each_repair(mnav_ctx* ctx, uint32_t n, const std::vector<uint3
   std::vector<PlanResult> res(m);                                     // per device plan, for the statistics of the whole call
   const TileTables T{ E.d_plans, E.d_tplans, E.d_tctl, E.d_res };
   HIPCHK(hipEventRecord(E.ev[2], ctx->stream));
-  if (nr) {
+  if (nr && !warm) {
     hipLaunchKernelGGL(k_replan_rewind, dim3(ctx->tiles_meta.ntiles ? ctx->tiles_meta.ntiles : 1u, nr), dim3(kTileBlock), 0, ctx->stream,
                        E.d_tplans, E.d_plans, E.d_level, E.d_cnt);
     HIPCHK(hipGetLastError());
   }
   HIPCHK(hipEventRecord(E.ev[3], ctx->stream));
   HIPCHK(hipEventRecord(ctx->ev[2], ctx->stream));
-  if (nr) {
+  if (nr && !warm) {
     const int rc = run_tile_rounds(ctx, nr, &T);
     if (rc != 0) { (void)hipStreamSynchronize(ctx->stream); return rc < 0 ? -1 : 1; }
     E.rounds = ctx->stats.launches; E.ms_rounds = (float)ctx->ms_chunks;
@@ -147,13 +148,24 @@ static int replan_each_repair(mnav_ctx* ctx, uint32_t n, const std::vector<uint3
     HIPCHK(hipEventRecord(E.ev[5], ctx->stream));
   }
   HIPCHK(hipEventRecord(ctx->ev[3], ctx->stream));
-  if (nr + nk) {
-    std::vector<uint32_t> tmap(nr + nk);
-    for (uint32_t j = 0; j < nr + nk; ++j) tmap[j] = map[tail[j]];
-    const TailSub sub{ E.d_plans, E.d_res, E.d_vecptrs, nr, tail.data() };
-    if (dijkstra_tail(ctx, nr + nk, 0, tmap, codes, dist_out, pred_out, path_out, path_cap, path_len, nullptr, ctx->want_vec, &sub)) return -1;
-    for (uint32_t j = 0; j < nr + nk; ++j) res[tail[j]] = ctx->h_res[j];
+  // the compacted arrays: the REPAIRED plans the rounds finished, then the KEPT ones -- the KEPT ones alone when the repair runs
+  // warm (first: the control records a KEPT plan's tail reads stand at its position, which the warm sub-batch takes over)
+  const uint32_t skip = warm ? nr : 0u, nt = nr + nk - skip;
+  if (nt) {
+    std::vector<uint32_t> tmap(nt);
+    for (uint32_t j = 0; j < nt; ++j) tmap[j] = map[tail[skip + j]];
+    const TailSub sub{ E.d_plans.get() + skip, E.d_res.get() + skip, E.d_vecptrs.get() + skip, nr - skip, tail.data() + skip };
+    if (dijkstra_tail(ctx, nt, 0, tmap, codes, dist_out, pred_out, path_out, path_cap, path_len, nullptr, ctx->want_vec, &sub)) return -1;
+    for (uint32_t j = 0; j < nt; ++j) res[tail[skip + j]] = ctx->h_res[j];
   }
+  if (warm) {
+    const std::vector<uint32_t> who(tail.begin(), tail.begin() + nr);
+    ReplanCnt tot{};
+    const int rc = replan_warm_run(ctx, m, in, who, lv, map, offset, codes, dist_out, pred_out, path_out, path_cap, path_len, &res, &tot);
+    if (rc != 0) return rc;
+    E.kept = tot.kept; E.rewound = tot.rewound; E.tiles_woken = tot.woken;
+    E.rounds = R.warm.iters; E.ms_rewind = R.warm.ms_warm; E.ms_rounds = R.warm.ms_engine; E.ms_finalize = R.warm.ms_finalize;
+  } else
   if (nr) {
     std::vector<ReplanCnt> cnt(nr);
     HIPCHK(hipMemcpy(cnt.data(), E.d_cnt, sizeof(ReplanCnt) * (size_t)nr, hipMemcpyDeviceToHost));
@@ -195,7 +207,7 @@ static int replan_each_repair(mnav_ctx* ctx, uint32_t n, const std::vector<uint3
   for (uint32_t k = 0; k < m; ++k) ctx->h_res[k] = res[k];
   ctx->last_n = m;
   finish_stats(ctx, m, false);
-  R.each_engines = 256 + (nr ? 128 : 0) + (sub_engine >= 0 ? sub_engine : 127);
+  R.each_engines = 256 + (warm ? 512 + (R.warm.kernel == 1 ? 1024 : 0) : nr ? 128 : 0) + (sub_engine >= 0 ? sub_engine : 127);
   R.levels = E.levels; R.kept = E.kept; R.rewound = E.rewound; R.tiles_woken = E.tiles_woken; R.rounds = E.rounds;
   R.ms_level = E.ms_classify; R.ms_rewind = E.ms_rewind; R.ms_rounds = E.ms_rounds; R.ms_finalize = E.ms_finalize;
   R.targets = tg; R.offset = offset; R.usable = true; R.len = 0; R.all = false;   // the change log starts over

@@ -180,7 +180,7 @@ int mnav_shard_begin(mnav_ctx* ctx, uint32_t seed_vertex, uint32_t target_vertex
   if (ctx->d_cancel) { (void)hipStreamSynchronize(ctx->cancel_stream); (void)hipMemsetAsync(ctx->d_cancel, 0, 4, ctx->stream); }
   ctx->want_vec = false;
   ctx->tb.count_pending = false; ctx->tb_args_valid = false;         // slot 0 and d_res are taken over by the sharded plan
-  ctx->last_planner = kPlannerDijkstra; ctx->last_engine = 0; ctx->last_n = 0; ctx->caller_slot.clear();
+  ctx->last_planner = kPlannerDijkstra; ctx->last_engine = 0; ctx->last_n = 0; ctx->caller_slot.clear(); ctx->rp.warm.live = false;
   ctx->rp.usable = ctx->rp.partial = false;                          // slot 0 holds a part of a sharded plan: nothing a replan can rewind
   if (materialize(ctx, false, cost_limit)) return -1;
   if (ensure_slots(ctx, 1, false, false, false)) return -1;

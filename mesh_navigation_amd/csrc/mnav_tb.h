@@ -921,6 +921,7 @@ struct TbState : TbTables, TbBatch {
   float band_mult = 2.0f;               // band = band_mult * mean edge weight * sqrt(T)  (measured on C2: 1 -> 236 ms, 2 -> 218 ms per 5120 plans)
   int iters_per_replay = 16, waves_per_cu = 0;
   Stream fill_stream; Event fill_done;  // (the fill of D2)
+  Event warm_ev[4]; float ms_warm = 0.f, ms_warm_fin = 0.f;   // a warm start (run_dijkstra_tb with a TbWarmIn): k_tb_warm and the finalize pass of the last one
   tb::Ctl last{};                       // counters of the last batch
   bool count_pending = false;           // the settled-vertex count of the last (paths-only) batch has not been taken yet
 };

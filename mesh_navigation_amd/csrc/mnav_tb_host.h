@@ -235,7 +235,11 @@ int tb_clean_other(mnav_ctx* ctx)
   return 0;
 }
 
-int run_dijkstra_tb(mnav_ctx* ctx, uint32_t n, const std::vector<PlanIn>& in, double offset)
+// warm: the n plans do not start afresh but from their rewound resident fields (k_tb_warm, mnav_tb_warm.h) -- device arrays in
+// the order of `in`: rewind levels, the potentials to read, counters (zeroed here).  Everything after the start state is the same.
+struct TbWarmIn { const uint32_t* d_level; const float* const* d_dist; ReplanCnt* d_cnt; };
+
+int run_dijkstra_tb(mnav_ctx* ctx, uint32_t n, const std::vector<PlanIn>& in, double offset, const TbWarmIn* warm = nullptr)
 {
   TbState& S = ctx->tb;
   if (tb_build(ctx)) return -1;
@@ -279,27 +283,43 @@ int run_dijkstra_tb(mnav_ctx* ctx, uint32_t n, const std::vector<PlanIn>& in, do
     A.band = band;
   }
   HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
-  bool prefilled = false;
-  if (S.D2 && S.d2_clean && S.d2_clean_np >= n) {                     // a clean buffer was prepared behind the previous call
-    std::swap(S.D, S.D2); A.D = S.D;
-    HIPCHK(hipStreamWaitEvent(ctx->stream, S.fill_done, 0));
-    prefilled = true;
+  if (!warm) {
+    bool prefilled = false;
+    if (S.D2 && S.d2_clean && S.d2_clean_np >= n) {                   // a clean buffer was prepared behind the previous call
+      std::swap(S.D, S.D2); A.D = S.D;
+      HIPCHK(hipStreamWaitEvent(ctx->stream, S.fill_done, 0));
+      prefilled = true;
+    }
+    S.d2_clean = false;
+    if (!prefilled && tb_fill(ctx, S.D, 4 * (size_t)S.S * n, kTbInfBits)) return -1;
+    if (tb_fill(ctx, S.pend, 4 * (size_t)S.ntiles * n, kTbInfBits)) return -1;
   }
-  S.d2_clean = false;
-  if (!prefilled && tb_fill(ctx, S.D, 4 * (size_t)S.S * n, kTbInfBits)) return -1;
-  if (tb_fill(ctx, S.pend, 4 * (size_t)S.ntiles * n, kTbInfBits)) return -1;
+  // (a warm start writes every word of its slices and pending words itself: it neither waits for a prepared clean buffer nor
+  // uses it up -- the buffer stays clean for the next fresh batch)
   HIPCHK(hipMemsetAsync(S.pflag, 0, (size_t)(S.ntiles ? S.ntiles : 1) * ((n + 63u) / 64u) + 64u, ctx->stream));   // (+ the padding k_tb_pairs reads as 16-byte units)
   if (tb_fill(ctx, S.marr[0], 4 * (size_t)n, kTbInfBits)) return -1;
   if (tb_fill(ctx, S.marr[1], 4 * (size_t)n, kTbInfBits)) return -1;
   HIPCHK(hipMemsetAsync(S.ctl, 0, sizeof(tb::Ctl), ctx->stream));
   HIPCHK(hipMemsetAsync(S.wstat, 0, 32 * (size_t)kTbStatSlots, ctx->stream));
   HIPCHK(hipMemsetAsync(S.bcnt, 0, 4 * (size_t)(S.ntiles ? S.ntiles : 1), ctx->stream));
+  if (warm) {
+    if (!S.warm_ev[0]) for (auto& e : S.warm_ev) HIPCHK(hipEventCreate(e.out()));
+    HIPCHK(hipMemsetAsync(warm->d_cnt, 0, sizeof(ReplanCnt) * (size_t)n, ctx->stream));
+    TbWarm Wm{};
+    Wm.level = warm->d_level; Wm.dist = warm->d_dist; Wm.cnt = warm->d_cnt;
+    Wm.verts = S.d_verts; Wm.ghost_gid = S.d_ghost_gid; Wm.order = S.d_fin_order; Wm.T = S.T;
+    const size_t groups = (size_t)std::max(S.ntiles, 1u) * ((n + 63u) / 64u);
+    if (groups >= (1ull << 31)) { ctx->err = "tile-batch engine: warm start beyond 2^31 workgroups"; return -1; }
+    HIPCHK(hipEventRecord(S.warm_ev[0], ctx->stream));
+    if (S.ntiles) hipLaunchKernelGGL(k_tb_warm, dim3((uint32_t)groups), dim3(kWarmBlock), 0, ctx->stream, A, Wm);
+    HIPCHK(hipEventRecord(S.warm_ev[1], ctx->stream));
+  } else
   hipLaunchKernelGGL(k_tb_seed, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, A);
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(ctx->ev[2], ctx->stream));
   // (the other buffer -- the previous call's distances, superseded the moment this call began -- is cleaned for the NEXT call at the
   // end of this one: tb_clean_other)
-  S.d2_wanted_np = S.D2 ? n : 0u;
+  if (!warm || !S.d2_clean) S.d2_wanted_np = S.D2 ? n : 0u;
 
   int ncu = 256;
   (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->device);
@@ -346,12 +366,18 @@ int run_dijkstra_tb(mnav_ctx* ctx, uint32_t n, const std::vector<PlanIn>& in, do
   if (rc == 0 && !ctx->lazy_paths) {
     // V-sized outputs wanted (potential, predecessors, vector map): the finalize pass of the tile engines derives the
     // reference's exact cut-off semantics and predecessors straight from the blocked distances (k_tb_finalize)
+    if (warm) HIPCHK(hipEventRecord(S.warm_ev[2], ctx->stream));
     if (tb_fields(ctx, n, in, offset, A)) return -1;
+    if (warm) HIPCHK(hipEventRecord(S.warm_ev[3], ctx->stream));
   }
   HIPCHK(hipEventRecord(ctx->ev[3], ctx->stream));
   HIPCHK(hipEventSynchronize(ctx->evc[1]));
   ctx->ms_chunks = ev_ms(ctx->evc[0], ctx->evc[1]);
   S.last = *S.h_ctl;
+  if (warm && rc == 0) {
+    HIPCHK(hipEventSynchronize(S.warm_ev[3]));
+    S.ms_warm = ev_ms(S.warm_ev[0], S.warm_ev[1]); S.ms_warm_fin = ev_ms(S.warm_ev[2], S.warm_ev[3]);
+  }
   ctx->stats.launches = 1;                                           // one engine run per batch (iterations: stats.steps)
   ctx->tb_args = A; ctx->tb_args_valid = (rc == 0);
   if (opt_on(ctx->opt.trace))

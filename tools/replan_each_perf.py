@@ -22,7 +22,14 @@ One batch size per process, every GPU step under its own time limit, chained:
 
     timeout -k 10 600 python tools/replan_each_perf.py --plans 64 &&
     timeout -k 10 600 python tools/replan_each_perf.py --plans 1024 --append &&
-    timeout -k 10 1100 python tools/replan_each_perf.py --plans 7168 --append --sequential"""
+    timeout -k 10 1100 python tools/replan_each_perf.py --plans 7168 --append --sequential
+
+--repair-engine 0,5 measures the repair engines of the REPAIRED plans against each other instead (option replan_repair_engine:
+0 the tile rounds, 5 the tile-batch engine started from the rewound fields by k_tb_warm): one `each` context per value and the
+fresh plan, in the same run, no `batch` context; the rows go to the list `repair_engine_cases` of the file, next to the old
+rows, with the warm start's own figures (mnav_replan_warm_stats: plans, iterations, ms of k_tb_warm, of the engine and of the
+finalize pass, and k_tb_warm's GB/s over NP * S * 8 bytes) and, for comparison, the iterations of the fresh batch and the rate
+of a 1 GiB device-to-device copy taken in the same process."""
 from __future__ import annotations
 
 import argparse
@@ -75,8 +82,29 @@ def make(mesh, w, costs):
     return c
 
 
+def copy_rate():
+    """GB/s (read + written) of a 1 GiB device-to-device copy, best of 5 after a warm-up; None without torch"""
+    try:
+        import torch
+    except ImportError:
+        return None
+    a = torch.empty(1 << 28, dtype=torch.float32, device="cuda")
+    b = torch.empty_like(a)
+    a.fill_(1.0)
+    best = None
+    for k in range(6):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(); b.copy_(a); e1.record(); torch.cuda.synchronize()
+        ms = e0.elapsed_time(e1)
+        if k and (best is None or ms < best):
+            best = ms
+    del a, b
+    torch.cuda.empty_cache()
+    return 2.0 * (1 << 30) / (best * 1e-3) / 1e9
+
+
 def call(kind, ctx, seeds, tg):
-    if kind == "each":
+    if kind.startswith("each"):
         return ctx.replan_dijkstra_each(tg, 0.3, path_cap=PATH_CAP, want_stats=False)
     if kind == "batch":
         return ctx.replan_dijkstra(tg, 0.3, path_cap=PATH_CAP, want_stats=False)
@@ -105,7 +133,15 @@ def run_case(ctxs, seeds, robots, events, reps, warm):
             r = rec[kind]
             if k >= warm:
                 r["ms"].append(ms)
-                if kind == "each":
+                if kind.startswith("each@"):
+                    wm = c.replan_warm_stats()
+                    for key in ("plans", "iterations", "pairs_woken", "words", "ms_warm", "ms_engine", "ms_finalize", "fallback"):
+                        r.setdefault("warm_" + key, []).append(wm[key])
+                    r["warm_kernel"] = wm["kernel"]
+                if kind == "fresh":
+                    r.setdefault("iterations", []).append(c.timing().get("steps", 0))
+                    r["engine"] = c.last_engine()
+                if kind.startswith("each"):
                     e = c.replan_each_stats(n)
                     for key in ("kept_plans", "repaired_plans", "fresh_plans", "kept", "rewound", "tiles_woken", "rounds", "whole_fresh", "reason",
                                 "ms_classify", "ms_rewind", "ms_rounds", "ms_finalize", "ms_fresh"):
@@ -116,7 +152,14 @@ def run_case(ctxs, seeds, robots, events, reps, warm):
     out = {}
     for kind, r in rec.items():
         o = dict(ms=spread(r["ms"]))
-        if kind == "each":
+        if kind.startswith("each@"):
+            o["warm"] = {key: float(np.median(r["warm_" + key])) for key in ("plans", "iterations", "pairs_woken", "words", "ms_warm", "ms_engine", "ms_finalize", "fallback")}
+            o["warm"]["kernel"] = r["warm_kernel"]
+            if o["warm"]["ms_warm"] > 0:
+                o["warm"]["k_tb_warm_GBps"] = 8.0 * o["warm"]["words"] / (o["warm"]["ms_warm"] * 1e-3) / 1e9
+        if kind == "fresh":
+            o["iterations"] = int(np.median(r["iterations"])); o["engine"] = r["engine"]
+        if kind.startswith("each"):
             for key in ("kept_plans", "repaired_plans", "fresh_plans", "kept", "rewound", "tiles_woken", "rounds"):
                 o[key] = int(np.median(r[key]))
             o["split_ms"] = {key[3:]: float(np.median(r[key])) for key in ("ms_classify", "ms_rewind", "ms_rounds", "ms_finalize", "ms_fresh")}
@@ -153,9 +196,13 @@ def main():
     ap.add_argument("--only", default="", help="run the cases of this kind only")
     ap.add_argument("--sequential", action="store_true", help="one context at a time (resident outputs of a large batch fill the device)")
     ap.add_argument("--append", action="store_true", help="add this batch size to an existing file")
+    ap.add_argument("--repair-engine", default="", help="values of replan_repair_engine to measure against each other (0,5): rows go to repair_engine_cases")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "replan_each_perf.json"))
     args = ap.parse_args()
     n, reps, warm = args.plans, args.reps, args.warmup
+    engines = [int(x) for x in args.repair_engine.split(",") if x]
+    kinds = tuple("each@%d" % e for e in engines) + ("fresh",) if engines else KINDS
+    d2d = copy_rate() if engines else None
     shares = [float(s) for s in args.shares.split(",") if s]
     mesh = meshgen.terrain(N, 0.1, 2)
     w = meshgen.edge_lengths(mesh)
@@ -182,9 +229,12 @@ def main():
             ev = (lambda robots, hop: lambda k: (None, None, hop if k % 2 == 0 else robots))(robots, hop)
         inputs.append((kind, phi, seeds, robots, ev, ids))
     records = [dict(plans=n, kind=kind, goals_near_the_patch=phi) for kind, phi, *_ in inputs]
-    groups = [[k] for k in KINDS] if args.sequential else [list(KINDS)]
+    groups = [[k] for k in kinds] if args.sequential else [list(kinds)]
     for group in groups:
         ctxs = {kind: make(mesh, w, costs) for kind in group}
+        for kind, c in ctxs.items():
+            if kind.startswith("each@"):
+                c.set_option("replan_repair_engine", int(kind[5:]))
         for rec, (kind, phi, seeds, robots, ev, ids) in zip(records, inputs):
             rec.update(run_case(ctxs, seeds, robots, ev, reps, warm))
             if kind != "robots only" and (warm + reps) % 2:            # leave the map as it was
@@ -196,9 +246,21 @@ def main():
     result = dict(mesh="terrain(1000, 0.1, 2): 1 000 000 vertices, uploaded weights (edge_cost_factor 0)", offset=0.3,
                   method="wall ms per call, resident outputs on, one context per entry point on the same final map; medians of the repetitions after the warm-ups",
                   cases=[], crossing={})
-    if args.append and os.path.exists(args.out):
+    if (args.append or engines) and os.path.exists(args.out):
         with open(args.out) as fh:
             result = json.load(fh)
+    if engines:                                                        # next to the old rows, not over them
+        rows = result.setdefault("repair_engine_cases", [])
+        done = {(r["kind"], r["goals_near_the_patch"]) for r in records}
+        rows[:] = [c for c in rows if c["plans"] != n or (c["kind"], c["goals_near_the_patch"]) not in done]
+        for rec in records:
+            rec.update(repetitions=reps, warmups=warm, alternated=not args.sequential, d2d_copy_GBps=d2d)
+            rows.append(rec)
+        with open(args.out, "w") as fh:
+            json.dump(result, fh, indent=1)
+            fh.write("\n")
+        return
+    if args.append and os.path.exists(args.out):
         done = {(r["kind"], r["goals_near_the_patch"]) for r in records}
         result["cases"] = [c for c in result["cases"] if c["plans"] != n or (c["kind"], c["goals_near_the_patch"]) not in done]
     for rec in records:

@@ -16,7 +16,11 @@ buffers, the C call, mnav_get_timing; mnav_replan_stats and the downloads for th
 The replan is split by mnav_replan_stats into level, rewind, rounds and finalize; `tail` is the rest of the call (tables
 rebuilt for the new costs, path walks, vector map, result download).
 
-    python tools/replan_perf.py [--reps K] [--out FILE]"""
+    python tools/replan_perf.py [--reps K] [--out FILE]
+
+--repair-engine 0,5 runs the same cases once per value of the option replan_repair_engine on context A (0 the tile rounds, 5
+the tile-batch engine started from the rewound fields by k_tb_warm) and appends the rows, each with its `repair_engine` and the
+figures of mnav_replan_warm_stats, to the list `repair_engine_cases` of the file, next to the old rows."""
 from __future__ import annotations
 
 import argparse
@@ -78,6 +82,7 @@ def run_case(A, B, seeds, target0, events, reps, warm):
         assert np.array_equal(a["codes"], b["codes"]) and np.array_equal(a["path_len"], b["path_len"]), "replan and fresh plan differ"
         rp = A.replan_stats(n)
         if k >= warm:
+            rec.setdefault("warm", []).append(A.replan_warm_stats())
             rec["replan"].append(ms_a); rec["fresh"].append(ms_b)
             for key in ("level", "rewind", "rounds", "finalize"):
                 rec[key].append(rp["ms_" + key])
@@ -95,14 +100,41 @@ def run_case(A, B, seeds, target0, events, reps, warm):
                level_over_cut=dict(min=float(np.median(rec["ratio_min"])), median=float(np.median(rec["ratio_median"]))) if rec["ratio_min"] else None)
     out["split_ms"]["tail"] = out["replan_ms"]["median"] - sum(out["split_ms"].values())
     out["speedup"] = out["fresh_ms"]["median"] / out["replan_ms"]["median"]
+    out["warm"] = {k: float(np.median([x[k] for x in rec["warm"]])) for k in ("plans", "iterations", "pairs_woken", "words", "ms_warm", "ms_engine", "ms_finalize", "fallback")}
     print(json.dumps(out), flush=True)
     return out
+
+
+def all_cases(A, B, batches, robot, reps, warm, engine):
+    """every patch position and the target-only move for every batch; engine: A's replan_repair_engine (None: unset)"""
+    cases = []
+    for n, seeds in batches.items():
+        for f in FRACTIONS:
+            ids = patch(int(round((0.1 + 0.8 * f) * (N - 1))), (N - 1) // 2)
+            rec = run_case(A, B, seeds, robot, lambda k: (ids, 1.5 if k % 2 == 0 else 0.0, robot), reps, warm)
+            if rec["reasons"] != [0]:
+                raise SystemExit("a replan planned afresh: nothing to compare")
+            # leave the map as it was (an even number of events frees the patch again)
+            if (warm + reps) % 2:
+                for c in (A, B):
+                    c.update_costs(ids, np.zeros(ids.size, np.float32))
+            rec.update(kind="patch", placed_at=f)
+            cases.append(rec)
+        hop = robot - 10
+        rec = run_case(A, B, seeds, robot, lambda k: (None, None, hop if k % 2 == 0 else robot), reps, warm)
+        rec.update(kind="target only", placed_at=None)
+        cases.append(rec)
+    if engine is not None:
+        for rec in cases:
+            rec.update(repair_engine=engine)
+    return cases
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--repair-engine", default="", help="values of replan_repair_engine to run the cases with (0,5): rows go to repair_engine_cases")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "replan_perf.json"))
     args = ap.parse_args()
     reps = max(7, args.reps)
@@ -121,22 +153,22 @@ def main():
     result = dict(mesh="terrain(1000, 0.1, 2): 1 000 000 vertices, uploaded weights (edge_cost_factor 0)", offset=0.3, repetitions=reps,
                   method="alternating replan (context A) / fresh plan under auto (context B) on the same final map, wall ms per call, resident outputs on",
                   cases=[])
-    for n, seeds in batches.items():
-        for f in FRACTIONS:
-            ids = patch(int(round((0.1 + 0.8 * f) * (N - 1))), (N - 1) // 2)
-            rec = run_case(A, B, seeds, robot, lambda k: (ids, 1.5 if k % 2 == 0 else 0.0, robot), reps, args.warmup)
-            if rec["reasons"] != [0]:
-                raise SystemExit("a replan planned afresh: nothing to compare")
-            # leave the map as it was (an even number of events frees the patch again)
-            if (args.warmup + reps) % 2:
-                for c in (A, B):
-                    c.update_costs(ids, np.zeros(ids.size, np.float32))
-            rec.update(kind="patch", placed_at=f)
-            result["cases"].append(rec)
-        hop = robot - 10
-        rec = run_case(A, B, seeds, robot, lambda k: (None, None, hop if k % 2 == 0 else robot), reps, args.warmup)
-        rec.update(kind="target only", placed_at=None)
-        result["cases"].append(rec)
+    engines = [int(x) for x in args.repair_engine.split(",") if x]
+    for engine in engines or [None]:
+        A.set_option("replan_repair_engine", engine)
+        result["cases"] += all_cases(A, B, batches, robot, reps, args.warmup, engine)
+    if engines:                                                        # next to the old rows, not over them
+        rows = result["cases"]
+        result = {}
+        if os.path.exists(args.out):
+            with open(args.out) as fh:
+                result = json.load(fh)
+        result["repair_engine_cases"] = rows
+        with open(args.out, "w") as fh:
+            json.dump(result, fh, indent=1)
+            fh.write("\n")
+        A.close(); B.close()
+        return
     # where the curves cross: the largest measured L / cut_old at which the fresh plan still wins (median against median)
     for n in batches:
         rows = sorted((c for c in result["cases"] if c["plans"] == n and c["kind"] == "patch"), key=lambda c: c["level_over_cut"]["min"])
