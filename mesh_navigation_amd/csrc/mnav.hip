@@ -178,7 +178,8 @@ struct mnav_ctx {
   DevBuf<float*> d_vecptrs;
   DevBuf<uint32_t> d_paths; size_t paths_words = 0; uint32_t path_stride = 0;   // n plans x path_stride vertex ids
   DevBuf<uint32_t> d_over; DevBuf<unsigned long long> d_over_off; DevBuf<uint32_t> d_over_cap;   // exact rows of the paths that did not fit
-  DevBuf<uint32_t> d_pack; PinnedBuf<uint32_t> h_pack; DevBuf<uint32_t> d_pack_meta; size_t pack_words = 0, pack_meta_n = 0;   // packed paths (device, pinned host), offsets + lengths
+  DevBuf<uint32_t> d_pack; PinnedBuf<uint32_t> h_pack; DevBuf<uint32_t> d_pack_meta; size_t pack_words = 0, h_pack_words = 0, pack_meta_n = 0;   // packed paths (device, pinned host), offsets + lengths
+  PinnedBuf<uint32_t> h_mism;   // the fixed-point check's counter, downloaded with the results
   PinnedBuf<Ctl> h_ctl;       // 2 per plan
   uint32_t infl_exact_bands = 0;   // bands of the last inflation wave that went through the exact band routine (k_exact_band)
   DevBuf<float> d_seed_pos; uint32_t seed_pos_cap = 1;
@@ -1415,11 +1416,37 @@ static int dijkstra_tail(mnav_ctx* ctx, uint32_t m, int engine, const std::vecto
   if (want_vecmap && n_vec && !(engine == 5 && !ctx->lazy_paths))   // (the tile-batch engine's finalize pass writes the vector map itself)
     hipLaunchKernelGGL(k_vecmap_dijkstra, dim3(gc ? gc : 1, n_vec), dim3(kBlock), 0, ctx->stream, d_plans, ctx->d_xyz, sub ? sub->vecptrs : ctx->d_vecptrs.get());
   (void)hipEventRecord(ctx->ev[5], ctx->stream);
+  // The packed paths follow the walk on the device: offsets by k_pack_offsets, k_pack_paths behind it, nothing in between that
+  // waits for the host (until this was moved the lengths went down, the host summed them and sent the offsets up again, with
+  // the device idle meanwhile).  The pack buffer holds the worst case, every row full.
+  const bool pack = path_out && path_cap;
+  auto ensure_pack = [&](size_t words) {
+    if (ctx->pack_words < words) {
+      ctx->d_pack.reset(); ctx->pack_words = 0;
+      if (ctx->d_pack.alloc(4 * words) != hipSuccess) return false;
+      ctx->pack_words = words;
+    }
+    if (ctx->pack_meta_n < 2 * (size_t)m) {
+      ctx->pack_meta_n = 0;
+      if (ctx->d_pack_meta.alloc(4 * 2 * (size_t)m) != hipSuccess) return false;
+      ctx->pack_meta_n = 2 * (size_t)m;
+    }
+    return true;
+  };
+  if (pack) {
+    if (!ensure_pack((size_t)m * (ctx->path_stride ? ctx->path_stride : 1u))) { ctx->err = "path buffers: out of memory"; return -1; }
+    hipLaunchKernelGGL(k_pack_offsets, dim3(1), dim3(1024), 0, ctx->stream, d_res, m, ctx->d_pack_meta, ctx->d_pack_meta + m);
+    hipLaunchKernelGGL(k_pack_paths, dim3(m), dim3(kBlock), 0, ctx->stream, rows1, rows2, ctx->d_pack_meta, ctx->d_pack_meta + m, ctx->d_pack);
+  }
+  const bool check_mism = ctx->last_engine != 1;
+  if (check_mism && !ctx->h_mism && ctx->h_mism.alloc(4) != hipSuccess) { ctx->err = "result download failed"; return -1; }
   if (hipMemcpyAsync(ctx->h_res, d_res, sizeof(PlanResult) * m, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+      (check_mism && hipMemcpyAsync(ctx->h_mism, ctx->d_mismatch, 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) ||
       hipStreamSynchronize(ctx->stream) != hipSuccess) { ctx->err = "result download failed"; return -1; }
+  bool repack = false;
   {
     // paths longer than the default rows (corridors, mazes): ONLY those plans are walked again, into rows of exactly their
-    // length (the first walk counted it) in one packed buffer
+    // length (the first walk counted it) in one packed buffer, and all paths are packed again with offsets from the host
     size_t over_words = 0;
     std::vector<unsigned long long> ooff(m, 0ull); std::vector<uint32_t> ocap(m, 0u);
     for (uint32_t k = 0; k < m; ++k)
@@ -1436,45 +1463,50 @@ static int dijkstra_tail(mnav_ctx* ctx, uint32_t m, int engine, const std::vecto
       else if (ctx->lazy_paths) hipLaunchKernelGGL(k_path_lazy, dim3(m), dim3(kWave), 0, ctx->stream, ctx->d_plans, ctx->d_tplans, ctx->d_res, rows2, ctx->d_mismatch);
       else hipLaunchKernelGGL(k_finish<kPlannerDijkstra>, dim3(m), dim3(64), 0, ctx->stream, d_plans, d_res, rows2);
       if (hipMemcpyAsync(ctx->h_res, d_res, sizeof(PlanResult) * m, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+          (check_mism && hipMemcpyAsync(ctx->h_mism, ctx->d_mismatch, 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) ||
           hipStreamSynchronize(ctx->stream) != hipSuccess) { ctx->err = "result download failed"; return -1; }
       for (uint32_t k = 0; k < m; ++k) ctx->h_res[k].settled = keep[k].settled;
+      repack = true;
     }
   }
-  if (ctx->last_engine != 1) {
-    uint32_t mism = 0;
-    if (hipMemcpy(&mism, ctx->d_mismatch, 4, hipMemcpyDeviceToHost) != hipSuccess || mism != 0) {
-      ctx->err = "tiled SSSP did not reach its fixed point (" + std::to_string(mism) + " vertices)";
-      return -1;
-    }
+  if (check_mism && *ctx->h_mism != 0u) {
+    ctx->err = "tiled SSSP did not reach its fixed point (" + std::to_string(*ctx->h_mism) + " vertices)";
+    return -1;
   }
   MTRACE("results downloaded");
-  // all vertex paths: packed and reversed on the device (k_pack_paths), one dense copy into a pinned buffer
+  // all vertex paths: packed and reversed on the device (k_pack_paths), one dense copy into a pinned buffer -- of the words
+  // the downloaded lengths add up to, which is why this copy comes after the results and not with them (rows are sized
+  // for paths an order of magnitude longer than a terrain's, so the row-full worst case is many times these words)
   std::vector<uint32_t> offs(m + 1, 0), lens(m, 0);
   for (uint32_t k = 0; k < m; ++k) {
     lens[k] = (ctx->h_res[k].code == MNAV_SUCCESS) ? ctx->h_res[k].path_len : 0u;
     offs[k + 1] = offs[k] + lens[k];
   }
   const size_t total = offs[m];
-  if (total && path_out && path_cap) {
-    if (ctx->pack_words < total) {
-      ctx->d_pack.reset(); ctx->h_pack.reset(); ctx->pack_words = 0;
+  if (total && pack) {
+    if (ctx->h_pack_words < total) {
+      ctx->h_pack.reset(); ctx->h_pack_words = 0;
       const size_t want = total + total / 4 + 1024;
-      if (ctx->d_pack.alloc(4 * want) != hipSuccess || ctx->h_pack.alloc(4 * want) != hipSuccess)
-        { ctx->err = "path buffers: out of memory"; return -1; }
-      ctx->pack_words = want;
+      if (ctx->h_pack.alloc(4 * want) != hipSuccess) { ctx->err = "path buffers: out of memory"; return -1; }
+      ctx->h_pack_words = want;
     }
-    if (ctx->pack_meta_n < 2 * (size_t)m) {
-      ctx->pack_meta_n = 0;
-      if (ctx->d_pack_meta.alloc(4 * 2 * (size_t)m) != hipSuccess) { ctx->err = "path buffers: out of memory"; return -1; }
-      ctx->pack_meta_n = 2 * (size_t)m;
+    if (repack) {
+      if (!ensure_pack(total)) { ctx->err = "path buffers: out of memory"; return -1; }
+      if (hipMemcpyAsync(ctx->d_pack_meta, offs.data(), 4 * (size_t)m, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+          hipMemcpyAsync(ctx->d_pack_meta + m, lens.data(), 4 * (size_t)m, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+        { ctx->err = "path download failed"; return -1; }
+      hipLaunchKernelGGL(k_pack_paths, dim3(m), dim3(kBlock), 0, ctx->stream, rows1, rows2, ctx->d_pack_meta, ctx->d_pack_meta + m, ctx->d_pack);
     }
-    if (hipMemcpyAsync(ctx->d_pack_meta, offs.data(), 4 * (size_t)m, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
-        hipMemcpyAsync(ctx->d_pack_meta + m, lens.data(), 4 * (size_t)m, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-      { ctx->err = "path download failed"; return -1; }
-    hipLaunchKernelGGL(k_pack_paths, dim3(m), dim3(kBlock), 0, ctx->stream, rows1, rows2, ctx->d_pack_meta, ctx->d_pack_meta + m, ctx->d_pack);
-    if (hipMemcpyAsync(ctx->h_pack, ctx->d_pack, 4 * total, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-        hipStreamSynchronize(ctx->stream) != hipSuccess) { ctx->err = "path download failed"; return -1; }
+    if (hipMemcpyAsync(ctx->h_pack, ctx->d_pack, 4 * total, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) { ctx->err = "path download failed"; return -1; }
   }
+  // The tile-batch engine's other distance buffer is cleaned for the next call from HERE (tb_clean_other: its stream waits for an
+  // event recorded at this point), under the host's copy-out below and the gap before the next call.  Not earlier: launched
+  // behind k_pack_paths, the fill held the download of the results back until it had finished (6.6 - 7.2 ms for a copy of
+  // microseconds, profiles/sched_pass_kernel_stats.md) -- the copy is a kernel too, and a kernel next to the fill ends with it.
+  // (A call that downloads V-sized outputs below cleans behind those instead.)
+  const bool field_downloads = dist_out || pred_out || (vecmap_out && want_vecmap);
+  if (engine == 5 && !field_downloads && tb_clean_other(ctx)) return -1;
+  if (total && pack && hipStreamSynchronize(ctx->stream) != hipSuccess) { ctx->err = "path download failed"; return -1; }
   MTRACE("paths downloaded");
   for (uint32_t k = 0; k < m; ++k) {
     const uint32_t i = map[k];
@@ -1496,7 +1528,7 @@ static int dijkstra_tail(mnav_ctx* ctx, uint32_t m, int engine, const std::vecto
   MTRACE("paths copied out");
   (void)hipEventRecord(ctx->ev[6], ctx->stream);
   if (hipStreamSynchronize(ctx->stream) != hipSuccess) { ctx->err = "sync failed"; return -1; }
-  if (engine == 5 && tb_clean_other(ctx)) return -1;   // (the next call's distance buffer, in the gap between the calls)
+  if (engine == 5 && tb_clean_other(ctx)) return -1;   // (does nothing when the buffer was cleaned above)
   finish_stats(ctx, m, false);
   MTRACE("stats done");
   return 0;

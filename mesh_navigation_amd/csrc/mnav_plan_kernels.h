@@ -190,6 +190,32 @@ __global__ __launch_bounds__(kBlock) void k_pack_paths(PathRows rows, PathRows o
   for (uint32_t q = threadIdx.x; q < len; q += kBlock) dst[q] = src[len - 1 - q];
 }
 
+// Where k_pack_paths puts each path, computed where the lengths are: lens[k] = the path length of a successful plan (0
+// otherwise), offs[k] = the sum of the lengths before it.  One workgroup walks the m plans 1024 at a time (m <= 65535: a
+// few microseconds), so that the pack follows the path walk without a trip to the host for a prefix sum.
+__global__ __launch_bounds__(1024) void k_pack_offsets(const PlanResult* __restrict__ res, uint32_t m, uint32_t* __restrict__ offs, uint32_t* __restrict__ lens)
+{
+  __shared__ uint32_t s_wave[16], s_carry;
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  if (threadIdx.x == 0) s_carry = 0u;
+  __syncthreads();
+  for (uint32_t base = 0; base < m; base += 1024u) {
+    const uint32_t k = base + threadIdx.x;
+    const uint32_t len = (k < m && res[k].code == kSuccess) ? res[k].path_len : 0u;
+    uint32_t incl = len;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const uint32_t x = __shfl_up(incl, o); if (lane >= (uint32_t)o) incl += x; }
+    if (lane == 63u) s_wave[wave] = incl;
+    __syncthreads();
+    uint32_t before = s_carry;
+    for (uint32_t w = 0; w < wave; ++w) before += s_wave[w];
+    if (k < m) { offs[k] = before + incl - len; lens[k] = len; }
+    __syncthreads();
+    if (threadIdx.x == 1023u) s_carry = before + incl;
+    __syncthreads();
+  }
+}
+
 // settled vertices of a lazily finished plan: the popped ones, dist <= goal_dist (conservative against k_dij_finalize's
 // count, which includes the tentative ring beyond goal_dist)
 __global__ __launch_bounds__(kBlock) void k_count_goal(const Plan* __restrict__ plans, PlanResult* __restrict__ res)

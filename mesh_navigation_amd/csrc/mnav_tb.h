@@ -14,7 +14,7 @@
 //
 // Schedule (level-synchronous over all plans, a few launches per iteration, replayed from a hipGraph):
 //   k_tb_plan    per plan: band threshold thr = (smallest pending wake-up) + band, bound = dist[target] + offset
-//   k_tb_scan    every pending value pend[tile][plan]: < thr -> the tile's bucket; > bound -> dropped; else carried (counted)
+//   k_tb_sched   every pending value pend[tile][plan]: < thr -> the tile's bucket; > bound -> dropped; else carried (a wave per tile)
 //   k_tb_items   per tile: the bucket is cut into work items of <= 16 plans
 //   k_tb_solve_q per item: load the plans' slices, fold the ghost values in, sweep, write back what changed, wake the
 //                neighbouring tiles whose vertices were undercut, export changed boundary values to their ghost slots
@@ -49,7 +49,6 @@ struct Ctl {
   unsigned long long sweeps; // wave sweeps
   unsigned long long items;  // work items (waves of <= 64 plans)
   unsigned long long wakes;
-  uint32_t n_pairs, pad_;    // (tile, block of 64 plans) pairs whose pending flag is set this iteration (k_tb_pairs -> k_tb_scan)
 };
 
 struct Args {
@@ -57,13 +56,12 @@ struct Args {
   float* D; uint32_t* pend; uint32_t NP, ntiles;
   uint16_t* bucket; uint32_t* bcnt; uint2* items; Ctl* ctl;
   uint32_t* marr[2];
+  uint32_t* mcarry;                                                   // kTbMinCopies x NP: the smallest CARRIED value per plan, by tile % kTbMinCopies (k_tb_sched -> k_tb_plan)
   float* thr; float* bnd;
   const uint32_t* seed; const uint32_t* target;                        // per plan: wave source / robot vertex
   const uint2* vaddr; const uint32_t* vert_tile;                      // per vertex: {soff, sl << 8 | local}, tile
   double offset; float band;
   uint8_t* pflag; uint32_t nblk;                                     // per (tile, block of 64 plans): 1 = some pend[tile][plan] of the block may be set
-  uint32_t* pairs; uint32_t n_flag16;                                // the flagged pairs of the iteration (tile * nblk + block); 16-byte units of the flag matrix
-  uint32_t nblk_magic, nblk_shift;                                   // pair / nblk as one multiply-high and a shift (tb::div_magic; k_tb_scan divides once per listed row)
   unsigned long long* wstat; uint32_t wstat_slots;                  // statistics per persistent wave {items, activations, sweeps, wakes}: k_tb_stats sums them
   uint32_t item_plans;                                               // plans per work item: 16 (a quarter of a wave, k_tb_solve_q) or 64 (a wave, k_tbv_solve)
 };
@@ -79,12 +77,6 @@ typedef __attribute__((address_space(3))) u32x4* lds_u32x4_t;
 __device__ __forceinline__ u32x4 ldsr4(uint32_t off) { return *(lds_u32x4_t)(uintptr_t)off; }   // uniform address: broadcast
 
 __device__ __forceinline__ uint32_t rfl(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
-
-// n / d for n < 2^31 as one multiply-high and a shift (mnav::tb_div_magic, mnav_tb_build.h, makes the pair on the host)
-__device__ __forceinline__ uint32_t div_by_magic(uint32_t n, uint32_t d, uint32_t magic, uint32_t shift)
-{
-  return d <= 1u ? n : (__umulhi(n, magic) >> shift);                  // (= mnav::tb_div_by_magic, the host's copy the CPU test runs)
-}
 
 }  // namespace tb
 
@@ -122,17 +114,32 @@ __global__ __launch_bounds__(kBlock) void k_tb_seed(tb::Args A)
   A.pend[(size_t)t * A.NP + p] = 0u;
   A.pflag[(size_t)t * A.nblk + (p >> 6)] = 1;
   A.marr[0][p] = 0u;
-  A.ctl->n_cand[0] = 1u;                                              // (a flag: see k_tb_scan)
+  A.ctl->n_cand[0] = 1u;                                              // (a flag: see k_tb_sched)
 }
 
+// The smallest carried value of a plan is an atomicMin per carried (tile, plan) -- ~180 tiles per plan and iteration at 7168 plans
+// on the 1M mesh, from every CU at once.  Atomics execute at the memory side, and all of them into the 28 KB of ONE array of NP words is the
+// contended case; so k_tb_sched keeps kTbMinCopies arrays, a tile using copy tile % kTbMinCopies, and k_tb_plan folds them into the plan's
+// minimum (and resets them) when it reads it.  The solve kernels and the start kernels keep writing marr[] itself.
+constexpr uint32_t kTbMinCopies = 64;
 // per plan and iteration: band threshold and goal bound
 __global__ __launch_bounds__(kBlock) void k_tb_plan(tb::Args A, int par)
 {
   const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
-  if (p == 0) { A.ctl->n_cand[par ^ 1] = 0u; A.ctl->next_item = 0u; A.ctl->n_items = 0u; A.ctl->n_pairs = 0u; A.ctl->iters += 1u; }
+  if (p == 0) { A.ctl->n_cand[par ^ 1] = 0u; A.ctl->next_item = 0u; A.ctl->n_items = 0u; A.ctl->iters += 1u; }
   if (p >= A.NP) return;
-  const uint32_t mb = A.marr[par][p];
+  uint32_t mb = A.marr[par][p];
   A.marr[par ^ 1][p] = kTbInfBits;
+  {
+    uint32_t x[kTbMinCopies];
+#pragma unroll
+    for (uint32_t c = 0; c < kTbMinCopies; ++c) x[c] = A.mcarry[(size_t)c * A.NP + p];
+#pragma unroll
+    for (uint32_t c = 0; c < kTbMinCopies; ++c) {
+      mb = min(mb, x[c]);                                               // (values >= 0: their bits order like they do)
+      if (x[c] != kTbInfBits) A.mcarry[(size_t)c * A.NP + p] = kTbInfBits;
+    }
+  }
   const float m = u2f(mb);
   const float dt = A.D[tb::slot_addr(A.vaddr[A.target[p]], A.NP, p)];
   const float bound = (float)((double)dt + fmax(A.offset, 0.0));    // >= the final goal_dist (dijkstra :296); a negative offset is applied after the rounds (goal_cut)
@@ -145,130 +152,125 @@ __global__ __launch_bounds__(kBlock) void k_tb_plan(tb::Args A, int par)
 
 // The pending values pend[tile][plan] (+inf: none) once per iteration: an entry below its plan's band threshold is READY (cleared,
 // the plan goes into the tile's bucket), one beyond the goal bound is dropped (it can never propagate any more: the bound only
-// shrinks), the rest is CARRIED (counted, and its smallest value per plan is next iteration's band start).  The matrix is sparse --
+// shrinks), the rest is CARRIED (and its smallest value per plan is next iteration's band start).  The matrix is sparse --
 // a plan's pending tiles are the ring around its front --: one byte per (tile, block of 64 plans), set by whoever writes a pending
 // value, says whether a 256-byte row of it may hold anything.  Rounds 3-4 walked ALL rows (a thread per plan down a column of 16
-// tiles, skipping rows by their flag): 92 600 tiles x 64 blocks of flags per iteration on the 10M mesh, 21 % of the engine run
-// (profiles/r05_c4_kernel_stats.md).  Now k_tb_pairs compacts the set flags into a list (the 5.9 MB flag matrix read as 16-byte
-// units: microseconds) and k_tb_scan gives one wave to each listed row.
-constexpr uint32_t kTbPairUnits = 4;                                 // 16-byte units of the flag matrix per thread of k_tb_pairs
-// (one atomic per WORKGROUP of 256 threads x 4 units = 16 384 flags: the list's counter is one address, and one atomic per wave of 64
-// units was 5 800 atomics in a row at the L2 on the 10M mesh -- 52 us for a pass that reads 6 MB)
-__global__ __launch_bounds__(kBlock) void k_tb_pairs(tb::Args A)
+// tiles, skipping rows by their flag); rounds 5-6 compacted the set flags into one global list and dealt its rows to persistent
+// waves, which made every row pay for the list: the entry fetch, a division by the blocks per tile, 64-bit addresses rebuilt from
+// the tile, and a returning atomicAdd on the tile's bucket counter (zero counts included) in the middle of the turn -- ~130
+// instructions per row for 6-16 % of the lanes holding a value, and a launch of its own to build the list.
+// Now ONE WAVE OWNS A TILE for the iteration (a workgroup: kTbSchedTiles consecutive tiles).  It loads the tile's flag bytes, a
+// byte per lane and 64 blocks at a time, ballots them into a mask and walks the set blocks in ascending order.  The bucket base is
+// a running count in a scalar register and bcnt[tile] one plain store at the end: no atomic on the counter, no list, no division,
+// and the tile part of every address is computed once per wave.  A tile without a set flag leaves after the flag load (the 10M
+// mesh: 92 600 tiles, most of them idle).  What round 6 learnt stays: a block's four loads -- pending values, thresholds,
+// bounds, the plans' carried minima -- go out a turn ahead, every one of them unconditional at a clamped address, and no word is
+// written by every wave ("something is still pending" is a plain store of 1 by the waves that carried something).
+// A turn is one trip to memory whatever it carries -- the wait for a block's loads also waits for the stores of the turn before,
+// the memory counter counts in order -- and with one block per turn the pass took as long as the list did: a tile's ~22 set
+// blocks of 112 (7168 plans, 1M mesh) were 22 trips in a row, 58 us per launch against 49 + 6 us for list and scan, with every
+// wave slot of the device taken (9 260 tiles, 8 192 slots: a second wave per tile has nowhere to run).  So a turn takes
+// kTbSchedDepth blocks: their loads go out together, a group ahead.
+// The order of a tile's bucket is now ascending by plan; the fixed point does not depend on it.
+constexpr uint32_t kTbStatSlots = 16384;                             // >= the persistent waves of a solve launch (k_tb_stats; the host clamps the grid)
+constexpr uint32_t kTbSchedTiles = kBlock / 64;                      // tiles per workgroup of k_tb_sched: one per wave
+#ifndef MNAV_TB_SCHED_DEPTH
+#define MNAV_TB_SCHED_DEPTH 4
+#endif
+constexpr uint32_t kTbSchedDepth = MNAV_TB_SCHED_DEPTH;              // set blocks of a tile per turn of k_tb_sched
+__global__ __launch_bounds__(kBlock) void k_tb_sched(tb::Args A, int par)
 {
-  __shared__ uint32_t s_wave[kBlock / 64], s_base;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const uint32_t i0 = (blockIdx.x * kBlock + threadIdx.x) * kTbPairUnits;
-  u32x4 f[kTbPairUnits];
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t t = tb::rfl(blockIdx.x * kTbSchedTiles + (threadIdx.x >> 6));
+  if (t >= A.ntiles) return;
+  const uint32_t nblk = A.nblk, NP = A.NP;
+  MNAV_GLOBAL uint8_t* const g_flag = as_global(A.pflag) + (size_t)t * nblk;
+  auto flags = [&](uint32_t c) { const uint32_t i = c * 64u + lane; return i < nblk ? (uint32_t)g_flag[i] : 0u; };
+  // the set blocks of the tile in ascending order: chunk c of 64 flags in `m`, chunk c + 1 already fetched
+  const uint32_t f0 = flags(0u), f1 = flags(1u);
+  unsigned long long m = __ballot(f0 != 0u), m_next = __ballot(f1 != 0u);
   uint32_t c = 0;
-#pragma unroll
-  for (uint32_t u = 0; u < kTbPairUnits; ++u) {
-    f[u] = u32x4{ 0u, 0u, 0u, 0u };
-    if (i0 + u < A.n_flag16) f[u] = ((MNAV_GLOBAL const u32x4*)as_global(A.pflag))[i0 + u];
-    const uint32_t w[4] = { f[u].x, f[u].y, f[u].z, f[u].w };
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-#pragma unroll
-      for (int b = 0; b < 4; ++b) c += ((w[k] >> (8 * b)) & 0xFFu) ? 1u : 0u;
-  }
-  uint32_t incl = c;                                                 // inclusive scan over the wave, then over the workgroup's waves
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { const uint32_t x = __shfl_up(incl, o); if (lane >= o) incl += x; }
-  if (lane == 63) s_wave[wave] = incl;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t tot = 0;
-#pragma unroll
-    for (int w = 0; w < kBlock / 64; ++w) { const uint32_t x = s_wave[w]; s_wave[w] = tot; tot += x; }
-    s_base = tot ? atomicAdd(&A.ctl->n_pairs, tot) : 0u;
-  }
-  __syncthreads();
-  uint32_t base = s_base + s_wave[wave] + incl - c;
-  if (c) {
-#pragma unroll
-    for (uint32_t u = 0; u < kTbPairUnits; ++u) {
-      const uint32_t w[4] = { f[u].x, f[u].y, f[u].z, f[u].w };
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-#pragma unroll
-        for (int b = 0; b < 4; ++b)
-          if ((w[k] >> (8 * b)) & 0xFFu) A.pairs[base++] = 16u * (i0 + u) + 4u * k + b;
+  auto next_block = [&]() -> uint32_t {
+    while (m == 0ull) {
+      if ((c + 1u) * 64u >= nblk) return kNone;
+      ++c; m = m_next; m_next = __ballot(flags(c + 1u) != 0u);
     }
-  }
-}
-
-constexpr uint32_t kTbStatSlots = 16384;                             // >= the persistent waves of a solve launch (k_tb_stats)
-constexpr uint32_t kTbScanWaves = 8192;                              // persistent waves of k_tb_scan (a row of the list after the other)
-// One listed row per wave and turn.  A row is a chain of dependent round trips -- list entry -> the row of pending values and the
-// plans' thresholds -> the bucket's counter -> the bucket entries.  What a turn issues, in this order: (B) the current row is
-// classified (its loads were issued a turn ago) and lane 0 asks the bucket's counter for slots; (A) the NEXT row's loads go out --
-// pending values, thresholds, bounds, the plans' carried minima, and the list entry after that one --, every one of them
-// unconditional at a clamped address; (C) the bucket entries are stored once the counter has answered.  The memory counter counts
-// in order, so (C) waits for the atomic with the loads of (A) still in flight (s_waitcnt vmcnt(5) in the ISA), and (B) of the next
-// turn finds them arrived.  Measured: no faster than the unpipelined loop (102 us per launch at 7168 plans either way) -- the pass
-// is not waiting for memory, it is issuing: ~200 000 listed rows per iteration x 130 instructions, 8 waves per SIMD, for 6-16 %
-// of the lanes holding a value.  (A list of the VALUES instead of the rows was tried too)
-__global__ __launch_bounds__(kBlock) void k_tb_scan(tb::Args A, int par)
-{
-  const int lane = threadIdx.x & 63;
-  const uint32_t wave = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6), nwaves = gridDim.x * (kBlock / 64);
-  const uint32_t n_pairs = A.ctl->n_pairs;
-  if (wave >= n_pairs) return;
-  MNAV_GLOBAL const uint32_t* const pairs = as_global(A.pairs);
+    const uint32_t b = c * 64u + (uint32_t)__builtin_ctzll(m);
+    m &= m - 1ull;
+    return b;
+  };
+  const uint32_t b_first = next_block();
+  if (b_first == kNone) return;
   MNAV_GLOBAL const float* const g_thr = as_global(A.thr);
   MNAV_GLOBAL const float* const g_bnd = as_global(A.bnd);
-  MNAV_GLOBAL uint32_t* const g_pend = as_global(A.pend);
-  MNAV_GLOBAL uint32_t* const g_min = as_global(A.marr[par ^ 1]);
-  uint32_t carried = 0;
-  struct Row { uint32_t pr, t, p, pb, pm; float thr, bnd; bool live; };
-  auto fetch = [&](uint32_t pr, bool have) {                          // the loads of one row, all issued together and none of them under a branch
-    Row r; r.pr = pr;
-    const uint32_t t = tb::div_by_magic(pr, A.nblk, A.nblk_magic, A.nblk_shift), p = (pr - t * A.nblk) * 64u + (uint32_t)lane;
-    r.live = have && t < A.ntiles && p < A.NP;                         // (padding bytes of the flag matrix are never set)
-    r.t = r.live ? t : 0u; r.p = r.live ? p : 0u;
-    r.pb = g_pend[(size_t)r.t * A.NP + r.p]; r.thr = g_thr[r.p]; r.bnd = g_bnd[r.p]; r.pm = g_min[r.p];
+  MNAV_GLOBAL uint32_t* const g_pend = as_global(A.pend) + (size_t)t * NP;
+  MNAV_GLOBAL uint16_t* const g_bucket = as_global(A.bucket) + (size_t)t * NP;
+  MNAV_GLOBAL uint32_t* const g_min = as_global(A.mcarry) + (size_t)(t % kTbMinCopies) * NP;   // (k_tb_plan)
+  struct Row { uint32_t p, pb, pm; float thr, bnd; bool live; };
+  auto fetch = [&](uint32_t b) {                                      // the loads of one block, all issued together and none of them under a branch
+    Row r;
+    const uint32_t p = (b != kNone ? b : 0u) * 64u + lane;            // (no block: block 0's addresses, and nothing of it is used)
+    r.live = b != kNone && p < NP;
+    r.p = r.live ? p : 0u;
+    r.pb = g_pend[r.p]; r.thr = g_thr[r.p]; r.bnd = g_bnd[r.p]; r.pm = g_min[r.p];
     return r;
   };
-  uint32_t k = wave;
-  const uint32_t last = n_pairs - 1u;
-  uint32_t pr_next = pairs[min(k + nwaves, last)];
-  Row cur = fetch(pairs[k], true);
-  for (; k < n_pairs; k += nwaves) {
-    // ---- (B) the current row
-    asm volatile("" :: "v"(cur.pb), "v"(cur.thr), "v"(cur.bnd), "v"(cur.pm));   // (all four loads waited for HERE: a value only read under a
-                                                                       // branch stays "in flight" for the compiler on the other path, and it then
-                                                                       // makes room for the next loads by waiting for everything issued since)
-    const uint32_t t = cur.t, p = cur.p, pb = cur.pb;
-    MNAV_GLOBAL uint32_t* const pe = g_pend + ((size_t)t * A.NP + p);
-    bool ready = false, keep = false;
-    if (cur.live && pb != kTbInfBits) {
-      const float pv = u2f(pb);
-      if (pv > cur.bnd) *pe = kTbInfBits;
-      else if (pv < cur.thr) { *pe = kTbInfBits; ready = true; }
-      else {
-        keep = true; ++carried;
-        if (pb < cur.pm) atomicMin((uint32_t*)(g_min + p), pb);       // (cur.pm is a turn old: the minimum only falls, an older value only lets more through)
+  const unsigned long long below = (1ull << lane) - 1ull;
+  uint32_t count = 0;                                                 // the tile's bucket so far (wave-uniform)
+  bool carried = false;
+  constexpr int K = (int)kTbSchedDepth;
+  uint32_t b_cur[K];
+  Row cur[K];
+  b_cur[0] = b_first;
+#pragma unroll
+  for (int k = 1; k < K; ++k) b_cur[k] = next_block();
+#pragma unroll
+  for (int k = 0; k < K; ++k) cur[k] = fetch(b_cur[k]);
+  for (;;) {
+    // ---- the next group's loads
+    uint32_t b_next[K];
+    Row nxt[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) b_next[k] = next_block();
+#pragma unroll
+    for (int k = 0; k < K; ++k) nxt[k] = fetch(b_next[k]);
+    __builtin_amdgcn_sched_barrier(0);                                 // (the loads stay above the wait for the current group's)
+    // ---- the current group
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+      asm volatile("" :: "v"(cur[k].pb), "v"(cur[k].thr), "v"(cur[k].bnd), "v"(cur[k].pm));   // (all loads of the group waited for HERE: a value
+                                                                       // only read under a branch stays "in flight" for the compiler on the other path,
+                                                                       // and it then makes room for the next loads by waiting for everything issued since)
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      if (b_cur[k] == kNone) break;                                    // (uniform: the blocks of a group are in ascending order, the missing ones last)
+      const uint32_t p = cur[k].p, pb = cur[k].pb;
+      bool ready = false, keep = false;
+      if (cur[k].live && pb != kTbInfBits) {
+        const float pv = u2f(pb);
+        if (pv > cur[k].bnd) g_pend[p] = kTbInfBits;
+        else if (pv < cur[k].thr) { g_pend[p] = kTbInfBits; ready = true; }
+        else {
+          keep = true;
+          if (pb < cur[k].pm) atomicMin((uint32_t*)(g_min + p), pb);   // (pm is a turn old: the minimum only falls, an older value only lets more through)
+        }
       }
+      const bool any_keep = __any(keep);
+      carried |= any_keep;
+      if (!any_keep && lane == 0u) g_flag[b_cur[k]] = 0;
+      const unsigned long long rm = __ballot(ready);
+      if (ready) g_bucket[count + (uint32_t)__popcll(rm & below)] = (uint16_t)p;
+      count += (uint32_t)__popcll(rm);
     }
-    if (!__any(keep) && lane == 0) A.pflag[cur.pr] = 0;
-    const unsigned long long m = __ballot(ready);
-    uint32_t base = 0;
-    if (lane == 0) base = atomicAdd(&A.bcnt[t], (uint32_t)__popcll(m));   // (+0 when nothing is ready: the atomic is not worth a branch)
-    // ---- (A) the next row's loads, and the list entry after it
-    const bool have_next = k + nwaves < n_pairs;
-    const uint32_t pr_after = pairs[min(k + 2u * nwaves, last)];
-    const Row nxt = fetch(pr_next, have_next);
-    pr_next = pr_after;
-    __builtin_amdgcn_sched_barrier(0);                                 // (the scheduler would pull the read of `base`, and with it the wait, above the loads)
-    // ---- (C) the bucket entries
-    base = tb::rfl(base);
-    if (ready) A.bucket[(size_t)t * A.NP + base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = (uint16_t)p;
-    cur = nxt;
+    if (b_next[0] == kNone) break;
+#pragma unroll
+    for (int k = 0; k < K; ++k) { cur[k] = nxt[k]; b_cur[k] = b_next[k]; }
   }
-  carried = wave_sum(carried);
-  // "something is still pending" is all anybody asks of this word (the host's loop, the finalize pass): a plain store of 1, not
-  // a count -- 8192 waves adding to ONE address were 8192 atomics in a row at the L2 at the end of every launch
-  if (lane == 0 && carried) A.ctl->n_cand[par ^ 1] = 1u;
+  if (lane == 0u) {
+    if (count) A.bcnt[t] = count;                                     // (k_tb_items left it 0)
+    // "something is still pending" is all anybody asks of this word (the host's loop, the finalize pass): a plain store of 1
+    if (carried) A.ctl->n_cand[par ^ 1] = 1u;
+  }
 }
 
 constexpr uint32_t kTbItemPlans = 16;     // plans per work item = lanes per quarter of a wave (k_tb_solve_q)
@@ -286,7 +288,7 @@ __global__ __launch_bounds__(kBlock) void k_tb_items(tb::Args A)
   uint32_t incl = k;
 #pragma unroll
   for (int o = 1; o < 64; o <<= 1) { const uint32_t x = __shfl_up(incl, o); if (lane >= o) incl += x; }
-  __shared__ uint32_t s_wave[kBlock / 64], s_base;                    // (one atomic per workgroup: see k_tb_pairs)
+  __shared__ uint32_t s_wave[kBlock / 64], s_base;                    // (one atomic per workgroup of 256 tiles: the counter is one address)
   const int wave = threadIdx.x >> 6;
   if (lane == 63) s_wave[wave] = incl;
   __syncthreads();
@@ -742,7 +744,7 @@ __global__ __launch_bounds__(64) void k_tb_solve_q(tb::Args A, int par)
   if (lane == 0) for (int k = 0; k < 8; ++k) if (tt[k]) atomicAdd(&g_tb_timing[k], tt[k]);
 #endif
   my_wakes = wave_sum(my_wakes); my_acts = wave_sum(my_acts);
-  if (__any(my_first != 0u) && lane == 0) A.ctl->n_cand[par ^ 1] = 1u;   // "pairs are pending" (k_tb_scan)
+  if (__any(my_first != 0u) && lane == 0) A.ctl->n_cand[par ^ 1] = 1u;   // "pairs are pending" (k_tb_sched)
   if (lane == 0 && my_items && blockIdx.x < A.wstat_slots) {         // (its own slot, a plain read-modify-write: see k_tb_stats)
     unsigned long long* const ws = A.wstat + 4u * blockIdx.x;
     ws[0] += (unsigned long long)my_items; ws[1] += (unsigned long long)my_acts; ws[2] += (unsigned long long)my_sweeps; ws[3] += (unsigned long long)my_wakes;
@@ -903,7 +905,7 @@ struct TbTables {
 // ... and the batch state, sized for cap_np plans (tb_ensure_batch; dropped by tb_free_batch)
 struct TbBatch {
   uint32_t cap_np = 0;
-  DevBuf<float> D; DevBuf<uint32_t> pend; DevBuf<uint8_t> pflag; DevBuf<uint32_t> pairs; DevBuf<uint16_t> bucket; DevBuf<uint32_t> bcnt; DevBuf<uint2> items;
+  DevBuf<float> D; DevBuf<uint32_t> pend; DevBuf<uint32_t> mcarry; DevBuf<uint8_t> pflag; DevBuf<uint16_t> bucket; DevBuf<uint32_t> bcnt; DevBuf<uint2> items;
   DevBuf<tb::Ctl> ctl; PinnedBuf<tb::Ctl> h_ctl;
   DevBuf<unsigned long long> wstat; DevBuf<struct FinRec> d_recs;
   DevBuf<uint32_t> marr[2];
@@ -920,7 +922,7 @@ struct TbState : TbTables, TbBatch {
   uint32_t min_batch = 48;              // auto engine: batches of at least this many plans (and of tiles / 1000: mnav.hip dijkstra_impl)
   float band_mult = 2.0f;               // band = band_mult * mean edge weight * sqrt(T)  (measured on C2: 1 -> 236 ms, 2 -> 218 ms per 5120 plans)
   int iters_per_replay = 16, waves_per_cu = 0;
-  Stream fill_stream; Event fill_done;  // (the fill of D2)
+  Stream fill_stream; Event fill_done, call_done;  // (the fill of D2; call_done: behind the call's last kernel, what the fill waits for)
   Event warm_ev[4]; float ms_warm = 0.f, ms_warm_fin = 0.f;   // a warm start (run_dijkstra_tb with a TbWarmIn): k_tb_warm and the finalize pass of the last one
   tb::Ctl last{};                       // counters of the last batch
   bool count_pending = false;           // the settled-vertex count of the last (paths-only) batch has not been taken yet

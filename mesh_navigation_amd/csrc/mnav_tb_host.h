@@ -118,11 +118,10 @@ int tb_ensure_batch(mnav_ctx* ctx, uint32_t np)
   HIPCHK(S.D.alloc(4 * (size_t)S.S * np + 64));
   if (8 * (size_t)S.S * np <= ((size_t)96 << 30) && !opt_on(ctx->opt.tb_no_prefill)) {
     if (S.D2.alloc(4 * (size_t)S.S * np + 64) != hipSuccess) (void)hipGetLastError();   // (optional: the batch runs without it)
-    if (S.D2 && !S.fill_stream) { HIPCHK(hipStreamCreateWithFlags(S.fill_stream.out(), hipStreamNonBlocking)); HIPCHK(hipEventCreateWithFlags(S.fill_done.out(), hipEventDisableTiming)); }
+    if (S.D2 && !S.fill_stream) { HIPCHK(hipStreamCreateWithFlags(S.fill_stream.out(), hipStreamNonBlocking)); HIPCHK(hipEventCreateWithFlags(S.fill_done.out(), hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(S.call_done.out(), hipEventDisableTiming)); }
   }
   HIPCHK(S.pend.alloc(4 * pairs + 64));
   HIPCHK(S.pflag.alloc(nt * (((size_t)np + 63) / 64) + 64));
-  HIPCHK(S.pairs.alloc(4 * (nt * (((size_t)np + 63) / 64) + 64)));   // worst case: every (tile, block) flagged
   HIPCHK(S.bucket.alloc(2 * pairs + 64));
   HIPCHK(S.bcnt.alloc(4 * nt));
   HIPCHK(S.items.alloc(8 * (nt + pairs / kTbItemPlans + 64)));
@@ -130,6 +129,7 @@ int tb_ensure_batch(mnav_ctx* ctx, uint32_t np)
   HIPCHK(S.wstat.alloc(32 * (size_t)kTbStatSlots));
   HIPCHK(S.h_ctl.alloc(sizeof(tb::Ctl)));
   for (int k = 0; k < 2; ++k) HIPCHK(S.marr[k].alloc(4 * (size_t)np));
+  HIPCHK(S.mcarry.alloc(4 * (size_t)kTbMinCopies * np + 64));
   HIPCHK(S.thr.alloc(4 * (size_t)np)); HIPCHK(S.bnd.alloc(4 * (size_t)np));
   HIPCHK(S.seed.alloc(4 * (size_t)np)); HIPCHK(S.target.alloc(4 * (size_t)np));
   HIPCHK(S.d_recs.alloc(sizeof(FinRec) * (size_t)np));
@@ -153,8 +153,7 @@ int tb_launch_iterations(mnav_ctx* ctx, const tb::Args& A, int count, uint32_t w
   for (int j = 0; j < count; ++j) {
     const int par = j & 1;
     hipLaunchKernelGGL(k_tb_plan, dim3(gp), dim3(kBlock), 0, ctx->stream, A, par);
-    hipLaunchKernelGGL(k_tb_pairs, dim3((A.n_flag16 + kBlock * kTbPairUnits - 1) / (kBlock * kTbPairUnits)), dim3(kBlock), 0, ctx->stream, A);
-    hipLaunchKernelGGL(k_tb_scan, dim3(kTbScanWaves / (kBlock / 64)), dim3(kBlock), 0, ctx->stream, A, par);
+    hipLaunchKernelGGL(k_tb_sched, dim3(std::max((A.ntiles + kTbSchedTiles - 1) / kTbSchedTiles, 1u)), dim3(kBlock), 0, ctx->stream, A, par);
     hipLaunchKernelGGL(k_tb_items, dim3((A.ntiles + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, A);
     if (ctx->tb.kernel == 1) hipLaunchKernelGGL((k_tbv_solve<120>), dim3(waves), dim3(64), 0, ctx->stream, A, ctx->tb.d_vtile, ctx->tb.d_vstream, ctx->tb.d_vgroups, ctx->tb.d_vexps, par);
     else if (ctx->tb.T == 64) hipLaunchKernelGGL((k_tb_solve_q<64>), dim3(waves), dim3(64), 0, ctx->stream, A, par);
@@ -214,12 +213,14 @@ int tb_fields(mnav_ctx* ctx, uint32_t n, const std::vector<PlanIn>& in, double o
 }
 
 // Dijkstra batches through the tile-batch engine.  Returns 0, -1 (error) or 1 (cancelled).
-// The clean-up of the OTHER distance buffer for the next call, launched by the entry point when this call's last result has been
-// downloaded: on its own stream, with nothing of this call left on the device.  Round 6 measured where it must NOT run
-// (profiles/r06_fill_modes.txt, r06_fill_trace.txt): next to the call's own kernels.  Whatever kernel of the call's stream is in
-// flight when the fill starts does not finish before the fill does -- a 5 us memset took 6.9 ms next to a 7.5 ms fill -- and that
-// is the fill's DURATION, not its rate: 48 / 24 / 12 / 6 workgroups stretched the batch by 0 / 6 / 18 / 40 ms.  So it runs at
-// full width (44 GB in 7 ms at 7168 plans) in the gap the host leaves between two calls; a call that comes sooner waits for the
+// The clean-up of the OTHER distance buffer for the next call, launched by the entry point when the call's last download has been
+// enqueued: on its own stream, which first waits for an event recorded there, so that it starts with nothing of this call left on
+// the device.  Round 6 measured where it must NOT run (profiles/r06_fill_modes.txt, r06_fill_trace.txt): next to the call's own
+// kernels.  Whatever kernel of the call's stream is in flight when the fill starts does not finish before the fill does -- a 5 us
+// memset took 6.9 ms next to a 7.5 ms fill -- and that is the fill's DURATION, not its rate: 48 / 24 / 12 / 6 workgroups stretched
+// the batch by 0 / 6 / 18 / 40 ms.  The downloads are such kernels too (profiles/sched_pass_kernel_stats.md).  So it runs at full
+// width (44 GB in 7 ms at 7168 plans) under the host's copy-out of the paths and the gap the host leaves between two calls (until
+// this was moved it started after the copy-out and the call's last synchronize); a call that still comes sooner waits for the
 // event, which costs what cleaning at its start would.
 int tb_clean_other(mnav_ctx* ctx)
 {
@@ -229,6 +230,8 @@ int tb_clean_other(mnav_ctx* ctx)
   S.d2_wanted_np = 0u;
   const size_t n16 = (4 * (size_t)S.S * n + 15) / 16;
   const uint32_t g = (uint32_t)std::max<size_t>(std::min<size_t>((n16 + kBlock - 1) / kBlock, 256 * 32), 1);
+  HIPCHK(hipEventRecord(S.call_done, ctx->stream));
+  HIPCHK(hipStreamWaitEvent(S.fill_stream, S.call_done, 0));
   hipLaunchKernelGGL(k_tb_fill, dim3(g), dim3(kBlock), 0, S.fill_stream, (u32x4*)S.D2.get(), n16, kTbInfBits);
   HIPCHK(hipEventRecord(S.fill_done, S.fill_stream));
   S.d2_clean = true; S.d2_clean_np = n;
@@ -258,10 +261,7 @@ int run_dijkstra_tb(mnav_ctx* ctx, uint32_t n, const std::vector<PlanIn>& in, do
   tb::Args A{};
   A.tiles = S.d_tiles; A.stream = S.d_stream; A.exps = S.d_exps; A.D = S.D; A.pend = S.pend; A.pflag = S.pflag; A.nblk = (n + 63u) / 64u; A.NP = n; A.ntiles = S.ntiles;
   A.bucket = S.bucket; A.bcnt = S.bcnt; A.items = S.items; A.ctl = S.ctl; A.wstat = S.wstat; A.wstat_slots = kTbStatSlots;
-  A.pairs = S.pairs; A.n_flag16 = (uint32_t)(((size_t)S.ntiles * A.nblk + 15u) / 16u);
-  tb_div_magic(A.nblk, &A.nblk_magic, &A.nblk_shift);
-  if ((size_t)S.ntiles * A.nblk >= (1ull << 31)) { ctx->err = "tile-batch engine: flag matrix beyond 2^31 entries"; return -1; }
-  A.marr[0] = S.marr[0]; A.marr[1] = S.marr[1];
+  A.marr[0] = S.marr[0]; A.marr[1] = S.marr[1]; A.mcarry = S.mcarry;
   A.thr = S.thr; A.bnd = S.bnd; A.seed = S.seed; A.target = S.target; A.vaddr = S.d_vaddr; A.vert_tile = S.d_vert_tile;
   A.offset = offset;
   // Solve kernel and band.  k_tbv_solve (distances in registers, mnav_tbv.h) takes whole waves per tile.  A plan's front crosses
@@ -296,9 +296,10 @@ int run_dijkstra_tb(mnav_ctx* ctx, uint32_t n, const std::vector<PlanIn>& in, do
   }
   // (a warm start writes every word of its slices and pending words itself: it neither waits for a prepared clean buffer nor
   // uses it up -- the buffer stays clean for the next fresh batch)
-  HIPCHK(hipMemsetAsync(S.pflag, 0, (size_t)(S.ntiles ? S.ntiles : 1) * ((n + 63u) / 64u) + 64u, ctx->stream));   // (+ the padding k_tb_pairs reads as 16-byte units)
+  HIPCHK(hipMemsetAsync(S.pflag, 0, (size_t)(S.ntiles ? S.ntiles : 1) * ((n + 63u) / 64u) + 64u, ctx->stream));
   if (tb_fill(ctx, S.marr[0], 4 * (size_t)n, kTbInfBits)) return -1;
   if (tb_fill(ctx, S.marr[1], 4 * (size_t)n, kTbInfBits)) return -1;
+  if (tb_fill(ctx, S.mcarry, 4 * (size_t)kTbMinCopies * n, kTbInfBits)) return -1;
   HIPCHK(hipMemsetAsync(S.ctl, 0, sizeof(tb::Ctl), ctx->stream));
   HIPCHK(hipMemsetAsync(S.wstat, 0, 32 * (size_t)kTbStatSlots, ctx->stream));
   HIPCHK(hipMemsetAsync(S.bcnt, 0, 4 * (size_t)(S.ntiles ? S.ntiles : 1), ctx->stream));
@@ -317,8 +318,8 @@ int run_dijkstra_tb(mnav_ctx* ctx, uint32_t n, const std::vector<PlanIn>& in, do
   hipLaunchKernelGGL(k_tb_seed, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, A);
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(ctx->ev[2], ctx->stream));
-  // (the other buffer -- the previous call's distances, superseded the moment this call began -- is cleaned for the NEXT call at the
-  // end of this one: tb_clean_other)
+  // (the other buffer -- the previous call's distances, superseded the moment this call began -- is cleaned for the NEXT call behind
+  // the last kernel of this one: tb_clean_other)
   if (!warm || !S.d2_clean) S.d2_wanted_np = S.D2 ? n : 0u;
 
   int ncu = 256;
@@ -327,7 +328,7 @@ int run_dijkstra_tb(mnav_ctx* ctx, uint32_t n, const std::vector<PlanIn>& in, do
   if (S.kernel == 1) per_cu = 8u;                                      // k_tbv_solve: 256 VGPRs per wave, two waves per SIMD, no LDS
   if (opt_set(ctx->opt.tb_waves_per_cu)) S.waves_per_cu = (int)ctx->opt.tb_waves_per_cu;
   if (S.waves_per_cu > 0) per_cu = (uint32_t)S.waves_per_cu;
-  const uint32_t waves = per_cu * (uint32_t)ncu;
+  const uint32_t waves = std::min(per_cu * (uint32_t)ncu, kTbStatSlots);   // (a wave beyond the statistics' slots would go uncounted)
   const int chunk = S.iters_per_replay & ~1;
   // graph of `chunk` iterations, re-captured when the kernel arguments change
   int gi = 0;                                                         // graph slot: the one captured with these arguments, else the older one

@@ -103,7 +103,7 @@ __device__ __forceinline__ void run(const tb::Args& A, const TbWarm& W, const Tb
     if (my_wake != kInfBits) {
       A.pflag[(size_t)t * A.nblk + (p >> 6)] = 1;
       atomicMin(&A.marr[0][p], my_wake);
-      A.ctl->n_cand[0] = 1u;                                           // (a flag: see k_tb_scan)
+      A.ctl->n_cand[0] = 1u;                                           // (a flag: see k_tb_sched)
       atomicAdd(&W.cnt[p].woken, 1u);
     }
     if (my_kept) atomicAdd(&W.cnt[p].kept, (unsigned long long)my_kept);
@@ -118,7 +118,7 @@ __device__ __forceinline__ void run(const tb::Args& A, const TbWarm& W, const Tb
 // the seed at 0, a value strictly below the plan's level, +inf otherwise) applied to dist_p[verts[v0 + i]], slot T <= i < T + nh
 // the same for the ghost ghost_gid[goff + i - T], every other slot +inf.  Values at or above the level are dropped, so the
 // tentative values the finalize pass left beyond the old cut never enter.  The wake-up word is the smallest kept value among the
-// tile's owned and ghost slots when the tile owns a vertex that is not kept, +inf otherwise: too low a value is safe (k_tb_scan
+// tile's owned and ghost slots when the tile owns a vertex that is not kept, +inf otherwise: too low a value is safe (k_tb_sched
 // drops only what lies above the goal bound), a missing one would be a wrong field.  Counters per plan as ReplanCnt defines them:
 // owned vertices kept (seed included), owned vertices dropped from a finite value, (tile, plan) pairs woken.
 //

@@ -443,7 +443,7 @@ void k_tbv_solve(tb::Args A, const uint32_t* __restrict__ vtile, const uint32_t*
   if (lane == 0) for (int k = 0; k < 8; ++k) if (tt[k]) atomicAdd(&g_tb_timing[k], tt[k]);
 #endif
   my_wakes = wave_sum(my_wakes); my_acts = wave_sum(my_acts);
-  if (__any(my_first != 0u) && lane == 0) A.ctl->n_cand[par ^ 1] = 1u;   // "pairs are pending" (k_tb_scan)
+  if (__any(my_first != 0u) && lane == 0) A.ctl->n_cand[par ^ 1] = 1u;   // "pairs are pending" (k_tb_sched)
   if (lane == 0 && my_items && blockIdx.x < A.wstat_slots) {         // (its own slot, a plain read-modify-write: see k_tb_stats)
     unsigned long long* const ws = A.wstat + 4u * blockIdx.x;
     ws[0] += (unsigned long long)my_items; ws[1] += (unsigned long long)my_acts; ws[2] += (unsigned long long)my_sweeps; ws[3] += (unsigned long long)my_wakes;
