@@ -723,6 +723,65 @@ int mnav_fleet_walk_plans(mnav_ctx* ctx, uint32_t n, const uint32_t* slots, uint
 int mnav_fleet_stats(const mnav_ctx* ctx, uint32_t* served, uint32_t* beyond_field, uint32_t* no_path, uint32_t* invalid,
                      uint64_t* entries, uint32_t* built_index, uint32_t* chunks, float* ms_kernels, float* ms_total);
 
+/* -- fleet dispatch: which goal does each robot go to? ------------------------------------------------
+ * Every fleet call above takes slots[i], the goal of robot i, as an input.  With K goal fields resident and R robots the
+ * cost of robot r to reach goal k is one float, d_k[v_r]; the two calls below compute the R x K matrix of them on the
+ * device and an optimal one-to-one assignment from it, so that only R slot ids cross PCIe between planning the goals and
+ * mnav_fleet_plans.
+ *
+ * Robots: n of them, given as in mnav_fleet_paths (start_vertex, or start_pos resolved by the rule of mnav_locate with the
+ * ids staying on the device).  Columns: slots[0 .. m), DISTINCT plan indices of the recorded Dijkstra call or replan;
+ * slots == NULL stands for all its plans in order and m must then equal its plan count.
+ * code_out / potential_out: n * m entries, row-major [robot][column].  Entry (i, j) is the code (it fits a byte) and the
+ * potential_out that mnav_fleet_paths gives a robot on vertex v_i with slot slots[j], bit for bit, with ONE difference:
+ * rule 4 does not walk the chain, it returns MNAV_SUCCESS whenever pred[v] != v.  A chain that does not reach the seed is
+ * MNAV_INTERNAL_ERROR in mnav_fleet_paths; here that case is not detected (the pair is MNAV_SUCCESS with potential d[v]).
+ * Rule 5 under a finite cut takes the same lazy look at the marked plans as mnav_fleet_paths.
+ * A pair is FEASIBLE when its code is MNAV_SUCCESS and its potential is finite; that leaves out every pair of a plan whose
+ * seed is its target (rule 2's CAUTION).  nearest_slot_out[i]: the COLUMN INDEX j (not the slot id) of the smallest
+ * potential among the feasible pairs of row i, ties to the smallest column, MNAV_NONE for a row without a feasible pair;
+ * nearest_robot_out[j]: the same per column, ties to the smallest robot.  vertex_out: as in mnav_fleet_paths.
+ * Any output pointer may be NULL; with all of them NULL nothing of the matrix's size leaves the device.  n = 0 does nothing.
+ * Returns 0, or -1 with mnav_last_error set and NOTHING touched (no output, no statistic): every refusal of
+ * mnav_fleet_paths, m = 0, a slot out of range or given twice, slots == NULL with m different from the plan count, a
+ * matrix of more than the option dispatch_max_mb MiB on the device (5 bytes per pair; default 4096).  The call changes no
+ * plan output, no layer and no statistic of another entry point; with positions it builds the lookup index of
+ * mnav_locate when none exists yet. */
+int mnav_fleet_costs(mnav_ctx* ctx, uint32_t n, const uint32_t* start_vertex, const float* start_pos, uint32_t m,
+                     const uint32_t* slots, uint8_t* code_out, float* potential_out, uint32_t* vertex_out,
+                     uint32_t* nearest_slot_out, uint32_t* nearest_robot_out);
+/* The optimal assignment over the matrix of mnav_fleet_costs, which the call computes itself (same robots, columns and
+ * refusals; 9 bytes per pair against dispatch_max_mb): a matrix can never be stale.
+ * With q_ij = (int64) floor((double) potential_ij / quantum + 0.5) over the feasible pairs, an assignment maps robots to
+ * distinct columns over feasible pairs only; the result has MAXIMUM SIZE and, among those, MINIMUM sum of q.  Both numbers
+ * are unique; the assignment itself is the one the fixed algorithm below gives, the same in every call.
+ * slot_of_robot_out[i] (n): the plan slot id slots[j] of robot i's column -- what mnav_fleet_plans takes -- or MNAV_NONE
+ * for a robot without one; robot_of_slot_out[j] (m, per column): its robot or MNAV_NONE; potential_out[i] (n): the pair's
+ * float potential, +inf when unassigned; *assigned_out: the size; *total_q_out: the sum of q; *total_potential_out: the
+ * double sum of the assigned potentials in robot order.  Any output pointer may be NULL.
+ * Algorithm: pad to a square of N = max(n, m); cost q for a feasible pair, M = N q_max + 1 for an infeasible real pair, 0
+ * for a pair with a dummy row or column, all multiplied by N + 1; a synchronous (Jacobi) auction in int64 with eps-scaling:
+ * eps starts at max(1, C / 2) with C the largest scaled cost and is divided by 8 per phase down to 1, prices are kept
+ * across phases and every phase starts with nobody assigned.  In a round every unassigned bidder bids on its best column
+ * (smallest cost + price, ties to the smallest column) the column's price + (second-best value - best value) + eps, and
+ * every column takes its highest bid (ties to the smallest bidder) and evicts its owner.  A robot left on an M pair or on
+ * a dummy column is unassigned.  Rounds with at most dispatch_tail_bidders unassigned bidders (default 16) run inside one
+ * single-workgroup kernel, the others as wide launches; the result does not depend on that option.
+ * Returns 0, or -1 with mnav_last_error set and NOTHING written: every refusal of mnav_fleet_costs, a quantum that is not
+ * finite and positive, a q above 2^31 - 1, (N + 1) (N q_max + 1) >= 2^56 ("quantum too fine for this fleet"), a bid that
+ * reaches 2^62, or more than dispatch_max_rounds rounds (default 4194304): the call never hangs. */
+int mnav_fleet_assign(mnav_ctx* ctx, uint32_t n, const uint32_t* start_vertex, const float* start_pos, uint32_t m,
+                      const uint32_t* slots, double quantum, uint32_t* slot_of_robot_out, uint32_t* robot_of_slot_out,
+                      float* potential_out, uint32_t* assigned_out, int64_t* total_q_out, double* total_potential_out);
+/* The last mnav_fleet_costs or mnav_fleet_assign that returned 0: pairs[4] = pairs per outcome (MNAV_SUCCESS, beyond the
+ * field, without a path, every other code), the feasible pairs; of an assignment (0 after a costs call) its size, phases,
+ * rounds, the rounds the tail kernel took and the bids placed; built_index = 1 if the call built the lookup index; device
+ * milliseconds of the matrix pass and of the assignment (quantisation to result), host milliseconds of the whole call.
+ * Any pointer may be NULL. */
+int mnav_dispatch_stats(const mnav_ctx* ctx, uint64_t* pairs, uint64_t* feasible, uint32_t* assigned, uint32_t* phases,
+                        uint64_t* rounds, uint64_t* tail_rounds, uint64_t* bids, uint32_t* built_index, float* ms_costs,
+                        float* ms_assign, float* ms_total);
+
 /* -- one plan over several GPUs (BASELINE config 4) ---------------------------------------------
  * The reference's loop (dijkstra_mesh_planner.cpp:287-348) on a mesh that is range-partitioned over `world`
  * processes, one per GPU: the LDS tiles are in Morton order and process `rank` owns a contiguous range of them.

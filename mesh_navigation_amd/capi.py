@@ -40,6 +40,7 @@ SYMBOLS = [
     "mnav_replan_warm_stats",
     "mnav_fleet_paths", "mnav_fleet_walks", "mnav_fleet_stats",
     "mnav_upload_face_normals", "mnav_fleet_plans", "mnav_fleet_walk_plans",
+    "mnav_fleet_costs", "mnav_fleet_assign", "mnav_dispatch_stats",
     "mnav_set_option", "mnav_get_option", "mnav_shard_set_goal_tie", "mnav_last_engine",
 ]
 
@@ -325,6 +326,12 @@ def load(path: str | None = None):
     L.mnav_fleet_walk_plans.argtypes = [vp, u32, vp, u32, vp, vp, vp, vp, vp, f64, C.c_int32, u32] + [vp] * 6 + [C.c_uint64, vp]
     L.mnav_fleet_stats.restype = C.c_int
     L.mnav_fleet_stats.argtypes = [vp] + [C.POINTER(u32)] * 4 + [C.POINTER(C.c_uint64)] + [C.POINTER(u32)] * 2 + [C.POINTER(C.c_float)] * 2
+    L.mnav_fleet_costs.restype = C.c_int
+    L.mnav_fleet_costs.argtypes = [vp, u32, vp, vp, u32] + [vp] * 6
+    L.mnav_fleet_assign.restype = C.c_int
+    L.mnav_fleet_assign.argtypes = [vp, u32, vp, vp, u32, vp, f64] + [vp] * 6
+    L.mnav_dispatch_stats.restype = C.c_int
+    L.mnav_dispatch_stats.argtypes = [vp] + [vp] * 11
     if path is None:
         _lib = L
     return L
@@ -1165,6 +1172,53 @@ class MnavContext:
         rc = call(poses, cap)
         t = int(total.value)
         return dict(rc=rc, status=st, start_face=face0, path_len=lens, offsets=off, cost=cost, poses=poses[:t] if rc == 0 else None, total=t)
+
+    def _dispatch_args(self, who, start_vertex, start_pos, slots, m):
+        sv = None if start_vertex is None else _u32(start_vertex).reshape(-1)
+        sp = None if start_pos is None else _f32(start_pos).reshape(-1, 3)
+        if sv is None and sp is None:
+            raise RuntimeError(f"{who}: neither start vertices nor start positions")
+        n = int(sv.shape[0] if sv is not None else sp.shape[0])
+        sl = None if slots is None else _u32(slots).reshape(-1)
+        if sl is None and m is None:
+            raise ValueError(f"{who}: slots=None needs m, the plan count of the recorded call")
+        return n, sv, sp, int(sl.shape[0] if sl is not None else m), sl
+
+    def fleet_costs(self, start_vertex=None, start_pos=None, slots=None, m: int | None = None, want_matrix: bool = True) -> dict:
+        """The robot-to-goal matrix over the resident fields of the last Dijkstra call or replan (mnav_fleet_costs,
+        include/mnav.h): entry (i, j) is what fleet_paths gives robot i on plan slots[j] (slots None: all m plans in order),
+        without the walk of the chain.  Returns dict(codes (n x m uint8), potential (n x m), vertex, nearest_slot (column
+        index per robot), nearest_robot (per column)); want_matrix=False leaves the matrix on the device (codes and
+        potential are None)."""
+        n, sv, sp, m, sl = self._dispatch_args("fleet_costs", start_vertex, start_pos, slots, m)
+        codes = np.zeros((n, m), np.uint8) if want_matrix else None
+        pot = np.zeros((n, m), np.float32) if want_matrix else None
+        vtx, ns, nr = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(m, np.uint32)
+        if self._L.mnav_fleet_costs(self._h, n, _p(sv), _p(sp), m, _p(sl), _p(codes), _p(pot), _p(vtx), _p(ns), _p(nr)) != 0:
+            raise RuntimeError(f"mnav_fleet_costs failed: {self._err()}")
+        return dict(codes=codes, potential=pot, vertex=vtx, nearest_slot=ns, nearest_robot=nr)
+
+    def fleet_assign(self, start_vertex=None, start_pos=None, slots=None, m: int | None = None, quantum: float = 1e-3) -> dict:
+        """The optimal one-to-one assignment of robots to goals (mnav_fleet_assign, include/mnav.h): maximum size, then the
+        minimum sum of q = floor(potential / quantum + 0.5).  Returns dict(slot_of_robot (plan slot ids, NONE: unassigned),
+        robot_of_slot (per column), potential, assigned, total_q, total_potential)."""
+        n, sv, sp, m, sl = self._dispatch_args("fleet_assign", start_vertex, start_pos, slots, m)
+        sor, ros, pot = np.zeros(n, np.uint32), np.zeros(m, np.uint32), np.zeros(n, np.float32)
+        a, tq, tp = C.c_uint32(0), C.c_int64(0), C.c_double(0.0)
+        if self._L.mnav_fleet_assign(self._h, n, _p(sv), _p(sp), m, _p(sl), float(quantum), _p(sor), _p(ros), _p(pot), C.byref(a), C.byref(tq), C.byref(tp)) != 0:
+            raise RuntimeError(f"mnav_fleet_assign failed: {self._err()}")
+        return dict(slot_of_robot=sor, robot_of_slot=ros, potential=pot, assigned=a.value, total_q=tq.value, total_potential=tp.value)
+
+    def dispatch_stats(self) -> dict:
+        """The last fleet_costs / fleet_assign that succeeded (mnav_dispatch_stats)."""
+        pairs = (C.c_uint64 * 4)()
+        f, r, tr, b = (C.c_uint64(0) for _ in range(4))
+        a, ph, bi = (C.c_uint32(0) for _ in range(3))
+        mc, ma, mt = (C.c_float(0) for _ in range(3))
+        self._L.mnav_dispatch_stats(self._h, pairs, C.byref(f), C.byref(a), C.byref(ph), C.byref(r), C.byref(tr), C.byref(b), C.byref(bi), C.byref(mc), C.byref(ma),
+                                    C.byref(mt))
+        return dict(served=pairs[0], beyond_field=pairs[1], no_path=pairs[2], invalid=pairs[3], feasible=f.value, assigned=a.value, phases=ph.value,
+                    rounds=r.value, tail_rounds=tr.value, bids=b.value, built_index=bi.value, ms_costs=mc.value, ms_assign=ma.value, ms_total=mt.value)
 
     def fleet_stats(self) -> dict:
         """The last fleet_paths / fleet_walks / fleet_plans / fleet_walk_plans call (mnav_fleet_stats; entries: ids, walk entries or poses)."""

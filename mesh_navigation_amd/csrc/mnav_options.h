@@ -34,7 +34,10 @@
   X(replan_each_fresh_share) /* per-plan replan: plan the whole call afresh when more than this share of its plans is FRESH (default 0.004, measured; 1: never) */ \
   X(replan_repair_engine) /* replan: what finishes the repaired plans -- 0 the tile rounds, 5 the tile-batch engine started from the rewound fields (k_tb_warm); unset: by replan_warm_min_plans */ \
   X(replan_warm_min_plans) /* replan, replan_repair_engine unset: the tile-batch warm start from this many repaired plans on (default 299, measured: DESIGN.md section 3.14) */ \
-  X(fleet_scratch_mb)    /* fleet walks: MiB of scratch rows per chunk of robots (default 256; the result does not depend on it) */
+  X(fleet_scratch_mb)    /* fleet walks: MiB of scratch rows per chunk of robots (default 256; the result does not depend on it) */ \
+  X(dispatch_max_mb)     /* fleet dispatch: MiB of device matrix (5 bytes per pair, 9 for an assignment) a call may take (default 4096) */ \
+  X(dispatch_max_rounds) /* fleet assign: auction rounds after which the call gives up (default 4194304) */ \
+  X(dispatch_tail_bidders) /* fleet assign: rounds with at most this many unassigned bidders run in the single-workgroup tail kernel (default 16, measured, at most 8192; 0: never; the result does not depend on it) */
 
 struct Options {
 #define X(name) double name = NAN;
