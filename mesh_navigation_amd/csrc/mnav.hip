@@ -39,6 +39,7 @@
 #include "mnav_build.h"
 #include "mnav_eval.h"
 #include "mnav_options.h"
+#include "mnav_resident.h"
 
 using namespace mnav;
 
@@ -148,9 +149,10 @@ struct mnav_ctx {
   std::vector<uint32_t> h_row_ptr, h_nbr_u;   // gather CSR (host copy): the tile-batch engine builds its streams from it on first use
   TbState tb; tb::Args tb_args{};             // tile-batch SSSP engine (mnav_tb.h); arguments of the last batch
   bool tb_args_valid = false;                 // ... which still describe live device memory (last tile-batch call succeeded, nothing freed since)
-  bool want_vec = false;               // the running call asked for vector maps (lazy 12 B/vertex/plan)
+  bool want_vec = false;               // parameter of the RUNNING call: it asked for vector maps (lazy 12 B/vertex/plan).  What the outputs
+                                       // left behind hold is the record's to say (ctx->res)
   bool resident_vecmap = false;        // mnav_set_resident_outputs: always compute the vector map, leave it on the device
-  std::vector<uint32_t> caller_slot;   // plan index of the caller's batch -> device slot of the last call (kNone: never ran)
+  Resident res;                        // what the last plan call left on the device (mnav_resident.h): every reader of resident outputs asks it
   std::vector<uint32_t> h_faces;
   std::vector<uint32_t> h_vf_ptr, h_vf;    // getFacesOfVertex rows (host copy; uploaded on the first device back-tracking call)
   DevBuf<uint32_t> d_faces, d_vf_ptr, d_vf; bool walk_mesh_valid = false;
@@ -188,7 +190,8 @@ struct mnav_ctx {
   // tiled SSSP engine
   int dij_engine = 3;          // 0 tiled rounds, 1 band steps, 3 auto, 5 tile-batch, 6 asynchronous tiles (2: the per-plan persistent kernel, retired round 5)
   int last_engine = 0;
-  bool lazy_paths = false;      // this call only wants vertex paths: k_path_lazy instead of k_dij_finalize + k_finish
+  bool lazy_paths = false;      // parameter of the RUNNING call: it only wants vertex paths, k_path_lazy instead of k_dij_finalize + k_finish
+                                // (whether the outputs left behind are paths-only: ctx->res)
   bool allow_lazy_paths = true; // MNAV_LAZY_PATHS=0: always finalize (predecessors / tentative values for everybody)
   uint32_t max_steps = 1u << 20;   // per plan; set from the mesh size at upload (a wavefront needs O(diameter) steps)
   double max_wall_s = 120.0;   // host-side guard: a plan that takes longer is abandoned with an error
@@ -252,12 +255,7 @@ struct mnav_ctx {
     // change log: vertices whose cost, blocked status or incident edge weights may have changed since the last Dijkstra call.
     // Every writer knows its count on the host, so the length lives there; `all`: a writer replaced whole arrays, or the log ran over
     DevBuf<uint32_t> log; uint32_t len = 0; bool all = false;
-    // the last Dijkstra call, in the caller's order; which device slot each plan ran in; whether slots[k].dist holds a field to rewind
-    std::vector<uint32_t> seeds, targets, caller_slot; double cost_limit = 1.0, offset = 0.0; bool have_call = false, usable = false;
-    bool partial = false;            // the last Dijkstra call went through, but a plan of it never reached the device (rejected ids, seed == target)
-    bool finalized = false;          // the fields of the last call went through a finalize pass (not a paths-only call): what mnav_replan_dijkstra_each may keep
-    bool slot0_taken = false;        // an inflation wave has worked in slot 0 since
-    bool vec_resident = false;       // ... and left the vector maps of its plans resident
+    // (the recorded Dijkstra call itself, its slot map and what can be rewound: ctx->res)
     int each_engines = 0;            // mnav_last_engine after mnav_replan_dijkstra_each repaired per plan: 256 + (128: tile rounds ran) + (512: the REPAIRED plans ran warm on the
                                      // tile-batch engine, 1024: with k_tbv_solve) + (engine of the FRESH sub-batch, 127: none)
     // the warm repair on the tile-batch engine (k_tb_warm): its device arrays in sub-batch order and the statistics of the last
@@ -283,8 +281,6 @@ struct mnav_ctx {
       float ms_classify = 0.f, ms_rewind = 0.f, ms_rounds = 0.f, ms_finalize = 0.f, ms_fresh = 0.f;
     } each;
   } rp;
-  uint32_t last_planner = 0, last_n = 0;
-  std::vector<uint32_t> last_target; double last_offset = 0.0;   // Dijkstra: robot vertex per device slot, goal_dist_offset of the last call
   mnav_stats stats{};
   uint64_t algo_bytes = 0;
   Event ev[8];
@@ -598,7 +594,7 @@ int check_ready(mnav_ctx* ctx)
 uint32_t replan_log_room(mnav_ctx* ctx, uint32_t n)
 {
   mnav_ctx::Replan& R = ctx->rp;
-  if (!R.have_call || R.all || n == 0) return 0;
+  if (!ctx->res.has_recorded_call() || R.all || n == 0) return 0;
   const uint32_t cap = std::min(opt_u32(ctx->opt.replan_log_cap, ctx->V), ctx->V);
   if (n > cap || R.len > cap - n) { R.all = true; return 0; }        // overflow: the next replan plans afresh
   if (!R.log && R.log.alloc(sizeof(uint32_t) * (size_t)(ctx->V ? ctx->V : 1)) != hipSuccess) { R.all = true; return 0; }
@@ -620,6 +616,25 @@ void replan_log_edges(mnav_ctx* ctx, const uint32_t* d_edge_ids, uint32_t n)
   hipLaunchKernelGGL(k_replan_log_edges, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, n, d_edge_ids, ctx->d_edge_vtx, R.log + R.len);
   if (hipGetLastError() != hipSuccess) { R.all = true; return; }
   R.len += 2u * n;
+}
+
+// -- the record of the resident outputs (mnav_resident.h): the context's half of its transitions ------------------------
+// Outputs begin (ctx->res.outputs_begin / repair_begin / shard_took_slot0): whatever still names the previous call's device
+// memory is void -- the lazy settled-vertex count and the arguments of a tile-batch call, the predecessors of a sharded
+// plan -- and so is what mnav_last_engine said about a replan.
+void resident_outputs_begin(mnav_ctx* ctx)
+{
+  ctx->shard.finalized = false; ctx->tb.count_pending = false; ctx->tb_args_valid = false;
+  ctx->rp.each_engines = 0; ctx->rp.warm.live = false;
+}
+// A Dijkstra call or a repair committed (ctx->res.commit_dijkstra / repair_commit): the change log starts over.
+void resident_outputs_commit(mnav_ctx* ctx) { ctx->rp.len = 0; ctx->rp.all = false; }
+
+// A stale cancel flag does not cancel the call that starts (dijkstra :238, cvp :679).
+void cancel_reset(mnav_ctx* ctx)
+{
+  ctx->cancel.store(0);
+  if (ctx->d_cancel) { (void)hipStreamSynchronize(ctx->cancel_stream); (void)hipMemsetAsync(ctx->d_cancel, 0, 4, ctx->stream); }
 }
 
 // the face tables that the device back-tracking and the containing-face search walk: uploaded by whichever comes first
@@ -708,7 +723,7 @@ int mnav_upload_mesh(mnav_ctx* ctx, uint32_t V, uint32_t F, uint32_t E, const fl
   (void)hipStreamSynchronize(ctx->stream);
   // V-, E- and F-sized state of the old mesh
   ctx->slots.clear();
-  ctx->rp.log.reset(); ctx->rp.len = 0; ctx->rp.all = false; ctx->rp.have_call = ctx->rp.usable = ctx->rp.partial = false;   // (the log is V-sized; the recorded seeds are the old mesh's)
+  ctx->rp.log.reset(); ctx->rp.len = 0; ctx->rp.all = false; ctx->res.mesh_replaced();   // (the log is V-sized; the recorded seeds are the old mesh's)
   ctx->layers.clear();
   ctx->d_crn_infl.reset(); ctx->d_infl_mask.reset(); ctx->d_zero_u8.reset(); ctx->d_infl_keyd.reset(); ctx->crn_infl_valid = false;
   ctx->obs = {};                                                     // rebuilt lazily
@@ -1131,8 +1146,7 @@ static int layer_inflation_impl(mnav_ctx* ctx, uint32_t layer, uint32_t input_la
   if (!diff) HIPCHK(hipMemcpyAsync(L.lethal, In.lethal, V, hipMemcpyDeviceToDevice, ctx->stream));    // lethal_vertices_ = input->lethals() :170,:584
   if (ensure_slots(ctx, 1, true, true, false)) return -1;
   Slot& s = ctx->slots[0];
-  ctx->caller_slot.assign(1, kNone);                                // the wave works in plan slot 0: the last plan's resident outputs are gone
-  ctx->rp.slot0_taken = true;                                       // (its predecessors: a replan re-derives them, and keeps no plan in slot 0 as it is)
+  ctx->res.wave_took_slot0();                                       // the wave works in plan slot 0: the last plan's resident outputs are gone
   ctx->shard.finalized = false;
   Plan P;
   memset(&P, 0, sizeof(P));
@@ -1621,22 +1635,14 @@ static uint32_t dijkstra_impl(mnav_ctx* ctx, uint32_t n, const uint32_t* seeds, 
   // below dist[target] is final then -- and the passes that derive tentative values, predecessors and paths apply the
   // reference's expanded set through goal_cut() (mnav_eval.h).
   if (offset != offset) { ctx->err = "goal_dist_offset is NaN"; return MNAV_INTERNAL_ERROR; }
-  ctx->cancel.store(0);                                               // dijkstra :238
-  if (ctx->d_cancel) { (void)hipStreamSynchronize(ctx->cancel_stream); (void)hipMemsetAsync(ctx->d_cancel, 0, 4, ctx->stream); }
+  cancel_reset(ctx);
   want_vecmap = want_vecmap || ctx->resident_vecmap;
   ctx->want_vec = want_vecmap;
   if (hipSetDevice(ctx->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return MNAV_INTERNAL_ERROR; }
   MTRACE("start");
   const uint32_t V = ctx->V;
   uint32_t worst = MNAV_SUCCESS;
-  {
-    // what a replan needs of this call (the caller's arrays may be the record's own: mnav_replan_dijkstra_batch); its fields
-    // count once the call has gone through
-    mnav_ctx::Replan& R = ctx->rp;
-    const std::vector<uint32_t> s_(seeds, seeds + n), t_(targets, targets + n);
-    R.seeds = s_; R.targets = t_; R.cost_limit = cost_limit; R.offset = offset; R.have_call = true; R.usable = false; R.partial = false;
-    R.finalized = false; R.each_engines = 0; R.warm.live = false;
-  }
+  ctx->res.record_dijkstra(n, seeds, targets, cost_limit, offset);   // what a replan needs of this call; its fields count once it has gone through
   // id checks stand in for the optional-handle tests of dijkstra :240-243
   std::vector<PlanIn> in; std::vector<uint32_t> map;   // map: device plan -> caller index
   std::vector<uint32_t> codes(n, MNAV_SUCCESS);
@@ -1646,10 +1652,7 @@ static uint32_t dijkstra_impl(mnav_ctx* ctx, uint32_t n, const uint32_t* seeds, 
     if (seeds[i] >= V) { codes[i] = MNAV_INVALID_START; continue; }
     if (targets[i] >= V) { codes[i] = MNAV_INVALID_GOAL; continue; }
     if (seeds[i] == targets[i]) { cleared[i] = 1; continue; }   // :252-255 SUCCESS right after clearing the maps
-    PlanIn p{};
-    for (int k = 0; k < 3; ++k) { p.seed[k] = kNone; p.target[k] = kNone; p.seed_d[k] = 0.f; p.seed_expands[k] = 1; p.target_expands[k] = 1; }
-    p.seed[0] = seeds[i]; p.target[0] = targets[i]; p.seed_face = kNone;
-    in.push_back(p); map.push_back(i);
+    in.push_back(vertex_plan(seeds[i], targets[i])); map.push_back(i);
   }
   // Longest plans first: a plan's work grows with the area its wave sweeps before it reaches the robot
   // vertex, i.e. with the squared seed-target distance.  Workgroups are dispatched in plan order, so when a
@@ -1668,32 +1671,21 @@ static uint32_t dijkstra_impl(mnav_ctx* ctx, uint32_t n, const uint32_t* seeds, 
     if (engine == 1 && offset < 0.0) engine = 0;                      // the band steps arm goal_dist inside the loop: tile rounds for a negative offset
   }
   if (dijkstra_order(ctx, engine, in, map)) return MNAV_INTERNAL_ERROR;
-  ctx->caller_slot.assign(n, kNone);
-  ctx->shard.finalized = false;
-  for (size_t i = 0; i < map.size(); ++i) ctx->caller_slot[map[i]] = (uint32_t)i;
+  ctx->res.outputs_begin(Resident::kDijkstra, n, map);               // outputs of the previous call are gone; this call's once it has gone through:
+  resident_outputs_begin(ctx);                                        // every error return below leaves none
   (void)hipEventRecord(ctx->ev[0], ctx->stream);
   const uint32_t m = (uint32_t)in.size();
-  ctx->tb.count_pending = false; ctx->tb_args_valid = false;
-  ctx->last_planner = kPlannerDijkstra; ctx->last_n = 0;            // outputs of the previous call are gone; this call's count once its engine succeeded
-  ctx->last_target.resize(m); for (uint32_t k = 0; k < m; ++k) ctx->last_target[k] = in[k].target[0];
-  ctx->last_offset = offset;
   if (m) {
     if (materialize(ctx, false, cost_limit)) return MNAV_INTERNAL_ERROR;
     const int rc = dijkstra_dispatch(ctx, m, in, offset, engine_auto, &engine);
     if (rc < 0) return MNAV_INTERNAL_ERROR;
     if (rc == 1) { for (uint32_t i = 0; i < n; ++i) if (codes_out) codes_out[i] = MNAV_CANCELED; return MNAV_CANCELED; }   // :350-354
-    ctx->last_engine = engine; ctx->last_n = m;                       // only a call whose engine succeeded leaves outputs behind
+    ctx->last_engine = engine;
     if (engine == 1) ctx->lazy_paths = false;                         // the band steps keep their predecessors as they go
     if (dijkstra_tail(ctx, m, engine, map, codes, dist_out, pred_out, path_out, path_cap, path_len, vecmap_out, want_vecmap)) return MNAV_INTERNAL_ERROR;
-    // slots[k].dist is a field a replan can rewind: below the cut every value is final after the tile rounds and the
-    // asynchronous tiles (finalized or not) and after the tile-batch engine's finalize pass; the band steps keep other values
-    ctx->rp.usable = engine == 0 || engine == 6 || (engine == 5 && !ctx->lazy_paths);
-    ctx->rp.finalized = !ctx->lazy_paths;                             // (the per-plan replan keeps finalized fields only)
-    ctx->rp.vec_resident = want_vecmap;
   }
-  ctx->rp.slot0_taken = false; ctx->rp.each_engines = 0; ctx->rp.warm.live = false;
-  ctx->rp.caller_slot = ctx->caller_slot; ctx->rp.len = 0; ctx->rp.all = false;   // the change log starts over
-  ctx->rp.partial = m != n;
+  ctx->res.commit_dijkstra(engine, m, ctx->lazy_paths, want_vecmap);
+  resident_outputs_commit(ctx);
   // plans rejected before reaching the device: the reference has cleared its maps by then
   for (uint32_t i = 0; i < n; ++i) {
     if (codes[i] == MNAV_INVALID_START || codes[i] == MNAV_INVALID_GOAL || cleared[i]) {
@@ -1738,8 +1730,7 @@ static uint32_t cvp_impl(mnav_ctx* ctx, uint32_t n, const float* seed_pos, const
   ctx->err.clear();
   if (goal_dist_offset != goal_dist_offset) { ctx->err = "goal_dist_offset is NaN"; return MNAV_INTERNAL_ERROR; }   // any double otherwise: a negative one
                                                                                                                       // stops the wave at the arming pop (passes_goal_cut)
-  ctx->cancel.store(0);                                               // cvp :679
-  if (ctx->d_cancel) { (void)hipStreamSynchronize(ctx->cancel_stream); (void)hipMemsetAsync(ctx->d_cancel, 0, 4, ctx->stream); }
+  cancel_reset(ctx);
   if (hipSetDevice(ctx->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return MNAV_INTERNAL_ERROR; }
   const uint32_t V = ctx->V;
   if (!ctx->have_normals) { ctx->err = "vertex normals were not uploaded"; return MNAV_INTERNAL_ERROR; }
@@ -1770,13 +1761,10 @@ static uint32_t cvp_impl(mnav_ctx* ctx, uint32_t n, const float* seed_pos, const
     sp.insert(sp.end(), seed_pos + 3 * (size_t)i, seed_pos + 3 * (size_t)i + 3);
   }
   const uint32_t m = (uint32_t)in.size();
-  ctx->caller_slot.assign(n, kNone);
-  ctx->shard.finalized = false;
-  for (size_t i = 0; i < map.size(); ++i) ctx->caller_slot[map[i]] = (uint32_t)i;
+  ctx->res.outputs_begin(Resident::kCvp, n, map);                    // the slots' dist now holds CVP potentials: nothing a replan can rewind.
+  resident_outputs_begin(ctx);                                        // (As found: the recorded Dijkstra call survives -- a replan then plans it afresh, reason 1)
   (void)hipEventRecord(ctx->ev[0], ctx->stream);
-  ctx->tb.count_pending = false; ctx->tb_args_valid = false;         // (a lazy settled-vertex count of an earlier Dijkstra batch is void now)
-  ctx->last_planner = kPlannerCvp; ctx->last_n = 0; ctx->last_engine = 1; ctx->rp.warm.live = false;
-  ctx->rp.usable = ctx->rp.partial = false;                          // the slots' dist now holds CVP potentials
+  ctx->last_engine = 1;
   uint32_t worst = MNAV_SUCCESS;
   if (m) {
     if (materialize(ctx, true, cost_limit)) return MNAV_INTERNAL_ERROR;
@@ -1790,7 +1778,7 @@ static uint32_t cvp_impl(mnav_ctx* ctx, uint32_t n, const float* seed_pos, const
     if (rc != 0) (void)hipStreamSynchronize(ctx->stream);
     if (rc < 0) return MNAV_INTERNAL_ERROR;
     if (rc == 1) { if (codes_out) for (uint32_t i = 0; i < n; ++i) codes_out[i] = MNAV_CANCELED; return MNAV_CANCELED; }   // cvp :888-892
-    ctx->last_n = m;
+    ctx->res.commit_cvp(m);
     hipLaunchKernelGGL(k_finish<kPlannerCvp>, dim3(m), dim3(64), 0, ctx->stream, ctx->d_plans, ctx->d_res, PathRows{ nullptr, 0u, nullptr, nullptr });
     const uint32_t gc = (V + kBlock * 4 - 1) / (kBlock * 4);
     hipLaunchKernelGGL(k_count, dim3(gc ? gc : 1, m), dim3(kBlock), 0, ctx->stream, ctx->d_plans, ctx->d_res);
@@ -1880,8 +1868,8 @@ static void settle_stats(mnav_ctx* ctx)
   if (!ctx->tb.count_pending) return;
   ctx->tb.count_pending = false;
   // only the arguments of a tile-batch call that succeeded and whose buffers are still allocated may be dereferenced
-  if (!ctx->tb_args_valid || ctx->last_planner != kPlannerDijkstra || ctx->last_engine != 5 || !ctx->tb.built) return;
-  const uint32_t m = ctx->last_n;
+  if (!ctx->tb_args_valid || !ctx->res.dijkstra_family() || ctx->last_engine != 5 || !ctx->tb.built) return;
+  const uint32_t m = ctx->res.live();
   if (!m || hipSetDevice(ctx->device) != hipSuccess) return;
   hipLaunchKernelGGL(k_tb_count, dim3(ctx->tb.ntiles ? ctx->tb.ntiles : 1, 16), dim3(kBlock), 0, ctx->stream, ctx->tb_args, ctx->tb.T, ctx->d_res);
   if (hipMemcpyAsync(ctx->h_res, ctx->d_res, sizeof(PlanResult) * m, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
@@ -1945,20 +1933,16 @@ double mnav_get_option(const mnav_ctx* ctx, const char* name)
 const void* mnav_device_output(const mnav_ctx* ctx, uint32_t slot, int what)
 {
   if (!ctx) return nullptr;
-  if (slot >= ctx->caller_slot.size()) return nullptr;                    // not a plan of the last call (a stale slot of an earlier, larger batch is never handed out)
-  slot = ctx->caller_slot[slot];                                          // caller's plan index -> device slot (kNone: never reached the device)
-  if (slot >= ctx->last_n || slot >= ctx->slots.size()) return nullptr;   // last_n == 0: the last call failed or was cancelled
-  const Slot& s = ctx->slots[slot];
-  // a paths-only Dijkstra call finalized nothing: values beyond goal_dist are engine-tentative, predecessors were derived
-  // along the path only (mnav_download_output what = 5 returns the popped potential of such a call)
-  const bool lazy = ctx->lazy_paths && ctx->last_planner == kPlannerDijkstra;
+  // the record decides (a stale slot of an earlier, larger batch, the dist of a paths-only call -- mnav_download_output what = 5
+  // returns its popped potential --, an earlier call's vector map are never handed out); the slots may be gone with the mesh
+  if (!ctx->res.available(slot, what) || ctx->res.slot(slot) >= ctx->slots.size()) return nullptr;
+  const Slot& s = ctx->slots[ctx->res.slot(slot)];
   switch (what) {
-    case 0: return lazy ? nullptr : s.dist;
-    case 1: return lazy ? nullptr : s.pred;
+    case 0: return s.dist;
+    case 1: return s.pred;
     case 2: return s.dirn;
     case 3: return s.cutf;
-    case 4: return (ctx->last_planner == kPlannerDijkstra && !ctx->want_vec) ? nullptr : s.vecmap;   // (a Dijkstra call that was not asked for vector maps
-                                                                                                       //  must not hand out an earlier call's)
+    case 4: return s.vecmap;
     default: return nullptr;
   }
 }
@@ -1974,16 +1958,17 @@ int mnav_download_output(mnav_ctx* ctx, uint32_t slot, int what, void* host_out)
 {
   if (!ctx || !host_out) return -1;
   if (what == 5) {                                                   // popped potential (Dijkstra): exact wherever dist <= goal_dist, +inf elsewhere
-    if (ctx->last_planner != kPlannerDijkstra) { ctx->err = "popped potential: the last call was not a Dijkstra plan"; return -1; }
-    if (slot < ctx->caller_slot.size()) slot = ctx->caller_slot[slot];
-    if (slot >= ctx->last_n) { ctx->err = "output not resident"; return -1; }
+    if (!ctx->res.dijkstra_family()) { ctx->err = "popped potential: the last call was not a Dijkstra plan"; return -1; }
+    slot = ctx->res.slot_or_raw(slot);
+    if (slot >= ctx->res.live()) { ctx->err = "output not resident"; return -1; }
     if (hipSetDevice(ctx->device) != hipSuccess) return -1;
     DevBuf<float> tmp;
     HIPCHK(tmp.alloc(4 * (size_t)(ctx->V ? ctx->V : 1)));
     const uint32_t g = std::min<uint32_t>((ctx->V + kBlock - 1) / kBlock + 1, 4096);
-    if (ctx->last_engine == 5 && ctx->lazy_paths && !ctx->tb_args_valid) { ctx->err = "output not resident"; return -1; }
-    if (ctx->last_engine == 5 && ctx->lazy_paths) hipLaunchKernelGGL(k_tb_popped, dim3(g), dim3(kBlock), 0, ctx->stream, ctx->tb_args, slot, ctx->V, tmp);
-    else hipLaunchKernelGGL(k_popped, dim3(g), dim3(kBlock), 0, ctx->stream, ctx->slots[slot].dist, ctx->last_target[slot], ctx->last_offset, ctx->V, tmp);
+    const bool tb_paths_only = ctx->last_engine == 5 && ctx->res.paths_only();
+    if (tb_paths_only && !ctx->tb_args_valid) { ctx->err = "output not resident"; return -1; }
+    if (tb_paths_only) hipLaunchKernelGGL(k_tb_popped, dim3(g), dim3(kBlock), 0, ctx->stream, ctx->tb_args, slot, ctx->V, tmp);
+    else hipLaunchKernelGGL(k_popped, dim3(g), dim3(kBlock), 0, ctx->stream, ctx->slots[slot].dist, ctx->res.robot_vertex(slot), ctx->res.offset(), ctx->V, tmp);
     const hipError_t e1 = hipMemcpyAsync(host_out, tmp, 4 * (size_t)ctx->V, hipMemcpyDeviceToHost, ctx->stream);
     const hipError_t e2 = hipStreamSynchronize(ctx->stream);
     tmp.reset();
@@ -2007,11 +1992,10 @@ int mnav_vector_at(mnav_ctx* ctx, uint32_t slot, const uint32_t vs[3], const flo
   if (!ctx || !vs || !bary || !out) return -1;
   for (int k = 0; k < 3; ++k) if (vs[k] >= ctx->V) { ctx->err = "vertex id out of range"; return -1; }
   float v[3][3];
-  if (ctx->last_planner == kPlannerDijkstra && ctx->last_engine == 5 && ctx->lazy_paths && ctx->tb_args_valid) {
+  if (ctx->last_engine == 5 && ctx->res.paths_only() && ctx->tb_args_valid) {
     // paths-only batch of the tile-batch engine: no vector map was written -- the three entries are derived from the blocked distances
-    uint32_t p = slot;
-    if (p < ctx->caller_slot.size()) p = ctx->caller_slot[p];
-    if (p >= ctx->last_n) { ctx->err = "output not resident"; return -1; }
+    const uint32_t p = ctx->res.slot_or_raw(slot);
+    if (p >= ctx->res.live()) { ctx->err = "output not resident"; return -1; }
     if (hipSetDevice(ctx->device) != hipSuccess) return -1;
     if (!ctx->d_vec3) HIPCHK(ctx->d_vec3.alloc(64));
     hipLaunchKernelGGL(k_tb_vector3, dim3(3), dim3(kWave), 0, ctx->stream, ctx->tb_args, ctx->d_row_ptr, ctx->d_nbr, ctx->d_xyz, p,
@@ -2052,14 +2036,14 @@ int mnav_backtrack_cvp_batch(mnav_ctx* ctx, uint32_t n, const float* seed_pos, c
   if (!seed_pos || !seed_faces || !target_pos || !target_faces || !positions_out || !faces_out || !n_out || !status_out) { ctx->err = "null argument"; return -1; }
   if (cap < 2 || (uint64_t)cap * n > (1ull << 28)) { ctx->err = "path capacity out of range"; return -1; }
   if (!(step_width > 0.0)) { ctx->err = "step_width must be positive"; return -1; }   // a zero step never leaves the start
-  if (ctx->last_planner != kPlannerCvp) { ctx->err = "back-tracking: the last call was not a CVP plan"; return -1; }
+  if (ctx->res.kind() != Resident::kCvp) { ctx->err = "back-tracking: the last call was not a CVP plan"; return -1; }
   if (hipSetDevice(ctx->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return -1; }
-  if (n != ctx->caller_slot.size()) { ctx->err = "back-tracking: n differs from the last mnav_plan_cvp(_batch) call"; return -1; }
+  if (n != ctx->res.plans()) { ctx->err = "back-tracking: n differs from the last mnav_plan_cvp(_batch) call"; return -1; }
   std::vector<WalkJob> jobs(n);
   for (uint32_t i = 0; i < n; ++i) {
     const float* vm = static_cast<const float*>(mnav_device_output(ctx, i, 4));
     jobs[i].vecmap = nullptr;
-    if (ctx->caller_slot[i] == kNone) continue;                       // a plan rejected before it reached the device (INVALID_START / _GOAL): status 0, no entries
+    if (ctx->res.slot(i) == kNone) continue;                       // a plan rejected before it reached the device (INVALID_START / _GOAL): status 0, no entries
     if (!vm) { ctx->err = "vector map not resident (mnav_set_resident_outputs, or pass vecmap_out to the plan call)"; return -1; }
     if (seed_faces[i] >= ctx->F || target_faces[i] >= ctx->F) { ctx->err = "face id out of range"; return -1; }
     jobs[i].vecmap = vm; jobs[i].seed_face = seed_faces[i]; jobs[i].target_face = target_faces[i];
@@ -2131,7 +2115,7 @@ uint64_t mnav_algorithmic_bytes(const mnav_ctx* ctx)
 
 int mnav_last_engine(const mnav_ctx* ctx)
 {
-  if (!ctx || ctx->last_planner != kPlannerDijkstra || ctx->last_n == 0) return -1;
+  if (!ctx || !ctx->res.dijkstra_family() || ctx->res.live() == 0) return -1;
   if (ctx->rp.each_engines) return ctx->rp.each_engines;
   return ctx->last_engine + ((ctx->last_engine == 5 && ctx->tb.kernel == 1) ? 16 : 0);
 }

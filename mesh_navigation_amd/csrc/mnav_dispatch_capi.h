@@ -23,7 +23,7 @@ static int dispatch_check(mnav_ctx* ctx, const std::string& who, uint32_t n, con
   if (check_ready(ctx)) return -1;
   std::vector<mnav_fleet::Field> fields;
   if (fleet_fields_of(ctx, who, 0, nullptr, fields)) return -1;             // (the recorded call itself, before anything is said about its slots)
-  const size_t n_plans = ctx->rp.seeds.size();
+  const size_t n_plans = ctx->res.seeds().size();
   if (!slots && m != n_plans) { ctx->err = who + ": slots == NULL needs m = the plan count of the recorded call"; return -1; }
   D.col_slot.resize(m);
   for (uint32_t j = 0; j < m; ++j) D.col_slot[j] = slots ? slots[j] : j;
@@ -92,7 +92,7 @@ static int dispatch_costs_run(mnav_ctx* ctx, uint32_t n, const uint32_t* start_v
   P.need = S.need; P.cnt = S.cnt;
   HIPCHK(hipEventRecord(S.ev[0], ctx->stream));
   hipLaunchKernelGGL(mnav_fleet::k_fleet_cut, dim3((m + mnav_fleet::kFleetBlock - 1) / mnav_fleet::kFleetBlock), dim3(mnav_fleet::kFleetBlock), 0, ctx->stream, m, S.cols.get(),
-                     ctx->rp.offset);
+                     ctx->res.offset());
   hipLaunchKernelGGL(k_dispatch_costs, dim3((uint32_t)(RT * CT)), dim3(kDispBlock), 0, ctx->stream, P);
   if (nearest) hipLaunchKernelGGL(k_dispatch_nearest, dim3((n + m + kDispBlock - 1) / kDispBlock), dim3(kDispBlock), 0, ctx->stream, n, m, S.rowpart.get(), S.colpart.get(), S.nearest.get(), S.nearest + n);
   HIPCHK(hipGetLastError());

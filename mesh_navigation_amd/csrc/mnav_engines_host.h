@@ -11,6 +11,15 @@ struct PlanIn {
   uint32_t seed_expands[3], target_expands[3];
 };
 
+// a Dijkstra plan from one vertex to another
+inline PlanIn vertex_plan(uint32_t seed, uint32_t target)
+{
+  PlanIn p{};
+  for (int k = 0; k < 3; ++k) { p.seed[k] = kNone; p.target[k] = kNone; p.seed_d[k] = 0.f; p.seed_expands[k] = 1; p.target_expands[k] = 1; }
+  p.seed[0] = seed; p.target[0] = target; p.seed_face = kNone;
+  return p;
+}
+
 // Runs n plans of one planner to completion on the device.  Returns 0, -1 (error) or 1 (cancelled).
 template <uint32_t PLANNER>
 int run_plans(mnav_ctx* ctx, uint32_t n, const std::vector<PlanIn>& in, double offset, bool want_path)

@@ -61,12 +61,12 @@ static int fleet_fields_of(mnav_ctx* ctx, const std::string& who, uint32_t n, co
   using namespace mnav_fleet;
   if (check_ready(ctx)) return -1;
   if (n > 0x7FFFFFFFu) { ctx->err = who + ": too many robots in one call"; return -1; }
-  const mnav_ctx::Replan& R = ctx->rp;
-  const size_t n_slots = R.seeds.size();
-  if (!R.have_call || ctx->last_planner != kPlannerDijkstra || ctx->caller_slot != R.caller_slot || R.caller_slot.size() != n_slots || R.targets.size() != n_slots) {
+  const Resident& R = ctx->res;
+  const size_t n_slots = R.seeds().size();
+  if (!R.fields_resident()) {
     ctx->err = who + ": the last plan call was not a Dijkstra call or replan whose fields are resident"; return -1;
   }
-  if (R.len || R.all) { ctx->err = who + ": the costs changed since the plan (mnav_replan_dijkstra_batch first)"; return -1; }
+  if (ctx->rp.len || ctx->rp.all) { ctx->err = who + ": the costs changed since the plan (mnav_replan_dijkstra_batch first)"; return -1; }
   std::vector<uint8_t> used(n_slots ? n_slots : 1, 0);
   for (uint32_t i = 0; i < n; ++i) {
     if (slots[i] >= n_slots) { ctx->err = who + ": slot out of range (not a plan of the last call)"; return -1; }
@@ -74,14 +74,14 @@ static int fleet_fields_of(mnav_ctx* ctx, const std::string& who, uint32_t n, co
   }
   fields.resize(n_slots);
   for (size_t s = 0; s < n_slots; ++s) {
-    Field Fd; Fd.dist = nullptr; Fd.pred = nullptr; Fd.seed = R.seeds[s]; Fd.target = R.targets[s]; Fd.cut = INFINITY;
-    Fd.code = R.seeds[s] >= ctx->V ? MNAV_INVALID_START : R.targets[s] >= ctx->V ? MNAV_INVALID_GOAL : MNAV_SUCCESS;   // what the plan call gave a plan it did not run
-    if (used[s] && R.caller_slot[s] != kNone) {
-      // R.usable is the replan's record of "slots[k].dist is the reference's below the cut" (not after the band steps, a failed or cancelled
-      // call, a half-rewound replan); on top of it the predecessors must be resident, which a paths-only call does not leave
+    Field Fd; Fd.dist = nullptr; Fd.pred = nullptr; Fd.seed = R.seeds()[s]; Fd.target = R.targets()[s]; Fd.cut = INFINITY;
+    Fd.code = R.seeds()[s] >= ctx->V ? MNAV_INVALID_START : R.targets()[s] >= ctx->V ? MNAV_INVALID_GOAL : MNAV_SUCCESS;   // what the plan call gave a plan it did not run
+    if (used[s] && R.recorded_slot((uint32_t)s) != kNone) {
+      // rewindable: "slots[k].dist is the reference's below the cut" (not after the band steps, a failed or cancelled call, a
+      // half-rewound replan); on top of it the predecessors must be resident, which a paths-only call does not leave
       Fd.dist = static_cast<const float*>(mnav_device_output(ctx, (uint32_t)s, 0));
       Fd.pred = static_cast<const uint32_t*>(mnav_device_output(ctx, (uint32_t)s, 1));
-      if (!R.usable || !Fd.dist || !Fd.pred) {
+      if (!R.rewindable() || !Fd.dist || !Fd.pred) {
         ctx->err = who + ": predecessors of slot " + std::to_string(s) + " not resident (a paths-only, band-step, failed or cancelled call)"; return -1;
       }
     }
@@ -113,7 +113,7 @@ static int fleet_classify_robots(mnav_ctx* ctx, uint32_t n, const uint32_t* slot
   P.mark = S.status; P.need = S.need;
   const uint32_t nb = (n + kFleetBlock - 1) / kFleetBlock;
   HIPCHK(hipEventRecord(S.ev[0], ctx->stream));
-  hipLaunchKernelGGL(k_fleet_cut, dim3(((uint32_t)n_slots + kFleetBlock - 1) / kFleetBlock), dim3(kFleetBlock), 0, ctx->stream, (uint32_t)n_slots, S.fields.get(), ctx->rp.offset);
+  hipLaunchKernelGGL(k_fleet_cut, dim3(((uint32_t)n_slots + kFleetBlock - 1) / kFleetBlock), dim3(kFleetBlock), 0, ctx->stream, (uint32_t)n_slots, S.fields.get(), ctx->res.offset());
   hipLaunchKernelGGL(k_fleet_len, dim3(nb), dim3(kFleetBlock), 0, ctx->stream, P);
   return 0;
 }
@@ -242,7 +242,7 @@ static int fleet_walks_run(mnav_ctx* ctx, bool plans, uint32_t n, const uint32_t
   if (n > 0x7FFFFFFFu) { ctx->err = "fleet walks: too many robots in one call"; return -1; }
   if (walk_cap < 2 || walk_cap > (1u << 24)) { ctx->err = "fleet walks: walk_cap out of range (2 .. 2^24)"; return -1; }
   if (!(step_width > 0.0)) { ctx->err = "step_width must be positive"; return -1; }   // a zero step never leaves the start
-  if (n_plans != ctx->caller_slot.size()) { ctx->err = "fleet walks: n_plans differs from the last plan call"; return -1; }
+  if (n_plans != ctx->res.plans()) { ctx->err = "fleet walks: n_plans differs from the last plan call"; return -1; }
   std::vector<uint8_t> used(n_plans ? n_plans : 1, 0);
   for (uint32_t i = 0; i < n; ++i) {
     if (slots[i] >= n_plans) { ctx->err = "fleet walks: slot out of range (not a plan of the last call)"; return -1; }
@@ -253,7 +253,7 @@ static int fleet_walks_run(mnav_ctx* ctx, bool plans, uint32_t n, const uint32_t
   for (uint32_t s = 0; s < n_plans; ++s) {
     WalkSlot W{};
     W.vecmap = nullptr; W.seed_face = kNone;
-    if (used[s] && ctx->caller_slot[s] != kNone) {                    // (a plan rejected before it reached the device: status 0, no entries)
+    if (used[s] && ctx->res.slot(s) != kNone) {                    // (a plan rejected before it reached the device: status 0, no entries)
       W.vecmap = static_cast<const float*>(mnav_device_output(ctx, s, 4));
       if (!W.vecmap) { ctx->err = "fleet walks: vector map of slot " + std::to_string(s) + " not resident (mnav_set_resident_outputs, or pass vecmap_out to the plan call)"; return -1; }
       if (seed_faces[s] >= ctx->F) { ctx->err = "fleet walks: seed face id out of range"; return -1; }

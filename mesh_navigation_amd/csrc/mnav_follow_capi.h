@@ -17,7 +17,7 @@ static int follow_check(mnav_ctx* ctx, uint32_t n, const float* pos, const float
   if (n > 0x7FFFFFFFu) { ctx->err = "follow: too many robots in one call"; return -1; }
   if (!(config->max_search_radius > 0.0) || !std::isfinite(config->max_search_radius)) { ctx->err = "follow: max_search_radius must be positive and finite"; return -1; }
   if (!(config->max_search_distance > 0.0) || !std::isfinite(config->max_search_distance)) { ctx->err = "follow: max_search_distance must be positive and finite"; return -1; }
-  const size_t n_slots = ctx->caller_slot.size();
+  const size_t n_slots = ctx->res.plans();
   maps.assign(n_slots ? n_slots : 1, nullptr);
   std::vector<uint8_t> used(n_slots ? n_slots : 1, 0);
   for (uint32_t i = 0; i < n; ++i) {
@@ -67,7 +67,7 @@ static int staging_upload(mnav_ctx* ctx, uint32_t n, const float* pos, const flo
   HIPCHK(hipMemcpyAsync(G.face, face_in, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipMemcpyAsync(G.slot, slots, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
   if (seed_faces) HIPCHK(hipMemcpyAsync(G.seed_face, seed_faces, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(G.vecmaps, maps.data(), sizeof(const float*) * ctx->caller_slot.size(), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(G.vecmaps, maps.data(), sizeof(const float*) * ctx->res.plans(), hipMemcpyHostToDevice, ctx->stream));
   R.n = n; R.slot = G.slot; R.seed_face = seed_faces ? G.seed_face.get() : nullptr; R.vecmaps = G.vecmaps; R.costs = ctx->d_cost;
   R.nb_list = G.nb_list; R.gl_list = G.gl_list;
   return 0;
@@ -100,7 +100,7 @@ int mnav_follow_batch(mnav_ctx* ctx, uint32_t n, const float* pos, const float* 
   if (follow_check(ctx, n, pos, dir, up, face_in, slots, seed_faces, config, maps)) return -1;
   if (hipSetDevice(ctx->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return -1; }
   if (upload_walk_mesh(ctx)) return -1;
-  if (staging_reserve(ctx, n, ctx->caller_slot.size(), "follow") || follow_reserve(ctx, n)) return -1;
+  if (staging_reserve(ctx, n, ctx->res.plans(), "follow") || follow_reserve(ctx, n)) return -1;
   State& S = ctx->fol;
   Staging& G = ctx->stage;
   S.stayed = S.neighbour = S.global = S.lost = S.no_field = S.built_index = 0; S.ms_kernels = S.ms_total = 0.f;

@@ -118,6 +118,71 @@ static int replan_warm_run(mnav_ctx* ctx, uint32_t m, const std::vector<PlanIn>&
   return 0;
 }
 
+static int replan_each_reserve(mnav_ctx* ctx, uint32_t m);            // (mnav_replan_each_capi.h)
+
+// What both repairs of the m = n recorded fields start with.  in: the plans towards the new robot vertices in their recorded
+// slots; map: device plan -> caller's index.  The other vectors are sources of copies in flight: the whole struct lives
+// until the repair's first synchronisation.
+struct RepairHead {
+  std::vector<PlanIn> in; std::vector<uint32_t> map, old_target;
+  std::vector<Plan> hp; std::vector<TilePlan> tp; std::vector<float*> vecs;
+};
+
+// The head of a repair: the parameters of the running call, every reservation, the tile records, the old targets on the
+// device and, behind the event ev_begin, the rewind levels (k_replan_begin, for the per-plan repair k_replan_open,
+// k_replan_level over the change log).  ev_begin may be created by the reservations.  The fields are as they were when it returns.
+static int replan_repair_head(mnav_ctx* ctx, uint32_t m, const std::vector<uint32_t>& tg, double offset, bool each, const Event& ev_begin, RepairHead& H)
+{
+  mnav_ctx::Replan& R = ctx->rp;
+  const Resident& L = ctx->res;
+  H.in.resize(m); H.map.resize(m); H.old_target.resize(m);
+  for (uint32_t i = 0; i < m; ++i) {
+    const uint32_t k = L.recorded_slot(i);
+    H.in[k] = vertex_plan(L.seeds()[i], tg[i]); H.map[k] = i; H.old_target[k] = L.targets()[i];
+  }
+  ctx->want_vec = ctx->resident_vecmap;
+  ctx->lazy_paths = false;                                            // the finalize pass always runs: predecessors and vector maps are re-derived
+  if (replan_reserve(ctx, m) || (each && replan_each_reserve(ctx, m))) return -1;
+  if (materialize(ctx, false, L.cost_limit())) return -1;
+  if (ensure_slots(ctx, m, false, false, ctx->want_vec)) return -1;
+  if (ensure_paths(ctx, m)) return -1;
+  if (ensure_tile_state(ctx, m)) return -1;
+  if (tile_weights(ctx)) return -1;
+  (void)hipEventRecord(ctx->ev[0], ctx->stream);
+  if (fill_tile_records(ctx, m, H.in, offset, H.hp, H.tp, H.vecs)) return -1;
+  HIPCHK(hipMemcpyAsync(R.d_old_target, H.old_target.data(), 4 * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
+  HIPCHK(hipEventRecord(ev_begin, ctx->stream));
+  const uint32_t gm = (m + kBlock - 1) / kBlock;
+  hipLaunchKernelGGL(k_replan_begin, dim3(gm), dim3(kBlock), 0, ctx->stream, ctx->d_tplans, m, R.d_old_target, L.offset(), R.d_level, R.d_cut, R.d_cnt);
+  if (each) hipLaunchKernelGGL(k_replan_open, dim3(gm), dim3(kBlock), 0, ctx->stream, m, R.d_cut, R.d_level);
+  if (R.len)
+    hipLaunchKernelGGL(k_replan_level, dim3((R.len + kBlock - 1) / kBlock, m), dim3(kBlock), 0, ctx->stream, ctx->d_tplans, R.log, R.len,
+                       ctx->d_row_ptr, ctx->d_nbr_u, R.d_level);
+  return 0;
+}
+
+// From here on a repair changes the fields: the record follows, the outputs count again once the repair commits.
+static void replan_repair_begin(mnav_ctx* ctx, uint32_t n, uint32_t* path_len)
+{
+  ctx->res.repair_begin();
+  resident_outputs_begin(ctx);
+  for (uint32_t i = 0; i < n; ++i) if (path_len) path_len[i] = 0;
+}
+
+// The repair went through: the record takes the new robot vertices and the offset, the caller its codes.
+static void replan_repair_commit(mnav_ctx* ctx, const std::vector<uint32_t>& tg, double offset, const std::vector<uint32_t>& codes, uint32_t* codes_out, uint32_t* code)
+{
+  ctx->res.repair_commit(tg, offset, ctx->want_vec);
+  resident_outputs_commit(ctx);
+  uint32_t worst = MNAV_SUCCESS;
+  for (size_t i = 0; i < codes.size(); ++i) {
+    if (codes_out) codes_out[i] = codes[i];
+    if (codes[i] != MNAV_SUCCESS && worst == MNAV_SUCCESS) worst = codes[i];
+  }
+  *code = worst;
+}
+
 // The repair of the m = n resident fields.  tg: the new robot vertices in the caller's order.  Returns 0 (done, *code set),
 // -1 (error), 1 (cancelled) or 2 (policy: nothing was rewound yet, the caller plans afresh).
 static int replan_repair(mnav_ctx* ctx, uint32_t n, const std::vector<uint32_t>& tg, double offset, uint32_t* codes_out, float* dist_out,
@@ -125,33 +190,9 @@ static int replan_repair(mnav_ctx* ctx, uint32_t n, const std::vector<uint32_t>&
 {
   mnav_ctx::Replan& R = ctx->rp;
   const uint32_t m = n;
-  std::vector<PlanIn> in(m); std::vector<uint32_t> map(m), old_target(m);
-  for (uint32_t i = 0; i < n; ++i) {
-    const uint32_t k = R.caller_slot[i];
-    PlanIn p{};
-    for (int q = 0; q < 3; ++q) { p.seed[q] = kNone; p.target[q] = kNone; p.seed_d[q] = 0.f; p.seed_expands[q] = 1; p.target_expands[q] = 1; }
-    p.seed[0] = R.seeds[i]; p.target[0] = tg[i]; p.seed_face = kNone;
-    in[k] = p; map[k] = i; old_target[k] = R.targets[i];
-  }
-  ctx->want_vec = ctx->resident_vecmap;
-  ctx->lazy_paths = false;                                            // the finalize pass always runs: predecessors and vector maps are re-derived
-  if (replan_reserve(ctx, m)) return -1;
-  if (materialize(ctx, false, R.cost_limit)) return -1;
-  if (ensure_slots(ctx, m, false, false, ctx->want_vec)) return -1;
-  if (ensure_paths(ctx, m)) return -1;
-  if (ensure_tile_state(ctx, m)) return -1;
-  if (tile_weights(ctx)) return -1;
-  std::vector<Plan> hp; std::vector<TilePlan> tp; std::vector<float*> vecs;
-  (void)hipEventRecord(ctx->ev[0], ctx->stream);
-  if (fill_tile_records(ctx, m, in, offset, hp, tp, vecs)) return -1;
-  HIPCHK(hipMemcpyAsync(R.d_old_target, old_target.data(), 4 * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
-  HIPCHK(hipEventRecord(R.ev[0], ctx->stream));
-  hipLaunchKernelGGL(k_replan_begin, dim3((m + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, ctx->d_tplans, m, R.d_old_target, R.offset,
-                     R.d_level, R.d_cut, R.d_cnt);
-  if (R.len)
-    hipLaunchKernelGGL(k_replan_level, dim3((R.len + kBlock - 1) / kBlock, m), dim3(kBlock), 0, ctx->stream, ctx->d_tplans, R.log, R.len,
-                       ctx->d_row_ptr, ctx->d_nbr_u, R.d_level);
+  RepairHead H;
+  if (replan_repair_head(ctx, m, tg, offset, false, R.ev[0], H)) return -1;
+  const std::vector<PlanIn>& in = H.in; const std::vector<uint32_t>& map = H.map;
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(R.ev[1], ctx->stream));
   std::vector<float> cut(m);
@@ -166,21 +207,15 @@ static int replan_repair(mnav_ctx* ctx, uint32_t n, const std::vector<uint32_t>&
     if (share < f) return 2;
   }
   const bool warm = replan_takes_warm(ctx, m);                        // all m plans from their rewound fields on the tile-batch engine
-  // from here on the fields change: the record of the last call follows
-  ctx->caller_slot = R.caller_slot;                                   // (an inflation wave in between took slot 0's bookkeeping, not its dist)
-  ctx->shard.finalized = false; ctx->tb.count_pending = false; ctx->tb_args_valid = false;
-  ctx->last_planner = kPlannerDijkstra; ctx->last_n = 0; R.usable = false;
-  ctx->last_target.resize(m); for (uint32_t k = 0; k < m; ++k) ctx->last_target[k] = in[k].target[0];
-  ctx->last_offset = offset; R.each_engines = 0;
+  replan_repair_begin(ctx, n, path_len);
   std::vector<uint32_t> codes(n, MNAV_SUCCESS);
-  for (uint32_t i = 0; i < n; ++i) if (path_len) path_len[i] = 0;
   if (warm) {
     std::vector<uint32_t> who(m);
     std::iota(who.begin(), who.end(), 0u);
     ReplanCnt tot{};
     const int rc = replan_warm_run(ctx, m, in, who, R.levels, map, offset, codes, dist_out, pred_out, path_out, path_cap, path_len, nullptr, &tot);
     if (rc != 0) return rc;
-    ctx->last_engine = 5; ctx->last_n = m;
+    ctx->last_engine = 5;
     R.kept = tot.kept; R.rewound = tot.rewound; R.tiles_woken = tot.woken;
   } else {
   hipLaunchKernelGGL(k_replan_rewind, dim3(ctx->tiles_meta.ntiles ? ctx->tiles_meta.ntiles : 1u, m), dim3(kTileBlock), 0, ctx->stream,
@@ -195,8 +230,8 @@ static int replan_repair(mnav_ctx* ctx, uint32_t n, const std::vector<uint32_t>&
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(R.ev[4], ctx->stream));
   HIPCHK(hipEventRecord(ctx->ev[3], ctx->stream));
-  ctx->last_engine = 0; ctx->last_n = m;
-  if (dijkstra_tail(ctx, m, 0, map, codes, dist_out, pred_out, path_out, path_cap, path_len, nullptr, ctx->want_vec)) { ctx->last_n = 0; return -1; }
+  ctx->last_engine = 0;
+  if (dijkstra_tail(ctx, m, 0, map, codes, dist_out, pred_out, path_out, path_cap, path_len, nullptr, ctx->want_vec)) return -1;
   std::vector<ReplanCnt> cnt(m);
   HIPCHK(hipMemcpy(cnt.data(), R.d_cnt, sizeof(ReplanCnt) * (size_t)m, hipMemcpyDeviceToHost));
   R.kept = R.rewound = 0; R.tiles_woken = 0;
@@ -210,14 +245,7 @@ static int replan_repair(mnav_ctx* ctx, uint32_t n, const std::vector<uint32_t>&
   R.ms_level = ev_ms(R.ev[0], R.ev[1]);
   if (warm) { R.rounds = R.warm.iters; R.ms_rewind = R.warm.ms_warm; R.ms_rounds = R.warm.ms_engine; R.ms_finalize = R.warm.ms_finalize; }
   else { R.rounds = ctx->stats.launches; R.ms_rewind = ev_ms(R.ev[1], R.ev[2]); R.ms_rounds = (float)ctx->ms_chunks; R.ms_finalize = ev_ms(R.ev[3], R.ev[4]); }
-  R.targets = tg; R.offset = offset; R.usable = true; R.len = 0; R.all = false;   // the change log starts over
-  R.finalized = true; R.vec_resident = ctx->want_vec; R.slot0_taken = false;
-  uint32_t worst = MNAV_SUCCESS;
-  for (uint32_t i = 0; i < n; ++i) {
-    if (codes_out) codes_out[i] = codes[i];
-    if (codes[i] != MNAV_SUCCESS && worst == MNAV_SUCCESS) worst = codes[i];
-  }
-  *code = worst;
+  replan_repair_commit(ctx, tg, offset, codes, codes_out, code);
   return 0;
 }
 
@@ -233,27 +261,22 @@ static uint32_t replan_call(mnav_ctx* ctx, uint32_t n, const uint32_t* targets, 
 {
   if (!ctx) return MNAV_INTERNAL_ERROR;
   mnav_ctx::Replan& R = ctx->rp;
+  Resident& L = ctx->res;
   // refusals: outputs, change log and replan state stay as they are
   ctx->err.clear();
   if (!ctx->have_mesh) { ctx->err = "mnav_upload_mesh has not been called"; return MNAV_INTERNAL_ERROR; }
   if (goal_dist_offset != goal_dist_offset) { ctx->err = "goal_dist_offset is NaN"; return MNAV_INTERNAL_ERROR; }
-  if (!R.have_call) { ctx->err = "replan: no Dijkstra call to bring up to date (mnav_plan_dijkstra* first)"; return MNAV_INTERNAL_ERROR; }
-  if (n != R.seeds.size()) { ctx->err = "replan: n differs from the last Dijkstra call"; return MNAV_INTERNAL_ERROR; }
+  if (!L.has_recorded_call()) { ctx->err = "replan: no Dijkstra call to bring up to date (mnav_plan_dijkstra* first)"; return MNAV_INTERNAL_ERROR; }
+  if (n != L.seeds().size()) { ctx->err = "replan: n differs from the last Dijkstra call"; return MNAV_INTERNAL_ERROR; }
   if (check_ready(ctx)) return MNAV_INTERNAL_ERROR;
   if (n == 0) return MNAV_SUCCESS;
   if (hipSetDevice(ctx->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return MNAV_INTERNAL_ERROR; }
-  ctx->cancel.store(0);                                               // a stale flag does not cancel (dijkstra :238)
-  if (ctx->d_cancel) { (void)hipStreamSynchronize(ctx->cancel_stream); (void)hipMemsetAsync(ctx->d_cancel, 0, 4, ctx->stream); }
-  const std::vector<uint32_t> seeds = R.seeds;
-  const std::vector<uint32_t> tg = targets ? std::vector<uint32_t>(targets, targets + n) : R.targets;
+  cancel_reset(ctx);
+  const std::vector<uint32_t> seeds = L.seeds();
+  const std::vector<uint32_t> tg = targets ? std::vector<uint32_t>(targets, targets + n) : L.targets();
   const uint32_t log_len = R.len;
-  uint32_t reason = 0;
-  if (R.partial && ctx->last_planner == kPlannerDijkstra) reason = 3; // a plan of the last call never reached the device (none of them: no field either)
-  else if (!R.usable || ctx->last_planner != kPlannerDijkstra || ctx->last_n != n || R.caller_slot.size() != n || ctx->slots.size() < n) reason = 1;
-  else if (R.all) reason = 2;
-  else
-    for (uint32_t i = 0; i < n; ++i)
-      if (R.caller_slot[i] >= n || tg[i] >= ctx->V || tg[i] == seeds[i]) { reason = 3; break; }
+  const double cost_limit = L.cost_limit();
+  const uint32_t reason = L.replan_reason(n, tg, ctx->V, ctx->slots.size(), R.all);
   R.reason = reason; R.stat_log_len = log_len; R.kept = R.rewound = 0; R.tiles_woken = R.rounds = 0; R.levels.clear();
   R.ms_level = R.ms_rewind = R.ms_rounds = R.ms_finalize = 0.f;
   replan_warm_begin_stats(ctx);
@@ -264,18 +287,18 @@ static uint32_t replan_call(mnav_ctx* ctx, uint32_t n, const uint32_t* targets, 
                         : replan_repair(ctx, n, tg, goal_dist_offset, codes_out, dist_out, pred_out, path_out, path_cap, path_len, &code);
     if (rc == 0) return code;
     if (rc == 1) {                                                    // cancelled between two chunks of rounds: the fields are half rewound
-      R.usable = false; ctx->last_n = 0;
+      L.call_failed();
       for (uint32_t i = 0; i < n; ++i) if (codes_out) codes_out[i] = MNAV_CANCELED;
       return MNAV_CANCELED;
     }
-    if (rc < 0) { R.usable = false; ctx->last_n = 0; (void)hipStreamSynchronize(ctx->stream); return MNAV_INTERNAL_ERROR; }
+    if (rc < 0) { L.call_failed(); (void)hipStreamSynchronize(ctx->stream); return MNAV_INTERNAL_ERROR; }
     R.reason = 4; R.levels.clear(); R.warm.fallback = 0;              // policy: plan afresh
     if (each) { R.each.reason = 4; R.each.whole_fresh = 1; }
   }
   // a fresh plan from the recorded seeds, finalize pass included: always a correct answer
   const bool lazy = ctx->allow_lazy_paths;
   ctx->allow_lazy_paths = false;
-  const uint32_t rc = dijkstra_impl(ctx, n, seeds.data(), tg.data(), goal_dist_offset, R.cost_limit, codes_out, dist_out, pred_out, path_out, path_cap,
+  const uint32_t rc = dijkstra_impl(ctx, n, seeds.data(), tg.data(), goal_dist_offset, cost_limit, codes_out, dist_out, pred_out, path_out, path_cap,
                                     path_len, nullptr, false);
   ctx->allow_lazy_paths = lazy;
   return rc;
@@ -287,7 +310,7 @@ uint32_t mnav_replan_dijkstra_batch(mnav_ctx* ctx, uint32_t n, const uint32_t* t
   return replan_call(ctx, n, targets, goal_dist_offset, codes_out, dist_out, pred_out, path_out, path_cap, path_len, false);
 }
 
-uint32_t mnav_replan_plans(const mnav_ctx* ctx) { return ctx && ctx->rp.have_call ? (uint32_t)ctx->rp.seeds.size() : 0u; }
+uint32_t mnav_replan_plans(const mnav_ctx* ctx) { return ctx && ctx->res.has_recorded_call() ? (uint32_t)ctx->res.seeds().size() : 0u; }
 
 int mnav_replan_stats(const mnav_ctx* ctx, uint32_t* reason, uint32_t* log_len, float* levels_out, uint64_t* kept, uint64_t* rewound,
                       uint32_t* tiles_woken, uint32_t* rounds, float* ms_level, float* ms_rewind, float* ms_rounds, float* ms_finalize)

@@ -58,40 +58,15 @@ static int replan_each_repair(mnav_ctx* ctx, uint32_t n, const std::vector<uint3
   mnav_ctx::Replan& R = ctx->rp;
   mnav_ctx::Replan::Each& E = R.each;
   const uint32_t m = n;
-  std::vector<PlanIn> in(m); std::vector<uint32_t> map(m), old_target(m);
-  for (uint32_t i = 0; i < n; ++i) {
-    const uint32_t k = R.caller_slot[i];
-    PlanIn p{};
-    for (int q = 0; q < 3; ++q) { p.seed[q] = kNone; p.target[q] = kNone; p.seed_d[q] = 0.f; p.seed_expands[q] = 1; p.target_expands[q] = 1; }
-    p.seed[0] = R.seeds[i]; p.target[0] = tg[i]; p.seed_face = kNone;
-    in[k] = p; map[k] = i; old_target[k] = R.targets[i];
-  }
-  ctx->want_vec = ctx->resident_vecmap;
-  ctx->lazy_paths = false;                                            // every plan leaves a finalized field behind
-  if (replan_reserve(ctx, m) || replan_each_reserve(ctx, m)) return -1;
-  if (materialize(ctx, false, R.cost_limit)) return -1;
-  if (ensure_slots(ctx, m, false, false, ctx->want_vec)) return -1;
-  if (ensure_paths(ctx, m)) return -1;
-  if (ensure_tile_state(ctx, m)) return -1;
-  if (tile_weights(ctx)) return -1;
-  std::vector<Plan> hp; std::vector<TilePlan> tp; std::vector<float*> vecs;
-  (void)hipEventRecord(ctx->ev[0], ctx->stream);
-  if (fill_tile_records(ctx, m, in, offset, hp, tp, vecs)) return -1;
-  HIPCHK(hipMemcpyAsync(R.d_old_target, old_target.data(), 4 * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
-  HIPCHK(hipEventRecord(E.ev[0], ctx->stream));
-  const uint32_t gm = (m + kBlock - 1) / kBlock;
-  hipLaunchKernelGGL(k_replan_begin, dim3(gm), dim3(kBlock), 0, ctx->stream, ctx->d_tplans, m, R.d_old_target, R.offset, R.d_level, R.d_cut, R.d_cnt);
-  hipLaunchKernelGGL(k_replan_open, dim3(gm), dim3(kBlock), 0, ctx->stream, m, R.d_cut, R.d_level);
-  if (R.len)
-    hipLaunchKernelGGL(k_replan_level, dim3((R.len + kBlock - 1) / kBlock, m), dim3(kBlock), 0, ctx->stream, ctx->d_tplans, R.log, R.len,
-                       ctx->d_row_ptr, ctx->d_nbr_u, R.d_level);
-  // a plan is kept as it is only when its field went through a finalize pass, its vector map (if one is wanted) is resident
-  // and the offset has the recorded bits; never in slot 0 after an inflation wave took that slot's predecessors
-  const bool keepable = R.finalized && (!ctx->want_vec || R.vec_resident) && memcmp(&offset, &R.offset, sizeof(double)) == 0;
+  RepairHead H;
+  if (replan_repair_head(ctx, m, tg, offset, true, E.ev[0], H)) return -1;
+  const std::vector<PlanIn>& in = H.in; const std::vector<uint32_t>& map = H.map;
+  // a plan is kept as it is only when the record allows it (finalized field, vector map if one is wanted, the recorded
+  // offset bits); never in slot 0 after an inflation wave took that slot's predecessors
+  const bool keepable = ctx->res.may_keep(offset, ctx->want_vec);
   const double f = opt_set(ctx->opt.replan_fresh_below) ? ctx->opt.replan_fresh_below : kReplanFreshBelow;
   hipLaunchKernelGGL(k_replan_classify, dim3(1), dim3(kClassifyBlock), 0, ctx->stream, ctx->d_tplans, m, R.d_old_target, R.d_cut, R.d_level,
-                     keepable ? 1u : 0u, R.slot0_taken ? 0u : kNone, f, E.d_cls, E.d_ratio, E.d_lists, E.d_counts);
+                     keepable ? 1u : 0u, ctx->res.slot0_lost() ? 0u : kNone, f, E.d_cls, E.d_ratio, E.d_lists, E.d_counts);
   EachGather G{};
   G.plans = ctx->d_plans; G.tplans = ctx->d_tplans; G.vecptrs = ctx->d_vecptrs; G.level = R.d_level; G.lists = E.d_lists; G.counts = E.d_counts; G.n = m;
   G.c_plans = E.d_plans; G.c_tplans = E.d_tplans; G.c_vecptrs = E.d_vecptrs; G.c_level = E.d_level; G.c_cnt = E.d_cnt; G.c_tctl = E.d_tctl; G.c_res = E.d_res;
@@ -119,15 +94,9 @@ static int replan_each_repair(mnav_ctx* ctx, uint32_t n, const std::vector<uint3
   for (uint32_t k = 0; k < m; ++k) if (cls[k] == kEachRepaired) tail.push_back(k);
   for (uint32_t k = 0; k < m; ++k) if (cls[k] == kEachKept) tail.push_back(k);
   for (uint32_t k = 0; k < m; ++k) if (cls[k] == kEachFresh) fresh.push_back(k);
-  // from here on the fields change: the record of the last call follows
-  ctx->caller_slot = R.caller_slot;                                   // (an inflation wave in between took slot 0's bookkeeping, not its dist)
-  ctx->shard.finalized = false; ctx->tb.count_pending = false; ctx->tb_args_valid = false;
-  ctx->last_planner = kPlannerDijkstra; ctx->last_n = 0; R.usable = false; R.each_engines = 0;
-  ctx->last_target.resize(m); for (uint32_t k = 0; k < m; ++k) ctx->last_target[k] = in[k].target[0];
-  ctx->last_offset = offset;
+  replan_repair_begin(ctx, n, path_len);
   ctx->last_engine = 0;
   std::vector<uint32_t> codes(n, MNAV_SUCCESS);
-  for (uint32_t i = 0; i < n; ++i) if (path_len) path_len[i] = 0;
   std::vector<PlanResult> res(m);                                     // per device plan, for the statistics of the whole call
   const TileTables T{ E.d_plans, E.d_tplans, E.d_tctl, E.d_res };
   HIPCHK(hipEventRecord(E.ev[2], ctx->stream));
@@ -205,19 +174,11 @@ static int replan_each_repair(mnav_ctx* ctx, uint32_t n, const std::vector<uint3
   E.fresh_engine = sub_engine;
   // the whole call's results in device-plan order, as the statistics and the lazy readers expect them
   for (uint32_t k = 0; k < m; ++k) ctx->h_res[k] = res[k];
-  ctx->last_n = m;
   finish_stats(ctx, m, false);
   R.each_engines = 256 + (warm ? 512 + (R.warm.kernel == 1 ? 1024 : 0) : nr ? 128 : 0) + (sub_engine >= 0 ? sub_engine : 127);
   R.levels = E.levels; R.kept = E.kept; R.rewound = E.rewound; R.tiles_woken = E.tiles_woken; R.rounds = E.rounds;
   R.ms_level = E.ms_classify; R.ms_rewind = E.ms_rewind; R.ms_rounds = E.ms_rounds; R.ms_finalize = E.ms_finalize;
-  R.targets = tg; R.offset = offset; R.usable = true; R.len = 0; R.all = false;   // the change log starts over
-  R.finalized = true; R.vec_resident = ctx->want_vec; R.slot0_taken = false;
-  uint32_t worst = MNAV_SUCCESS;
-  for (uint32_t i = 0; i < n; ++i) {
-    if (codes_out) codes_out[i] = codes[i];
-    if (codes[i] != MNAV_SUCCESS && worst == MNAV_SUCCESS) worst = codes[i];
-  }
-  *code = worst;
+  replan_repair_commit(ctx, tg, offset, codes, codes_out, code);
   return 0;
 }
 

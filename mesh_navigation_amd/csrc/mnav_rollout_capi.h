@@ -52,10 +52,9 @@ int mnav_follow_rollout(mnav_ctx* ctx, uint32_t n, const float* pos, const float
   if (!(turn < 100.0)) { ctx->err = "rollout: max_ang_velocity * max(1, ang_vel_factor) * dt must stay below 100 rad per tick"; return -1; }
   const uint32_t ticks = rollout->ticks, stride = rollout->trace_stride, rows = stride ? ticks / stride : 0;
   if (hipSetDevice(ctx->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return -1; }
-  ctx->cancel.store(0);                                               // as the plan calls do
-  if (ctx->d_cancel) { (void)hipStreamSynchronize(ctx->cancel_stream); (void)hipMemsetAsync(ctx->d_cancel, 0, 4, ctx->stream); }
+  cancel_reset(ctx);                                                  // as the plan calls do
   if (upload_walk_mesh(ctx)) return -1;
-  if (staging_reserve(ctx, n, ctx->caller_slot.size(), "rollout") || rollout_reserve(ctx, n, goal_pos != nullptr, ticks, 3 * (size_t)n * rows)) return -1;
+  if (staging_reserve(ctx, n, ctx->res.plans(), "rollout") || rollout_reserve(ctx, n, goal_pos != nullptr, ticks, 3 * (size_t)n * rows)) return -1;
   Dev& S = ctx->rol;
   mnav_fol::Staging& G = ctx->stage;
   for (auto& c : S.final_status) c = 0;

@@ -176,12 +176,11 @@ int mnav_shard_begin(mnav_ctx* ctx, uint32_t seed_vertex, uint32_t target_vertex
   if (goal_dist_offset != goal_dist_offset) { ctx->err = "goal_dist_offset is NaN"; return -1; }
   if (hipSetDevice(ctx->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return -1; }
   ctx->err.clear();
-  ctx->cancel.store(0);
-  if (ctx->d_cancel) { (void)hipStreamSynchronize(ctx->cancel_stream); (void)hipMemsetAsync(ctx->d_cancel, 0, 4, ctx->stream); }
+  cancel_reset(ctx);
   ctx->want_vec = false;
-  ctx->tb.count_pending = false; ctx->tb_args_valid = false;         // slot 0 and d_res are taken over by the sharded plan
-  ctx->last_planner = kPlannerDijkstra; ctx->last_engine = 0; ctx->last_n = 0; ctx->caller_slot.clear(); ctx->rp.warm.live = false;
-  ctx->rp.usable = ctx->rp.partial = false;                          // slot 0 holds a part of a sharded plan: nothing a replan can rewind
+  ctx->res.shard_took_slot0();                                        // slot 0 and d_res are taken over by the sharded plan: nothing a replan can rewind
+  resident_outputs_begin(ctx);
+  ctx->last_engine = 0;
   if (materialize(ctx, false, cost_limit)) return -1;
   if (ensure_slots(ctx, 1, false, false, false)) return -1;
   if (ensure_paths(ctx, 1)) return -1;
