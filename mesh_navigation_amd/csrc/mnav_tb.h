@@ -56,7 +56,7 @@ struct Args {
   float* D; uint32_t* pend; uint32_t NP, ntiles;
   uint16_t* bucket; uint32_t* bcnt; uint2* items; Ctl* ctl;
   uint32_t* marr[2];
-  uint32_t* mcarry;                                                   // kTbMinCopies x NP: the smallest CARRIED value per plan, by tile % kTbMinCopies (k_tb_sched -> k_tb_plan)
+  uint32_t* mcarry;                                                   // kTbMinCopies x NP: the smallest CARRIED value per plan, min_copies arrays of it in use (k_tb_sched -> k_tb_plan)
   float* thr; float* bnd;
   const uint32_t* seed; const uint32_t* target;                        // per plan: wave source / robot vertex
   const uint2* vaddr; const uint32_t* vert_tile;                      // per vertex: {soff, sl << 8 | local}, tile
@@ -64,6 +64,7 @@ struct Args {
   uint8_t* pflag; uint32_t nblk;                                     // per (tile, block of 64 plans): 1 = some pend[tile][plan] of the block may be set
   unsigned long long* wstat; uint32_t wstat_slots;                  // statistics per persistent wave {items, activations, sweeps, wakes}: k_tb_stats sums them
   uint32_t item_plans;                                               // plans per work item: 16 (a quarter of a wave, k_tb_solve_q) or 64 (a wave, k_tbv_solve)
+  uint32_t sched_lds, min_copies;                                    // k_tb_sched: 1 = carried minima meet in LDS first; the arrays of mcarry in use (k_tb_plan folds them)
 };
 
 __device__ __forceinline__ size_t slot_addr(const uint2 va, uint32_t NP, uint32_t p)
@@ -121,8 +122,17 @@ __global__ __launch_bounds__(kBlock) void k_tb_seed(tb::Args A)
 // on the 1M mesh, from every CU at once.  Atomics execute at the memory side, and all of them into the 28 KB of ONE array of NP words is the
 // contended case; so k_tb_sched keeps kTbMinCopies arrays, a tile using copy tile % kTbMinCopies, and k_tb_plan folds them into the plan's
 // minimum (and resets them) when it reads it.  The solve kernels and the start kernels keep writing marr[] itself.
+// A workgroup of k_tb_sched that reduces its tiles' carried values in LDS first (A.sched_lds) sends one atomicMin per plan it
+// carried instead of one per (tile, plan): kTbMinCopiesLds arrays, by workgroup, are enough then, and k_tb_plan folds only those
+// (A.min_copies; the arrays beyond stay +inf).
 constexpr uint32_t kTbMinCopies = 64;
-// per plan and iteration: band threshold and goal bound
+#ifndef MNAV_TB_MIN_COPIES_LDS
+#define MNAV_TB_MIN_COPIES_LDS 4
+#endif
+constexpr uint32_t kTbMinCopiesLds = MNAV_TB_MIN_COPIES_LDS;
+static_assert(kTbMinCopiesLds >= 1 && kTbMinCopiesLds <= kTbMinCopies, "the LDS path's copies are the first ones of mcarry");
+// per plan and iteration: band threshold and goal bound.  NC = A.min_copies.
+template <uint32_t NC>
 __global__ __launch_bounds__(kBlock) void k_tb_plan(tb::Args A, int par)
 {
   const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
@@ -131,11 +141,11 @@ __global__ __launch_bounds__(kBlock) void k_tb_plan(tb::Args A, int par)
   uint32_t mb = A.marr[par][p];
   A.marr[par ^ 1][p] = kTbInfBits;
   {
-    uint32_t x[kTbMinCopies];
+    uint32_t x[NC];
 #pragma unroll
-    for (uint32_t c = 0; c < kTbMinCopies; ++c) x[c] = A.mcarry[(size_t)c * A.NP + p];
+    for (uint32_t c = 0; c < NC; ++c) x[c] = A.mcarry[(size_t)c * A.NP + p];
 #pragma unroll
-    for (uint32_t c = 0; c < kTbMinCopies; ++c) {
+    for (uint32_t c = 0; c < NC; ++c) {
       mb = min(mb, x[c]);                                               // (values >= 0: their bits order like they do)
       if (x[c] != kTbInfBits) A.mcarry[(size_t)c * A.NP + p] = kTbInfBits;
     }
@@ -173,16 +183,38 @@ __global__ __launch_bounds__(kBlock) void k_tb_plan(tb::Args A, int par)
 // kTbSchedDepth blocks: their loads go out together, a group ahead.
 // The order of a tile's bucket is now ascending by plan; the fixed point does not depend on it.
 constexpr uint32_t kTbStatSlots = 16384;                             // >= the persistent waves of a solve launch (k_tb_stats; the host clamps the grid)
-constexpr uint32_t kTbSchedTiles = kBlock / 64;                      // tiles per workgroup of k_tb_sched: one per wave
+//
+// The carried minima.  A plan's carried tiles are the ring ahead of its front, so neighbouring tiles carry the same plans: with
+// A.sched_lds the workgroup -- kTbSchedTiles tiles that follow each other in the bisection order, a compact patch -- keeps NP words
+// of LDS (+inf), a carried value is an LDS min on its float bits and nothing carried goes to global memory during the walk; after a
+// barrier the threads walk the array and send ONE atomicMin per plan the workgroup carried, behind the same stale filter, to copy
+// (workgroup % kTbMinCopiesLds).  Every wave has to reach the barriers: a tile without a set flag skips the walk, it does not
+// return.  NP words must fit the 64 KB a workgroup may take (tb_sched_lds_fits: batches of up to 65 535 plans are legal); beyond
+// that, or with the option tb_sched_lds = 0, the values go to the global copies as before (copy = tile % kTbMinCopies).
+// The items are NOT cut here (tried: the workgroup's item count taken with one returning atomicAdd on n_items -- 579 / 1158 / 2315
+// atomics on one address per launch at 16 / 8 / 4 tiles per workgroup cost 27 / 57 / 114 us, 50 ns each, against the 4.8 us of
+// k_tb_items, which needs 37; profiles/sched_lds_kernel_stats.md).
+#ifndef MNAV_TB_SCHED_TILES
+#define MNAV_TB_SCHED_TILES 16
+#endif
+constexpr uint32_t kTbSchedTiles = MNAV_TB_SCHED_TILES;              // tiles per workgroup of k_tb_sched: one per wave
+static_assert(kTbSchedTiles >= 1 && kTbSchedTiles <= 16, "a workgroup holds at most 16 waves");
+constexpr uint32_t kTbSchedLdsMax = 64u * 1024u;                     // LDS of a k_tb_sched workgroup: the NP words and one of its own
+inline bool tb_sched_lds_fits(uint32_t np) { return 4u * ((size_t)np + 1u) <= kTbSchedLdsMax; }
+#ifndef MNAV_TB_SCHED_FLUSH
+#define MNAV_TB_SCHED_FLUSH 8
+#endif
+constexpr uint32_t kTbSchedFlush = MNAV_TB_SCHED_FLUSH;              // plans per thread whose filter loads are in flight together when the workgroup's minima are sent
 #ifndef MNAV_TB_SCHED_DEPTH
 #define MNAV_TB_SCHED_DEPTH 4
 #endif
 constexpr uint32_t kTbSchedDepth = MNAV_TB_SCHED_DEPTH;              // set blocks of a tile per turn of k_tb_sched
-__global__ __launch_bounds__(kBlock) void k_tb_sched(tb::Args A, int par)
+// The walk of one wave over its tile t.  g_min: the copy of the carried minima the wave's values go to (LDS = false), s_min: the
+// workgroup's NP words (LDS = true).  count: the tile's bucket; carried: something of it is still pending.
+template <bool LDS>
+__device__ __forceinline__ void tb_sched_walk(const tb::Args& A, uint32_t t, uint32_t lane, MNAV_GLOBAL uint32_t* g_min, uint32_t* s_min,
+                                              uint32_t& count, bool& carried)
 {
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t t = tb::rfl(blockIdx.x * kTbSchedTiles + (threadIdx.x >> 6));
-  if (t >= A.ntiles) return;
   const uint32_t nblk = A.nblk, NP = A.NP;
   MNAV_GLOBAL uint8_t* const g_flag = as_global(A.pflag) + (size_t)t * nblk;
   auto flags = [&](uint32_t c) { const uint32_t i = c * 64u + lane; return i < nblk ? (uint32_t)g_flag[i] : 0u; };
@@ -205,19 +237,17 @@ __global__ __launch_bounds__(kBlock) void k_tb_sched(tb::Args A, int par)
   MNAV_GLOBAL const float* const g_bnd = as_global(A.bnd);
   MNAV_GLOBAL uint32_t* const g_pend = as_global(A.pend) + (size_t)t * NP;
   MNAV_GLOBAL uint16_t* const g_bucket = as_global(A.bucket) + (size_t)t * NP;
-  MNAV_GLOBAL uint32_t* const g_min = as_global(A.mcarry) + (size_t)(t % kTbMinCopies) * NP;   // (k_tb_plan)
   struct Row { uint32_t p, pb, pm; float thr, bnd; bool live; };
   auto fetch = [&](uint32_t b) {                                      // the loads of one block, all issued together and none of them under a branch
     Row r;
     const uint32_t p = (b != kNone ? b : 0u) * 64u + lane;            // (no block: block 0's addresses, and nothing of it is used)
     r.live = b != kNone && p < NP;
     r.p = r.live ? p : 0u;
-    r.pb = g_pend[r.p]; r.thr = g_thr[r.p]; r.bnd = g_bnd[r.p]; r.pm = g_min[r.p];
+    r.pb = g_pend[r.p]; r.thr = g_thr[r.p]; r.bnd = g_bnd[r.p];
+    r.pm = LDS ? 0u : g_min[r.p];                                     // (the LDS path filters when it sends the workgroup's minimum)
     return r;
   };
   const unsigned long long below = (1ull << lane) - 1ull;
-  uint32_t count = 0;                                                 // the tile's bucket so far (wave-uniform)
-  bool carried = false;
   constexpr int K = (int)kTbSchedDepth;
   uint32_t b_cur[K];
   Row cur[K];
@@ -237,10 +267,12 @@ __global__ __launch_bounds__(kBlock) void k_tb_sched(tb::Args A, int par)
     __builtin_amdgcn_sched_barrier(0);                                 // (the loads stay above the wait for the current group's)
     // ---- the current group
 #pragma unroll
-    for (int k = 0; k < K; ++k)
-      asm volatile("" :: "v"(cur[k].pb), "v"(cur[k].thr), "v"(cur[k].bnd), "v"(cur[k].pm));   // (all loads of the group waited for HERE: a value
+    for (int k = 0; k < K; ++k) {
+      asm volatile("" :: "v"(cur[k].pb), "v"(cur[k].thr), "v"(cur[k].bnd));   // (all loads of the group waited for HERE: a value
                                                                        // only read under a branch stays "in flight" for the compiler on the other path,
                                                                        // and it then makes room for the next loads by waiting for everything issued since)
+      if (!LDS) asm volatile("" :: "v"(cur[k].pm));
+    }
 #pragma unroll
     for (int k = 0; k < K; ++k) {
       if (b_cur[k] == kNone) break;                                    // (uniform: the blocks of a group are in ascending order, the missing ones last)
@@ -252,7 +284,8 @@ __global__ __launch_bounds__(kBlock) void k_tb_sched(tb::Args A, int par)
         else if (pv < cur[k].thr) { g_pend[p] = kTbInfBits; ready = true; }
         else {
           keep = true;
-          if (pb < cur[k].pm) atomicMin((uint32_t*)(g_min + p), pb);   // (pm is a turn old: the minimum only falls, an older value only lets more through)
+          if (LDS) atomicMin(s_min + p, pb);                           // (values >= 0: their bits order like they do)
+          else if (pb < cur[k].pm) atomicMin((uint32_t*)(g_min + p), pb);   // (pm is a turn old: the minimum only falls, an older value only lets more through)
         }
       }
       const bool any_keep = __any(keep);
@@ -266,14 +299,52 @@ __global__ __launch_bounds__(kBlock) void k_tb_sched(tb::Args A, int par)
 #pragma unroll
     for (int k = 0; k < K; ++k) { cur[k] = nxt[k]; b_cur[k] = b_next[k]; }
   }
-  if (lane == 0u) {
-    if (count) A.bcnt[t] = count;                                     // (k_tb_items left it 0)
-    // "something is still pending" is all anybody asks of this word (the host's loop, the finalize pass): a plain store of 1
-    if (carried) A.ctl->n_cand[par ^ 1] = 1u;
-  }
 }
 
 constexpr uint32_t kTbItemPlans = 16;     // plans per work item = lanes per quarter of a wave (k_tb_solve_q)
+
+template <bool LDS>
+__global__ __launch_bounds__(kTbSchedTiles * 64) void k_tb_sched(tb::Args A, int par)
+{
+  constexpr uint32_t G = kTbSchedTiles, kThreads = G * 64u;
+  extern __shared__ uint32_t s_dyn[];                                  // LDS: {1: a wave of the workgroup carried something, the NP minima}
+  uint32_t* const s_carried = s_dyn; uint32_t* const s_min = s_dyn + 1u;
+  const uint32_t lane = threadIdx.x & 63u, wave = tb::rfl(threadIdx.x >> 6);
+  const uint32_t t = blockIdx.x * G + wave, NP = A.NP;
+  if (LDS) {
+    for (uint32_t i = threadIdx.x; i < NP; i += kThreads) s_min[i] = kTbInfBits;
+    if (threadIdx.x == 0u) *s_carried = 0u;
+    __syncthreads();
+  }
+  MNAV_GLOBAL uint32_t* const g_min = as_global(A.mcarry) + (size_t)(LDS ? blockIdx.x % kTbMinCopiesLds : t % kTbMinCopies) * NP;   // (k_tb_plan)
+  uint32_t count = 0;                                                 // the tile's bucket (wave-uniform)
+  bool carried = false;
+  if (t < A.ntiles) tb_sched_walk<LDS>(A, t, lane, g_min, s_min, count, carried);
+  if (lane == 0u) {
+    if (count) A.bcnt[t] = count;                                     // (k_tb_items left it 0)
+    if (carried) {
+      if (LDS) *s_carried = 1u;
+      // "something is still pending" is all anybody asks of this word (the host's loop, the finalize pass): a plain store of 1
+      A.ctl->n_cand[par ^ 1] = 1u;
+    }
+  }
+  if (!LDS) return;
+  __syncthreads();
+  if (*s_carried == 0u) return;                                       // (uniform over the workgroup)
+  // one atomicMin per plan the workgroup carried, behind the stale filter.  The filter's loads of kU plans per thread go out
+  // together (7168 plans, 1024 threads: one trip to memory for the whole array); the atomics return nothing and nobody waits for them.
+  constexpr uint32_t kU = kTbSchedFlush;
+  for (uint32_t i0 = threadIdx.x; i0 < NP; i0 += kU * kThreads) {
+    uint32_t v[kU], pm[kU];
+#pragma unroll
+    for (uint32_t j = 0; j < kU; ++j) { const uint32_t i = i0 + j * kThreads; v[j] = i < NP ? s_min[i] : kTbInfBits; }
+#pragma unroll
+    for (uint32_t j = 0; j < kU; ++j) pm[j] = v[j] != kTbInfBits ? g_min[i0 + j * kThreads] : 0u;
+#pragma unroll
+    for (uint32_t j = 0; j < kU; ++j) if (v[j] < pm[j]) atomicMin((uint32_t*)(g_min + (i0 + j * kThreads)), v[j]);
+  }
+}
+
 // per tile: cut the bucket into items of <= kTbItemPlans plans.  One thread per tile, one atomic per wave for the item slots (the
 // items of a tile stay adjacent; their order among the tiles is whatever the atomics make it -- the fixed point does not care).
 // Rounds 3-4 ran ONE workgroup over all tiles for a deterministic order: 122 us per iteration at 92 600 tiles, 8 % of the C4 run.
@@ -908,6 +979,7 @@ struct TbBatch {
   DevBuf<float> D; DevBuf<uint32_t> pend; DevBuf<uint32_t> mcarry; DevBuf<uint8_t> pflag; DevBuf<uint16_t> bucket; DevBuf<uint32_t> bcnt; DevBuf<uint2> items;
   DevBuf<tb::Ctl> ctl; PinnedBuf<tb::Ctl> h_ctl;
   DevBuf<unsigned long long> wstat; DevBuf<struct FinRec> d_recs;
+  PinnedBuf<Plan> h_plans; PinnedBuf<float*> h_vecs;   // staging of the finalize pass's plan records: written and sent before the engine runs (tb_fields_upload)
   DevBuf<uint32_t> marr[2];
   DevBuf<float> thr, bnd; DevBuf<uint32_t> seed, target;
   GraphExec graph[2]; tb::Args graph_args[2]{};   // one per distance buffer

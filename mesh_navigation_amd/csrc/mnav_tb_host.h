@@ -133,6 +133,7 @@ int tb_ensure_batch(mnav_ctx* ctx, uint32_t np)
   HIPCHK(S.thr.alloc(4 * (size_t)np)); HIPCHK(S.bnd.alloc(4 * (size_t)np));
   HIPCHK(S.seed.alloc(4 * (size_t)np)); HIPCHK(S.target.alloc(4 * (size_t)np));
   HIPCHK(S.d_recs.alloc(sizeof(FinRec) * (size_t)np));
+  HIPCHK(S.h_plans.alloc(sizeof(Plan) * (size_t)np)); HIPCHK(S.h_vecs.alloc(sizeof(float*) * (size_t)np));
   S.cap_np = np;
   return 0;
 }
@@ -150,10 +151,17 @@ int tb_fill(mnav_ctx* ctx, void* p, size_t bytes, uint32_t v)
 int tb_launch_iterations(mnav_ctx* ctx, const tb::Args& A, int count, uint32_t waves)
 {
   const uint32_t gp = (A.NP + kBlock - 1) / kBlock;
+  const dim3 gs(std::max((A.ntiles + kTbSchedTiles - 1) / kTbSchedTiles, 1u)), bs(kTbSchedTiles * 64u);
+  const size_t lds_s = A.sched_lds ? 4 * ((size_t)A.NP + 1u) : 0;   // (k_tb_sched: <= kTbSchedLdsMax, tb_sched_lds_fits)
   for (int j = 0; j < count; ++j) {
     const int par = j & 1;
-    hipLaunchKernelGGL(k_tb_plan, dim3(gp), dim3(kBlock), 0, ctx->stream, A, par);
-    hipLaunchKernelGGL(k_tb_sched, dim3(std::max((A.ntiles + kTbSchedTiles - 1) / kTbSchedTiles, 1u)), dim3(kBlock), 0, ctx->stream, A, par);
+    if (A.sched_lds) {
+      hipLaunchKernelGGL((k_tb_plan<kTbMinCopiesLds>), dim3(gp), dim3(kBlock), 0, ctx->stream, A, par);
+      hipLaunchKernelGGL((k_tb_sched<true>), gs, bs, lds_s, ctx->stream, A, par);
+    } else {
+      hipLaunchKernelGGL((k_tb_plan<kTbMinCopies>), dim3(gp), dim3(kBlock), 0, ctx->stream, A, par);
+      hipLaunchKernelGGL((k_tb_sched<false>), gs, bs, lds_s, ctx->stream, A, par);
+    }
     hipLaunchKernelGGL(k_tb_items, dim3((A.ntiles + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, A);
     if (ctx->tb.kernel == 1) hipLaunchKernelGGL((k_tbv_solve<120>), dim3(waves), dim3(64), 0, ctx->stream, A, ctx->tb.d_vtile, ctx->tb.d_vstream, ctx->tb.d_vgroups, ctx->tb.d_vexps, par);
     else if (ctx->tb.T == 64) hipLaunchKernelGGL((k_tb_solve_q<64>), dim3(waves), dim3(64), 0, ctx->stream, A, par);
@@ -166,14 +174,18 @@ int tb_launch_iterations(mnav_ctx* ctx, const tb::Args& A, int count, uint32_t w
   return 0;
 }
 
-// per-plan arrays in vertex order + the finalize pass, for calls that want V-sized outputs
-int tb_fields(mnav_ctx* ctx, uint32_t n, const std::vector<PlanIn>& in, double offset, const tb::Args& A)
+// What the finalize pass needs besides the engine's result -- the output slots, the weights of its tables and the plans' records
+// on the device -- depends on nothing the engine computes: it is prepared and sent BEFORE the engine runs, so that tb_fields only
+// enqueues kernels behind the last chunk.  (It used to fill the records, upload them from pageable memory and synchronise after
+// the last chunk had been waited for, with the device idle.)  The records are written in pinned staging that lives with the batch
+// state: nothing dangles when a call ends early, and no synchronisation is needed for the host's sake.
+int tb_fields_upload(mnav_ctx* ctx, uint32_t n, const std::vector<PlanIn>& in, double offset)
 {
   TbState& S = ctx->tb;
   if (ensure_slots(ctx, n, false, false, ctx->want_vec)) return -1;
   if (tb_fin_weights(ctx)) return -1;
-  std::vector<Plan> hp(n);
-  std::vector<float*> vecs(n);
+  Plan* const hp = S.h_plans.get();
+  float** const vecs = S.h_vecs.get();
   for (uint32_t i = 0; i < n; ++i) {
     Slot& s = ctx->slots[i];
     Plan& P = hp[i];
@@ -186,9 +198,15 @@ int tb_fields(mnav_ctx* ctx, uint32_t n, const std::vector<PlanIn>& in, double o
     P.seed_face = kNone;
     vecs[i] = s.vecmap;
   }
-  HIPCHK(hipMemcpyAsync(ctx->d_plans, hp.data(), sizeof(Plan) * n, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(ctx->d_vecptrs, vecs.data(), sizeof(float*) * n, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));                          // hp / vecs go out of scope
+  HIPCHK(hipMemcpyAsync(ctx->d_plans, hp, sizeof(Plan) * n, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(ctx->d_vecptrs, vecs, sizeof(float*) * n, hipMemcpyHostToDevice, ctx->stream));
+  return 0;
+}
+
+// per-plan arrays in vertex order: the finalize pass, for calls that want V-sized outputs (tb_fields_upload has run)
+int tb_fields(mnav_ctx* ctx, uint32_t n, const tb::Args& A)
+{
+  TbState& S = ctx->tb;
   // potential (with the reference's tentative values beyond goal_dist), predecessors and vector map of every plan, in vertex
   // order, straight from the blocked distances: one wave per (tile, 64 plans), eight tiles per workgroup, mnav_tb_finalize.h
   FinTb F{};
@@ -258,6 +276,7 @@ int run_dijkstra_tb(mnav_ctx* ctx, uint32_t n, const std::vector<PlanIn>& in, do
   HIPCHK(hipMemcpyAsync(S.target, targets.data(), 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipMemsetAsync(ctx->d_res, 0, sizeof(PlanResult) * n, ctx->stream));
   HIPCHK(hipMemsetAsync(ctx->d_mismatch, 0, 4, ctx->stream));
+  if (!ctx->lazy_paths && tb_fields_upload(ctx, n, in, offset)) return -1;   // (V-sized outputs wanted: everything the finalize pass needs from the host, now)
   tb::Args A{};
   A.tiles = S.d_tiles; A.stream = S.d_stream; A.exps = S.d_exps; A.D = S.D; A.pend = S.pend; A.pflag = S.pflag; A.nblk = (n + 63u) / 64u; A.NP = n; A.ntiles = S.ntiles;
   A.bucket = S.bucket; A.bcnt = S.bcnt; A.items = S.items; A.ctl = S.ctl; A.wstat = S.wstat; A.wstat_slots = kTbStatSlots;
@@ -275,6 +294,9 @@ int run_dijkstra_tb(mnav_ctx* ctx, uint32_t n, const std::vector<PlanIn>& in, do
   S.kernel = (v_fits && density >= 8.0) ? 1 : 0;
   if (opt_set(ctx->opt.tb_kernel)) S.kernel = (opt_u32(ctx->opt.tb_kernel, 0u) == 1u && v_fits) ? 1 : 0;
   A.item_plans = S.kernel == 1 ? 64u : kTbItemPlans;
+  // the schedule pass reduces the carried minima per workgroup in LDS while the plans' words fit there (mnav_tb.h)
+  A.sched_lds = (tb_sched_lds_fits(n) && !(opt_set(ctx->opt.tb_sched_lds) && !opt_on(ctx->opt.tb_sched_lds))) ? 1u : 0u;
+  A.min_copies = A.sched_lds ? kTbMinCopiesLds : kTbMinCopies;
   {
     const float band_mult = (S.kernel == 1 && density < 40.0) ? 4.0f : S.band_mult;
     float band = (ctx->delta_auto / 3.0f) * std::sqrt((float)S.T) * band_mult;   // potential across one tile
@@ -368,7 +390,7 @@ int run_dijkstra_tb(mnav_ctx* ctx, uint32_t n, const std::vector<PlanIn>& in, do
     // V-sized outputs wanted (potential, predecessors, vector map): the finalize pass of the tile engines derives the
     // reference's exact cut-off semantics and predecessors straight from the blocked distances (k_tb_finalize)
     if (warm) HIPCHK(hipEventRecord(S.warm_ev[2], ctx->stream));
-    if (tb_fields(ctx, n, in, offset, A)) return -1;
+    if (tb_fields(ctx, n, A)) return -1;
     if (warm) HIPCHK(hipEventRecord(S.warm_ev[3], ctx->stream));
   }
   HIPCHK(hipEventRecord(ctx->ev[3], ctx->stream));
@@ -382,8 +404,8 @@ int run_dijkstra_tb(mnav_ctx* ctx, uint32_t n, const std::vector<PlanIn>& in, do
   ctx->stats.launches = 1;                                           // one engine run per batch (iterations: stats.steps)
   ctx->tb_args = A; ctx->tb_args_valid = (rc == 0);
   if (opt_on(ctx->opt.trace))
-    fprintf(stderr, "[mnav] tile-batch: %u iterations, %llu activations (%.1f per item), %llu items, %.2f sweeps per item, %llu wakes\n", S.h_ctl->iters,
+    fprintf(stderr, "[mnav] tile-batch: %u iterations, %llu activations (%.1f per item), %llu items, %.2f sweeps per item, %llu wakes, carried minima %s\n", S.h_ctl->iters,
             S.h_ctl->acts, S.h_ctl->items ? (double)S.h_ctl->acts / S.h_ctl->items : 0.0, S.h_ctl->items,
-            S.h_ctl->items ? (double)S.h_ctl->sweeps / S.h_ctl->items : 0.0, S.h_ctl->wakes);
+            S.h_ctl->items ? (double)S.h_ctl->sweeps / S.h_ctl->items : 0.0, S.h_ctl->wakes, A.sched_lds ? "reduced in LDS" : "in global memory");
   return rc;
 }
