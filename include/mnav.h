@@ -352,6 +352,7 @@ int mnav_map_compute(mnav_ctx* ctx);
  *                           here, so an inflation node on this input re-runs its wave whenever n > 0
  *   mnav_map_obstacle       mnav_layer_obstacle on the slot (same arguments from n_points to max_obstacle_dist); its change
  *                           list never leaves the device
+ *   mnav_map_traffic        (declared with the fleet traffic calls below) mnav_layer_traffic on the slot, in the same way
  * Then every dependent node is visited in dependency order with the union of the change lists of its inputs that changed
  * in this call.  A combination recombines those vertices (cost and flag); its own list is the subset whose cost bits or
  * flag now differ.  An inflation node whose input had no lethal flag flipped on the list is left alone and emits nothing
@@ -781,6 +782,55 @@ int mnav_fleet_assign(mnav_ctx* ctx, uint32_t n, const uint32_t* start_vertex, c
 int mnav_dispatch_stats(const mnav_ctx* ctx, uint64_t* pairs, uint64_t* feasible, uint32_t* assigned, uint32_t* phases,
                         uint64_t* rounds, uint64_t* tail_rounds, uint64_t* bids, uint32_t* built_index, float* ms_costs,
                         float* ms_assign, float* ms_total);
+
+/* -- fleet traffic: how many planned paths cross each vertex, and the congestion cost of the excess ------
+ * Every fleet call above gives a robot the shortest path of its field as if it were alone.  The calls below close the
+ * loop of negotiated congestion on the device: count the paths per vertex, turn the excess into a cost layer, let the
+ * layer graph propagate it and replan.  No path id and no V-sized array crosses PCIe.
+ *
+ * The context owns V uint32 counts c and T, the 64-bit total of the accumulated weight; both are zero after
+ * mnav_upload_mesh.  mnav_fleet_traffic takes robots, slots, start_vertex / start_pos, code_out, vertex_out and
+ * potential_out exactly as mnav_fleet_paths does and gives them the same values for the same inputs (the lazy look of
+ * rule 5 included).  weights[i] (NULL: 1) is the weight w_i of robot i.
+ * Robot i CONTRIBUTES iff mnav_fleet_paths gives it MNAV_SUCCESS with a finite potential_out: rule 3 (it stands on the
+ * seed) and rule 4 with a chain that reaches the seed; never the seed == target plans of rule 2's CAUTION, no other code.
+ * A contributing robot adds w_i to c[v_i] and to c[u] for every id u of its path (pred[v], pred[pred[v]], ..., seed):
+ * len + 1 adds, one add -- to c[seed] -- under rule 3; w_i == 0 is classified and adds nothing.  T grows by the weights of
+ * the contributing robots.  A path visits a vertex at most once, so no count exceeds T.
+ * accumulate == 0: c and T are zeroed first, but only after every refusal check has passed (n = 0 then only zeroes them);
+ * accumulate != 0: the call adds on top -- two calls over two halves of a fleet equal one call over the whole fleet; n = 0
+ * does nothing.  Sums of integers do not depend on their order: c is the same bits in every call and on every path.
+ * Returns 0, or -1 with mnav_last_error set and NOTHING touched (c, T, the outputs and the statistics included): every
+ * refusal of mnav_fleet_paths, a field made stale by a cost-changing call included, and the sum of w_i over ALL n robots
+ * (as uint64, plus T when accumulating) above 2^32 - 1: "total weight does not fit the counters".  The call changes no plan
+ * output, no layer and no statistic of another entry point (mnav_fleet_stats keeps its values); with positions it builds
+ * the lookup index of mnav_locate when none exists yet.  Option traffic_combine (default 0): a wave whose contributors all
+ * end on one vertex issues one add for them; the counts do not depend on it. */
+int mnav_fleet_traffic(mnav_ctx* ctx, uint32_t n, const uint32_t* slots, const uint32_t* start_vertex, const float* start_pos,
+                       const uint32_t* weights, int accumulate, uint32_t* code_out, uint32_t* vertex_out, float* potential_out);
+/* The counts: V words.  All zero when no traffic call ran since mnav_upload_mesh.  -1: no mesh, a null array. */
+int mnav_traffic_download(const mnav_ctx* ctx, uint32_t* counts_out);
+/* The last mnav_fleet_traffic that returned 0: robots that contributed with a weight above 0, vertex adds performed, T,
+ * the vertices with c > 0 and the largest count after the call; built_index = 1 if the call built the lookup index; device
+ * milliseconds of its kernels and host milliseconds of the whole call.  Any pointer may be NULL. */
+int mnav_traffic_stats(const mnav_ctx* ctx, uint32_t* contributing, uint64_t* adds, uint64_t* total_weight, uint32_t* occupied,
+                       uint32_t* peak, uint32_t* built_index, float* ms_kernels, float* ms_total);
+/* The traffic layer, a layer writer like mnav_layer_border.  Per vertex: e = c[v] > free_count ? c[v] - free_count : 0;
+ * cost = 0.0f when e == 0, else fminf((float) e * (float) gain, (float) cap) -- conversions round to nearest, one float
+ * multiply, no contraction.  No vertex is lethal: traffic is a soft cost.  gain must be finite and >= 0, cap >= 0 and not
+ * NaN (+inf: no cap).  changed_out (room for V ids, may be NULL) receives the ascending ids whose cost bits (or lethal
+ * flag) differ from what the slot held, for a fresh slot every vertex; *n_changed their number.  The call reads c as it
+ * stands and does not care whether the fields are stale.  Returns -1 with mnav_last_error set and the slot untouched on
+ * an argument error (no mesh, gain, cap, layer >= 64). */
+int mnav_layer_traffic(mnav_ctx* ctx, uint32_t layer, uint32_t free_count, double gain, double cap, uint32_t* changed_out,
+                       uint32_t* n_changed);
+/* mnav_layer_traffic on an INPUT node of the layer graph, then the propagation, as mnav_map_obstacle does for the obstacle
+ * writer: the layer's change list stays on the device, dependents, vertex costs and edge weights follow, changed_out /
+ * n_changed receive D as in the other update calls, and the replans' change log receives it -- mnav_fleet_paths and
+ * mnav_fleet_traffic refuse the now stale fields until a replan has run.  Refusals: those of the update calls (no computed
+ * graph, the layer is not an input node) and the argument errors above; the graph stays usable after them. */
+int mnav_map_traffic(mnav_ctx* ctx, uint32_t layer, uint32_t free_count, double gain, double cap, uint32_t* changed_out,
+                     uint32_t* n_changed);
 
 /* -- one plan over several GPUs (BASELINE config 4) ---------------------------------------------
  * The reference's loop (dijkstra_mesh_planner.cpp:287-348) on a mesh that is range-partitioned over `world`

@@ -41,6 +41,7 @@ SYMBOLS = [
     "mnav_fleet_paths", "mnav_fleet_walks", "mnav_fleet_stats",
     "mnav_upload_face_normals", "mnav_fleet_plans", "mnav_fleet_walk_plans",
     "mnav_fleet_costs", "mnav_fleet_assign", "mnav_dispatch_stats",
+    "mnav_fleet_traffic", "mnav_traffic_download", "mnav_traffic_stats", "mnav_layer_traffic", "mnav_map_traffic",
     "mnav_set_option", "mnav_get_option", "mnav_shard_set_goal_tie", "mnav_last_engine",
 ]
 
@@ -332,6 +333,15 @@ def load(path: str | None = None):
     L.mnav_fleet_assign.argtypes = [vp, u32, vp, vp, u32, vp, f64] + [vp] * 6
     L.mnav_dispatch_stats.restype = C.c_int
     L.mnav_dispatch_stats.argtypes = [vp] + [vp] * 11
+    L.mnav_fleet_traffic.restype = C.c_int
+    L.mnav_fleet_traffic.argtypes = [vp, u32, vp, vp, vp, vp, C.c_int, vp, vp, vp]
+    L.mnav_traffic_download.restype = C.c_int
+    L.mnav_traffic_download.argtypes = [vp, vp]
+    L.mnav_traffic_stats.restype = C.c_int
+    L.mnav_traffic_stats.argtypes = [vp, C.POINTER(u32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)] + [C.POINTER(u32)] * 3 + [C.POINTER(C.c_float)] * 2
+    for name in ("mnav_layer_traffic", "mnav_map_traffic"):
+        getattr(L, name).restype = C.c_int
+        getattr(L, name).argtypes = [vp, u32, u32, f64, f64, vp, C.POINTER(u32)]
     if path is None:
         _lib = L
     return L
@@ -1219,6 +1229,52 @@ class MnavContext:
                                     C.byref(mt))
         return dict(served=pairs[0], beyond_field=pairs[1], no_path=pairs[2], invalid=pairs[3], feasible=f.value, assigned=a.value, phases=ph.value,
                     rounds=r.value, tail_rounds=tr.value, bids=b.value, built_index=bi.value, ms_costs=mc.value, ms_assign=ma.value, ms_total=mt.value)
+
+    # ---- fleet traffic (mnav_fleet_traffic, mnav_layer_traffic, mnav_map_traffic; include/mnav.h) ----
+    def fleet_traffic(self, slots, start_vertex=None, start_pos=None, weights=None, accumulate: bool = False) -> dict:
+        """Adds the paths of n robots to the context's per-vertex counts (mnav_fleet_traffic): robots as in fleet_paths,
+        weights uint32 per robot (None: 1), accumulate False: the counts start from zero.  Returns dict(codes, vertex,
+        potential) -- fleet_paths' values; the counts stay on the device (traffic_download, traffic_stats)."""
+        sl = _u32(slots).reshape(-1)
+        n = int(sl.shape[0])
+        sv = None if start_vertex is None else _u32(start_vertex).reshape(-1)
+        sp = None if start_pos is None else _f32(start_pos).reshape(-1, 3)
+        w = None if weights is None else _u32(weights).reshape(-1)
+        if (sv is not None and sv.shape[0] != n) or (sv is None and sp is not None and sp.shape[0] != n) or (w is not None and w.shape[0] != n):
+            raise ValueError("fleet_traffic: the per-robot arrays differ in length")
+        codes, vtx, pot = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.float32)
+        if self._L.mnav_fleet_traffic(self._h, n, _p(sl), _p(sv), _p(sp), _p(w), 1 if accumulate else 0, _p(codes), _p(vtx), _p(pot)) != 0:
+            raise RuntimeError(f"mnav_fleet_traffic failed: {self._err()}")
+        return dict(codes=codes, vertex=vtx, potential=pot)
+
+    def traffic_download(self) -> np.ndarray:
+        """the counts: uint32[V]"""
+        c = np.zeros(max(self.V, 1), np.uint32)
+        if self._L.mnav_traffic_download(self._h, _p(c)) != 0:
+            raise RuntimeError(f"mnav_traffic_download failed: {self._err()}")
+        return c[:self.V]
+
+    def traffic_stats(self) -> dict:
+        """The last fleet_traffic that succeeded (mnav_traffic_stats)."""
+        a, t = C.c_uint64(), C.c_uint64()
+        c, o, p, b = (C.c_uint32() for _ in range(4))
+        mk, mt = C.c_float(), C.c_float()
+        self._L.mnav_traffic_stats(self._h, C.byref(c), C.byref(a), C.byref(t), C.byref(o), C.byref(p), C.byref(b), C.byref(mk), C.byref(mt))
+        return dict(contributing=c.value, adds=a.value, total_weight=t.value, occupied=o.value, peak=p.value, built_index=b.value,
+                    ms_kernels=mk.value, ms_total=mt.value)
+
+    def layer_traffic(self, layer: int, free_count: int = 0, gain: float = 1.0, cap: float = np.inf) -> dict:
+        """the traffic layer from the counts as they stand (mnav_layer_traffic): dict(changed = ascending uint32 ids whose
+        cost bits or lethal flag changed)"""
+        changed = np.empty(max(self.V, 1), np.uint32)
+        nc = C.c_uint32()
+        if self._L.mnav_layer_traffic(self._h, int(layer), int(free_count), float(gain), float(cap), _p(changed), C.byref(nc)) != 0:
+            raise RuntimeError(f"mnav_layer_traffic failed: {self._err()}")
+        return dict(changed=changed[:nc.value].copy())
+
+    def map_traffic(self, layer: int, free_count: int = 0, gain: float = 1.0, cap: float = np.inf) -> dict:
+        """layer_traffic on an input node of the graph, then the propagation; same arguments"""
+        return self._map_call("mnav_map_traffic", layer, int(free_count), float(gain), float(cap))
 
     def fleet_stats(self) -> dict:
         """The last fleet_paths / fleet_walks / fleet_plans / fleet_walk_plans call (mnav_fleet_stats; entries: ids, walk entries or poses)."""

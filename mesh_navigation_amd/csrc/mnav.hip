@@ -115,6 +115,7 @@ __global__ __launch_bounds__(64) void k_backtrack(WalkMesh M, WalkInflation L, c
 #include "mnav_fleet.h"      // fleet paths and walks: many robots per resident field (mnav_fleet::; after the locate and follow headers, and after WalkJob)
 #include "mnav_plans.h"      // fleet plans: makePlan's pose lists and costs over those paths and walks (mnav_fleet::, mnav_pose.h)
 #include "mnav_dispatch.h"   // fleet dispatch: the robot-to-goal cost matrix over the resident fields and the auction on it (mnav_dispatch::)
+#include "mnav_traffic.h"    // fleet traffic: path-occupancy counts over the resident fields and the congestion cost layer (mnav_traffic::)
 namespace {
 
 struct Slot {
@@ -232,6 +233,7 @@ struct mnav_ctx {
   mnav_fol::State fol;                                             // vector-field follower: outputs and counters of the last mnav_follow_batch
   mnav_fleet::State fleet;                                         // fleet paths / walks: buffers and statistics of the last mnav_fleet_* call
   mnav_dispatch::State dispatch;                                   // fleet dispatch: the matrix, the auction's state and the statistics of the last mnav_fleet_costs / _assign
+  mnav_traffic::State traffic;                                     // fleet traffic: the V counts, their total and the statistics of the last mnav_fleet_traffic
   mnav_fleet::PlanState plans;                                     // fleet plans: counts, costs, id / length scratch and packed poses of the last call
   DevBuf<float> d_fnrm; bool have_face_normals = false;            // MeshMap::faceNormals() (mnav_upload_face_normals): F x 3, gone with the mesh
   mnav_rol::Dev rol;                                               // device rollout: the rest of the resident robot state and statistics of the last mnav_follow_rollout
@@ -730,6 +732,7 @@ int mnav_upload_mesh(mnav_ctx* ctx, uint32_t V, uint32_t F, uint32_t E, const fl
   ctx->nbhd = {};                                                    // V-sized spill lists
   ctx->clr = {};                                                     // cached clearance: recast lazily
   ctx->chg = {};                                                     // V-sized change list
+  ctx->traffic = {};                                                 // V counts: zero again
   ctx->map = {};                                                     // the layer graph: its slots are gone
   ctx->loc = {};                                                     // vertex index: rebuilt lazily
   ctx->rp = {};                                                      // change log and replan state: the fields are gone with the slots
@@ -1852,6 +1855,7 @@ uint32_t mnav_plan_cvp_batch(mnav_ctx* ctx, uint32_t n, const float* seed_pos, c
 #include "mnav_fleet_capi.h"      // mnav_fleet_paths, mnav_fleet_walks, mnav_fleet_stats
 #include "mnav_plans_capi.h"      // mnav_upload_face_normals, mnav_fleet_plans, mnav_fleet_walk_plans
 #include "mnav_dispatch_capi.h"   // mnav_fleet_costs, mnav_fleet_assign, mnav_dispatch_stats
+#include "mnav_traffic_capi.h"    // mnav_fleet_traffic, mnav_traffic_download, mnav_traffic_stats, mnav_layer_traffic, mnav_map_traffic
 
 void mnav_cancel(mnav_ctx* ctx)
 {
