@@ -832,6 +832,75 @@ int mnav_layer_traffic(mnav_ctx* ctx, uint32_t layer, uint32_t free_count, doubl
 int mnav_map_traffic(mnav_ctx* ctx, uint32_t layer, uint32_t free_count, double gain, double cap, uint32_t* changed_out,
                      uint32_t* n_changed);
 
+/* -- timed fleet traffic: occupancy per (vertex, time window), who holds a cell and who yields --------------
+ * mnav_fleet_traffic has no notion of time: two robots that use a corridor ten minutes apart raise its count as two that
+ * meet in it.  A field stores dist[u] for every vertex of a robot's chain, so dist[v] - dist[u] is how far along its path
+ * the robot is when it reaches u.  The calls below count per (vertex, window), price the PEAK simultaneous use of a vertex
+ * and tell every robot where it meets an over-full cell and whether it has to yield; a caller
+ * staggers departures (depart[i] += tau for the robots that yield) or prices the peaks and replans.  No path id, no
+ * potential and no V-sized array crosses PCIe.
+ *
+ * The context owns V x windows uint32 cells and V x windows uint32 holders (row-major: cell[v * windows + k]), their own
+ * 64-bit total T of the accumulated weight (mnav_fleet_traffic's c, T and statistics are not touched), and per vertex
+ * peak[v] = max_k cell[v][k] and peak_window[v] = the smallest k that attains it (MNAV_NONE when the peak is 0).  After
+ * mnav_upload_mesh the cells are gone: peaks 0, windows MNAV_NONE, T 0.
+ * A call carries `windows` = B windows (1 .. 1024) of width tau (used as (float) tau, finite and > 0); the horizon is
+ * B tau.  Robots, slots, start_vertex / start_pos, weights, code_out, vertex_out, potential_out are exactly those of
+ * mnav_fleet_traffic (stale fields, the lazy look of rule 5 and the 2^32 - 1 total-weight check included).  Per robot,
+ * each may be NULL: depart[i] (NULL: 0; finite and >= 0), pace[i] (NULL: 1; finite and > 0: time per unit of potential --
+ * with edge_cost_factor 0 the potential is metres and pace = 1 / speed), key[i] (NULL: i; the priority, smaller wins).
+ * Robot i CONTRIBUTES iff mnav_fleet_traffic's rule holds and w_i > 0.  A contributor on vertex v with potential P
+ * visits u = v, pred[v], pred[pred[v]], ..., seed: len + 1 visits, one for a robot on the seed.  The window of a visit, all
+ * float32, separate operations, no contraction, correctly rounded division:
+ *   dt = fmaxf(P - dist[u], 0.f);  t = depart_i + dt * pace_i;  q = t / (float) tau;
+ *   in the horizon iff q < (float) B (false for +inf);  k = (uint32_t) q
+ * An in-horizon visit adds w_i to cell[u][k] and lowers holder[u][k] (initially 0xFFFFFFFF) to min(holder, key_i); a visit
+ * beyond the horizon adds nothing and is counted in the statistics.  T grows by the contributors' weights.  Integer sums
+ * and minima do not depend on their order: cells and holders are the same bits in every call, on every schedule, in one
+ * call or in several.  A visit at t >= B tau is dropped, never wrapped into an earlier window: windows do not
+ * alias.
+ * accumulate == 0: cells, holders and T start over -- only after every refusal check has passed; a new (windows, tau)
+ * reallocates.  accumulate != 0: the call adds on top of the last one (n = 0 does nothing); a windows or (float) tau other
+ * than the cells' is refused.
+ * The report is computed after ALL adds of the call, on the cells as they then stand (earlier accumulated calls included).
+ * For each contributor, over its in-horizon visits from v to the seed: a visit is OVER when cell[u][k] > free_count; it
+ * YIELDS when it is over and holder[u][k] != key_i.  conflict_hops_out[i] = the over visits, yield_hops_out[i] = the
+ * yielding visits, first_yield_vertex_out / _window_out / _time_out[i] = u, k and the float t of the first yielding visit
+ * in that order; every other robot, and a contributor without a yielding visit: 0 / 0 / MNAV_NONE / MNAV_NONE / +inf.  Robots
+ * with EQUAL keys in one cell are both its holders: neither yields there.  With free_count > 0 every robot of an over cell
+ * but its holder yields -- more than strictly must, free_count of them could stay; a stagger loop still converges because
+ * each round counts again.  Any output may be NULL.
+ * Returns 0, or -1 with mnav_last_error set and NOTHING touched (cells, holders, T, outputs and statistics included):
+ * everything mnav_fleet_traffic refuses; windows outside 1 .. 1024; a tau that is not finite and positive as a float; a
+ * depart that is not finite or is negative; a pace that is not finite or is <= 0 (both checked on the host over all n robots
+ * before the first device call); the configuration mismatch under accumulate; 8 V windows bytes above the option
+ * timed_traffic_max_mb MiB (default 2048).  mnav_fleet_stats and mnav_traffic_stats keep their values. */
+int mnav_fleet_timed_traffic(mnav_ctx* ctx, uint32_t n, const uint32_t* slots, const uint32_t* start_vertex, const float* start_pos,
+                             const uint32_t* weights, const float* depart, const float* pace, const uint32_t* key, uint32_t windows,
+                             double tau, uint32_t free_count, int accumulate, uint32_t* code_out, uint32_t* vertex_out,
+                             float* potential_out, uint32_t* conflict_hops_out, uint32_t* yield_hops_out,
+                             uint32_t* first_yield_vertex_out, uint32_t* first_yield_window_out, float* first_yield_time_out);
+/* peak_out and window_out: V words each; cells_out and holders_out: V x windows words each, row-major, windows = that of
+ * the last call (mnav_timed_traffic_stats).  Any may be NULL.  No timed call since mnav_upload_mesh: peaks 0, windows
+ * MNAV_NONE, and there are no cells (nothing is written to cells_out / holders_out).  -1: no mesh. */
+int mnav_timed_traffic_download(const mnav_ctx* ctx, uint32_t* peak_out, uint32_t* window_out, uint32_t* cells_out,
+                                uint32_t* holders_out);
+/* The last mnav_fleet_timed_traffic that returned 0: contributing robots, in-horizon adds, visits beyond the horizon, T;
+ * after the call the cells above 0, the cells above its free_count and the largest cell; the robots with yield_hops > 0;
+ * its windows; built_index = 1 if the call built the lookup index; device milliseconds of its kernels and host milliseconds
+ * of the whole call.  Any pointer may be NULL. */
+int mnav_timed_traffic_stats(const mnav_ctx* ctx, uint32_t* contributing, uint64_t* adds, uint64_t* beyond_horizon,
+                             uint64_t* total_weight, uint64_t* occupied_cells, uint64_t* over_cells, uint32_t* largest_cell,
+                             uint32_t* yielding, uint32_t* windows, uint32_t* built_index, float* ms_kernels, float* ms_total);
+/* mnav_layer_traffic's rule on the peaks: cost = traffic cost of (peak[v], free_count, gain, cap), never lethal; the same
+ * arguments, change list and argument checks.  It reads the peaks as they stand (all zero before the first timed call). */
+int mnav_layer_timed_traffic(mnav_ctx* ctx, uint32_t layer, uint32_t free_count, double gain, double cap, uint32_t* changed_out,
+                             uint32_t* n_changed);
+/* mnav_layer_timed_traffic on an INPUT node of the layer graph, then the propagation: to it what mnav_map_traffic is to
+ * mnav_layer_traffic (the list stays on the device, the replans' change log is written, the same refusals). */
+int mnav_map_timed_traffic(mnav_ctx* ctx, uint32_t layer, uint32_t free_count, double gain, double cap, uint32_t* changed_out,
+                           uint32_t* n_changed);
+
 /* -- one plan over several GPUs (BASELINE config 4) ---------------------------------------------
  * The reference's loop (dijkstra_mesh_planner.cpp:287-348) on a mesh that is range-partitioned over `world`
  * processes, one per GPU: the LDS tiles are in Morton order and process `rank` owns a contiguous range of them.

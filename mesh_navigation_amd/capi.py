@@ -42,6 +42,7 @@ SYMBOLS = [
     "mnav_upload_face_normals", "mnav_fleet_plans", "mnav_fleet_walk_plans",
     "mnav_fleet_costs", "mnav_fleet_assign", "mnav_dispatch_stats",
     "mnav_fleet_traffic", "mnav_traffic_download", "mnav_traffic_stats", "mnav_layer_traffic", "mnav_map_traffic",
+    "mnav_fleet_timed_traffic", "mnav_timed_traffic_download", "mnav_timed_traffic_stats", "mnav_layer_timed_traffic", "mnav_map_timed_traffic",
     "mnav_set_option", "mnav_get_option", "mnav_shard_set_goal_tie", "mnav_last_engine",
 ]
 
@@ -339,7 +340,13 @@ def load(path: str | None = None):
     L.mnav_traffic_download.argtypes = [vp, vp]
     L.mnav_traffic_stats.restype = C.c_int
     L.mnav_traffic_stats.argtypes = [vp, C.POINTER(u32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)] + [C.POINTER(u32)] * 3 + [C.POINTER(C.c_float)] * 2
-    for name in ("mnav_layer_traffic", "mnav_map_traffic"):
+    L.mnav_fleet_timed_traffic.restype = C.c_int
+    L.mnav_fleet_timed_traffic.argtypes = [vp, u32] + [vp] * 7 + [u32, f64, u32, C.c_int] + [vp] * 8
+    L.mnav_timed_traffic_download.restype = C.c_int
+    L.mnav_timed_traffic_download.argtypes = [vp] * 5
+    L.mnav_timed_traffic_stats.restype = C.c_int
+    L.mnav_timed_traffic_stats.argtypes = [vp, C.POINTER(u32)] + [C.POINTER(C.c_uint64)] * 5 + [C.POINTER(u32)] * 4 + [C.POINTER(C.c_float)] * 2
+    for name in ("mnav_layer_traffic", "mnav_map_traffic", "mnav_layer_timed_traffic", "mnav_map_timed_traffic"):
         getattr(L, name).restype = C.c_int
         getattr(L, name).argtypes = [vp, u32, u32, f64, f64, vp, C.POINTER(u32)]
     if path is None:
@@ -1275,6 +1282,64 @@ class MnavContext:
     def map_traffic(self, layer: int, free_count: int = 0, gain: float = 1.0, cap: float = np.inf) -> dict:
         """layer_traffic on an input node of the graph, then the propagation; same arguments"""
         return self._map_call("mnav_map_traffic", layer, int(free_count), float(gain), float(cap))
+
+    # ---- timed fleet traffic (mnav_fleet_timed_traffic, mnav_layer_timed_traffic, mnav_map_timed_traffic; include/mnav.h) ----
+    def fleet_timed_traffic(self, slots, start_vertex=None, start_pos=None, weights=None, depart=None, pace=None, key=None, windows: int = 64,
+                            tau: float = 1.0, free_count: int = 0, accumulate: bool = False) -> dict:
+        """Adds the paths of n robots to the context's cells per (vertex, time window) and reports who yields
+        (mnav_fleet_timed_traffic): robots and weights as in fleet_traffic; per robot depart (float32, None: 0), pace (float32,
+        None: 1) and key (uint32, None: the index; smaller wins).  Returns dict(codes, vertex, potential, conflict_hops,
+        yield_hops, first_yield_vertex, first_yield_window, first_yield_time); the cells stay on the device
+        (timed_traffic_download, timed_traffic_stats)."""
+        sl = _u32(slots).reshape(-1)
+        n = int(sl.shape[0])
+        sv = None if start_vertex is None else _u32(start_vertex).reshape(-1)
+        sp = None if start_pos is None else _f32(start_pos).reshape(-1, 3)
+        w, ky = (None if a is None else _u32(a).reshape(-1) for a in (weights, key))
+        dp, pc = (None if a is None else _f32(a).reshape(-1) for a in (depart, pace))
+        if (sv is not None and sv.shape[0] != n) or (sv is None and sp is not None and sp.shape[0] != n) or any(a is not None and a.shape[0] != n for a in (w, ky, dp, pc)):
+            raise ValueError("fleet_timed_traffic: the per-robot arrays differ in length")
+        codes, vtx, conflict, yld, fv, fw = (np.zeros(n, np.uint32) for _ in range(6))
+        pot, ft = np.zeros(n, np.float32), np.zeros(n, np.float32)
+        if self._L.mnav_fleet_timed_traffic(self._h, n, _p(sl), _p(sv), _p(sp), _p(w), _p(dp), _p(pc), _p(ky), int(windows), float(tau), int(free_count),
+                                            1 if accumulate else 0, _p(codes), _p(vtx), _p(pot), _p(conflict), _p(yld), _p(fv), _p(fw), _p(ft)) != 0:
+            raise RuntimeError(f"mnav_fleet_timed_traffic failed: {self._err()}")
+        return dict(codes=codes, vertex=vtx, potential=pot, conflict_hops=conflict, yield_hops=yld, first_yield_vertex=fv, first_yield_window=fw,
+                    first_yield_time=ft)
+
+    def timed_traffic_download(self, want_cells: bool = True) -> dict:
+        """dict(peak uint32[V], window uint32[V], cells and holders uint32[V, windows] (None without want_cells)); windows =
+        timed_traffic_stats()["windows"], 0 when no timed call has run since upload_mesh"""
+        B = self.timed_traffic_stats()["windows"]
+        peak, window = np.zeros(max(self.V, 1), np.uint32), np.zeros(max(self.V, 1), np.uint32)
+        cells = np.zeros((self.V, B), np.uint32) if want_cells else None
+        holders = np.zeros((self.V, B), np.uint32) if want_cells else None
+        if self._L.mnav_timed_traffic_download(self._h, _p(peak), _p(window), _p(cells), _p(holders)) != 0:
+            raise RuntimeError(f"mnav_timed_traffic_download failed: {self._err()}")
+        return dict(peak=peak[:self.V], window=window[:self.V], cells=cells, holders=holders)
+
+    def timed_traffic_stats(self) -> dict:
+        """The last fleet_timed_traffic that succeeded (mnav_timed_traffic_stats)."""
+        a, bh, t, oc, ov = (C.c_uint64() for _ in range(5))
+        c, lg, y, w, b = (C.c_uint32() for _ in range(5))
+        mk, mt = C.c_float(), C.c_float()
+        self._L.mnav_timed_traffic_stats(self._h, C.byref(c), C.byref(a), C.byref(bh), C.byref(t), C.byref(oc), C.byref(ov), C.byref(lg), C.byref(y), C.byref(w),
+                                         C.byref(b), C.byref(mk), C.byref(mt))
+        return dict(contributing=c.value, adds=a.value, beyond_horizon=bh.value, total_weight=t.value, occupied_cells=oc.value, over_cells=ov.value,
+                    largest_cell=lg.value, yielding=y.value, windows=w.value, built_index=b.value, ms_kernels=mk.value, ms_total=mt.value)
+
+    def layer_timed_traffic(self, layer: int, free_count: int = 0, gain: float = 1.0, cap: float = np.inf) -> dict:
+        """the traffic rule on the peaks as they stand (mnav_layer_timed_traffic): dict(changed = ascending uint32 ids whose
+        cost bits or lethal flag changed)"""
+        changed = np.empty(max(self.V, 1), np.uint32)
+        nc = C.c_uint32()
+        if self._L.mnav_layer_timed_traffic(self._h, int(layer), int(free_count), float(gain), float(cap), _p(changed), C.byref(nc)) != 0:
+            raise RuntimeError(f"mnav_layer_timed_traffic failed: {self._err()}")
+        return dict(changed=changed[:nc.value].copy())
+
+    def map_timed_traffic(self, layer: int, free_count: int = 0, gain: float = 1.0, cap: float = np.inf) -> dict:
+        """layer_timed_traffic on an input node of the graph, then the propagation; same arguments"""
+        return self._map_call("mnav_map_timed_traffic", layer, int(free_count), float(gain), float(cap))
 
     def fleet_stats(self) -> dict:
         """The last fleet_paths / fleet_walks / fleet_plans / fleet_walk_plans call (mnav_fleet_stats; entries: ids, walk entries or poses)."""

@@ -116,6 +116,7 @@ __global__ __launch_bounds__(64) void k_backtrack(WalkMesh M, WalkInflation L, c
 #include "mnav_plans.h"      // fleet plans: makePlan's pose lists and costs over those paths and walks (mnav_fleet::, mnav_pose.h)
 #include "mnav_dispatch.h"   // fleet dispatch: the robot-to-goal cost matrix over the resident fields and the auction on it (mnav_dispatch::)
 #include "mnav_traffic.h"    // fleet traffic: path-occupancy counts over the resident fields and the congestion cost layer (mnav_traffic::)
+#include "mnav_timed.h"      // timed fleet traffic: occupancy per (vertex, time window), holders and the yield report (mnav_timed::)
 namespace {
 
 struct Slot {
@@ -234,6 +235,7 @@ struct mnav_ctx {
   mnav_fleet::State fleet;                                         // fleet paths / walks: buffers and statistics of the last mnav_fleet_* call
   mnav_dispatch::State dispatch;                                   // fleet dispatch: the matrix, the auction's state and the statistics of the last mnav_fleet_costs / _assign
   mnav_traffic::State traffic;                                     // fleet traffic: the V counts, their total and the statistics of the last mnav_fleet_traffic
+  mnav_timed::State timed;                                         // timed fleet traffic: the V x B cells and holders, the peaks and the statistics of the last mnav_fleet_timed_traffic
   mnav_fleet::PlanState plans;                                     // fleet plans: counts, costs, id / length scratch and packed poses of the last call
   DevBuf<float> d_fnrm; bool have_face_normals = false;            // MeshMap::faceNormals() (mnav_upload_face_normals): F x 3, gone with the mesh
   mnav_rol::Dev rol;                                               // device rollout: the rest of the resident robot state and statistics of the last mnav_follow_rollout
@@ -733,6 +735,7 @@ int mnav_upload_mesh(mnav_ctx* ctx, uint32_t V, uint32_t F, uint32_t E, const fl
   ctx->clr = {};                                                     // cached clearance: recast lazily
   ctx->chg = {};                                                     // V-sized change list
   ctx->traffic = {};                                                 // V counts: zero again
+  ctx->timed = {};                                                   // V x B cells and holders, V peaks: gone
   ctx->map = {};                                                     // the layer graph: its slots are gone
   ctx->loc = {};                                                     // vertex index: rebuilt lazily
   ctx->rp = {};                                                      // change log and replan state: the fields are gone with the slots
@@ -1856,6 +1859,7 @@ uint32_t mnav_plan_cvp_batch(mnav_ctx* ctx, uint32_t n, const float* seed_pos, c
 #include "mnav_plans_capi.h"      // mnav_upload_face_normals, mnav_fleet_plans, mnav_fleet_walk_plans
 #include "mnav_dispatch_capi.h"   // mnav_fleet_costs, mnav_fleet_assign, mnav_dispatch_stats
 #include "mnav_traffic_capi.h"    // mnav_fleet_traffic, mnav_traffic_download, mnav_traffic_stats, mnav_layer_traffic, mnav_map_traffic
+#include "mnav_timed_capi.h"      // mnav_fleet_timed_traffic, mnav_timed_traffic_download, mnav_timed_traffic_stats, mnav_layer_timed_traffic, mnav_map_timed_traffic
 
 void mnav_cancel(mnav_ctx* ctx)
 {
