@@ -1018,14 +1018,18 @@ int mnav_backtrack_cvp(mnav_ctx* ctx, const float seed_pos[3], uint32_t seed_fac
  * what = 0 dist, 1 pred, 2 direction, 3 cutface, 4 vecmap.  NULL if not available -- in particular dist / pred after a
  * paths-only Dijkstra call (no dist_out / pred_out / vector map asked for): such a call runs no finalize pass, values
  * beyond goal_dist would be engine-tentative.  mnav_download_output additionally takes what = 5, the POPPED potential of
- * a Dijkstra plan: the reference's value wherever it popped the vertex (dist <= goal_dist), +inf elsewhere. */
+ * a Dijkstra plan: the reference's value wherever it popped the vertex (dist <= goal_dist), +inf elsewhere.
+ * After a new mnav_upload_mesh and until the next plan call every output of the old mesh is gone: mnav_device_output
+ * returns NULL and mnav_download_output returns -1 with "output not resident", for what = 5 as for the others, before
+ * anything is allocated or launched. */
 const void* mnav_device_output(const mnav_ctx* ctx, uint32_t slot, int what);
 /* Algorithmic bytes of the last call per SURVEY.md §8(d): SSSP 24*V' + 24*E', CVP 32*V' + 68*F'
  * with V' = settled vertices and E'/F' their incident edges/faces scaled from the full mesh. */
 uint64_t mnav_algorithmic_bytes(const mnav_ctx* ctx);
 /* Which engine / kernel ran the last Dijkstra call (for reports and profiles): the engine of mnav_set_dijkstra_engine that `auto`
  * resolved to (0, 1, 5, 6), + 16 when the tile-batch engine (5) solved its tiles with the register-resident kernel k_tbv_solve
- * (64 plans per wave, distances in VGPRs) instead of k_tb_solve_q (16 plans per quarter of a wave, distances in LDS).  -1: none. */
+ * (64 plans per wave, distances in VGPRs) instead of k_tb_solve_q (16 plans per quarter of a wave, distances in LDS).  -1: none
+ * (no Dijkstra call yet, none whose plans reached the device, or a new mnav_upload_mesh since). */
 int mnav_last_engine(const mnav_ctx* ctx);
 
 #ifdef __cplusplus

@@ -151,6 +151,7 @@ struct mnav_ctx {
   std::vector<uint32_t> h_row_ptr, h_nbr_u;   // gather CSR (host copy): the tile-batch engine builds its streams from it on first use
   TbState tb; tb::Args tb_args{};             // tile-batch SSSP engine (mnav_tb.h); arguments of the last batch
   bool tb_args_valid = false;                 // ... which still describe live device memory (last tile-batch call succeeded, nothing freed since)
+  bool mesh_since_outputs = false;            // mnav_upload_mesh ran since the last plan call began its outputs: mnav_last_engine names no engine
   bool want_vec = false;               // parameter of the RUNNING call: it asked for vector maps (lazy 12 B/vertex/plan).  What the outputs
                                        // left behind hold is the record's to say (ctx->res)
   bool resident_vecmap = false;        // mnav_set_resident_outputs: always compute the vector map, leave it on the device
@@ -630,6 +631,7 @@ void resident_outputs_begin(mnav_ctx* ctx)
 {
   ctx->shard.finalized = false; ctx->tb.count_pending = false; ctx->tb_args_valid = false;
   ctx->rp.each_engines = 0; ctx->rp.warm.live = false;
+  ctx->mesh_since_outputs = false;
 }
 // A Dijkstra call or a repair committed (ctx->res.commit_dijkstra / repair_commit): the change log starts over.
 void resident_outputs_commit(mnav_ctx* ctx) { ctx->rp.len = 0; ctx->rp.all = false; }
@@ -726,7 +728,7 @@ int mnav_upload_mesh(mnav_ctx* ctx, uint32_t V, uint32_t F, uint32_t E, const fl
   catch (const std::exception& ex) { ctx->err = ex.what(); return -2; }
   (void)hipStreamSynchronize(ctx->stream);
   // V-, E- and F-sized state of the old mesh
-  ctx->slots.clear();
+  ctx->slots.clear(); ctx->mesh_since_outputs = true;
   ctx->rp.log.reset(); ctx->rp.len = 0; ctx->rp.all = false; ctx->res.mesh_replaced();   // (the log is V-sized; the recorded seeds are the old mesh's)
   ctx->layers.clear();
   ctx->d_crn_infl.reset(); ctx->d_infl_mask.reset(); ctx->d_zero_u8.reset(); ctx->d_infl_keyd.reset(); ctx->crn_infl_valid = false;
@@ -1969,12 +1971,14 @@ int mnav_download_output(mnav_ctx* ctx, uint32_t slot, int what, void* host_out)
     if (!ctx->res.dijkstra_family()) { ctx->err = "popped potential: the last call was not a Dijkstra plan"; return -1; }
     slot = ctx->res.slot_or_raw(slot);
     if (slot >= ctx->res.live()) { ctx->err = "output not resident"; return -1; }
+    // The record keeps its live count through mnav_upload_mesh, the memory is gone with the old mesh: a paths-only tile-batch
+    // call left its distances in the engine's buffers (no plan slot), every other call in slots[slot].dist
+    const bool tb_paths_only = ctx->last_engine == 5 && ctx->res.paths_only();
+    if (tb_paths_only ? !ctx->tb_args_valid : slot >= ctx->slots.size()) { ctx->err = "output not resident"; return -1; }
     if (hipSetDevice(ctx->device) != hipSuccess) return -1;
     DevBuf<float> tmp;
     HIPCHK(tmp.alloc(4 * (size_t)(ctx->V ? ctx->V : 1)));
     const uint32_t g = std::min<uint32_t>((ctx->V + kBlock - 1) / kBlock + 1, 4096);
-    const bool tb_paths_only = ctx->last_engine == 5 && ctx->res.paths_only();
-    if (tb_paths_only && !ctx->tb_args_valid) { ctx->err = "output not resident"; return -1; }
     if (tb_paths_only) hipLaunchKernelGGL(k_tb_popped, dim3(g), dim3(kBlock), 0, ctx->stream, ctx->tb_args, slot, ctx->V, tmp);
     else hipLaunchKernelGGL(k_popped, dim3(g), dim3(kBlock), 0, ctx->stream, ctx->slots[slot].dist, ctx->res.robot_vertex(slot), ctx->res.offset(), ctx->V, tmp);
     const hipError_t e1 = hipMemcpyAsync(host_out, tmp, 4 * (size_t)ctx->V, hipMemcpyDeviceToHost, ctx->stream);
@@ -2124,6 +2128,7 @@ uint64_t mnav_algorithmic_bytes(const mnav_ctx* ctx)
 int mnav_last_engine(const mnav_ctx* ctx)
 {
   if (!ctx || !ctx->res.dijkstra_family() || ctx->res.live() == 0) return -1;
+  if (ctx->mesh_since_outputs) return -1;                             // a new mesh since the call: its fields are gone, the record's live count is not
   if (ctx->rp.each_engines) return ctx->rp.each_engines;
   return ctx->last_engine + ((ctx->last_engine == 5 && ctx->tb.kernel == 1) ? 16 : 0);
 }
