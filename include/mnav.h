@@ -901,6 +901,65 @@ int mnav_layer_timed_traffic(mnav_ctx* ctx, uint32_t layer, uint32_t free_count,
 int mnav_map_timed_traffic(mnav_ctx* ctx, uint32_t layer, uint32_t free_count, double gain, double cap, uint32_t* changed_out,
                            uint32_t* n_changed);
 
+/* -- fleet schedule: a departure delay per robot such that no (vertex, window) cell is over capacity -----
+ * mnav_fleet_timed_traffic diagnoses: it counts, names a holder and tells every robot whether it yields.  This call is the
+ * cure: given the same robots, windows and a capacity it returns a delay per robot, in whole
+ * windows, such that no constrained cell exceeds `capacity`, and names the robots that cannot be fitted into the horizon.
+ * Robots, slots, start_vertex / start_pos, weights, depart, pace, key, windows = B, tau, accumulate, code_out, vertex_out,
+ * potential_out, the defaults, the contributor rule and the float32 window arithmetic are exactly those of
+ * mnav_fleet_timed_traffic.  capacity >= 1 plays the role free_count plays in the report; max_delay (0 .. B - 1) is in
+ * whole windows; max_rounds = 0 means no limit; flags: MNAV_SCHEDULE_SEED_FREE or 0.
+ * A contributor i tries delay d with depart_d = depart_i + (float) d * (float) tau (one multiply, then one add, no
+ * contraction: d = 0 gives depart_i bit for bit).  Its visits then fall at t = depart_d + fmaxf(P - dist[u], 0) * pace_i
+ * into the window of t.  Candidate d FITS iff every visit lies inside the horizon -- a schedule does not commit a robot to a
+ * trip it cannot see the end of -- and every CONSTRAINED visit has cell[u][k] + w_i <= capacity.  Every visit is
+ * constrained; with MNAV_SCHEDULE_SEED_FREE the last one, on the seed, is not (arrivals at a goal or depot are not
+ * rationed, but they are still counted on commit).  A robot with w_i > capacity never fits.
+ * Rounds r = 1, 2, ... on the committed cells and a current delay cur per robot (0 at the start):
+ *   probe   every OPEN robot takes the smallest d in [cur, max_delay] that fits the cells as they stand at the start of
+ *           the round and sets cur = d; none fits: MNAV_SCHEDULE_NO_SLOT, for good (cells only grow)
+ *   claim   every robot that found a d adds w_i to a tentative count of each constrained visit's cell and lowers the cell's
+ *           tentative holder to (key_i, i), ordered lexicographically: equal keys are broken by the smaller index
+ *   decide  a robot WINS iff for every constrained visit cell + tentative <= capacity or the tentative holder is the robot
+ *   commit  every winner is MNAV_SCHEDULE_COMMITTED with delay d in round r: ALL its visits (the seed's too) add w_i to
+ *           cell[u][k] and lower holder[u][k] to key_i, T grows by w_i; losers stay OPEN and probe again from cur
+ * until nobody is OPEN or r == max_rounds (robots still OPEN then report MNAV_SCHEDULE_OPEN).  With flags = 0 and
+ * accumulate = 0 no cell exceeds capacity; every round with an OPEN robot that found a delay commits at least the one with
+ * the smallest (key, index), so the loop ends within n rounds; sums and minima of integers do not depend on their order, so
+ * outputs and cells are the same bits on every run, with any schedule_chunk_rounds and either schedule_clean_fill.
+ * NOT claimed: the result is not the sequential "robots in key order" greedy schedule -- the rule above is its own
+ * definition; and two accumulating calls over two halves of a fleet are not one call over the whole fleet, unlike counting.
+ * The cells ARE the timed cells: the call writes the context's cells, holders, T, windows and tau and ends with the peak
+ * pass at free_count = capacity, so mnav_timed_traffic_download, mnav_layer_timed_traffic and mnav_map_timed_traffic see the
+ * schedule.  accumulate has mnav_fleet_timed_traffic's meaning: existing cells count as reservations, whoever made them
+ * (robots under way counted by a timed call, or an earlier schedule); cells already above capacity are simply blocked.
+ * mnav_timed_traffic_stats afterwards describes the cells as if the committed robots had been a timed call's
+ * contributors: contributing = the committed robots, adds = their visits, beyond_horizon = 0, yielding = 0, total_weight =
+ * T, occupied / over (above capacity) / largest from the peak pass, windows = B.
+ * Per robot, each may be NULL: status_out (MNAV_SCHEDULE_NONE for a robot that does not contribute); delay_out and
+ * round_out (MNAV_NONE unless committed); depart_out = depart_d of the committed delay, else +inf.
+ * Returns 0, or -1 with mnav_last_error set and NOTHING touched (cells, outputs, statistics): everything
+ * mnav_fleet_timed_traffic refuses; capacity == 0; max_delay >= windows; an unknown flag bit; 20 V windows bytes (cells,
+ * holders and the call's tentative arrays) above the option timed_traffic_max_mb.  n = 0 behaves as in the timed call.
+ * mnav_fleet_stats and mnav_traffic_stats keep their values. */
+#define MNAV_SCHEDULE_NONE 0u
+#define MNAV_SCHEDULE_COMMITTED 1u
+#define MNAV_SCHEDULE_NO_SLOT 2u
+#define MNAV_SCHEDULE_OPEN 3u
+#define MNAV_SCHEDULE_SEED_FREE 1u
+int mnav_fleet_schedule(mnav_ctx* ctx, uint32_t n, const uint32_t* slots, const uint32_t* start_vertex, const float* start_pos,
+                        const uint32_t* weights, const float* depart, const float* pace, const uint32_t* key, uint32_t windows,
+                        double tau, uint32_t capacity, uint32_t max_delay, uint32_t max_rounds, uint32_t flags, int accumulate,
+                        uint32_t* code_out, uint32_t* vertex_out, float* potential_out, uint32_t* status_out, uint32_t* delay_out,
+                        float* depart_out, uint32_t* round_out);
+/* The last mnav_fleet_schedule that returned 0: contributing, committed, NO_SLOT and still OPEN robots; the rounds that ran;
+ * the committed robots with a delay above 0 and the largest committed delay; claims = the sum over the rounds of the robots
+ * that claimed; the visits of the committed robots; built_index = 1 if the call built the lookup index; device milliseconds
+ * of its kernels and host milliseconds of the whole call.  Any pointer may be NULL. */
+int mnav_schedule_stats(const mnav_ctx* ctx, uint32_t* contributing, uint32_t* committed, uint32_t* no_slot, uint32_t* open,
+                        uint32_t* rounds, uint32_t* delayed, uint32_t* max_delay_used, uint64_t* claims, uint64_t* committed_visits,
+                        uint32_t* built_index, float* ms_kernels, float* ms_total);
+
 /* -- one plan over several GPUs (BASELINE config 4) ---------------------------------------------
  * The reference's loop (dijkstra_mesh_planner.cpp:287-348) on a mesh that is range-partitioned over `world`
  * processes, one per GPU: the LDS tiles are in Morton order and process `rank` owns a contiguous range of them.

@@ -18,6 +18,8 @@ from . import build as _build
 
 NONE = 0xFFFFFFFF
 SUCCESS, CANCELED, INVALID_START, INVALID_GOAL, NO_PATH_FOUND, INTERNAL_ERROR = 0, 51, 52, 53, 54, 60
+SCHEDULE_NONE, SCHEDULE_COMMITTED, SCHEDULE_NO_SLOT, SCHEDULE_OPEN = 0, 1, 2, 3     # mnav_fleet_schedule: status per robot
+SCHEDULE_SEED_FREE = 1      # mnav_fleet_schedule: flag bit 0
 BEYOND_FIELD = 70           # mnav_fleet_paths: the resident field cannot answer for this robot
 WALK_NO_FACE = -3           # mnav_fleet_walks: no face at the start
 
@@ -43,6 +45,7 @@ SYMBOLS = [
     "mnav_fleet_costs", "mnav_fleet_assign", "mnav_dispatch_stats",
     "mnav_fleet_traffic", "mnav_traffic_download", "mnav_traffic_stats", "mnav_layer_traffic", "mnav_map_traffic",
     "mnav_fleet_timed_traffic", "mnav_timed_traffic_download", "mnav_timed_traffic_stats", "mnav_layer_timed_traffic", "mnav_map_timed_traffic",
+    "mnav_fleet_schedule", "mnav_schedule_stats",
     "mnav_set_option", "mnav_get_option", "mnav_shard_set_goal_tie", "mnav_last_engine",
 ]
 
@@ -346,6 +349,10 @@ def load(path: str | None = None):
     L.mnav_timed_traffic_download.argtypes = [vp] * 5
     L.mnav_timed_traffic_stats.restype = C.c_int
     L.mnav_timed_traffic_stats.argtypes = [vp, C.POINTER(u32)] + [C.POINTER(C.c_uint64)] * 5 + [C.POINTER(u32)] * 4 + [C.POINTER(C.c_float)] * 2
+    L.mnav_fleet_schedule.restype = C.c_int
+    L.mnav_fleet_schedule.argtypes = [vp, u32] + [vp] * 7 + [u32, f64] + [u32] * 4 + [C.c_int] + [vp] * 7
+    L.mnav_schedule_stats.restype = C.c_int
+    L.mnav_schedule_stats.argtypes = [vp] + [C.POINTER(u32)] * 7 + [C.POINTER(C.c_uint64)] * 2 + [C.POINTER(u32)] + [C.POINTER(C.c_float)] * 2
     for name in ("mnav_layer_traffic", "mnav_map_traffic", "mnav_layer_timed_traffic", "mnav_map_timed_traffic"):
         getattr(L, name).restype = C.c_int
         getattr(L, name).argtypes = [vp, u32, u32, f64, f64, vp, C.POINTER(u32)]
@@ -1340,6 +1347,39 @@ class MnavContext:
     def map_timed_traffic(self, layer: int, free_count: int = 0, gain: float = 1.0, cap: float = np.inf) -> dict:
         """layer_timed_traffic on an input node of the graph, then the propagation; same arguments"""
         return self._map_call("mnav_map_timed_traffic", layer, int(free_count), float(gain), float(cap))
+
+    # ---- fleet schedule (mnav_fleet_schedule, mnav_schedule_stats; include/mnav.h) ----
+    def fleet_schedule(self, slots, start_vertex=None, start_pos=None, weights=None, depart=None, pace=None, key=None, windows: int = 64,
+                       tau: float = 1.0, capacity: int = 1, max_delay: int = 0, max_rounds: int = 0, flags: int = 0, accumulate: bool = False) -> dict:
+        """A departure delay per robot, in whole windows, such that no (vertex, window) cell holds more than `capacity`
+        (mnav_fleet_schedule): the robots and their arrays are those of fleet_timed_traffic; max_delay in 0 .. windows - 1,
+        max_rounds 0: no limit, flags: SCHEDULE_SEED_FREE or 0.  Returns dict(codes, vertex, potential, status, delay,
+        depart (the committed departure, +inf otherwise), round); the cells are the timed cells (timed_traffic_download,
+        timed_traffic_stats), the call's own figures are schedule_stats()."""
+        sl = _u32(slots).reshape(-1)
+        n = int(sl.shape[0])
+        sv = None if start_vertex is None else _u32(start_vertex).reshape(-1)
+        sp = None if start_pos is None else _f32(start_pos).reshape(-1, 3)
+        w, ky = (None if a is None else _u32(a).reshape(-1) for a in (weights, key))
+        dp, pc = (None if a is None else _f32(a).reshape(-1) for a in (depart, pace))
+        if (sv is not None and sv.shape[0] != n) or (sv is None and sp is not None and sp.shape[0] != n) or any(a is not None and a.shape[0] != n for a in (w, ky, dp, pc)):
+            raise ValueError("fleet_schedule: the per-robot arrays differ in length")
+        codes, vtx, status, delay, rnd = (np.zeros(n, np.uint32) for _ in range(5))
+        pot, out = np.zeros(n, np.float32), np.zeros(n, np.float32)
+        if self._L.mnav_fleet_schedule(self._h, n, _p(sl), _p(sv), _p(sp), _p(w), _p(dp), _p(pc), _p(ky), int(windows), float(tau), int(capacity), int(max_delay),
+                                       int(max_rounds), int(flags), 1 if accumulate else 0, _p(codes), _p(vtx), _p(pot), _p(status), _p(delay), _p(out), _p(rnd)) != 0:
+            raise RuntimeError(f"mnav_fleet_schedule failed: {self._err()}")
+        return dict(codes=codes, vertex=vtx, potential=pot, status=status, delay=delay, depart=out, round=rnd)
+
+    def schedule_stats(self) -> dict:
+        """The last fleet_schedule that succeeded (mnav_schedule_stats)."""
+        v = [C.c_uint32() for _ in range(7)]
+        cl, cv = C.c_uint64(), C.c_uint64()
+        b = C.c_uint32()
+        mk, mt = C.c_float(), C.c_float()
+        self._L.mnav_schedule_stats(self._h, *[C.byref(x) for x in v], C.byref(cl), C.byref(cv), C.byref(b), C.byref(mk), C.byref(mt))
+        names = ("contributing", "committed", "no_slot", "open", "rounds", "delayed", "max_delay_used")
+        return dict({k: x.value for k, x in zip(names, v)}, claims=cl.value, committed_visits=cv.value, built_index=b.value, ms_kernels=mk.value, ms_total=mt.value)
 
     def fleet_stats(self) -> dict:
         """The last fleet_paths / fleet_walks / fleet_plans / fleet_walk_plans call (mnav_fleet_stats; entries: ids, walk entries or poses)."""

@@ -117,6 +117,7 @@ __global__ __launch_bounds__(64) void k_backtrack(WalkMesh M, WalkInflation L, c
 #include "mnav_dispatch.h"   // fleet dispatch: the robot-to-goal cost matrix over the resident fields and the auction on it (mnav_dispatch::)
 #include "mnav_traffic.h"    // fleet traffic: path-occupancy counts over the resident fields and the congestion cost layer (mnav_traffic::)
 #include "mnav_timed.h"      // timed fleet traffic: occupancy per (vertex, time window), holders and the yield report (mnav_timed::)
+#include "mnav_schedule.h"   // fleet schedule: conflict-free departure delays on the timed cells, round by round (mnav_schedule::)
 namespace {
 
 struct Slot {
@@ -237,6 +238,7 @@ struct mnav_ctx {
   mnav_dispatch::State dispatch;                                   // fleet dispatch: the matrix, the auction's state and the statistics of the last mnav_fleet_costs / _assign
   mnav_traffic::State traffic;                                     // fleet traffic: the V counts, their total and the statistics of the last mnav_fleet_traffic
   mnav_timed::State timed;                                         // timed fleet traffic: the V x B cells and holders, the peaks and the statistics of the last mnav_fleet_timed_traffic
+  mnav_schedule::State schedule;                                   // fleet schedule: the V x B tentative counts and holders, the control record and the statistics of the last mnav_fleet_schedule
   mnav_fleet::PlanState plans;                                     // fleet plans: counts, costs, id / length scratch and packed poses of the last call
   DevBuf<float> d_fnrm; bool have_face_normals = false;            // MeshMap::faceNormals() (mnav_upload_face_normals): F x 3, gone with the mesh
   mnav_rol::Dev rol;                                               // device rollout: the rest of the resident robot state and statistics of the last mnav_follow_rollout
@@ -738,6 +740,7 @@ int mnav_upload_mesh(mnav_ctx* ctx, uint32_t V, uint32_t F, uint32_t E, const fl
   ctx->chg = {};                                                     // V-sized change list
   ctx->traffic = {};                                                 // V counts: zero again
   ctx->timed = {};                                                   // V x B cells and holders, V peaks: gone
+  ctx->schedule = {};                                                // ... and the schedule's tentative arrays with them
   ctx->map = {};                                                     // the layer graph: its slots are gone
   ctx->loc = {};                                                     // vertex index: rebuilt lazily
   ctx->rp = {};                                                      // change log and replan state: the fields are gone with the slots
@@ -1862,6 +1865,7 @@ uint32_t mnav_plan_cvp_batch(mnav_ctx* ctx, uint32_t n, const float* seed_pos, c
 #include "mnav_dispatch_capi.h"   // mnav_fleet_costs, mnav_fleet_assign, mnav_dispatch_stats
 #include "mnav_traffic_capi.h"    // mnav_fleet_traffic, mnav_traffic_download, mnav_traffic_stats, mnav_layer_traffic, mnav_map_traffic
 #include "mnav_timed_capi.h"      // mnav_fleet_timed_traffic, mnav_timed_traffic_download, mnav_timed_traffic_stats, mnav_layer_timed_traffic, mnav_map_timed_traffic
+#include "mnav_schedule_capi.h"   // mnav_fleet_schedule, mnav_schedule_stats
 
 void mnav_cancel(mnav_ctx* ctx)
 {

@@ -40,8 +40,10 @@
   X(dispatch_max_rounds) /* fleet assign: auction rounds after which the call gives up (default 4194304) */ \
   X(dispatch_tail_bidders) /* fleet assign: rounds with at most this many unassigned bidders run in the single-workgroup tail kernel (default 16, measured, at most 8192; 0: never; the result does not depend on it) */ \
   X(traffic_combine)     /* fleet traffic: 1 = a wave whose contributors all end on one vertex issues one add for them, 0 = one add per lane (default 0, measured: within 1 % either way; the counts do not depend on it) */ \
-  X(timed_traffic_max_mb) /* timed fleet traffic: MiB of cells and holders (8 bytes per vertex and window) a call may take (default 2048; 0 refuses every call) */ \
-  X(timed_peak_blocks)   /* timed fleet traffic: blocks of the peak pass, which stride over the vertices (default 2048; the result does not depend on it; tests force the strided path) */
+  X(timed_traffic_max_mb) /* timed fleet traffic: MiB of cells and holders (8 bytes per vertex and window; 20 with the tentative arrays of a fleet schedule) a call may take (default 2048; 0 refuses every call) */ \
+  X(timed_peak_blocks)   /* timed fleet traffic: blocks of the peak pass, which stride over the vertices (default 2048; the result does not depend on it; tests force the strided path) */ \
+  X(schedule_chunk_rounds) /* fleet schedule: rounds enqueued between two looks of the host at the control record (default 8; the result does not depend on it) */ \
+  X(schedule_clean_fill) /* fleet schedule: 1 = the tentative arrays are filled between the rounds, 0 = the claimants clean their own words in the commit pass (default 0; the result does not depend on it) */
 
 struct Options {
 #define X(name) double name = NAN;
