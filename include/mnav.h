@@ -1025,6 +1025,13 @@ int mnav_get_stats(const mnav_ctx* ctx, mnav_stats* out);
  * engine the count (instrumentation for mnav_algorithmic_bytes) is made by the first mnav_get_stats / mnav_algorithmic_bytes
  * call, from the resident distances -- mnav_get_timing never triggers it and reports settled = 0 until then. */
 int mnav_get_timing(const mnav_ctx* ctx, mnav_stats* out);
+/* What the finalize pass of the last tile-batch call kept from the call before it and left for the next one (option
+ * tb_fin_keep).  skipped_pairs: (tile, plan) pairs whose dist / pred / vecmap stores it left out, because the plan's wave did
+ * not come near the tile and the slot's arrays held that pattern from the previous pass already; reset_pairs: pairs whose
+ * slice of the distance buffer it reset to +inf itself (0: the buffer is cleaned by a fill); filled_at_start: 1 when the call
+ * had to fill the distance buffer before it could start.  The pairs are counted on this call, from the maps the pass left; all
+ * three are 0 after a call that ran no finalize pass except filled_at_start.  Returns 0, or -1 (mnav_last_error). */
+int mnav_tb_finalize_stats(mnav_ctx* ctx, uint64_t* skipped_pairs, uint64_t* reset_pairs, uint32_t* filled_at_start);
 /* Band width of the wavefront engine in potential units; <= 0 selects the default
  * (3 x mean finite edge weight for the Dijkstra band steps, 12 x for CVP, recomputed on every cost
  * upload).  Results do not depend on it. */

@@ -27,7 +27,7 @@ WALK_NO_FACE = -3           # mnav_fleet_walks: no face at the start
 SYMBOLS = [
     "mnav_create", "mnav_destroy", "mnav_last_error", "mnav_set_face_circulation", "mnav_upload_mesh", "mnav_upload_costs",
     "mnav_compute_edge_weights", "mnav_combine_costs", "mnav_plan_dijkstra", "mnav_plan_cvp", "mnav_plan_dijkstra_batch", "mnav_plan_cvp_batch",
-    "mnav_cancel", "mnav_get_stats", "mnav_get_timing", "mnav_set_band_width", "mnav_set_dijkstra_engine", "mnav_device_output",
+    "mnav_cancel", "mnav_get_stats", "mnav_get_timing", "mnav_tb_finalize_stats", "mnav_set_band_width", "mnav_set_dijkstra_engine", "mnav_device_output",
     "mnav_algorithmic_bytes", "mnav_shard_setup", "mnav_shard_setup_partition", "mnav_shard_walk", "mnav_device_bytes", "mnav_shard_info", "mnav_shard_begin", "mnav_shard_rounds", "mnav_shard_apply", "mnav_shard_rounds_async", "mnav_shard_apply_async",
     "mnav_shard_finalize", "mnav_update_costs", "mnav_update_edge_weights", "mnav_download_costs", "mnav_set_resident_outputs", "mnav_download_output",
     "mnav_vector_at", "mnav_backtrack_cvp", "mnav_backtrack_cvp_batch", "mnav_layer_upload", "mnav_layer_steepness", "mnav_layer_inflation", "mnav_layer_download",
@@ -233,6 +233,8 @@ def load(path: str | None = None):
     L.mnav_get_stats.argtypes = [vp, C.POINTER(Stats)]
     L.mnav_get_timing.restype = C.c_int
     L.mnav_get_timing.argtypes = [vp, C.POINTER(Stats)]
+    L.mnav_tb_finalize_stats.restype = C.c_int
+    L.mnav_tb_finalize_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(u32)]
     L.mnav_set_band_width.restype = C.c_int
     L.mnav_set_band_width.argtypes = [vp, C.c_float]
     L.mnav_set_dijkstra_engine.restype = C.c_int
@@ -869,6 +871,14 @@ class MnavContext:
         d = s.as_dict()
         d["algorithmic_bytes"] = int(self._L.mnav_algorithmic_bytes(self._h))
         return d
+
+    def tb_finalize_stats(self) -> dict:
+        """What the last tile-batch call's finalize pass kept (mnav_tb_finalize_stats): (tile, plan) pairs whose stores it
+        skipped, pairs whose distance slice it reset itself, whether the call filled the distance buffer at its start."""
+        sk, rs, fl = C.c_uint64(0), C.c_uint64(0), C.c_uint32(0)
+        if self._L.mnav_tb_finalize_stats(self._h, C.byref(sk), C.byref(rs), C.byref(fl)) != 0:
+            raise RuntimeError(f"mnav_tb_finalize_stats failed: {self._err()}")
+        return dict(skipped_pairs=int(sk.value), reset_pairs=int(rs.value), filled_at_start=bool(fl.value))
 
     def last_engine(self) -> str:
         """Engine / kernel of the last Dijkstra call, by name (mnav_last_engine)."""

@@ -1682,13 +1682,16 @@ static uint32_t dijkstra_impl(mnav_ctx* ctx, uint32_t n, const uint32_t* seeds, 
     if (engine == 1 && offset < 0.0) engine = 0;                      // the band steps arm goal_dist inside the loop: tile rounds for a negative offset
   }
   if (dijkstra_order(ctx, engine, in, map)) return MNAV_INTERNAL_ERROR;
+  const Resident::FinalizeClaim held = ctx->res.take_finalize_claim();   // what the last finalize pass of the tile-batch engine left in the slots (this call's to use, nobody's after)
   ctx->res.outputs_begin(Resident::kDijkstra, n, map);               // outputs of the previous call are gone; this call's once it has gone through:
   resident_outputs_begin(ctx);                                        // every error return below leaves none
   (void)hipEventRecord(ctx->ev[0], ctx->stream);
   const uint32_t m = (uint32_t)in.size();
   if (m) {
     if (materialize(ctx, false, cost_limit)) return MNAV_INTERNAL_ERROR;
+    ctx->tb.claim_np = held.slots; ctx->tb.claim_vec = held.vecmaps;   // (run_dijkstra_tb takes it; good for this dispatch only)
     const int rc = dijkstra_dispatch(ctx, m, in, offset, engine_auto, &engine);
+    ctx->tb.claim_np = 0;
     if (rc < 0) return MNAV_INTERNAL_ERROR;
     if (rc == 1) { for (uint32_t i = 0; i < n; ++i) if (codes_out) codes_out[i] = MNAV_CANCELED; return MNAV_CANCELED; }   // :350-354
     ctx->last_engine = engine;
@@ -1896,6 +1899,29 @@ int mnav_get_stats(const mnav_ctx* ctx, mnav_stats* out)
   if (!ctx || !out) return -1;
   settle_stats(const_cast<mnav_ctx*>(ctx));
   *out = ctx->stats;
+  return 0;
+}
+
+// What the last tile-batch call's finalize pass kept; the pairs are counted from the pass's maps here,
+// on request, not inside the call.
+int mnav_tb_finalize_stats(mnav_ctx* ctx, uint64_t* skipped_pairs, uint64_t* reset_pairs, uint32_t* filled_at_start)
+{
+  if (!ctx) return -1;
+  TbState& S = ctx->tb;
+  unsigned long long cnt[2] = { 0ull, 0ull };
+  if (S.fin_stats && S.umap && S.fin_np && S.ntiles) {
+    if (hipSetDevice(ctx->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return -1; }
+    const uint32_t nblk = (S.fin_np + 63u) / 64u;
+    HIPCHK(hipMemsetAsync(S.fin_cnt, 0, 16, ctx->stream));
+    hipLaunchKernelGGL(k_tb_fin_count, dim3(std::min<uint32_t>(((size_t)S.ntiles * nblk + kBlock - 1) / kBlock, 1024u)), dim3(kBlock), 0, ctx->stream,
+                       S.umap.get(), S.uskip.get(), S.ntiles, nblk, S.umap_stride, S.fin_cnt.get());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(cnt, S.fin_cnt, 16, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+  }
+  if (skipped_pairs) *skipped_pairs = cnt[1];
+  if (reset_pairs) *reset_pairs = (S.fin_stats && S.fin_reset) ? (uint64_t)S.ntiles * S.fin_np - cnt[0] : 0u;
+  if (filled_at_start) *filled_at_start = S.filled_at_start ? 1u : 0u;
   return 0;
 }
 

@@ -17,6 +17,11 @@ class Resident {
  public:
   static constexpr uint32_t kNone = 0xFFFFFFFFu;                     // a plan that never reached the device
   enum Kind : uint8_t { kNoCall, kDijkstra, kCvp, kSharded };        // the call that owns the outputs
+  // "The arrays of the first `slots` plan slots hold what the tile-batch engine's last finalize pass wrote, vector maps included
+  // or not": what lets the next such pass skip the stores of a (tile, plan) whose unreached pattern it wrote last time
+  // (mnav_tb_finalize.h).  It stands from the commit of a fresh tile-batch call that was finalized until the next transition
+  // after which something else may have written a slot -- every one but the commits.
+  struct FinalizeClaim { uint32_t slots = 0; bool vecmaps = false; };
 
   // -- transitions ----------------------------------------------------------------------------------------------------
   // A Dijkstra call is recorded (what a replan needs of it, in the caller's order); its fields count once it has committed.
@@ -30,6 +35,7 @@ class Resident {
   // The outputs of a call of n plans begin: those of the previous call are gone.  map: device plan -> caller's index.
   void outputs_begin(Kind kind, uint32_t n, const std::vector<uint32_t>& map)
   {
+    fin_claim_ = FinalizeClaim{};                                     // (the starting call took it out first: take_finalize_claim)
     kind_ = kind; hidden_ = false; live_ = 0;
     slot_.assign(n, kNone);
     for (size_t k = 0; k < map.size(); ++k) slot_[map[k]] = (uint32_t)k;
@@ -41,6 +47,7 @@ class Resident {
     if (live) {
       live_ = live; finalized_ = !paths_only; vec_ = vecmaps;
       rewindable_ = leaves_rewindable_field(engine, paths_only);
+      if (engine == 5 && !paths_only) { fin_claim_.slots = live; fin_claim_.vecmaps = vecmaps; }   // (a fresh call: device plan k is slot k)
     }
     slot0_taken_ = false;
     partial_ = live != slot_.size();
@@ -54,7 +61,7 @@ class Resident {
   void commit_cvp(uint32_t live) { live_ = live; finalized_ = vec_ = true; }
   // A repair starts to change the recorded fields (an inflation wave in between took slot 0's bookkeeping, not its dist: the
   // map is the recorded call's again).
-  void repair_begin() { kind_ = kDijkstra; hidden_ = false; live_ = 0; rewindable_ = false; }
+  void repair_begin() { kind_ = kDijkstra; hidden_ = false; live_ = 0; rewindable_ = false; fin_claim_ = FinalizeClaim{}; }
   // The repair went through, finalize pass included: the record follows the new robot vertices and offset.
   void repair_commit(const std::vector<uint32_t>& targets, double offset, bool vecmaps)
   {
@@ -63,19 +70,24 @@ class Resident {
     note_robots();
   }
   // The call failed or was cancelled: nothing is handed out, nothing can be rewound (the fields may be half rewound).
-  void call_failed() { live_ = 0; rewindable_ = false; }
+  void call_failed() { live_ = 0; rewindable_ = false; fin_claim_ = FinalizeClaim{}; }
   // An inflation wave worked in plan slot 0: the outputs are hidden (the wave took slot 0's predecessors, keys and lists; a
   // replan re-derives them, and keeps no plan in slot 0 as it is).  The recorded call and its map stay for the replan.
-  void wave_took_slot0() { hidden_ = true; slot0_taken_ = true; }
+  void wave_took_slot0() { hidden_ = true; slot0_taken_ = true; fin_claim_ = FinalizeClaim{}; }
   // Slot 0 and the result records were taken over by a sharded plan: nothing a replan can rewind.
   void shard_took_slot0()
   {
-    kind_ = kSharded; hidden_ = false; live_ = 0; slot_.clear();
+    kind_ = kSharded; hidden_ = false; live_ = 0; slot_.clear(); fin_claim_ = FinalizeClaim{};
     finalized_ = vec_ = rewindable_ = partial_ = false;
   }
   // The mesh was replaced: the recorded seeds are the old mesh's.  (As found: the map and the live count stay -- the slots
   // themselves are gone, so nothing is handed out, but the robot-side calls still see the old plan count.)
-  void mesh_replaced() { have_call_ = rewindable_ = partial_ = false; }
+  void mesh_replaced() { have_call_ = rewindable_ = partial_ = false; fin_claim_ = FinalizeClaim{}; }
+  // The tile-batch engine's batch state was freed (a larger batch, a new mesh): the map the claim speaks of is gone.
+  void batch_state_freed() { fin_claim_ = FinalizeClaim{}; }
+  // The call that starts takes the claim out, before its outputs_begin: it alone may use it, and only if it turns out to be a
+  // fresh tile-batch call; the claim is gone until that call commits.
+  FinalizeClaim take_finalize_claim() { const FinalizeClaim c = fin_claim_; fin_claim_ = FinalizeClaim{}; return c; }
 
   // -- queries --------------------------------------------------------------------------------------------------------
   Kind kind() const { return kind_; }
@@ -139,6 +151,7 @@ class Resident {
   {
     return finalized_ && (!want_vecmaps || vec_) && memcmp(&offset, &offset_, sizeof(double)) == 0;
   }
+  FinalizeClaim finalize_claim() const { return fin_claim_; }
 
  private:
   void note_robots()                                                  // robot vertex per device slot, for the popped potential
@@ -161,6 +174,7 @@ class Resident {
   bool have_call_ = false;
   bool partial_ = false;             // the call went through, but a plan of it never reached the device (rejected ids, seed == target)
   bool slot0_taken_ = false;
+  FinalizeClaim fin_claim_;
 };
 
 }  // namespace mnav

@@ -985,7 +985,14 @@ struct TbBatch {
   GraphExec graph[2]; tb::Args graph_args[2]{};   // one per distance buffer
   // second distance buffer, filled with +inf on its own stream behind the previous call (the fill of 6 B x slots x plans is
   // otherwise 2 % of a batch); only when both fit comfortably
+  // (allocated when a call first ends without a finalize pass that resets D itself: paths-only batches)
   DevBuf<float> D2; bool d2_clean = false; uint32_t d2_clean_np = 0, d2_wanted_np = 0;
+  // what the finalize pass leaves for the next call (mnav_tb_finalize.h, FinTb): D reset to +inf over the words of d_clean_np
+  // plans; per (tile, block of 64 plans) the plans whose slot arrays hold the unreached pattern, and the pairs the last pass skipped
+  uint32_t d_clean_np = 0;
+  DevBuf<unsigned long long> umap, uskip, fin_cnt; uint32_t umap_stride = 0;
+  uint32_t keep_np = 0;                 // tb_fields_upload: leading slots whose previous pass wrote through the same pointers under a standing claim
+  bool fin_stats = false, fin_reset = false, filled_at_start = false; uint32_t fin_np = 0;   // the last call, for mnav_tb_finalize_stats
 };
 
 struct TbState : TbTables, TbBatch {
@@ -998,6 +1005,7 @@ struct TbState : TbTables, TbBatch {
   Event warm_ev[4]; float ms_warm = 0.f, ms_warm_fin = 0.f;   // a warm start (run_dijkstra_tb with a TbWarmIn): k_tb_warm and the finalize pass of the last one
   tb::Ctl last{};                       // counters of the last batch
   bool count_pending = false;           // the settled-vertex count of the last (paths-only) batch has not been taken yet
+  uint32_t claim_np = 0; bool claim_vec = false;   // mnav::Resident::finalize_claim of the call that is being dispatched (dijkstra_impl sets it around the dispatch)
 };
 
 }  // namespace

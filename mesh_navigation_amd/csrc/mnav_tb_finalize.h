@@ -31,7 +31,30 @@ struct FinTb {
   const float* xyz; float* const* vecmaps;        // vecmaps != null: the vector map in the same pass
   const Plan* plans; PlanResult* res; uint32_t* mismatch; const FinRec* recs;
   uint32_t plans_per_wave, tiles_per_xcd, max_sl;
+  // What the pass keeps for the next call.  umap[tile * umap_stride + p / 64], bit p % 64: plan p's wave
+  // never came near the tile, so slot p's arrays hold dist = +inf, pred = own id, vecmap = 0 over the tile's vertices.  A wave
+  // owns the words of the plans it walks (plans_per_wave is a multiple of 64) and writes them on every pass; for the plans
+  // below umap_prev_np it reads them first -- the previous pass's, which the host vouches still describe the slots
+  // (mnav::Resident::finalize_claim) -- and stores nothing where the pattern stands already.  uskip: those pairs, same layout,
+  // for the statistics (one store per wave; counted on request, k_tb_fin_count).  clean_d: a wave stores +inf over every
+  // reached slice it has loaded, so that the call leaves A.D as a fill would.
+  unsigned long long* umap; unsigned long long* uskip;
+  uint32_t umap_stride, umap_prev_np, clean_d;
 };
+
+// popcounts of the two maps of the last pass over the words of its nblk blocks of plans: out[0] unreached pairs, out[1] skipped pairs
+__global__ __launch_bounds__(kBlock) void k_tb_fin_count(const unsigned long long* __restrict__ umap, const unsigned long long* __restrict__ uskip, uint32_t ntiles,
+                                                         uint32_t nblk, uint32_t stride, unsigned long long* __restrict__ out)
+{
+  const size_t n = (size_t)ntiles * nblk, step = (size_t)gridDim.x * kBlock;
+  uint32_t a = 0, b = 0;
+  for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += step) {
+    const size_t at = (i / nblk) * stride + i % nblk;
+    a += (uint32_t)__popcll(umap[at]); b += (uint32_t)__popcll(uskip[at]);
+  }
+  a = wave_sum(a); b = wave_sum(b);
+  if ((threadIdx.x & 63) == 0) { if (a) atomicAdd(out, (unsigned long long)a); if (b) atomicAdd(out + 1, (unsigned long long)b); }
+}
 
 // per plan: the plan record the path walk reads (k_finish) -- what k_dij_finalize's first tile chunk used to write
 __global__ __launch_bounds__(kBlock) void k_tb_fin_plans(tb::Args A, const Plan* __restrict__ plans, float* const* __restrict__ vecmaps, FinRec* __restrict__ recs)
@@ -162,6 +185,13 @@ __global__ __launch_bounds__(64 * kFinWaves, MNAV_FIN_OCC) void k_tb_finalize(tb
   }
   // ---- the plans of this wave: the next plan's slice is in flight while a plan is worked on
   MNAV_GLOBAL const float* const gD = as_global(A.D) + (size_t)W.soff * NP;
+  MNAV_GLOBAL uint32_t* const gDw = (MNAV_GLOBAL uint32_t*)(as_global(A.D) + (size_t)W.soff * NP);   // (clean_d: the same slices, to reset them)
+  const bool clean = F.clean_d != 0u && live;
+  // the words of this wave in the two maps: the previous pass's is loaded next to the first slice, this pass's gathered plan by
+  // plan in a scalar pair and stored once per 64 plans
+  MNAV_GLOBAL unsigned long long* const g_umap = as_global(F.umap) + (size_t)t * F.umap_stride;
+  MNAV_GLOBAL unsigned long long* const g_uskip = as_global(F.uskip) + (size_t)t * F.umap_stride;
+  unsigned long long uprev = p_beg < F.umap_prev_np ? g_umap[p_beg >> 6] : 0ull, ubits = 0ull, uskipped = 0ull;
   const uint32_t i0 = lane, i1 = lane + 64u, i2 = lane + 128u, i3 = lane + 192u;
   // Everything a plan needs is loaded one plan ahead, without a branch and record first.  (Until round 6 the record's fields were
   // separate loads issued AFTER the next slice's and needed at once, and the slice loads sat under `i < sl` branches, which leaves
@@ -190,12 +220,19 @@ __global__ __launch_bounds__(64 * kFinWaves, MNAV_FIN_OCC) void k_tb_finalize(tb
     const uint32_t seed = rw(6);
     const bool reached = __ballot(cur[0] != kTbInfBits || cur[1] != kTbInfBits || cur[2] != kTbInfBits || cur[3] != kTbInfBits) != 0ull;
     uint32_t cnt = 0;
+    const unsigned long long pbit = 1ull << (p & 63u);
     if (!reached) {                                                    // the plan's wave never came near this tile: dist = inf, pred = itself
+      ubits |= pbit;
+      if (p < F.umap_prev_np && (uprev & pbit)) uskipped |= pbit;       // ... which is what the slot's arrays hold already (uniform over the wave)
+      else {
 #pragma unroll
-      for (int v = 0; v < 2; ++v) if (own[v]) {
-        g_dist[gid[v]] = inf_f(); g_pred[gid[v]] = gid[v];
-        if (g_vm) { const f32x3_u z3 = { 0.f, 0.f, 0.f }; *(MNAV_GLOBAL f32x3_u*)(g_vm + 3 * (size_t)gid[v]) = z3; }
+        for (int v = 0; v < 2; ++v) if (own[v]) {
+          g_dist[gid[v]] = inf_f(); g_pred[gid[v]] = gid[v];
+          if (g_vm) { const f32x3_u z3 = { 0.f, 0.f, 0.f }; *(MNAV_GLOBAL f32x3_u*)(g_vm + 3 * (size_t)gid[v]) = z3; }
+        }
       }
+      // (the first 256 slots are +inf by the test above; a longer slice's tail is reset whatever it holds)
+      if (clean) for (uint32_t i = lane + 256u; i < W.sl; i += 64) gDw[(size_t)p * W.sl + i] = kTbInfBits;
     } else {
       GoalCut gcut; gcut.goal = 0.f; gcut.cut = u2f(rw(7)); gcut.tie = rw(8);   // dijkstra :296 (k_tb_fin_plans)
       __builtin_amdgcn_wave_barrier();                                 // (the previous plan's reads of ld[] are done: one wave, program order)
@@ -204,6 +241,14 @@ __global__ __launch_bounds__(64 * kFinWaves, MNAV_FIN_OCC) void k_tb_finalize(tb
       if (i2 < W.sl) ld[i2] = cur[2];
       if (i3 < W.sl) ld[i3] = cur[3];
       for (uint32_t i = lane + 256u; i < W.sl; i += 64) ld[i] = ((MNAV_GLOBAL const uint32_t*)(gD + (size_t)p * W.sl))[i];   // (slices beyond 256 slots: rare meshes)
+      if (clean) {                                                     // the slice is in cur[] and ld[]: nothing reads it in A.D again, the next call finds +inf
+        MNAV_GLOBAL uint32_t* const s = gDw + (size_t)p * W.sl;
+        if (i0 < W.sl) s[i0] = kTbInfBits;
+        if (i1 < W.sl) s[i1] = kTbInfBits;
+        if (i2 < W.sl) s[i2] = kTbInfBits;
+        if (i3 < W.sl) s[i3] = kTbInfBits;
+        for (uint32_t i = lane + 256u; i < W.sl; i += 64) s[i] = kTbInfBits;
+      }
       __builtin_amdgcn_wave_barrier();
 #pragma unroll
       for (int v = 0; v < 2; ++v) {
@@ -312,6 +357,11 @@ __global__ __launch_bounds__(64 * kFinWaves, MNAV_FIN_OCC) void k_tb_finalize(tb
     }
     cnt = wave_sum(cnt);
     if (lane == 0 && cnt && live) atomicAdd(&F.res[p].settled, (unsigned long long)cnt);
+    if ((p & 63u) == 63u || p + 1 == p_end) {                          // the block of 64 plans ends: its words (bits beyond NP stay 0)
+      if (lane == 0 && live) { g_umap[p >> 6] = ubits; g_uskip[p >> 6] = uskipped; }
+      ubits = 0ull; uskipped = 0ull;
+      uprev = (p + 1 < p_end && p + 1 < F.umap_prev_np) ? g_umap[(p + 1) >> 6] : 0ull;
+    }
 #pragma unroll
     for (int q = 0; q < 4; ++q) cur[q] = nxt[q];
     rcur = rnxt;

@@ -8,6 +8,7 @@ void tb_free_batch(mnav_ctx* ctx)
   if (S.fill_stream) (void)hipStreamSynchronize(S.fill_stream);      // (its fill may still be writing D2)
   static_cast<TbBatch&>(S) = TbBatch{};
   S.count_pending = false; ctx->tb_args_valid = false;               // the last batch's arguments point into freed memory now
+  ctx->res.batch_state_freed();                                       // (the map of unreached pairs went with it)
 }
 
 void tb_free(mnav_ctx* ctx)
@@ -116,10 +117,8 @@ int tb_ensure_batch(mnav_ctx* ctx, uint32_t np)
   tb_free_batch(ctx);
   const size_t nt = S.ntiles ? S.ntiles : 1, pairs = nt * (size_t)np;
   HIPCHK(S.D.alloc(4 * (size_t)S.S * np + 64));
-  if (8 * (size_t)S.S * np <= ((size_t)96 << 30) && !opt_on(ctx->opt.tb_no_prefill)) {
-    if (S.D2.alloc(4 * (size_t)S.S * np + 64) != hipSuccess) (void)hipGetLastError();   // (optional: the batch runs without it)
-    if (S.D2 && !S.fill_stream) { HIPCHK(hipStreamCreateWithFlags(S.fill_stream.out(), hipStreamNonBlocking)); HIPCHK(hipEventCreateWithFlags(S.fill_done.out(), hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(S.call_done.out(), hipEventDisableTiming)); }
-  }
+  S.umap_stride = (np + 63u) / 64u;                                   // (fixed by the capacity: a slot's bit stays where it is when the batch size changes)
+  HIPCHK(S.umap.alloc(8 * nt * S.umap_stride)); HIPCHK(S.uskip.alloc(8 * nt * S.umap_stride)); HIPCHK(S.fin_cnt.alloc(16));
   HIPCHK(S.pend.alloc(4 * pairs + 64));
   HIPCHK(S.pflag.alloc(nt * (((size_t)np + 63) / 64) + 64));
   HIPCHK(S.bucket.alloc(2 * pairs + 64));
@@ -135,6 +134,18 @@ int tb_ensure_batch(mnav_ctx* ctx, uint32_t np)
   HIPCHK(S.d_recs.alloc(sizeof(FinRec) * (size_t)np));
   HIPCHK(S.h_plans.alloc(sizeof(Plan) * (size_t)np)); HIPCHK(S.h_vecs.alloc(sizeof(float*) * (size_t)np));
   S.cap_np = np;
+  return 0;
+}
+
+// The second distance buffer, its stream and its events: wanted by the calls that end without a finalize pass that resets D
+// (tb_clean_other).  Optional: without it such a batch fills D at its start.
+int tb_ensure_other(mnav_ctx* ctx)
+{
+  TbState& S = ctx->tb;
+  if (S.D2 || 8 * (size_t)S.S * S.cap_np > ((size_t)96 << 30) || opt_on(ctx->opt.tb_no_prefill)) return 0;
+  if (S.D2.alloc(4 * (size_t)S.S * S.cap_np + 64) != hipSuccess) { (void)hipGetLastError(); return 0; }
+  if (!S.fill_stream) { HIPCHK(hipStreamCreateWithFlags(S.fill_stream.out(), hipStreamNonBlocking)); HIPCHK(hipEventCreateWithFlags(S.fill_done.out(), hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(S.call_done.out(), hipEventDisableTiming)); }
+  S.d2_clean = false;
   return 0;
 }
 
@@ -186,6 +197,14 @@ int tb_fields_upload(mnav_ctx* ctx, uint32_t n, const std::vector<PlanIn>& in, d
   if (tb_fin_weights(ctx)) return -1;
   Plan* const hp = S.h_plans.get();
   float** const vecs = S.h_vecs.get();
+  // The previous pass's map of unreached pairs may be used for the leading slots that the claim covers (the caller checked it)
+  // and, second lock, whose arrays are the ones that pass wrote: its records are still in the staging
+  uint32_t keep = std::min(S.keep_np, n);
+  for (uint32_t i = 0; i < keep; ++i) {
+    const Slot& s = ctx->slots[i];
+    if (hp[i].dist != s.dist.get() || hp[i].pred != s.pred.get() || vecs[i] != (float*)s.vecmap) keep = i;
+  }
+  S.keep_np = keep;
   for (uint32_t i = 0; i < n; ++i) {
     Slot& s = ctx->slots[i];
     Plan& P = hp[i];
@@ -217,7 +236,9 @@ int tb_fields(mnav_ctx* ctx, uint32_t n, const tb::Args& A)
 #ifndef MNAV_FIN_PPW
 #define MNAV_FIN_PPW 64u                  // plans a wave of k_tb_finalize walks; ms of the pass per 7168-plan batch at 32 / 64 / 128 / 256: 65.8 / 66.1 / 70.6 / 79.3
 #endif
+  static_assert(MNAV_FIN_PPW % 64u == 0u, "a wave of k_tb_finalize owns whole words of the map of unreached pairs");
   F.plans_per_wave = MNAV_FIN_PPW; F.tiles_per_xcd = (groups + 7u) / 8u; F.max_sl = S.max_sl;
+  F.umap = S.umap; F.uskip = S.uskip; F.umap_stride = S.umap_stride; F.umap_prev_np = S.keep_np; F.clean_d = S.fin_reset ? 1u : 0u;
   hipLaunchKernelGGL(k_tb_fin_plans, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, A, ctx->d_plans, F.vecmaps, S.d_recs);
   const uint32_t npg = (n + F.plans_per_wave - 1u) / F.plans_per_wave;
   const size_t lds = 4 * (size_t)fin_lds_words(S.max_sl, F.vecmaps != nullptr) * kFinWaves;
@@ -240,6 +261,9 @@ int tb_fields(mnav_ctx* ctx, uint32_t n, const tb::Args& A)
 // width (44 GB in 7 ms at 7168 plans) under the host's copy-out of the paths and the gap the host leaves between two calls (until
 // this was moved it started after the copy-out and the call's last synchronize); a call that still comes sooner waits for the
 // event, which costs what cleaning at its start would.
+// It is asked for (d2_wanted_np) by every call whose finalize pass does not reset D itself: paths-only calls always, finalized ones
+// unless option tb_fin_keep has bit 1 (FinTb::clean_d, mnav_tb_finalize.h -- then the call marks D clean, d_clean_np, and the next
+// fresh call of no more plans neither fills nor swaps).  The second buffer is allocated by the first call that asks (tb_ensure_other).
 int tb_clean_other(mnav_ctx* ctx)
 {
   TbState& S = ctx->tb;
@@ -263,10 +287,21 @@ struct TbWarmIn { const uint32_t* d_level; const float* const* d_dist; ReplanCnt
 int run_dijkstra_tb(mnav_ctx* ctx, uint32_t n, const std::vector<PlanIn>& in, double offset, const TbWarmIn* warm = nullptr)
 {
   TbState& S = ctx->tb;
+  // what the caller vouches for (the claim is good for this dispatch only) and what the option allows
+  const uint32_t claim_np = S.claim_np; const bool claim_vec = S.claim_vec;
+  S.claim_np = 0;
+  const uint32_t keep_opt = opt_u32(ctx->opt.tb_fin_keep, 1u);       // (default: the skipped stores; the reset pays in memory, not in time -- DESIGN.md section 4)
   if (tb_build(ctx)) return -1;
   if (tb_weights(ctx)) return -1;
   if (n > 65535u) { ctx->err = "tile-batch engine: more than 65535 plans in one batch"; return -1; }
+  const bool grown = n > S.cap_np;                                    // (new buffers: no map, nothing clean)
   if (tb_ensure_batch(ctx, n)) return -1;
+  // D is clean for was_clean plans: the mark is taken down here and put up again behind the finalize launch, so that every early
+  // return leaves none
+  const uint32_t was_clean = S.d_clean_np;
+  S.d_clean_np = 0; S.fin_stats = false; S.filled_at_start = false;
+  S.fin_reset = (keep_opt & 2u) != 0u && !ctx->lazy_paths;
+  S.keep_np = ((keep_opt & 1u) && !warm && !grown && !ctx->lazy_paths && claim_vec == ctx->want_vec) ? std::min(claim_np, n) : 0u;
   if (ensure_plan_tables(ctx, n)) return -1;
   if (ensure_paths(ctx, n)) return -1;
   if (!ctx->d_mismatch) HIPCHK(ctx->d_mismatch.alloc(4));
@@ -306,13 +341,16 @@ int run_dijkstra_tb(mnav_ctx* ctx, uint32_t n, const std::vector<PlanIn>& in, do
   }
   HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
   if (!warm) {
-    bool prefilled = false;
-    if (S.D2 && S.d2_clean && S.d2_clean_np >= n) {                   // a clean buffer was prepared behind the previous call
-      std::swap(S.D, S.D2); A.D = S.D;
-      HIPCHK(hipStreamWaitEvent(ctx->stream, S.fill_done, 0));
-      prefilled = true;
+    bool prefilled = was_clean >= n;                                  // the previous call's finalize pass left D clean: no fill, no swap
+    if (!prefilled) {
+      if (S.D2 && S.d2_clean && S.d2_clean_np >= n) {                 // a clean buffer was prepared behind the previous call
+        std::swap(S.D, S.D2); A.D = S.D;
+        HIPCHK(hipStreamWaitEvent(ctx->stream, S.fill_done, 0));
+        prefilled = true;
+      }
+      S.d2_clean = false;
     }
-    S.d2_clean = false;
+    S.filled_at_start = !prefilled;
     if (!prefilled && tb_fill(ctx, S.D, 4 * (size_t)S.S * n, kTbInfBits)) return -1;
     if (tb_fill(ctx, S.pend, 4 * (size_t)S.ntiles * n, kTbInfBits)) return -1;
   }
@@ -342,7 +380,9 @@ int run_dijkstra_tb(mnav_ctx* ctx, uint32_t n, const std::vector<PlanIn>& in, do
   HIPCHK(hipEventRecord(ctx->ev[2], ctx->stream));
   // (the other buffer -- the previous call's distances, superseded the moment this call began -- is cleaned for the NEXT call behind
   // the last kernel of this one: tb_clean_other)
-  if (!warm || !S.d2_clean) S.d2_wanted_np = S.D2 ? n : 0u;
+  // -- unless this call's finalize pass resets the buffer it works in (FinTb::clean_d): then there is no other buffer to prepare
+  if (!S.fin_reset && tb_ensure_other(ctx)) return -1;
+  if (!warm || !S.d2_clean) S.d2_wanted_np = (S.D2 && !S.fin_reset) ? n : 0u;
 
   int ncu = 256;
   (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->device);
@@ -392,6 +432,10 @@ int run_dijkstra_tb(mnav_ctx* ctx, uint32_t n, const std::vector<PlanIn>& in, do
     if (warm) HIPCHK(hipEventRecord(S.warm_ev[2], ctx->stream));
     if (tb_fields(ctx, n, A)) return -1;
     if (warm) HIPCHK(hipEventRecord(S.warm_ev[3], ctx->stream));
+    // the pass is enqueued: behind it every word of the first n plans is +inf again (the reached slices reset, the others never
+    // written), and so is what was clean beyond them.  A warm start of more plans than were clean wrote its slices only.
+    if (S.fin_reset) S.d_clean_np = warm ? (n <= was_clean ? was_clean : 0u) : std::max(n, was_clean);
+    S.fin_stats = true; S.fin_np = n;
   }
   HIPCHK(hipEventRecord(ctx->ev[3], ctx->stream));
   HIPCHK(hipEventSynchronize(ctx->evc[1]));
