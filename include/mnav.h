@@ -612,6 +612,75 @@ int mnav_follow_rollout(mnav_ctx* ctx, uint32_t n, const float* pos, const float
 int mnav_rollout_stats(const mnav_ctx* ctx, uint32_t* status_counts, uint64_t* robot_ticks, uint64_t* stayed, uint64_t* neighbour,
                        uint64_t* global, uint32_t* built_index, float* ms_kernels, float* ms_total);
 
+/* -- fleet rollouts: departure ticks and a separation check between robots ----------------------------
+ * mnav_follow_rollout with a start tick per robot (where mnav_fleet_schedule's departures go) and, at chosen ticks, a check
+ * on the device that tells every robot whether another robot stands within a radius, which one, when and how close: what
+ * a caller otherwise finds by pulling the strided trace over PCIe and searching it on the host.  The controller stays the
+ * reference's: nobody reacts to a near robot. */
+#define MNAV_SEP_WAITING_PRESENT 1u   /* a robot that has not departed yet stands in the way */
+#define MNAV_SEP_REACHED_PRESENT 2u   /* a robot that REACHED its goal stays in the way */
+typedef struct mnav_separation_config {
+  double   radius;        /* used as (float)radius, > 0; r2 = (float)radius * (float)radius must be finite and > 0 */
+  uint32_t check_stride;  /* a check after every check_stride-th tick of the call, 1 .. ticks */
+  uint32_t flags;         /* MNAV_SEP_* or 0 */
+} mnav_separation_config;
+/* Inputs and outputs up to trace_out are mnav_follow_rollout's, with its rule for a tick.
+ * DEPARTURE.  The ticks of a call are numbered 1 .. ticks.  start_tick: n entries, or NULL for all 0.  Robot i WAITS at tick
+ * t iff t <= start_tick[i]: its status stays RUNNING, it has no controller tick, its ticks, pos, dir, face, travel,
+ * cost_integral and min_goal_dist are untouched, and the trace repeats its position.  From tick start_tick[i] + 1 on it runs
+ * mnav_follow_rollout's tick unchanged.  So robot i's state outputs are those of mnav_follow_rollout over
+ * ticks - min(start_tick[i], ticks) ticks, its trace is that call's trace moved down by start_tick[i] rows (ticks, not
+ * strides) below rows that repeat the start position, and with start_tick[i] >= ticks it comes back as it went in.  With
+ * start_tick = NULL and separation = NULL every output is mnav_follow_rollout's bit for bit.  Resuming works as there; the
+ * caller subtracts the ticks already run from the start ticks (saturating at 0).
+ * A CHECK happens after call tick t for every t with t % check_stride == 0, on the positions as they then stand (those a
+ * trace row of that tick holds).  Robot i is PRESENT at it iff its three coordinates are finite and it is RUNNING and not
+ * waiting, or OUT_OF_MAP or NO_FIELD (a stranded robot is an obstacle), or waiting with MNAV_SEP_WAITING_PRESENT, or REACHED
+ * with MNAV_SEP_REACHED_PRESENT.  Two present robots i != j are NEAR iff d2 <= r2, with dx = pi.x - pj.x (dy, dz alike) and
+ * d2 = (dx*dx + dy*dy) + dz*dz, all float32, every operation rounded on its own (no contraction): d2 is symmetric.  The near
+ * robots of i at a check are its PARTNERS.  Per robot, over the checks of this call (any pointer may be NULL; all of them
+ * must be NULL when separation is NULL):
+ *   near_checks_out       checks with at least one partner
+ *   max_partners_out      the most partners at one check
+ *   first_near_tick_out   the tick of the first check with a partner, or MNAV_NONE
+ *   first_near_robot_out  at that check the partner with the smallest d2, ties to the smallest index; or MNAV_NONE
+ *   min_sep2_out          the smallest d2 over all checks and partners, or +inf (only partners count: nothing beyond the
+ *                         radius is measured)
+ *   min_sep_tick_out      the tick of the first check that attains min_sep2, or MNAV_NONE
+ *   min_sep_robot_out     at that check the partner with the smallest d2, ties to the smallest index; or MNAV_NONE
+ * Counts and minima only: the same bits on every run, with any separation_cell_scale (option, 1 .. 4, the side of the search
+ * grid's cells in radii).
+ * THE GUARD.  Before a check compares anything the device sums T, the distance tests it would perform: over the present
+ * robots, the population of the grid cells each one examines (its own cell, hence itself, included).  T depends on the
+ * positions and the grid only.  T > separation_max_tests (option, default 2^32): the check is SKIPPED -- nothing is compared,
+ * no robot's outputs change -- and the call goes on without asking the host.
+ * mnav_cancel as in mnav_follow_rollout; the separation outputs then cover the checks run.
+ * Returns 0; 1 when cancelled; 2 when the call ran to its end but at least one check was skipped; or -1 with
+ * mnav_last_error set and NOTHING touched: every refusal of mnav_follow_rollout, a radius that is not positive or whose r2
+ * is not finite and positive, a check_stride of 0 or above ticks, an unknown flag bit, a separation output without
+ * separation, a separation_cell_scale outside 1 .. 4.  n = 0 does nothing.  The call changes no plan output, no layer and no statistic of
+ * another entry point (mnav_rollout_stats keeps its values); it builds the lookup index as mnav_follow_rollout does.
+ * DESIGN.md section 3.20. */
+int mnav_fleet_rollout(mnav_ctx* ctx, uint32_t n, const float* pos, const float* dir, const float* up, const uint32_t* face_in,
+                       const uint32_t* slots, const uint32_t* seed_faces, const float* goal_pos, const float* goal_dir,
+                       const mnav_follow_config* config, const mnav_rollout_config* rollout, const uint32_t* start_tick,
+                       const mnav_separation_config* separation, int32_t* status_out, uint32_t* ticks_out, float* pos_out,
+                       float* dir_out, uint32_t* face_out, double* travel_out, double* cost_integral_out,
+                       float* min_goal_dist_out, float* trace_out, uint32_t* near_checks_out, uint32_t* max_partners_out,
+                       uint32_t* first_near_tick_out, uint32_t* first_near_robot_out, float* min_sep2_out,
+                       uint32_t* min_sep_tick_out, uint32_t* min_sep_robot_out);
+/* The last mnav_fleet_rollout.  status_counts .. built_index: as mnav_rollout_stats, for this call.  checks_run / _skipped and
+ * the tick of the first skipped check (MNAV_NONE: none); robots with near_checks > 0; the unordered near pairs summed over
+ * the checks run; the most near pairs at one check and its tick (the first such check; MNAV_NONE without a check run); the
+ * smallest d2 of the call and its pair min_pair[2] = (i, j), i < j (+inf and MNAV_NONE twice without a near pair); the
+ * distance tests performed (the T of every check run); the largest cell population met; device milliseconds of the
+ * separation kernels, of all kernels, and host milliseconds of the whole call.  Any pointer may be NULL. */
+int mnav_fleet_rollout_stats(const mnav_ctx* ctx, uint32_t* status_counts, uint64_t* robot_ticks, uint64_t* stayed,
+                             uint64_t* neighbour, uint64_t* global, uint32_t* built_index, uint32_t* checks_run,
+                             uint32_t* checks_skipped, uint32_t* first_skipped_tick, uint32_t* robots_near, uint64_t* near_pairs,
+                             uint64_t* max_pairs, uint32_t* max_pairs_tick, float* min_sep2, uint32_t* min_pair, uint64_t* tests,
+                             uint32_t* max_cell, float* ms_separation, float* ms_kernels, float* ms_total);
+
 /* -- fleet paths and walks: many robots per resident field ---------------------------------------------
  * A Dijkstra call returns one vertex path per plan, from the plan's seed (the goal) to its one target.  The field is seeded
  * at the goal, so it already holds the path of every robot inside it: mnav_fleet_paths hands Move Base Flex's setPlan a

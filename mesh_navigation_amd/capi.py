@@ -36,7 +36,7 @@ SYMBOLS = [
     "mnav_layer_height_diff", "mnav_layer_roughness", "mnav_layer_ridge", "mnav_neighbourhood_stats",
     "mnav_layer_border", "mnav_layer_clearance", "mnav_clearance_download", "mnav_clearance_stats",
     "mnav_locate", "mnav_locate_stats", "mnav_plan_dijkstra_batch_at", "mnav_plan_cvp_batch_at",
-    "mnav_follow_batch", "mnav_follow_stats", "mnav_follow_rollout", "mnav_rollout_stats",
+    "mnav_follow_batch", "mnav_follow_stats", "mnav_follow_rollout", "mnav_rollout_stats", "mnav_fleet_rollout", "mnav_fleet_rollout_stats",
     "mnav_map_configure", "mnav_map_compute", "mnav_map_layer_changed", "mnav_map_update_layer", "mnav_map_obstacle", "mnav_map_stats",
     "mnav_replan_dijkstra_batch", "mnav_replan_plans", "mnav_replan_stats", "mnav_replan_dijkstra_each", "mnav_replan_each_stats",
     "mnav_replan_warm_stats",
@@ -110,6 +110,19 @@ class RolloutConfig(C.Structure):
 ROLLOUT_RUNNING, ROLLOUT_REACHED, ROLLOUT_OUT_OF_MAP, ROLLOUT_NO_FIELD = 0, 1, 2, 3
 
 
+class SeparationConfig(C.Structure):
+    """mnav_separation_config (include/mnav.h): the radius of the separation check of a fleet rollout, the ticks between
+    two checks and the MNAV_SEP_* flags."""
+    _fields_ = [("radius", C.c_double), ("check_stride", C.c_uint32), ("flags", C.c_uint32)]
+    DEFAULTS = dict(radius=0.5, check_stride=1, flags=0)
+
+    def __init__(self, **kw):
+        super().__init__(**{**self.DEFAULTS, **kw})
+
+
+SEP_WAITING_PRESENT, SEP_REACHED_PRESENT = 1, 2
+
+
 class MapNode(C.Structure):
     """mnav_map_node (include/mnav.h): one node of the resident layer graph"""
     _fields_ = [("layer", C.c_uint32), ("kind", C.c_uint32), ("n_inputs", C.c_uint32), ("inputs", C.c_uint32 * 8),
@@ -148,6 +161,22 @@ class RolloutOut:
     trace: np.ndarray | None      # (n, ticks // trace_stride, 3) float32, or None without a trace
     cancelled: bool = False
 
+
+@dataclass
+class FleetRolloutOut(RolloutOut):
+    """One mnav_fleet_rollout call: RolloutOut and the separation outputs, one row per robot (None without a separation
+    config or where not asked for).  `skipped`: the guard skipped at least one check (fleet_rollout_stats tells which)."""
+    near_checks: np.ndarray | None = None
+    max_partners: np.ndarray | None = None
+    first_near_tick: np.ndarray | None = None
+    first_near_robot: np.ndarray | None = None
+    min_sep2: np.ndarray | None = None
+    min_sep_tick: np.ndarray | None = None
+    min_sep_robot: np.ndarray | None = None
+    skipped: bool = False
+
+
+SEPARATION_OUTPUTS = ("near_checks", "max_partners", "first_near_tick", "first_near_robot", "min_sep2", "min_sep_tick", "min_sep_robot")
 
 _lib = None
 
@@ -201,6 +230,10 @@ def load(path: str | None = None):
     L.mnav_follow_stats.argtypes = [vp] + [C.POINTER(u32)] * 6 + [C.POINTER(C.c_float)] * 2
     L.mnav_follow_rollout.restype = C.c_int
     L.mnav_follow_rollout.argtypes = [vp, u32] + [vp] * 8 + [C.POINTER(FollowConfig), C.POINTER(RolloutConfig)] + [vp] * 9
+    L.mnav_fleet_rollout.restype = C.c_int
+    L.mnav_fleet_rollout.argtypes = [vp, u32] + [vp] * 8 + [C.POINTER(FollowConfig), C.POINTER(RolloutConfig), vp, C.POINTER(SeparationConfig)] + [vp] * 16
+    L.mnav_fleet_rollout_stats.restype = C.c_int
+    L.mnav_fleet_rollout_stats.argtypes = [vp] + [vp] * 20
     L.mnav_rollout_stats.restype = C.c_int
     L.mnav_rollout_stats.argtypes = [vp, C.POINTER(u32 * 4)] + [C.POINTER(C.c_uint64)] * 4 + [C.POINTER(u32)] + [C.POINTER(C.c_float)] * 2
     L.mnav_map_configure.restype = C.c_int
@@ -1508,6 +1541,55 @@ class MnavContext:
         names = ("robot_ticks", "stayed", "neighbour", "global")
         return dict(running=sc[0], reached=sc[1], out_of_map=sc[2], no_field=sc[3], **{k: x.value for k, x in zip(names, v)},
                     built_index=b.value, ms_kernels=mk.value, ms_total=mt.value)
+
+    def fleet_rollout(self, pos, direction, up, face_in, slots, seed_faces=None, goal_pos=None, goal_dir=None, config: FollowConfig | None = None,
+                      rollout: RolloutConfig | None = None, start_tick=None, separation: SeparationConfig | None = None, outputs=None) -> FleetRolloutOut:
+        """rollout() with a departure tick per robot (start_tick: n entries or None) and, with `separation`, a check between
+        the robots on the device after every separation.check_stride-th tick (mnav_fleet_rollout, include/mnav.h).
+        `outputs`: the names of the FleetRolloutOut fields to fetch (default: all; the separation outputs only with
+        `separation`)."""
+        p, d, u = (_f32(a).reshape(-1, 3) for a in (pos, direction, up))
+        fi, sl = _u32(face_in).reshape(-1), _u32(slots).reshape(-1)
+        n = int(p.shape[0])
+        if not (d.shape[0] == u.shape[0] == fi.shape[0] == sl.shape[0] == n):
+            raise ValueError("fleet_rollout: the per-robot arrays differ in length")
+        sf = None if seed_faces is None else _u32(seed_faces).reshape(-1)
+        st = None if start_tick is None else _u32(start_tick).reshape(-1)
+        if any(a is not None and a.shape[0] != n for a in (sf, st)):
+            raise ValueError("fleet_rollout: seed_faces / start_tick need one entry per robot")
+        gp = None if goal_pos is None else _f32(goal_pos).reshape(-1, 3)
+        gd = None if goal_dir is None else _f32(goal_dir).reshape(-1, 3)
+        if any(g is not None and g.shape[0] != n for g in (gp, gd)):
+            raise ValueError("fleet_rollout: goal_pos / goal_dir need one row per robot")
+        cfg = config if config is not None else FollowConfig()
+        ro = rollout if rollout is not None else RolloutConfig()
+        rows = int(ro.ticks) // int(ro.trace_stride) if ro.trace_stride else 0
+        shapes = dict(status=((n,), np.int32), ticks=((n,), np.uint32), pos=((n, 3), np.float32), dir=((n, 3), np.float32), face=((n,), np.uint32),
+                      travel=((n,), np.float64), cost_integral=((n,), np.float64), min_goal_dist=((n,), np.float32))
+        if separation is not None:
+            shapes.update({k: ((n,), np.float32 if k == "min_sep2" else np.uint32) for k in SEPARATION_OUTPUTS})
+        want = set(shapes) if outputs is None else set(outputs)
+        o = {k: (np.zeros(*shapes[k]) if k in want else None) for k in shapes}
+        o["trace"] = np.zeros((n, rows, 3), np.float32) if ro.trace_stride else None
+        rc = self._L.mnav_fleet_rollout(self._h, n, _p(p), _p(d), _p(u), _p(fi), _p(sl), _p(sf), _p(gp), _p(gd), C.byref(cfg), C.byref(ro), _p(st),
+                                        None if separation is None else C.byref(separation),
+                                        _p(o["status"]), _p(o["ticks"]), _p(o["pos"]), _p(o["dir"]), _p(o["face"]), _p(o["travel"]),
+                                        _p(o["cost_integral"]), _p(o["min_goal_dist"]), _p(o["trace"]), *[_p(o.get(k)) for k in SEPARATION_OUTPUTS])
+        if rc < 0:
+            raise RuntimeError(f"mnav_fleet_rollout failed: {self._err()}")
+        return FleetRolloutOut(**o, cancelled=rc == 1, skipped=rc == 2)
+
+    def fleet_rollout_stats(self) -> dict:
+        sc, pair = (C.c_uint32 * 4)(), (C.c_uint32 * 2)()
+        u64, u32, f32 = C.c_uint64, C.c_uint32, C.c_float
+        spec = [("robot_ticks", u64), ("stayed", u64), ("neighbour", u64), ("global", u64), ("built_index", u32), ("checks_run", u32), ("checks_skipped", u32),
+                ("first_skipped_tick", u32), ("robots_near", u32), ("near_pairs", u64), ("max_pairs", u64), ("max_pairs_tick", u32), ("min_sep2", f32),
+                ("min_pair", None), ("tests", u64), ("max_cell", u32), ("ms_separation", f32), ("ms_kernels", f32), ("ms_total", f32)]
+        v = {k: (pair if t is None else t()) for k, t in spec}
+        self._L.mnav_fleet_rollout_stats(self._h, C.byref(sc), *[C.byref(v[k]) for k, _ in spec])
+        out = dict(running=sc[0], reached=sc[1], out_of_map=sc[2], no_field=sc[3])
+        out.update({k: ((pair[0], pair[1]) if t is None else v[k].value) for k, t in spec})
+        return out
 
     def plan_dijkstra_batch_at(self, goal_pos, start_pos, goal_dist_offset: float = 0.3, cost_limit: float = 1.0,
                                want_fields: bool = False, path_cap: int | None = None, want_stats: bool = True):

@@ -44,7 +44,9 @@
   X(timed_traffic_max_mb) /* timed fleet traffic: MiB of cells and holders (8 bytes per vertex and window; 20 with the tentative arrays of a fleet schedule) a call may take (default 2048; 0 refuses every call) */ \
   X(timed_peak_blocks)   /* timed fleet traffic: blocks of the peak pass, which stride over the vertices (default 2048; the result does not depend on it; tests force the strided path) */ \
   X(schedule_chunk_rounds) /* fleet schedule: rounds enqueued between two looks of the host at the control record (default 8; the result does not depend on it) */ \
-  X(schedule_clean_fill) /* fleet schedule: 1 = the tentative arrays are filled between the rounds, 0 = the claimants clean their own words in the commit pass (default 0; the result does not depend on it) */
+  X(schedule_clean_fill) /* fleet schedule: 1 = the tentative arrays are filled between the rounds, 0 = the claimants clean their own words in the commit pass (default 0; the result does not depend on it) */ \
+  X(separation_cell_scale) /* fleet rollout: side of the separation check's grid cells in radii, 1 .. 4 (default 2; the result does not depend on it) */ \
+  X(separation_max_tests) /* fleet rollout: a check whose pair pass would perform more distance tests than this is skipped (default 2^32, provisional: DESIGN.md section 3.20) */
 
 struct Options {
 #define X(name) double name = NAN;

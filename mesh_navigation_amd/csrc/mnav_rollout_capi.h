@@ -27,6 +27,25 @@ static int rollout_reserve(mnav_ctx* ctx, size_t n, bool goals, size_t ticks, si
   return 0;
 }
 
+// The argument checks of a rollout beside the follower's (mnav_follow_rollout, mnav_fleet_rollout), all on the host: -1 with
+// ctx->err set, or 0.
+static int rollout_check(mnav_ctx* ctx, const float* goal_pos, const float* goal_dir, const mnav_follow_config* config, const mnav_rollout_config* rollout,
+                         const float* trace_out)
+{
+  using namespace mnav_rol;
+  if (!rollout) { ctx->err = "rollout: null argument"; return -1; }
+  if (!(rollout->dt > 0.0) || !std::isfinite(rollout->dt)) { ctx->err = "rollout: dt must be positive and finite"; return -1; }
+  if (rollout->ticks < 1 || rollout->ticks > kMaxTicks) { ctx->err = "rollout: ticks out of range (1 .. 100000)"; return -1; }
+  if (rollout->trace_stride && !trace_out) { ctx->err = "rollout: trace_stride without trace_out"; return -1; }
+  if (rollout->trace_stride > rollout->ticks) { ctx->err = "rollout: trace_stride larger than ticks"; return -1; }
+  if (!goal_pos != !goal_dir) { ctx->err = "rollout: goal_pos and goal_dir go together"; return -1; }
+  if (std::isnan(rollout->dist_tolerance) || std::isnan(rollout->angle_tolerance)) { ctx->err = "rollout: dist_tolerance / angle_tolerance is NaN"; return -1; }
+  // the restated sinf / cosf are the host libm's on (-120, 120) only; NaN parameters give NaN commands, which std::min caps
+  const double turn = std::fabs(config->max_ang_velocity) * std::fmax(1.0, std::fabs(config->ang_vel_factor)) * rollout->dt;   // bounds |ang * dt|
+  if (!(turn < 100.0)) { ctx->err = "rollout: max_ang_velocity * max(1, ang_vel_factor) * dt must stay below 100 rad per tick"; return -1; }
+  return 0;
+}
+
 int mnav_follow_rollout(mnav_ctx* ctx, uint32_t n, const float* pos, const float* dir, const float* up, const uint32_t* face_in, const uint32_t* slots,
                         const uint32_t* seed_faces, const float* goal_pos, const float* goal_dir, const mnav_follow_config* config,
                         const mnav_rollout_config* rollout, int32_t* status_out, uint32_t* ticks_out, float* pos_out, float* dir_out, uint32_t* face_out,
@@ -40,16 +59,7 @@ int mnav_follow_rollout(mnav_ctx* ctx, uint32_t n, const float* pos, const float
   // every refusal comes before the first device call: a refused call touches nothing
   std::vector<const float*> maps;
   if (follow_check(ctx, n, pos, dir, up, face_in, slots, seed_faces, config, maps)) return -1;
-  if (!rollout) { ctx->err = "rollout: null argument"; return -1; }
-  if (!(rollout->dt > 0.0) || !std::isfinite(rollout->dt)) { ctx->err = "rollout: dt must be positive and finite"; return -1; }
-  if (rollout->ticks < 1 || rollout->ticks > kMaxTicks) { ctx->err = "rollout: ticks out of range (1 .. 100000)"; return -1; }
-  if (rollout->trace_stride && !trace_out) { ctx->err = "rollout: trace_stride without trace_out"; return -1; }
-  if (rollout->trace_stride > rollout->ticks) { ctx->err = "rollout: trace_stride larger than ticks"; return -1; }
-  if (!goal_pos != !goal_dir) { ctx->err = "rollout: goal_pos and goal_dir go together"; return -1; }
-  if (std::isnan(rollout->dist_tolerance) || std::isnan(rollout->angle_tolerance)) { ctx->err = "rollout: dist_tolerance / angle_tolerance is NaN"; return -1; }
-  // the restated sinf / cosf are the host libm's on (-120, 120) only; NaN parameters give NaN commands, which std::min caps
-  const double turn = std::fabs(config->max_ang_velocity) * std::fmax(1.0, std::fabs(config->ang_vel_factor)) * rollout->dt;   // bounds |ang * dt|
-  if (!(turn < 100.0)) { ctx->err = "rollout: max_ang_velocity * max(1, ang_vel_factor) * dt must stay below 100 rad per tick"; return -1; }
+  if (rollout_check(ctx, goal_pos, goal_dir, config, rollout, trace_out)) return -1;
   const uint32_t ticks = rollout->ticks, stride = rollout->trace_stride, rows = stride ? ticks / stride : 0;
   if (hipSetDevice(ctx->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return -1; }
   cancel_reset(ctx);                                                  // as the plan calls do

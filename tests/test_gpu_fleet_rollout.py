@@ -1,0 +1,340 @@
+"""The fleet rollout on the device (mnav_fleet_rollout, mnav_fleet_rollout_stats): without start ticks and separation it is
+mnav_follow_rollout bit for bit; with start ticks every robot is mnav_follow_rollout's robot run for the ticks that are left,
+its trace moved down; the separation outputs against tests/separation_model.py, the O(n^2) numpy restatement, every output by
+its bits; a cell wider than a wave; the guard; runs repeated and at other cell scales; refusals; the cancel flag.  On the
+64 x 64 terrain and the punched mesh of tests/test_gpu_rollout.py."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from mesh_navigation_amd import capi
+from tests import follow_model as FM
+from tests import locate_model as LM
+from tests import rollout_model as RM
+from tests import separation_model as SM
+from tests.test_gpu_rollout import SATURATING, World
+from tests.test_rollout_model import ANG_TOL, DIST_TOL, DT, TICKS
+from tests.test_separation_model import with_stranded
+
+pytestmark = pytest.mark.gpu
+
+F32 = np.float32
+RADIUS = 0.3
+STATE = RM.KEYS + ("trace",)
+
+
+@pytest.fixture(scope="module")
+def worlds(gpu_ctx_factory):
+    made = {}
+
+    def get(kind):
+        if kind not in made:
+            made[kind] = World(gpu_ctx_factory(), kind)
+        return made[kind]
+
+    return get
+
+
+def fleet_run(w, cfg, robots, goals, ticks, start_tick=None, separation=None, trace_stride=1, outputs=None):
+    ro = capi.RolloutConfig(dt=DT, dist_tolerance=DIST_TOL, angle_tolerance=ANG_TOL, ticks=ticks, trace_stride=trace_stride)
+    g = (None, None) if goals is None else goals
+    return w.ctx.fleet_rollout(robots["pos"], robots["dir"], robots["up"], robots["face_in"], robots["slot"], robots.get("seed_face"), g[0], g[1],
+                               capi.FollowConfig(**cfg), ro, start_tick, separation, outputs)
+
+
+def take(robots, goals, idx):
+    return {k: (None if v is None else v[idx]) for k, v in robots.items()}, (goals[0][idx], goals[1][idx])
+
+
+def starts(n):
+    """start ticks of a fleet: most robots leave at once, every fifth after 10 ticks, some after 1 or 40, one never"""
+    if n == 2:
+        return np.array([0, 3], np.uint32)
+    st = np.zeros(n, np.uint32)
+    st[::5] = 10
+    st[1::7] = 1
+    st[3::11] = 40
+    st[2] = 1000
+    return st
+
+
+def converging_fleet(w, n):
+    """n robots of which two are stranded beside the mesh (with_stranded) and at least a dozen head for the shared goal in
+    the middle of the mesh, several per plan; n = 2: one of those and a second one that starts 5 cm beside it on the same plan"""
+    if n == 2:
+        robots, goals = w.fleet(40, 0, 2, close=2)
+        robots["pos"][1] = robots["pos"][0] + np.array([0, 0.05, 0], F32)
+        robots["dir"][1], robots["slot"][1], robots["face_in"][1] = robots["dir"][0], robots["slot"][0], FM.NONE
+    else:
+        per_family = 3 if n == 65 else 9
+        robots, goals = with_stranded(w.model, *w.fleet(40, per_family, n - 9 * per_family - 2, close=12 if n == 65 else 40))
+    assert robots["pos"].shape[0] == n
+    return robots, goals
+
+
+@pytest.mark.parametrize("kind,cfg_name", [("async", "default"), ("tile_batch", "saturating"), ("cvp", "default")])
+def test_without_start_ticks_and_separation_it_is_the_rollout(worlds, kind, cfg_name):
+    w = worlds(kind)
+    cfg = SATURATING if cfg_name == "saturating" else FM.config()
+    robots, goals = w.fleet(42 if kind == "cvp" else 40, 3, 38)
+    assert robots["pos"].shape[0] == 65
+    want = w.device_run(cfg, robots, goals, TICKS)
+    rs = w.ctx.rollout_stats()
+    got = fleet_run(w, cfg, robots, goals, TICKS)
+    assert not got.cancelled and not got.skipped and got.near_checks is None and got.min_sep2 is None
+    RM.assert_same(got, {k: getattr(want, k) for k in STATE}, kind)
+    assert len(set(want.status.tolist())) == 4
+    fs = w.ctx.fleet_rollout_stats()
+    for k in ("running", "reached", "out_of_map", "no_field", "robot_ticks", "stayed", "neighbour", "global"):
+        assert fs[k] == rs[k], (k, fs, rs)
+    assert fs["checks_run"] == 0 and fs["checks_skipped"] == 0 and fs["tests"] == 0 and fs["ms_separation"] == 0 and fs["ms_kernels"] > 0
+    assert w.ctx.rollout_stats() == rs                                # the rollout's statistics keep their values
+    got7 = fleet_run(w, cfg, robots, goals, TICKS, start_tick=np.zeros(65, np.uint32), trace_stride=7)
+    RM.assert_same(got7, {k: getattr(want, k) for k in RM.KEYS}, (kind, "start ticks of 0"), keys=RM.KEYS)
+    assert FM.same_bits(got7.trace, SM.thin(want.trace, 7))
+
+
+def test_start_ticks_shorten_the_run_and_shift_the_trace(worlds):
+    w = worlds("async")
+    cfg, ticks = FM.config(), 300
+    robots, goals = w.fleet(40, 3, 38)
+    n = robots["pos"].shape[0]
+    start = np.array([0, 1, 7, 260, 300, 301, 1000], np.uint32)[np.arange(n) % 7]
+    got = fleet_run(w, cfg, robots, goals, ticks, start_tick=start)
+    assert not got.cancelled
+    for s in np.unique(start):
+        g = np.nonzero(start == s)[0]
+        own = ticks - min(int(s), ticks)
+        sub, sub_goals = take(robots, goals, g)
+        if own == 0:                                                  # comes back as it went in
+            assert (got.status[g] == RM.RUNNING).all() and (got.ticks[g] == 0).all() and (got.travel[g] == 0).all() and np.isinf(got.min_goal_dist[g]).all()
+            assert FM.same_bits(got.pos[g], sub["pos"]) and FM.same_bits(got.dir[g], sub["dir"]) and np.array_equal(got.face[g], sub["face_in"])
+            assert FM.same_bits(got.trace[g], np.repeat(sub["pos"][:, None, :], ticks, axis=1))
+            continue
+        want = w.device_run(cfg, sub, sub_goals, own)
+        RM.assert_same({k: getattr(got, k)[g] for k in RM.KEYS}, {k: getattr(want, k) for k in RM.KEYS}, ("start tick", int(s)), keys=RM.KEYS)
+        assert FM.same_bits(got.trace[g][:, int(s):], want.trace) and FM.same_bits(got.trace[g][:, : int(s)], np.repeat(sub["pos"][:, None, :], int(s), axis=1))
+    assert (got.ticks[start == 260] > 0).any() and len(set(got.status.tolist())) >= 3
+    # resumed in two calls with the start ticks reduced by the ticks already run: the state bits of one call
+    a = fleet_run(w, cfg, robots, goals, 100, start_tick=start, trace_stride=0)
+    run = np.nonzero(a.status == RM.RUNNING)[0]
+    sub = dict(pos=a.pos[run], dir=a.dir[run], up=robots["up"][run], face_in=a.face[run], slot=robots["slot"][run])
+    b = fleet_run(w, cfg, sub, (goals[0][run], goals[1][run]), 200, start_tick=np.maximum(start[run].astype(np.int64) - 100, 0), trace_stride=0)
+    for k in ("status", "pos", "dir", "face"):
+        assert FM.same_bits(getattr(b, k), getattr(got, k)[run]), k
+    assert np.array_equal(a.ticks[run] + b.ticks, got.ticks[run])
+
+
+@pytest.fixture(scope="module")
+def model_runs(worlds):
+    """the model's state, stride-1 trace and statuses of a converging fleet of n robots over `ticks` ticks, computed once"""
+    made = {}
+
+    def get(n, ticks):
+        if (n, ticks) not in made:
+            w = worlds("async")
+            robots, goals = converging_fleet(w, n)
+            start = starts(n)
+            made[(n, ticks)] = (robots, goals, start, SM.departures(w.model, FM.config(), w.fields, robots, goals, DT, ticks, DIST_TOL, ANG_TOL, start))
+        return made[(n, ticks)]
+
+    return get
+
+
+def check_sep_stats(st, want, ticks, check_stride):
+    ms = want["stats"]
+    for k in ("checks_run", "checks_skipped", "first_skipped_tick", "robots_near", "near_pairs", "max_pairs", "max_pairs_tick", "min_pair"):
+        assert st[k] == ms[k], (k, st, ms)
+    assert FM.same_bits(np.array([st["min_sep2"]], F32), np.array([ms["min_sep2"]], F32))
+    assert st["tests"] >= 2 * ms["near_pairs"] and st["max_cell"] >= 1 and 0 < st["ms_separation"] < st["ms_kernels"] <= st["ms_total"]
+
+
+# 65: one robot past a wave; 257: one past the stay pass's workgroup; 300 ticks at stride 7: checks in both blocks of the tick
+# loop (252, 259), none on the block boundary
+@pytest.mark.parametrize("flags", [0, 1, 2, 3])
+@pytest.mark.parametrize("n,ticks,check_stride", [(2, TICKS, 1), (65, TICKS, 1), (65, TICKS, 7), (257, TICKS, 1), (65, 300, 7)])
+def test_separation_equals_the_model(worlds, model_runs, n, ticks, check_stride, flags):
+    w = worlds("async")
+    robots, goals, start, late = model_runs(n, ticks)
+    want = SM.separation(late["trace"], late["status_at"], start, RADIUS, check_stride, flags)
+    stranded = np.isin(late["status"], (RM.OUT_OF_MAP, RM.NO_FIELD))
+    print(n, ticks, check_stride, flags, "status:", np.bincount(late["status"], minlength=4), want["stats"], "first != min:",
+          int((want["first_near_robot"] != want["min_sep_robot"]).sum()), "stranded partners:", int((want["partner_of"] & stranded).sum()))
+    # conditions on the MODEL's output: robots with near events and without, a first-near partner that is not the closest
+    # one, a stranded robot that is a partner, several robots per plan on the way to the shared goal
+    assert want["stats"]["near_pairs"] > 0
+    if n >= 65:
+        assert want["stats"]["robots_near"] >= 8 and (want["near_checks"] == 0).sum() >= 2
+        assert (want["first_near_robot"] != want["min_sep_robot"]).any() and (want["partner_of"] & stranded).any()
+        assert np.bincount(robots["slot"][late["status"] == RM.REACHED], minlength=w.n_plans).max() >= 2
+    got = fleet_run(w, FM.config(), robots, goals, ticks, start_tick=start, separation=capi.SeparationConfig(radius=RADIUS, check_stride=check_stride, flags=flags),
+                    trace_stride=check_stride)
+    assert not got.cancelled and not got.skipped
+    SM.assert_same_rows(got, want, (n, ticks, check_stride, flags))
+    RM.assert_same(got, late, "state", keys=RM.KEYS)
+    assert FM.same_bits(got.trace, SM.thin(late["trace"], check_stride))                 # the positions a check reads are a trace row's
+    check_sep_stats(w.ctx.fleet_rollout_stats(), want, ticks, check_stride)
+
+
+def standing(n, pos):
+    """n robots that never depart (start tick beyond every call), at `pos`: nothing of the mesh is asked"""
+    pos = np.ascontiguousarray(np.broadcast_to(np.asarray(pos, F32), (n, 3)))
+    robots = dict(pos=pos, dir=np.tile(np.array([1, 0, 0], F32), (n, 1)), up=np.tile(np.array([0, 0, 1], F32), (n, 1)), face_in=np.full(n, FM.NONE, np.uint32),
+                  slot=np.zeros(n, np.uint32), seed_face=None)
+    return robots, np.full(n, 100000, np.uint32)
+
+
+def standing_model(robots, start, ticks, radius, check_stride, flags):
+    n = robots["pos"].shape[0]
+    return SM.separation(np.repeat(robots["pos"][:, None, :], ticks, axis=1), np.zeros((n, ticks), np.int32), start, radius, check_stride, flags)
+
+
+def test_seventy_waiting_robots_on_one_point(worlds):
+    w = worlds("async")
+    robots, start = standing(70, [1.0, 2.0, 0.5])
+    want = standing_model(robots, start, 8, 0.25, 1, SM.WAITING_PRESENT)
+    assert (want["max_partners"] == 69).all() and (want["near_checks"] == 8).all() and (want["first_near_robot"][1:] == 0).all()
+    got = fleet_run(w, FM.config(), robots, None, 8, start_tick=start, separation=capi.SeparationConfig(radius=0.25, check_stride=1, flags=capi.SEP_WAITING_PRESENT))
+    SM.assert_same_rows(got, want, "70 on a point")
+    assert (got.status == RM.RUNNING).all() and (got.ticks == 0).all() and FM.same_bits(got.pos, robots["pos"])
+    st = w.ctx.fleet_rollout_stats()
+    assert st["max_cell"] == 70 and st["tests"] == 8 * 70 * 70 and st["near_pairs"] == 8 * 70 * 69 // 2 and st["robot_ticks"] == 0
+    # without the flag waiting robots are not there
+    gone = fleet_run(w, FM.config(), robots, None, 8, start_tick=start, separation=capi.SeparationConfig(radius=0.25, check_stride=1))
+    SM.assert_same_rows(gone, SM.start_rows(70), "not present")
+    assert w.ctx.fleet_rollout_stats()["tests"] == 0
+
+
+def test_the_guard(worlds):
+    w = worlds("async")
+    ctx, n, ticks, r = w.ctx, 200, 6, 0.25
+    robots, start = standing(n, [1.0, 2.0, 0.5])
+    sep = capi.SeparationConfig(radius=r, check_stride=2, flags=capi.SEP_WAITING_PRESENT)
+    try:
+        ctx.set_option("separation_max_tests", 1000)
+        got = fleet_run(w, FM.config(), robots, None, ticks, start_tick=start, separation=sep)
+        assert got.skipped and not got.cancelled
+        SM.assert_same_rows(got, SM.start_rows(n), "every check skipped")            # the "never" values
+        st = ctx.fleet_rollout_stats()
+        assert (st["checks_run"], st["checks_skipped"], st["first_skipped_tick"]) == (0, 3, 2) and st["tests"] == 0 and st["near_pairs"] == 0
+        assert st["max_cell"] == n and st["min_pair"] == (SM.NONE, SM.NONE) and np.isinf(st["min_sep2"])
+        # the same fleet with the default: served
+        ctx.set_option("separation_max_tests", None)
+        want = standing_model(robots, start, ticks, r, 2, SM.WAITING_PRESENT)
+        got = fleet_run(w, FM.config(), robots, None, ticks, start_tick=start, separation=sep)
+        assert not got.skipped
+        SM.assert_same_rows(got, want, "served")
+        st = ctx.fleet_rollout_stats()
+        assert (st["checks_run"], st["checks_skipped"], st["first_skipped_tick"]) == (3, 0, SM.NONE) and st["tests"] == 3 * n * n
+        assert st["near_pairs"] == 3 * n * (n - 1) // 2 and st["min_pair"] == (0, 1) and st["min_sep2"] == 0
+        # robots at least 8 r apart: with cells of at most 2 r a robot examines no populated cell but its own, T is exactly n
+        grid = np.stack(np.meshgrid(np.arange(6), np.arange(6), np.arange(6), indexing="ij"), axis=-1).reshape(-1, 3)[:n]
+        apart, start = standing(n, (grid * 8 * r - 5.0).astype(F32))
+        for scale in (None, 1.0):
+            ctx.set_option("separation_cell_scale", scale)
+            ctx.set_option("separation_max_tests", n)
+            got = fleet_run(w, FM.config(), apart, None, ticks, start_tick=start, separation=sep)
+            assert not got.skipped
+            SM.assert_same_rows(got, SM.start_rows(n), "apart")
+            st = ctx.fleet_rollout_stats()
+            assert st["checks_run"] == 3 and st["tests"] == 3 * n and st["max_cell"] == 1
+            ctx.set_option("separation_max_tests", n - 1)
+            assert fleet_run(w, FM.config(), apart, None, ticks, start_tick=start, separation=sep).skipped
+    finally:
+        ctx.set_option("separation_max_tests", None)
+        ctx.set_option("separation_cell_scale", None)
+
+
+def test_two_runs_and_other_cell_scales_give_the_same_bits(worlds, model_runs):
+    w = worlds("async")
+    robots, goals, start, late = model_runs(65, TICKS)
+    sep = capi.SeparationConfig(radius=RADIUS, check_stride=1, flags=3)
+    first = fleet_run(w, FM.config(), robots, goals, TICKS, start_tick=start, separation=sep)
+    pairs = w.ctx.fleet_rollout_stats()["near_pairs"]
+    assert pairs > 0
+    try:
+        for scale in (None, 1.0, 4.0):
+            w.ctx.set_option("separation_cell_scale", scale)
+            again = fleet_run(w, FM.config(), robots, goals, TICKS, start_tick=start, separation=sep)
+            SM.assert_same_rows(again, {k: getattr(first, k) for k in SM.SEP_KEYS}, scale)
+            RM.assert_same(again, {k: getattr(first, k) for k in STATE}, scale)
+            st = w.ctx.fleet_rollout_stats()
+            assert st["near_pairs"] == pairs and st["checks_run"] == TICKS
+    finally:
+        w.ctx.set_option("separation_cell_scale", None)
+
+
+def test_refusals_touch_nothing(worlds):
+    w = worlds("async")
+    ctx, cfg = w.ctx, FM.config()
+    robots, goals = w.fleet(40, 3, 38)
+    n = robots["pos"].shape[0]
+    status4 = w.device_run(cfg, robots, goals, 4, trace_stride=0).status
+    ctx.follow(robots["pos"], robots["dir"], robots["up"], robots["face_in"], robots["slot"])
+    fleet_run(w, cfg, robots, goals, 4, separation=capi.SeparationConfig(radius=RADIUS))
+    field0, stats0, fstats0, rstats0, frstats0 = ctx.download_output("vecmap", 1), ctx.stats(), ctx.follow_stats(), ctx.rollout_stats(), ctx.fleet_rollout_stats()
+    sentinel = dict(status=np.full(n, -7, np.int32), pos=np.full((n, 3), -7.0, F32), travel=np.full(n, -7.0), trace=np.full((n, 4, 3), -7.0, F32),
+                    near_checks=np.full(n, 7, np.uint32), min_sep2=np.full(n, -7.0, F32), min_sep_robot=np.full(n, 7, np.uint32))
+    p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+    SC, RC = capi.SeparationConfig, capi.RolloutConfig
+
+    def call(fc=None, ro=None, sep=SC(radius=RADIUS), no_sep=False, pos=robots["pos"], slots=robots["slot"], gd=goals[1], trace=sentinel["trace"], start=None):
+        fc = fc if fc is not None else capi.FollowConfig(**cfg)
+        ro = ro if ro is not None else RC(dt=DT, ticks=4, trace_stride=1)
+        return ctx._L.mnav_fleet_rollout(ctx._h, n, p(pos), p(robots["dir"]), p(robots["up"]), p(robots["face_in"]), p(slots), None, p(goals[0]), p(gd),
+                                         C.byref(fc), C.byref(ro), p(start), None if no_sep else C.byref(sep), p(sentinel["status"]), None, p(sentinel["pos"]),
+                                         None, None, p(sentinel["travel"]), None, None, p(trace), p(sentinel["near_checks"]), None, None, None,
+                                         p(sentinel["min_sep2"]), None, p(sentinel["min_sep_robot"]))
+
+    refusals = [
+        # those of mnav_follow_rollout
+        (dict(pos=None), "null"), (dict(slots=np.full(n, w.n_plans, np.uint32)), "slot out of range"), (dict(fc=capi.FollowConfig(max_search_radius=0.0)), "max_search_radius"),
+        (dict(ro=RC(dt=0.0, ticks=4)), "dt"), (dict(ro=RC(dt=DT, ticks=0)), "ticks"), (dict(ro=RC(dt=DT, ticks=100001)), "ticks"),
+        (dict(ro=RC(dt=DT, ticks=4, trace_stride=1), trace=None), "trace_out"), (dict(ro=RC(dt=DT, ticks=4, trace_stride=5)), "trace_stride"), (dict(gd=None), "goal"),
+        (dict(ro=RC(dt=DT, ticks=4, dist_tolerance=float("nan"))), "tolerance"), (dict(fc=capi.FollowConfig(max_ang_velocity=400.0)), "100"),
+        # the separation's own
+        (dict(sep=SC(radius=0.0)), "radius"), (dict(sep=SC(radius=-1.0)), "radius"), (dict(sep=SC(radius=float("nan"))), "radius"),
+        (dict(sep=SC(radius=float("inf"))), "radius"), (dict(sep=SC(radius=1e20)), "radius"), (dict(sep=SC(radius=1e-30)), "radius"),
+        (dict(sep=SC(radius=RADIUS, check_stride=0)), "check_stride"), (dict(sep=SC(radius=RADIUS, check_stride=5)), "check_stride"),
+        (dict(sep=SC(radius=RADIUS, flags=4)), "flag"), (dict(sep=SC(radius=RADIUS, flags=0x80000001)), "flag"),
+        (dict(no_sep=True), "separation output"),
+    ]
+    for kw, text in refusals:
+        assert call(**kw) == -1 and text in ctx._err(), (kw, ctx._err())
+        assert all((v == (7 if v.dtype == np.uint32 else -7)).all() for v in sentinel.values()), kw
+    try:
+        ctx.set_option("separation_cell_scale", 0.5)
+        assert call() == -1 and "separation_cell_scale" in ctx._err()
+        ctx.set_option("separation_cell_scale", 4.5)
+        assert call() == -1 and "separation_cell_scale" in ctx._err()
+    finally:
+        ctx.set_option("separation_cell_scale", None)
+    assert all((v == (7 if v.dtype == np.uint32 else -7)).all() for v in sentinel.values())
+    # the resident field and the statistics of every entry point are what they were
+    assert np.array_equal(LM.bits(ctx.download_output("vecmap", 1)), LM.bits(field0)) and ctx.stats() == stats0 and ctx.follow_stats() == fstats0
+    assert ctx.rollout_stats() == rstats0 and ctx.fleet_rollout_stats() == frstats0
+    # served: the smallest radius whose square is positive, NULL outputs, n = 0
+    assert call(sep=SC(radius=1e-22, check_stride=4)) == 0 and (sentinel["status"] != -7).all() and (sentinel["near_checks"] <= 1).all()
+    assert (sentinel["min_sep2"] >= 0).all() and (sentinel["trace"] != -7.0).all()
+    only = fleet_run(w, cfg, robots, goals, 4, separation=SC(radius=RADIUS), trace_stride=0, outputs=("status", "max_partners"))
+    assert only.pos is None and only.near_checks is None and only.trace is None and only.max_partners is not None
+    assert np.array_equal(only.status, status4)
+    empty = ctx.fleet_rollout(np.zeros((0, 3)), np.zeros((0, 3)), np.zeros((0, 3)), np.zeros(0), np.zeros(0), separation=SC(radius=RADIUS))
+    assert empty.status.shape == (0,) and empty.near_checks.shape == (0,) and not empty.cancelled and not empty.skipped
+    # a served fleet rollout changes no plan output and no statistic of the planner, the follower or the rollout
+    assert np.array_equal(LM.bits(ctx.download_output("vecmap", 1)), LM.bits(field0)) and ctx.stats() == stats0 and ctx.follow_stats() == fstats0
+    assert ctx.rollout_stats() == rstats0 and rstats0["robot_ticks"] > 0
+
+
+def test_a_cancel_flag_set_before_the_call_is_cleared_at_entry(worlds, model_runs):
+    w = worlds("async")
+    robots, goals, start, late = model_runs(65, TICKS)
+    sep = capi.SeparationConfig(radius=RADIUS, check_stride=7, flags=1)
+    want = fleet_run(w, FM.config(), robots, goals, 20, start_tick=start, separation=sep)
+    w.ctx.cancel()
+    got = fleet_run(w, FM.config(), robots, goals, 20, start_tick=start, separation=sep)
+    assert not got.cancelled and not got.skipped and got.ticks.max() == 20
+    RM.assert_same(got, {k: getattr(want, k) for k in STATE}, "after a stale cancel")
+    SM.assert_same_rows(got, {k: getattr(want, k) for k in SM.SEP_KEYS}, "after a stale cancel")
+    assert w.ctx.fleet_rollout_stats()["checks_run"] == 2
