@@ -208,6 +208,9 @@ __global__ __launch_bounds__(64 * kFinWaves, MNAV_FIN_OCC) void k_tb_finalize(tb
   load_slice(p_beg, rcur, cur);
   rnxt = rcur;
   uint32_t bad = 0;
+  // A slice beyond the 256 slots of cur[]: a tile that is a column through several sheets of a folded mesh, never one of a terrain.
+  // Read through the first lane, so that what the tail costs a short slice is one scalar branch where it is handled.
+  const bool long_slice = (uint32_t)__builtin_amdgcn_readfirstlane((int)W.sl) > 256u;
   for (uint32_t p = p_beg; p < p_end; ++p) {
 #ifndef MNAV_FIN_NOSYNC
     __syncthreads();                                                  // the tiles of the patch write plan p together
@@ -218,7 +221,16 @@ __global__ __launch_bounds__(64 * kFinWaves, MNAV_FIN_OCC) void k_tb_finalize(tb
     MNAV_GLOBAL uint32_t* const g_pred = (MNAV_GLOBAL uint32_t*)(uintptr_t)(((unsigned long long)rw(3) << 32) | rw(2));
     MNAV_GLOBAL float* const g_vm = (MNAV_GLOBAL float*)(uintptr_t)(((unsigned long long)rw(5) << 32) | rw(4));
     const uint32_t seed = rw(6);
-    const bool reached = __ballot(cur[0] != kTbInfBits || cur[1] != kTbInfBits || cur[2] != kTbInfBits || cur[3] != kTbInfBits) != 0ull;
+    bool reached = __ballot(cur[0] != kTbInfBits || cur[1] != kTbInfBits || cur[2] != kTbInfBits || cur[3] != kTbInfBits) != 0ull;
+    if (!reached && long_slice) {
+      // cur[] is the slice's first 256 slots.  A longer slice keeps the ghosts of its last neighbour tiles beyond them, and a front that stops at the goal bound inside such a
+      // neighbour leaves finite values THERE alone: the tile was never activated, but its owned neighbours of those ghosts have the
+      // reference's tentative values, which the reached branch derives.  So the whole slice decides.
+      MNAV_GLOBAL const uint32_t* const s = (MNAV_GLOBAL const uint32_t*)(gD + (size_t)p * W.sl);
+      bool tail = false;
+      for (uint32_t i = lane + 256u; i < W.sl; i += 64) tail |= s[i] != kTbInfBits;
+      reached = __ballot(tail) != 0ull;
+    }
     uint32_t cnt = 0;
     const unsigned long long pbit = 1ull << (p & 63u);
     if (!reached) {                                                    // the plan's wave never came near this tile: dist = inf, pred = itself
@@ -231,8 +243,7 @@ __global__ __launch_bounds__(64 * kFinWaves, MNAV_FIN_OCC) void k_tb_finalize(tb
           if (g_vm) { const f32x3_u z3 = { 0.f, 0.f, 0.f }; *(MNAV_GLOBAL f32x3_u*)(g_vm + 3 * (size_t)gid[v]) = z3; }
         }
       }
-      // (the first 256 slots are +inf by the test above; a longer slice's tail is reset whatever it holds)
-      if (clean) for (uint32_t i = lane + 256u; i < W.sl; i += 64) gDw[(size_t)p * W.sl + i] = kTbInfBits;
+      // (every slot is +inf by the test above, a longer slice's tail included: nothing to reset)
     } else {
       GoalCut gcut; gcut.goal = 0.f; gcut.cut = u2f(rw(7)); gcut.tie = rw(8);   // dijkstra :296 (k_tb_fin_plans)
       __builtin_amdgcn_wave_barrier();                                 // (the previous plan's reads of ld[] are done: one wave, program order)
@@ -240,14 +251,14 @@ __global__ __launch_bounds__(64 * kFinWaves, MNAV_FIN_OCC) void k_tb_finalize(tb
       if (i1 < W.sl) ld[i1] = cur[1];
       if (i2 < W.sl) ld[i2] = cur[2];
       if (i3 < W.sl) ld[i3] = cur[3];
-      for (uint32_t i = lane + 256u; i < W.sl; i += 64) ld[i] = ((MNAV_GLOBAL const uint32_t*)(gD + (size_t)p * W.sl))[i];   // (slices beyond 256 slots: rare meshes)
+      if (long_slice) for (uint32_t i = lane + 256u; i < W.sl; i += 64) ld[i] = ((MNAV_GLOBAL const uint32_t*)(gD + (size_t)p * W.sl))[i];
       if (clean) {                                                     // the slice is in cur[] and ld[]: nothing reads it in A.D again, the next call finds +inf
         MNAV_GLOBAL uint32_t* const s = gDw + (size_t)p * W.sl;
         if (i0 < W.sl) s[i0] = kTbInfBits;
         if (i1 < W.sl) s[i1] = kTbInfBits;
         if (i2 < W.sl) s[i2] = kTbInfBits;
         if (i3 < W.sl) s[i3] = kTbInfBits;
-        for (uint32_t i = lane + 256u; i < W.sl; i += 64) s[i] = kTbInfBits;
+        if (long_slice) for (uint32_t i = lane + 256u; i < W.sl; i += 64) s[i] = kTbInfBits;
       }
       __builtin_amdgcn_wave_barrier();
 #pragma unroll

@@ -204,6 +204,67 @@ def fan_field(spokes: int = 40, rings: int = 6, seed: int = 0) -> TerrainMesh:
     return from_faces(xyz, np.asarray(faces, np.uint32))
 
 
+def lattice_faces(nu: int, nv: int, wrap_u: bool = False, wrap_v: bool = False) -> np.ndarray:
+    """The cells of a (u, v) lattice, vertex id ``j * nu + i``, cell-major with u fastest, each cell (a, b, c, d) =
+    ((i, j), (i+1, j), (i+1, j+1), (i, j+1)) split into (a, b, c), (a, c, d); a wrapped direction closes on itself."""
+    ci = np.arange(nu if wrap_u else nu - 1, dtype=np.int64)
+    cj = np.arange(nv if wrap_v else nv - 1, dtype=np.int64)
+    i, j = np.meshgrid(ci, cj)
+    i, j = i.ravel(), j.ravel()
+    i1, j1 = (i + 1) % nu, (j + 1) % nv
+    a, b, c, d = j * nu + i, j * nu + i1, j1 * nu + i1, j1 * nu + i
+    return np.stack([a, b, c, a, c, d], axis=1).reshape(-1, 3).astype(np.uint32)
+
+
+def ramp(nu: int = 320, nv: int = 12, turns: float = 8.0, pitch: float = 0.05, r0: float = 1.0, width: float = 1.2, seed: int = 0,
+         jitter: float = 0.2) -> TerrainMesh:
+    """A helicoidal ramp, open in both directions: `turns` storeys `pitch` apart over the same ground, u along the lane (nu
+    vertices), v across it (nv vertices from radius r0 to r0 + width).  The vertices are jittered inside the surface.  Valence
+    2..6.  With a pitch below the footprint a coordinate bisection cuts it into columns through every storey."""
+    rng = np.random.default_rng(seed)
+    ju = rng.uniform(-jitter, jitter, size=(nv, nu))
+    jv = rng.uniform(-jitter, jitter, size=(nv, nu))
+    i, j = np.meshgrid(np.arange(nu, dtype=np.float64), np.arange(nv, dtype=np.float64))
+    th = 2.0 * np.pi * turns * (i + ju) / (nu - 1)
+    rho = r0 + width * (j + jv) / (nv - 1)
+    xyz = np.stack([(rho * np.cos(th)).ravel(), (rho * np.sin(th)).ravel(), (pitch * th / (2.0 * np.pi)).ravel()], axis=1)
+    return from_faces(xyz.astype(np.float32), lattice_faces(nu, nv))
+
+
+def torus(nu: int = 64, nv: int = 32, R: float = 2.0, r: float = 0.8, seed: int = 0, jitter: float = 0.2) -> TerrainMesh:
+    """A torus, periodic in both directions (u around the axis, v around the tube): closed, Euler characteristic 0, valence 6
+    everywhere.  Jittered inside the surface."""
+    rng = np.random.default_rng(seed)
+    ju = rng.uniform(-jitter, jitter, size=(nv, nu))
+    jv = rng.uniform(-jitter, jitter, size=(nv, nu))
+    i, j = np.meshgrid(np.arange(nu, dtype=np.float64), np.arange(nv, dtype=np.float64))
+    th = 2.0 * np.pi * (i + ju) / nu
+    ph = 2.0 * np.pi * (j + jv) / nv
+    rho = R + r * np.cos(ph)
+    xyz = np.stack([(rho * np.cos(th)).ravel(), (rho * np.sin(th)).ravel(), (r * np.sin(ph)).ravel()], axis=1)
+    return from_faces(xyz.astype(np.float32), lattice_faces(nu, nv, True, True))
+
+
+def tube(nu: int = 48, nv: int = 40, r: float = 0.8, h: float = 3.0, seed: int = 0, jitter: float = 0.2) -> TerrainMesh:
+    """A vertical wall closed to a tube, periodic in u, open at the bottom and the top.  A column of the lattice is one vertical
+    line (its angle is jittered as a whole, its heights one by one), so every cell is a vertical quad and every normal is
+    horizontal."""
+    rng = np.random.default_rng(seed)
+    ju = rng.uniform(-jitter, jitter, size=nu)
+    jv = rng.uniform(-jitter, jitter, size=(nv, nu))
+    th = 2.0 * np.pi * (np.arange(nu, dtype=np.float64) + ju) / nu
+    x, y = (r * np.cos(th)).astype(np.float32), (r * np.sin(th)).astype(np.float32)
+    z = h * (np.arange(nv, dtype=np.float64)[:, None] + jv) / (nv - 1)
+    xyz = np.stack([np.tile(x, nv), np.tile(y, nv), z.ravel().astype(np.float32)], axis=1)
+    return from_faces(xyz, lattice_faces(nu, nv, True, False))
+
+
+def moved(mesh: TerrainMesh, t) -> TerrainMesh:
+    """The same faces with every vertex translated by t: added in float64, rounded to float32 once."""
+    xyz = (mesh.xyz.astype(np.float64) + np.asarray(t, np.float64).reshape(1, 3)).astype(np.float32)
+    return TerrainMesh(N=mesh.N, h=mesh.h, xyz=xyz, faces=mesh.faces, edges=mesh.edges, face_edges=mesh.face_edges)
+
+
 def union_jack(N: int, h: float = 0.1, seed: int = 0, amplitude: float = 0.5, flat: bool = False) -> TerrainMesh:
     """The terrain's vertices with the cell diagonal alternating with (i + j) % 2: interior vertices alternate between
     valence 8 ((i + j) even) and valence 4.  `flat` takes flat_grid's vertices instead (terrain jitters x and y, so

@@ -440,6 +440,31 @@ def tile_batch_model(xyz, faces, edges, edge_weights, vertex_costs, seeds, targe
                 blocks_total=int(stats[8]), blocks_evaluated=int(stats[9]), stale_reads=int(stats[10]), max_ghosts=int(stats[11]))
 
 
+def tile_batch_tiling(xyz, faces, edges, tile=120):
+    """The tiling of the tile-batch engine (mnav_tb_build.h build_tb, the one the device uploads), by oracle/tb_model.cpp: per
+    vertex `vert_tile` and `vert_local` (its slot in the tile's slice); per tile `nv`, `nh` (ghosts), `sl` (slice length) and
+    `goff`; `ghost_gid[goff[t] + k]` is the vertex in slot `tile + k` of tile t's slice."""
+    faces, edges, pos = _u32(faces), _u32(edges), _f32(xyz)
+    V, F, E = pos.reshape(-1, 3).shape[0], faces.shape[0], edges.shape[0]
+    L = model_lib()
+    vp, u32 = C.c_void_p, C.c_uint32
+    L.tbm_tiling.restype = u32
+    L.tbm_tiling.argtypes = [u32, u32, u32, vp, vp, vp, u32, vp, vp, vp, u32, vp, vp, vp, vp, u32, vp]
+    counts = np.zeros(4, np.uint64)
+    code = L.tbm_tiling(V, F, E, _p(faces), _p(edges), _p(pos), int(tile), _p(counts), None, None, 0, None, None, None, None, 0, None)
+    if code:
+        raise RuntimeError(f"tbm_tiling: {code}")
+    nt, ng = int(counts[0]), int(counts[1])
+    vt, vl = np.empty(V, np.uint32), np.empty(V, np.uint32)
+    nv, nh, sl, goff = (np.empty(nt, np.uint32) for _ in range(4))
+    gid = np.empty(ng, np.uint32)
+    code = L.tbm_tiling(V, F, E, _p(faces), _p(edges), _p(pos), int(tile), _p(counts), _p(vt), _p(vl), nt, _p(nv), _p(nh), _p(sl), _p(goff), ng, _p(gid))
+    if code:
+        raise RuntimeError(f"tbm_tiling: {code}")
+    return dict(tile=int(tile), tiles=nt, max_ghosts=int(counts[2]), max_slice=int(counts[3]), vert_tile=vt, vert_local=vl, nv=nv, nh=nh, sl=sl,
+                goff=goff, ghost_gid=gid)
+
+
 def async_tile_model(xyz, faces, edges, edge_weights, vertex_costs, seeds, targets, offset=0.3, cost_limit=1.0, tile=64, band=0.0,
                      workgroups=4, sched_seed=1, budget=50_000_000, invalid=None, mutate=0, ring_cap=None):
     """The PROTOCOL of the asynchronous tile engine (mnav_async.h: ticket queue of woken tiles) on the CPU model

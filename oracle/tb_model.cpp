@@ -286,6 +286,31 @@ uint32_t tbm_run(uint32_t V, uint32_t F, uint32_t E, const uint32_t* face_vtx, c
   return 0;
 }
 
+// The tiling itself, for tests that choose plans by it: build_tb's, the one the device uploads.  counts_out: [0] tiles, [1] ghosts
+// of all tiles, [2] most ghosts of a tile, [3] longest slice.  Every array may be null (a first call for the sizes); tile_cap and
+// ghost_cap are the lengths of the per-tile arrays and of ghost_gid.  Per vertex: its tile and its slot there; per tile: nv, nh,
+// sl and goff, the position of its first ghost in ghost_gid (ghosts in slice order: slot T + k holds ghost_gid[goff + k]).
+uint32_t tbm_tiling(uint32_t V, uint32_t F, uint32_t E, const uint32_t* face_vtx, const uint32_t* edge_vtx, const float* xyz, uint32_t T,
+                    uint64_t* counts_out, uint32_t* vert_tile, uint32_t* vert_local, uint32_t tile_cap, uint32_t* nv, uint32_t* nh, uint32_t* sl,
+                    uint32_t* goff, uint32_t ghost_cap, uint32_t* ghost_gid)
+{
+  HostTopology topo = build_topology(V, F, E, face_vtx, edge_vtx);
+  HostTb H;
+  try { H = build_tb(topo, xyz, T); }
+  catch (const std::exception& ex) { fprintf(stderr, "tbm_tiling: %s\n", ex.what()); return 64; }
+  if (counts_out) { counts_out[0] = H.ntiles; counts_out[1] = H.ghost_gid.size(); counts_out[2] = H.max_nh; counts_out[3] = H.max_sl; }
+  if (vert_tile) std::copy(H.vert_tile.begin(), H.vert_tile.end(), vert_tile);
+  if (vert_local) std::copy(H.vert_local.begin(), H.vert_local.end(), vert_local);
+  for (uint32_t t = 0; t < H.ntiles && t < tile_cap; ++t) {
+    if (nv) nv[t] = H.tiles[t].nv;
+    if (nh) nh[t] = H.tiles[t].nh;
+    if (sl) sl[t] = H.tiles[t].sl;
+    if (goff) goff[t] = H.tiles[t].goff;
+  }
+  if (ghost_gid) std::copy(H.ghost_gid.begin(), H.ghost_gid.begin() + std::min<size_t>(ghost_cap, H.ghost_gid.size()), ghost_gid);
+  return 0;
+}
+
 // the pair of mnav::tb_div_magic against the division it replaces: every n of [n_lo, n_hi) in steps of `stride`, and the values
 // around every multiple of d in that range when `edges` is set; returns the number of differences
 unsigned long long tbm_div_magic_check(uint32_t d, uint32_t n_lo, uint32_t n_hi, uint32_t stride, int edges)

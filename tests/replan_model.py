@@ -29,12 +29,17 @@ def bits(a):
 
 
 @functools.lru_cache(maxsize=None)
-def terrain(N: int) -> Case:
+def _terrain(N: int) -> Case:
     return Case(meshgen.terrain(N, 0.1, N))
 
 
+def terrain(N) -> Case:
+    """the mesh behind a World's key: terrain(N) for a number, the case a World was given for a name (World(name, ..., case=...))"""
+    return World.named[N] if N in World.named else _terrain(N)
+
+
 @functools.lru_cache(maxsize=None)
-def adjacency(N: int):
+def adjacency(N):
     """per vertex: (neighbour, edge id) pairs"""
     m = terrain(N).mesh
     adj = [[] for _ in range(m.V)]
@@ -46,13 +51,19 @@ def adjacency(N: int):
 class World:
     """A terrain(N) with the cost state both contexts of a GPU test hold.  computed: the weights are derived from the costs
     with edge_cost_factor 1 (mnav_compute_edge_weights; mnav_update_costs re-weights the incident edges); otherwise they
-    are the caller's (mnav_upload_costs; only mnav_update_edge_weights changes them)."""
+    are the caller's (mnav_upload_costs; only mnav_update_edge_weights changes them).  With `case` the world stands on that
+    mesh instead and N is its name, a string: the key of adjacency() and of the rule's helpers (v, rect, ring and column are the
+    terrain's)."""
 
-    def __init__(self, N: int, computed: bool):
+    named = {}                          # name -> the case given for it (one mesh per name)
+
+    def __init__(self, N, computed: bool, case: Case | None = None):
+        if case is not None:
+            assert isinstance(N, str) and World.named.setdefault(N, case) is case
         self.N, self.computed = N, computed
         self.case = terrain(N)
         self.mesh, self.om = self.case.mesh, self.case.om
-        self.costs = (np.random.default_rng(N).random(self.mesh.V) * 0.8).astype(f32)
+        self.costs = (np.random.default_rng(N if case is None else len(N)).random(self.mesh.V) * 0.8).astype(f32)
         self.weights = self.om.edge_weights(self.case.edge_dist, self.costs, 1.0 if computed else 0.0)
 
     def v(self, fx, fy):

@@ -86,3 +86,59 @@ def test_hub_terrain_valences_and_faceless_vertices():
         except ValueError:
             continue
         raise AssertionError(bad)
+
+
+def _lattice_checked(mesh, chi, valences):
+    """a (u, v) lattice mesh: manifold, the oracle's edge ids, Euler characteristic, valence range, no zero-length edge"""
+    om = O.OracleMesh(mesh.xyz, mesh.faces)
+    assert om.manifold
+    assert np.array_equal(om.edges(), mesh.edges) and np.array_equal(om.face_edges(), mesh.face_edges)
+    assert np.array_equal(om.edge_distances().view(np.uint32), meshgen.edge_lengths(mesh).view(np.uint32))
+    assert mesh.V - mesh.E + mesh.F == chi
+    deg = np.bincount(mesh.edges.ravel(), minlength=mesh.V)
+    assert (int(deg.min()), int(deg.max())) == valences
+    assert om.edge_distances().min() > 0
+    return om, deg
+
+
+def test_ramp_is_an_open_helicoid_of_several_storeys():
+    m = meshgen.ramp(320, 12, 8.0, 0.05, 1.0, 1.2, 0)
+    _, deg = _lattice_checked(m, 1, (2, 6))                         # a disc
+    assert (m.V, m.F, m.E) == (3840, 7018, 10857)
+    assert np.array_equal(m.xyz, meshgen.ramp(320, 12, 8.0, 0.05, 1.0, 1.2, 0).xyz) and not np.array_equal(m.xyz, meshgen.ramp(seed=1).xyz)
+    assert np.array_equal(m.faces[:2], [[0, 1, 321], [0, 321, 320]])   # vertex id j * nu + i, cell (a, b, c, d) -> (a, b, c), (a, c, d)
+    assert sorted(deg[[0, 319, 320 * 11, 320 * 12 - 1]]) == [2, 2, 3, 3] and (deg.reshape(12, 320)[1:-1, 1:-1] == 6).all()
+    rho = np.hypot(m.xyz[:, 0], m.xyz[:, 1])
+    assert 0.97 < rho.min() < 1.03 and 2.17 < rho.max() < 2.23       # lane from r0 to r0 + width, jittered inside the surface
+    assert 0.39 < np.ptp(m.xyz[:, 2]) < 0.41                         # 8 turns, 0.05 apart: the height is far below the footprint
+    up = m.xyz[5 * 320 + 100 + 40] - m.xyz[5 * 320 + 100]            # one turn further along the lane (319 / 8 ~ 40): one storey up
+    assert abs(up[2] - 0.05) < 0.005 and np.hypot(up[0], up[1]) < 0.2
+
+
+def test_torus_is_closed_with_valence_six_everywhere():
+    m = meshgen.torus(64, 32, 2.0, 0.8, 0)
+    _lattice_checked(m, 0, (6, 6))
+    assert (m.V, m.F, m.E) == (2048, 4096, 6144)
+    assert (np.bincount(m.face_edges.ravel(), minlength=m.E) == 2).all()   # no boundary: every edge in two faces
+    rho = np.hypot(m.xyz[:, 0], m.xyz[:, 1])
+    assert np.abs(np.hypot(rho - 2.0, m.xyz[:, 2]) - 0.8).max() < 1e-5
+
+
+def test_tube_is_a_vertical_wall_with_horizontal_normals():
+    m = meshgen.tube(48, 40, 0.8, 3.0, 0)
+    om, deg = _lattice_checked(m, 0, (4, 6))                         # an annulus
+    assert (m.V, m.F, m.E) == (1920, 3744, 5664)
+    fn = om.face_normals()
+    assert (fn[:, 2] == 0).all() and np.abs(np.hypot(fn[:, 0], fn[:, 1]) - 1).max() < 1e-6
+    assert (om.vertex_normals(fn)[:, 2] == 0).all()
+    assert (np.bincount(m.face_edges.ravel(), minlength=m.E) == 1).sum() == 2 * 48   # two boundary loops
+
+
+def test_moved_translates_in_float64_and_rounds_once():
+    m = meshgen.ramp(64, 6, 2.0, 0.05, 1.0, 1.2, 3)
+    t = (-2048.0, 4096.0, 300.0)
+    mv = meshgen.moved(m, t)
+    _lattice_checked(mv, 1, (2, 6))
+    assert np.array_equal(mv.faces, m.faces) and np.array_equal(mv.edges, m.edges)
+    assert np.array_equal(mv.xyz, (m.xyz.astype(np.float64) + np.array(t)).astype(np.float32))
+    assert np.abs(mv.xyz.astype(np.float64) - np.array(t) - m.xyz).max() <= 2.0 ** -12          # half an ulp of [4096, 8192)
