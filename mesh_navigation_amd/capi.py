@@ -1500,37 +1500,51 @@ class MnavContext:
         names = ("stayed", "neighbour", "global", "lost", "no_field", "built_index")
         return dict(**{k: x.value for k, x in zip(names, v)}, ms_kernels=mk.value, ms_total=mt.value)
 
+    def _rollout(self, name, fn, pos, direction, up, face_in, slots, ids, ids_error, goal_pos, goal_dir, config, rollout, outputs,
+                 more=(), extra=(), with_extra=False):
+        """What rollout() and fleet_rollout() share: the conversions, the length checks (`name` prefixes their ValueErrors),
+        the output arrays and the call of the C function `fn`, whose arguments are mnav_follow_rollout's with the caller's
+        additions in between.  ids: the optional uint32 per-robot inputs, seed_faces first (the others follow the rollout
+        config in the call), ids_error: what to say when one has another length; more: ready arguments after those; extra:
+        the dtypes by name of per-robot outputs that follow the trace in the call, allocated with_extra, else NULL.
+        Returns the outputs by name and the return code."""
+        p, d, u = (_f32(a).reshape(-1, 3) for a in (pos, direction, up))
+        fi, sl = _u32(face_in).reshape(-1), _u32(slots).reshape(-1)
+        n = int(p.shape[0])
+        if not (d.shape[0] == u.shape[0] == fi.shape[0] == sl.shape[0] == n):
+            raise ValueError(f"{name}: the per-robot arrays differ in length")
+        ids = [None if a is None else _u32(a).reshape(-1) for a in ids]
+        if any(a is not None and a.shape[0] != n for a in ids):
+            raise ValueError(f"{name}: {ids_error}")
+        gp = None if goal_pos is None else _f32(goal_pos).reshape(-1, 3)
+        gd = None if goal_dir is None else _f32(goal_dir).reshape(-1, 3)
+        if any(g is not None and g.shape[0] != n for g in (gp, gd)):
+            raise ValueError(f"{name}: goal_pos / goal_dir need one row per robot")
+        cfg = config if config is not None else FollowConfig()
+        ro = rollout if rollout is not None else RolloutConfig()
+        rows = int(ro.ticks) // int(ro.trace_stride) if ro.trace_stride else 0
+        shapes = dict(status=((n,), np.int32), ticks=((n,), np.uint32), pos=((n, 3), np.float32), dir=((n, 3), np.float32), face=((n,), np.uint32),
+                      travel=((n,), np.float64), cost_integral=((n,), np.float64), min_goal_dist=((n,), np.float32))
+        state = [*shapes, "trace"]
+        if with_extra:
+            shapes.update({k: ((n,), t) for k, t in extra.items()})
+        want = set(shapes) if outputs is None else set(outputs)
+        o = {k: (np.zeros(*shapes[k]) if k in want else None) for k in shapes}
+        o["trace"] = np.zeros((n, rows, 3), np.float32) if ro.trace_stride else None
+        rc = fn(self._h, n, _p(p), _p(d), _p(u), _p(fi), _p(sl), _p(ids[0]), _p(gp), _p(gd), C.byref(cfg), C.byref(ro), *[_p(a) for a in ids[1:]], *more,
+                *[_p(o[k]) for k in state], *[_p(o.get(k)) for k in extra])
+        if rc < 0:
+            raise RuntimeError(f"{fn.__name__} failed: {self._err()}")
+        return o, rc
+
     def rollout(self, pos, direction, up, face_in, slots, seed_faces=None, goal_pos=None, goal_dir=None, config: FollowConfig | None = None,
                 rollout: RolloutConfig | None = None, outputs=None) -> RolloutOut:
         """`rollout.ticks` controller ticks of n robots over the resident vector maps of the last plan call, the robots'
         state resident and the loop on the device (mnav_follow_rollout, include/mnav.h).  The per-robot arrays are those
         of follow(); goal_pos / goal_dir: (n, 3) each, both or neither.  `outputs`: the names of the RolloutOut fields to
         fetch (default: all; the trace whenever rollout.trace_stride is set)."""
-        p, d, u = (_f32(a).reshape(-1, 3) for a in (pos, direction, up))
-        fi, sl = _u32(face_in).reshape(-1), _u32(slots).reshape(-1)
-        n = int(p.shape[0])
-        if not (d.shape[0] == u.shape[0] == fi.shape[0] == sl.shape[0] == n):
-            raise ValueError("rollout: the per-robot arrays differ in length")
-        sf = None if seed_faces is None else _u32(seed_faces).reshape(-1)
-        if sf is not None and sf.shape[0] != n:
-            raise ValueError("rollout: seed_faces needs one entry per robot")
-        gp = None if goal_pos is None else _f32(goal_pos).reshape(-1, 3)
-        gd = None if goal_dir is None else _f32(goal_dir).reshape(-1, 3)
-        if any(g is not None and g.shape[0] != n for g in (gp, gd)):
-            raise ValueError("rollout: goal_pos / goal_dir need one row per robot")
-        cfg = config if config is not None else FollowConfig()
-        ro = rollout if rollout is not None else RolloutConfig()
-        rows = int(ro.ticks) // int(ro.trace_stride) if ro.trace_stride else 0
-        shapes = dict(status=((n,), np.int32), ticks=((n,), np.uint32), pos=((n, 3), np.float32), dir=((n, 3), np.float32), face=((n,), np.uint32),
-                      travel=((n,), np.float64), cost_integral=((n,), np.float64), min_goal_dist=((n,), np.float32))
-        want = set(shapes) if outputs is None else set(outputs)
-        o = {k: (np.zeros(*shapes[k]) if k in want else None) for k in shapes}
-        o["trace"] = np.zeros((n, rows, 3), np.float32) if ro.trace_stride else None
-        rc = self._L.mnav_follow_rollout(self._h, n, _p(p), _p(d), _p(u), _p(fi), _p(sl), _p(sf), _p(gp), _p(gd), C.byref(cfg), C.byref(ro),
-                                         _p(o["status"]), _p(o["ticks"]), _p(o["pos"]), _p(o["dir"]), _p(o["face"]), _p(o["travel"]),
-                                         _p(o["cost_integral"]), _p(o["min_goal_dist"]), _p(o["trace"]))
-        if rc < 0:
-            raise RuntimeError(f"mnav_follow_rollout failed: {self._err()}")
+        o, rc = self._rollout("rollout", self._L.mnav_follow_rollout, pos, direction, up, face_in, slots, [seed_faces], "seed_faces needs one entry per robot",
+                              goal_pos, goal_dir, config, rollout, outputs)
         return RolloutOut(**o, cancelled=rc == 1)
 
     def rollout_stats(self) -> dict:
@@ -1548,35 +1562,10 @@ class MnavContext:
         the robots on the device after every separation.check_stride-th tick (mnav_fleet_rollout, include/mnav.h).
         `outputs`: the names of the FleetRolloutOut fields to fetch (default: all; the separation outputs only with
         `separation`)."""
-        p, d, u = (_f32(a).reshape(-1, 3) for a in (pos, direction, up))
-        fi, sl = _u32(face_in).reshape(-1), _u32(slots).reshape(-1)
-        n = int(p.shape[0])
-        if not (d.shape[0] == u.shape[0] == fi.shape[0] == sl.shape[0] == n):
-            raise ValueError("fleet_rollout: the per-robot arrays differ in length")
-        sf = None if seed_faces is None else _u32(seed_faces).reshape(-1)
-        st = None if start_tick is None else _u32(start_tick).reshape(-1)
-        if any(a is not None and a.shape[0] != n for a in (sf, st)):
-            raise ValueError("fleet_rollout: seed_faces / start_tick need one entry per robot")
-        gp = None if goal_pos is None else _f32(goal_pos).reshape(-1, 3)
-        gd = None if goal_dir is None else _f32(goal_dir).reshape(-1, 3)
-        if any(g is not None and g.shape[0] != n for g in (gp, gd)):
-            raise ValueError("fleet_rollout: goal_pos / goal_dir need one row per robot")
-        cfg = config if config is not None else FollowConfig()
-        ro = rollout if rollout is not None else RolloutConfig()
-        rows = int(ro.ticks) // int(ro.trace_stride) if ro.trace_stride else 0
-        shapes = dict(status=((n,), np.int32), ticks=((n,), np.uint32), pos=((n, 3), np.float32), dir=((n, 3), np.float32), face=((n,), np.uint32),
-                      travel=((n,), np.float64), cost_integral=((n,), np.float64), min_goal_dist=((n,), np.float32))
-        if separation is not None:
-            shapes.update({k: ((n,), np.float32 if k == "min_sep2" else np.uint32) for k in SEPARATION_OUTPUTS})
-        want = set(shapes) if outputs is None else set(outputs)
-        o = {k: (np.zeros(*shapes[k]) if k in want else None) for k in shapes}
-        o["trace"] = np.zeros((n, rows, 3), np.float32) if ro.trace_stride else None
-        rc = self._L.mnav_fleet_rollout(self._h, n, _p(p), _p(d), _p(u), _p(fi), _p(sl), _p(sf), _p(gp), _p(gd), C.byref(cfg), C.byref(ro), _p(st),
-                                        None if separation is None else C.byref(separation),
-                                        _p(o["status"]), _p(o["ticks"]), _p(o["pos"]), _p(o["dir"]), _p(o["face"]), _p(o["travel"]),
-                                        _p(o["cost_integral"]), _p(o["min_goal_dist"]), _p(o["trace"]), *[_p(o.get(k)) for k in SEPARATION_OUTPUTS])
-        if rc < 0:
-            raise RuntimeError(f"mnav_fleet_rollout failed: {self._err()}")
+        o, rc = self._rollout("fleet_rollout", self._L.mnav_fleet_rollout, pos, direction, up, face_in, slots, [seed_faces, start_tick],
+                              "seed_faces / start_tick need one entry per robot", goal_pos, goal_dir, config, rollout, outputs,
+                              more=[None if separation is None else C.byref(separation)],
+                              extra={k: np.float32 if k == "min_sep2" else np.uint32 for k in SEPARATION_OUTPUTS}, with_extra=separation is not None)
         return FleetRolloutOut(**o, cancelled=rc == 1, skipped=rc == 2)
 
     def fleet_rollout_stats(self) -> dict:

@@ -242,8 +242,10 @@ struct mnav_ctx {
   mnav_schedule::State schedule;                                   // fleet schedule: the V x B tentative counts and holders, the control record and the statistics of the last mnav_fleet_schedule
   mnav_fleet::PlanState plans;                                     // fleet plans: counts, costs, id / length scratch and packed poses of the last call
   DevBuf<float> d_fnrm; bool have_face_normals = false;            // MeshMap::faceNormals() (mnav_upload_face_normals): F x 3, gone with the mesh
-  mnav_rol::Dev rol;                                               // device rollout: the rest of the resident robot state and statistics of the last mnav_follow_rollout
-  mnav_frol::State frol;                                           // fleet rollout: start ticks, the separation check's table, records and rows, statistics of the last mnav_fleet_rollout
+  mnav_rol::Dev rol;                                               // device rollouts, both entry points: the rest of the resident robot state, goals, counter rows, trace
+  mnav_frol::State frol;                                           // fleet rollout: start ticks, the separation check's table, records, rows and check rows, its event pairs
+  mnav_rol::Stats rol_stats, frol_stats;                           // statistics of the last mnav_follow_rollout / of the last mnav_fleet_rollout
+  mnav_frol::SepStats frol_sep_stats;                              // ... and of the latter's checks
   mnav_chg::Scratch chg;                                           // obstacle / clearance / border layers: change list and counters of the last call
   mnav_map::State map;                                             // resident layer graph (mnav_map_*): nodes, tables, change lists of the last update
   uint32_t infl_steps = 0, infl_bands = 0; uint64_t infl_evals = 0; float infl_ms = 0.f, infl_ms_wave = 0.f;   // last inflation wave
@@ -1861,8 +1863,7 @@ uint32_t mnav_plan_cvp_batch(mnav_ctx* ctx, uint32_t n, const float* seed_pos, c
 #include "mnav_clearance_capi.h"  // mnav_layer_clearance, mnav_layer_border, mnav_clearance_download, mnav_clearance_stats
 #include "mnav_locate_capi.h"     // mnav_locate, mnav_locate_stats, mnav_plan_dijkstra_batch_at, mnav_plan_cvp_batch_at
 #include "mnav_follow_capi.h"     // mnav_follow_batch, mnav_follow_stats
-#include "mnav_rollout_capi.h"    // mnav_follow_rollout, mnav_rollout_stats
-#include "mnav_fleet_rollout_capi.h"   // mnav_fleet_rollout, mnav_fleet_rollout_stats
+#include "mnav_rollout_capi.h"    // mnav_follow_rollout, mnav_rollout_stats, mnav_fleet_rollout, mnav_fleet_rollout_stats
 #include "mnav_graph_capi.h"      // mnav_map_configure / _compute / _layer_changed / _update_layer / _obstacle / _stats
 #include "mnav_replan_capi.h"     // mnav_replan_dijkstra_batch, mnav_replan_stats
 #include "mnav_replan_each_capi.h"   // mnav_replan_dijkstra_each, mnav_replan_each_stats

@@ -1,10 +1,11 @@
 // mnav_fleet_rollout.h -- fleet rollouts (mnav_fleet_rollout): mnav_follow_rollout with a departure tick per robot and a
-// separation check between the robots on the device.  Two additions to mnav_rollout.h, nothing of which changes:
+// separation check between the robots on the device.  Two additions to mnav_rollout.h:
 //
 //   * FleetTick, a tick policy derived from mnav_rol::Tick whose first() also asks `tick >= start_tick[i]` (device ticks
 //     count from 0: frol_waits(tick + 1, start_tick[i]) is false).  A waiting robot is a robot without a tick -- idle()
 //     repeats its position in the trace, nothing else of its row is read or written -- so k_fleet_rollout_stay / _search /
 //     _global are the three passes of mnav_follow.h once more, and a robot that has departed runs mnav_rollout.h's rule.
+//     They run when a call has start ticks; one without runs k_rollout_*, so FleetTick does not test for null.
 //
 //   * the check.  After all passes of call tick t with t % check_stride == 0 every PRESENT robot (sep_present) learns
 //     which other present robots stand within the radius: d2 = (dx*dx + dy*dy) + dz*dz <= r2 in float32 (sep_d2, symmetric
@@ -31,7 +32,8 @@
 //                  Else one lane per robot streams the records of its range; only robot i writes row i; the near partners
 //                  of a wave go as one 64-bit add into the check's row.
 // The atomics decide a record's place inside its cell and a key's slot in the table; neither is visible in an output.
-// The host mirror sep_check_host runs the same MNAV_HD pieces serially.
+// The host mirror sep_check_host runs the same MNAV_HD pieces serially; sep_fold makes a call's statistics (SepStats) of its
+// check rows on the host.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -283,13 +285,44 @@ inline bool sep_check_host(uint32_t n, const float* pos, const int32_t* status, 
 }
 #endif
 
+// What a call tells of its checks afterwards (mnav_fleet_rollout_stats); `= {}` is the reset, the values of a call without
+// a check.
+struct SepStats {
+  uint32_t checks_run = 0, checks_skipped = 0, first_skipped_tick = kNone, robots_near = 0, max_pairs_tick = kNone, min_pair[2] = { kNone, kNone }, max_cell = 0;
+  uint64_t near_pairs = 0, max_pairs = 0, tests = 0; float min_sep2 = INFINITY;
+  float ms_separation = 0.f;
+};
+
+// The check rows of the `checks` checks a call of n robots ran (check c after call tick (c + 1) * check_stride) and three of
+// the rows' columns, folded into a reset S, on the host (plain C++, as rol_fold_counters).  A skipped check counts, with the first one's tick, and its largest cell counts;
+// its tests and pairs do not.  The first check with the most pairs gives max_pairs_tick, the smallest index min_pair.
+inline void sep_fold(const uint64_t* chk, uint32_t checks, uint32_t check_stride, uint32_t n, const uint32_t* near_checks, const float* min_sep2,
+                     const uint32_t* min_sep_robot, SepStats& S)
+{
+  for (uint32_t c = 0; c < checks; ++c) {
+    const uint64_t* row = chk + (size_t)kCheckWords * c;
+    const uint32_t tick = (c + 1) * check_stride;
+    if (row[kChkMaxCell] > S.max_cell) S.max_cell = (uint32_t)row[kChkMaxCell];
+    if (row[kChkSkipped]) { if (!S.checks_skipped++) S.first_skipped_tick = tick; continue; }
+    S.checks_run += 1; S.tests += row[kChkTests];
+    const uint64_t pairs = row[kChkOrdered] / 2;                      // every near pair was met from both sides
+    S.near_pairs += pairs;
+    if (S.max_pairs_tick == kNone || pairs > S.max_pairs) { S.max_pairs = pairs; S.max_pairs_tick = tick; }
+  }
+  for (uint32_t i = 0; i < n; ++i) {
+    if (near_checks[i]) S.robots_near += 1;
+    if (min_sep2[i] < S.min_sep2) { S.min_sep2 = min_sep2[i]; S.min_pair[0] = i; S.min_pair[1] = min_sep_robot[i]; }   // the smallest i: its partner is larger
+  }
+}
+
 #if defined(__HIPCC__)
 
 constexpr int kSepBlock = 256;     // lanes per workgroup of every pass of a check
 constexpr int kSepPer = 8;         // slots per lane of the scan: tiles of kSepBlock * kSepPer slots
 constexpr uint32_t kSepTile = kSepBlock * kSepPer;
 
-// The rollout's tick with a departure: robot i has no tick before device tick start_tick[i] (null: all 0).
+// The rollout's tick with a departure: robot i has no tick before device tick start_tick[i] (never null: a call without
+// start ticks runs k_rollout_*).
 struct FleetTick : mnav_rol::Tick {
   const uint32_t* start_tick; uint32_t tick;
 
@@ -298,7 +331,7 @@ struct FleetTick : mnav_rol::Tick {
   __device__ __forceinline__ bool first(uint32_t ic, uint32_t& f, W3& p) const
   {
     const bool running = mnav_rol::Tick::first(ic, f, p);
-    return running && !(start_tick && frol_waits(tick + 1, start_tick[ic]));
+    return running && !frol_waits(tick + 1, start_tick[ic]);
   }
 };
 
@@ -465,17 +498,13 @@ __global__ __launch_bounds__(kSepBlock) void k_sep_pair(Sep S, uint32_t check, u
   if ((threadIdx.x & 63u) == 0 && partners) atomicAdd(&row[kChkOrdered], partners);
 }
 
-// what a fleet rollout keeps beside the rollout's own buffers (grown on demand, kept between calls), and the statistics
-// of the last call
+// what a fleet rollout adds on the device to mnav_rol::Dev (grown on demand, kept between calls): the start ticks, the
+// check's table, records, separation rows and check rows, and the event pairs that time the checks of a block
 struct State {
-  mnav::DevBuf<uint32_t> start_tick, cnt, cell_cnt, cell_start, tile, slot_of, rank, near_checks, max_partners, first_near_tick, first_near_robot, min_sep_tick, min_sep_robot;
+  mnav::DevBuf<uint32_t> start_tick, cell_cnt, cell_start, tile, slot_of, rank, near_checks, max_partners, first_near_tick, first_near_robot, min_sep_tick, min_sep_robot;
   mnav::DevBuf<float> rec, min_sep2; mnav::DevBuf<unsigned long long> keys, chk;
-  size_t cap = 0, cnt_cap = 0, sep_cap = 0, table_cap = 0, chk_cap = 0;
+  size_t cap = 0, sep_cap = 0, table_cap = 0, chk_cap = 0;
   mnav::Event ev[2 * mnav_rol::kBlockTicks]; bool have_ev = false;
-  uint32_t final_status[4] = { 0, 0, 0, 0 }, built_index = 0; uint64_t robot_ticks = 0, stayed = 0, neighbour = 0, global = 0;
-  uint32_t checks_run = 0, checks_skipped = 0, first_skipped_tick = kNone, robots_near = 0, max_pairs_tick = kNone, min_pair[2] = { kNone, kNone }, max_cell = 0;
-  uint64_t near_pairs = 0, max_pairs = 0, tests = 0; float global_min_sep2 = INFINITY;
-  float ms_separation = 0.f, ms_kernels = 0.f, ms_total = 0.f;
 };
 
 #endif  // __HIPCC__

@@ -23,8 +23,9 @@
 // Result goes through rol_after_tick into its row instead of into an output row.  Unlike the one-tick call nothing goes
 // to the host between ticks: both list passes size themselves from the list lengths on the device (grid-stride), the
 // lookup index exists before the first tick, and every tick has its own row of 8 counters (cleared once up front), which
-// are the lists' lengths and the statistics at once.  A robot's row is written by exactly one pass per tick; passes hand
-// over through vector stores and vector atomics at kernel boundaries.
+// are the lists' lengths and the statistics at once (rol_fold_counters makes a call's Stats of them on the host).  A
+// robot's row is written by exactly one pass per tick; passes hand over through vector stores and vector atomics at kernel
+// boundaries.  mnav_fleet_rollout without start ticks runs these kernels too (mnav_rollout_capi.h, rollout_run).
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -101,6 +102,28 @@ inline void rol_run(const WalkMesh& M, const mnav_loc::Index& I, Stack& st, cons
   }
 }
 #endif
+
+// What a call tells of itself afterwards (mnav_rollout_stats; the first fields of mnav_fleet_rollout_stats).  The context
+// keeps one record per entry point; `= {}` is the reset.
+struct Stats {
+  uint32_t final_status[4] = { 0, 0, 0, 0 }, built_index = 0; uint64_t robot_ticks = 0, stayed = 0, neighbour = 0, global = 0;
+  float ms_kernels = 0.f, ms_total = 0.f;
+};
+constexpr int kCounterWords = 8;                                          // a tick's counter row (mnav_follow.h, kCounters)
+
+// The counter rows of the `ticks` ticks a call of n robots ran, folded into its statistics, on the host (plain C++; not
+// behind the host mirrors' guard, since the device pass of the compiler reads the caller too).  Words 0 and 1 of a row are
+// the work lists' lengths and tell nothing; a robot that has not stopped is still running.
+inline void rol_fold_counters(const uint32_t* cnt, size_t ticks, uint32_t n, Stats& S)
+{
+  uint64_t sum[kCounterWords] = {};
+  for (size_t t = 0; t < ticks; ++t)
+    for (int k = 2; k < kCounterWords; ++k) sum[k] += cnt[(size_t)kCounterWords * t + k];
+  S.stayed = sum[2]; S.neighbour = sum[3]; S.global = sum[4];
+  S.final_status[kReached] = (uint32_t)sum[5]; S.final_status[kOutOfMap] = (uint32_t)sum[6]; S.final_status[kNoField] = (uint32_t)sum[7];
+  S.final_status[kRunning] = n - (uint32_t)(sum[5] + sum[6] + sum[7]);
+  S.robot_ticks = sum[2] + sum[3] + sum[4] + sum[6];                  // every tick of a robot ends in a face or out of the map
+}
 
 // The call's tick loop on the host, in blocks of at most kBlockTicks: run_block(first_tick, n_ticks) enqueues a block and waits for it
 // (non-zero: an error, passed on), then `cancelled()` is looked at once.  Returns 0, 1 when the flag ended the loop (also
@@ -200,14 +223,14 @@ __global__ __launch_bounds__(mnav_loc::kLocBlock) void k_rollout_global(Batch B,
   mnav_fol::fol_pass_global(T, M, C, I, T.cnt[1] < T.n ? T.cnt[1] : T.n, s_node, s_bound);
 }
 
-// what a rollout keeps beside the context's staging (grown on demand, kept between calls): the rest of the robots' rows,
-// goals, counter rows, trace, and the statistics of the last call
+static_assert(kCounterWords == kCounters, "rol_fold_counters reads the rows the passes write");
+
+// what a rollout keeps on the device beside the context's staging (grown on demand, kept between calls; both entry points
+// use it, a call uploads every input at entry): the rest of the robots' rows, goals, counter rows, trace
 struct Dev {
   mnav::DevBuf<float> min_goal_dist, goal_pos, goal_dir, trace; mnav::DevBuf<double> travel, cost_integral;
   mnav::DevBuf<uint32_t> ticks, cnt; mnav::DevBuf<int32_t> status;
   size_t cap = 0, cnt_cap = 0, trace_cap = 0;
-  uint32_t final_status[4] = { 0, 0, 0, 0 }, built_index = 0; uint64_t robot_ticks = 0, stayed = 0, neighbour = 0, global = 0;
-  float ms_kernels = 0.f, ms_total = 0.f;
 };
 
 #endif  // __HIPCC__

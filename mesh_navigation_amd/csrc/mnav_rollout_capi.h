@@ -1,9 +1,16 @@
-// mnav_rollout_capi.h -- the C ABI of the device rollout (include/mnav.h: mnav_follow_rollout, mnav_rollout_stats) over
-// the kernels of mnav_rollout.h.  Included by mnav.hip inside its extern "C" block, after mnav_follow_capi.h (the argument
-// checks are the follower's) and mnav_locate_capi.h (the index build is the lookup's own).
+// mnav_rollout_capi.h -- the C ABI of the device rollouts (include/mnav.h: mnav_follow_rollout, mnav_rollout_stats,
+// mnav_fleet_rollout, mnav_fleet_rollout_stats) over the kernels of mnav_rollout.h and mnav_fleet_rollout.h.  Included by
+// mnav.hip inside its extern "C" block, after mnav_follow_capi.h (the argument checks are the follower's) and
+// mnav_locate_capi.h (the index build is the lookup's own).  One driver, rollout_run, holds the call; the two entry points
+// hand it their arguments and their own statistics record.  The device buffers are shared (a call uploads every input at
+// entry), the statistics are kept apart: a call of one entry point leaves what the other's *_stats tells alone.
 #pragma once
 
-static int rollout_reserve(mnav_ctx* ctx, size_t n, bool goals, size_t ticks, size_t trace_floats)
+static_assert(mnav_frol::kWaitingPresent == MNAV_SEP_WAITING_PRESENT && mnav_frol::kReachedPresent == MNAV_SEP_REACHED_PRESENT,
+              "mnav_fleet_rollout.h restates the values of include/mnav.h");
+
+// (the counter rows' message names the entry point, the others the rollout, as callers have seen them)
+static int rollout_reserve(mnav_ctx* ctx, const char* tag, size_t n, bool goals, size_t ticks, size_t trace_floats)
 {
   mnav_rol::Dev& S = ctx->rol;
   const char* oom = "rollout: out of device memory";
@@ -16,7 +23,7 @@ static int rollout_reserve(mnav_ctx* ctx, size_t n, bool goals, size_t ticks, si
   if (goals && !S.goal_pos && alloc_group(S.goal_pos, 12 * S.cap, S.goal_dir, 12 * S.cap) != hipSuccess) { ctx->err = oom; return -1; }
   if (ticks > S.cnt_cap) {
     S.cnt_cap = 0;
-    if (S.cnt.alloc(sizeof(uint32_t) * mnav_rol::kCounters * ticks) != hipSuccess) { ctx->err = oom; return -1; }
+    if (S.cnt.alloc(sizeof(uint32_t) * mnav_rol::kCounters * ticks) != hipSuccess) { ctx->err = std::string(tag) + ": out of device memory"; return -1; }
     S.cnt_cap = ticks;
   }
   if (trace_floats > S.trace_cap) {
@@ -27,8 +34,43 @@ static int rollout_reserve(mnav_ctx* ctx, size_t n, bool goals, size_t ticks, si
   return 0;
 }
 
-// The argument checks of a rollout beside the follower's (mnav_follow_rollout, mnav_fleet_rollout), all on the host: -1 with
-// ctx->err set, or 0.
+// what start ticks and a separation check need beside the rollout's buffers
+static int fleet_rollout_reserve(mnav_ctx* ctx, size_t n, bool starts, bool sep, size_t table, size_t checks)
+{
+  mnav_frol::State& S = ctx->frol;
+  const char* oom = "fleet rollout: out of device memory";
+  if (starts && n > S.cap) {
+    S.cap = 0;
+    if (S.start_tick.alloc(4 * n) != hipSuccess) { ctx->err = oom; return -1; }
+    S.cap = n;
+  }
+  if (!sep) return 0;
+  if (!S.have_ev) {                                                   // only a check records them: a call without one creates none
+    for (auto& e : S.ev) HIPCHK(hipEventCreate(e.out()));
+    S.have_ev = true;
+  }
+  if (n > S.sep_cap) {
+    S.sep_cap = 0;
+    if (alloc_group(S.slot_of, 4 * n, S.rank, 4 * n, S.rec, 16 * n, S.near_checks, 4 * n, S.max_partners, 4 * n, S.first_near_tick, 4 * n, S.first_near_robot, 4 * n,
+                    S.min_sep2, 4 * n, S.min_sep_tick, 4 * n, S.min_sep_robot, 4 * n) != hipSuccess) { ctx->err = oom; return -1; }
+    S.sep_cap = n;
+  }
+  if (table > S.table_cap) {
+    S.table_cap = 0;
+    if (alloc_group(S.keys, 8 * table, S.cell_cnt, 4 * table, S.cell_start, 4 * table, S.tile, 4 * ((table + mnav_frol::kSepTile - 1) / mnav_frol::kSepTile)) != hipSuccess) {
+      ctx->err = oom; return -1;
+    }
+    S.table_cap = table;
+  }
+  if (checks > S.chk_cap) {
+    S.chk_cap = 0;
+    if (S.chk.alloc(sizeof(unsigned long long) * mnav_frol::kCheckWords * checks) != hipSuccess) { ctx->err = oom; return -1; }
+    S.chk_cap = checks;
+  }
+  return 0;
+}
+
+// The argument checks of a rollout beside the follower's, all on the host: -1 with ctx->err set, or 0.
 static int rollout_check(mnav_ctx* ctx, const float* goal_pos, const float* goal_dir, const mnav_follow_config* config, const mnav_rollout_config* rollout,
                          const float* trace_out)
 {
@@ -46,13 +88,18 @@ static int rollout_check(mnav_ctx* ctx, const float* goal_pos, const float* goal
   return 0;
 }
 
-int mnav_follow_rollout(mnav_ctx* ctx, uint32_t n, const float* pos, const float* dir, const float* up, const uint32_t* face_in, const uint32_t* slots,
-                        const uint32_t* seed_faces, const float* goal_pos, const float* goal_dir, const mnav_follow_config* config,
-                        const mnav_rollout_config* rollout, int32_t* status_out, uint32_t* ticks_out, float* pos_out, float* dir_out, uint32_t* face_out,
-                        double* travel_out, double* cost_integral_out, float* min_goal_dist_out, float* trace_out)
+// The whole call of both entry points.  start_tick: null, or a departure tick per robot; separation: null, or the check,
+// whose per-robot outputs go to sep_out (host pointers, each may be null; all null without a separation).  `tag` names the
+// entry point in the messages that do, `stats` / `sep_stats` are the records of its *_stats function.  Returns 0, 1 when
+// cancelled, 2 when a check was skipped, -1 with ctx->err set.
+static int rollout_run(mnav_ctx* ctx, const char* tag, mnav_rol::Stats& stats, mnav_frol::SepStats& sep_stats, uint32_t n, const float* pos, const float* dir,
+                       const float* up, const uint32_t* face_in, const uint32_t* slots, const uint32_t* seed_faces, const float* goal_pos, const float* goal_dir,
+                       const mnav_follow_config* config, const mnav_rollout_config* rollout, const uint32_t* start_tick, const mnav_separation_config* separation,
+                       int32_t* status_out, uint32_t* ticks_out, float* pos_out, float* dir_out, uint32_t* face_out, double* travel_out, double* cost_integral_out,
+                       float* min_goal_dist_out, float* trace_out, const mnav_frol::Rows& sep_out)
 {
-  using namespace mnav_rol;
-  if (!ctx) return -1;
+  using namespace mnav_frol;
+  using mnav_rol::Batch; using mnav_rol::kCounters; using mnav_rol::kStayBlock; using mnav_rol::Params; using mnav::WalkMesh;
   ctx->err.clear();
   if (!n) return 0;
   const auto t0 = std::chrono::steady_clock::now();
@@ -61,32 +108,69 @@ int mnav_follow_rollout(mnav_ctx* ctx, uint32_t n, const float* pos, const float
   if (follow_check(ctx, n, pos, dir, up, face_in, slots, seed_faces, config, maps)) return -1;
   if (rollout_check(ctx, goal_pos, goal_dir, config, rollout, trace_out)) return -1;
   const uint32_t ticks = rollout->ticks, stride = rollout->trace_stride, rows = stride ? ticks / stride : 0;
+  Grid grid{};
+  uint32_t check_stride = 0, flags = 0;
+  if (!separation) {
+    if (sep_out.near_checks || sep_out.max_partners || sep_out.first_near_tick || sep_out.first_near_robot || sep_out.min_sep2 || sep_out.min_sep_tick ||
+        sep_out.min_sep_robot) {
+      ctx->err = "fleet rollout: a separation output without a separation config"; return -1;
+    }
+  } else {
+    double scale = opt_set(ctx->opt.separation_cell_scale) ? ctx->opt.separation_cell_scale : (double)kDefaultCellScale;
+    if (!(scale >= 1.0 && scale <= 4.0)) { ctx->err = "fleet rollout: separation_cell_scale outside 1 .. 4"; return -1; }
+    grid = sep_grid((float)separation->radius, (float)scale);
+    if (!((float)separation->radius > 0.f) || !sep_grid_ok(grid)) { ctx->err = "fleet rollout: radius: (float)radius must be positive, its square finite and positive"; return -1; }
+    check_stride = separation->check_stride; flags = separation->flags;
+    if (check_stride < 1 || check_stride > ticks) { ctx->err = "fleet rollout: check_stride outside 1 .. ticks"; return -1; }
+    if (flags & ~kKnownFlags) { ctx->err = "fleet rollout: unknown separation flag"; return -1; }
+  }
+  const uint32_t checks = separation ? ticks / check_stride : 0, table = separation ? sep_table_size(n) : 0;
+  const double max_tests_d = opt_set(ctx->opt.separation_max_tests) ? std::max(ctx->opt.separation_max_tests, 0.0) : kDefaultMaxTests;
+  const unsigned long long max_tests = max_tests_d >= 18446744073709551615.0 ? ~0ull : (unsigned long long)max_tests_d;
   if (hipSetDevice(ctx->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return -1; }
   cancel_reset(ctx);                                                  // as the plan calls do
   if (upload_walk_mesh(ctx)) return -1;
-  if (staging_reserve(ctx, n, ctx->res.plans(), "rollout") || rollout_reserve(ctx, n, goal_pos != nullptr, ticks, 3 * (size_t)n * rows)) return -1;
-  Dev& S = ctx->rol;
+  if (staging_reserve(ctx, n, ctx->res.plans(), tag) || rollout_reserve(ctx, tag, n, goal_pos != nullptr, ticks, 3 * (size_t)n * rows) ||
+      fleet_rollout_reserve(ctx, n, start_tick != nullptr, separation != nullptr, table, checks)) return -1;
+  mnav_rol::Dev& R = ctx->rol;
+  State& S = ctx->frol;
   mnav_fol::Staging& G = ctx->stage;
-  for (auto& c : S.final_status) c = 0;
-  S.built_index = 0; S.robot_ticks = S.stayed = S.neighbour = S.global = 0; S.ms_kernels = S.ms_total = 0.f;
-  if (locate_ensure(ctx, &S.built_index)) return -1;                  // no look at the lists between ticks: the index exists before the first one
+  stats = {}; sep_stats = {};
+  if (locate_ensure(ctx, &stats.built_index)) return -1;              // no look at the lists between ticks: the index exists before the first one
   const mnav_loc::State& L = ctx->loc;
   Batch B{};
   if (staging_upload(ctx, n, pos, dir, up, face_in, slots, seed_faces, maps, B)) return -1;
   if (goal_pos) {
-    HIPCHK(hipMemcpyAsync(S.goal_pos, goal_pos, 12 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(S.goal_dir, goal_dir, 12 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(R.goal_pos, goal_pos, 12 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(R.goal_dir, goal_dir, 12 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
   }
-  HIPCHK(hipMemsetAsync(S.status, 0, 4 * (size_t)n, ctx->stream));    // kRunning
-  HIPCHK(hipMemsetAsync(S.ticks, 0, 4 * (size_t)n, ctx->stream));
-  HIPCHK(hipMemsetAsync(S.travel, 0, 8 * (size_t)n, ctx->stream));
-  HIPCHK(hipMemsetAsync(S.cost_integral, 0, 8 * (size_t)n, ctx->stream));
-  HIPCHK(hipMemsetD32Async((hipDeviceptr_t)S.min_goal_dist.get(), 0x7F800000, n, ctx->stream));   // +inf
-  HIPCHK(hipMemsetAsync(S.cnt, 0, sizeof(uint32_t) * kCounters * (size_t)ticks, ctx->stream));    // every tick's row, once
-  B.pos = G.pos; B.dir = G.dir; B.up = G.up; B.face = G.face; B.cnt = S.cnt;
-  B.status = S.status; B.ticks = S.ticks; B.travel = S.travel; B.cost_integral = S.cost_integral; B.min_goal_dist = S.min_goal_dist;
-  B.goal_pos = goal_pos ? S.goal_pos.get() : nullptr; B.goal_dir = goal_pos ? S.goal_dir.get() : nullptr;
-  B.trace = rows ? S.trace.get() : nullptr; B.trace_rows = rows;
+  if (start_tick) HIPCHK(hipMemcpyAsync(S.start_tick, start_tick, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemsetAsync(R.status, 0, 4 * (size_t)n, ctx->stream));    // kRunning
+  HIPCHK(hipMemsetAsync(R.ticks, 0, 4 * (size_t)n, ctx->stream));
+  HIPCHK(hipMemsetAsync(R.travel, 0, 8 * (size_t)n, ctx->stream));
+  HIPCHK(hipMemsetAsync(R.cost_integral, 0, 8 * (size_t)n, ctx->stream));
+  HIPCHK(hipMemsetD32Async((hipDeviceptr_t)R.min_goal_dist.get(), 0x7F800000, n, ctx->stream));   // +inf
+  HIPCHK(hipMemsetAsync(R.cnt, 0, sizeof(uint32_t) * kCounters * (size_t)ticks, ctx->stream));    // every tick's row, once
+  B.pos = G.pos; B.dir = G.dir; B.up = G.up; B.face = G.face; B.cnt = R.cnt;
+  B.status = R.status; B.ticks = R.ticks; B.travel = R.travel; B.cost_integral = R.cost_integral; B.min_goal_dist = R.min_goal_dist;
+  B.goal_pos = goal_pos ? R.goal_pos.get() : nullptr; B.goal_dir = goal_pos ? R.goal_dir.get() : nullptr;
+  B.trace = rows ? R.trace.get() : nullptr; B.trace_rows = rows;
+  const uint32_t* d_start = start_tick ? S.start_tick.get() : nullptr;
+  Sep Q{};
+  if (separation) {
+    HIPCHK(hipMemsetAsync(S.near_checks, 0, 4 * (size_t)n, ctx->stream));                          // sep_row_start
+    HIPCHK(hipMemsetAsync(S.max_partners, 0, 4 * (size_t)n, ctx->stream));
+    HIPCHK(hipMemsetAsync(S.first_near_tick, 0xFF, 4 * (size_t)n, ctx->stream));
+    HIPCHK(hipMemsetAsync(S.first_near_robot, 0xFF, 4 * (size_t)n, ctx->stream));
+    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)S.min_sep2.get(), 0x7F800000, n, ctx->stream));
+    HIPCHK(hipMemsetAsync(S.min_sep_tick, 0xFF, 4 * (size_t)n, ctx->stream));
+    HIPCHK(hipMemsetAsync(S.min_sep_robot, 0xFF, 4 * (size_t)n, ctx->stream));
+    HIPCHK(hipMemsetAsync(S.chk, 0, sizeof(unsigned long long) * kCheckWords * (size_t)checks, ctx->stream));
+    Q.n = n; Q.flags = flags; Q.mask = table - 1; Q.tiles = (table + kSepTile - 1) / kSepTile; Q.G = grid; Q.max_tests = max_tests;
+    Q.pos = G.pos; Q.status = R.status; Q.start_tick = d_start;
+    Q.keys = S.keys; Q.cnt = S.cell_cnt; Q.start = S.cell_start; Q.tile = S.tile; Q.slot_of = S.slot_of; Q.rank = S.rank; Q.rec = S.rec; Q.chk = S.chk;
+    Q.rows = Rows{ S.near_checks, S.max_partners, S.first_near_tick, S.first_near_robot, S.min_sep2, S.min_sep_tick, S.min_sep_robot };
+  }
   mnav_fol::Config C;
   std::memcpy(&C, config, sizeof(C));
   const Params P{ rollout->dt, (float)rollout->dist_tolerance, (float)rollout->angle_tolerance, goal_pos != nullptr };
@@ -94,54 +178,112 @@ int mnav_follow_rollout(mnav_ctx* ctx, uint32_t n, const float* pos, const float
   const mnav_loc::Index I{ L.nodes, L.pts, L.n_pts, L.n_leaves, mnav_loc::loc_root(L.n_leaves) };
   const uint32_t g_stay = (n + kStayBlock - 1) / kStayBlock, g_search = n < 2048u ? n : 2048u;
   const uint32_t g_all = (n + mnav_loc::kLocBlock - 1) / mnav_loc::kLocBlock, g_global = g_all < 1024u ? g_all : 1024u;
-  float ms_kernels = 0.f;
+  const uint32_t g_sep = (n + kSepBlock - 1) / kSepBlock, g_clear = Q.tiles < 4096u ? Q.tiles : 4096u;
+  float ms_kernels = 0.f, ms_separation = 0.f;
   // one block: plain launches, no host look in between; then one synchronise
   const auto run_block = [&](uint32_t first, uint32_t nt) -> int {
     HIPCHK(hipEventRecord(G.ev[0], ctx->stream));
+    uint32_t in_block = 0;
     for (uint32_t t = first; t < first + nt; ++t) {
       const uint32_t row = stride && (t + 1) % stride == 0 ? (t + 1) / stride - 1 : kNone;
-      hipLaunchKernelGGL(k_rollout_stay, dim3(g_stay), dim3(kStayBlock), 0, ctx->stream, B, M, C, P, t, row);
-      hipLaunchKernelGGL(k_rollout_search, dim3(g_search), dim3(64), 0, ctx->stream, B, M, C, P, t, row);
-      hipLaunchKernelGGL(k_rollout_global, dim3(g_global), dim3(mnav_loc::kLocBlock), 0, ctx->stream, B, M, C, P, I, t, row);
+      if (d_start) {
+        hipLaunchKernelGGL(k_fleet_rollout_stay, dim3(g_stay), dim3(kStayBlock), 0, ctx->stream, B, M, C, P, t, row, d_start);
+        hipLaunchKernelGGL(k_fleet_rollout_search, dim3(g_search), dim3(64), 0, ctx->stream, B, M, C, P, t, row, d_start);
+        hipLaunchKernelGGL(k_fleet_rollout_global, dim3(g_global), dim3(mnav_loc::kLocBlock), 0, ctx->stream, B, M, C, P, I, t, row, d_start);
+      } else {                                                        // nobody waits: the rollout's own passes, the same bits
+        hipLaunchKernelGGL(mnav_rol::k_rollout_stay, dim3(g_stay), dim3(kStayBlock), 0, ctx->stream, B, M, C, P, t, row);
+        hipLaunchKernelGGL(mnav_rol::k_rollout_search, dim3(g_search), dim3(64), 0, ctx->stream, B, M, C, P, t, row);
+        hipLaunchKernelGGL(mnav_rol::k_rollout_global, dim3(g_global), dim3(mnav_loc::kLocBlock), 0, ctx->stream, B, M, C, P, I, t, row);
+      }
+      if (!separation || (t + 1) % check_stride) continue;
+      const uint32_t check = (t + 1) / check_stride - 1;
+      HIPCHK(hipEventRecord(S.ev[2 * in_block], ctx->stream));
+      hipLaunchKernelGGL(k_sep_clear, dim3(g_clear), dim3(kSepBlock), 0, ctx->stream, Q);
+      hipLaunchKernelGGL(k_sep_insert, dim3(g_sep), dim3(kSepBlock), 0, ctx->stream, Q, t + 1);
+      hipLaunchKernelGGL(k_sep_sums, dim3(Q.tiles), dim3(kSepBlock), 0, ctx->stream, Q);
+      hipLaunchKernelGGL(k_sep_top, dim3(1), dim3(kSepBlock), 0, ctx->stream, Q);
+      hipLaunchKernelGGL(k_sep_starts, dim3(Q.tiles), dim3(kSepBlock), 0, ctx->stream, Q);
+      hipLaunchKernelGGL(k_sep_fill, dim3(g_sep), dim3(kSepBlock), 0, ctx->stream, Q, check);
+      hipLaunchKernelGGL(k_sep_pair, dim3(g_sep), dim3(kSepBlock), 0, ctx->stream, Q, check, t + 1);
+      HIPCHK(hipEventRecord(S.ev[2 * in_block + 1], ctx->stream));
+      ++in_block;
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(G.ev[1], ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     ms_kernels += ev_ms(G.ev[0], G.ev[1]);
+    for (uint32_t k = 0; k < in_block; ++k) ms_separation += ev_ms(S.ev[2 * k], S.ev[2 * k + 1]);
     return 0;
   };
   uint32_t done = 0;
-  const int rc = rol_blocks(ticks, run_block, [&] { return ctx->cancel.load(std::memory_order_relaxed) != 0; }, &done);
+  const int rc = mnav_rol::rol_blocks(ticks, run_block, [&] { return ctx->cancel.load(std::memory_order_relaxed) != 0; }, &done);
   if (rc < 0) return -1;
+  const uint32_t checks_done = separation ? done / check_stride : 0;
   std::vector<uint32_t> cnt((size_t)kCounters * done);
-  HIPCHK(hipMemcpyAsync(cnt.data(), S.cnt, sizeof(uint32_t) * cnt.size(), hipMemcpyDeviceToHost, ctx->stream));
-  if (status_out) HIPCHK(hipMemcpyAsync(status_out, S.status, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-  if (ticks_out) HIPCHK(hipMemcpyAsync(ticks_out, S.ticks, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  std::vector<uint64_t> chk((size_t)kCheckWords * checks_done);
+  std::vector<uint32_t> h_near, h_robot; std::vector<float> h_min;
+  HIPCHK(hipMemcpyAsync(cnt.data(), R.cnt, sizeof(uint32_t) * cnt.size(), hipMemcpyDeviceToHost, ctx->stream));
+  if (status_out) HIPCHK(hipMemcpyAsync(status_out, R.status, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  if (ticks_out) HIPCHK(hipMemcpyAsync(ticks_out, R.ticks, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
   if (pos_out) HIPCHK(hipMemcpyAsync(pos_out, G.pos, 12 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
   if (dir_out) HIPCHK(hipMemcpyAsync(dir_out, G.dir, 12 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
   if (face_out) HIPCHK(hipMemcpyAsync(face_out, G.face, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-  if (travel_out) HIPCHK(hipMemcpyAsync(travel_out, S.travel, 8 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-  if (cost_integral_out) HIPCHK(hipMemcpyAsync(cost_integral_out, S.cost_integral, 8 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-  if (min_goal_dist_out) HIPCHK(hipMemcpyAsync(min_goal_dist_out, S.min_goal_dist, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-  if (rows) HIPCHK(hipMemcpyAsync(trace_out, S.trace, 12 * (size_t)n * rows, hipMemcpyDeviceToHost, ctx->stream));   // (rows past a cancel are not written)
+  if (travel_out) HIPCHK(hipMemcpyAsync(travel_out, R.travel, 8 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  if (cost_integral_out) HIPCHK(hipMemcpyAsync(cost_integral_out, R.cost_integral, 8 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  if (min_goal_dist_out) HIPCHK(hipMemcpyAsync(min_goal_dist_out, R.min_goal_dist, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  if (rows) HIPCHK(hipMemcpyAsync(trace_out, R.trace, 12 * (size_t)n * rows, hipMemcpyDeviceToHost, ctx->stream));   // (rows past a cancel are not written)
+  if (separation) {
+    h_near.resize(n); h_robot.resize(n); h_min.resize(n);             // the statistics read three of the rows' columns
+    if (checks_done) HIPCHK(hipMemcpyAsync(chk.data(), S.chk, sizeof(uint64_t) * chk.size(), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(h_near.data(), S.near_checks, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(h_min.data(), S.min_sep2, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(h_robot.data(), S.min_sep_robot, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    if (sep_out.max_partners) HIPCHK(hipMemcpyAsync(sep_out.max_partners, S.max_partners, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    if (sep_out.first_near_tick) HIPCHK(hipMemcpyAsync(sep_out.first_near_tick, S.first_near_tick, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    if (sep_out.first_near_robot) HIPCHK(hipMemcpyAsync(sep_out.first_near_robot, S.first_near_robot, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    if (sep_out.min_sep_tick) HIPCHK(hipMemcpyAsync(sep_out.min_sep_tick, S.min_sep_tick, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  }
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  uint64_t sum[kCounters] = {};
-  for (size_t t = 0; t < done; ++t)
-    for (int k = 2; k < kCounters; ++k) sum[k] += cnt[(size_t)kCounters * t + k];
-  S.stayed = sum[2]; S.neighbour = sum[3]; S.global = sum[4];
-  S.final_status[kReached] = (uint32_t)sum[5]; S.final_status[kOutOfMap] = (uint32_t)sum[6]; S.final_status[kNoField] = (uint32_t)sum[7];
-  S.final_status[kRunning] = n - (uint32_t)(sum[5] + sum[6] + sum[7]);
-  S.robot_ticks = sum[2] + sum[3] + sum[4] + sum[6];                  // every tick of a robot ends in a face or out of the map
-  S.ms_kernels = ms_kernels;
-  S.ms_total = (float)(1e-3 * (double)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count());
-  return rc;
+  mnav_rol::rol_fold_counters(cnt.data(), done, n, stats);
+  if (separation) {
+    sep_fold(chk.data(), checks_done, check_stride, n, h_near.data(), h_min.data(), h_robot.data(), sep_stats);
+    if (sep_out.near_checks) std::memcpy(sep_out.near_checks, h_near.data(), 4 * (size_t)n);
+    if (sep_out.min_sep2) std::memcpy(sep_out.min_sep2, h_min.data(), 4 * (size_t)n);
+    if (sep_out.min_sep_robot) std::memcpy(sep_out.min_sep_robot, h_robot.data(), 4 * (size_t)n);
+  }
+  stats.ms_kernels = ms_kernels; sep_stats.ms_separation = ms_separation;
+  stats.ms_total = (float)(1e-3 * (double)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count());
+  return rc ? rc : sep_stats.checks_skipped ? 2 : 0;
 }
 
-int mnav_rollout_stats(const mnav_ctx* ctx, uint32_t* status_counts, uint64_t* robot_ticks, uint64_t* stayed, uint64_t* neighbour, uint64_t* global,
-                       uint32_t* built_index, float* ms_kernels, float* ms_total)
+int mnav_follow_rollout(mnav_ctx* ctx, uint32_t n, const float* pos, const float* dir, const float* up, const uint32_t* face_in, const uint32_t* slots,
+                        const uint32_t* seed_faces, const float* goal_pos, const float* goal_dir, const mnav_follow_config* config,
+                        const mnav_rollout_config* rollout, int32_t* status_out, uint32_t* ticks_out, float* pos_out, float* dir_out, uint32_t* face_out,
+                        double* travel_out, double* cost_integral_out, float* min_goal_dist_out, float* trace_out)
 {
   if (!ctx) return -1;
-  const mnav_rol::Dev& S = ctx->rol;
+  mnav_frol::SepStats no_checks;                                      // nothing reads it: mnav_rollout_stats tells of no check
+  return rollout_run(ctx, "rollout", ctx->rol_stats, no_checks, n, pos, dir, up, face_in, slots, seed_faces, goal_pos, goal_dir, config, rollout, nullptr, nullptr,
+                     status_out, ticks_out, pos_out, dir_out, face_out, travel_out, cost_integral_out, min_goal_dist_out, trace_out, mnav_frol::Rows{});
+}
+
+int mnav_fleet_rollout(mnav_ctx* ctx, uint32_t n, const float* pos, const float* dir, const float* up, const uint32_t* face_in, const uint32_t* slots,
+                       const uint32_t* seed_faces, const float* goal_pos, const float* goal_dir, const mnav_follow_config* config,
+                       const mnav_rollout_config* rollout, const uint32_t* start_tick, const mnav_separation_config* separation, int32_t* status_out,
+                       uint32_t* ticks_out, float* pos_out, float* dir_out, uint32_t* face_out, double* travel_out, double* cost_integral_out,
+                       float* min_goal_dist_out, float* trace_out, uint32_t* near_checks_out, uint32_t* max_partners_out, uint32_t* first_near_tick_out,
+                       uint32_t* first_near_robot_out, float* min_sep2_out, uint32_t* min_sep_tick_out, uint32_t* min_sep_robot_out)
+{
+  if (!ctx) return -1;
+  return rollout_run(ctx, "fleet rollout", ctx->frol_stats, ctx->frol_sep_stats, n, pos, dir, up, face_in, slots, seed_faces, goal_pos, goal_dir, config, rollout,
+                     start_tick, separation, status_out, ticks_out, pos_out, dir_out, face_out, travel_out, cost_integral_out, min_goal_dist_out, trace_out,
+                     mnav_frol::Rows{ near_checks_out, max_partners_out, first_near_tick_out, first_near_robot_out, min_sep2_out, min_sep_tick_out, min_sep_robot_out });
+}
+
+// the first eight values of both *_stats functions
+static void rollout_stats_get(const mnav_rol::Stats& S, uint32_t* status_counts, uint64_t* robot_ticks, uint64_t* stayed, uint64_t* neighbour, uint64_t* global,
+                              uint32_t* built_index, float* ms_kernels, float* ms_total)
+{
   if (status_counts) for (int k = 0; k < 4; ++k) status_counts[k] = S.final_status[k];
   if (robot_ticks) *robot_ticks = S.robot_ticks;
   if (stayed) *stayed = S.stayed;
@@ -150,5 +292,35 @@ int mnav_rollout_stats(const mnav_ctx* ctx, uint32_t* status_counts, uint64_t* r
   if (built_index) *built_index = S.built_index;
   if (ms_kernels) *ms_kernels = S.ms_kernels;
   if (ms_total) *ms_total = S.ms_total;
+}
+
+int mnav_rollout_stats(const mnav_ctx* ctx, uint32_t* status_counts, uint64_t* robot_ticks, uint64_t* stayed, uint64_t* neighbour, uint64_t* global,
+                       uint32_t* built_index, float* ms_kernels, float* ms_total)
+{
+  if (!ctx) return -1;
+  rollout_stats_get(ctx->rol_stats, status_counts, robot_ticks, stayed, neighbour, global, built_index, ms_kernels, ms_total);
+  return 0;
+}
+
+int mnav_fleet_rollout_stats(const mnav_ctx* ctx, uint32_t* status_counts, uint64_t* robot_ticks, uint64_t* stayed, uint64_t* neighbour, uint64_t* global,
+                             uint32_t* built_index, uint32_t* checks_run, uint32_t* checks_skipped, uint32_t* first_skipped_tick, uint32_t* robots_near,
+                             uint64_t* near_pairs, uint64_t* max_pairs, uint32_t* max_pairs_tick, float* min_sep2, uint32_t* min_pair, uint64_t* tests,
+                             uint32_t* max_cell, float* ms_separation, float* ms_kernels, float* ms_total)
+{
+  if (!ctx) return -1;
+  rollout_stats_get(ctx->frol_stats, status_counts, robot_ticks, stayed, neighbour, global, built_index, ms_kernels, ms_total);
+  const mnav_frol::SepStats& S = ctx->frol_sep_stats;
+  if (checks_run) *checks_run = S.checks_run;
+  if (checks_skipped) *checks_skipped = S.checks_skipped;
+  if (first_skipped_tick) *first_skipped_tick = S.first_skipped_tick;
+  if (robots_near) *robots_near = S.robots_near;
+  if (near_pairs) *near_pairs = S.near_pairs;
+  if (max_pairs) *max_pairs = S.max_pairs;
+  if (max_pairs_tick) *max_pairs_tick = S.max_pairs_tick;
+  if (min_sep2) *min_sep2 = S.min_sep2;
+  if (min_pair) { min_pair[0] = S.min_pair[0]; min_pair[1] = S.min_pair[1]; }
+  if (tests) *tests = S.tests;
+  if (max_cell) *max_cell = S.max_cell;
+  if (ms_separation) *ms_separation = S.ms_separation;
   return 0;
 }

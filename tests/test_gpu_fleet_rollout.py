@@ -1,9 +1,11 @@
 """The fleet rollout on the device (mnav_fleet_rollout, mnav_fleet_rollout_stats): without start ticks and separation it is
 mnav_follow_rollout bit for bit; with start ticks every robot is mnav_follow_rollout's robot run for the ticks that are left,
 its trace moved down; the separation outputs against tests/separation_model.py, the O(n^2) numpy restatement, every output by
-its bits; a cell wider than a wave; the guard; runs repeated and at other cell scales; refusals; the cancel flag.  On the
+its bits; a cell wider than a wave; the guard; runs repeated and at other cell scales; refusals; the cancel flag; the two
+entry points over one set of buffers, each growing what the other then uses.  On the
 64 x 64 terrain and the punched mesh of tests/test_gpu_rollout.py."""
 import ctypes as C
+import dataclasses
 
 import numpy as np
 import pytest
@@ -15,13 +17,14 @@ from tests import rollout_model as RM
 from tests import separation_model as SM
 from tests.test_gpu_rollout import SATURATING, World
 from tests.test_rollout_model import ANG_TOL, DIST_TOL, DT, TICKS
-from tests.test_separation_model import with_stranded
+from tests.test_separation_model import converging_fleet, starts
 
 pytestmark = pytest.mark.gpu
 
 F32 = np.float32
 RADIUS = 0.3
 STATE = RM.KEYS + ("trace",)
+SHARED_TICKS = 260                                                    # one block of 256 ticks of the tick loop and 4
 
 
 @pytest.fixture(scope="module")
@@ -45,32 +48,6 @@ def fleet_run(w, cfg, robots, goals, ticks, start_tick=None, separation=None, tr
 
 def take(robots, goals, idx):
     return {k: (None if v is None else v[idx]) for k, v in robots.items()}, (goals[0][idx], goals[1][idx])
-
-
-def starts(n):
-    """start ticks of a fleet: most robots leave at once, every fifth after 10 ticks, some after 1 or 40, one never"""
-    if n == 2:
-        return np.array([0, 3], np.uint32)
-    st = np.zeros(n, np.uint32)
-    st[::5] = 10
-    st[1::7] = 1
-    st[3::11] = 40
-    st[2] = 1000
-    return st
-
-
-def converging_fleet(w, n):
-    """n robots of which two are stranded beside the mesh (with_stranded) and at least a dozen head for the shared goal in
-    the middle of the mesh, several per plan; n = 2: one of those and a second one that starts 5 cm beside it on the same plan"""
-    if n == 2:
-        robots, goals = w.fleet(40, 0, 2, close=2)
-        robots["pos"][1] = robots["pos"][0] + np.array([0, 0.05, 0], F32)
-        robots["dir"][1], robots["slot"][1], robots["face_in"][1] = robots["dir"][0], robots["slot"][0], FM.NONE
-    else:
-        per_family = 3 if n == 65 else 9
-        robots, goals = with_stranded(w.model, *w.fleet(40, per_family, n - 9 * per_family - 2, close=12 if n == 65 else 40))
-    assert robots["pos"].shape[0] == n
-    return robots, goals
 
 
 @pytest.mark.parametrize("kind,cfg_name", [("async", "default"), ("tile_batch", "saturating"), ("cvp", "default")])
@@ -338,3 +315,60 @@ def test_a_cancel_flag_set_before_the_call_is_cleared_at_entry(worlds, model_run
     RM.assert_same(got, {k: getattr(want, k) for k in STATE}, "after a stale cancel")
     SM.assert_same_rows(got, {k: getattr(want, k) for k in SM.SEP_KEYS}, "after a stale cancel")
     assert w.ctx.fleet_rollout_stats()["checks_run"] == 2
+
+
+def test_one_entry_point_grows_the_buffers_the_other_then_uses(gpu_ctx_factory, model_runs):
+    """Both entry points keep their robots' rows, counter rows and trace in one set of buffers of the context.  Four calls
+    -- a small rollout, a large fleet rollout (65 robots: one past a wave; SHARED_TICKS: a block of 256 ticks and a rest), a
+    large rollout, a small fleet rollout -- on a fresh context in this order, so that the fleet call grows what the rollout
+    made, on a second fresh context in the opposite order, so that the rollout grows what the fleet call made, and on the
+    first context once more in the opposite order, the small calls over the capacities the large ones left: every output of
+    a call by its bits and every statistic but the times are the same each time, and a call leaves the statistics of the
+    other entry point exactly as they were."""
+    cfg, T = FM.config(), SHARED_TICKS
+    r2, g2, s2, _ = model_runs(2, TICKS)
+    r65, g65, s65, late = model_runs(65, T)
+    both = capi.SEP_WAITING_PRESENT | capi.SEP_REACHED_PRESENT
+    calls = [("rollout", lambda w: w.device_run(cfg, r2, None, 3, trace_stride=0)),
+             ("fleet", lambda w: fleet_run(w, cfg, r65, g65, T, start_tick=s65, separation=capi.SeparationConfig(radius=RADIUS, check_stride=7, flags=both), trace_stride=7)),
+             ("rollout", lambda w: w.device_run(cfg, r65, g65, T, trace_stride=1)),
+             ("fleet", lambda w: fleet_run(w, cfg, r2, g2, 3, start_tick=s2, separation=capi.SeparationConfig(radius=RADIUS, check_stride=1)))]
+
+    def fresh():
+        w = World(gpu_ctx_factory(), "async")
+        w.ctx.locate(w.model.xyz[:8])                                 # the lookup index exists: no call's statistics tell of its build
+        return w
+
+    def run(w, order):
+        seen = {}
+        for k in order:
+            kind, call = calls[k]
+            own, other = (w.ctx.rollout_stats, w.ctx.fleet_rollout_stats) if kind == "rollout" else (w.ctx.fleet_rollout_stats, w.ctx.rollout_stats)
+            before = other()
+            out = call(w)
+            assert other() == before, (order, k)
+            assert not out.cancelled and not getattr(out, "skipped", False)
+            seen[k] = (out, own())
+        return seen
+
+    def assert_same_calls(a, b, what):
+        for k in range(4):
+            (oa, sa), (ob, sb) = a[k], b[k]
+            for f in dataclasses.fields(oa):
+                x, y = getattr(oa, f.name), getattr(ob, f.name)
+                assert (x is None and y is None) or (isinstance(x, bool) and x == y) or FM.same_bits(x, y), (what, k, f.name)
+            assert {n: v for n, v in sa.items() if not n.startswith("ms_")} == {n: v for n, v in sb.items() if not n.startswith("ms_")}, (what, k, sa, sb)
+
+    wa, wb = fresh(), fresh()
+    up = run(wa, (0, 1, 2, 3))
+    down = run(wb, (3, 2, 1, 0))
+    assert_same_calls(up, down, "grown by the fleet rollout / grown by the rollout")
+    assert_same_calls(up, run(wa, (3, 2, 1, 0)), "over the capacities left")
+    # the large fleet call is the model's
+    got, st = up[1]
+    want = SM.separation(late["trace"], late["status_at"], s65, RADIUS, 7, both)
+    SM.assert_same_rows(got, want, "call 2")
+    RM.assert_same(got, late, "call 2", keys=RM.KEYS)
+    assert FM.same_bits(got.trace, SM.thin(late["trace"], 7))
+    check_sep_stats(st, want, T, 7)
+    assert up[0][1]["robot_ticks"] > 0 and up[2][1]["robot_ticks"] > st["robot_ticks"] > 0 and up[3][1]["checks_run"] == 3 and st["checks_run"] == T // 7

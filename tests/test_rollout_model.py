@@ -2,8 +2,8 @@
 -ffp-contract=off, the flags of the library) -- rol_after_tick is the device's own source, rol_run composes it with
 mnav_follow.h's fol_tick serially -- against tests/rollout_model.py, the Python restatement of the specification with the
 host libm's cosf, sinf and acosf.  Every comparison is exact (floats and doubles by their bits; any NaN equals any NaN),
-and the trace at stride 1 pins every tick, not only the end.  Also: chunk invariance of rol_run, stopped robots, and the
-block loop's look at the cancel flag."""
+and the trace at stride 1 pins every tick, not only the end.  Also: chunk invariance of rol_run, stopped robots, the
+block loop's look at the cancel flag, and the fold of a call's counter rows into its statistics (rol_fold_counters)."""
 import ctypes as C
 import shutil
 import subprocess
@@ -92,6 +92,16 @@ extern "C" int rol_block_loop(uint32_t ticks, uint32_t cancel_at, int fail_at, u
                               [&](uint32_t first, uint32_t nt) { blocks[2 * *n_blocks] = first; blocks[2 * *n_blocks + 1] = nt; ++*n_blocks; return (int)*n_blocks == fail_at ? -1 : 0; },
                               [&] { return ++*looks == cancel_at; }, done);
 }
+// rol_fold_counters over `ticks` counter rows of a call of n robots; out: the four final statuses, robot_ticks, stayed,
+// neighbour, global, and what the fold must leave alone: built_index, ms_kernels, ms_total
+extern "C" void rol_fold(const uint32_t* cnt, uint32_t ticks, uint32_t n, uint64_t* out)
+{
+  mnav_rol::Stats S;
+  mnav_rol::rol_fold_counters(cnt, ticks, n, S);
+  for (int k = 0; k < 4; ++k) out[k] = S.final_status[k];
+  out[4] = S.robot_ticks; out[5] = S.stayed; out[6] = S.neighbour; out[7] = S.global;
+  out[8] = S.built_index; out[9] = S.ms_kernels != 0.f; out[10] = S.ms_total != 0.f;
+}
 '''
 
 
@@ -112,6 +122,7 @@ def build_shim(tmp_path_factory):
     L.rol_after.argtypes = [u32] + [vp] * 18
     L.rol_block_loop.restype = C.c_int
     L.rol_block_loop.argtypes = [u32, u32, C.c_int] + [vp] * 4
+    L.rol_fold.argtypes = [vp, u32, u32, vp]
     return L
 
 
@@ -280,3 +291,27 @@ def test_the_block_loop_looks_at_the_flag_once_per_block(shim):
     assert loop(300, cancel_at=2) == (1, [[0, 256], [256, 44]], 2, 300)   # after the last block: still "cancelled"
     # an error of a block is passed on, nothing more is started and the flag is not looked at
     assert loop(1000, fail_at=2) == (-1, [[0, 256], [256, 256]], 1, 256)
+
+
+def test_the_counter_rows_fold_into_the_statistics(shim):
+    """a counter table written by hand in which every statistic is another number; words 0 and 1 of a row (the work lists'
+    lengths) tell nothing"""
+    cnt = np.array([[9999, 77777, 1, 20, 300, 4000, 50000, 600000],
+                    [123, 456, 2, 30, 400, 5000, 60000, 700000],
+                    [7, 8, 4, 40, 500, 6000, 70000, 800000]], np.uint32)
+    names = ("running", "reached", "out_of_map", "no_field", "robot_ticks", "stayed", "neighbour", "global", "built_index", "ms_kernels", "ms_total")
+
+    def fold(ticks, n):
+        out = np.full(len(names), 99, np.uint64)
+        shim.rol_fold(_p(cnt), ticks, n, _p(out))
+        return dict(zip(names, out.tolist()))
+
+    stopped = 15000 + 180000 + 2100000
+    want = dict(running=13, reached=15000, out_of_map=180000, no_field=2100000, robot_ticks=7 + 90 + 1200 + 180000, stayed=7, neighbour=90,
+                **{"global": 1200}, built_index=0, ms_kernels=0, ms_total=0)
+    assert fold(3, stopped + 13) == want and len(set(list(want.values())[:8])) == 8
+    assert fold(3, stopped)["running"] == 0
+    # a cancelled call folds the rows of the ticks it ran
+    assert fold(2, 2000000) == dict(want, running=2000000 - (9000 + 110000 + 1300000), reached=9000, out_of_map=110000, no_field=1300000,
+                                    robot_ticks=3 + 50 + 700 + 110000, stayed=3, neighbour=50, **{"global": 700})
+    assert fold(0, 5) == dict(want, running=5, reached=0, out_of_map=0, no_field=0, robot_ticks=0, stayed=0, neighbour=0, **{"global": 0})

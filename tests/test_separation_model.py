@@ -3,7 +3,8 @@
 search (sep_range, sep_insert, sep_find, sep_visit) are the device's own source, sep_check_host composes them serially --
 against tests/separation_model.py, the O(n^2) numpy restatement of the specification.  Point sets built to break a grid, each
 at separation_cell_scale 1.0, the default and 4.0 and at two table sizes; presence under the four flag combinations; the tie
-rules; the guard's count; and the departure equivalences of include/mnav.h on a mesh.  Every comparison is exact."""
+rules; the guard's count; the departure equivalences of include/mnav.h on a mesh; and the fold of a call's check rows into
+its statistics (sep_fold) against the model's and on tables written by hand.  Every comparison is exact."""
 import ctypes as C
 import shutil
 import subprocess
@@ -80,6 +81,17 @@ extern "C" void frol_batch(void* h, uint32_t n, const uint32_t* slot, const uint
                                 chk + (size_t)mnav_frol::kCheckWords * (t / check_stride - 1));
   }
 }
+// sep_fold over the rows of `checks` checks and three of the robots' columns; out: checks_run, checks_skipped,
+// first_skipped_tick, robots_near, near_pairs, max_pairs, max_pairs_tick, min_pair (2), tests, max_cell; *min_out: min_sep2
+extern "C" void sep_fold_stats(const uint64_t* chk, uint32_t checks, uint32_t check_stride, uint32_t n, const uint32_t* near_checks, const float* min_sep2,
+                               const uint32_t* min_sep_robot, uint64_t* out, float* min_out)
+{
+  mnav_frol::SepStats S;
+  mnav_frol::sep_fold(chk, checks, check_stride, n, near_checks, min_sep2, min_sep_robot, S);
+  out[0] = S.checks_run; out[1] = S.checks_skipped; out[2] = S.first_skipped_tick; out[3] = S.robots_near; out[4] = S.near_pairs; out[5] = S.max_pairs;
+  out[6] = S.max_pairs_tick; out[7] = S.min_pair[0]; out[8] = S.min_pair[1]; out[9] = S.tests; out[10] = S.max_cell;
+  *min_out = S.min_sep2;
+}
 '''
 
 
@@ -104,6 +116,7 @@ def build_shim(tmp_path_factory):
     L.sep_check.restype = C.c_int
     L.sep_check.argtypes = [u32, vp, vp, vp, u32, u32, f32, f32, u32, C.c_uint64] + [vp] * 8
     L.frol_batch.argtypes = [vp, u32] + [vp] * 8 + [u32] * 4 + [vp] * 15 + [vp, f32, f32, u32, u32, C.c_uint64] + [vp] * 8
+    L.sep_fold_stats.argtypes = [vp, u32, u32, u32] + [vp] * 5
     return L
 
 
@@ -411,8 +424,13 @@ class FleetMirror(Mirror):
 
 
 @pytest.fixture(scope="module")
-def world(shim):
-    mesh, model, fields, seed_faces, start_face = build_world("terrain")
+def built():
+    return build_world("terrain")
+
+
+@pytest.fixture(scope="module")
+def world(shim, built):
+    mesh, model, fields, seed_faces, start_face = built
     mirror = FleetMirror(shim, model)
     robots, goals = with_stranded(model, *fleet(model, len(fields), seed_faces, 40, per_family=1, drivers=15))
     assert robots["pos"].shape[0] == START.shape[0]
@@ -477,3 +495,113 @@ def test_the_whole_call_equals_the_model(world, flags, check_stride):
     if flags == 3:
         stranded = np.isin(late["status"], (RM.OUT_OF_MAP, RM.NO_FIELD))
         assert (want["first_near_robot"] != want["min_sep_robot"]).any() and (want["partner_of"] & stranded).any()
+
+
+# -- the statistics of a call: sep_fold over its check rows ----------------------------------------------------------------
+
+def starts(n):
+    """start ticks of a fleet: most robots leave at once, every fifth after 10 ticks, some after 1 or 40, one never"""
+    if n == 2:
+        return np.array([0, 3], np.uint32)
+    st = np.zeros(n, np.uint32)
+    st[::5] = 10
+    st[1::7] = 1
+    st[3::11] = 40
+    st[2] = 1000
+    return st
+
+
+def converging_fleet(w, n):
+    """n robots of which two are stranded beside the mesh (with_stranded) and at least a dozen head for the shared goal in
+    the middle of the mesh, several per plan; n = 2: one of those and a second one that starts 5 cm beside it on the same plan.
+    w: a world with `model` and `fleet(seed, per_family, drivers, close)` (tests/test_gpu_rollout.py's, or HostWorld)"""
+    if n == 2:
+        robots, goals = w.fleet(40, 0, 2, close=2)
+        robots["pos"][1] = robots["pos"][0] + np.array([0, 0.05, 0], F32)
+        robots["dir"][1], robots["slot"][1], robots["face_in"][1] = robots["dir"][0], robots["slot"][0], FM.NONE
+        if robots.get("seed_face") is not None:
+            robots["seed_face"][1] = robots["seed_face"][0]
+    else:
+        per_family = 3 if n == 65 else 9
+        robots, goals = with_stranded(w.model, *w.fleet(40, per_family, n - 9 * per_family - 2, close=12 if n == 65 else 40))
+    assert robots["pos"].shape[0] == n
+    return robots, goals
+
+
+class HostWorld:
+    """what converging_fleet asks of a world, without a device: the three fields of build_world as the plans"""
+
+    def __init__(self, model, fields, seed_faces):
+        self.model, self.fields, self.seed_faces = model, fields, seed_faces
+
+    def fleet(self, seed, per_family, drivers, close=5):
+        return fleet(self.model, len(self.fields), self.seed_faces, seed, per_family, drivers, close)
+
+
+FOLD_KEYS = ("checks_run", "checks_skipped", "first_skipped_tick", "robots_near", "near_pairs", "max_pairs", "max_pairs_tick", "min_pair", "tests", "max_cell")
+
+
+def fold(L, chk, check_stride, near_checks, min_sep2, min_sep_robot):
+    """sep_fold (the header's own) over check rows (k, 4) and the three columns; returns the statistics by name"""
+    chk = np.ascontiguousarray(chk, np.uint64).reshape(-1, 4)
+    near, m, who = np.ascontiguousarray(near_checks, np.uint32), np.ascontiguousarray(min_sep2, F32), np.ascontiguousarray(min_sep_robot, np.uint32)
+    out, m_out = np.full(11, 99, np.uint64), np.zeros(1, F32)
+    L.sep_fold_stats(_p(chk), chk.shape[0], check_stride, near.shape[0], _p(near), _p(m), _p(who), _p(out), _p(m_out))
+    v = [int(x) for x in out]
+    return dict(zip(FOLD_KEYS, v[:7] + [(v[7], v[8])] + v[9:]), min_sep2=m_out[0])
+
+
+@pytest.fixture(scope="module")
+def converging(built):
+    """the converging fleets of tests/test_gpu_fleet_rollout.py on the host world and the model's run of each over TICKS
+    ticks, computed once per n"""
+    mesh, model, fields, seed_faces, start_face = built
+    made = {}
+
+    def get(n):
+        if n not in made:
+            robots, goals = converging_fleet(HostWorld(model, fields, seed_faces), n)
+            made[n] = (robots, goals, starts(n), SM.departures(model, CONFIGS["default"], fields, robots, goals, DT, TICKS, DIST_TOL, ANG_TOL, starts(n)))
+        return made[n]
+
+    return get
+
+
+@pytest.mark.parametrize("n,check_stride", [(2, 1), (2, 7), (65, 1), (65, 7)])
+def test_the_fold_of_a_call_gives_the_models_statistics(world, converging, n, check_stride):
+    model, fields, _, _, mirror, cfg, _, _ = world
+    robots, goals, start, late = converging(n)
+    want = SM.separation(late["trace"], late["status_at"], start, RADIUS, check_stride, 3)
+    got = mirror.run_fleet(cfg, fields, robots, goals, TICKS, start_tick=start, radius=RADIUS, check_stride=check_stride, flags=3)
+    SM.assert_same_rows(got, want, (n, check_stride))
+    st = fold(mirror.L, got["chk"][: TICKS // check_stride], check_stride, got["near_checks"], got["min_sep2"], got["min_sep_robot"])
+    for k in ("checks_run", "checks_skipped", "first_skipped_tick", "robots_near", "near_pairs", "max_pairs", "max_pairs_tick", "min_pair"):   # check_sep_stats' keys
+        assert st[k] == want["stats"][k], (k, st, want["stats"])
+    assert FM.same_bits(np.array([st["min_sep2"]], F32), np.array([want["stats"]["min_sep2"]], F32))
+    assert want["stats"]["near_pairs"] > 0 and st["tests"] >= 2 * st["near_pairs"] and st["max_cell"] >= 1
+    if n == 65:
+        assert 0 < want["stats"]["robots_near"] < n and want["stats"]["max_pairs_tick"] > check_stride
+
+
+def test_the_fold_of_tables_written_by_hand(shim):
+    none = SM.NONE
+    near, m, who = [0, 2, 1, 0], [np.inf, 0.25, 0.25, np.inf], [none, 2, 1, none]
+    # a skipped check in the middle (rows: tests, ordered near pairs, largest cell, skipped): it counts, with its tick, and so
+    # does its largest cell; its tests and pairs do not
+    st = fold(shim, [[100, 6, 4, 0], [999999, 8, 50, 1], [30, 2, 3, 0]], 5, near, m, who)
+    assert st == dict(checks_run=2, checks_skipped=1, first_skipped_tick=10, robots_near=2, near_pairs=4, max_pairs=3, max_pairs_tick=5, min_pair=(1, 2), tests=130,
+                      max_cell=50, min_sep2=F32(0.25))
+    # ... only the first skipped check gives the tick
+    st = fold(shim, [[1, 0, 1, 1], [100, 6, 4, 0], [7, 0, 9, 1]], 5, near, m, who)
+    assert (st["checks_run"], st["checks_skipped"], st["first_skipped_tick"], st["max_cell"], st["tests"], st["max_pairs_tick"]) == (1, 2, 5, 9, 100, 10)
+    # two checks with the same number of pairs: the first keeps max_pairs_tick; the smallest index of the closest pair wins
+    st = fold(shim, [[5, 2, 1, 0], [10, 4, 2, 0], [12, 4, 2, 0]], 3, near, m, who)
+    assert (st["max_pairs"], st["max_pairs_tick"], st["near_pairs"], st["min_pair"]) == (2, 6, 5, (1, 2))
+    # checks without a pair: the first one is the maximum; nobody near: the values of "never"
+    st = fold(shim, [[3, 0, 1, 0], [3, 0, 1, 0]], 4, [0, 0], [np.inf, np.inf], [none, none])
+    assert st == dict(checks_run=2, checks_skipped=0, first_skipped_tick=none, robots_near=0, near_pairs=0, max_pairs=0, max_pairs_tick=4, min_pair=(none, none), tests=6,
+                      max_cell=1, min_sep2=F32(np.inf))
+    # no check at all: the reset values
+    st = fold(shim, np.zeros((0, 4)), 1, [0], [np.inf], [none])
+    assert st == dict(checks_run=0, checks_skipped=0, first_skipped_tick=none, robots_near=0, near_pairs=0, max_pairs=0, max_pairs_tick=none, min_pair=(none, none), tests=0,
+                      max_cell=0, min_sep2=F32(np.inf))
