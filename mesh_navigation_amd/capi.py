@@ -1086,18 +1086,26 @@ class MnavContext:
         return dict(reason=r.value, log_len=ll.value, levels=lv, kept=k.value, rewound=w.value, tiles_woken=tw.value, rounds=rd.value,
                     ms_level=ms[0].value, ms_rewind=ms[1].value, ms_rounds=ms[2].value, ms_finalize=ms[3].value)
 
+    @staticmethod
+    def _fleet_robots(who, slots, start_vertex, start_pos, weights=None, depart=None, pace=None, key=None):
+        """the per-robot arrays of a fleet call as its C signature takes them: (n, slots, start_vertex, start_pos, weights,
+        depart, pace, key), None where None was given"""
+        sl = _u32(slots).reshape(-1)
+        n = int(sl.shape[0])
+        sv, w, ky = (None if a is None else _u32(a).reshape(-1) for a in (start_vertex, weights, key))
+        sp = None if start_pos is None else _f32(start_pos).reshape(-1, 3)
+        dp, pc = (None if a is None else _f32(a).reshape(-1) for a in (depart, pace))
+        if any(a is not None and a.shape[0] != n for a in (sv, sp if sv is None else None, w, ky, dp, pc)):
+            raise ValueError(f"{who}: the per-robot arrays differ in length")
+        return n, sl, sv, sp, w, dp, pc, ky
+
     def fleet_paths(self, slots, start_vertex=None, start_pos=None, ids_cap: int | None = None) -> dict:
         """Vertex paths of n robots out of the resident fields of the last Dijkstra call or replan (mnav_fleet_paths,
         include/mnav.h): robot i stands on start_vertex[i] (or on the vertex nearest to start_pos[i]) of plan slots[i].
         Returns dict(rc, codes, vertex, potential, path_len, offsets, ids, total): the ids of robot i are
         ids[offsets[i]:offsets[i + 1]], seed first.  Without ids_cap the call sizes the buffer itself (two calls); with it,
         rc = 1 and ids = None tell that `total` ids did not fit."""
-        sl = _u32(slots).reshape(-1)
-        n = int(sl.shape[0])
-        sv = None if start_vertex is None else _u32(start_vertex).reshape(-1)
-        sp = None if start_pos is None else _f32(start_pos).reshape(-1, 3)
-        if (sv is not None and sv.shape[0] != n) or (sv is None and sp is not None and sp.shape[0] != n):
-            raise ValueError("fleet_paths: the per-robot arrays differ in length")
+        n, sl, sv, sp = self._fleet_robots("fleet_paths", slots, start_vertex, start_pos)[:4]
         codes, vtx, lens = (np.zeros(n, np.uint32) for _ in range(3))
         pot = np.zeros(n, np.float32)
         off = np.zeros(n + 1, np.uint64)
@@ -1292,13 +1300,7 @@ class MnavContext:
         """Adds the paths of n robots to the context's per-vertex counts (mnav_fleet_traffic): robots as in fleet_paths,
         weights uint32 per robot (None: 1), accumulate False: the counts start from zero.  Returns dict(codes, vertex,
         potential) -- fleet_paths' values; the counts stay on the device (traffic_download, traffic_stats)."""
-        sl = _u32(slots).reshape(-1)
-        n = int(sl.shape[0])
-        sv = None if start_vertex is None else _u32(start_vertex).reshape(-1)
-        sp = None if start_pos is None else _f32(start_pos).reshape(-1, 3)
-        w = None if weights is None else _u32(weights).reshape(-1)
-        if (sv is not None and sv.shape[0] != n) or (sv is None and sp is not None and sp.shape[0] != n) or (w is not None and w.shape[0] != n):
-            raise ValueError("fleet_traffic: the per-robot arrays differ in length")
+        n, sl, sv, sp, w = self._fleet_robots("fleet_traffic", slots, start_vertex, start_pos, weights)[:5]
         codes, vtx, pot = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.float32)
         if self._L.mnav_fleet_traffic(self._h, n, _p(sl), _p(sv), _p(sp), _p(w), 1 if accumulate else 0, _p(codes), _p(vtx), _p(pot)) != 0:
             raise RuntimeError(f"mnav_fleet_traffic failed: {self._err()}")
@@ -1320,14 +1322,18 @@ class MnavContext:
         return dict(contributing=c.value, adds=a.value, total_weight=t.value, occupied=o.value, peak=p.value, built_index=b.value,
                     ms_kernels=mk.value, ms_total=mt.value)
 
+    def _traffic_layer(self, name: str, layer: int, free_count: int, gain: float, cap: float) -> dict:
+        """mnav_layer_traffic or mnav_layer_timed_traffic: dict(changed)"""
+        changed = np.empty(max(self.V, 1), np.uint32)
+        nc = C.c_uint32()
+        if getattr(self._L, name)(self._h, int(layer), int(free_count), float(gain), float(cap), _p(changed), C.byref(nc)) != 0:
+            raise RuntimeError(f"{name} failed: {self._err()}")
+        return dict(changed=changed[:nc.value].copy())
+
     def layer_traffic(self, layer: int, free_count: int = 0, gain: float = 1.0, cap: float = np.inf) -> dict:
         """the traffic layer from the counts as they stand (mnav_layer_traffic): dict(changed = ascending uint32 ids whose
         cost bits or lethal flag changed)"""
-        changed = np.empty(max(self.V, 1), np.uint32)
-        nc = C.c_uint32()
-        if self._L.mnav_layer_traffic(self._h, int(layer), int(free_count), float(gain), float(cap), _p(changed), C.byref(nc)) != 0:
-            raise RuntimeError(f"mnav_layer_traffic failed: {self._err()}")
-        return dict(changed=changed[:nc.value].copy())
+        return self._traffic_layer("mnav_layer_traffic", layer, free_count, gain, cap)
 
     def map_traffic(self, layer: int, free_count: int = 0, gain: float = 1.0, cap: float = np.inf) -> dict:
         """layer_traffic on an input node of the graph, then the propagation; same arguments"""
@@ -1341,14 +1347,7 @@ class MnavContext:
         None: 1) and key (uint32, None: the index; smaller wins).  Returns dict(codes, vertex, potential, conflict_hops,
         yield_hops, first_yield_vertex, first_yield_window, first_yield_time); the cells stay on the device
         (timed_traffic_download, timed_traffic_stats)."""
-        sl = _u32(slots).reshape(-1)
-        n = int(sl.shape[0])
-        sv = None if start_vertex is None else _u32(start_vertex).reshape(-1)
-        sp = None if start_pos is None else _f32(start_pos).reshape(-1, 3)
-        w, ky = (None if a is None else _u32(a).reshape(-1) for a in (weights, key))
-        dp, pc = (None if a is None else _f32(a).reshape(-1) for a in (depart, pace))
-        if (sv is not None and sv.shape[0] != n) or (sv is None and sp is not None and sp.shape[0] != n) or any(a is not None and a.shape[0] != n for a in (w, ky, dp, pc)):
-            raise ValueError("fleet_timed_traffic: the per-robot arrays differ in length")
+        n, sl, sv, sp, w, dp, pc, ky = self._fleet_robots("fleet_timed_traffic", slots, start_vertex, start_pos, weights, depart, pace, key)
         codes, vtx, conflict, yld, fv, fw = (np.zeros(n, np.uint32) for _ in range(6))
         pot, ft = np.zeros(n, np.float32), np.zeros(n, np.float32)
         if self._L.mnav_fleet_timed_traffic(self._h, n, _p(sl), _p(sv), _p(sp), _p(w), _p(dp), _p(pc), _p(ky), int(windows), float(tau), int(free_count),
@@ -1381,11 +1380,7 @@ class MnavContext:
     def layer_timed_traffic(self, layer: int, free_count: int = 0, gain: float = 1.0, cap: float = np.inf) -> dict:
         """the traffic rule on the peaks as they stand (mnav_layer_timed_traffic): dict(changed = ascending uint32 ids whose
         cost bits or lethal flag changed)"""
-        changed = np.empty(max(self.V, 1), np.uint32)
-        nc = C.c_uint32()
-        if self._L.mnav_layer_timed_traffic(self._h, int(layer), int(free_count), float(gain), float(cap), _p(changed), C.byref(nc)) != 0:
-            raise RuntimeError(f"mnav_layer_timed_traffic failed: {self._err()}")
-        return dict(changed=changed[:nc.value].copy())
+        return self._traffic_layer("mnav_layer_timed_traffic", layer, free_count, gain, cap)
 
     def map_timed_traffic(self, layer: int, free_count: int = 0, gain: float = 1.0, cap: float = np.inf) -> dict:
         """layer_timed_traffic on an input node of the graph, then the propagation; same arguments"""
@@ -1399,14 +1394,7 @@ class MnavContext:
         max_rounds 0: no limit, flags: SCHEDULE_SEED_FREE or 0.  Returns dict(codes, vertex, potential, status, delay,
         depart (the committed departure, +inf otherwise), round); the cells are the timed cells (timed_traffic_download,
         timed_traffic_stats), the call's own figures are schedule_stats()."""
-        sl = _u32(slots).reshape(-1)
-        n = int(sl.shape[0])
-        sv = None if start_vertex is None else _u32(start_vertex).reshape(-1)
-        sp = None if start_pos is None else _f32(start_pos).reshape(-1, 3)
-        w, ky = (None if a is None else _u32(a).reshape(-1) for a in (weights, key))
-        dp, pc = (None if a is None else _f32(a).reshape(-1) for a in (depart, pace))
-        if (sv is not None and sv.shape[0] != n) or (sv is None and sp is not None and sp.shape[0] != n) or any(a is not None and a.shape[0] != n for a in (w, ky, dp, pc)):
-            raise ValueError("fleet_schedule: the per-robot arrays differ in length")
+        n, sl, sv, sp, w, dp, pc, ky = self._fleet_robots("fleet_schedule", slots, start_vertex, start_pos, weights, depart, pace, key)
         codes, vtx, status, delay, rnd = (np.zeros(n, np.uint32) for _ in range(5))
         pot, out = np.zeros(n, np.float32), np.zeros(n, np.float32)
         if self._L.mnav_fleet_schedule(self._h, n, _p(sl), _p(sv), _p(sp), _p(w), _p(dp), _p(pc), _p(ky), int(windows), float(tau), int(capacity), int(max_delay),

@@ -309,6 +309,11 @@ __global__ __launch_bounds__(64) void k_fleet_pack(uint32_t cap, const float* __
   }
 }
 
+// what mnav_fleet_stats tells of the last fleet call
+struct Stats {
+  uint32_t outcome[kCounters] = { 0, 0, 0, 0 }, built_index = 0, chunks = 0; uint64_t entries = 0; float ms_kernels = 0.f, ms_total = 0.f;
+};
+
 // buffers and statistics of the last fleet call
 struct State {
   mnav::DevBuf<uint32_t> slot, vtx, code, len, cnt, face; mnav::DevBuf<float> potential, pos; mnav::DevBuf<int32_t> status;
@@ -318,7 +323,7 @@ struct State {
   mnav::DevBuf<::WalkJob> jobs; mnav::DevBuf<int32_t> ctl; mnav::DevBuf<float> row_pos; mnav::DevBuf<uint32_t> row_face; size_t rows = 0, row_entries = 0;   // one chunk of walks
   mnav::DevBuf<float> out_pos; mnav::DevBuf<uint32_t> out_face; size_t out_cap = 0;   // packed walks
   mnav::Event ev[2]; bool have_ev = false;
-  uint32_t outcome[kCounters] = { 0, 0, 0, 0 }, built_index = 0, chunks = 0; uint64_t entries = 0; float ms_kernels = 0.f, ms_total = 0.f;
+  Stats stats;
 };
 
 #endif  // __HIPCC__

@@ -42,17 +42,19 @@ static int fleet_locate(mnav_ctx* ctx, uint32_t n, const float* pos)
   mnav_loc::State& L = ctx->loc;
   const uint32_t built = L.built; const float ms_query = L.ms_query; const uint64_t candidates = L.candidates;
   if (locate_run(ctx, n, pos, 0, nullptr)) return -1;
-  ctx->fleet.built_index = L.built;
+  ctx->fleet.stats.built_index = L.built;
   if (!L.built) L.built = built;
   L.ms_query = ms_query; L.candidates = candidates;
   return 0;
 }
 
-static void fleet_clear_stats(mnav_fleet::State& S)
-{
-  for (uint32_t& c : S.outcome) c = 0;
-  S.built_index = 0; S.chunks = 0; S.entries = 0; S.ms_kernels = S.ms_total = 0.f;
-}
+// The statistics of mnav_fleet_stats while another entry point (traffic, timed traffic, schedule) runs the fleet calls'
+// shared steps: put back when it ends.
+struct FleetStatsKeep {
+  mnav_fleet::State& S; const mnav_fleet::Stats kept;
+  explicit FleetStatsKeep(mnav_fleet::State& s) : S(s), kept(s.stats) {}
+  ~FleetStatsKeep() { S.stats = kept; }
+};
 
 // The plans of the recorded Dijkstra call as the robots see them (`who` opens the error text).  Every refusal comes before
 // the first device call: a refused call touches nothing.
@@ -90,60 +92,104 @@ static int fleet_fields_of(mnav_ctx* ctx, const std::string& who, uint32_t n, co
   return 0;
 }
 
-// The robots and the plan records go up, k_fleet_cut and k_fleet_len run (codes, hops, potentials, outcome counters, block
-// sums of the hops); ev[0] is recorded in front of the kernels.  *d_vtx: where the robots' vertices are resident.
-static int fleet_classify_robots(mnav_ctx* ctx, uint32_t n, const uint32_t* slots, const uint32_t* start_vertex, const float* start_pos,
-                                 const std::vector<mnav_fleet::Field>& fields, mnav_fleet::Paths& P, const uint32_t** d_vtx)
-{
-  using namespace mnav_fleet;
-  const size_t n_slots = fields.size();
-  if (hipSetDevice(ctx->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return -1; }
-  if (fleet_reserve(ctx, n, n_slots)) return -1;
-  State& S = ctx->fleet;
-  fleet_clear_stats(S);
-  *d_vtx = S.vtx;
-  if (start_vertex) HIPCHK(hipMemcpyAsync(S.vtx, start_vertex, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-  else { if (fleet_locate(ctx, n, start_pos)) return -1; *d_vtx = ctx->loc.vtx; }   // the ids stay on the device
-  HIPCHK(hipMemcpyAsync(S.slot, slots, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemcpyAsync(S.fields, fields.data(), sizeof(Field) * n_slots, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipMemsetAsync(S.cnt, 0, sizeof(uint32_t) * (kCounters + 1), ctx->stream));
-  HIPCHK(hipMemsetAsync(S.need, 0, 8 * n_slots, ctx->stream));
-  P = Paths{};
-  P.n = n; P.V = ctx->V; P.slot = S.slot; P.vtx = *d_vtx; P.fields = S.fields; P.code = S.code; P.len = S.len; P.potential = S.potential; P.bsum = S.bsum; P.cnt = S.cnt;
-  P.mark = S.status; P.need = S.need;
-  const uint32_t nb = (n + kFleetBlock - 1) / kFleetBlock;
-  HIPCHK(hipEventRecord(S.ev[0], ctx->stream));
-  hipLaunchKernelGGL(k_fleet_cut, dim3(((uint32_t)n_slots + kFleetBlock - 1) / kFleetBlock), dim3(kFleetBlock), 0, ctx->stream, (uint32_t)n_slots, S.fields.get(), ctx->res.offset());
-  hipLaunchKernelGGL(k_fleet_len, dim3(nb), dim3(kFleetBlock), 0, ctx->stream, P);
-  return 0;
-}
+// One fleet call over the robots of the resident fields (paths, plans, traffic, timed traffic, schedule): who asks, the robots
+// as the caller gave them, and what the steps leave for the caller's own kernels (P, and d_vtx: where the robots' vertices
+// are resident).  begin, classify, the caller's kernels, finish, download.
+struct FleetCall {
+  mnav_ctx* ctx; const char* who; uint32_t n; const uint32_t* slots; const uint32_t* start_vertex; const float* start_pos;
+  std::vector<mnav_fleet::Field> fields; mnav_fleet::Paths P{}; const uint32_t* d_vtx = nullptr;
+  const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
 
-// After the scan: ev[1], the total and the counters come down; robots the wave never reached under a finite cut are settled
-// (did their plans' waves run out?  rule 5) and S.ms_kernels holds the time so far.
-static int fleet_finish_classify(mnav_ctx* ctx, const mnav_fleet::Paths& P, size_t n_slots, unsigned long long* total, uint32_t* cnt /* kCounters + 1 */)
-{
-  using namespace mnav_fleet;
-  State& S = ctx->fleet;
-  const uint32_t n = P.n, nb = (n + kFleetBlock - 1) / kFleetBlock;
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(S.ev[1], ctx->stream));
-  HIPCHK(hipMemcpyAsync(total, S.off + n, sizeof(*total), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipMemcpyAsync(cnt, S.cnt, sizeof(uint32_t) * (kCounters + 1), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  S.ms_kernels = ev_ms(S.ev[0], S.ev[1]);
-  if (cnt[kCounters]) {
+  // Every refusal comes before the first device call: a refused call touches nothing.  `why`: the caller's own verdict on its
+  // position arguments where "a start vertex or a start position" is not its rule (null: they are fine).
+  int begin(const char* why)
+  {
+    if (n && !slots) why = "null slots";
+    if (why) { ctx->err = std::string(who) + ": " + why; return -1; }
+    return fleet_fields_of(ctx, who, n, slots, fields);
+  }
+  int begin() { return begin(n && !start_vertex && !start_pos ? "neither start vertices nor start positions" : nullptr); }
+
+  // The robots and the plan records go up, k_fleet_cut and k_fleet_len run (codes, hops, potentials, outcome counters, block
+  // sums of the hops); ev[0] is recorded in front of the kernels.
+  int classify()
+  {
+    using namespace mnav_fleet;
+    const size_t n_slots = fields.size();
+    if (hipSetDevice(ctx->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return -1; }
+    if (fleet_reserve(ctx, n, n_slots)) return -1;
+    State& S = ctx->fleet;
+    S.stats = {};
+    d_vtx = S.vtx;
+    if (start_vertex) HIPCHK(hipMemcpyAsync(S.vtx, start_vertex, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    else { if (fleet_locate(ctx, n, start_pos)) return -1; d_vtx = ctx->loc.vtx; }   // the ids stay on the device
+    HIPCHK(hipMemcpyAsync(S.slot, slots, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(S.fields, fields.data(), sizeof(Field) * n_slots, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemsetAsync(S.cnt, 0, sizeof(uint32_t) * (kCounters + 1), ctx->stream));
+    HIPCHK(hipMemsetAsync(S.need, 0, 8 * n_slots, ctx->stream));
+    P.n = n; P.V = ctx->V; P.slot = S.slot; P.vtx = d_vtx; P.fields = S.fields; P.code = S.code; P.len = S.len; P.potential = S.potential; P.bsum = S.bsum; P.cnt = S.cnt;
+    P.mark = S.status; P.need = S.need;
+    const uint32_t nb = (n + kFleetBlock - 1) / kFleetBlock;
     HIPCHK(hipEventRecord(S.ev[0], ctx->stream));
-    hipLaunchKernelGGL(k_fleet_open, dim3((uint32_t)n_slots * kOpenBlocks), dim3(kFleetBlock), 0, ctx->stream, (uint32_t)n_slots, ctx->V, S.fields.get(), S.need.get(),
-                       S.need + n_slots);
-    hipLaunchKernelGGL(k_fleet_resolve, dim3(nb), dim3(kFleetBlock), 0, ctx->stream, P, S.need + n_slots);
+    hipLaunchKernelGGL(k_fleet_cut, dim3(((uint32_t)n_slots + kFleetBlock - 1) / kFleetBlock), dim3(kFleetBlock), 0, ctx->stream, (uint32_t)n_slots, S.fields.get(), ctx->res.offset());
+    hipLaunchKernelGGL(k_fleet_len, dim3(nb), dim3(kFleetBlock), 0, ctx->stream, P);
+    return 0;
+  }
+
+  // After the caller's kernels (with a scan among them: its total): ev[1], the total and the counters come down; robots the
+  // wave never reached under a finite cut are settled (did their plans' waves run out?  rule 5) and the statistics' ms_kernels
+  // holds the time so far.
+  int finish(unsigned long long* total, uint32_t* cnt /* kCounters + 1 */)
+  {
+    using namespace mnav_fleet;
+    State& S = ctx->fleet;
+    const uint32_t n_slots = (uint32_t)fields.size(), nb = (n + kFleetBlock - 1) / kFleetBlock;
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(S.ev[1], ctx->stream));
+    HIPCHK(hipMemcpyAsync(total, S.off + n, sizeof(*total), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipMemcpyAsync(cnt, S.cnt, sizeof(uint32_t) * (kCounters + 1), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    S.ms_kernels += ev_ms(S.ev[0], S.ev[1]);
+    S.stats.ms_kernels = ev_ms(S.ev[0], S.ev[1]);
+    if (cnt[kCounters]) {
+      HIPCHK(hipEventRecord(S.ev[0], ctx->stream));
+      hipLaunchKernelGGL(k_fleet_open, dim3(n_slots * kOpenBlocks), dim3(kFleetBlock), 0, ctx->stream, n_slots, ctx->V, S.fields.get(), S.need.get(), S.need + n_slots);
+      hipLaunchKernelGGL(k_fleet_resolve, dim3(nb), dim3(kFleetBlock), 0, ctx->stream, P, S.need + n_slots);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipEventRecord(S.ev[1], ctx->stream));
+      HIPCHK(hipMemcpyAsync(cnt, S.cnt, sizeof(uint32_t) * (kCounters + 1), hipMemcpyDeviceToHost, ctx->stream));
+      HIPCHK(hipStreamSynchronize(ctx->stream));
+      S.stats.ms_kernels += ev_ms(S.ev[0], S.ev[1]);
+    }
+    return 0;
   }
-  return 0;
+  int finish() { unsigned long long unused = 0; uint32_t cnt[mnav_fleet::kCounters + 1] = {}; return finish(&unused, cnt); }   // (no scan ran: the hop total is not this call's)
+
+  // codes, vertices and potentials of the robots, each where the caller wants it: in stream order, no wait
+  int download(uint32_t* code_out, uint32_t* vertex_out, float* potential_out)
+  {
+    if (code_out) HIPCHK(hipMemcpyAsync(code_out, ctx->fleet.code, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    if (vertex_out) HIPCHK(hipMemcpyAsync(vertex_out, d_vtx, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    if (potential_out) HIPCHK(hipMemcpyAsync(potential_out, ctx->fleet.potential, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    return 0;
+  }
+
+  float ms_total() const { return (float)(1e-3 * (double)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count()); }
+  void report(const uint32_t* cnt, unsigned long long total) const    // what mnav_fleet_stats tells of a paths or plans call
+  {
+    mnav_fleet::Stats& st = ctx->fleet.stats;
+    for (int k = 0; k < mnav_fleet::kCounters; ++k) st.outcome[k] = cnt[k];
+    st.entries = total; st.ms_total = ms_total();
+  }
+};
+
+// the robots of a classified call as a kernel's argument record names them (mnav_traffic::Add, mnav_timed::Walk, mnav_schedule::Job)
+extern "C++" {
+template <class Args>
+static void fleet_fill(Args& A, const FleetCall& R, const uint32_t* weight)
+{
+  A.n = R.P.n; A.V = R.P.V; A.slot = R.P.slot; A.vtx = R.P.vtx; A.fields = R.P.fields; A.code = R.P.code; A.len = R.P.len; A.potential = R.P.potential; A.weight = weight;
 }
+}  // extern "C++"
 
 int mnav_fleet_paths(mnav_ctx* ctx, uint32_t n, const uint32_t* slots, const uint32_t* start_vertex, const float* start_pos, uint32_t* code_out,
                      uint32_t* vertex_out, float* potential_out, uint32_t* len_out, uint64_t* offset_out, uint32_t* ids_out, uint64_t ids_cap,
@@ -153,21 +199,14 @@ int mnav_fleet_paths(mnav_ctx* ctx, uint32_t n, const uint32_t* slots, const uin
   if (!ctx) return -1;
   ctx->err.clear();
   if (!n) return 0;
-  const auto t0 = std::chrono::steady_clock::now();
-  // every refusal comes before the first device call: a refused call touches nothing
-  if (!slots) { ctx->err = "fleet paths: null slots"; return -1; }
-  if (!start_vertex && !start_pos) { ctx->err = "fleet paths: neither start vertices nor start positions"; return -1; }
-  std::vector<Field> fields;
-  if (fleet_fields_of(ctx, "fleet paths", n, slots, fields)) return -1;
-  Paths P{};
-  const uint32_t* d_vtx = nullptr;
-  if (fleet_classify_robots(ctx, n, slots, start_vertex, start_pos, fields, P, &d_vtx)) return -1;
+  FleetCall R{ ctx, "fleet paths", n, slots, start_vertex, start_pos };
+  if (R.begin() || R.classify()) return -1;
   State& S = ctx->fleet;
   const uint32_t nb = (n + kFleetBlock - 1) / kFleetBlock;
   hipLaunchKernelGGL(k_fleet_scan, dim3(1), dim3(kFleetBlock), 0, ctx->stream, nb, S.bsum.get(), (const unsigned long long*)nullptr, S.off + n);
   hipLaunchKernelGGL(k_fleet_offsets, dim3(nb), dim3(kFleetBlock), 0, ctx->stream, n, S.len.get(), S.bsum.get(), S.off.get());
   unsigned long long total = 0; uint32_t cnt[kCounters + 1] = {};
-  if (fleet_finish_classify(ctx, P, fields.size(), &total, cnt)) return -1;
+  if (R.finish(&total, cnt)) return -1;
   const bool fits = ids_out && total <= ids_cap;
   if (fits && total) {
     if (total > S.ids_cap) {
@@ -176,22 +215,18 @@ int mnav_fleet_paths(mnav_ctx* ctx, uint32_t n, const uint32_t* slots, const uin
       S.ids_cap = total;
     }
     HIPCHK(hipEventRecord(S.ev[0], ctx->stream));
-    hipLaunchKernelGGL(k_fleet_write, dim3(nb), dim3(kFleetBlock), 0, ctx->stream, P, S.off.get(), S.ids.get());
+    hipLaunchKernelGGL(k_fleet_write, dim3(nb), dim3(kFleetBlock), 0, ctx->stream, R.P, S.off.get(), S.ids.get());
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(S.ev[1], ctx->stream));
     HIPCHK(hipMemcpyAsync(ids_out, S.ids, 4 * (size_t)total, hipMemcpyDeviceToHost, ctx->stream));   // one dense copy
   }
-  if (code_out) HIPCHK(hipMemcpyAsync(code_out, S.code, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-  if (vertex_out) HIPCHK(hipMemcpyAsync(vertex_out, d_vtx, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-  if (potential_out) HIPCHK(hipMemcpyAsync(potential_out, S.potential, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  if (R.download(code_out, vertex_out, potential_out)) return -1;
   if (len_out) HIPCHK(hipMemcpyAsync(len_out, S.len, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
   if (offset_out) HIPCHK(hipMemcpyAsync(offset_out, S.off, 8 * ((size_t)n + 1), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  if (fits && total) S.ms_kernels += ev_ms(S.ev[0], S.ev[1]);
+  if (fits && total) S.stats.ms_kernels += ev_ms(S.ev[0], S.ev[1]);
   if (total_out) *total_out = total;
-  for (int k = 0; k < kCounters; ++k) S.outcome[k] = cnt[k];
-  S.entries = total;
-  S.ms_total = (float)(1e-3 * (double)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count());
+  R.report(cnt, total);
   return fits ? 0 : 1;
 }
 
@@ -276,7 +311,7 @@ static int fleet_walks_run(mnav_ctx* ctx, bool plans, uint32_t n, const uint32_t
   if (upload_walk_mesh(ctx)) return -1;
   if (fleet_reserve(ctx, n, n_plans)) return -1;
   State& S = ctx->fleet;
-  fleet_clear_stats(S);
+  S.stats = {};
   // scratch rows of walk_cap entries (16 bytes each) for one chunk of robots
   const double mb = opt_set(ctx->opt.fleet_scratch_mb) && ctx->opt.fleet_scratch_mb > 0.0 ? ctx->opt.fleet_scratch_mb : kFleetScratchMb;
   const double fit = std::floor(mb * 1048576.0 / (16.0 * (double)walk_cap));
@@ -324,14 +359,14 @@ static int fleet_walks_run(mnav_ctx* ctx, bool plans, uint32_t n, const uint32_t
     } else if (out_cap)
       hipLaunchKernelGGL(k_fleet_pack, dim3(c), dim3(64), 0, ctx->stream, walk_cap, S.row_pos.get(), S.row_face.get(), S.len + a, S.off + a, S.out_pos.get(), S.out_face.get(), out_cap);
     HIPCHK(hipGetLastError());
-    ++S.chunks;
+    ++S.stats.chunks;
   }
   HIPCHK(hipEventRecord(S.ev[1], ctx->stream));
   unsigned long long total = 0; uint32_t cnt[kCounters] = {};
   HIPCHK(hipMemcpyAsync(&total, S.off + n, sizeof(total), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipMemcpyAsync(cnt, S.cnt, sizeof(cnt), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  S.ms_kernels = ev_ms(S.ev[0], S.ev[1]);
+  S.stats.ms_kernels = ev_ms(S.ev[0], S.ev[1]);
   const bool fits = want && total <= entries_cap;
   if (fits && total && plans) HIPCHK(hipMemcpyAsync(poses_out, PS.poses, sizeof(double) * kPoseDoubles * (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
   if (plans && cost_out) HIPCHK(hipMemcpyAsync(cost_out, PS.cost, 8 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
@@ -345,9 +380,9 @@ static int fleet_walks_run(mnav_ctx* ctx, bool plans, uint32_t n, const uint32_t
   if (offset_out) HIPCHK(hipMemcpyAsync(offset_out, S.off, 8 * ((size_t)n + 1), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   if (total_out) *total_out = total;
-  for (int k = 0; k < kCounters; ++k) S.outcome[k] = cnt[k];
-  S.entries = total;
-  S.ms_total = (float)(1e-3 * (double)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count());
+  for (int k = 0; k < kCounters; ++k) S.stats.outcome[k] = cnt[k];
+  S.stats.entries = total;
+  S.stats.ms_total = (float)(1e-3 * (double)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count());
   return fits ? 0 : 1;
 }
 
@@ -364,7 +399,7 @@ int mnav_fleet_stats(const mnav_ctx* ctx, uint32_t* served, uint32_t* beyond_fie
                      uint32_t* built_index, uint32_t* chunks, float* ms_kernels, float* ms_total)
 {
   if (!ctx) return -1;
-  const mnav_fleet::State& S = ctx->fleet;
+  const mnav_fleet::Stats& S = ctx->fleet.stats;
   if (served) *served = S.outcome[0];
   if (beyond_field) *beyond_field = S.outcome[1];
   if (no_path) *no_path = S.outcome[2];

@@ -26,17 +26,11 @@ int mnav_fleet_plans(mnav_ctx* ctx, uint32_t n, const uint32_t* slots, const uin
   if (!ctx) return -1;
   ctx->err.clear();
   if (!n) return 0;
-  const auto t0 = std::chrono::steady_clock::now();
-  // every refusal comes before the first device call: a refused call touches nothing
-  if (!slots) { ctx->err = "fleet plans: null slots"; return -1; }
-  if (!start_pos || !goal_pos) { ctx->err = "fleet plans: null start or goal positions"; return -1; }
-  std::vector<Field> fields;
-  if (fleet_fields_of(ctx, "fleet plans", n, slots, fields)) return -1;
+  FleetCall R{ ctx, "fleet plans", n, slots, start_vertex, start_pos };
+  if (R.begin(!start_pos || !goal_pos ? "null start or goal positions" : nullptr)) return -1;   // (the positions are the poses' ends, with start vertices too)
   if (!ctx->have_normals) { ctx->err = "fleet plans: vertex normals are not resident (mnav_upload_mesh with vertex_normals)"; return -1; }
-  if (n_plans != fields.size()) { ctx->err = "fleet plans: n_plans differs from the last plan call"; return -1; }
-  Paths P{};
-  const uint32_t* d_vtx = nullptr;
-  if (fleet_classify_robots(ctx, n, slots, start_vertex, start_pos, fields, P, &d_vtx)) return -1;
+  if (n_plans != R.fields.size()) { ctx->err = "fleet plans: n_plans differs from the last plan call"; return -1; }
+  if (R.classify()) return -1;
   State& S = ctx->fleet;
   PlanState& PS = ctx->plans;
   if (plans_reserve(ctx, n, n_plans, 0, 0)) return -1;
@@ -49,7 +43,7 @@ int mnav_fleet_plans(mnav_ctx* ctx, uint32_t n, const uint32_t* slots, const uin
   hipLaunchKernelGGL(k_fleet_scan, dim3(1), dim3(kFleetBlock), 0, ctx->stream, nb, S.bsum.get(), (const unsigned long long*)nullptr, S.off + n);
   hipLaunchKernelGGL(k_fleet_offsets, dim3(nb), dim3(kFleetBlock), 0, ctx->stream, n, PS.count.get(), S.bsum.get(), S.off.get());
   unsigned long long total = 0; uint32_t cnt[kCounters + 1] = {};
-  if (fleet_finish_classify(ctx, P, fields.size(), &total, cnt)) return -1;
+  if (R.finish(&total, cnt)) return -1;
   const bool fits = poses_out && total <= poses_cap;
   if (plans_reserve(ctx, n, n_plans, total, fits ? total : 0)) return -1;
   HIPCHK(hipEventRecord(S.ev[0], ctx->stream));
@@ -57,7 +51,7 @@ int mnav_fleet_plans(mnav_ctx* ctx, uint32_t n, const uint32_t* slots, const uin
     PlanView Q{};
     Q.n = n; Q.V = ctx->V; Q.xyz = ctx->d_xyz.get(); Q.vn = ctx->d_nrm.get(); Q.start = d_start; Q.goal = PS.goal.get(); Q.slot = S.slot.get(); Q.count = PS.count.get();
     Q.ids = PS.ids.get(); Q.off = S.off.get();
-    hipLaunchKernelGGL(k_fleet_write, dim3(nb), dim3(kFleetBlock), 0, ctx->stream, P, S.off.get(), PS.ids.get());   // robot i's hops at its pose offset
+    hipLaunchKernelGGL(k_fleet_write, dim3(nb), dim3(kFleetBlock), 0, ctx->stream, R.P, S.off.get(), PS.ids.get());   // robot i's hops at its pose offset
     hipLaunchKernelGGL(k_plan_poses, dim3((uint32_t)((total + kFleetBlock - 1) / kFleetBlock)), dim3(kFleetBlock), 0, ctx->stream, Q, total,
                        fits ? PS.poses.get() : (double*)nullptr, PS.lengths.get());
   }
@@ -65,18 +59,14 @@ int mnav_fleet_plans(mnav_ctx* ctx, uint32_t n, const uint32_t* slots, const uin
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(S.ev[1], ctx->stream));
   if (fits && total) HIPCHK(hipMemcpyAsync(poses_out, PS.poses, sizeof(double) * kPoseDoubles * (size_t)total, hipMemcpyDeviceToHost, ctx->stream));   // one dense copy
-  if (code_out) HIPCHK(hipMemcpyAsync(code_out, S.code, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-  if (vertex_out) HIPCHK(hipMemcpyAsync(vertex_out, d_vtx, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-  if (potential_out) HIPCHK(hipMemcpyAsync(potential_out, S.potential, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  if (R.download(code_out, vertex_out, potential_out)) return -1;
   if (len_out) HIPCHK(hipMemcpyAsync(len_out, PS.count, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
   if (offset_out) HIPCHK(hipMemcpyAsync(offset_out, S.off, 8 * ((size_t)n + 1), hipMemcpyDeviceToHost, ctx->stream));
   if (cost_out) HIPCHK(hipMemcpyAsync(cost_out, PS.cost, 8 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  S.ms_kernels += ev_ms(S.ev[0], S.ev[1]);
+  S.stats.ms_kernels += ev_ms(S.ev[0], S.ev[1]);
   if (total_out) *total_out = total;
-  for (int k = 0; k < kCounters; ++k) S.outcome[k] = cnt[k];
-  S.entries = total;
-  S.ms_total = (float)(1e-3 * (double)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count());
+  R.report(cnt, total);
   return fits ? 0 : 1;
 }
 

@@ -1,5 +1,5 @@
 // mnav_schedule_capi.h -- the C ABI of the fleet schedule (include/mnav.h: mnav_fleet_schedule, mnav_schedule_stats) over
-// the kernels of mnav_schedule.h, the cells, the peak pass and the reservations of mnav_timed_capi.h and the shared steps of
+// the kernels of mnav_schedule.h, the TimedCells and the peak pass of mnav_timed_capi.h and the FleetCall of
 // mnav_fleet_capi.h.  Included by mnav.hip inside its extern "C" block, after mnav_timed_capi.h.
 #pragma once
 
@@ -38,64 +38,36 @@ int mnav_fleet_schedule(mnav_ctx* ctx, uint32_t n, const uint32_t* slots, const 
                         uint32_t* status_out, uint32_t* delay_out, float* depart_out, uint32_t* round_out)
 {
   using namespace mnav_schedule;
-  using mnav_timed::kWords;
   if (!ctx) return -1;
   ctx->err.clear();
   if (!n && accumulate) return 0;                                     // (n = 0 without `accumulate` still starts the cells over)
-  const auto t0 = std::chrono::steady_clock::now();
-  // every refusal comes before the first device call: a refused call touches nothing
-  if (n && !slots) { ctx->err = "fleet schedule: null slots"; return -1; }
-  if (n && !start_vertex && !start_pos) { ctx->err = "fleet schedule: neither start vertices nor start positions"; return -1; }
-  std::vector<mnav_fleet::Field> fields;
-  if (fleet_fields_of(ctx, "fleet schedule", n, slots, fields)) return -1;
+  FleetCall R{ ctx, "fleet schedule", n, slots, start_vertex, start_pos };
+  if (R.begin()) return -1;
   mnav_timed::State& T = ctx->timed;
   State& S = ctx->schedule;
-  const uint32_t B = windows, V = ctx->V;
+  TimedCells C{ ctx, n, windows, tau, accumulate };
+  const uint32_t B = windows;
   const char* why = mnav_timed::timed_refusal(n, weights, depart, pace, B, tau, accumulate, T.T, T.cell ? T.B : 0u, T.tau);
   if (!why) why = schedule_refusal(B, capacity, max_delay, flags);
   if (why) { ctx->err = std::string("fleet schedule: ") + why; return -1; }
-  const double mb = opt_set(ctx->opt.timed_traffic_max_mb) ? std::max(ctx->opt.timed_traffic_max_mb, 0.0) : kTimedTrafficMaxMb;
-  if ((double)kBytesPerCell * (double)(V ? V : 1) * (double)B > mb * 1048576.0) {
-    ctx->err = "fleet schedule: cells, holders and the tentative arrays are larger than timed_traffic_max_mb"; return -1;
-  }
+  if (C.too_large((double)kBytesPerCell, "fleet schedule: cells, holders and the tentative arrays are larger than timed_traffic_max_mb")) return -1;
   FleetStatsKeep keep(ctx->fleet);
-  bool fresh = false;
-  if (timed_reserve(ctx, n, B, &fresh)) return -1;
-  const size_t cells = (size_t)(V ? V : 1) * B;
-  if (schedule_reserve(ctx, n, cells)) return -1;
-  if (!accumulate || fresh) {
-    HIPCHK(hipMemsetAsync(T.cell, 0, 4 * cells, ctx->stream));
-    HIPCHK(hipMemsetAsync(T.holder, 0xFF, 4 * cells, ctx->stream));
-    T.T = 0ull; T.tau = (float)tau;
-  }
-  HIPCHK(hipMemsetAsync(T.words, 0, sizeof(unsigned long long) * kWords, ctx->stream));
+  const size_t cells = C.cells();
+  if (C.reserve() || schedule_reserve(ctx, n, cells) || C.reset()) return -1;   // (the tentative arrays before the cells start over)
   HIPCHK(hipMemsetAsync(S.ctl, 0, sizeof(Counts), ctx->stream));
-  T.contributing = T.adds = T.beyond = 0; T.built_index = 0; T.ms_kernels = 0.f;
   S.last = Counts{}; S.built_index = 0; S.ms_kernels = 0.f;
   mnav_fleet::State& FS = ctx->fleet;
-  uint32_t G = 1u;
-  while (G < B && G < 64u) G <<= 1;                                   // lanes per vertex of the peak pass
-  const uint32_t peak_blocks = (uint32_t)std::min<size_t>(((size_t)V * G + mnav_timed::kTimedBlock - 1) / mnav_timed::kTimedBlock,
-                                                          std::max(1u, opt_u32(ctx->opt.timed_peak_blocks, mnav_timed::kPeakBlocks)));
   Counts K = {};
   if (n) {
-    if (weights) HIPCHK(hipMemcpyAsync(T.weight, weights, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    if (depart) HIPCHK(hipMemcpyAsync(T.depart, depart, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    if (pace) HIPCHK(hipMemcpyAsync(T.pace, pace, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    if (key) HIPCHK(hipMemcpyAsync(T.key, key, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    mnav_fleet::Paths P{};
-    const uint32_t* d_vtx = nullptr;
-    if (fleet_classify_robots(ctx, n, slots, start_vertex, start_pos, fields, P, &d_vtx)) return -1;
-    S.built_index = T.built_index = FS.built_index;
+    if (C.upload(weights, depart, pace, key) || R.classify()) return -1;
+    S.built_index = T.built_index = FS.stats.built_index;
     const uint32_t rounds_most = max_rounds ? std::min(max_rounds, n) : n;   // progress: a round commits a robot or ends the loop
     const uint32_t chunk = std::max(1u, opt_u32(ctx->opt.schedule_chunk_rounds, kChunkRounds));
     const bool fill = opt_on(ctx->opt.schedule_clean_fill);
     Job J{};
-    J.n = n; J.V = V; J.B = B; J.tau = T.tau; J.capacity = capacity; J.max_delay = max_delay; J.limit = rounds_most; J.flags = flags; J.undo = fill ? 0u : 1u;
-    J.slot = P.slot; J.vtx = P.vtx; J.fields = P.fields; J.code = P.code; J.len = P.len; J.potential = P.potential;
-    J.weight = weights ? T.weight.get() : (const uint32_t*)nullptr; J.depart = depart ? T.depart.get() : (const float*)nullptr;
-    J.pace = pace ? T.pace.get() : (const float*)nullptr; J.key = key ? T.key.get() : (const uint32_t*)nullptr;
-    J.cell = T.cell; J.holder = T.holder; J.tent = S.tent; J.thold = S.thold; J.ctl = S.ctl; J.list = S.list;
+    timed_fill(J, C, R);
+    J.capacity = capacity; J.max_delay = max_delay; J.limit = rounds_most; J.flags = flags; J.undo = fill ? 0u : 1u;
+    J.tent = S.tent; J.thold = S.thold; J.ctl = S.ctl; J.list = S.list;
     J.st = S.st; J.cur = S.cur; J.win = S.win; J.delay_out = S.delay; J.round_out = S.round; J.depart_out = S.depart_out;
     const dim3 lanes((n + kScheduleBlock - 1) / kScheduleBlock), waves((n + kScheduleBlock / 64 - 1) / (kScheduleBlock / 64)), block(kScheduleBlock);
     // `chunk` rounds in stream order; the kernels of a round that has nothing to do return at once
@@ -118,9 +90,8 @@ int mnav_fleet_schedule(mnav_ctx* ctx, uint32_t n, const uint32_t* slots, const 
     hipLaunchKernelGGL(k_schedule_init, lanes, block, 0, ctx->stream, J);
     if (enqueue(std::min(chunk, rounds_most), true)) { ctx->err = "fleet schedule: hipMemsetAsync failed"; return -1; }
     HIPCHK(hipMemcpyAsync(&K, S.ctl, sizeof(K), hipMemcpyDeviceToHost, ctx->stream));
-    unsigned long long unused = 0; uint32_t cnt[mnav_fleet::kCounters + 1] = {};     // (no scan ran: the hop total is not this call's)
-    if (fleet_finish_classify(ctx, P, fields.size(), &unused, cnt)) return -1;       // synchronises: K is the record after the first chunk
-    S.ms_kernels = FS.ms_kernels;
+    if (R.finish()) return -1;                                        // synchronises: K is the record after the first chunk
+    S.ms_kernels = FS.stats.ms_kernels;
     for (uint32_t c = 1; c < chunks_most && K.open && K.round < rounds_most; ++c) {
       HIPCHK(hipEventRecord(FS.ev[0], ctx->stream));
       if (enqueue(std::min(chunk, rounds_most - K.round), false)) { ctx->err = "fleet schedule: hipMemsetAsync failed"; return -1; }
@@ -131,33 +102,22 @@ int mnav_fleet_schedule(mnav_ctx* ctx, uint32_t n, const uint32_t* slots, const 
       S.ms_kernels += ev_ms(FS.ev[0], FS.ev[1]);
     }
     HIPCHK(hipEventRecord(FS.ev[0], ctx->stream));
-    if (V) hipLaunchKernelGGL(mnav_timed::k_timed_peak, dim3(peak_blocks), dim3(mnav_timed::kTimedBlock), 0, ctx->stream, V, B, G, capacity, T.cell.get(), T.peak.get(),
-                              T.window.get(), T.words.get());
-    HIPCHK(hipGetLastError());
+    if (timed_peak(ctx, B, capacity)) return -1;
     HIPCHK(hipEventRecord(FS.ev[1], ctx->stream));
-    if (code_out) HIPCHK(hipMemcpyAsync(code_out, FS.code, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    if (vertex_out) HIPCHK(hipMemcpyAsync(vertex_out, d_vtx, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    if (potential_out) HIPCHK(hipMemcpyAsync(potential_out, FS.potential, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    if (R.download(code_out, vertex_out, potential_out)) return -1;
     if (status_out) HIPCHK(hipMemcpyAsync(status_out, S.st, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     if (delay_out) HIPCHK(hipMemcpyAsync(delay_out, S.delay, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     if (depart_out) HIPCHK(hipMemcpyAsync(depart_out, S.depart_out, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     if (round_out) HIPCHK(hipMemcpyAsync(round_out, S.round, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-  } else if (V) {
-    hipLaunchKernelGGL(mnav_timed::k_timed_peak, dim3(peak_blocks), dim3(mnav_timed::kTimedBlock), 0, ctx->stream, V, B, G, capacity, T.cell.get(), T.peak.get(),
-                       T.window.get(), T.words.get());
-    HIPCHK(hipGetLastError());
-  }
-  unsigned long long words[kWords] = {};
-  HIPCHK(hipMemcpyAsync(words, T.words, sizeof(words), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
+  } else if (timed_peak(ctx, B, capacity)) return -1;
+  if (C.read_words()) return -1;
   if (n) S.ms_kernels += ev_ms(FS.ev[0], FS.ev[1]);
   // the cells as if the committed robots had been a timed call's contributors
   T.T += K.weight;
   T.contributing = K.committed; T.adds = K.visits; T.beyond = 0;
-  T.occupied = words[mnav_timed::kOccupied]; T.over = words[mnav_timed::kOver]; T.largest = (uint32_t)words[mnav_timed::kLargest]; T.yielding = 0;
-  T.windows = B; T.ms_kernels = S.ms_kernels;
+  T.yielding = 0; T.ms_kernels = S.ms_kernels;
   S.last = K;
-  S.ms_total = T.ms_total = (float)(1e-3 * (double)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count());
+  S.ms_total = T.ms_total = R.ms_total();
   return 0;
 }
 

@@ -1,7 +1,8 @@
 // mnav_timed_capi.h -- the C ABI of timed fleet traffic (include/mnav.h: mnav_fleet_timed_traffic,
 // mnav_timed_traffic_download, mnav_timed_traffic_stats, mnav_layer_timed_traffic, mnav_map_timed_traffic) over the kernels
-// of mnav_timed.h, the shared steps of mnav_fleet_capi.h, layer_change_list and map_propagate.  Included by mnav.hip inside
-// its extern "C" block, after mnav_traffic_capi.h (FleetStatsKeep, traffic_check_args).
+// of mnav_timed.h, the FleetCall of mnav_fleet_capi.h and the layer and map bodies of mnav_traffic_capi.h.  TimedCells and
+// timed_peak state the life of the cells through a call once, for this call and for mnav_schedule_capi.h.  Included by
+// mnav.hip inside its extern "C" block, after mnav_traffic_capi.h.
 #pragma once
 
 constexpr double kTimedTrafficMaxMb = 2048.0;   // default of the option timed_traffic_max_mb
@@ -23,25 +24,105 @@ static int timed_reserve_peak(mnav_ctx* ctx)
   return 0;
 }
 
-// cells and holders of B windows (*fresh: they are new and hold nothing yet), room for n robots
-static int timed_reserve(mnav_ctx* ctx, size_t n, uint32_t B, bool* fresh)
+// The timed cells through one call that adds to them (mnav_fleet_timed_traffic, mnav_fleet_schedule), in this order:
+// too_large (a refusal: before anything is touched), reserve, reset, upload, the caller's kernels with timed_peak after the
+// last add, read_words.  A caller with arrays of its own per cell reserves them between reserve and reset.
+struct TimedCells {
+  mnav_ctx* ctx; uint32_t n, B; double tau; int accumulate;
+  bool fresh = false; unsigned long long words[mnav_timed::kWords] = {};
+  const uint32_t* weight = nullptr; const float* depart = nullptr; const float* pace = nullptr; const uint32_t* key = nullptr;   // on the device, null: not given
+
+  size_t cells() const { return (size_t)(ctx->V ? ctx->V : 1) * B; }
+  // `text`: the whole message, it names what the caller keeps per cell
+  int too_large(double bytes_per_cell, const char* text) const
+  {
+    const double mb = opt_set(ctx->opt.timed_traffic_max_mb) ? std::max(ctx->opt.timed_traffic_max_mb, 0.0) : kTimedTrafficMaxMb;
+    if (bytes_per_cell * (double)(ctx->V ? ctx->V : 1) * (double)B > mb * 1048576.0) { ctx->err = text; return -1; }
+    return 0;
+  }
+
+  // cells and holders of B windows (fresh: they are new and hold nothing yet), room for n robots
+  int reserve()
+  {
+    mnav_timed::State& T = ctx->timed;
+    if (timed_reserve_peak(ctx)) return -1;
+    if (T.B != B || !T.cell) {
+      T.B = 0; T.T = 0ull;
+      if (alloc_group(T.cell, 4 * cells(), T.holder, 4 * cells()) != hipSuccess) { ctx->err = "timed traffic: out of device memory"; return -1; }
+      T.B = B; fresh = true;
+    }
+    if (n > T.cap) {
+      T.cap = 0;
+      const size_t b = 4 * (size_t)n;
+      if (alloc_group(T.weight, b, T.key, b, T.conflict, b, T.yield, b, T.fy_vertex, b, T.fy_window, b, T.depart, b, T.pace, b, T.fy_time, b) != hipSuccess) {
+        ctx->err = "timed traffic: out of device memory"; return -1;
+      }
+      T.cap = n;
+    }
+    return 0;
+  }
+
+  // the cells start over unless the call accumulates on cells that hold something; the words and the call's statistics always do
+  int reset()
+  {
+    using namespace mnav_timed;
+    State& T = ctx->timed;
+    if (!accumulate || fresh) {
+      HIPCHK(hipMemsetAsync(T.cell, 0, 4 * cells(), ctx->stream));
+      HIPCHK(hipMemsetAsync(T.holder, 0xFF, 4 * cells(), ctx->stream));
+      T.T = 0ull; T.tau = (float)tau;
+    }
+    HIPCHK(hipMemsetAsync(T.words, 0, sizeof(unsigned long long) * kWords, ctx->stream));
+    T.contributing = T.adds = T.beyond = 0; T.built_index = 0; T.ms_kernels = 0.f;
+    return 0;
+  }
+
+  // the optional arrays per robot (n > 0)
+  int upload(const uint32_t* weights, const float* h_depart, const float* h_pace, const uint32_t* h_key)
+  {
+    mnav_timed::State& T = ctx->timed;
+    const size_t bytes = 4 * (size_t)n;
+    if (weights) { HIPCHK(hipMemcpyAsync(T.weight, weights, bytes, hipMemcpyHostToDevice, ctx->stream)); weight = T.weight; }
+    if (h_depart) { HIPCHK(hipMemcpyAsync(T.depart, h_depart, bytes, hipMemcpyHostToDevice, ctx->stream)); depart = T.depart; }
+    if (h_pace) { HIPCHK(hipMemcpyAsync(T.pace, h_pace, bytes, hipMemcpyHostToDevice, ctx->stream)); pace = T.pace; }
+    if (h_key) { HIPCHK(hipMemcpyAsync(T.key, h_key, bytes, hipMemcpyHostToDevice, ctx->stream)); key = T.key; }
+    return 0;
+  }
+
+  // the words of the peak pass come down (the call's last wait) with what they tell of the cells
+  int read_words()
+  {
+    using namespace mnav_timed;
+    State& T = ctx->timed;
+    HIPCHK(hipMemcpyAsync(words, T.words, sizeof(words), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    T.occupied = words[kOccupied]; T.over = words[kOver]; T.largest = (uint32_t)words[kLargest]; T.windows = B;
+    return 0;
+  }
+};
+
+// the robots and the cells as a kernel's argument record names them (mnav_timed::Walk, mnav_schedule::Job)
+extern "C++" {
+template <class Args>
+static void timed_fill(Args& A, const TimedCells& C, const FleetCall& R)
+{
+  fleet_fill(A, R, C.weight);
+  A.B = C.B; A.tau = C.ctx->timed.tau; A.depart = C.depart; A.pace = C.pace; A.key = C.key; A.cell = C.ctx->timed.cell; A.holder = C.ctx->timed.holder;
+}
+}  // extern "C++"
+
+// peak, first window over `threshold` and the cell statistics from the cells as they stand
+static int timed_peak(mnav_ctx* ctx, uint32_t B, uint32_t threshold)
 {
   using namespace mnav_timed;
   State& T = ctx->timed;
-  if (timed_reserve_peak(ctx)) return -1;
-  *fresh = false;
-  if (T.B != B || !T.cell) {
-    const size_t cells = (size_t)(ctx->V ? ctx->V : 1) * B;
-    T.B = 0; T.T = 0ull;
-    if (alloc_group(T.cell, 4 * cells, T.holder, 4 * cells) != hipSuccess) { ctx->err = "timed traffic: out of device memory"; return -1; }
-    T.B = B; *fresh = true;
-  }
-  if (n > T.cap) {
-    T.cap = 0;
-    if (alloc_group(T.weight, 4 * n, T.key, 4 * n, T.conflict, 4 * n, T.yield, 4 * n, T.fy_vertex, 4 * n, T.fy_window, 4 * n, T.depart, 4 * n, T.pace, 4 * n,
-                    T.fy_time, 4 * n) != hipSuccess) { ctx->err = "timed traffic: out of device memory"; return -1; }
-    T.cap = n;
-  }
+  const uint32_t V = ctx->V;
+  if (!V) return 0;
+  uint32_t G = 1u;
+  while (G < B && G < 64u) G <<= 1;                                   // lanes per vertex of the peak pass
+  const uint32_t peak_blocks = (uint32_t)std::min<size_t>(((size_t)V * G + kTimedBlock - 1) / kTimedBlock, std::max(1u, opt_u32(ctx->opt.timed_peak_blocks, kPeakBlocks)));
+  hipLaunchKernelGGL(k_timed_peak, dim3(peak_blocks), dim3(kTimedBlock), 0, ctx->stream, V, B, G, threshold, T.cell.get(), T.peak.get(), T.window.get(), T.words.get());
+  HIPCHK(hipGetLastError());
   return 0;
 }
 
@@ -54,77 +135,40 @@ int mnav_fleet_timed_traffic(mnav_ctx* ctx, uint32_t n, const uint32_t* slots, c
   if (!ctx) return -1;
   ctx->err.clear();
   if (!n && accumulate) return 0;                                     // (n = 0 without `accumulate` still starts the cells over)
-  const auto t0 = std::chrono::steady_clock::now();
-  // every refusal comes before the first device call: a refused call touches nothing
-  if (n && !slots) { ctx->err = "fleet timed traffic: null slots"; return -1; }
-  if (n && !start_vertex && !start_pos) { ctx->err = "fleet timed traffic: neither start vertices nor start positions"; return -1; }
-  std::vector<mnav_fleet::Field> fields;
-  if (fleet_fields_of(ctx, "fleet timed traffic", n, slots, fields)) return -1;
+  FleetCall R{ ctx, "fleet timed traffic", n, slots, start_vertex, start_pos };
+  if (R.begin()) return -1;
   State& T = ctx->timed;
-  const uint32_t B = windows, V = ctx->V;
-  if (const char* why = timed_refusal(n, weights, depart, pace, B, tau, accumulate, T.T, T.cell ? T.B : 0u, T.tau)) {
+  TimedCells C{ ctx, n, windows, tau, accumulate };
+  if (const char* why = timed_refusal(n, weights, depart, pace, C.B, tau, accumulate, T.T, T.cell ? T.B : 0u, T.tau)) {
     ctx->err = std::string("fleet timed traffic: ") + why; return -1;
   }
-  const double mb = opt_set(ctx->opt.timed_traffic_max_mb) ? std::max(ctx->opt.timed_traffic_max_mb, 0.0) : kTimedTrafficMaxMb;
-  if (8.0 * (double)(V ? V : 1) * (double)B > mb * 1048576.0) { ctx->err = "fleet timed traffic: cells and holders are larger than timed_traffic_max_mb"; return -1; }
+  if (C.too_large(8.0, "fleet timed traffic: cells and holders are larger than timed_traffic_max_mb")) return -1;
   FleetStatsKeep keep(ctx->fleet);
-  bool fresh = false;
-  if (timed_reserve(ctx, n, B, &fresh)) return -1;
-  const size_t cells = (size_t)(V ? V : 1) * B;
-  if (!accumulate || fresh) {
-    HIPCHK(hipMemsetAsync(T.cell, 0, 4 * cells, ctx->stream));
-    HIPCHK(hipMemsetAsync(T.holder, 0xFF, 4 * cells, ctx->stream));
-    T.T = 0ull; T.tau = (float)tau;
-  }
-  HIPCHK(hipMemsetAsync(T.words, 0, sizeof(unsigned long long) * kWords, ctx->stream));
-  T.contributing = T.adds = T.beyond = 0; T.built_index = 0; T.ms_kernels = 0.f;
-  mnav_fleet::State& S = ctx->fleet;
-  uint32_t G = 1u;
-  while (G < B && G < 64u) G <<= 1;                                   // lanes per vertex of the peak pass
-  const uint32_t peak_blocks = (uint32_t)std::min<size_t>(((size_t)V * G + kTimedBlock - 1) / kTimedBlock, std::max(1u, opt_u32(ctx->opt.timed_peak_blocks, kPeakBlocks)));
+  if (C.reserve() || C.reset()) return -1;
   if (n) {
-    if (weights) HIPCHK(hipMemcpyAsync(T.weight, weights, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    if (depart) HIPCHK(hipMemcpyAsync(T.depart, depart, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    if (pace) HIPCHK(hipMemcpyAsync(T.pace, pace, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    if (key) HIPCHK(hipMemcpyAsync(T.key, key, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    mnav_fleet::Paths P{};
-    const uint32_t* d_vtx = nullptr;
-    if (fleet_classify_robots(ctx, n, slots, start_vertex, start_pos, fields, P, &d_vtx)) return -1;
-    T.built_index = S.built_index;
+    if (C.upload(weights, depart, pace, key) || R.classify()) return -1;
+    T.built_index = ctx->fleet.stats.built_index;
     Walk A{};
-    A.n = n; A.V = V; A.B = B; A.tau = T.tau; A.free_count = free_count;
-    A.slot = P.slot; A.vtx = P.vtx; A.fields = P.fields; A.code = P.code; A.len = P.len; A.potential = P.potential;
-    A.weight = weights ? T.weight.get() : (const uint32_t*)nullptr; A.depart = depart ? T.depart.get() : (const float*)nullptr;
-    A.pace = pace ? T.pace.get() : (const float*)nullptr; A.key = key ? T.key.get() : (const uint32_t*)nullptr;
-    A.cell = T.cell; A.holder = T.holder; A.words = T.words;
+    timed_fill(A, C, R);
+    A.free_count = free_count; A.words = T.words;
     A.conflict = T.conflict; A.yield = T.yield; A.fy_vertex = T.fy_vertex; A.fy_window = T.fy_window; A.fy_time = T.fy_time;
     const dim3 grid((n + kTimedBlock - 1) / kTimedBlock);
     hipLaunchKernelGGL(k_timed_add, grid, dim3(kTimedBlock), 0, ctx->stream, A);
-    if (V) hipLaunchKernelGGL(k_timed_peak, dim3(peak_blocks), dim3(kTimedBlock), 0, ctx->stream, V, B, G, free_count, T.cell.get(), T.peak.get(), T.window.get(), T.words.get());
+    if (timed_peak(ctx, C.B, free_count)) return -1;
     hipLaunchKernelGGL(k_timed_report, grid, dim3(kTimedBlock), 0, ctx->stream, A);   // after every add: the kernel boundary orders the reads
-    unsigned long long unused = 0; uint32_t cnt[mnav_fleet::kCounters + 1] = {};     // (no scan ran: the hop total is not this call's)
-    if (fleet_finish_classify(ctx, P, fields.size(), &unused, cnt)) return -1;
-    T.ms_kernels = S.ms_kernels;
-    if (code_out) HIPCHK(hipMemcpyAsync(code_out, S.code, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    if (vertex_out) HIPCHK(hipMemcpyAsync(vertex_out, d_vtx, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    if (potential_out) HIPCHK(hipMemcpyAsync(potential_out, S.potential, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    if (R.finish()) return -1;
+    T.ms_kernels = ctx->fleet.stats.ms_kernels;
+    if (R.download(code_out, vertex_out, potential_out)) return -1;
     if (conflict_hops_out) HIPCHK(hipMemcpyAsync(conflict_hops_out, T.conflict, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     if (yield_hops_out) HIPCHK(hipMemcpyAsync(yield_hops_out, T.yield, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     if (first_yield_vertex_out) HIPCHK(hipMemcpyAsync(first_yield_vertex_out, T.fy_vertex, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     if (first_yield_window_out) HIPCHK(hipMemcpyAsync(first_yield_window_out, T.fy_window, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     if (first_yield_time_out) HIPCHK(hipMemcpyAsync(first_yield_time_out, T.fy_time, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-  } else if (V) {
-    hipLaunchKernelGGL(k_timed_peak, dim3(peak_blocks), dim3(kTimedBlock), 0, ctx->stream, V, B, G, free_count, T.cell.get(), T.peak.get(), T.window.get(), T.words.get());
-    HIPCHK(hipGetLastError());
-  }
-  unsigned long long words[kWords] = {};
-  HIPCHK(hipMemcpyAsync(words, T.words, sizeof(words), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  T.T += words[kWeight];
-  T.contributing = words[kContributing]; T.adds = words[kAdds]; T.beyond = words[kBeyond];
-  T.occupied = words[kOccupied]; T.over = words[kOver]; T.largest = (uint32_t)words[kLargest]; T.yielding = (uint32_t)words[kYielding];
-  T.windows = B;
-  T.ms_total = (float)(1e-3 * (double)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count());
+  } else if (timed_peak(ctx, C.B, free_count)) return -1;
+  if (C.read_words()) return -1;
+  T.T += C.words[kWeight];
+  T.contributing = C.words[kContributing]; T.adds = C.words[kAdds]; T.beyond = C.words[kBeyond]; T.yielding = (uint32_t)C.words[kYielding];
+  T.ms_total = R.ms_total();
   return 0;
 }
 
@@ -177,30 +221,10 @@ int mnav_timed_traffic_stats(const mnav_ctx* ctx, uint32_t* contributing, uint64
 
 int mnav_layer_timed_traffic(mnav_ctx* ctx, uint32_t layer, uint32_t free_count, double gain, double cap, uint32_t* changed_out, uint32_t* n_changed)
 {
-  using namespace mnav_traffic;
-  if (!ctx) return -1;
-  ctx->err.clear();
-  if (traffic_check_args(ctx, gain, cap)) return -1;
-  if (layer_slot(ctx, layer, false)) return -1;
-  if (timed_reserve_peak(ctx)) return -1;
-  uint32_t c[mnav_chg::kCounters];
-  const TrafficRule rule{ ctx->timed.peak, free_count, (float)gain, (float)cap };   // the traffic rule on the peaks
-  return layer_change_list(ctx, ctx->layers[layer], rule, ctx->ev[7], c, changed_out, n_changed, nullptr);
+  return traffic_layer_run(ctx, true, layer, free_count, gain, cap, changed_out, n_changed);   // the traffic rule on the peaks
 }
 
 int mnav_map_timed_traffic(mnav_ctx* ctx, uint32_t layer, uint32_t free_count, double gain, double cap, uint32_t* changed_out, uint32_t* n_changed)
 {
-  using namespace mnav_map;
-  if (!ctx) return -1;
-  ctx->err.clear();
-  if (map_update_ready(ctx, layer, true)) return -1;
-  if (traffic_check_args(ctx, gain, cap)) return -1;                // (the graph stays usable)
-  State& S = ctx->map;
-  HIPCHK(hipEventRecord(S.ev[0], ctx->stream));
-  uint32_t nc = 0;
-  // the writer leaves its list (the vertices whose cost bits or flag changed) in the change-list scratch: it stays there
-  if (mnav_layer_timed_traffic(ctx, layer, free_count, gain, cap, nullptr, &nc)) return map_finish(ctx, -1);
-  Node& src = S.order[S.pos[layer]];
-  src.out = ctx->chg.ids; src.n_out = nc; src.flipped = nc;          // (the slot may have held lethal flags: assume some flipped)
-  return map_finish(ctx, map_propagate(ctx, (uint32_t)S.pos[layer], changed_out, n_changed));
+  return traffic_map_run(ctx, true, layer, free_count, gain, cap, changed_out, n_changed);
 }

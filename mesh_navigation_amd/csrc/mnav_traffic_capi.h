@@ -1,23 +1,8 @@
 // mnav_traffic_capi.h -- the C ABI of fleet traffic (include/mnav.h: mnav_fleet_traffic, mnav_traffic_download,
-// mnav_traffic_stats, mnav_layer_traffic, mnav_map_traffic) over the kernels of mnav_traffic.h, the shared steps of
-// mnav_fleet_capi.h, layer_change_list and map_propagate.  Included by mnav.hip inside its extern "C" block, after
-// mnav_dispatch_capi.h.
+// mnav_traffic_stats, mnav_layer_traffic, mnav_map_traffic) over the kernels of mnav_traffic.h, the FleetCall of
+// mnav_fleet_capi.h, layer_change_list and map_propagate; traffic_layer_run and traffic_map_run also serve the timed pair of
+// mnav_timed_capi.h.  Included by mnav.hip inside its extern "C" block, after mnav_dispatch_capi.h.
 #pragma once
-
-// The statistics of mnav_fleet_stats while a traffic call runs the fleet calls' shared steps: put back when it ends.
-struct FleetStatsKeep {
-  mnav_fleet::State& S;
-  uint32_t outcome[mnav_fleet::kCounters], built_index, chunks; uint64_t entries; float ms_kernels, ms_total;
-  explicit FleetStatsKeep(mnav_fleet::State& s) : S(s), built_index(s.built_index), chunks(s.chunks), entries(s.entries), ms_kernels(s.ms_kernels), ms_total(s.ms_total)
-  {
-    for (int k = 0; k < mnav_fleet::kCounters; ++k) outcome[k] = s.outcome[k];
-  }
-  ~FleetStatsKeep()
-  {
-    for (int k = 0; k < mnav_fleet::kCounters; ++k) S.outcome[k] = outcome[k];
-    S.built_index = built_index; S.chunks = chunks; S.entries = entries; S.ms_kernels = ms_kernels; S.ms_total = ms_total;
-  }
-};
 
 // the counts (zero when they are new), the counters and room for n weights
 static int traffic_reserve(mnav_ctx* ctx, size_t n)
@@ -48,12 +33,8 @@ int mnav_fleet_traffic(mnav_ctx* ctx, uint32_t n, const uint32_t* slots, const u
   if (!ctx) return -1;
   ctx->err.clear();
   if (!n && accumulate) return 0;                                     // (n = 0 without `accumulate` still starts the counts over)
-  const auto t0 = std::chrono::steady_clock::now();
-  // every refusal comes before the first device call: a refused call touches nothing
-  if (n && !slots) { ctx->err = "fleet traffic: null slots"; return -1; }
-  if (n && !start_vertex && !start_pos) { ctx->err = "fleet traffic: neither start vertices nor start positions"; return -1; }
-  std::vector<mnav_fleet::Field> fields;
-  if (fleet_fields_of(ctx, "fleet traffic", n, slots, fields)) return -1;
+  FleetCall R{ ctx, "fleet traffic", n, slots, start_vertex, start_pos };
+  if (R.begin()) return -1;
   State& T = ctx->traffic;
   unsigned long long all = accumulate ? T.T : 0ull;
   if (weights) for (uint32_t i = 0; i < n; ++i) all += weights[i];
@@ -66,26 +47,19 @@ int mnav_fleet_traffic(mnav_ctx* ctx, uint32_t n, const uint32_t* slots, const u
   HIPCHK(hipMemsetAsync(T.sums, 0, sizeof(unsigned long long) * kSums, ctx->stream));
   HIPCHK(hipMemsetAsync(T.vstat, 0, sizeof(uint32_t) * kVertexStats, ctx->stream));
   T.contributing = T.built_index = 0; T.adds = 0; T.ms_kernels = 0.f;
-  mnav_fleet::State& S = ctx->fleet;
-  const uint32_t gv = (V + kTrafficBlock - 1) / kTrafficBlock;
   if (n) {
     if (weights) HIPCHK(hipMemcpyAsync(T.weight, weights, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    mnav_fleet::Paths P{};
-    const uint32_t* d_vtx = nullptr;
-    if (fleet_classify_robots(ctx, n, slots, start_vertex, start_pos, fields, P, &d_vtx)) return -1;
-    T.built_index = S.built_index;
+    if (R.classify()) return -1;
+    T.built_index = ctx->fleet.stats.built_index;
     Add A{};
-    A.n = n; A.V = V; A.slot = P.slot; A.vtx = P.vtx; A.fields = P.fields; A.code = P.code; A.len = P.len; A.potential = P.potential;
-    A.weight = weights ? T.weight.get() : (const uint32_t*)nullptr; A.c = T.c; A.sums = T.sums;
+    fleet_fill(A, R, weights ? T.weight.get() : nullptr);
+    A.c = T.c; A.sums = T.sums;
     A.combine = opt_on(ctx->opt.traffic_combine) ? 1u : 0u;           // (off by default: measured)
     hipLaunchKernelGGL(k_traffic_add, dim3((n + kTrafficBlock - 1) / kTrafficBlock), dim3(kTrafficBlock), 0, ctx->stream, A);
-    if (V) hipLaunchKernelGGL(k_traffic_stats, dim3(gv), dim3(kTrafficBlock), 0, ctx->stream, V, T.c.get(), T.vstat.get());
-    unsigned long long unused = 0; uint32_t cnt[mnav_fleet::kCounters + 1] = {};   // (no scan ran: the hop total is not this call's)
-    if (fleet_finish_classify(ctx, P, fields.size(), &unused, cnt)) return -1;
-    T.ms_kernels = S.ms_kernels;
-    if (code_out) HIPCHK(hipMemcpyAsync(code_out, S.code, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    if (vertex_out) HIPCHK(hipMemcpyAsync(vertex_out, d_vtx, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    if (potential_out) HIPCHK(hipMemcpyAsync(potential_out, S.potential, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    if (V) hipLaunchKernelGGL(k_traffic_stats, dim3((V + kTrafficBlock - 1) / kTrafficBlock), dim3(kTrafficBlock), 0, ctx->stream, V, T.c.get(), T.vstat.get());
+    if (R.finish()) return -1;
+    T.ms_kernels = ctx->fleet.stats.ms_kernels;
+    if (R.download(code_out, vertex_out, potential_out)) return -1;
   }
   unsigned long long sums[kSums] = {}; uint32_t vstat[kVertexStats] = {};
   HIPCHK(hipMemcpyAsync(sums, T.sums, sizeof(sums), hipMemcpyDeviceToHost, ctx->stream));
@@ -94,7 +68,7 @@ int mnav_fleet_traffic(mnav_ctx* ctx, uint32_t n, const uint32_t* slots, const u
   T.T += sums[kWeight];
   T.contributing = (uint32_t)sums[kContributing]; T.adds = sums[kAdds];
   T.occupied = vstat[kOccupied]; T.peak = vstat[kPeak];
-  T.ms_total = (float)(1e-3 * (double)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count());
+  T.ms_total = R.ms_total();
   return 0;
 }
 
@@ -137,20 +111,25 @@ static int traffic_check_args(mnav_ctx* ctx, double gain, double cap)
   return 0;
 }
 
-int mnav_layer_traffic(mnav_ctx* ctx, uint32_t layer, uint32_t free_count, double gain, double cap, uint32_t* changed_out, uint32_t* n_changed)
+static int timed_reserve_peak(mnav_ctx* ctx);   // (mnav_timed_capi.h)
+
+// mnav_layer_traffic (timed == false: the rule reads the counts) and mnav_layer_timed_traffic (timed == true: the peaks of
+// the timed cells), as they stand
+static int traffic_layer_run(mnav_ctx* ctx, bool timed, uint32_t layer, uint32_t free_count, double gain, double cap, uint32_t* changed_out, uint32_t* n_changed)
 {
   using namespace mnav_traffic;
   if (!ctx) return -1;
   ctx->err.clear();
   if (traffic_check_args(ctx, gain, cap)) return -1;
   if (layer_slot(ctx, layer, false)) return -1;
-  if (traffic_reserve(ctx, 0)) return -1;
+  if (timed ? timed_reserve_peak(ctx) : traffic_reserve(ctx, 0)) return -1;
   uint32_t c[mnav_chg::kCounters];
-  const TrafficRule rule{ ctx->traffic.c, free_count, (float)gain, (float)cap };
+  const TrafficRule rule{ timed ? ctx->timed.peak.get() : ctx->traffic.c.get(), free_count, (float)gain, (float)cap };
   return layer_change_list(ctx, ctx->layers[layer], rule, ctx->ev[7], c, changed_out, n_changed, nullptr);
 }
 
-int mnav_map_traffic(mnav_ctx* ctx, uint32_t layer, uint32_t free_count, double gain, double cap, uint32_t* changed_out, uint32_t* n_changed)
+// mnav_map_traffic and mnav_map_timed_traffic: that layer call on an input node of the graph, then the propagation
+static int traffic_map_run(mnav_ctx* ctx, bool timed, uint32_t layer, uint32_t free_count, double gain, double cap, uint32_t* changed_out, uint32_t* n_changed)
 {
   using namespace mnav_map;
   if (!ctx) return -1;
@@ -161,8 +140,18 @@ int mnav_map_traffic(mnav_ctx* ctx, uint32_t layer, uint32_t free_count, double 
   HIPCHK(hipEventRecord(S.ev[0], ctx->stream));
   uint32_t nc = 0;
   // the writer leaves its list (the vertices whose cost bits or flag changed) in the change-list scratch: it stays there
-  if (mnav_layer_traffic(ctx, layer, free_count, gain, cap, nullptr, &nc)) return map_finish(ctx, -1);
+  if (traffic_layer_run(ctx, timed, layer, free_count, gain, cap, nullptr, &nc)) return map_finish(ctx, -1);
   Node& src = S.order[S.pos[layer]];
   src.out = ctx->chg.ids; src.n_out = nc; src.flipped = nc;          // (the slot may have held lethal flags: assume some flipped)
   return map_finish(ctx, map_propagate(ctx, (uint32_t)S.pos[layer], changed_out, n_changed));
+}
+
+int mnav_layer_traffic(mnav_ctx* ctx, uint32_t layer, uint32_t free_count, double gain, double cap, uint32_t* changed_out, uint32_t* n_changed)
+{
+  return traffic_layer_run(ctx, false, layer, free_count, gain, cap, changed_out, n_changed);
+}
+
+int mnav_map_traffic(mnav_ctx* ctx, uint32_t layer, uint32_t free_count, double gain, double cap, uint32_t* changed_out, uint32_t* n_changed)
+{
+  return traffic_map_run(ctx, false, layer, free_count, gain, cap, changed_out, n_changed);
 }

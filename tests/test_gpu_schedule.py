@@ -29,7 +29,7 @@ from tests import traffic_model as TM
 from tests.fleet_model import bits
 from tests.test_fleet_schedule_model import COUNTS, STAGGER_SCHEDULE, timing
 from tests.test_gpu_fleet import LIMIT, OFFSET, World, make_ctx, robots
-from tests.test_gpu_timed_traffic import same_cells, same_snapshot, snapshot
+from tests.test_gpu_timed_traffic import OUTPUTS as TT_OUTPUTS, STATS as TT_STATS, same_cells, same_snapshot, snapshot
 from tests.test_gpu_traffic import FAR
 from tests.test_timed_traffic_model import STAGGER_FREE, STAGGER_ROBOTS, STAGGER_WINDOWS, largest_potential
 
@@ -366,3 +366,110 @@ def test_the_layer_prices_the_schedule(world):
             assert np.array_equal(bits(cost), bits(TM.cost(peak, free_count, gain, cap))) and not lethal.any(), (free_count, gain, cap)
     finally:
         ctx.close()
+
+
+def test_the_occupancy_calls_grow_the_buffers_the_next_one_uses(world):
+    """mnav_fleet_traffic, mnav_fleet_timed_traffic and mnav_fleet_schedule share the fleet scratch, the per-robot weight /
+    depart / pace / key arrays and the cells, and each call grows what the next one then uses.  Ten calls whose arguments do
+    not depend on where they stand -- traffic with 3 robots; timed traffic with 200 robots in 70 windows (past 64: the peak
+    pass's lanes per vertex saturate); a schedule of 1 robot in 5 windows (the cells are made anew); a schedule of 200 robots
+    in 70 windows with all four per-robot arrays; timed traffic accumulated on top; traffic with 200 weighted robots; a
+    schedule of 300 robots (a second block of kFleetBlock = 256); n = 0 without accumulate to each of the three -- on a fresh
+    context in this order, on a second fresh context in the opposite order and on the first once more in the opposite order.
+    Every output of a call by its bits, its counts or cells, holders, peaks and windows and every statistic but the times
+    are the same in the three runs; the accumulating call, whose cells depend on the schedule before it (200 robots going
+    up, 300 coming down), equals the model on the model's cells of that schedule; no call moves fleet_stats() or the
+    statistics of an entry point whose state it does not write."""
+    W = world
+    fields = W.fields(offset=FAR)
+    tau = timing(1, fields, 0)[3]
+    none = np.zeros(0, np.uint32)
+
+    def fleet(n, seed):
+        sl, vt, run = run_of(W, fields, FAR, n, seed)
+        depart, pace, key, _ = timing(n, fields, seed)
+        w = np.random.default_rng(seed).integers(1, 4, n).astype(np.uint32)
+        return sl, vt, run, dict(weights=w, depart=depart, pace=pace, key=key)
+
+    r3, r1, ra, rb, rc, rd, re = fleet(3, 41), fleet(1, 42), fleet(200, 43), fleet(200, 44), fleet(200, 45), fleet(200, 46), fleet(300, 47)
+    calls = [("traffic", r3, dict()),
+             ("timed", ra, dict(weights=ra[3]["weights"], windows=70, tau=tau, free_count=1)),
+             ("schedule", r1, dict(windows=5, tau=tau, capacity=1, max_delay=4)),
+             ("schedule", rb, dict(rb[3], windows=70, tau=tau, capacity=3, max_delay=40)),
+             ("timed", rc, dict(rc[3], windows=70, tau=tau, free_count=3, accumulate=True)),
+             ("traffic", rd, dict(weights=rd[3]["weights"])),
+             ("schedule", re, dict(re[3], windows=70, tau=tau, capacity=2, max_delay=69)),
+             ("traffic", (none, none, None, {}), dict()),
+             ("timed", (none, none, None, {}), dict(windows=70, tau=tau)),
+             ("schedule", (none, none, None, {}), dict(windows=70, tau=tau))]
+    ON_TOP = 4
+
+    def fresh():
+        ctx = make_ctx(W)
+        ctx.plan_dijkstra_batch(W.seeds, W.targets, FAR, LIMIT)
+        return ctx
+
+    def plain(stats):
+        return {k: v for k, v in stats.items() if not k.startswith("ms_")}
+
+    def run(ctx, order):
+        seen = {}
+        for k in order:
+            kind, (sl, vt, _, _), kw = calls[k]
+            fs, others = ctx.fleet_stats(), (ctx.traffic_stats(), ctx.timed_traffic_stats(), ctx.schedule_stats())
+            if kind == "traffic":
+                out = ctx.fleet_traffic(sl, vt, **kw)
+                state = dict(counts=ctx.traffic_download(), traffic=plain(ctx.traffic_stats()))
+                assert (ctx.timed_traffic_stats(), ctx.schedule_stats()) == others[1:], (order, k)
+            else:
+                out = ctx.fleet_timed_traffic(sl, vt, **kw) if kind == "timed" else ctx.fleet_schedule(sl, vt, **kw)
+                state = dict(ctx.timed_traffic_download(), timed=plain(ctx.timed_traffic_stats()), schedule=plain(ctx.schedule_stats()) if kind == "schedule" else {})
+                assert ctx.traffic_stats() == others[0] and (kind == "schedule" or ctx.schedule_stats() == others[2]), (order, k)
+            assert ctx.fleet_stats() == fs, (order, k)
+            seen[k] = (out, state)
+        return seen
+
+    def same(a, b):
+        return a == b if isinstance(a, dict) else a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
+
+    def assert_same_calls(a, b, what):
+        for k in range(len(calls)):
+            if k != ON_TOP:
+                for x, y in zip(a[k], b[k]):
+                    assert x.keys() == y.keys() and all(same(x[f], y[f]) for f in x), (what, k, [f for f in x if not same(x[f], y[f])])
+
+    def assert_on_top(got, before, where):
+        """the accumulating call against the model: on the cells the model's schedule `before` leaves"""
+        _, (sl, vt, r, _), kw = calls[before]
+        cells = XM.Cells(W.V)
+        assert SM.schedule(cells, fields, sl, vt, kw["weights"], kw["depart"], kw["pace"], kw["key"], 70, tau, kw["capacity"], kw["max_delay"], run=r) is not None
+        _, (sl, vt, r, _), kw = calls[ON_TOP]
+        want = XM.timed(cells, fields, sl, vt, kw["weights"], kw["depart"], kw["pace"], kw["key"], 70, tau, kw["free_count"], True, run=r)
+        out, state = got
+        assert np.array_equal(out["vertex"], vt) and all(np.array_equal(out[f], want[f]) for f in TT_OUTPUTS if f != "vertex"), where
+        assert np.array_equal(bits(out["potential"]), bits(want["potential"])) and np.array_equal(bits(out["first_yield_time"]), bits(want["first_yield_time"])), where
+        assert np.array_equal(state["cells"], cells.cell) and np.array_equal(state["holders"], cells.holder), where
+        assert np.array_equal(state["peak"], cells.peak) and np.array_equal(state["window"], cells.window), where
+        assert {f: state["timed"][f] for f in TT_STATS} == {f: want[f] for f in TT_STATS} and want["contributing"] > 50 and want["over_cells"] > 0, (where, state["timed"])
+
+    up_order, down_order = tuple(range(len(calls))), tuple(reversed(range(len(calls))))
+    a, b = fresh(), fresh()
+    try:
+        up = run(a, up_order)
+        down = run(b, down_order)
+        assert_same_calls(up, down, "each call grows what the next uses, up / down")
+        a.fleet_paths(r3[0], r3[1])                                   # fleet_stats() tells of a call: the occupancy calls put it back
+        assert a.fleet_stats()["served"] + a.fleet_stats()["beyond_field"] + a.fleet_stats()["no_path"] + a.fleet_stats()["invalid"] == 3
+        again = run(a, down_order)
+        assert_same_calls(up, again, "over the capacities left")
+        assert_on_top(up[ON_TOP], 3, "on the 200-robot schedule")
+        assert_on_top(down[ON_TOP], 6, "on the 300-robot schedule")
+        for x, y in zip(down[ON_TOP], again[ON_TOP]):
+            assert all(same(x[f], y[f]) for f in x), "on the 300-robot schedule, again"
+        # what the calls were: the schedules commit and delay, the n = 0 calls leave nothing
+        assert up[3][1]["schedule"]["committed"] > 50 and up[3][1]["schedule"]["delayed"] > 0 and up[6][1]["schedule"]["committed"] > 50
+        assert up[1][1]["timed"]["windows"] == 70 and up[2][1]["timed"]["windows"] == 5 and up[5][1]["traffic"]["contributing"] > 50
+        assert not up[7][1]["counts"].any() and not up[8][1]["cells"].any() and not up[9][1]["cells"].any() and up[9][1]["cells"].shape == (W.V, 70)
+    finally:
+        a.close()
+        b.close()
