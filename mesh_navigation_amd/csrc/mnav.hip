@@ -464,10 +464,21 @@ int launch_steps(mnav_ctx* ctx, uint32_t n, uint32_t G, int count, bool wide)
 
 __global__ void k_stamp_to_host(unsigned long long* __restrict__ dst_host) { *dst_host = wall_clock64(); }   // (trace: the device's 100 MHz clock)
 
+// Step launches of one chunk: kChunk per graph replay; with no_graph the option debug_chunk (a finer control-block trace).
+// Every chunk starts its launches at j = 0 and the kernels rotate control and counter blocks by j % 6, so a chunk is a whole
+// number of rotations: debug_chunk is rounded up to a multiple of 6, and a value below 1 (or a NaN) is the default.
+int steps_per_chunk(const mnav_ctx* ctx)
+{
+  const double c = ctx->opt.debug_chunk;
+  if (ctx->use_graph || !(c >= 1.0)) return kChunk;
+  const double up = 6.0 * std::ceil(std::min(c, 6.0e6) / 6.0);
+  return (int)up;
+}
+
 template <uint32_t PLANNER>
 int run_chunk(mnav_ctx* ctx, uint32_t n, uint32_t G, bool wide)
 {
-  if (!ctx->use_graph) return launch_steps<PLANNER>(ctx, n, G, opt_set(ctx->opt.debug_chunk) ? (int)ctx->opt.debug_chunk : kChunk, wide);   // debug: finer control-block trace
+  if (!ctx->use_graph) return launch_steps<PLANNER>(ctx, n, G, steps_per_chunk(ctx), wide);
   const uint64_t key = ((uint64_t)PLANNER << 60) | ((uint64_t)(wide ? ctx->wide_groups : 0u) << 57) | ((uint64_t)n << 32) | G;
   auto it = ctx->graphs.find(key);
   if (it == ctx->graphs.end()) {

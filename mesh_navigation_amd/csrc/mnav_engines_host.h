@@ -28,7 +28,8 @@ int run_plans(mnav_ctx* ctx, uint32_t n, const std::vector<PlanIn>& in, double o
   if (ensure_slots(ctx, n, cvp, true, cvp || ctx->want_vec)) return -1;
   if (want_path && ensure_paths(ctx, n)) return -1;
   // default band width: 3 mean edge weights for the Dijkstra gather steps, 12 for CVP (measured on C3:
-  // fewer, fuller bands -- 20 % less time for one plan and for batches; results do not depend on it)
+  // fewer, fuller bands -- 20 % less time for one plan and for batches; that the results do not depend on it is what
+  // tests/test_gpu_engine_knobs.py holds both step kernels to, from 0.05 mean edge weights to a band wider than the field)
   const float delta = ctx->delta_user > 0.f ? ctx->delta_user : (cvp ? 4.0f * ctx->delta_auto : ctx->delta_auto);
   std::vector<Plan> hp(n);
   std::vector<float*> vecs(n);
@@ -97,7 +98,7 @@ int run_plans(mnav_ctx* ctx, uint32_t n, const std::vector<PlanIn>& in, double o
     HIPCHK(hipEventRecord(ctx->evc[0], ctx->stream));
     if (run_chunk<PLANNER>(ctx, n, G, wide)) return -1;
     HIPCHK(hipEventRecord(ctx->evc[1], ctx->stream));
-    launches += kChunk;
+    launches += (uint32_t)steps_per_chunk(ctx);
     HIPCHK(hipMemcpyAsync(ctx->h_ctl, ctx->d_ctl_pool, 2 * sizeof(Ctl) * n, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     ctx->ms_chunks += ev_ms(ctx->evc[0], ctx->evc[1]);

@@ -8,7 +8,7 @@
   X(verbose)             /* 1: one line per engine build / asynchronous call on stderr */                                                 \
   X(trace)               /* 1: host-side trace points on stderr */                                                                        \
   X(no_graph)            /* 1: launch the step / round kernels one by one instead of replaying hipGraphs (profilers that cannot see into graphs) */ \
-  X(debug_chunk)         /* steps per host look when no_graph is set */                                                                   \
+  X(debug_chunk)         /* step launches per host look when no_graph is set: rounded up to a multiple of 6 (the kernels rotate their control blocks by launch % 6 and every chunk starts at 0); below 1: the default, 96; the result does not depend on it */ \
   X(dijkstra_engine)     /* 0 tile rounds, 1 band steps, 3 auto, 5 tile-batch, 6 asynchronous tiles */                            \
   X(blocks_per_plan)     /* band steps: workgroups per plan */                                                                            \
   X(tile_blocks)         /* tile rounds: workgroups per plan */                                                                           \
