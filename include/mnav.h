@@ -681,6 +681,86 @@ int mnav_fleet_rollout_stats(const mnav_ctx* ctx, uint32_t* status_counts, uint6
                              uint64_t* max_pairs, uint32_t* max_pairs_tick, float* min_sep2, uint32_t* min_pair, uint64_t* tests,
                              uint32_t* max_cell, float* ms_separation, float* ms_kernels, float* ms_total);
 
+/* -- fleet rollouts in which robots yield: right of way, decided inside the check ------------------------
+ * mnav_fleet_rollout reports near robots and nobody reacts.  mnav_fleet_rollout_yield evaluates a right-of-way rule inside the
+ * same check, on the device: a robot that has to yield has no controller tick until the next check, so followers queue
+ * behind the robot ahead instead of driving through it, and arrival ticks, travel and cost integrals are those of robots
+ * that share the mesh.  The rule is stateless per check and made of compares, counts and minima: the same bits on every
+ * run, with any separation_cell_scale. */
+typedef struct mnav_yield_config {
+  double   ahead_cos;   /* used as c = (float)ahead_cos, finite, 0 <= c < 1: the cosine of the half angle of the cone "ahead";
+                           c2 = c * c in float32 */
+  uint32_t flags;       /* reserved, must be 0 */
+} mnav_yield_config;
+/* Every argument up to min_sep_robot_out is mnav_fleet_rollout's, in its order and with its meaning; then the yield group.
+ * YIELD IS NULL.  Then priority, hold_in, hold_out and the four yield outputs must be NULL too, every output is
+ * mnav_fleet_rollout's bit for bit, and the call launches the very kernels that call launches.
+ * YIELD IS GIVEN.  separation must be given: the rule uses its radius, check_stride and presence flags, and the separation
+ * outputs are what mnav_fleet_rollout would report for the motion that results.
+ * TERMS at the check after call tick t (t % check_stride == 0), on positions, headings, statuses, start ticks and priorities
+ * as they stand after tick t:
+ *   robot i is a MOVER iff its status is RUNNING and it is not waiting (t > start_tick[i]);
+ *   a PARTNER of i is what it is in mnav_fleet_rollout: a present robot j != i with d2 <= r2, d2 the float32 sum defined there;
+ *   A(i, j), "j is AHEAD of i": ex = pj.x - pi.x (ey, ez alike), dot = (dir_i.x*ex + dir_i.y*ey) + dir_i.z*ez,
+ *     A = dot > 0 && dot*dot >= c2*d2, all float32, every operation rounded on its own (no contraction), d2 the pair's d2
+ *     above.  A NaN anywhere gives false (a NaN heading sees nobody ahead).  Coincident robots have dot == 0: they are ahead
+ *     of nobody;
+ *   before(j, i) iff (priority[j], j) < (priority[i], i) lexicographically.  priority: n entries, or NULL for all equal, so
+ *     that the index decides.  A smaller priority value has right of way.
+ * THE DECISION.  A present mover i YIELDS TO its partner j iff
+ *     j is not a mover (stranded, or waiting or REACHED and kept present by a flag) and A(i, j), or
+ *     j is a mover and A(i, j) && (!A(j, i) || before(j, i)).
+ * A follower yields to whoever drives ahead of it, whatever the priorities; of two robots that face each other the one
+ * without right of way yields; robots side by side do not yield.  hold[i] = 1 iff i is a present mover and yields to at
+ * least one partner, else 0.  The decision never reads the flags of the check before, so within a check it cannot
+ * oscillate, and a check depends on nothing but the state after its tick.  A check that the guard skips sets every hold to
+ * 0: with no information nobody is held.
+ * THE TICK.  At call tick t robot i has a controller tick iff it is RUNNING, not waiting, and hold[i] == 0, where hold is
+ * hold_in (n bytes, NULL for all 0; any non-zero byte is 1) until the first check of the call and afterwards what the latest
+ * check left.  A held robot is treated like a waiting one: its ticks, pos, dir, face, travel, cost_integral and
+ * min_goal_dist are untouched and the trace repeats its position.
+ * Per robot, over this call (any pointer may be NULL; all of them must be NULL when yield is NULL):
+ *   hold_checks_out       checks that left it held
+ *   held_ticks_out        call ticks at which it was RUNNING, not waiting and held
+ *   first_hold_tick_out   the tick of the first check that held it, or MNAV_NONE
+ *   first_hold_robot_out  its BLOCKER at that check: the yielded-to partner with the smallest d2, ties to the smallest index;
+ *                         or MNAV_NONE
+ *   hold_out              n bytes, 0 or 1: the flags after the last check of the call (hold_in as flags if no check ran)
+ * RESUMING works as in mnav_fleet_rollout -- the RUNNING robots' pos_out, dir_out and face_out back in, the start ticks
+ * reduced by the ticks already run -- with those robots' hold_out fed back as hold_in.  The second call continues the first
+ * exactly (the state bits of one call of a + b ticks; hold_checks and held_ticks add up) when the first call's tick count a
+ * is a multiple of check_stride -- its last tick then had a check, the flags are that check's, and the checks of the second
+ * call fall on the ticks they fall on in one call -- and no robot left out was present in a later check (a stopped robot
+ * that is not fed back stands in nobody's way any more).
+ * WHAT THE RULE DOES NOT PROMISE.  It is right of way, not avoidance: the velocity command is never changed, and a robot with
+ * right of way drives on, into a held robot if that is where its field leads.  A ring of followers, each behind the next, can
+ * hold each other for good; nothing resolves that deadlock, mnav_fleet_yield_stats shows it (robots held after the last
+ * check, held robot-ticks).
+ * Returns 0, 1 and 2 as mnav_fleet_rollout, or -1 with mnav_last_error set and NOTHING touched: every refusal of
+ * mnav_fleet_rollout, yield given without separation, an ahead_cos whose float is not finite or outside 0 <= c < 1, a non-zero
+ * flag, priority, hold_in, hold_out or a yield output given without yield.  n = 0 does nothing.  The call has statistics
+ * records of its own: it leaves mnav_rollout_stats and mnav_fleet_rollout_stats as they were, and those calls leave
+ * mnav_fleet_yield_stats.  DESIGN.md section 3.21. */
+int mnav_fleet_rollout_yield(mnav_ctx* ctx, uint32_t n, const float* pos, const float* dir, const float* up, const uint32_t* face_in,
+                             const uint32_t* slots, const uint32_t* seed_faces, const float* goal_pos, const float* goal_dir,
+                             const mnav_follow_config* config, const mnav_rollout_config* rollout, const uint32_t* start_tick,
+                             const mnav_separation_config* separation, int32_t* status_out, uint32_t* ticks_out, float* pos_out,
+                             float* dir_out, uint32_t* face_out, double* travel_out, double* cost_integral_out,
+                             float* min_goal_dist_out, float* trace_out, uint32_t* near_checks_out, uint32_t* max_partners_out,
+                             uint32_t* first_near_tick_out, uint32_t* first_near_robot_out, float* min_sep2_out,
+                             uint32_t* min_sep_tick_out, uint32_t* min_sep_robot_out, const mnav_yield_config* yield,
+                             const uint32_t* priority, const uint8_t* hold_in, uint8_t* hold_out, uint32_t* hold_checks_out,
+                             uint32_t* held_ticks_out, uint32_t* first_hold_tick_out, uint32_t* first_hold_robot_out);
+/* The last mnav_fleet_rollout_yield: robots with hold_checks > 0; the sum of held_ticks over the robots; the most robots one
+ * check held and that check's tick (the first such check among those run; 0 and MNAV_NONE without a check run; a skipped
+ * check holds nobody and is no candidate); the robots held after the last check (the set bytes of hold_out); the checks
+ * run and skipped and the tick of the first skipped check (MNAV_NONE: none), as mnav_fleet_rollout_stats counts them; device
+ * milliseconds of the pair passes (the kernel that decides), of all kernels of the checks, of all kernels, and host
+ * milliseconds of the whole call.  All 0 / MNAV_NONE after a call with yield = NULL, except the times.  Any pointer may be
+ * NULL. */
+int mnav_fleet_yield_stats(const mnav_ctx* ctx, uint32_t* robots_held, uint64_t* held_ticks, uint32_t* max_held, uint32_t* max_held_tick,
+                           uint32_t* held_last, uint32_t* checks_run, uint32_t* checks_skipped, uint32_t* first_skipped_tick, float* ms_pair, float* ms_separation, float* ms_kernels, float* ms_total);
+
 /* -- fleet paths and walks: many robots per resident field ---------------------------------------------
  * A Dijkstra call returns one vertex path per plan, from the plan's seed (the goal) to its one target.  The field is seeded
  * at the goal, so it already holds the path of every robot inside it: mnav_fleet_paths hands Move Base Flex's setPlan a

@@ -37,6 +37,7 @@ SYMBOLS = [
     "mnav_layer_border", "mnav_layer_clearance", "mnav_clearance_download", "mnav_clearance_stats",
     "mnav_locate", "mnav_locate_stats", "mnav_plan_dijkstra_batch_at", "mnav_plan_cvp_batch_at",
     "mnav_follow_batch", "mnav_follow_stats", "mnav_follow_rollout", "mnav_rollout_stats", "mnav_fleet_rollout", "mnav_fleet_rollout_stats",
+    "mnav_fleet_rollout_yield", "mnav_fleet_yield_stats",
     "mnav_map_configure", "mnav_map_compute", "mnav_map_layer_changed", "mnav_map_update_layer", "mnav_map_obstacle", "mnav_map_stats",
     "mnav_replan_dijkstra_batch", "mnav_replan_plans", "mnav_replan_stats", "mnav_replan_dijkstra_each", "mnav_replan_each_stats",
     "mnav_replan_warm_stats",
@@ -123,6 +124,16 @@ class SeparationConfig(C.Structure):
 SEP_WAITING_PRESENT, SEP_REACHED_PRESENT = 1, 2
 
 
+class YieldConfig(C.Structure):
+    """mnav_yield_config (include/mnav.h): the cosine of the half angle of the cone in which a partner counts as ahead, and
+    the reserved flags (0)."""
+    _fields_ = [("ahead_cos", C.c_double), ("flags", C.c_uint32)]
+    DEFAULTS = dict(ahead_cos=0.5, flags=0)
+
+    def __init__(self, **kw):
+        super().__init__(**{**self.DEFAULTS, **kw})
+
+
 class MapNode(C.Structure):
     """mnav_map_node (include/mnav.h): one node of the resident layer graph"""
     _fields_ = [("layer", C.c_uint32), ("kind", C.c_uint32), ("n_inputs", C.c_uint32), ("inputs", C.c_uint32 * 8),
@@ -176,6 +187,18 @@ class FleetRolloutOut(RolloutOut):
     skipped: bool = False
 
 
+@dataclass
+class FleetYieldOut(FleetRolloutOut):
+    """One mnav_fleet_rollout_yield call: FleetRolloutOut and the yield outputs, one row per robot (None without a yield
+    config or where not asked for).  `hold`: the flags after the last check, what a resumed call takes as hold_in."""
+    hold: np.ndarray | None = None             # (n,) uint8, 0 or 1
+    hold_checks: np.ndarray | None = None
+    held_ticks: np.ndarray | None = None
+    first_hold_tick: np.ndarray | None = None
+    first_hold_robot: np.ndarray | None = None
+
+
+YIELD_OUTPUTS = ("hold", "hold_checks", "held_ticks", "first_hold_tick", "first_hold_robot")
 SEPARATION_OUTPUTS = ("near_checks", "max_partners", "first_near_tick", "first_near_robot", "min_sep2", "min_sep_tick", "min_sep_robot")
 
 _lib = None
@@ -234,6 +257,10 @@ def load(path: str | None = None):
     L.mnav_fleet_rollout.argtypes = [vp, u32] + [vp] * 8 + [C.POINTER(FollowConfig), C.POINTER(RolloutConfig), vp, C.POINTER(SeparationConfig)] + [vp] * 16
     L.mnav_fleet_rollout_stats.restype = C.c_int
     L.mnav_fleet_rollout_stats.argtypes = [vp] + [vp] * 20
+    L.mnav_fleet_rollout_yield.restype = C.c_int
+    L.mnav_fleet_rollout_yield.argtypes = L.mnav_fleet_rollout.argtypes + [C.POINTER(YieldConfig)] + [vp] * 7
+    L.mnav_fleet_yield_stats.restype = C.c_int
+    L.mnav_fleet_yield_stats.argtypes = [vp] + [vp] * 12
     L.mnav_rollout_stats.restype = C.c_int
     L.mnav_rollout_stats.argtypes = [vp, C.POINTER(u32 * 4)] + [C.POINTER(C.c_uint64)] * 4 + [C.POINTER(u32)] + [C.POINTER(C.c_float)] * 2
     L.mnav_map_configure.restype = C.c_int
@@ -1567,6 +1594,42 @@ class MnavContext:
         out = dict(running=sc[0], reached=sc[1], out_of_map=sc[2], no_field=sc[3])
         out.update({k: ((pair[0], pair[1]) if t is None else v[k].value) for k, t in spec})
         return out
+
+    def fleet_rollout_yield(self, pos, direction, up, face_in, slots, seed_faces=None, goal_pos=None, goal_dir=None, config: FollowConfig | None = None,
+                            rollout: RolloutConfig | None = None, start_tick=None, separation: SeparationConfig | None = None,
+                            yield_config: YieldConfig | None = None, priority=None, hold_in=None, outputs=None) -> FleetYieldOut:
+        """fleet_rollout() in which a robot that has to yield to a partner ahead of it has no tick until the next check
+        (mnav_fleet_rollout_yield, include/mnav.h).  yield_config None: fleet_rollout() bit for bit.  priority: n uint32 or
+        None (the index decides); hold_in: n bytes or None, the `hold` of the call this one resumes.  `outputs`: the names of
+        the FleetYieldOut fields to fetch (default: all; the yield outputs only with `yield_config`)."""
+        n = int(_f32(pos).reshape(-1, 3).shape[0])
+        prio = None if priority is None else _u32(priority).reshape(-1)
+        hin = None if hold_in is None else np.ascontiguousarray(hold_in, np.uint8).reshape(-1)
+        if any(a is not None and a.shape[0] != n for a in (prio, hin)):
+            raise ValueError("fleet_rollout_yield: priority / hold_in need one entry per robot")
+        want = set(YIELD_OUTPUTS) if outputs is None else set(outputs) & set(YIELD_OUTPUTS)
+        y = {k: (np.zeros(n, np.uint8 if k == "hold" else np.uint32) if yield_config is not None and k in want else None) for k in YIELD_OUTPUTS}
+        tail = [None if yield_config is None else C.byref(yield_config), _p(prio), _p(hin), *[_p(y[k]) for k in YIELD_OUTPUTS]]
+
+        def fn(*args):
+            return self._L.mnav_fleet_rollout_yield(*args, *tail)
+
+        fn.__name__ = "mnav_fleet_rollout_yield"
+        o, rc = self._rollout("fleet_rollout_yield", fn, pos, direction, up, face_in, slots, [seed_faces, start_tick],
+                              "seed_faces / start_tick need one entry per robot", goal_pos, goal_dir, config, rollout,
+                              None if outputs is None else [k for k in outputs if k not in YIELD_OUTPUTS],
+                              more=[None if separation is None else C.byref(separation)],
+                              extra={k: np.float32 if k == "min_sep2" else np.uint32 for k in SEPARATION_OUTPUTS}, with_extra=separation is not None)
+        return FleetYieldOut(**o, **y, cancelled=rc == 1, skipped=rc == 2)
+
+    def fleet_yield_stats(self) -> dict:
+        u64, u32, f32 = C.c_uint64, C.c_uint32, C.c_float
+        spec = [("robots_held", u32), ("held_ticks", u64), ("max_held", u32), ("max_held_tick", u32), ("held_last", u32), ("checks_run", u32), ("checks_skipped", u32),
+                ("first_skipped_tick", u32), ("ms_pair", f32), ("ms_separation", f32),
+                ("ms_kernels", f32), ("ms_total", f32)]
+        v = {k: t() for k, t in spec}
+        self._L.mnav_fleet_yield_stats(self._h, *[C.byref(v[k]) for k, _ in spec])
+        return {k: v[k].value for k, _ in spec}
 
     def plan_dijkstra_batch_at(self, goal_pos, start_pos, goal_dist_offset: float = 0.3, cost_limit: float = 1.0,
                                want_fields: bool = False, path_cap: int | None = None, want_stats: bool = True):

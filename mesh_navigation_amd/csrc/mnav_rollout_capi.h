@@ -1,8 +1,9 @@
 // mnav_rollout_capi.h -- the C ABI of the device rollouts (include/mnav.h: mnav_follow_rollout, mnav_rollout_stats,
-// mnav_fleet_rollout, mnav_fleet_rollout_stats) over the kernels of mnav_rollout.h and mnav_fleet_rollout.h.  Included by
+// mnav_fleet_rollout, mnav_fleet_rollout_stats, mnav_fleet_rollout_yield, mnav_fleet_yield_stats) over the kernels of
+// mnav_rollout.h, mnav_fleet_rollout.h and mnav_fleet_yield.h.  Included by
 // mnav.hip inside its extern "C" block, after mnav_follow_capi.h (the argument checks are the follower's) and
-// mnav_locate_capi.h (the index build is the lookup's own).  One driver, rollout_run, holds the call; the two entry points
-// hand it their arguments and their own statistics record.  The device buffers are shared (a call uploads every input at
+// mnav_locate_capi.h (the index build is the lookup's own).  One driver, rollout_run, holds the call; the three entry points
+// hand it their arguments and their own statistics records.  The device buffers are shared (a call uploads every input at
 // entry), the statistics are kept apart: a call of one entry point leaves what the other's *_stats tells alone.
 #pragma once
 
@@ -70,6 +71,37 @@ static int fleet_rollout_reserve(mnav_ctx* ctx, size_t n, bool starts, bool sep,
   return 0;
 }
 
+// what the right-of-way rule needs beside the separation check's buffers
+static int fleet_yield_reserve(mnav_ctx* ctx, size_t n, size_t checks)
+{
+  mnav_frol::YldState& Y = ctx->yld;
+  const char* oom = "fleet rollout yield: out of device memory";
+  if (!Y.have_ev) {
+    for (auto& e : Y.ev) HIPCHK(hipEventCreate(e.out()));
+    Y.have_ev = true;
+  }
+  if (n > Y.cap) {
+    Y.cap = 0;
+    if (alloc_group(Y.hold, n, Y.priority, 4 * n, Y.hold_checks, 4 * n, Y.held_ticks, 4 * n, Y.first_hold_tick, 4 * n, Y.first_hold_robot, 4 * n) != hipSuccess) {
+      ctx->err = oom; return -1;
+    }
+    Y.cap = n;
+  }
+  if (checks > Y.chk_cap) {
+    Y.chk_cap = 0;
+    if (Y.ychk.alloc(sizeof(uint32_t) * mnav_frol::kYldCheckWords * checks) != hipSuccess) { ctx->err = oom; return -1; }
+    Y.chk_cap = checks;
+  }
+  return 0;
+}
+
+// The optional last input of rollout_run: the right-of-way rule of mnav_fleet_rollout_yield.  config null: no rule, and then
+// every other pointer must be null; host pointers, each output may be null.  stats: the record of mnav_fleet_yield_stats.
+struct YieldCall {
+  const mnav_yield_config* config = nullptr; const uint32_t* priority = nullptr; const uint8_t* hold_in = nullptr; uint8_t* hold_out = nullptr;
+  mnav_frol::YRows out = { nullptr, nullptr, nullptr, nullptr }; mnav_frol::YldStats* stats = nullptr;
+};
+
 // The argument checks of a rollout beside the follower's, all on the host: -1 with ctx->err set, or 0.
 static int rollout_check(mnav_ctx* ctx, const float* goal_pos, const float* goal_dir, const mnav_follow_config* config, const mnav_rollout_config* rollout,
                          const float* trace_out)
@@ -88,15 +120,16 @@ static int rollout_check(mnav_ctx* ctx, const float* goal_pos, const float* goal
   return 0;
 }
 
-// The whole call of both entry points.  start_tick: null, or a departure tick per robot; separation: null, or the check,
-// whose per-robot outputs go to sep_out (host pointers, each may be null; all null without a separation).  `tag` names the
+// The whole call of every entry point.  start_tick: null, or a departure tick per robot; separation: null, or the check,
+// whose per-robot outputs go to sep_out (host pointers, each may be null; all null without a separation); yld: the rule
+// inside the check, or one without a config.  `tag` names the
 // entry point in the messages that do, `stats` / `sep_stats` are the records of its *_stats function.  Returns 0, 1 when
 // cancelled, 2 when a check was skipped, -1 with ctx->err set.
 static int rollout_run(mnav_ctx* ctx, const char* tag, mnav_rol::Stats& stats, mnav_frol::SepStats& sep_stats, uint32_t n, const float* pos, const float* dir,
                        const float* up, const uint32_t* face_in, const uint32_t* slots, const uint32_t* seed_faces, const float* goal_pos, const float* goal_dir,
                        const mnav_follow_config* config, const mnav_rollout_config* rollout, const uint32_t* start_tick, const mnav_separation_config* separation,
                        int32_t* status_out, uint32_t* ticks_out, float* pos_out, float* dir_out, uint32_t* face_out, double* travel_out, double* cost_integral_out,
-                       float* min_goal_dist_out, float* trace_out, const mnav_frol::Rows& sep_out)
+                       float* min_goal_dist_out, float* trace_out, const mnav_frol::Rows& sep_out, const YieldCall& yld)
 {
   using namespace mnav_frol;
   using mnav_rol::Batch; using mnav_rol::kCounters; using mnav_rol::kStayBlock; using mnav_rol::Params; using mnav::WalkMesh;
@@ -124,6 +157,19 @@ static int rollout_run(mnav_ctx* ctx, const char* tag, mnav_rol::Stats& stats, m
     if (check_stride < 1 || check_stride > ticks) { ctx->err = "fleet rollout: check_stride outside 1 .. ticks"; return -1; }
     if (flags & ~kKnownFlags) { ctx->err = "fleet rollout: unknown separation flag"; return -1; }
   }
+  const bool yielding = yld.config != nullptr;
+  float ahead_c2 = 0.f;
+  if (!yielding) {
+    if (yld.priority || yld.hold_in || yld.hold_out || yld.out.hold_checks || yld.out.held_ticks || yld.out.first_hold_tick || yld.out.first_hold_robot) {
+      ctx->err = "fleet rollout yield: a yield input or output without a yield config"; return -1;
+    }
+  } else {
+    if (!separation) { ctx->err = "fleet rollout yield: a yield config without a separation config"; return -1; }
+    const float c = (float)yld.config->ahead_cos;
+    if (!yld_cos_ok(c)) { ctx->err = "fleet rollout yield: ahead_cos: (float)ahead_cos must be finite, at least 0 and below 1"; return -1; }
+    if (yld.config->flags) { ctx->err = "fleet rollout yield: the flags of the yield config are reserved and must be 0"; return -1; }
+    ahead_c2 = c * c;
+  }
   const uint32_t checks = separation ? ticks / check_stride : 0, table = separation ? sep_table_size(n) : 0;
   const double max_tests_d = opt_set(ctx->opt.separation_max_tests) ? std::max(ctx->opt.separation_max_tests, 0.0) : kDefaultMaxTests;
   const unsigned long long max_tests = max_tests_d >= 18446744073709551615.0 ? ~0ull : (unsigned long long)max_tests_d;
@@ -131,11 +177,13 @@ static int rollout_run(mnav_ctx* ctx, const char* tag, mnav_rol::Stats& stats, m
   cancel_reset(ctx);                                                  // as the plan calls do
   if (upload_walk_mesh(ctx)) return -1;
   if (staging_reserve(ctx, n, ctx->res.plans(), tag) || rollout_reserve(ctx, tag, n, goal_pos != nullptr, ticks, 3 * (size_t)n * rows) ||
-      fleet_rollout_reserve(ctx, n, start_tick != nullptr, separation != nullptr, table, checks)) return -1;
+      fleet_rollout_reserve(ctx, n, start_tick != nullptr || yielding, separation != nullptr, table, checks) || (yielding && fleet_yield_reserve(ctx, n, checks))) return -1;
   mnav_rol::Dev& R = ctx->rol;
   State& S = ctx->frol;
+  YldState& Y = ctx->yld;
   mnav_fol::Staging& G = ctx->stage;
   stats = {}; sep_stats = {};
+  if (yld.stats) *yld.stats = {};
   if (locate_ensure(ctx, &stats.built_index)) return -1;              // no look at the lists between ticks: the index exists before the first one
   const mnav_loc::State& L = ctx->loc;
   Batch B{};
@@ -145,6 +193,8 @@ static int rollout_run(mnav_ctx* ctx, const char* tag, mnav_rol::Stats& stats, m
     HIPCHK(hipMemcpyAsync(R.goal_dir, goal_dir, 12 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
   }
   if (start_tick) HIPCHK(hipMemcpyAsync(S.start_tick, start_tick, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  else if (yielding) HIPCHK(hipMemsetAsync(S.start_tick, 0, 4 * (size_t)n, ctx->stream));   // FleetTick's start ticks are never null
+  std::vector<uint8_t> h_hold;                                        // hold_in as flags; lives until the synchronise of the first block
   HIPCHK(hipMemsetAsync(R.status, 0, 4 * (size_t)n, ctx->stream));    // kRunning
   HIPCHK(hipMemsetAsync(R.ticks, 0, 4 * (size_t)n, ctx->stream));
   HIPCHK(hipMemsetAsync(R.travel, 0, 8 * (size_t)n, ctx->stream));
@@ -155,8 +205,9 @@ static int rollout_run(mnav_ctx* ctx, const char* tag, mnav_rol::Stats& stats, m
   B.status = R.status; B.ticks = R.ticks; B.travel = R.travel; B.cost_integral = R.cost_integral; B.min_goal_dist = R.min_goal_dist;
   B.goal_pos = goal_pos ? R.goal_pos.get() : nullptr; B.goal_dir = goal_pos ? R.goal_dir.get() : nullptr;
   B.trace = rows ? R.trace.get() : nullptr; B.trace_rows = rows;
-  const uint32_t* d_start = start_tick ? S.start_tick.get() : nullptr;
+  const uint32_t* d_start = start_tick || yielding ? S.start_tick.get() : nullptr;
   Sep Q{};
+  Yld YQ{};
   if (separation) {
     HIPCHK(hipMemsetAsync(S.near_checks, 0, 4 * (size_t)n, ctx->stream));                          // sep_row_start
     HIPCHK(hipMemsetAsync(S.max_partners, 0, 4 * (size_t)n, ctx->stream));
@@ -171,6 +222,21 @@ static int rollout_run(mnav_ctx* ctx, const char* tag, mnav_rol::Stats& stats, m
     Q.keys = S.keys; Q.cnt = S.cell_cnt; Q.start = S.cell_start; Q.tile = S.tile; Q.slot_of = S.slot_of; Q.rank = S.rank; Q.rec = S.rec; Q.chk = S.chk;
     Q.rows = Rows{ S.near_checks, S.max_partners, S.first_near_tick, S.first_near_robot, S.min_sep2, S.min_sep_tick, S.min_sep_robot };
   }
+  if (yielding) {
+    if (yld.hold_in) {                                                // any non-zero byte is 1
+      h_hold.assign(yld.hold_in, yld.hold_in + n);
+      for (auto& b : h_hold) b = b != 0;
+      HIPCHK(hipMemcpyAsync(Y.hold, h_hold.data(), n, hipMemcpyHostToDevice, ctx->stream));
+    } else HIPCHK(hipMemsetAsync(Y.hold, 0, n, ctx->stream));
+    if (yld.priority) HIPCHK(hipMemcpyAsync(Y.priority, yld.priority, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemsetAsync(Y.hold_checks, 0, 4 * (size_t)n, ctx->stream));                           // yld_row_start
+    HIPCHK(hipMemsetAsync(Y.held_ticks, 0, 4 * (size_t)n, ctx->stream));
+    HIPCHK(hipMemsetAsync(Y.first_hold_tick, 0xFF, 4 * (size_t)n, ctx->stream));
+    HIPCHK(hipMemsetAsync(Y.first_hold_robot, 0xFF, 4 * (size_t)n, ctx->stream));
+    HIPCHK(hipMemsetAsync(Y.ychk, 0, sizeof(uint32_t) * kYldCheckWords * (size_t)checks, ctx->stream));
+    YQ.c2 = ahead_c2; YQ.dir = G.dir; YQ.priority = yld.priority ? Y.priority.get() : nullptr; YQ.hold = Y.hold; YQ.ychk = Y.ychk;
+    YQ.rows = YRows{ Y.hold_checks, Y.held_ticks, Y.first_hold_tick, Y.first_hold_robot };
+  }
   mnav_fol::Config C;
   std::memcpy(&C, config, sizeof(C));
   const Params P{ rollout->dt, (float)rollout->dist_tolerance, (float)rollout->angle_tolerance, goal_pos != nullptr };
@@ -179,14 +245,18 @@ static int rollout_run(mnav_ctx* ctx, const char* tag, mnav_rol::Stats& stats, m
   const uint32_t g_stay = (n + kStayBlock - 1) / kStayBlock, g_search = n < 2048u ? n : 2048u;
   const uint32_t g_all = (n + mnav_loc::kLocBlock - 1) / mnav_loc::kLocBlock, g_global = g_all < 1024u ? g_all : 1024u;
   const uint32_t g_sep = (n + kSepBlock - 1) / kSepBlock, g_clear = Q.tiles < 4096u ? Q.tiles : 4096u;
-  float ms_kernels = 0.f, ms_separation = 0.f;
+  float ms_kernels = 0.f, ms_separation = 0.f, ms_pair = 0.f;
   // one block: plain launches, no host look in between; then one synchronise
   const auto run_block = [&](uint32_t first, uint32_t nt) -> int {
     HIPCHK(hipEventRecord(G.ev[0], ctx->stream));
     uint32_t in_block = 0;
     for (uint32_t t = first; t < first + nt; ++t) {
       const uint32_t row = stride && (t + 1) % stride == 0 ? (t + 1) / stride - 1 : kNone;
-      if (d_start) {
+      if (yielding) {                                                 // a held robot has no tick
+        hipLaunchKernelGGL(k_yield_rollout_stay, dim3(g_stay), dim3(kStayBlock), 0, ctx->stream, B, M, C, P, t, row, d_start, YQ.hold, YQ.rows.held_ticks);
+        hipLaunchKernelGGL(k_yield_rollout_search, dim3(g_search), dim3(64), 0, ctx->stream, B, M, C, P, t, row, d_start, YQ.hold, YQ.rows.held_ticks);
+        hipLaunchKernelGGL(k_yield_rollout_global, dim3(g_global), dim3(mnav_loc::kLocBlock), 0, ctx->stream, B, M, C, P, I, t, row, d_start, YQ.hold, YQ.rows.held_ticks);
+      } else if (d_start) {
         hipLaunchKernelGGL(k_fleet_rollout_stay, dim3(g_stay), dim3(kStayBlock), 0, ctx->stream, B, M, C, P, t, row, d_start);
         hipLaunchKernelGGL(k_fleet_rollout_search, dim3(g_search), dim3(64), 0, ctx->stream, B, M, C, P, t, row, d_start);
         hipLaunchKernelGGL(k_fleet_rollout_global, dim3(g_global), dim3(mnav_loc::kLocBlock), 0, ctx->stream, B, M, C, P, I, t, row, d_start);
@@ -204,7 +274,11 @@ static int rollout_run(mnav_ctx* ctx, const char* tag, mnav_rol::Stats& stats, m
       hipLaunchKernelGGL(k_sep_top, dim3(1), dim3(kSepBlock), 0, ctx->stream, Q);
       hipLaunchKernelGGL(k_sep_starts, dim3(Q.tiles), dim3(kSepBlock), 0, ctx->stream, Q);
       hipLaunchKernelGGL(k_sep_fill, dim3(g_sep), dim3(kSepBlock), 0, ctx->stream, Q, check);
-      hipLaunchKernelGGL(k_sep_pair, dim3(g_sep), dim3(kSepBlock), 0, ctx->stream, Q, check, t + 1);
+      if (yielding) {
+        HIPCHK(hipEventRecord(Y.ev[2 * in_block], ctx->stream));
+        hipLaunchKernelGGL(k_yld_pair, dim3(g_sep), dim3(kSepBlock), 0, ctx->stream, Q, YQ, check, t + 1);
+        HIPCHK(hipEventRecord(Y.ev[2 * in_block + 1], ctx->stream));
+      } else hipLaunchKernelGGL(k_sep_pair, dim3(g_sep), dim3(kSepBlock), 0, ctx->stream, Q, check, t + 1);
       HIPCHK(hipEventRecord(S.ev[2 * in_block + 1], ctx->stream));
       ++in_block;
     }
@@ -213,6 +287,7 @@ static int rollout_run(mnav_ctx* ctx, const char* tag, mnav_rol::Stats& stats, m
     HIPCHK(hipStreamSynchronize(ctx->stream));
     ms_kernels += ev_ms(G.ev[0], G.ev[1]);
     for (uint32_t k = 0; k < in_block; ++k) ms_separation += ev_ms(S.ev[2 * k], S.ev[2 * k + 1]);
+    if (yielding) for (uint32_t k = 0; k < in_block; ++k) ms_pair += ev_ms(Y.ev[2 * k], Y.ev[2 * k + 1]);
     return 0;
   };
   uint32_t done = 0;
@@ -222,6 +297,7 @@ static int rollout_run(mnav_ctx* ctx, const char* tag, mnav_rol::Stats& stats, m
   std::vector<uint32_t> cnt((size_t)kCounters * done);
   std::vector<uint64_t> chk((size_t)kCheckWords * checks_done);
   std::vector<uint32_t> h_near, h_robot; std::vector<float> h_min;
+  std::vector<uint32_t> ychk((size_t)kYldCheckWords * (yielding ? checks_done : 0)), h_hold_checks, h_held_ticks;
   HIPCHK(hipMemcpyAsync(cnt.data(), R.cnt, sizeof(uint32_t) * cnt.size(), hipMemcpyDeviceToHost, ctx->stream));
   if (status_out) HIPCHK(hipMemcpyAsync(status_out, R.status, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
   if (ticks_out) HIPCHK(hipMemcpyAsync(ticks_out, R.ticks, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
@@ -243,6 +319,15 @@ static int rollout_run(mnav_ctx* ctx, const char* tag, mnav_rol::Stats& stats, m
     if (sep_out.first_near_robot) HIPCHK(hipMemcpyAsync(sep_out.first_near_robot, S.first_near_robot, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     if (sep_out.min_sep_tick) HIPCHK(hipMemcpyAsync(sep_out.min_sep_tick, S.min_sep_tick, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
   }
+  if (yielding) {
+    h_hold_checks.resize(n); h_held_ticks.resize(n); h_hold.resize(n); // the statistics read two of the yield rows' columns and the flags
+    if (checks_done) HIPCHK(hipMemcpyAsync(ychk.data(), Y.ychk, sizeof(uint32_t) * ychk.size(), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(h_hold_checks.data(), Y.hold_checks, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(h_held_ticks.data(), Y.held_ticks, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(h_hold.data(), Y.hold, n, hipMemcpyDeviceToHost, ctx->stream));
+    if (yld.out.first_hold_tick) HIPCHK(hipMemcpyAsync(yld.out.first_hold_tick, Y.first_hold_tick, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    if (yld.out.first_hold_robot) HIPCHK(hipMemcpyAsync(yld.out.first_hold_robot, Y.first_hold_robot, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  }
   HIPCHK(hipStreamSynchronize(ctx->stream));
   mnav_rol::rol_fold_counters(cnt.data(), done, n, stats);
   if (separation) {
@@ -251,8 +336,15 @@ static int rollout_run(mnav_ctx* ctx, const char* tag, mnav_rol::Stats& stats, m
     if (sep_out.min_sep2) std::memcpy(sep_out.min_sep2, h_min.data(), 4 * (size_t)n);
     if (sep_out.min_sep_robot) std::memcpy(sep_out.min_sep_robot, h_robot.data(), 4 * (size_t)n);
   }
+  if (yielding) {
+    if (yld.stats) yld_fold(chk.data(), ychk.data(), checks_done, check_stride, n, h_hold_checks.data(), h_held_ticks.data(), h_hold.data(), *yld.stats);
+    if (yld.out.hold_checks) std::memcpy(yld.out.hold_checks, h_hold_checks.data(), 4 * (size_t)n);
+    if (yld.out.held_ticks) std::memcpy(yld.out.held_ticks, h_held_ticks.data(), 4 * (size_t)n);
+    if (yld.hold_out) std::memcpy(yld.hold_out, h_hold.data(), n);
+  }
   stats.ms_kernels = ms_kernels; sep_stats.ms_separation = ms_separation;
   stats.ms_total = (float)(1e-3 * (double)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count());
+  if (yld.stats) { yld.stats->ms_pair = ms_pair; yld.stats->ms_separation = ms_separation; yld.stats->ms_kernels = ms_kernels; yld.stats->ms_total = stats.ms_total; }
   return rc ? rc : sep_stats.checks_skipped ? 2 : 0;
 }
 
@@ -264,7 +356,7 @@ int mnav_follow_rollout(mnav_ctx* ctx, uint32_t n, const float* pos, const float
   if (!ctx) return -1;
   mnav_frol::SepStats no_checks;                                      // nothing reads it: mnav_rollout_stats tells of no check
   return rollout_run(ctx, "rollout", ctx->rol_stats, no_checks, n, pos, dir, up, face_in, slots, seed_faces, goal_pos, goal_dir, config, rollout, nullptr, nullptr,
-                     status_out, ticks_out, pos_out, dir_out, face_out, travel_out, cost_integral_out, min_goal_dist_out, trace_out, mnav_frol::Rows{});
+                     status_out, ticks_out, pos_out, dir_out, face_out, travel_out, cost_integral_out, min_goal_dist_out, trace_out, mnav_frol::Rows{}, YieldCall{});
 }
 
 int mnav_fleet_rollout(mnav_ctx* ctx, uint32_t n, const float* pos, const float* dir, const float* up, const uint32_t* face_in, const uint32_t* slots,
@@ -277,7 +369,26 @@ int mnav_fleet_rollout(mnav_ctx* ctx, uint32_t n, const float* pos, const float*
   if (!ctx) return -1;
   return rollout_run(ctx, "fleet rollout", ctx->frol_stats, ctx->frol_sep_stats, n, pos, dir, up, face_in, slots, seed_faces, goal_pos, goal_dir, config, rollout,
                      start_tick, separation, status_out, ticks_out, pos_out, dir_out, face_out, travel_out, cost_integral_out, min_goal_dist_out, trace_out,
-                     mnav_frol::Rows{ near_checks_out, max_partners_out, first_near_tick_out, first_near_robot_out, min_sep2_out, min_sep_tick_out, min_sep_robot_out });
+                     mnav_frol::Rows{ near_checks_out, max_partners_out, first_near_tick_out, first_near_robot_out, min_sep2_out, min_sep_tick_out, min_sep_robot_out },
+                     YieldCall{});
+}
+
+int mnav_fleet_rollout_yield(mnav_ctx* ctx, uint32_t n, const float* pos, const float* dir, const float* up, const uint32_t* face_in, const uint32_t* slots,
+                             const uint32_t* seed_faces, const float* goal_pos, const float* goal_dir, const mnav_follow_config* config,
+                             const mnav_rollout_config* rollout, const uint32_t* start_tick, const mnav_separation_config* separation, int32_t* status_out,
+                             uint32_t* ticks_out, float* pos_out, float* dir_out, uint32_t* face_out, double* travel_out, double* cost_integral_out,
+                             float* min_goal_dist_out, float* trace_out, uint32_t* near_checks_out, uint32_t* max_partners_out, uint32_t* first_near_tick_out,
+                             uint32_t* first_near_robot_out, float* min_sep2_out, uint32_t* min_sep_tick_out, uint32_t* min_sep_robot_out,
+                             const mnav_yield_config* yield, const uint32_t* priority, const uint8_t* hold_in, uint8_t* hold_out, uint32_t* hold_checks_out,
+                             uint32_t* held_ticks_out, uint32_t* first_hold_tick_out, uint32_t* first_hold_robot_out)
+{
+  if (!ctx) return -1;
+  YieldCall Y;
+  Y.config = yield; Y.priority = priority; Y.hold_in = hold_in; Y.hold_out = hold_out;
+  Y.out = mnav_frol::YRows{ hold_checks_out, held_ticks_out, first_hold_tick_out, first_hold_robot_out }; Y.stats = &ctx->yld_stats;
+  return rollout_run(ctx, "fleet rollout yield", ctx->yld_rol_stats, ctx->yld_sep_stats, n, pos, dir, up, face_in, slots, seed_faces, goal_pos, goal_dir, config, rollout,
+                     start_tick, separation, status_out, ticks_out, pos_out, dir_out, face_out, travel_out, cost_integral_out, min_goal_dist_out, trace_out,
+                     mnav_frol::Rows{ near_checks_out, max_partners_out, first_near_tick_out, first_near_robot_out, min_sep2_out, min_sep_tick_out, min_sep_robot_out }, Y);
 }
 
 // the first eight values of both *_stats functions
@@ -322,5 +433,25 @@ int mnav_fleet_rollout_stats(const mnav_ctx* ctx, uint32_t* status_counts, uint6
   if (tests) *tests = S.tests;
   if (max_cell) *max_cell = S.max_cell;
   if (ms_separation) *ms_separation = S.ms_separation;
+  return 0;
+}
+
+int mnav_fleet_yield_stats(const mnav_ctx* ctx, uint32_t* robots_held, uint64_t* held_ticks, uint32_t* max_held, uint32_t* max_held_tick, uint32_t* held_last,
+                           uint32_t* checks_run, uint32_t* checks_skipped, uint32_t* first_skipped_tick, float* ms_pair, float* ms_separation, float* ms_kernels, float* ms_total)
+{
+  if (!ctx) return -1;
+  const mnav_frol::YldStats& S = ctx->yld_stats;
+  if (robots_held) *robots_held = S.robots_held;
+  if (held_ticks) *held_ticks = S.held_ticks;
+  if (max_held) *max_held = S.max_held;
+  if (max_held_tick) *max_held_tick = S.max_held_tick;
+  if (held_last) *held_last = S.held_last;
+  if (checks_run) *checks_run = S.checks_run;
+  if (checks_skipped) *checks_skipped = S.checks_skipped;
+  if (first_skipped_tick) *first_skipped_tick = S.first_skipped_tick;
+  if (ms_pair) *ms_pair = S.ms_pair;
+  if (ms_separation) *ms_separation = S.ms_separation;
+  if (ms_kernels) *ms_kernels = S.ms_kernels;
+  if (ms_total) *ms_total = S.ms_total;
   return 0;
 }

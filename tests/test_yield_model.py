@@ -1,0 +1,514 @@
+"""The yielding fleet rollout without a GPU: mesh_navigation_amd/csrc/mnav_fleet_yield.h compiled for the host (g++
+-ffp-contract=off, the flags of the library) -- the rule (yld_mover, yld_ahead, yld_before, yld_yields, the fold of the
+blockers) is the device's own source, yld_check_host composes it serially over the check's grid -- against
+tests/yield_model.py, the O(n^2) numpy restatement of include/mnav.h.  Point sets that pin every clause of the rule, each at
+separation_cell_scale 1, 2 and 4; a convoy on a mesh through the whole call's host mirror; the equivalences of the header; and
+the fold of a call's check rows into its statistics (yld_fold).  Every comparison is exact."""
+import ctypes as C
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+from tests import follow_model as FM
+from tests import rollout_model as RM
+from tests import separation_model as SM
+from tests import yield_model as YM
+from tests.test_follow_model import build_world
+from tests.test_locate_model import CSRC
+from tests.test_rollout_model import ANG_TOL, DIST_TOL, DT, Mirror
+from tests.test_separation_model import SCALES, SHIM as SEPARATION_SHIM
+
+F32 = np.float32
+NONE = SM.NONE
+
+SHIM = SEPARATION_SHIM + r'''
+#include "mnav_fleet_yield.h"
+
+// A(i, j) with c2 given as it is (no float c has c * c == 0.5)
+extern "C" int yld_ahead_of(const float* pi, const float* di, const float* pj, float c2)
+{
+  const mnav::W3 a = mnav::w3_load(pi), b = mnav::w3_load(pj);
+  return mnav_frol::yld_ahead(a, mnav::w3_load(di), b, mnav_frol::sep_d2(a, b), c2) ? 1 : 0;
+}
+extern "C" int yld_cos_ok(double c) { return mnav_frol::yld_cos_ok((float)c) ? 1 : 0; }
+// one check with the rule over n robots; rows: the seven separation arrays; yrows: hold_checks, held_ticks, first_hold_tick,
+// first_hold_robot; hold: n bytes; chk: kCheckWords; ychk: kYldCheckWords.  Returns 1 when the pair pass ran
+extern "C" int yld_check(uint32_t n, const float* pos, const float* dir, const int32_t* status, const uint32_t* start_tick, const uint32_t* priority, uint32_t tick,
+                         uint32_t flags, float r, float scale, float c, uint32_t table_size, uint64_t max_tests, uint32_t* near_checks, uint32_t* max_partners,
+                         uint32_t* first_near_tick, uint32_t* first_near_robot, float* min_sep2, uint32_t* min_sep_tick, uint32_t* min_sep_robot,
+                         uint32_t* hold_checks, uint32_t* held_ticks, uint32_t* first_hold_tick, uint32_t* first_hold_robot, uint8_t* hold, uint64_t* chk, uint32_t* ychk)
+{
+  const mnav_frol::Rows A{ near_checks, max_partners, first_near_tick, first_near_robot, min_sep2, min_sep_tick, min_sep_robot };
+  const mnav_frol::YRows Y{ hold_checks, held_ticks, first_hold_tick, first_hold_robot };
+  return mnav_frol::yld_check_host(n, pos, dir, status, start_tick, priority, tick, flags, mnav_frol::sep_grid(r, scale), c * c, table_size, max_tests, A, Y, hold, chk,
+                                   ychk) ? 1 : 0;
+}
+// The yielding fleet rollout serially: per call tick every robot that neither waits nor is held has one tick of rol_run, a
+// held one that is RUNNING counts a held tick, then the trace row, then the check.  Arguments as frol_batch up to chk, then
+// the rule: c = (float)ahead_cos, priority (null: all 0), hold (n bytes, in and out), the four yield rows and ychk
+extern "C" void yrol_batch(void* h, uint32_t n, const uint32_t* slot, const uint32_t* seed_face, const float* goal_pos, const float* goal_dir, const float* fields,
+                           const float* costs, const double* cfg, const double* par, uint32_t ticks, uint32_t stride, uint32_t V, uint32_t F, const float* xyz,
+                           const uint32_t* faces, const uint32_t* vf_ptr, const uint32_t* vf, int32_t* status, uint32_t* tk, float* pos, float* dir,
+                           const float* up, uint32_t* face, double* travel, double* cost_integral, float* min_goal_dist, float* trace, uint64_t* how,
+                           const uint32_t* start_tick, float r, float scale, uint32_t check_stride, uint32_t flags, uint64_t max_tests, uint32_t* near_checks,
+                           uint32_t* max_partners, uint32_t* first_near_tick, uint32_t* first_near_robot, float* min_sep2, uint32_t* min_sep_tick,
+                           uint32_t* min_sep_robot, uint64_t* chk, float c, const uint32_t* priority, uint8_t* hold, uint32_t* hold_checks, uint32_t* held_ticks,
+                           uint32_t* first_hold_tick, uint32_t* first_hold_robot, uint32_t* ychk)
+{
+  Host* H = (Host*)h;
+  const Index I{ H->nodes.data(), H->pts.data(), H->n_pts, H->n_leaves, loc_root(H->n_leaves) };
+  const mnav::WalkMesh Mh{ xyz, faces, vf_ptr, vf, V, F };
+  mnav_fol::Config Cf;
+  std::memcpy(&Cf, cfg, sizeof(Cf));
+  const mnav_rol::Params P = params(par, goal_pos != nullptr);
+  const ::Rows A{ status, tk, pos, dir, up, face, travel, cost_integral, min_goal_dist };
+  const mnav_frol::Rows S{ near_checks, max_partners, first_near_tick, first_near_robot, min_sep2, min_sep_tick, min_sep_robot };
+  const mnav_frol::YRows Y{ hold_checks, held_ticks, first_hold_tick, first_hold_robot };
+  VecStack st; st.cap = kStack;
+  std::vector<uint32_t> list(mnav::kWalkScratchWords);
+  const uint32_t rows = stride ? ticks / stride : 0;
+  const mnav::W3 zero = mnav::w3(0, 0, 0);
+  for (uint32_t t = 1; t <= ticks; ++t) {
+    for (uint32_t i = 0; i < n; ++i) {
+      const bool waits = start_tick && mnav_frol::frol_waits(t, start_tick[i]);
+      if (!waits && !hold[i]) {
+        const mnav::WalkField Fd = mnav_fol::fol_field(Mh, fields + 3 * (size_t)V * slot[i], seed_face ? seed_face[i] : mnav::kNone);
+        State R = load(A, i);
+        mnav_rol::rol_run(Mh, I, st, Fd, costs, Cf, P, goal_pos ? mnav::w3_load(goal_pos + 3 * (size_t)i) : zero, goal_dir ? mnav::w3_load(goal_dir + 3 * (size_t)i) : zero,
+                          R, 1, 0, nullptr, list.data(), how);
+        store(A, i, R);
+      } else if (mnav_frol::yld_mover(status[i], waits)) held_ticks[i] += 1;
+      if (stride && t % stride == 0) std::memcpy(trace + 3 * ((size_t)rows * i + t / stride - 1), pos + 3 * (size_t)i, 12);
+    }
+    if (t % check_stride == 0) {
+      const uint32_t k = t / check_stride - 1;
+      mnav_frol::yld_check_host(n, pos, dir, status, start_tick, priority, t, flags, mnav_frol::sep_grid(r, scale), c * c, mnav_frol::sep_table_size(n), max_tests, S, Y,
+                                hold, chk + (size_t)mnav_frol::kCheckWords * k, ychk + (size_t)mnav_frol::kYldCheckWords * k);
+    }
+  }
+}
+// yld_fold over the rows of `checks` checks, two of the robots' columns and the flags; out: robots_held, held_ticks, max_held,
+// max_held_tick, held_last, (5) what the fold must leave alone: the four times, then checks_run, checks_skipped, first_skipped_tick
+extern "C" void yld_fold_stats(const uint64_t* chk, const uint32_t* ychk, uint32_t checks, uint32_t check_stride, uint32_t n, const uint32_t* hold_checks,
+                               const uint32_t* held_ticks, const uint8_t* hold, uint64_t* out)
+{
+  mnav_frol::YldStats S;
+  mnav_frol::yld_fold(chk, ychk, checks, check_stride, n, hold_checks, held_ticks, hold, S);
+  out[0] = S.robots_held; out[1] = S.held_ticks; out[2] = S.max_held; out[3] = S.max_held_tick; out[4] = S.held_last;
+  out[6] = S.checks_run; out[7] = S.checks_skipped; out[8] = S.first_skipped_tick;
+  out[5] = (S.ms_pair != 0.f) + (S.ms_separation != 0.f) + (S.ms_kernels != 0.f) + (S.ms_total != 0.f);
+}
+'''
+
+
+def build_shim(tmp_path_factory):
+    gxx = shutil.which("g++")
+    assert gxx, "g++ is needed to build the host shim of mnav_fleet_yield.h"
+    d = tmp_path_factory.mktemp("yield_shim")
+    src = d / "shim.cpp"
+    src.write_text(SHIM)
+    lib = d / "libshim.so"
+    subprocess.check_call([gxx, "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I", CSRC, "-o", str(lib), str(src)])
+    L = C.CDLL(str(lib))
+    vp, u32, f32 = C.c_void_p, C.c_uint32, C.c_float
+    L.loc_build.restype = vp
+    L.loc_build.argtypes = [u32, vp]
+    L.loc_free.argtypes = [vp]
+    L.sep_table_size.restype = u32
+    L.sep_table_size.argtypes = [u32]
+    L.yld_ahead_of.restype = C.c_int
+    L.yld_ahead_of.argtypes = [vp, vp, vp, f32]
+    L.yld_cos_ok.restype = C.c_int
+    L.yld_cos_ok.argtypes = [C.c_double]
+    L.yld_check.restype = C.c_int
+    L.yld_check.argtypes = [u32] + [vp] * 5 + [u32, u32, f32, f32, f32, u32, C.c_uint64] + [vp] * 14
+    L.yrol_batch.argtypes = [vp, u32] + [vp] * 8 + [u32] * 4 + [vp] * 15 + [vp, f32, f32, u32, u32, C.c_uint64] + [vp] * 8 + [f32] + [vp] * 7
+    L.yld_fold_stats.argtypes = [vp, vp, u32, u32, u32] + [vp] * 4
+    return L
+
+
+@pytest.fixture(scope="module")
+def shim(tmp_path_factory):
+    return build_shim(tmp_path_factory)
+
+
+def _p(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+X, Y_, Z = np.array([1, 0, 0], F32), np.array([0, 1, 0], F32), np.array([0, 0, 1], F32)
+
+
+def host_check(L, pos, direction, radius, ahead_cos, scale, status=None, start_tick=None, priority=None, tick=1, flags=0, rows=None, yrows=None, max_tests=2 ** 63):
+    """yld_check_host on one point set: the separation rows, the yield rows, the flags, the two check rows, whether it ran"""
+    pos, direction = np.ascontiguousarray(pos, F32).reshape(-1, 3), np.ascontiguousarray(direction, F32).reshape(-1, 3)
+    n = pos.shape[0]
+    rows = SM.start_rows(n) if rows is None else rows
+    yrows = YM.start_yrows(n) if yrows is None else yrows
+    status = np.zeros(n, np.int32) if status is None else np.ascontiguousarray(status, np.int32)
+    st = None if start_tick is None else np.ascontiguousarray(start_tick, np.uint32)
+    pr = None if priority is None else np.ascontiguousarray(priority, np.uint32)
+    hold, chk, ychk = np.full(n, 9, np.uint8), np.zeros(4, np.uint64), np.full(1, 99, np.uint32)
+    ran = L.yld_check(n, _p(pos), _p(direction), _p(status), _p(st), _p(pr), tick, flags, radius, scale, ahead_cos, L.sep_table_size(n), max_tests,
+                      *[_p(rows[k]) for k in SM.SEP_KEYS], *[_p(yrows[k]) for k in ("hold_checks", "held_ticks", "first_hold_tick", "first_hold_robot")],
+                      _p(hold), _p(chk), _p(ychk))
+    return rows, yrows, hold, chk, int(ychk[0]), bool(ran)
+
+
+def both(L, pos, direction, radius, ahead_cos, status=None, start_tick=None, priority=None, tick=1, flags=0, what=""):
+    """one check by the model and, at every scale, by the header: equal; returns the model's flags and yield rows"""
+    pos, direction = np.ascontiguousarray(pos, F32).reshape(-1, 3), np.ascontiguousarray(direction, F32).reshape(-1, 3)
+    n = pos.shape[0]
+    status = np.zeros(n, np.int32) if status is None else np.asarray(status, np.int32)
+    waiting = np.zeros(n, bool) if start_tick is None else tick <= np.asarray(start_tick, np.int64)
+    rows, yrows = SM.start_rows(n), YM.start_yrows(n)
+    hold, near, yields = YM.check(rows, yrows, pos, direction, status, waiting, flags, radius, ahead_cos, priority, tick)
+    for scale in SCALES:
+        g_rows, g_yrows, g_hold, chk, held, ran = host_check(L, pos, direction, radius, ahead_cos, scale, status, start_tick, priority, tick, flags)
+        assert ran and np.array_equal(g_hold, hold), (what, scale, g_hold, hold)
+        SM.assert_same_rows(g_rows, rows, (what, scale))
+        YM.assert_same_yield(dict(g_yrows, hold=g_hold), dict(yrows, hold=hold), (what, scale))
+        assert held == int(hold.sum()) and int(chk[1]) == int(near.sum()), (what, scale)
+    return hold.tolist(), yrows
+
+
+def test_a_follower_yields_to_the_leader_whatever_the_priorities(shim):
+    pos, d = [[0, 0, 0], [0.2, 0, 0]], [X, X]
+    for prio in (None, [0, 1], [1, 0], [5, 5]):
+        hold, y = both(shim, pos, d, 0.3, 0.5, priority=prio, tick=4, what=("follower", prio))
+        assert hold == [1, 0] and y["first_hold_robot"].tolist() == [1, NONE] and y["first_hold_tick"].tolist() == [4, NONE] and y["hold_checks"].tolist() == [1, 0]
+    # beyond the radius nobody is a partner: nobody yields
+    assert both(shim, [[0, 0, 0], [0.31, 0, 0]], d, 0.3, 0.5)[0] == [0, 0]
+
+
+def test_head_on_the_priority_decides_then_the_index(shim):
+    pos, d = [[0, 0, 0], [0.2, 0, 0]], [X, -X]
+    assert both(shim, pos, d, 0.3, 0.5, priority=[0, 1], what="0 first")[0] == [0, 1]
+    assert both(shim, pos, d, 0.3, 0.5, priority=[1, 0], what="1 first")[0] == [1, 0]          # swapping the priorities swaps the outcome
+    assert both(shim, pos, d, 0.3, 0.5, priority=[7, 7], what="equal")[0] == [0, 1]            # equal: the smaller index has right of way
+    assert both(shim, pos, d, 0.3, 0.5, priority=None, what="none")[0] == [0, 1]
+    assert both(shim, pos, d, 0.3, 0.5, priority=[0xFFFFFFFF, 0], what="largest value")[0] == [1, 0]
+
+
+def test_side_by_side_and_coincident_robots_do_not_yield(shim):
+    assert both(shim, [[0, 0, 0], [0, 0.2, 0]], [X, X], 0.3, 0.5, what="side by side")[0] == [0, 0]
+    assert both(shim, [[0, 0, 0], [0, 0, 0.2]], [X, X], 0.3, 0.0, what="side by side, c = 0")[0] == [0, 0]      # dot == 0 is not ahead
+    assert both(shim, [[1, 2, 3], [1, 2, 3], [1, 2, 3]], [X, -X, Y_], 0.3, 0.0, what="coincident")[0] == [0, 0, 0]
+
+
+def test_a_stationary_partner_ahead_and_one_behind(shim):
+    for status in (RM.OUT_OF_MAP, RM.NO_FIELD):
+        assert both(shim, [[0, 0, 0], [0.2, 0, 0]], [X, -X], 0.3, 0.5, status=[RM.RUNNING, status], priority=[0, 9], what="ahead")[0] == [1, 0]
+        assert both(shim, [[0, 0, 0], [-0.2, 0, 0]], [X, X], 0.3, 0.5, status=[RM.RUNNING, status], what="behind")[0] == [0, 0]
+
+
+def test_the_presence_flags_decide_who_is_an_obstacle(shim):
+    pos, d = [[0, 0, 0], [0.2, 0, 0]], [X, X]
+    # robot 1 waits at tick 5 (start tick 7); it has departed at tick 8, a mover that does not face robot 0
+    for flags, want in ((0, [0, 0]), (SM.WAITING_PRESENT, [1, 0]), (SM.REACHED_PRESENT, [0, 0]), (3, [1, 0])):
+        assert both(shim, pos, d, 0.3, 0.5, start_tick=[0, 7], tick=5, flags=flags, what=("waiting", flags))[0] == want
+        assert both(shim, pos, d, 0.3, 0.5, start_tick=[0, 7], tick=8, flags=flags, what=("departed", flags))[0] == [1, 0]
+    for flags, want in ((0, [0, 0]), (SM.WAITING_PRESENT, [0, 0]), (SM.REACHED_PRESENT, [1, 0]), (3, [1, 0])):
+        assert both(shim, pos, d, 0.3, 0.5, status=[RM.RUNNING, RM.REACHED], flags=flags, what=("reached", flags))[0] == want
+    # a waiting robot is no mover: it is never held, even behind a present robot
+    assert both(shim, pos, d, 0.3, 0.5, start_tick=[7, 0], tick=5, flags=3, what="the waiting one behind")[0] == [0, 0]
+
+
+def test_the_boundary_of_the_cone(shim):
+    o = np.zeros(3, F32)
+    e = np.array([1, 1, 0], F32)
+    assert shim.yld_ahead_of(_p(o), _p(X), _p(e), 0.5) == 1           # c2 = 0.5: dot * dot == 1 == c2 * d2 counts as ahead
+    e_up = np.array([1, np.nextafter(F32(1), F32(2)), 0], F32)
+    assert shim.yld_ahead_of(_p(o), _p(X), _p(e_up), 0.5) == 0        # d2 = 2 + 2^-22, c2 * d2 > 1
+    assert shim.yld_ahead_of(_p(o), _p(-X), _p(e), 0.5) == 0 and shim.yld_ahead_of(_p(o), _p(X), _p(o), 0.0) == 0      # behind; coincident
+    # through a whole check c2 comes from a float c; no float squares to 0.5 (0.70710677^2 rounds to 0.49999997), so the cone
+    # of that c holds e and, the model agrees, still holds e one float up
+    c = float(np.sqrt(0.5))
+    assert F32(c) * F32(c) < F32(0.5)
+    assert both(shim, [o, e], [X, X], 2.0, c, status=[RM.RUNNING, RM.NO_FIELD], what="inside the cone")[0] == [1, 0]
+    both(shim, [o, e_up], [X, X], 2.0, c, status=[RM.RUNNING, RM.NO_FIELD], what="one float up")
+    assert both(shim, [o, [1, 1.001, 0]], [X, X], 2.0, c, status=[RM.RUNNING, RM.NO_FIELD], what="outside")[0] == [0, 0]
+    # the configuration's bounds
+    assert [shim.yld_cos_ok(v) for v in (0.0, 0.5, 0.99999, 1.0, -0.0, -1e-3, float("nan"), float("inf"), 1.0 - 1e-12)] == [1, 1, 1, 0, 1, 0, 0, 0, 0]
+
+
+def test_a_wide_cone_and_a_narrow_one(shim):
+    pos, d, status = [[0, 0, 0], [0.1, 0.15, 0]], [X, X], [RM.RUNNING, RM.OUT_OF_MAP]        # about 56 degrees off the heading
+    assert both(shim, pos, d, 0.3, 0.0, status=status, what="c = 0")[0] == [1, 0]
+    assert both(shim, pos, d, 0.3, 0.9, status=status, what="c = 0.9")[0] == [0, 0]
+
+
+def test_a_nan_heading_yields_to_nobody(shim):
+    nan = np.array([np.nan, 0, 0], F32)
+    assert both(shim, [[0, 0, 0], [0.2, 0, 0]], [nan, X], 0.3, 0.0, what="nan behind")[0] == [0, 0]
+    # ... and the robot that faces it sees it ahead and is not faced back: it yields whatever the priorities
+    assert both(shim, [[0, 0, 0], [0.2, 0, 0]], [nan, -X], 0.3, 0.0, priority=[9, 0], what="nan faced")[0] == [0, 1]
+    assert both(shim, [[0, 0, 0], [0.2, 0, 0]], [np.array([1, np.nan, 0], F32), X], 0.3, 0.0, what="nan in y")[0] == [0, 0]
+
+
+def test_a_chain_and_a_ring(shim):
+    hold, y = both(shim, [[0, 0, 0], [0.2, 0, 0], [0.4, 0, 0]], [X, X, X], 0.3, 0.5, what="chain")
+    assert hold == [1, 1, 0] and y["first_hold_robot"].tolist() == [1, 2, NONE]
+    hold, y = both(shim, [[0, 0, 0], [0.2, 0, 0], [0.4, 0, 0]], [X, X, X], 0.5, 0.5, what="chain, both ahead within the radius")
+    assert hold == [1, 1, 0] and y["first_hold_robot"].tolist() == [1, 2, NONE]                # the nearer blocker
+    # three followers on a triangle, each heading for the next: the one ahead sees its follower 60 degrees off its own
+    # heading, outside a cone of cos 0.9, so everybody yields -- the documented deadlock
+    tri = np.array([[0, 0, 0], [0.2, 0, 0], [0.1, 0.2 * np.sqrt(0.75), 0]], F32)
+    d = np.array([(tri[(i + 1) % 3] - tri[i]) / np.linalg.norm(tri[(i + 1) % 3] - tri[i]) for i in range(3)], F32)
+    for prio in (None, [2, 1, 0]):
+        hold, y = both(shim, tri, d, 0.3, 0.9, priority=prio, what=("ring", prio))
+        assert hold == [1, 1, 1] and y["first_hold_robot"].tolist() == [1, 2, 0]
+
+
+def test_blocker_ties_go_to_the_smaller_index(shim):
+    pos = [[0, 0, 0], [9, 9, 9], [0.2, -0.1, 0], [0.2, 0.1, 0], [0.25, 0, 0]]
+    status = [RM.RUNNING, RM.RUNNING, RM.NO_FIELD, RM.NO_FIELD, RM.NO_FIELD]
+    hold, y = both(shim, pos, [X] * 5, 0.3, 0.5, status=status, what="tie")
+    assert hold == [1, 0, 0, 0, 0] and y["first_hold_robot"][0] == 2
+    # the nearest partner is behind: the blocker is the nearest one yielded to, not the nearest partner
+    pos = [[0, 0, 0], [-0.05, 0, 0], [0.2, 0, 0]]
+    rows, yrows, hold, chk, held, ran = host_check(shim, pos, [X] * 3, 0.3, 0.5, 2.0, status=[RM.RUNNING, RM.NO_FIELD, RM.NO_FIELD])
+    assert rows["first_near_robot"][0] == 1 and yrows["first_hold_robot"][0] == 2 and held == 1
+    both(shim, pos, [X] * 3, 0.3, 0.5, status=[RM.RUNNING, RM.NO_FIELD, RM.NO_FIELD], what="nearest behind")
+
+
+def test_only_the_first_check_that_holds_gives_tick_and_blocker(shim):
+    apart = np.array([[0, 0, 0], [5, 0, 0], [9, 9, 9]], F32)         # nobody near
+    a = np.array([[0, 0, 0], [0.2, 0, 0], [9, 9, 9]], F32)           # robot 1 ahead of robot 0
+    b = np.array([[0, 0, 0], [5, 0, 0], [0.1, 0, 0]], F32)           # robot 2 ahead of robot 0, closer
+    for scale in SCALES:
+        rows, yrows = SM.start_rows(3), YM.start_yrows(3)
+        holds = []
+        for t, pts in ((3, apart), (6, a), (9, b), (12, apart)):
+            holds.append(host_check(shim, pts, [X] * 3, 0.3, 0.5, scale, tick=t, rows=rows, yrows=yrows)[2].tolist())
+        assert holds == [[0, 0, 0], [1, 0, 0], [1, 0, 0], [0, 0, 0]]                           # stateless: released as soon as nobody is ahead
+        assert (yrows["hold_checks"][0], yrows["first_hold_tick"][0], yrows["first_hold_robot"][0]) == (2, 6, 1)
+
+
+def test_257_random_robots_in_a_box_a_few_radii_wide(shim):
+    rng = np.random.default_rng(21)
+    n, r = 257, 0.25
+    for trial, (c, flags) in enumerate(((0.5, 3), (0.0, 0), (0.95, 1))):
+        pos = rng.uniform(-1.2, 1.2, (n, 3)).astype(F32) * np.array([1, 1, 0.3], F32)         # about four partners each
+        a = rng.uniform(0, 2 * np.pi, n)
+        d = np.stack([np.cos(a), np.sin(a), rng.uniform(-0.2, 0.2, n)], axis=1).astype(F32)
+        status = rng.choice([RM.RUNNING] * 5 + [RM.REACHED, RM.OUT_OF_MAP, RM.NO_FIELD], n).astype(np.int32)
+        start = rng.choice([0, 0, 0, 3, 50], n).astype(np.uint32)
+        prio = rng.integers(0, 4, n).astype(np.uint32)
+        pos[5], d[9] = pos[4], np.array([np.nan, 0, 0], F32)                                 # a coincident pair, a NaN heading
+        for k in range(20, 36, 2):                                    # eight head-on pairs beside the box: the larger index has right of way
+            pos[k], pos[k + 1], d[k], d[k + 1] = [5 + k, 0, 0], [5.1 + k, 0, 0], X, -X
+            status[k:k + 2], start[k:k + 2], prio[k:k + 2] = RM.RUNNING, 0, (3, 0)
+        holds = []
+        for priority in (prio, None):
+            hold, y = both(shim, pos, d, r, c, status=status, start_tick=start, priority=priority, tick=10, flags=flags, what=("random", trial))
+            assert 10 < sum(hold) < n - 10 and hold[9] == 0
+            holds.append(hold)
+        print(trial, "held:", sum(holds[0]), sum(holds[1]), "differ:", sum(x != y for x, y in zip(*holds)))
+        assert holds[0] != holds[1]                                   # the priorities matter to somebody
+
+
+def test_a_skipped_check_releases_everybody(shim):
+    pos, d = np.array([[0, 0, 0], [0.2, 0, 0]], F32), [X, X]
+    for scale in SCALES:
+        rows, yrows, hold, chk, held, ran = host_check(shim, pos, d, 0.3, 0.5, scale, max_tests=3)
+        assert not ran and hold.tolist() == [0, 0] and held == 0 and int(chk[3]) == 1 and int(chk[0]) == 4
+        YM.assert_same_yield(dict(yrows, hold=hold), dict(YM.start_yrows(2), hold=np.zeros(2, np.uint8)), "skipped")
+        SM.assert_same_rows(rows, SM.start_rows(2), "skipped")
+        assert host_check(shim, pos, d, 0.3, 0.5, scale, max_tests=4)[2].tolist() == [1, 0]    # T == the bound: served
+
+
+# -- a convoy on a mesh: the whole call ----------------------------------------------------------------------------------
+
+TICKS, RADIUS, AHEAD_COS = 260, 0.3, 0.5
+CONVOY, SPACING_TICKS = 6, 4           # six robots on one plan, each started where the one behind it stands four ticks later
+SLOW = FM.config(max_lin_velocity=0.2) # 0.05 m per tick: a robot that is held for a check interval falls visibly behind
+
+
+def convoy(model, fields, seed_faces, start_face, cfg, n=CONVOY, every=SPACING_TICKS, slot=2):
+    """n robots on plan `slot`, placed along the path one of them drives from `start_face` towards the goal, `every` ticks of
+    free driving apart (the spacing in metres is asserted by the caller): robot 0 leads.  Returns robots, goals, spacing"""
+    cen = model.xyz[model.faces].astype(np.float64).mean(axis=1)
+    mid = np.nanmean(cen, axis=0)
+    p0 = cen[start_face].astype(F32)
+    to_mid = (mid - p0) * np.array([1, 1, 0])
+    S = RM.start(p0, (to_mid / np.linalg.norm(to_mid)).astype(F32), Z, start_face)
+    has = FM.has_vector(model, fields[slot], int(seed_faces[slot]))
+    goal_pos = cen[int(np.nanargmin(np.linalg.norm(cen[:, :2] - mid[None, :2], axis=1)))].astype(F32)
+    goal = (goal_pos, X)
+    along = []
+    for t in range(every * n):
+        if t % every == 0:
+            along.append((np.array(S["pos"], F32), np.array(S["dir"], F32), S["face"]))
+        RM.one_tick(model, cfg, fields[slot], has, S, goal, DT, DIST_TOL, ANG_TOL)
+        assert S["status"] == RM.RUNNING
+    along = along[::-1]                                               # the farthest along leads
+    robots = dict(pos=np.array([a[0] for a in along], F32), dir=np.array([a[1] for a in along], F32), up=np.tile(Z, (n, 1)),
+                  face_in=np.array([a[2] for a in along], np.uint32), slot=np.full(n, slot, np.uint32), seed_face=np.full(n, seed_faces[slot], np.uint32))
+    gaps = np.linalg.norm(np.diff(robots["pos"].astype(np.float64), axis=0), axis=1)
+    return robots, (np.tile(goal_pos, (n, 1)), np.tile(X, (n, 1))), gaps
+
+
+class YieldMirror(Mirror):
+    def run_yield(self, cfg, fields, robots, goals, ticks, start_tick=None, radius=RADIUS, scale=2.0, check_stride=1, flags=0, ahead_cos=AHEAD_COS, priority=None,
+                  hold_in=None, max_tests=2 ** 63, state=None):
+        m = self.m
+        n = robots["pos"].shape[0]
+        S = dict(status=np.zeros(n, np.int32), ticks=np.zeros(n, np.uint32), pos=np.array(robots["pos"], F32), dir=np.array(robots["dir"], F32),
+                 face=np.array(robots["face_in"], np.uint32), travel=np.zeros(n), cost_integral=np.zeros(n), min_goal_dist=np.full(n, np.inf, F32))
+        fl = np.ascontiguousarray(np.stack(fields), F32)
+        c = np.array([cfg[k] for k in FM.CFG_NAMES], np.float64)
+        par = np.array([DT, DIST_TOL, ANG_TOL], np.float64)
+        upv, slot = np.ascontiguousarray(robots["up"], F32), np.ascontiguousarray(robots["slot"], np.uint32)
+        sf = None if robots.get("seed_face") is None else np.ascontiguousarray(robots["seed_face"], np.uint32)
+        gp, gd = (None, None) if goals is None else (np.ascontiguousarray(goals[0], F32), np.ascontiguousarray(goals[1], F32))
+        trace, how = np.zeros((n, ticks, 3), F32), np.zeros(5, np.uint64)
+        st = None if start_tick is None else np.ascontiguousarray(start_tick, np.uint32)
+        pr = None if priority is None else np.ascontiguousarray(priority, np.uint32)
+        rows, yrows = SM.start_rows(n), YM.start_yrows(n)
+        hold = np.zeros(n, np.uint8) if hold_in is None else (np.asarray(hold_in) != 0).astype(np.uint8)
+        checks = max(ticks // check_stride, 1)
+        chk, ychk = np.zeros((checks, 4), np.uint64), np.zeros(checks, np.uint32)
+        self.L.yrol_batch(self.h, n, _p(slot), _p(sf), _p(gp), _p(gd), _p(fl), _p(m.costs), _p(c), _p(par), ticks, 1, m.V, m.F, _p(m.xyz),
+                          _p(m.faces), _p(self.ptr), _p(self.vf), _p(S["status"]), _p(S["ticks"]), _p(S["pos"]), _p(S["dir"]), _p(upv), _p(S["face"]),
+                          _p(S["travel"]), _p(S["cost_integral"]), _p(S["min_goal_dist"]), _p(trace), _p(how), _p(st), radius, scale, check_stride, flags,
+                          max_tests, *[_p(rows[k]) for k in SM.SEP_KEYS], _p(chk), ahead_cos, _p(pr), _p(hold),
+                          *[_p(yrows[k]) for k in ("hold_checks", "held_ticks", "first_hold_tick", "first_hold_robot")], _p(ychk))
+        return dict(S, trace=trace, how=how.astype(np.int64), **rows, **yrows, hold=hold, chk=chk, ychk=ychk)
+
+
+def fold(L, chk, ychk, check_stride, hold_checks, held_ticks, hold):
+    chk, ychk = np.ascontiguousarray(chk, np.uint64).reshape(-1, 4), np.ascontiguousarray(ychk, np.uint32).reshape(-1)
+    hc, ht, h = np.ascontiguousarray(hold_checks, np.uint32), np.ascontiguousarray(held_ticks, np.uint32), np.ascontiguousarray(hold, np.uint8)
+    out = np.full(9, 99, np.uint64)
+    L.yld_fold_stats(_p(chk), _p(ychk), chk.shape[0], check_stride, hc.shape[0], _p(hc), _p(ht), _p(h), _p(out))
+    assert out[5] == 0                                                # the fold leaves the times alone
+    return dict(zip(("robots_held", "held_ticks", "max_held", "max_held_tick", "held_last", "checks_run", "checks_skipped", "first_skipped_tick"),
+                    (int(v) for v in np.delete(out, 5))))
+
+
+@pytest.fixture(scope="module")
+def world(shim):
+    mesh, model, fields, seed_faces, start_face = build_world("terrain")
+    mirror = YieldMirror(shim, model)
+    cfg = SLOW
+    robots, goals, gaps = convoy(model, fields, seed_faces, start_face, cfg)
+    # the departures: the last two robots leave late, so that the convoy also meets waiting robots
+    start = np.array([0, 0, 0, 0, 4, 9], np.uint32)
+    runs = {}
+
+    def model_run(check_stride, flags=0, priority=None, ticks=TICKS, **kw):
+        key = (check_stride, flags, None if priority is None else tuple(priority), ticks, tuple(sorted(kw.items())))
+        if key not in runs:
+            runs[key] = YM.run(model, cfg, fields, robots, goals, DT, ticks, DIST_TOL, ANG_TOL, start, RADIUS, check_stride, flags, AHEAD_COS, priority, **kw)
+        return runs[key]
+
+    yield model, fields, robots, goals, gaps, start, mirror, cfg, model_run
+    mirror.close()
+
+
+@pytest.mark.parametrize("check_stride", [1, 7])
+def test_the_convoy_through_the_mirror_equals_the_model(world, check_stride):
+    model, fields, robots, goals, gaps, start, mirror, cfg, model_run = world
+    # the spacing: four ticks of free driving along the synthetic field, about 0.2 m: two thirds of the radius
+    print("gaps:", gaps)
+    assert (gaps < 0.8 * RADIUS).all() and (gaps > 0.5 * RADIUS).all()
+    want = model_run(check_stride)
+    print(check_stride, "status:", want["status"], "ticks:", want["ticks"], "held_ticks:", want["held_ticks"], "hold_checks:", want["hold_checks"], want["stats"])
+    # conditions on the MODEL's own output
+    released = [(want["held_at"][:, i].any() and want["had_tick"][i, (np.nonzero(want["held_at"][:, i])[0][0] + 1) * check_stride:].any()) for i in range(len(start))]
+    assert any(released)                                              # some robot is held and later has a tick again
+    assert (want["hold_checks"] == 0).any()                           # some robot is never held
+    assert ((want["status"] == RM.REACHED) & (want["hold_checks"] > 0)).any()        # some robot ends REACHED after being held
+    assert len(set(want["held_ticks"].tolist())) >= 3                 # held_ticks differs between robots
+    for scale in SCALES:
+        got = mirror.run_yield(cfg, fields, robots, goals, TICKS, start_tick=start, scale=scale, check_stride=check_stride)
+        RM.assert_same(got, want, ("state", scale))
+        SM.assert_same_rows(got, want, ("separation", scale))
+        YM.assert_same_yield(got, want, ("yield", scale))
+        assert np.array_equal(got["ychk"][: TICKS // check_stride], want["held_at"].sum(axis=1))
+        st = fold(mirror.L, got["chk"][: TICKS // check_stride], got["ychk"][: TICKS // check_stride], check_stride, got["hold_checks"], got["held_ticks"], got["hold"])
+        assert st == want["stats"], (st, want["stats"])
+
+
+@pytest.mark.parametrize("flags,priority", [(1, None), (2, (3, 0, 2, 0, 1, 0)), (3, (0, 5, 4, 3, 2, 1))])
+def test_the_convoy_under_the_presence_flags_and_priorities(world, flags, priority):
+    model, fields, robots, goals, gaps, start, mirror, cfg, model_run = world
+    want = model_run(7, flags, priority, ticks=120)
+    got = mirror.run_yield(cfg, fields, robots, goals, 120, start_tick=start, check_stride=7, flags=flags, priority=priority)
+    RM.assert_same(got, want, ("state", flags))
+    SM.assert_same_rows(got, want, ("separation", flags))
+    YM.assert_same_yield(got, want, ("yield", flags))
+    assert want["hold_checks"].any()
+
+
+def test_a_radius_that_finds_nobody_leaves_the_fleet_rollout(world):
+    """with a radius so small that nobody is near the call is the fleet rollout: the model of separation_model.departures
+    (independent robots), all yield rows at their start values"""
+    model, fields, robots, goals, gaps, start, mirror, cfg, model_run = world
+    ticks = 60
+    late = SM.departures(model, cfg, fields, robots, goals, DT, ticks, DIST_TOL, ANG_TOL, start)
+    got = mirror.run_yield(cfg, fields, robots, goals, ticks, start_tick=start, radius=1e-4, check_stride=1, flags=0)          # (the robots of a convoy stop on one point: REACHED ones are left out)
+    RM.assert_same(got, late, "state")
+    SM.assert_same_rows(got, SM.start_rows(len(start)), "nobody near")
+    YM.assert_same_yield(got, dict(YM.start_yrows(len(start)), hold=np.zeros(len(start), np.uint8)), "start values")
+    assert not got["ychk"].any()
+    # ... and the yielding run is NOT that: the rule changes where robots are
+    want = model_run(1, ticks=ticks)
+    assert not FM.same_bits(want["pos"], late["pos"])
+
+
+def test_two_calls_through_hold_out_and_hold_in_equal_one(world):
+    """a + b ticks, a a multiple of the stride, no robot stopped after a: every robot is fed back"""
+    model, fields, robots, goals, gaps, start, mirror, cfg, model_run = world
+    stride, a, b = 7, 14, 46
+    whole = mirror.run_yield(cfg, fields, robots, goals, a + b, start_tick=start, check_stride=stride)
+    first = mirror.run_yield(cfg, fields, robots, goals, a, start_tick=start, check_stride=stride)
+    assert (first["status"] == RM.RUNNING).all() and first["hold"].any() and not first["hold"].all()
+    again = dict(robots, pos=first["pos"], dir=first["dir"], face_in=first["face"])
+    left = np.maximum(start.astype(np.int64) - a, 0).astype(np.uint32)
+    second = mirror.run_yield(cfg, fields, again, goals, b, start_tick=left, check_stride=stride, hold_in=first["hold"])
+    for k in ("status", "pos", "dir", "face", "hold"):
+        assert FM.same_bits(second[k], whole[k]), k
+    assert FM.same_bits(np.concatenate([first["trace"], second["trace"]], axis=1), whole["trace"])
+    for k in ("ticks", "hold_checks", "held_ticks"):
+        assert np.array_equal(first[k] + second[k], whole[k]), k
+    assert whole["held_ticks"].any()
+    # without the flags the second call is another one: the held robots drive until its first check
+    loose = mirror.run_yield(cfg, fields, again, goals, b, start_tick=left, check_stride=stride)
+    assert not FM.same_bits(loose["trace"], second["trace"])
+    # any non-zero byte of hold_in is a set flag
+    loud = mirror.run_yield(cfg, fields, again, goals, b, start_tick=left, check_stride=stride, hold_in=first["hold"] * 200)
+    assert FM.same_bits(loud["pos"], whole["pos"])
+
+
+def test_a_skipped_check_in_the_middle_of_a_call(world):
+    """the model with the check of tick 14 skipped; the mirror cannot skip one check only, so this pins the model's own
+    behaviour that the device test relies on: every hold cleared, no row changed"""
+    model, fields, robots, goals, gaps, start, mirror, cfg, model_run = world
+    served = model_run(7, ticks=42)
+    skipped = model_run(7, ticks=42, skip_checks=(14,))
+    assert served["held_at"][1].any() and not skipped["held_at"][1].any()
+    assert np.array_equal(skipped["held_at"][0], served["held_at"][0]) and skipped["stats"]["held_ticks"] < served["stats"]["held_ticks"]
+    assert skipped["sep_stats"] is None and len(skipped["pairs"]) == 5
+
+
+# -- the statistics of a call: yld_fold over its check rows -------------------------------------------------------------
+
+def test_the_fold_of_tables_written_by_hand(shim):
+    # separation rows: tests, ordered near pairs, largest cell, skipped; yield rows: robots held
+    hc, ht, h = [0, 2, 1, 0], [0, 9, 4, 0], [0, 1, 0, 0]
+    st = fold(shim, [[100, 6, 4, 0], [999999, 0, 50, 1], [30, 2, 3, 0]], [2, 0, 1], 5, hc, ht, h)
+    assert st == dict(robots_held=2, held_ticks=13, max_held=2, max_held_tick=5, held_last=1, checks_run=2, checks_skipped=1, first_skipped_tick=10)
+    # a skipped check is no candidate, whatever its row says; the first check with the most robots held keeps the tick
+    st = fold(shim, [[1, 0, 1, 1], [100, 6, 4, 0], [7, 2, 9, 0], [7, 2, 9, 1]], [77, 3, 3, 99], 5, hc, ht, h)
+    assert (st["max_held"], st["max_held_tick"], st["checks_run"], st["checks_skipped"], st["first_skipped_tick"]) == (3, 10, 2, 2, 5)
+    # checks that hold nobody: the first one run is the maximum; every check skipped or none at all: the reset values
+    none = dict(robots_held=0, held_ticks=0, max_held=0, max_held_tick=NONE, held_last=0, checks_run=0, checks_skipped=0, first_skipped_tick=NONE)
+    assert fold(shim, [[3, 0, 1, 1], [3, 0, 1, 0]], [0, 0], 4, [0, 0], [0, 0], [0, 0]) == dict(none, max_held_tick=8, checks_run=1, checks_skipped=1, first_skipped_tick=4)
+    assert fold(shim, [[3, 0, 1, 1]], [0], 4, [0], [0], [1]) == dict(none, held_last=1, checks_skipped=1, first_skipped_tick=4)
+    assert fold(shim, np.zeros((0, 4)), np.zeros(0), 1, [3], [2 ** 32 - 1], [0]) == dict(none, robots_held=1, held_ticks=2 ** 32 - 1)
+    # held ticks sum in 64 bits
+    assert fold(shim, np.zeros((0, 4)), np.zeros(0), 1, [1, 1], [2 ** 32 - 1, 2 ** 32 - 1], [1, 1])["held_ticks"] == 2 ** 33 - 2
