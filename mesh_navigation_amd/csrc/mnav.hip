@@ -245,10 +245,9 @@ struct mnav_ctx {
   DevBuf<float> d_fnrm; bool have_face_normals = false;            // MeshMap::faceNormals() (mnav_upload_face_normals): F x 3, gone with the mesh
   mnav_rol::Dev rol;                                               // device rollouts, both entry points: the rest of the resident robot state, goals, counter rows, trace
   mnav_frol::State frol;                                           // fleet rollout: start ticks, the separation check's table, records, rows and check rows, its event pairs
-  mnav_rol::Stats rol_stats, frol_stats;                           // statistics of the last mnav_follow_rollout / of the last mnav_fleet_rollout
-  mnav_frol::SepStats frol_sep_stats;                              // ... and of the latter's checks
+  struct RolloutRecord { mnav_rol::Stats rol; mnav_frol::SepStats sep; mnav_frol::YldStats yld; };   // what one rollout entry point's *_stats tell of its last call
+  RolloutRecord rol_rec, frol_rec, yld_rec;                        // mnav_follow_rollout, mnav_fleet_rollout, mnav_fleet_rollout_yield: kept apart
   mnav_frol::YldState yld;                                         // yielding fleet rollout: hold flags, priorities, yield rows and check rows, the pair passes' event pairs
-  mnav_rol::Stats yld_rol_stats; mnav_frol::SepStats yld_sep_stats; mnav_frol::YldStats yld_stats;   // the last mnav_fleet_rollout_yield: its own records, the holds among them
   mnav_chg::Scratch chg;                                           // obstacle / clearance / border layers: change list and counters of the last call
   mnav_map::State map;                                             // resident layer graph (mnav_map_*): nodes, tables, change lists of the last update
   uint32_t infl_steps = 0, infl_bands = 0; uint64_t infl_evals = 0; float infl_ms = 0.f, infl_ms_wave = 0.f;   // last inflation wave

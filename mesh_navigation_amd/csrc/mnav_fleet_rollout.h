@@ -27,17 +27,18 @@
 //   k_sep_sums / k_sep_top / k_sep_starts   exclusive scan of the counts in slot order (tiles of 2048 slots: tile sums, one
 //                  workgroup over the tile sums, every tile over its own counts; no kernel waits for another workgroup)
 //   k_sep_fill     record (x, y, z, id) at start[slot] + rank; T += the populations of the cells in the robot's range
-//                  (uint64, one atomic per wave): the distance tests the pair pass would perform; largest cell population
+//                  (sep_tests; uint64, one atomic per wave): the distance tests the pair pass would perform; largest cell
 //   k_sep_pair     T > separation_max_tests: the check is SKIPPED (flag in the check's row, read here, no host round trip).
-//                  Else one lane per robot streams the records of its range; only robot i writes row i; the near partners
-//                  of a wave go as one 64-bit add into the check's row.
+//                  Else one lane per robot streams the records of its range (sep_near); only robot i writes row i; the
+//                  near partners of a wave go as one 64-bit add into the check's row.
 // The atomics decide a record's place inside its cell and a key's slot in the table; neither is visible in an output.
-// The host mirror sep_check_host runs the same MNAV_HD pieces serially; sep_fold makes a call's statistics (SepStats) of its
-// check rows on the host.
+// One walk, sep_cells, visits a range's cells for sep_tests and sep_near.  The host mirror runs the same MNAV_HD pieces
+// serially (HostGrid, sep_check_host_each, sep_check_host); sep_fold makes a call's statistics (SepStats) of its check rows.
 #pragma once
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <vector>
 
 #include "mnav_rollout.h"
 
@@ -184,29 +185,42 @@ MNAV_HD void sep_close(Row& R, const Best& b, uint32_t tick)
   if (b.d2 < R.min_sep2) { R.min_sep2 = b.d2; R.min_sep_tick = tick; R.min_sep_robot = b.id; }
 }
 
-// The cells of robot i's range: *tests += their populations; with `best`, every record in them but i's own is compared.
-// rec: 4 floats per record, (x, y, z, the id's bits), sorted by slot; cnt / start: per slot.
-template <class Keys>
-MNAV_HD void sep_visit(const Grid& G, const Keys* keys, uint32_t mask, const uint32_t* cnt, const uint32_t* start, const float* rec, uint32_t i, W3 p,
-                       uint64_t* tests, Best* best)
+// The one walk over the cells of the range of a robot at p: cell(slot) for every cell of it that exists.
+template <class Keys, class Cell>
+MNAV_HD void sep_cells(const Grid& G, const Keys* keys, uint32_t mask, W3 p, Cell cell)
 {
   const Range R = sep_range(G, p);
   for (int cx = R.lo[0]; cx <= R.hi[0]; ++cx)
     for (int cy = R.lo[1]; cy <= R.hi[1]; ++cy)
       for (int cz = R.lo[2]; cz <= R.hi[2]; ++cz) {
         const uint32_t s = sep_find(keys, mask, sep_key(cx, cy, cz));
-        if (s == kNone) continue;
-        const uint32_t c = cnt[s];
-        *tests += c;
-        if (!best) continue;
-        const float* q = rec + 4 * (size_t)start[s];
-        for (uint32_t k = 0; k < c; ++k, q += 4) {
-          const uint32_t j = sep_bits(q[3]);
-          if (j == i) continue;
-          const float d2 = sep_d2(p, mnav::w3(q[0], q[1], q[2]));
-          if (d2 <= G.r2) sep_meet(*best, d2, j);
-        }
+        if (s != kNone) cell(s);
       }
+}
+// the populations of those cells: the distance tests sep_near performs for the robot (its own record among them)
+template <class Keys>
+MNAV_HD uint64_t sep_tests(const Grid& G, const Keys* keys, uint32_t mask, const uint32_t* cnt, W3 p)
+{
+  uint64_t tests = 0;
+  sep_cells(G, keys, mask, p, [&](uint32_t s) { tests += cnt[s]; });
+  return tests;
+}
+// Every record of those cells but robot i's own whose d2 <= r2 goes to near(j, d2, pj).  rec: 4 floats per record, (x, y, z,
+// the id's bits), sorted by slot; cnt / start: per slot.
+template <class Keys, class Near>
+MNAV_HD void sep_near(const Grid& G, const Keys* keys, uint32_t mask, const uint32_t* cnt, const uint32_t* start, const float* rec, uint32_t i, W3 p, Near near)
+{
+  sep_cells(G, keys, mask, p, [&](uint32_t s) {
+    const uint32_t c = cnt[s];
+    const float* q = rec + 4 * (size_t)start[s];
+    for (uint32_t k = 0; k < c; ++k, q += 4) {
+      const uint32_t j = sep_bits(q[3]);
+      if (j == i) continue;
+      const W3 pj = mnav::w3(q[0], q[1], q[2]);
+      const float d2 = sep_d2(p, pj);
+      if (d2 <= G.r2) near(j, d2, pj);
+    }
+  });
 }
 
 // the per-robot outputs as arrays (device or host)
@@ -235,53 +249,59 @@ inline uint32_t sep_table_size(uint32_t n)
 }
 
 #if !defined(__HIP_DEVICE_COMPILE__)
-// The host mirror of one check, serially, over the same pieces: call tick `tick` (from 1), positions and statuses as they
-// stand after it.  table_size: a power of two > n.  chk: the check's row (kCheckWords).  Returns false when the guard
-// skipped the pair pass.
+// The host mirrors of a check, serially, over the same pieces.  HostGrid: what the device passes up to k_sep_fill leave of
+// call tick `tick` (from 1), positions and statuses as they stand after it.  table_size: a power of two > n.
+struct HostGrid {
+  uint32_t mask; uint64_t tests = 0, max_cell = 0;
+  std::vector<uint64_t> keys; std::vector<uint32_t> cnt, start, slot_of, rank; std::vector<float> rec;
+  HostGrid(uint32_t n, const float* pos, const int32_t* status, const uint32_t* start_tick, uint32_t tick, uint32_t flags, const Grid& G, uint32_t table_size)
+      : mask(table_size - 1), keys(table_size, kEmptyKey), cnt(table_size, 0u), start(table_size), slot_of(n, kNone), rank(n), rec(4 * (size_t)n)
+  {
+    for (uint32_t i = 0; i < n; ++i) {
+      const W3 p = mnav::w3_load(pos + 3 * (size_t)i);
+      if (!sep_present(status[i], start_tick && frol_waits(tick, start_tick[i]), flags, p)) continue;
+      const uint32_t s = sep_insert(mask, sep_key_of(G, p), [&](uint32_t at, uint64_t key) { const uint64_t was = keys[at]; if (was == kEmptyKey) keys[at] = key; return was; });
+      slot_of[i] = s; rank[i] = cnt[s]++;
+    }
+    uint32_t sum = 0;
+    for (uint32_t s = 0; s < table_size; ++s) { start[s] = sum; sum += cnt[s]; }
+    for (uint32_t i = 0; i < n; ++i) {
+      if (slot_of[i] == kNone) continue;
+      const W3 p = mnav::w3_load(pos + 3 * (size_t)i);
+      float* q = rec.data() + 4 * (size_t)(start[slot_of[i]] + rank[i]);
+      q[0] = p.x; q[1] = p.y; q[2] = p.z; q[3] = sep_float(i);
+      if (cnt[slot_of[i]] > max_cell) max_cell = cnt[slot_of[i]];
+      tests += sep_tests(G, keys.data(), mask, cnt.data(), p);        // (keys and counts are final: only the records are being placed)
+    }
+  }
+};
+// One check: the check's row chk (kCheckWords), the guard, and for every present robot robot(grid, i, b) -- which meets the
+// robot's partners into b -- and b into the robot's Row.  Returns false when the guard skipped the pair pass: no robot ran.
+template <class Robot>
+inline bool sep_check_host_each(uint32_t n, const float* pos, const int32_t* status, const uint32_t* start_tick, uint32_t tick, uint32_t flags, const Grid& G,
+                                uint32_t table_size, uint64_t max_tests, const Rows& rows, uint64_t* chk, Robot robot)
+{
+  const HostGrid H(n, pos, status, start_tick, tick, flags, G, table_size);
+  chk[kChkTests] = H.tests; chk[kChkMaxCell] = H.max_cell; chk[kChkOrdered] = 0; chk[kChkSkipped] = H.tests > max_tests;
+  if (chk[kChkSkipped]) return false;
+  for (uint32_t i = 0; i < n; ++i) {
+    if (H.slot_of[i] == kNone) continue;
+    Best b = sep_best_start();
+    robot(H, i, b);
+    Row R = sep_row_load(rows, i);
+    sep_close(R, b, tick);
+    sep_row_store(rows, i, R);
+    chk[kChkOrdered] += b.partners;
+  }
+  return true;
+}
+// the mirror of k_sep_clear .. k_sep_pair
 inline bool sep_check_host(uint32_t n, const float* pos, const int32_t* status, const uint32_t* start_tick, uint32_t tick, uint32_t flags, const Grid& G,
                            uint32_t table_size, uint64_t max_tests, const Rows& rows, uint64_t* chk)
 {
-  const uint32_t mask = table_size - 1;
-  uint64_t* keys = new uint64_t[table_size];
-  uint32_t* cnt = new uint32_t[table_size]();
-  uint32_t* start = new uint32_t[table_size];
-  uint32_t* slot_of = new uint32_t[n ? n : 1];
-  uint32_t* rank = new uint32_t[n ? n : 1];
-  float* rec = new float[4 * (size_t)(n ? n : 1)];
-  for (uint32_t s = 0; s < table_size; ++s) keys[s] = kEmptyKey;
-  for (uint32_t i = 0; i < n; ++i) {
-    const W3 p = mnav::w3_load(pos + 3 * (size_t)i);
-    slot_of[i] = kNone;
-    if (!sep_present(status[i], start_tick && frol_waits(tick, start_tick[i]), flags, p)) continue;
-    const uint32_t s = sep_insert(mask, sep_key_of(G, p), [&](uint32_t at, uint64_t key) { const uint64_t was = keys[at]; if (was == kEmptyKey) keys[at] = key; return was; });
-    slot_of[i] = s; rank[i] = cnt[s]++;
-  }
-  uint32_t sum = 0;
-  for (uint32_t s = 0; s < table_size; ++s) { start[s] = sum; sum += cnt[s]; }
-  uint64_t tests = 0, max_cell = 0;
-  for (uint32_t i = 0; i < n; ++i) {
-    if (slot_of[i] == kNone) continue;
-    const W3 p = mnav::w3_load(pos + 3 * (size_t)i);
-    float* q = rec + 4 * (size_t)(start[slot_of[i]] + rank[i]);
-    q[0] = p.x; q[1] = p.y; q[2] = p.z; q[3] = sep_float(i);
-    if (cnt[slot_of[i]] > max_cell) max_cell = cnt[slot_of[i]];
-  }
-  for (uint32_t i = 0; i < n; ++i)
-    if (slot_of[i] != kNone) sep_visit(G, keys, mask, cnt, start, rec, i, mnav::w3_load(pos + 3 * (size_t)i), &tests, (Best*)nullptr);
-  chk[kChkTests] = tests; chk[kChkMaxCell] = max_cell; chk[kChkOrdered] = 0; chk[kChkSkipped] = tests > max_tests;
-  if (!chk[kChkSkipped])
-    for (uint32_t i = 0; i < n; ++i) {
-      if (slot_of[i] == kNone) continue;
-      Best b = sep_best_start();
-      uint64_t unused = 0;
-      sep_visit(G, keys, mask, cnt, start, rec, i, mnav::w3_load(pos + 3 * (size_t)i), &unused, &b);
-      Row R = sep_row_load(rows, i);
-      sep_close(R, b, tick);
-      sep_row_store(rows, i, R);
-      chk[kChkOrdered] += b.partners;
-    }
-  delete[] keys; delete[] cnt; delete[] start; delete[] slot_of; delete[] rank; delete[] rec;
-  return !chk[kChkSkipped];
+  return sep_check_host_each(n, pos, status, start_tick, tick, flags, G, table_size, max_tests, rows, chk, [&](const HostGrid& H, uint32_t i, Best& b) {
+    sep_near(G, H.keys.data(), H.mask, H.cnt.data(), H.start.data(), H.rec.data(), i, mnav::w3_load(pos + 3 * (size_t)i), [&](uint32_t j, float d2, W3) { sep_meet(b, d2, j); });
+  });
 }
 #endif
 
@@ -460,9 +480,7 @@ __global__ __launch_bounds__(kSepBlock) void k_sep_fill(Sep S, uint32_t check)
       float* q = S.rec + 4 * (size_t)(S.start[slot] + S.rank[i]);     // start + rank < the present robots <= n
       q[0] = p.x; q[1] = p.y; q[2] = p.z; q[3] = sep_float(i);
       cell = S.cnt[slot];
-      uint64_t t = 0;
-      sep_visit(S.G, S.keys, S.mask, S.cnt, S.start, S.rec, i, p, &t, (Best*)nullptr);
-      tests = t;
+      tests = sep_tests(S.G, S.keys, S.mask, S.cnt, p);
     }
   }
   tests = sep_wave_sum(tests);
@@ -485,8 +503,7 @@ __global__ __launch_bounds__(kSepBlock) void k_sep_pair(Sep S, uint32_t check, u
   unsigned long long partners = 0;
   if (i < S.n && S.slot_of[i] != kNone) {
     Best b = sep_best_start();
-    uint64_t unused = 0;
-    sep_visit(S.G, S.keys, S.mask, S.cnt, S.start, S.rec, i, mnav::w3_load(S.pos + 3 * (size_t)i), &unused, &b);
+    sep_near(S.G, S.keys, S.mask, S.cnt, S.start, S.rec, i, mnav::w3_load(S.pos + 3 * (size_t)i), [&](uint32_t j, float d2, W3) { sep_meet(b, d2, j); });
     if (b.partners) {
       Row R = sep_row_load(S.rows, i);
       sep_close(R, b, tick);

@@ -1,6 +1,6 @@
 // mnav_fleet_yield.h -- fleet rollouts in which robots yield (mnav_fleet_rollout_yield): mnav_fleet_rollout.h's check with a
 // right-of-way rule evaluated inside its pair pass, whose result keeps a robot from ticking until the next check.  Three
-// additions to mnav_fleet_rollout.h, which stays as it is:
+// additions to mnav_fleet_rollout.h, over its grid walk (sep_near) and its host check loop (sep_check_host_each):
 //
 //   * the rule (include/mnav.h has it in full), in MNAV_HD pieces that device, host mirror and tests share: yld_mover (RUNNING
 //     and departed), yld_ahead (partner j lies inside the cone of half angle acos(c) about robot i's heading: dot > 0 &&
@@ -15,17 +15,16 @@
 //     robot without a tick, like a waiting one.  k_yield_rollout_stay / _search / _global are the unchanged pass bodies of
 //     mnav_follow.h over it.  FleetTick's start ticks are never null: the driver supplies zeros.
 //
-//   * k_yld_pair, the pair pass of a check with the rule.  It visits what k_sep_pair visits (yld_visit: sep_visit's cells and
-//     records, every near partner handed to a callable) and folds the same partners into the same separation Row, so the
-//     separation outputs are k_sep_pair's bit for bit.  For a near partner only -- the 16-byte records stay as they are --
-//     and among those only for one that is ahead and could still become the blocker, it gathers the partner's status, start
-//     tick, heading and priority by id from the resident rows.  It writes hold[i] for
-//     every robot (0 for one that is not present, not a mover or yields to nobody), the YRow of a held robot, and adds the
-//     held robots of a wave as one integer add to the check's yield row.  A check the guard skips clears hold: with no
-//     information nobody is held.
+//   * k_yld_pair, the pair pass of a check with the rule.  It visits what k_sep_pair visits (sep_near: every near partner
+//     handed to a callable) and folds the same partners into the same separation Row, so the separation outputs are
+//     k_sep_pair's bit for bit.  For a near partner only -- the 16-byte records stay as they are -- and among those only for
+//     one that is ahead and could still become the blocker, it gathers the partner's status, start tick, heading and
+//     priority by id from the resident rows.  It writes hold[i] for every robot (0 for one that is not present, not a mover
+//     or yields to nobody), the YRow of a held robot, and adds the held robots of a wave as one integer add to the check's
+//     yield row.  A check the guard skips clears hold: with no information nobody is held.
 //
-// The host mirror yld_check_host runs the same pieces serially; yld_fold makes a call's statistics (YldStats) of the check
-// rows on the host.
+// The host mirror yld_check_host runs the same pieces serially, inside sep_check_host's own loop; yld_fold makes a call's
+// statistics (YldStats) of the check rows on the host.
 #pragma once
 #include "mnav_fleet_rollout.h"
 
@@ -75,29 +74,6 @@ MNAV_HD void yld_row_store(const YRows& A, uint32_t i, const YRow& R) { A.hold_c
 // the resident rows a decision gathers from, by robot id; start_tick and priority may be null (all 0)
 struct YGather { const float* pos; const float* dir; const int32_t* status; const uint32_t* start_tick; const uint32_t* priority; float c2; };
 
-// sep_visit's walk with `best` given: every record of the cells of robot i's range but i's own whose d2 <= r2 goes to
-// near(j, d2, pj)
-template <class Keys, class Near>
-MNAV_HD void yld_visit(const Grid& G, const Keys* keys, uint32_t mask, const uint32_t* cnt, const uint32_t* start, const float* rec, uint32_t i, W3 p, Near near)
-{
-  const Range R = sep_range(G, p);
-  for (int cx = R.lo[0]; cx <= R.hi[0]; ++cx)
-    for (int cy = R.lo[1]; cy <= R.hi[1]; ++cy)
-      for (int cz = R.lo[2]; cz <= R.hi[2]; ++cz) {
-        const uint32_t s = sep_find(keys, mask, sep_key(cx, cy, cz));
-        if (s == kNone) continue;
-        const uint32_t c = cnt[s];
-        const float* q = rec + 4 * (size_t)start[s];
-        for (uint32_t k = 0; k < c; ++k, q += 4) {
-          const uint32_t j = sep_bits(q[3]);
-          if (j == i) continue;
-          const W3 pj = mnav::w3(q[0], q[1], q[2]);
-          const float d2 = sep_d2(p, pj);
-          if (d2 <= G.r2) near(j, d2, pj);
-        }
-      }
-}
-
 // One present robot i at the check after call tick `tick`: its partners into `partners` (what k_sep_pair folds), those it
 // yields to into `blockers` -- its d2 / id are the blocker's, its count is only zero or not (see below).  Only a mover asks
 // anything of a partner's row.
@@ -109,7 +85,7 @@ MNAV_HD void yld_robot(const Grid& G, const Keys* keys, uint32_t mask, const uin
   const bool mover = yld_mover(Y.status[i], Y.start_tick && frol_waits(tick, Y.start_tick[i]));
   const W3 di = mover ? mnav::w3_load(Y.dir + 3 * (size_t)i) : mnav::w3(0, 0, 0);
   const uint32_t prio_i = Y.priority ? Y.priority[i] : 0u;
-  yld_visit(G, keys, mask, cnt, start, rec, i, p, [&](uint32_t j, float d2, W3 pj) {
+  sep_near(G, keys, mask, cnt, start, rec, i, p, [&](uint32_t j, float d2, W3 pj) {
     sep_meet(partners, d2, j);
     if (!mover) return;
     // a robot that is held already asks only partners that could become its blocker (nearer, or as near with a smaller
@@ -127,61 +103,24 @@ MNAV_HD void yld_robot(const Grid& G, const Keys* keys, uint32_t mask, const uin
 }
 
 #if !defined(__HIP_DEVICE_COMPILE__)
-// The host mirror of one check with the rule, serially, over the same pieces: what sep_check_host does for `rows` and `chk`,
-// and hold (n bytes, every one written), yrows and ychk (kYldCheckWords).  Returns false when the guard skipped the pair
-// pass: then hold is all 0.
+// The host mirror of one check with the rule: sep_check_host's `rows` and `chk` out of the same loop, and hold (n bytes,
+// every one written), yrows and ychk (kYldCheckWords).  Returns false when the guard skipped the pair pass: hold is all 0.
 inline bool yld_check_host(uint32_t n, const float* pos, const float* dir, const int32_t* status, const uint32_t* start_tick, const uint32_t* priority, uint32_t tick,
                            uint32_t flags, const Grid& G, float c2, uint32_t table_size, uint64_t max_tests, const Rows& rows, const YRows& yrows, uint8_t* hold,
                            uint64_t* chk, uint32_t* ychk)
 {
-  const uint32_t mask = table_size - 1;
-  uint64_t* keys = new uint64_t[table_size];
-  uint32_t* cnt = new uint32_t[table_size]();
-  uint32_t* start = new uint32_t[table_size];
-  uint32_t* slot_of = new uint32_t[n ? n : 1];
-  uint32_t* rank = new uint32_t[n ? n : 1];
-  float* rec = new float[4 * (size_t)(n ? n : 1)];
-  for (uint32_t s = 0; s < table_size; ++s) keys[s] = kEmptyKey;
-  for (uint32_t i = 0; i < n; ++i) {
-    const W3 p = mnav::w3_load(pos + 3 * (size_t)i);
-    slot_of[i] = kNone; hold[i] = 0;
-    if (!sep_present(status[i], start_tick && frol_waits(tick, start_tick[i]), flags, p)) continue;
-    const uint32_t s = sep_insert(mask, sep_key_of(G, p), [&](uint32_t at, uint64_t key) { const uint64_t was = keys[at]; if (was == kEmptyKey) keys[at] = key; return was; });
-    slot_of[i] = s; rank[i] = cnt[s]++;
-  }
-  uint32_t sum = 0;
-  for (uint32_t s = 0; s < table_size; ++s) { start[s] = sum; sum += cnt[s]; }
-  uint64_t tests = 0, max_cell = 0;
-  for (uint32_t i = 0; i < n; ++i) {
-    if (slot_of[i] == kNone) continue;
-    const W3 p = mnav::w3_load(pos + 3 * (size_t)i);
-    float* q = rec + 4 * (size_t)(start[slot_of[i]] + rank[i]);
-    q[0] = p.x; q[1] = p.y; q[2] = p.z; q[3] = sep_float(i);
-    if (cnt[slot_of[i]] > max_cell) max_cell = cnt[slot_of[i]];
-  }
-  for (uint32_t i = 0; i < n; ++i)
-    if (slot_of[i] != kNone) sep_visit(G, keys, mask, cnt, start, rec, i, mnav::w3_load(pos + 3 * (size_t)i), &tests, (Best*)nullptr);
-  chk[kChkTests] = tests; chk[kChkMaxCell] = max_cell; chk[kChkOrdered] = 0; chk[kChkSkipped] = tests > max_tests;
+  for (uint32_t i = 0; i < n; ++i) hold[i] = 0;
   ychk[kYchkHeld] = 0;
   const YGather Y{ pos, dir, status, start_tick, priority, c2 };
-  if (!chk[kChkSkipped])
-    for (uint32_t i = 0; i < n; ++i) {
-      if (slot_of[i] == kNone) continue;
-      Best b = sep_best_start(), blockers = sep_best_start();
-      yld_robot(G, keys, mask, cnt, start, rec, Y, i, tick, b, blockers);
-      Row R = sep_row_load(rows, i);
-      sep_close(R, b, tick);
-      sep_row_store(rows, i, R);
-      chk[kChkOrdered] += b.partners;
-      if (blockers.partners) {
-        YRow H = yld_row_load(yrows, i);
-        yld_close(H, blockers, tick);
-        yld_row_store(yrows, i, H);
-        hold[i] = 1; ychk[kYchkHeld] += 1;
-      }
-    }
-  delete[] keys; delete[] cnt; delete[] start; delete[] slot_of; delete[] rank; delete[] rec;
-  return !chk[kChkSkipped];
+  return sep_check_host_each(n, pos, status, start_tick, tick, flags, G, table_size, max_tests, rows, chk, [&](const HostGrid& H, uint32_t i, Best& b) {
+    Best blockers = sep_best_start();
+    yld_robot(G, H.keys.data(), H.mask, H.cnt.data(), H.start.data(), H.rec.data(), Y, i, tick, b, blockers);
+    if (!blockers.partners) return;
+    YRow R = yld_row_load(yrows, i);
+    yld_close(R, blockers, tick);
+    yld_row_store(yrows, i, R);
+    hold[i] = 1; ychk[kYchkHeld] += 1;
+  });
 }
 #endif
 

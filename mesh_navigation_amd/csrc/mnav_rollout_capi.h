@@ -3,7 +3,7 @@
 // mnav_rollout.h, mnav_fleet_rollout.h and mnav_fleet_yield.h.  Included by
 // mnav.hip inside its extern "C" block, after mnav_follow_capi.h (the argument checks are the follower's) and
 // mnav_locate_capi.h (the index build is the lookup's own).  One driver, rollout_run, holds the call; the three entry points
-// hand it their arguments and their own statistics records.  The device buffers are shared (a call uploads every input at
+// hand it one RolloutCall with their arguments and their own statistics record.  The device buffers are shared (a call uploads every input at
 // entry), the statistics are kept apart: a call of one entry point leaves what the other's *_stats tells alone.
 #pragma once
 
@@ -96,10 +96,23 @@ static int fleet_yield_reserve(mnav_ctx* ctx, size_t n, size_t checks)
 }
 
 // The optional last input of rollout_run: the right-of-way rule of mnav_fleet_rollout_yield.  config null: no rule, and then
-// every other pointer must be null; host pointers, each output may be null.  stats: the record of mnav_fleet_yield_stats.
+// every other pointer must be null; host pointers, each output may be null.
 struct YieldCall {
   const mnav_yield_config* config = nullptr; const uint32_t* priority = nullptr; const uint8_t* hold_in = nullptr; uint8_t* hold_out = nullptr;
-  mnav_frol::YRows out = { nullptr, nullptr, nullptr, nullptr }; mnav_frol::YldStats* stats = nullptr;
+  mnav_frol::YRows out = { nullptr, nullptr, nullptr, nullptr };
+};
+
+// One call of rollout_run, as its entry point fills it.  tag names the entry point in the messages that do, rec is the record
+// its *_stats functions read.  start_tick: null, or a departure tick per robot; separation: null, or the check, whose
+// per-robot outputs go to sep_out; yld: the rule inside the check, or one without a config.  Host pointers; each output may be
+// null, and all of sep_out are without a separation.
+struct RolloutCall {
+  const char* tag; mnav_ctx::RolloutRecord* rec;
+  uint32_t n; const float* pos; const float* dir; const float* up; const uint32_t* face_in; const uint32_t* slots; const uint32_t* seed_faces;
+  const float* goal_pos; const float* goal_dir; const mnav_follow_config* config; const mnav_rollout_config* rollout;
+  const uint32_t* start_tick; const mnav_separation_config* separation;
+  struct { int32_t* status; uint32_t* ticks; float* pos; float* dir; uint32_t* face; double* travel; double* cost_integral; float* min_goal_dist; float* trace; } out;
+  mnav_frol::Rows sep_out; YieldCall yld;
 };
 
 // The argument checks of a rollout beside the follower's, all on the host: -1 with ctx->err set, or 0.
@@ -120,79 +133,72 @@ static int rollout_check(mnav_ctx* ctx, const float* goal_pos, const float* goal
   return 0;
 }
 
-// The whole call of every entry point.  start_tick: null, or a departure tick per robot; separation: null, or the check,
-// whose per-robot outputs go to sep_out (host pointers, each may be null; all null without a separation); yld: the rule
-// inside the check, or one without a config.  `tag` names the
-// entry point in the messages that do, `stats` / `sep_stats` are the records of its *_stats function.  Returns 0, 1 when
-// cancelled, 2 when a check was skipped, -1 with ctx->err set.
-static int rollout_run(mnav_ctx* ctx, const char* tag, mnav_rol::Stats& stats, mnav_frol::SepStats& sep_stats, uint32_t n, const float* pos, const float* dir,
-                       const float* up, const uint32_t* face_in, const uint32_t* slots, const uint32_t* seed_faces, const float* goal_pos, const float* goal_dir,
-                       const mnav_follow_config* config, const mnav_rollout_config* rollout, const uint32_t* start_tick, const mnav_separation_config* separation,
-                       int32_t* status_out, uint32_t* ticks_out, float* pos_out, float* dir_out, uint32_t* face_out, double* travel_out, double* cost_integral_out,
-                       float* min_goal_dist_out, float* trace_out, const mnav_frol::Rows& sep_out, const YieldCall& yld)
+// The whole call of every entry point.  Returns 0, 1 when cancelled, 2 when a check was skipped, -1 with ctx->err set.
+static int rollout_run(mnav_ctx* ctx, const RolloutCall& A)
 {
   using namespace mnav_frol;
   using mnav_rol::Batch; using mnav_rol::kCounters; using mnav_rol::kStayBlock; using mnav_rol::Params; using mnav::WalkMesh;
+  const uint32_t n = A.n;
   ctx->err.clear();
   if (!n) return 0;
   const auto t0 = std::chrono::steady_clock::now();
   // every refusal comes before the first device call: a refused call touches nothing
   std::vector<const float*> maps;
-  if (follow_check(ctx, n, pos, dir, up, face_in, slots, seed_faces, config, maps)) return -1;
-  if (rollout_check(ctx, goal_pos, goal_dir, config, rollout, trace_out)) return -1;
-  const uint32_t ticks = rollout->ticks, stride = rollout->trace_stride, rows = stride ? ticks / stride : 0;
+  if (follow_check(ctx, n, A.pos, A.dir, A.up, A.face_in, A.slots, A.seed_faces, A.config, maps)) return -1;
+  if (rollout_check(ctx, A.goal_pos, A.goal_dir, A.config, A.rollout, A.out.trace)) return -1;
+  const uint32_t ticks = A.rollout->ticks, stride = A.rollout->trace_stride, rows = stride ? ticks / stride : 0;
   Grid grid{};
   uint32_t check_stride = 0, flags = 0;
-  if (!separation) {
-    if (sep_out.near_checks || sep_out.max_partners || sep_out.first_near_tick || sep_out.first_near_robot || sep_out.min_sep2 || sep_out.min_sep_tick ||
-        sep_out.min_sep_robot) {
+  if (!A.separation) {
+    if (A.sep_out.near_checks || A.sep_out.max_partners || A.sep_out.first_near_tick || A.sep_out.first_near_robot || A.sep_out.min_sep2 || A.sep_out.min_sep_tick ||
+        A.sep_out.min_sep_robot) {
       ctx->err = "fleet rollout: a separation output without a separation config"; return -1;
     }
   } else {
     double scale = opt_set(ctx->opt.separation_cell_scale) ? ctx->opt.separation_cell_scale : (double)kDefaultCellScale;
     if (!(scale >= 1.0 && scale <= 4.0)) { ctx->err = "fleet rollout: separation_cell_scale outside 1 .. 4"; return -1; }
-    grid = sep_grid((float)separation->radius, (float)scale);
-    if (!((float)separation->radius > 0.f) || !sep_grid_ok(grid)) { ctx->err = "fleet rollout: radius: (float)radius must be positive, its square finite and positive"; return -1; }
-    check_stride = separation->check_stride; flags = separation->flags;
+    grid = sep_grid((float)A.separation->radius, (float)scale);
+    if (!((float)A.separation->radius > 0.f) || !sep_grid_ok(grid)) { ctx->err = "fleet rollout: radius: (float)radius must be positive, its square finite and positive"; return -1; }
+    check_stride = A.separation->check_stride; flags = A.separation->flags;
     if (check_stride < 1 || check_stride > ticks) { ctx->err = "fleet rollout: check_stride outside 1 .. ticks"; return -1; }
     if (flags & ~kKnownFlags) { ctx->err = "fleet rollout: unknown separation flag"; return -1; }
   }
-  const bool yielding = yld.config != nullptr;
+  const bool yielding = A.yld.config != nullptr;
   float ahead_c2 = 0.f;
   if (!yielding) {
-    if (yld.priority || yld.hold_in || yld.hold_out || yld.out.hold_checks || yld.out.held_ticks || yld.out.first_hold_tick || yld.out.first_hold_robot) {
+    if (A.yld.priority || A.yld.hold_in || A.yld.hold_out || A.yld.out.hold_checks || A.yld.out.held_ticks || A.yld.out.first_hold_tick || A.yld.out.first_hold_robot) {
       ctx->err = "fleet rollout yield: a yield input or output without a yield config"; return -1;
     }
   } else {
-    if (!separation) { ctx->err = "fleet rollout yield: a yield config without a separation config"; return -1; }
-    const float c = (float)yld.config->ahead_cos;
+    if (!A.separation) { ctx->err = "fleet rollout yield: a yield config without a separation config"; return -1; }
+    const float c = (float)A.yld.config->ahead_cos;
     if (!yld_cos_ok(c)) { ctx->err = "fleet rollout yield: ahead_cos: (float)ahead_cos must be finite, at least 0 and below 1"; return -1; }
-    if (yld.config->flags) { ctx->err = "fleet rollout yield: the flags of the yield config are reserved and must be 0"; return -1; }
+    if (A.yld.config->flags) { ctx->err = "fleet rollout yield: the flags of the yield config are reserved and must be 0"; return -1; }
     ahead_c2 = c * c;
   }
-  const uint32_t checks = separation ? ticks / check_stride : 0, table = separation ? sep_table_size(n) : 0;
+  const uint32_t checks = A.separation ? ticks / check_stride : 0, table = A.separation ? sep_table_size(n) : 0;
   const double max_tests_d = opt_set(ctx->opt.separation_max_tests) ? std::max(ctx->opt.separation_max_tests, 0.0) : kDefaultMaxTests;
   const unsigned long long max_tests = max_tests_d >= 18446744073709551615.0 ? ~0ull : (unsigned long long)max_tests_d;
   if (hipSetDevice(ctx->device) != hipSuccess) { ctx->err = "hipSetDevice failed"; return -1; }
   cancel_reset(ctx);                                                  // as the plan calls do
   if (upload_walk_mesh(ctx)) return -1;
-  if (staging_reserve(ctx, n, ctx->res.plans(), tag) || rollout_reserve(ctx, tag, n, goal_pos != nullptr, ticks, 3 * (size_t)n * rows) ||
-      fleet_rollout_reserve(ctx, n, start_tick != nullptr || yielding, separation != nullptr, table, checks) || (yielding && fleet_yield_reserve(ctx, n, checks))) return -1;
+  if (staging_reserve(ctx, n, ctx->res.plans(), A.tag) || rollout_reserve(ctx, A.tag, n, A.goal_pos != nullptr, ticks, 3 * (size_t)n * rows) ||
+      fleet_rollout_reserve(ctx, n, A.start_tick != nullptr || yielding, A.separation != nullptr, table, checks) || (yielding && fleet_yield_reserve(ctx, n, checks))) return -1;
   mnav_rol::Dev& R = ctx->rol;
   State& S = ctx->frol;
   YldState& Y = ctx->yld;
   mnav_fol::Staging& G = ctx->stage;
-  stats = {}; sep_stats = {};
-  if (yld.stats) *yld.stats = {};
-  if (locate_ensure(ctx, &stats.built_index)) return -1;              // no look at the lists between ticks: the index exists before the first one
+  mnav_ctx::RolloutRecord& rec = *A.rec;
+  rec = {};
+  if (locate_ensure(ctx, &rec.rol.built_index)) return -1;            // no look at the lists between ticks: the index exists before the first one
   const mnav_loc::State& L = ctx->loc;
   Batch B{};
-  if (staging_upload(ctx, n, pos, dir, up, face_in, slots, seed_faces, maps, B)) return -1;
-  if (goal_pos) {
-    HIPCHK(hipMemcpyAsync(R.goal_pos, goal_pos, 12 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(R.goal_dir, goal_dir, 12 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  if (staging_upload(ctx, n, A.pos, A.dir, A.up, A.face_in, A.slots, A.seed_faces, maps, B)) return -1;
+  if (A.goal_pos) {
+    HIPCHK(hipMemcpyAsync(R.goal_pos, A.goal_pos, 12 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(R.goal_dir, A.goal_dir, 12 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
   }
-  if (start_tick) HIPCHK(hipMemcpyAsync(S.start_tick, start_tick, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  if (A.start_tick) HIPCHK(hipMemcpyAsync(S.start_tick, A.start_tick, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
   else if (yielding) HIPCHK(hipMemsetAsync(S.start_tick, 0, 4 * (size_t)n, ctx->stream));   // FleetTick's start ticks are never null
   std::vector<uint8_t> h_hold;                                        // hold_in as flags; lives until the synchronise of the first block
   HIPCHK(hipMemsetAsync(R.status, 0, 4 * (size_t)n, ctx->stream));    // kRunning
@@ -203,12 +209,12 @@ static int rollout_run(mnav_ctx* ctx, const char* tag, mnav_rol::Stats& stats, m
   HIPCHK(hipMemsetAsync(R.cnt, 0, sizeof(uint32_t) * kCounters * (size_t)ticks, ctx->stream));    // every tick's row, once
   B.pos = G.pos; B.dir = G.dir; B.up = G.up; B.face = G.face; B.cnt = R.cnt;
   B.status = R.status; B.ticks = R.ticks; B.travel = R.travel; B.cost_integral = R.cost_integral; B.min_goal_dist = R.min_goal_dist;
-  B.goal_pos = goal_pos ? R.goal_pos.get() : nullptr; B.goal_dir = goal_pos ? R.goal_dir.get() : nullptr;
+  B.goal_pos = A.goal_pos ? R.goal_pos.get() : nullptr; B.goal_dir = A.goal_pos ? R.goal_dir.get() : nullptr;
   B.trace = rows ? R.trace.get() : nullptr; B.trace_rows = rows;
-  const uint32_t* d_start = start_tick || yielding ? S.start_tick.get() : nullptr;
+  const uint32_t* d_start = A.start_tick || yielding ? S.start_tick.get() : nullptr;
   Sep Q{};
   Yld YQ{};
-  if (separation) {
+  if (A.separation) {
     HIPCHK(hipMemsetAsync(S.near_checks, 0, 4 * (size_t)n, ctx->stream));                          // sep_row_start
     HIPCHK(hipMemsetAsync(S.max_partners, 0, 4 * (size_t)n, ctx->stream));
     HIPCHK(hipMemsetAsync(S.first_near_tick, 0xFF, 4 * (size_t)n, ctx->stream));
@@ -223,23 +229,23 @@ static int rollout_run(mnav_ctx* ctx, const char* tag, mnav_rol::Stats& stats, m
     Q.rows = Rows{ S.near_checks, S.max_partners, S.first_near_tick, S.first_near_robot, S.min_sep2, S.min_sep_tick, S.min_sep_robot };
   }
   if (yielding) {
-    if (yld.hold_in) {                                                // any non-zero byte is 1
-      h_hold.assign(yld.hold_in, yld.hold_in + n);
+    if (A.yld.hold_in) {                                              // any non-zero byte is 1
+      h_hold.assign(A.yld.hold_in, A.yld.hold_in + n);
       for (auto& b : h_hold) b = b != 0;
       HIPCHK(hipMemcpyAsync(Y.hold, h_hold.data(), n, hipMemcpyHostToDevice, ctx->stream));
     } else HIPCHK(hipMemsetAsync(Y.hold, 0, n, ctx->stream));
-    if (yld.priority) HIPCHK(hipMemcpyAsync(Y.priority, yld.priority, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    if (A.yld.priority) HIPCHK(hipMemcpyAsync(Y.priority, A.yld.priority, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemsetAsync(Y.hold_checks, 0, 4 * (size_t)n, ctx->stream));                           // yld_row_start
     HIPCHK(hipMemsetAsync(Y.held_ticks, 0, 4 * (size_t)n, ctx->stream));
     HIPCHK(hipMemsetAsync(Y.first_hold_tick, 0xFF, 4 * (size_t)n, ctx->stream));
     HIPCHK(hipMemsetAsync(Y.first_hold_robot, 0xFF, 4 * (size_t)n, ctx->stream));
     HIPCHK(hipMemsetAsync(Y.ychk, 0, sizeof(uint32_t) * kYldCheckWords * (size_t)checks, ctx->stream));
-    YQ.c2 = ahead_c2; YQ.dir = G.dir; YQ.priority = yld.priority ? Y.priority.get() : nullptr; YQ.hold = Y.hold; YQ.ychk = Y.ychk;
+    YQ.c2 = ahead_c2; YQ.dir = G.dir; YQ.priority = A.yld.priority ? Y.priority.get() : nullptr; YQ.hold = Y.hold; YQ.ychk = Y.ychk;
     YQ.rows = YRows{ Y.hold_checks, Y.held_ticks, Y.first_hold_tick, Y.first_hold_robot };
   }
   mnav_fol::Config C;
-  std::memcpy(&C, config, sizeof(C));
-  const Params P{ rollout->dt, (float)rollout->dist_tolerance, (float)rollout->angle_tolerance, goal_pos != nullptr };
+  std::memcpy(&C, A.config, sizeof(C));
+  const Params P{ A.rollout->dt, (float)A.rollout->dist_tolerance, (float)A.rollout->angle_tolerance, A.goal_pos != nullptr };
   const WalkMesh M{ ctx->d_xyz, ctx->d_faces, ctx->d_vf_ptr, ctx->d_vf, ctx->V, ctx->F };
   const mnav_loc::Index I{ L.nodes, L.pts, L.n_pts, L.n_leaves, mnav_loc::loc_root(L.n_leaves) };
   const uint32_t g_stay = (n + kStayBlock - 1) / kStayBlock, g_search = n < 2048u ? n : 2048u;
@@ -265,7 +271,7 @@ static int rollout_run(mnav_ctx* ctx, const char* tag, mnav_rol::Stats& stats, m
         hipLaunchKernelGGL(mnav_rol::k_rollout_search, dim3(g_search), dim3(64), 0, ctx->stream, B, M, C, P, t, row);
         hipLaunchKernelGGL(mnav_rol::k_rollout_global, dim3(g_global), dim3(mnav_loc::kLocBlock), 0, ctx->stream, B, M, C, P, I, t, row);
       }
-      if (!separation || (t + 1) % check_stride) continue;
+      if (!A.separation || (t + 1) % check_stride) continue;
       const uint32_t check = (t + 1) / check_stride - 1;
       HIPCHK(hipEventRecord(S.ev[2 * in_block], ctx->stream));
       hipLaunchKernelGGL(k_sep_clear, dim3(g_clear), dim3(kSepBlock), 0, ctx->stream, Q);
@@ -293,31 +299,31 @@ static int rollout_run(mnav_ctx* ctx, const char* tag, mnav_rol::Stats& stats, m
   uint32_t done = 0;
   const int rc = mnav_rol::rol_blocks(ticks, run_block, [&] { return ctx->cancel.load(std::memory_order_relaxed) != 0; }, &done);
   if (rc < 0) return -1;
-  const uint32_t checks_done = separation ? done / check_stride : 0;
+  const uint32_t checks_done = A.separation ? done / check_stride : 0;
   std::vector<uint32_t> cnt((size_t)kCounters * done);
   std::vector<uint64_t> chk((size_t)kCheckWords * checks_done);
   std::vector<uint32_t> h_near, h_robot; std::vector<float> h_min;
   std::vector<uint32_t> ychk((size_t)kYldCheckWords * (yielding ? checks_done : 0)), h_hold_checks, h_held_ticks;
   HIPCHK(hipMemcpyAsync(cnt.data(), R.cnt, sizeof(uint32_t) * cnt.size(), hipMemcpyDeviceToHost, ctx->stream));
-  if (status_out) HIPCHK(hipMemcpyAsync(status_out, R.status, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-  if (ticks_out) HIPCHK(hipMemcpyAsync(ticks_out, R.ticks, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-  if (pos_out) HIPCHK(hipMemcpyAsync(pos_out, G.pos, 12 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-  if (dir_out) HIPCHK(hipMemcpyAsync(dir_out, G.dir, 12 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-  if (face_out) HIPCHK(hipMemcpyAsync(face_out, G.face, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-  if (travel_out) HIPCHK(hipMemcpyAsync(travel_out, R.travel, 8 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-  if (cost_integral_out) HIPCHK(hipMemcpyAsync(cost_integral_out, R.cost_integral, 8 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-  if (min_goal_dist_out) HIPCHK(hipMemcpyAsync(min_goal_dist_out, R.min_goal_dist, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-  if (rows) HIPCHK(hipMemcpyAsync(trace_out, R.trace, 12 * (size_t)n * rows, hipMemcpyDeviceToHost, ctx->stream));   // (rows past a cancel are not written)
-  if (separation) {
+  if (A.out.status) HIPCHK(hipMemcpyAsync(A.out.status, R.status, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  if (A.out.ticks) HIPCHK(hipMemcpyAsync(A.out.ticks, R.ticks, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  if (A.out.pos) HIPCHK(hipMemcpyAsync(A.out.pos, G.pos, 12 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  if (A.out.dir) HIPCHK(hipMemcpyAsync(A.out.dir, G.dir, 12 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  if (A.out.face) HIPCHK(hipMemcpyAsync(A.out.face, G.face, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  if (A.out.travel) HIPCHK(hipMemcpyAsync(A.out.travel, R.travel, 8 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  if (A.out.cost_integral) HIPCHK(hipMemcpyAsync(A.out.cost_integral, R.cost_integral, 8 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  if (A.out.min_goal_dist) HIPCHK(hipMemcpyAsync(A.out.min_goal_dist, R.min_goal_dist, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  if (rows) HIPCHK(hipMemcpyAsync(A.out.trace, R.trace, 12 * (size_t)n * rows, hipMemcpyDeviceToHost, ctx->stream));   // (rows past a cancel are not written)
+  if (A.separation) {
     h_near.resize(n); h_robot.resize(n); h_min.resize(n);             // the statistics read three of the rows' columns
     if (checks_done) HIPCHK(hipMemcpyAsync(chk.data(), S.chk, sizeof(uint64_t) * chk.size(), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipMemcpyAsync(h_near.data(), S.near_checks, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipMemcpyAsync(h_min.data(), S.min_sep2, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipMemcpyAsync(h_robot.data(), S.min_sep_robot, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    if (sep_out.max_partners) HIPCHK(hipMemcpyAsync(sep_out.max_partners, S.max_partners, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    if (sep_out.first_near_tick) HIPCHK(hipMemcpyAsync(sep_out.first_near_tick, S.first_near_tick, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    if (sep_out.first_near_robot) HIPCHK(hipMemcpyAsync(sep_out.first_near_robot, S.first_near_robot, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    if (sep_out.min_sep_tick) HIPCHK(hipMemcpyAsync(sep_out.min_sep_tick, S.min_sep_tick, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    if (A.sep_out.max_partners) HIPCHK(hipMemcpyAsync(A.sep_out.max_partners, S.max_partners, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    if (A.sep_out.first_near_tick) HIPCHK(hipMemcpyAsync(A.sep_out.first_near_tick, S.first_near_tick, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    if (A.sep_out.first_near_robot) HIPCHK(hipMemcpyAsync(A.sep_out.first_near_robot, S.first_near_robot, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    if (A.sep_out.min_sep_tick) HIPCHK(hipMemcpyAsync(A.sep_out.min_sep_tick, S.min_sep_tick, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
   }
   if (yielding) {
     h_hold_checks.resize(n); h_held_ticks.resize(n); h_hold.resize(n); // the statistics read two of the yield rows' columns and the flags
@@ -325,27 +331,27 @@ static int rollout_run(mnav_ctx* ctx, const char* tag, mnav_rol::Stats& stats, m
     HIPCHK(hipMemcpyAsync(h_hold_checks.data(), Y.hold_checks, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipMemcpyAsync(h_held_ticks.data(), Y.held_ticks, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipMemcpyAsync(h_hold.data(), Y.hold, n, hipMemcpyDeviceToHost, ctx->stream));
-    if (yld.out.first_hold_tick) HIPCHK(hipMemcpyAsync(yld.out.first_hold_tick, Y.first_hold_tick, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    if (yld.out.first_hold_robot) HIPCHK(hipMemcpyAsync(yld.out.first_hold_robot, Y.first_hold_robot, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    if (A.yld.out.first_hold_tick) HIPCHK(hipMemcpyAsync(A.yld.out.first_hold_tick, Y.first_hold_tick, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    if (A.yld.out.first_hold_robot) HIPCHK(hipMemcpyAsync(A.yld.out.first_hold_robot, Y.first_hold_robot, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
   }
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  mnav_rol::rol_fold_counters(cnt.data(), done, n, stats);
-  if (separation) {
-    sep_fold(chk.data(), checks_done, check_stride, n, h_near.data(), h_min.data(), h_robot.data(), sep_stats);
-    if (sep_out.near_checks) std::memcpy(sep_out.near_checks, h_near.data(), 4 * (size_t)n);
-    if (sep_out.min_sep2) std::memcpy(sep_out.min_sep2, h_min.data(), 4 * (size_t)n);
-    if (sep_out.min_sep_robot) std::memcpy(sep_out.min_sep_robot, h_robot.data(), 4 * (size_t)n);
+  mnav_rol::rol_fold_counters(cnt.data(), done, n, rec.rol);
+  if (A.separation) {
+    sep_fold(chk.data(), checks_done, check_stride, n, h_near.data(), h_min.data(), h_robot.data(), rec.sep);
+    if (A.sep_out.near_checks) std::memcpy(A.sep_out.near_checks, h_near.data(), 4 * (size_t)n);
+    if (A.sep_out.min_sep2) std::memcpy(A.sep_out.min_sep2, h_min.data(), 4 * (size_t)n);
+    if (A.sep_out.min_sep_robot) std::memcpy(A.sep_out.min_sep_robot, h_robot.data(), 4 * (size_t)n);
   }
   if (yielding) {
-    if (yld.stats) yld_fold(chk.data(), ychk.data(), checks_done, check_stride, n, h_hold_checks.data(), h_held_ticks.data(), h_hold.data(), *yld.stats);
-    if (yld.out.hold_checks) std::memcpy(yld.out.hold_checks, h_hold_checks.data(), 4 * (size_t)n);
-    if (yld.out.held_ticks) std::memcpy(yld.out.held_ticks, h_held_ticks.data(), 4 * (size_t)n);
-    if (yld.hold_out) std::memcpy(yld.hold_out, h_hold.data(), n);
+    yld_fold(chk.data(), ychk.data(), checks_done, check_stride, n, h_hold_checks.data(), h_held_ticks.data(), h_hold.data(), rec.yld);
+    if (A.yld.out.hold_checks) std::memcpy(A.yld.out.hold_checks, h_hold_checks.data(), 4 * (size_t)n);
+    if (A.yld.out.held_ticks) std::memcpy(A.yld.out.held_ticks, h_held_ticks.data(), 4 * (size_t)n);
+    if (A.yld.hold_out) std::memcpy(A.yld.hold_out, h_hold.data(), n);
   }
-  stats.ms_kernels = ms_kernels; sep_stats.ms_separation = ms_separation;
-  stats.ms_total = (float)(1e-3 * (double)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count());
-  if (yld.stats) { yld.stats->ms_pair = ms_pair; yld.stats->ms_separation = ms_separation; yld.stats->ms_kernels = ms_kernels; yld.stats->ms_total = stats.ms_total; }
-  return rc ? rc : sep_stats.checks_skipped ? 2 : 0;
+  rec.rol.ms_kernels = ms_kernels; rec.sep.ms_separation = ms_separation;
+  rec.rol.ms_total = (float)(1e-3 * (double)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count());
+  rec.yld.ms_pair = ms_pair; rec.yld.ms_separation = ms_separation; rec.yld.ms_kernels = ms_kernels; rec.yld.ms_total = rec.rol.ms_total;
+  return rc ? rc : rec.sep.checks_skipped ? 2 : 0;
 }
 
 int mnav_follow_rollout(mnav_ctx* ctx, uint32_t n, const float* pos, const float* dir, const float* up, const uint32_t* face_in, const uint32_t* slots,
@@ -354,9 +360,9 @@ int mnav_follow_rollout(mnav_ctx* ctx, uint32_t n, const float* pos, const float
                         double* travel_out, double* cost_integral_out, float* min_goal_dist_out, float* trace_out)
 {
   if (!ctx) return -1;
-  mnav_frol::SepStats no_checks;                                      // nothing reads it: mnav_rollout_stats tells of no check
-  return rollout_run(ctx, "rollout", ctx->rol_stats, no_checks, n, pos, dir, up, face_in, slots, seed_faces, goal_pos, goal_dir, config, rollout, nullptr, nullptr,
-                     status_out, ticks_out, pos_out, dir_out, face_out, travel_out, cost_integral_out, min_goal_dist_out, trace_out, mnav_frol::Rows{}, YieldCall{});
+  return rollout_run(ctx, RolloutCall{ "rollout", &ctx->rol_rec, n, pos, dir, up, face_in, slots, seed_faces, goal_pos, goal_dir, config, rollout, nullptr, nullptr,
+                                       { status_out, ticks_out, pos_out, dir_out, face_out, travel_out, cost_integral_out, min_goal_dist_out, trace_out },
+                                       mnav_frol::Rows{}, YieldCall{} });
 }
 
 int mnav_fleet_rollout(mnav_ctx* ctx, uint32_t n, const float* pos, const float* dir, const float* up, const uint32_t* face_in, const uint32_t* slots,
@@ -367,10 +373,10 @@ int mnav_fleet_rollout(mnav_ctx* ctx, uint32_t n, const float* pos, const float*
                        uint32_t* first_near_robot_out, float* min_sep2_out, uint32_t* min_sep_tick_out, uint32_t* min_sep_robot_out)
 {
   if (!ctx) return -1;
-  return rollout_run(ctx, "fleet rollout", ctx->frol_stats, ctx->frol_sep_stats, n, pos, dir, up, face_in, slots, seed_faces, goal_pos, goal_dir, config, rollout,
-                     start_tick, separation, status_out, ticks_out, pos_out, dir_out, face_out, travel_out, cost_integral_out, min_goal_dist_out, trace_out,
-                     mnav_frol::Rows{ near_checks_out, max_partners_out, first_near_tick_out, first_near_robot_out, min_sep2_out, min_sep_tick_out, min_sep_robot_out },
-                     YieldCall{});
+  return rollout_run(ctx, RolloutCall{ "fleet rollout", &ctx->frol_rec, n, pos, dir, up, face_in, slots, seed_faces, goal_pos, goal_dir, config, rollout, start_tick,
+                                       separation, { status_out, ticks_out, pos_out, dir_out, face_out, travel_out, cost_integral_out, min_goal_dist_out, trace_out },
+                                       { near_checks_out, max_partners_out, first_near_tick_out, first_near_robot_out, min_sep2_out, min_sep_tick_out, min_sep_robot_out },
+                                       YieldCall{} });
 }
 
 int mnav_fleet_rollout_yield(mnav_ctx* ctx, uint32_t n, const float* pos, const float* dir, const float* up, const uint32_t* face_in, const uint32_t* slots,
@@ -383,12 +389,10 @@ int mnav_fleet_rollout_yield(mnav_ctx* ctx, uint32_t n, const float* pos, const 
                              uint32_t* held_ticks_out, uint32_t* first_hold_tick_out, uint32_t* first_hold_robot_out)
 {
   if (!ctx) return -1;
-  YieldCall Y;
-  Y.config = yield; Y.priority = priority; Y.hold_in = hold_in; Y.hold_out = hold_out;
-  Y.out = mnav_frol::YRows{ hold_checks_out, held_ticks_out, first_hold_tick_out, first_hold_robot_out }; Y.stats = &ctx->yld_stats;
-  return rollout_run(ctx, "fleet rollout yield", ctx->yld_rol_stats, ctx->yld_sep_stats, n, pos, dir, up, face_in, slots, seed_faces, goal_pos, goal_dir, config, rollout,
-                     start_tick, separation, status_out, ticks_out, pos_out, dir_out, face_out, travel_out, cost_integral_out, min_goal_dist_out, trace_out,
-                     mnav_frol::Rows{ near_checks_out, max_partners_out, first_near_tick_out, first_near_robot_out, min_sep2_out, min_sep_tick_out, min_sep_robot_out }, Y);
+  return rollout_run(ctx, RolloutCall{ "fleet rollout yield", &ctx->yld_rec, n, pos, dir, up, face_in, slots, seed_faces, goal_pos, goal_dir, config, rollout, start_tick,
+                                       separation, { status_out, ticks_out, pos_out, dir_out, face_out, travel_out, cost_integral_out, min_goal_dist_out, trace_out },
+                                       { near_checks_out, max_partners_out, first_near_tick_out, first_near_robot_out, min_sep2_out, min_sep_tick_out, min_sep_robot_out },
+                                       YieldCall{ yield, priority, hold_in, hold_out, { hold_checks_out, held_ticks_out, first_hold_tick_out, first_hold_robot_out } } });
 }
 
 // the first eight values of both *_stats functions
@@ -409,7 +413,7 @@ int mnav_rollout_stats(const mnav_ctx* ctx, uint32_t* status_counts, uint64_t* r
                        uint32_t* built_index, float* ms_kernels, float* ms_total)
 {
   if (!ctx) return -1;
-  rollout_stats_get(ctx->rol_stats, status_counts, robot_ticks, stayed, neighbour, global, built_index, ms_kernels, ms_total);
+  rollout_stats_get(ctx->rol_rec.rol, status_counts, robot_ticks, stayed, neighbour, global, built_index, ms_kernels, ms_total);
   return 0;
 }
 
@@ -419,8 +423,8 @@ int mnav_fleet_rollout_stats(const mnav_ctx* ctx, uint32_t* status_counts, uint6
                              uint32_t* max_cell, float* ms_separation, float* ms_kernels, float* ms_total)
 {
   if (!ctx) return -1;
-  rollout_stats_get(ctx->frol_stats, status_counts, robot_ticks, stayed, neighbour, global, built_index, ms_kernels, ms_total);
-  const mnav_frol::SepStats& S = ctx->frol_sep_stats;
+  rollout_stats_get(ctx->frol_rec.rol, status_counts, robot_ticks, stayed, neighbour, global, built_index, ms_kernels, ms_total);
+  const mnav_frol::SepStats& S = ctx->frol_rec.sep;
   if (checks_run) *checks_run = S.checks_run;
   if (checks_skipped) *checks_skipped = S.checks_skipped;
   if (first_skipped_tick) *first_skipped_tick = S.first_skipped_tick;
@@ -440,7 +444,7 @@ int mnav_fleet_yield_stats(const mnav_ctx* ctx, uint32_t* robots_held, uint64_t*
                            uint32_t* checks_run, uint32_t* checks_skipped, uint32_t* first_skipped_tick, float* ms_pair, float* ms_separation, float* ms_kernels, float* ms_total)
 {
   if (!ctx) return -1;
-  const mnav_frol::YldStats& S = ctx->yld_stats;
+  const mnav_frol::YldStats& S = ctx->yld_rec.yld;
   if (robots_held) *robots_held = S.robots_held;
   if (held_ticks) *held_ticks = S.held_ticks;
   if (max_held) *max_held = S.max_held;

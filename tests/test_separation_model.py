@@ -1,7 +1,7 @@
 """The fleet rollout without a GPU: mesh_navigation_amd/csrc/mnav_fleet_rollout.h compiled for the host (g++
 -ffp-contract=off, the flags of the library) -- the rule (frol_waits, sep_present, sep_d2, sep_meet, sep_close) and the grid
-search (sep_range, sep_insert, sep_find, sep_visit) are the device's own source, sep_check_host composes them serially --
-against tests/separation_model.py, the O(n^2) numpy restatement of the specification.  Point sets built to break a grid, each
+search (sep_range, sep_insert, sep_find, sep_cells, sep_tests, sep_near) are the device's own source, sep_check_host composes
+them serially -- against tests/separation_model.py, the O(n^2) numpy restatement of the specification.  Point sets built to break a grid, each
 at separation_cell_scale 1.0, the default and 4.0 and at two table sizes; presence under the four flag combinations; the tie
 rules; the guard's count; the departure equivalences of include/mnav.h on a mesh; and the fold of a call's check rows into
 its statistics (sep_fold) against the model's and on tables written by hand.  Every comparison is exact."""

@@ -122,6 +122,8 @@ def build_shim(tmp_path_factory):
     L.yld_ahead_of.argtypes = [vp, vp, vp, f32]
     L.yld_cos_ok.restype = C.c_int
     L.yld_cos_ok.argtypes = [C.c_double]
+    L.sep_check.restype = C.c_int
+    L.sep_check.argtypes = [u32, vp, vp, vp, u32, u32, f32, f32, u32, C.c_uint64] + [vp] * 8
     L.yld_check.restype = C.c_int
     L.yld_check.argtypes = [u32] + [vp] * 5 + [u32, u32, f32, f32, f32, u32, C.c_uint64] + [vp] * 14
     L.yrol_batch.argtypes = [vp, u32] + [vp] * 8 + [u32] * 4 + [vp] * 15 + [vp, f32, f32, u32, u32, C.c_uint64] + [vp] * 8 + [f32] + [vp] * 7
@@ -287,20 +289,26 @@ def test_only_the_first_check_that_holds_gives_tick_and_blocker(shim):
         assert (yrows["hold_checks"][0], yrows["first_hold_tick"][0], yrows["first_hold_robot"][0]) == (2, 6, 1)
 
 
+def random_fleet(rng, n=257):
+    """n robots in a box a few radii (0.25) wide: positions, headings, statuses, start ticks, priorities"""
+    pos = rng.uniform(-1.2, 1.2, (n, 3)).astype(F32) * np.array([1, 1, 0.3], F32)             # about four partners each
+    a = rng.uniform(0, 2 * np.pi, n)
+    d = np.stack([np.cos(a), np.sin(a), rng.uniform(-0.2, 0.2, n)], axis=1).astype(F32)
+    status = rng.choice([RM.RUNNING] * 5 + [RM.REACHED, RM.OUT_OF_MAP, RM.NO_FIELD], n).astype(np.int32)
+    start = rng.choice([0, 0, 0, 3, 50], n).astype(np.uint32)
+    prio = rng.integers(0, 4, n).astype(np.uint32)
+    pos[5], d[9] = pos[4], np.array([np.nan, 0, 0], F32)                                     # a coincident pair, a NaN heading
+    for k in range(20, 36, 2):                                        # eight head-on pairs beside the box: the larger index has right of way
+        pos[k], pos[k + 1], d[k], d[k + 1] = [5 + k, 0, 0], [5.1 + k, 0, 0], X, -X
+        status[k:k + 2], start[k:k + 2], prio[k:k + 2] = RM.RUNNING, 0, (3, 0)
+    return pos, d, status, start, prio
+
+
 def test_257_random_robots_in_a_box_a_few_radii_wide(shim):
     rng = np.random.default_rng(21)
     n, r = 257, 0.25
     for trial, (c, flags) in enumerate(((0.5, 3), (0.0, 0), (0.95, 1))):
-        pos = rng.uniform(-1.2, 1.2, (n, 3)).astype(F32) * np.array([1, 1, 0.3], F32)         # about four partners each
-        a = rng.uniform(0, 2 * np.pi, n)
-        d = np.stack([np.cos(a), np.sin(a), rng.uniform(-0.2, 0.2, n)], axis=1).astype(F32)
-        status = rng.choice([RM.RUNNING] * 5 + [RM.REACHED, RM.OUT_OF_MAP, RM.NO_FIELD], n).astype(np.int32)
-        start = rng.choice([0, 0, 0, 3, 50], n).astype(np.uint32)
-        prio = rng.integers(0, 4, n).astype(np.uint32)
-        pos[5], d[9] = pos[4], np.array([np.nan, 0, 0], F32)                                 # a coincident pair, a NaN heading
-        for k in range(20, 36, 2):                                    # eight head-on pairs beside the box: the larger index has right of way
-            pos[k], pos[k + 1], d[k], d[k + 1] = [5 + k, 0, 0], [5.1 + k, 0, 0], X, -X
-            status[k:k + 2], start[k:k + 2], prio[k:k + 2] = RM.RUNNING, 0, (3, 0)
+        pos, d, status, start, prio = random_fleet(rng, n)
         holds = []
         for priority in (prio, None):
             hold, y = both(shim, pos, d, r, c, status=status, start_tick=start, priority=priority, tick=10, flags=flags, what=("random", trial))
@@ -318,6 +326,29 @@ def test_a_skipped_check_releases_everybody(shim):
         YM.assert_same_yield(dict(yrows, hold=hold), dict(YM.start_yrows(2), hold=np.zeros(2, np.uint8)), "skipped")
         SM.assert_same_rows(rows, SM.start_rows(2), "skipped")
         assert host_check(shim, pos, d, 0.3, 0.5, scale, max_tests=4)[2].tolist() == [1, 0]    # T == the bound: served
+
+
+def test_the_separation_outputs_are_those_of_the_check_without_the_rule(shim):
+    """yld_check_host and sep_check_host run one grid and one check loop: for the same inputs the seven separation rows and
+    the four words of the check's row are equal bit for bit -- no robot, one robot, the 257 random robots at every cell
+    scale, and a check that the guard skips in both (max_tests = 0)."""
+    pos, d, status, start, prio = random_fleet(np.random.default_rng(21))
+    one = slice(0, 1)
+    cases = [("nobody", slice(0, 0), 2.0, 2 ** 63), ("one robot", one, 2.0, 2 ** 63), ("skipped", slice(None), 2.0, 0)]
+    cases += [(("random", scale), slice(None), scale, 2 ** 63) for scale in SCALES]
+    for what, sl, scale, max_tests in cases:
+        p, n = np.ascontiguousarray(pos[sl]), pos[sl].shape[0]
+        y_rows, _, hold, y_chk, _, y_ran = host_check(shim, p, d[sl], 0.25, 0.5, scale, status[sl], start[sl], prio[sl], tick=10, flags=3, max_tests=max_tests)
+        rows, chk = SM.start_rows(n), np.full(4, 77, np.uint64)
+        ran = shim.sep_check(n, _p(p), _p(np.ascontiguousarray(status[sl])), _p(np.ascontiguousarray(start[sl])), 10, 3, 0.25, scale, shim.sep_table_size(n),
+                             max_tests, *[_p(rows[k]) for k in SM.SEP_KEYS], _p(chk))
+        assert y_ran == bool(ran) == (max_tests != 0 or n == 0), what
+        assert y_chk.tobytes() == chk.tobytes(), (what, y_chk, chk)
+        for k in SM.SEP_KEYS:
+            assert y_rows[k].dtype == rows[k].dtype and y_rows[k].tobytes() == rows[k].tobytes(), (what, k)
+        if not ran:
+            assert int(chk[3]) == 1 and not hold.any(), what
+    assert int(chk[1]) > 0                                            # the last case met partners: the rows compared are not the start rows
 
 
 # -- a convoy on a mesh: the whole call ----------------------------------------------------------------------------------
