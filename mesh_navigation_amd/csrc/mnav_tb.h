@@ -991,6 +991,7 @@ struct TbBatch {
   // plans; per (tile, block of 64 plans) the plans whose slot arrays hold the unreached pattern, and the pairs the last pass skipped
   uint32_t d_clean_np = 0;
   DevBuf<unsigned long long> umap, uskip, fin_cnt; uint32_t umap_stride = 0;
+  DevBuf<uint8_t> cnt8;                 // settled vertices per (tile, plan), rows of cap_np bytes (FinTb::cnt8); allocated by the first finalize pass that counts in bytes
   uint32_t keep_np = 0;                 // tb_fields_upload: leading slots whose previous pass wrote through the same pointers under a standing claim
   bool fin_stats = false, fin_reset = false, filled_at_start = false; uint32_t fin_np = 0;   // the last call, for mnav_tb_finalize_stats
 };

@@ -40,7 +40,22 @@ struct FinTb {
   // reached slice it has loaded, so that the call leaves A.D as a fill would.
   unsigned long long* umap; unsigned long long* uskip;
   uint32_t umap_stride, umap_prev_np, clean_d;
+  // cnt8[tile * cnt8_stride + plan], one byte (null: one atomicAdd per reached pair onto res[plan].settled): the settled vertices
+  // of the pair, <= T.  Lane plan % 64 keeps the count, the wave stores the bytes of a block of 64 plans when the block ends (0 for
+  // an unreached pair), k_tb_fin_settled sums a plan's tiles behind the pass -- no word that every wave writes.
+  uint8_t* cnt8; uint32_t cnt8_stride;
 };
+
+// settled vertices per plan from the per-pair counts of the pass (FinTb::cnt8): a thread per plan walks a share of the tiles (rows
+// of `stride` bytes: a workgroup reads 256 adjacent bytes per tile), one atomicAdd per thread with a count
+__global__ __launch_bounds__(kBlock) void k_tb_fin_settled(const uint8_t* __restrict__ cnt8, uint32_t ntiles, uint32_t np, uint32_t stride, PlanResult* __restrict__ res)
+{
+  const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
+  if (p >= np) return;
+  uint32_t c = 0;
+  for (uint32_t t = blockIdx.y; t < ntiles; t += gridDim.y) c += cnt8[(size_t)t * stride + p];
+  if (c) atomicAdd(&res[p].settled, (unsigned long long)c);
+}
 
 // popcounts of the two maps of the last pass over the words of its nblk blocks of plans: out[0] unreached pairs, out[1] skipped pairs
 __global__ __launch_bounds__(kBlock) void k_tb_fin_count(const unsigned long long* __restrict__ umap, const unsigned long long* __restrict__ uskip, uint32_t ntiles,
@@ -207,7 +222,7 @@ __global__ __launch_bounds__(64 * kFinWaves, MNAV_FIN_OCC) void k_tb_finalize(tb
   uint32_t cur[4], nxt[4], rcur, rnxt;
   load_slice(p_beg, rcur, cur);
   rnxt = rcur;
-  uint32_t bad = 0;
+  uint32_t bad = 0, cnt8v = 0;
   // A slice beyond the 256 slots of cur[]: a tile that is a column through several sheets of a folded mesh, never one of a terrain.
   // Read through the first lane, so that what the tail costs a short slice is one scalar branch where it is handled.
   const bool long_slice = (uint32_t)__builtin_amdgcn_readfirstlane((int)W.sl) > 256u;
@@ -367,8 +382,12 @@ __global__ __launch_bounds__(64 * kFinWaves, MNAV_FIN_OCC) void k_tb_finalize(tb
       }
     }
     cnt = wave_sum(cnt);
-    if (lane == 0 && cnt && live) atomicAdd(&F.res[p].settled, (unsigned long long)cnt);
+    if (F.cnt8) cnt8v = (uint32_t)lane == (p & 63u) ? cnt : cnt8v;      // (the sum is in every lane)
+    else if (lane == 0 && cnt && live) atomicAdd(&F.res[p].settled, (unsigned long long)cnt);
     if ((p & 63u) == 63u || p + 1 == p_end) {                          // the block of 64 plans ends: its words (bits beyond NP stay 0)
+      if (F.cnt8 && live && (uint32_t)lane <= (p & 63u))
+        as_global(F.cnt8)[(size_t)tb::rfl(t) * F.cnt8_stride + (p & ~63u) + (uint32_t)lane] = (uint8_t)cnt8v;
+      cnt8v = 0;
       if (lane == 0 && live) { g_umap[p >> 6] = ubits; g_uskip[p >> 6] = uskipped; }
       ubits = 0ull; uskipped = 0ull;
       uprev = (p + 1 < p_end && p + 1 < F.umap_prev_np) ? g_umap[(p + 1) >> 6] : 0ull;

@@ -239,6 +239,12 @@ int tb_fields(mnav_ctx* ctx, uint32_t n, const tb::Args& A)
   static_assert(MNAV_FIN_PPW % 64u == 0u, "a wave of k_tb_finalize owns whole words of the map of unreached pairs");
   F.plans_per_wave = MNAV_FIN_PPW; F.tiles_per_xcd = (groups + 7u) / 8u; F.max_sl = S.max_sl;
   F.umap = S.umap; F.uskip = S.uskip; F.umap_stride = S.umap_stride; F.umap_prev_np = S.keep_np; F.clean_d = S.fin_reset ? 1u : 0u;
+  // settled vertices: a byte per (tile, plan) summed behind the pass instead of an atomicAdd per reached pair (option tb_fin_cnt8);
+  // the bytes live with the batch state from the first pass that wants them (paths-only contexts never do)
+  if (opt_u32(ctx->opt.tb_fin_cnt8, 1u) != 0u && S.ntiles) {
+    if (!S.cnt8) HIPCHK(S.cnt8.alloc((size_t)S.ntiles * S.cap_np + 64));
+    F.cnt8 = S.cnt8; F.cnt8_stride = S.cap_np;
+  }
   hipLaunchKernelGGL(k_tb_fin_plans, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, A, ctx->d_plans, F.vecmaps, S.d_recs);
   const uint32_t npg = (n + F.plans_per_wave - 1u) / F.plans_per_wave;
   const size_t lds = 4 * (size_t)fin_lds_words(S.max_sl, F.vecmaps != nullptr) * kFinWaves;
@@ -247,6 +253,7 @@ int tb_fields(mnav_ctx* ctx, uint32_t n, const tb::Args& A)
   else if (S.T == 96) hipLaunchKernelGGL((k_tb_finalize<96>), grid, dim3(64 * kFinWaves), lds, ctx->stream, A, F);
   else if (S.T == 120) hipLaunchKernelGGL((k_tb_finalize<120>), grid, dim3(64 * kFinWaves), lds, ctx->stream, A, F);
   else hipLaunchKernelGGL((k_tb_finalize<128>), grid, dim3(64 * kFinWaves), lds, ctx->stream, A, F);
+  if (F.cnt8) hipLaunchKernelGGL(k_tb_fin_settled, dim3((n + kBlock - 1) / kBlock, 64), dim3(kBlock), 0, ctx->stream, F.cnt8, S.ntiles, n, F.cnt8_stride, ctx->d_res);
   HIPCHK(hipGetLastError());
   return 0;
 }
