@@ -734,8 +734,8 @@ typedef struct mnav_yield_config {
  * that is not fed back stands in nobody's way any more).
  * WHAT THE RULE DOES NOT PROMISE.  It is right of way, not avoidance: the velocity command is never changed, and a robot with
  * right of way drives on, into a held robot if that is where its field leads.  A ring of followers, each behind the next, can
- * hold each other for good; nothing resolves that deadlock, mnav_fleet_yield_stats shows it (robots held after the last
- * check, held robot-ticks).
+ * hold each other for good; this call does not resolve that deadlock, mnav_fleet_yield_stats shows it (robots held after the
+ * last check, held robot-ticks).  mnav_fleet_rollout_rings, below, tells such rings from harmless queues and releases them.
  * Returns 0, 1 and 2 as mnav_fleet_rollout, or -1 with mnav_last_error set and NOTHING touched: every refusal of
  * mnav_fleet_rollout, yield given without separation, an ahead_cos whose float is not finite or outside 0 <= c < 1, a non-zero
  * flag, priority, hold_in, hold_out or a yield output given without yield.  n = 0 does nothing.  The call has statistics
@@ -760,6 +760,84 @@ int mnav_fleet_rollout_yield(mnav_ctx* ctx, uint32_t n, const float* pos, const 
  * NULL. */
 int mnav_fleet_yield_stats(const mnav_ctx* ctx, uint32_t* robots_held, uint64_t* held_ticks, uint32_t* max_held, uint32_t* max_held_tick,
                            uint32_t* held_last, uint32_t* checks_run, uint32_t* checks_skipped, uint32_t* first_skipped_tick, float* ms_pair, float* ms_separation, float* ms_kernels, float* ms_total);
+
+/* -- wait-for analysis of a yielding fleet rollout: why a robot is held, rings found and released ---------
+ * mnav_fleet_rollout_yield holds robots and cannot say why.  Three cases look alike in its outputs: a stop-and-go queue behind
+ * a robot that still drives, a queue behind a robot that stands for good where a presence flag keeps it, and a ring of robots
+ * that wait for each other -- a deadlock.  mnav_fleet_rollout_rings classifies every held robot at every check, on the device,
+ * and can release one robot of every ring. */
+#define MNAV_RING_RELEASE 1u      /* the leader of every ring is released at the check that finds the ring */
+typedef struct mnav_ring_config {
+  uint32_t flags;       /* MNAV_RING_* or 0 */
+} mnav_ring_config;
+#define MNAV_WAIT_FREE        0u  /* not held by the rule at that check */
+#define MNAV_WAIT_QUEUED      1u  /* its chain ends at a robot that is not held and is a MOVER */
+#define MNAV_WAIT_PARKED      2u  /* its chain ends at a robot that is not held and is no mover */
+#define MNAV_WAIT_RING_TAIL   3u  /* its chain runs into a ring it is not part of */
+#define MNAV_WAIT_RING_MEMBER 4u  /* it lies on a ring */
+/* Every argument up to first_hold_robot_out is mnav_fleet_rollout_yield's, in its order and with its meaning; then the ring group.
+ * RINGS IS NULL.  Then the six ring outputs must be NULL too, every output is mnav_fleet_rollout_yield's bit for bit, and the
+ * call launches the very kernels that call launches.
+ * RINGS IS GIVEN.  yield (and so separation) must be given.  With flags = 0 the state, the trace, the separation outputs and
+ * the yield outputs are mnav_fleet_rollout_yield's bit for bit; only the ring outputs are new.
+ * THE RULE applies at a check that ran, after the decision of mnav_fleet_rollout_yield:
+ *   hold0[i] is the flag the right-of-way rule gives robot i;
+ *   b[i] is robot i's BLOCKER at this check: the yielded-to partner with the smallest d2, ties to the smallest index -- the
+ *     definition of first_hold_robot_out, applied at every check;
+ *   w(i) = b[i] if hold0[i], else i.
+ * b[i] != i, and b[i] is present.  Two robots never yield to each other: A(i, j) && A(j, i) would need before(j, i) &&
+ * before(i, j), and a robot that is no mover is never held.  So every cycle of w other than a fixed point has at least three
+ * robots: the smallest ring is a triangle.
+ * The CHAIN of i is i, w(i), w(w(i)), ...  It ends at a fixed point, or it enters a cycle.  The fixed point is its ROOT, a robot
+ * that is not held.  A RING is a cycle.  A ring's LEADER is its member with the smallest (priority, index), the order of before.
+ * The CLASS of robot i is MNAV_WAIT_FREE if !hold0[i]; MNAV_WAIT_QUEUED if its chain ends at a root that is a mover at this
+ * check; MNAV_WAIT_PARKED if it ends at a root that is no mover (waiting, REACHED or stranded, kept present); MNAV_WAIT_RING_MEMBER
+ * if i lies on a ring; MNAV_WAIT_RING_TAIL if its chain enters a ring i is not part of.  anchor[i] is the root for QUEUED and
+ * PARKED, the ring's leader for RING_TAIL and RING_MEMBER, MNAV_NONE for FREE.
+ * The analysis follows the nearest blocker only.  A robot may yield to more partners; the classes describe that one graph.
+ * RELEASE, with MNAV_RING_RELEASE: after the classification hold[leader] = 0 for every ring, every other flag is hold0.  The
+ * released robot has controller ticks until the next check, whatever else it yielded to; tails and the other members stay
+ * held.  Without the flag hold = hold0.  The check stays a function of the state after its tick and reads no flag of the check
+ * before: nothing oscillates within a check, and every run and every separation_cell_scale gives the same bits.
+ * A check that the guard skips leaves every class FREE, every anchor MNAV_NONE, and counts nothing.
+ * Per robot, over the checks of this call (any pointer may be NULL; all of them must be NULL when rings is NULL):
+ *   wait_class_out        n bytes: the class at the last check of the call (FREE if no check ran)
+ *   wait_anchor_out       the anchor at the last check of the call (MNAV_NONE if no check ran)
+ *   ring_checks_out       checks at which the robot was RING_MEMBER
+ *   first_ring_tick_out   the tick of the first such check, or MNAV_NONE
+ *   parked_checks_out     checks at which the robot was PARKED
+ *   released_checks_out   checks at which it was released as a leader
+ * THE YIELD OUTPUTS UNDER RELEASE.  hold_checks_out and first_hold_tick_out / first_hold_robot_out count the checks at which
+ * the rule held the robot (hold0), released or not.  held_ticks_out and hold_out follow the flags as they stand after the
+ * release, and so do the robots held after the last check.
+ * RESUMING works through hold_out -> hold_in exactly as in mnav_fleet_rollout_yield; nothing new is fed back.
+ * Returns 0, 1 and 2 as mnav_fleet_rollout_yield, or -1 with mnav_last_error set and NOTHING touched: every refusal of
+ * mnav_fleet_rollout_yield, rings given without yield, an unknown ring flag bit, a ring output given without rings.  The
+ * call has a statistics record of its own (mnav_fleet_ring_stats): it leaves mnav_rollout_stats, mnav_fleet_rollout_stats and
+ * mnav_fleet_yield_stats as they were, and those calls leave mnav_fleet_ring_stats.  DESIGN.md section 3.22. */
+int mnav_fleet_rollout_rings(mnav_ctx* ctx, uint32_t n, const float* pos, const float* dir, const float* up, const uint32_t* face_in,
+                             const uint32_t* slots, const uint32_t* seed_faces, const float* goal_pos, const float* goal_dir,
+                             const mnav_follow_config* config, const mnav_rollout_config* rollout, const uint32_t* start_tick,
+                             const mnav_separation_config* separation, int32_t* status_out, uint32_t* ticks_out, float* pos_out,
+                             float* dir_out, uint32_t* face_out, double* travel_out, double* cost_integral_out,
+                             float* min_goal_dist_out, float* trace_out, uint32_t* near_checks_out, uint32_t* max_partners_out,
+                             uint32_t* first_near_tick_out, uint32_t* first_near_robot_out, float* min_sep2_out,
+                             uint32_t* min_sep_tick_out, uint32_t* min_sep_robot_out, const mnav_yield_config* yield,
+                             const uint32_t* priority, const uint8_t* hold_in, uint8_t* hold_out, uint32_t* hold_checks_out,
+                             uint32_t* held_ticks_out, uint32_t* first_hold_tick_out, uint32_t* first_hold_robot_out,
+                             const mnav_ring_config* rings, uint8_t* wait_class_out, uint32_t* wait_anchor_out, uint32_t* ring_checks_out,
+                             uint32_t* first_ring_tick_out, uint32_t* parked_checks_out, uint32_t* released_checks_out);
+/* The last mnav_fleet_rollout_rings: robots with ring_checks > 0; the rings summed over the checks run; the most rings at one
+ * check and that check's tick (the first such check among those run; 0 and MNAV_NONE without a check run); the releases summed
+ * over the checks; RING_MEMBER, RING_TAIL, PARKED and QUEUED robots and rings at the last check of the call (all 0 when the
+ * guard skipped it or no check ran); the checks run and skipped and the tick of the first skipped check, as
+ * mnav_fleet_rollout_stats counts them; device milliseconds of the kernels of the analysis behind the pair passes, of all
+ * kernels of the checks, of all kernels, and host milliseconds of the whole call.  All 0 / MNAV_NONE after a call with
+ * rings = NULL, except the times.  Any pointer may be NULL. */
+int mnav_fleet_ring_stats(const mnav_ctx* ctx, uint32_t* robots_ring, uint64_t* rings, uint32_t* max_rings, uint32_t* max_rings_tick,
+                          uint64_t* releases, uint32_t* members_last, uint32_t* tails_last, uint32_t* parked_last, uint32_t* queued_last,
+                          uint32_t* rings_last, uint32_t* checks_run, uint32_t* checks_skipped, uint32_t* first_skipped_tick,
+                          float* ms_ring, float* ms_separation, float* ms_kernels, float* ms_total);
 
 /* -- fleet paths and walks: many robots per resident field ---------------------------------------------
  * A Dijkstra call returns one vertex path per plan, from the plan's seed (the goal) to its one target.  The field is seeded

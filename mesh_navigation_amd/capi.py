@@ -37,7 +37,7 @@ SYMBOLS = [
     "mnav_layer_border", "mnav_layer_clearance", "mnav_clearance_download", "mnav_clearance_stats",
     "mnav_locate", "mnav_locate_stats", "mnav_plan_dijkstra_batch_at", "mnav_plan_cvp_batch_at",
     "mnav_follow_batch", "mnav_follow_stats", "mnav_follow_rollout", "mnav_rollout_stats", "mnav_fleet_rollout", "mnav_fleet_rollout_stats",
-    "mnav_fleet_rollout_yield", "mnav_fleet_yield_stats",
+    "mnav_fleet_rollout_yield", "mnav_fleet_yield_stats", "mnav_fleet_rollout_rings", "mnav_fleet_ring_stats",
     "mnav_map_configure", "mnav_map_compute", "mnav_map_layer_changed", "mnav_map_update_layer", "mnav_map_obstacle", "mnav_map_stats",
     "mnav_replan_dijkstra_batch", "mnav_replan_plans", "mnav_replan_stats", "mnav_replan_dijkstra_each", "mnav_replan_each_stats",
     "mnav_replan_warm_stats",
@@ -134,6 +134,19 @@ class YieldConfig(C.Structure):
         super().__init__(**{**self.DEFAULTS, **kw})
 
 
+class RingConfig(C.Structure):
+    """mnav_ring_config (include/mnav.h): the MNAV_RING_* flags of the wait-for analysis of a yielding fleet rollout."""
+    _fields_ = [("flags", C.c_uint32)]
+    DEFAULTS = dict(flags=0)
+
+    def __init__(self, **kw):
+        super().__init__(**{**self.DEFAULTS, **kw})
+
+
+RING_RELEASE = 1
+WAIT_FREE, WAIT_QUEUED, WAIT_PARKED, WAIT_RING_TAIL, WAIT_RING_MEMBER = 0, 1, 2, 3, 4
+
+
 class MapNode(C.Structure):
     """mnav_map_node (include/mnav.h): one node of the resident layer graph"""
     _fields_ = [("layer", C.c_uint32), ("kind", C.c_uint32), ("n_inputs", C.c_uint32), ("inputs", C.c_uint32 * 8),
@@ -198,6 +211,19 @@ class FleetYieldOut(FleetRolloutOut):
     first_hold_robot: np.ndarray | None = None
 
 
+@dataclass
+class FleetRingOut(FleetYieldOut):
+    """One mnav_fleet_rollout_rings call: FleetYieldOut and the ring outputs, one row per robot (None without a ring config
+    or where not asked for).  `wait_class` (WAIT_*) and `wait_anchor` are those of the last check of the call."""
+    wait_class: np.ndarray | None = None       # (n,) uint8
+    wait_anchor: np.ndarray | None = None
+    ring_checks: np.ndarray | None = None
+    first_ring_tick: np.ndarray | None = None
+    parked_checks: np.ndarray | None = None
+    released_checks: np.ndarray | None = None
+
+
+RING_OUTPUTS = ("wait_class", "wait_anchor", "ring_checks", "first_ring_tick", "parked_checks", "released_checks")
 YIELD_OUTPUTS = ("hold", "hold_checks", "held_ticks", "first_hold_tick", "first_hold_robot")
 SEPARATION_OUTPUTS = ("near_checks", "max_partners", "first_near_tick", "first_near_robot", "min_sep2", "min_sep_tick", "min_sep_robot")
 
@@ -261,6 +287,10 @@ def load(path: str | None = None):
     L.mnav_fleet_rollout_yield.argtypes = L.mnav_fleet_rollout.argtypes + [C.POINTER(YieldConfig)] + [vp] * 7
     L.mnav_fleet_yield_stats.restype = C.c_int
     L.mnav_fleet_yield_stats.argtypes = [vp] + [vp] * 12
+    L.mnav_fleet_rollout_rings.restype = C.c_int
+    L.mnav_fleet_rollout_rings.argtypes = L.mnav_fleet_rollout_yield.argtypes + [C.POINTER(RingConfig)] + [vp] * 6
+    L.mnav_fleet_ring_stats.restype = C.c_int
+    L.mnav_fleet_ring_stats.argtypes = [vp] + [vp] * 17
     L.mnav_rollout_stats.restype = C.c_int
     L.mnav_rollout_stats.argtypes = [vp, C.POINTER(u32 * 4)] + [C.POINTER(C.c_uint64)] * 4 + [C.POINTER(u32)] + [C.POINTER(C.c_float)] * 2
     L.mnav_map_configure.restype = C.c_int
@@ -1597,7 +1627,7 @@ class MnavContext:
 
     def fleet_rollout_yield(self, pos, direction, up, face_in, slots, seed_faces=None, goal_pos=None, goal_dir=None, config: FollowConfig | None = None,
                             rollout: RolloutConfig | None = None, start_tick=None, separation: SeparationConfig | None = None,
-                            yield_config: YieldConfig | None = None, priority=None, hold_in=None, outputs=None) -> FleetYieldOut:
+                            yield_config: YieldConfig | None = None, priority=None, hold_in=None, outputs=None, _rings=None) -> FleetYieldOut:
         """fleet_rollout() in which a robot that has to yield to a partner ahead of it has no tick until the next check
         (mnav_fleet_rollout_yield, include/mnav.h).  yield_config None: fleet_rollout() bit for bit.  priority: n uint32 or
         None (the index decides); hold_in: n bytes or None, the `hold` of the call this one resumes.  `outputs`: the names of
@@ -1611,13 +1641,19 @@ class MnavContext:
         y = {k: (np.zeros(n, np.uint8 if k == "hold" else np.uint32) if yield_config is not None and k in want else None) for k in YIELD_OUTPUTS}
         tail = [None if yield_config is None else C.byref(yield_config), _p(prio), _p(hin), *[_p(y[k]) for k in YIELD_OUTPUTS]]
 
-        def fn(*args):
-            return self._L.mnav_fleet_rollout_yield(*args, *tail)
+        if _rings is None:
+            def fn(*args):
+                return self._L.mnav_fleet_rollout_yield(*args, *tail)
 
-        fn.__name__ = "mnav_fleet_rollout_yield"
+            fn.__name__ = "mnav_fleet_rollout_yield"
+        else:                                                             # fleet_rollout_rings(): the same call with the ring group behind
+            def fn(*args):
+                return self._L.mnav_fleet_rollout_rings(*args, *tail, *_rings)
+
+            fn.__name__ = "mnav_fleet_rollout_rings"
         o, rc = self._rollout("fleet_rollout_yield", fn, pos, direction, up, face_in, slots, [seed_faces, start_tick],
                               "seed_faces / start_tick need one entry per robot", goal_pos, goal_dir, config, rollout,
-                              None if outputs is None else [k for k in outputs if k not in YIELD_OUTPUTS],
+                              None if outputs is None else [k for k in outputs if k not in YIELD_OUTPUTS + RING_OUTPUTS],
                               more=[None if separation is None else C.byref(separation)],
                               extra={k: np.float32 if k == "min_sep2" else np.uint32 for k in SEPARATION_OUTPUTS}, with_extra=separation is not None)
         return FleetYieldOut(**o, **y, cancelled=rc == 1, skipped=rc == 2)
@@ -1629,6 +1665,30 @@ class MnavContext:
                 ("ms_kernels", f32), ("ms_total", f32)]
         v = {k: t() for k, t in spec}
         self._L.mnav_fleet_yield_stats(self._h, *[C.byref(v[k]) for k, _ in spec])
+        return {k: v[k].value for k, _ in spec}
+
+    def fleet_rollout_rings(self, pos, direction, up, face_in, slots, seed_faces=None, goal_pos=None, goal_dir=None, config: FollowConfig | None = None,
+                            rollout: RolloutConfig | None = None, start_tick=None, separation: SeparationConfig | None = None,
+                            yield_config: YieldConfig | None = None, priority=None, hold_in=None, ring_config: RingConfig | None = None, outputs=None) -> FleetRingOut:
+        """fleet_rollout_yield() with a wait-for analysis behind every check: the class of every held robot (queued, parked,
+        tail or member of a ring), its anchor, and with RING_RELEASE the release of every ring's leader
+        (mnav_fleet_rollout_rings, include/mnav.h).  ring_config None: fleet_rollout_yield() bit for bit.  `outputs`: the names
+        of the FleetRingOut fields to fetch (default: all; the ring outputs only with `ring_config`)."""
+        n = int(_f32(pos).reshape(-1, 3).shape[0])
+        want = set(RING_OUTPUTS) if outputs is None else set(outputs) & set(RING_OUTPUTS)
+        r = {k: (np.full(n, 0xFFFFFFFF if k == "wait_anchor" else 0, np.uint8 if k == "wait_class" else np.uint32) if ring_config is not None and k in want else None)
+             for k in RING_OUTPUTS}
+        y = self.fleet_rollout_yield(pos, direction, up, face_in, slots, seed_faces, goal_pos, goal_dir, config, rollout, start_tick, separation, yield_config, priority,
+                                     hold_in, outputs, _rings=[None if ring_config is None else C.byref(ring_config), *[_p(r[k]) for k in RING_OUTPUTS]])
+        return FleetRingOut(**{k: getattr(y, k) for k in FleetYieldOut.__dataclass_fields__}, **r)
+
+    def fleet_ring_stats(self) -> dict:
+        u64, u32, f32 = C.c_uint64, C.c_uint32, C.c_float
+        spec = [("robots_ring", u32), ("rings", u64), ("max_rings", u32), ("max_rings_tick", u32), ("releases", u64), ("members_last", u32), ("tails_last", u32),
+                ("parked_last", u32), ("queued_last", u32), ("rings_last", u32), ("checks_run", u32), ("checks_skipped", u32), ("first_skipped_tick", u32),
+                ("ms_ring", f32), ("ms_separation", f32), ("ms_kernels", f32), ("ms_total", f32)]
+        v = {k: t() for k, t in spec}
+        self._L.mnav_fleet_ring_stats(self._h, *[C.byref(v[k]) for k, _ in spec])
         return {k: v[k].value for k, _ in spec}
 
     def plan_dijkstra_batch_at(self, goal_pos, start_pos, goal_dist_offset: float = 0.3, cost_limit: float = 1.0,

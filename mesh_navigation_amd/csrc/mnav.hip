@@ -87,6 +87,7 @@ constexpr int kChunk = 96;  // step launches per graph replay; multiple of 6 (sl
 #include "mnav_rollout.h"    // device rollouts: many controller ticks per call over resident robot state (mnav_rol::)
 #include "mnav_fleet_rollout.h"   // fleet rollouts: a departure tick per robot and the separation check between robots (mnav_frol::)
 #include "mnav_fleet_yield.h"     // ... in which robots yield: the right-of-way rule inside the check's pair pass, held robots without a tick (mnav_frol::)
+#include "mnav_fleet_ring.h"      // ... and learn why they are held: the wait-for analysis behind the pair pass, the release of rings (mnav_frol::)
 #include "mnav_replan.h"     // replan on a resident potential: rewind level from the change log, rewind with the tiles' wake-up words (k_replan_*)
 #include "mnav_replan_each.h"  // the per-plan replan: class of every plan, ordered lists, compacted records (k_replan_classify, k_replan_gather)
 #include "mnav_tb_warm.h"    // warm start of the tile-batch engine from rewound fields: every slice and pending word of a sub-batch (k_tb_warm)
@@ -245,9 +246,10 @@ struct mnav_ctx {
   DevBuf<float> d_fnrm; bool have_face_normals = false;            // MeshMap::faceNormals() (mnav_upload_face_normals): F x 3, gone with the mesh
   mnav_rol::Dev rol;                                               // device rollouts, both entry points: the rest of the resident robot state, goals, counter rows, trace
   mnav_frol::State frol;                                           // fleet rollout: start ticks, the separation check's table, records, rows and check rows, its event pairs
-  struct RolloutRecord { mnav_rol::Stats rol; mnav_frol::SepStats sep; mnav_frol::YldStats yld; };   // what one rollout entry point's *_stats tell of its last call
-  RolloutRecord rol_rec, frol_rec, yld_rec;                        // mnav_follow_rollout, mnav_fleet_rollout, mnav_fleet_rollout_yield: kept apart
+  struct RolloutRecord { mnav_rol::Stats rol; mnav_frol::SepStats sep; mnav_frol::YldStats yld; mnav_frol::RingStats ring; };   // what one rollout entry point's *_stats tell of its last call
+  RolloutRecord rol_rec, frol_rec, yld_rec, ring_rec;              // mnav_follow_rollout, mnav_fleet_rollout, mnav_fleet_rollout_yield, mnav_fleet_rollout_rings: kept apart
   mnav_frol::YldState yld;                                         // yielding fleet rollout: hold flags, priorities, yield rows and check rows, the pair passes' event pairs
+  mnav_frol::RingState ring;                                       // wait-for analysis: blockers, the doubling's buffers, marks, ring rows and check rows, its event pairs
   mnav_chg::Scratch chg;                                           // obstacle / clearance / border layers: change list and counters of the last call
   mnav_map::State map;                                             // resident layer graph (mnav_map_*): nodes, tables, change lists of the last update
   uint32_t infl_steps = 0, infl_bands = 0; uint64_t infl_evals = 0; float infl_ms = 0.f, infl_ms_wave = 0.f;   // last inflation wave
@@ -1876,7 +1878,7 @@ uint32_t mnav_plan_cvp_batch(mnav_ctx* ctx, uint32_t n, const float* seed_pos, c
 #include "mnav_clearance_capi.h"  // mnav_layer_clearance, mnav_layer_border, mnav_clearance_download, mnav_clearance_stats
 #include "mnav_locate_capi.h"     // mnav_locate, mnav_locate_stats, mnav_plan_dijkstra_batch_at, mnav_plan_cvp_batch_at
 #include "mnav_follow_capi.h"     // mnav_follow_batch, mnav_follow_stats
-#include "mnav_rollout_capi.h"    // mnav_follow_rollout, mnav_rollout_stats, mnav_fleet_rollout, mnav_fleet_rollout_stats, mnav_fleet_rollout_yield, mnav_fleet_yield_stats
+#include "mnav_rollout_capi.h"    // mnav_follow_rollout, mnav_rollout_stats, mnav_fleet_rollout, mnav_fleet_rollout_stats, mnav_fleet_rollout_yield, mnav_fleet_yield_stats, mnav_fleet_rollout_rings, mnav_fleet_ring_stats
 #include "mnav_graph_capi.h"      // mnav_map_configure / _compute / _layer_changed / _update_layer / _obstacle / _stats
 #include "mnav_replan_capi.h"     // mnav_replan_dijkstra_batch, mnav_replan_stats
 #include "mnav_replan_each_capi.h"   // mnav_replan_dijkstra_each, mnav_replan_each_stats

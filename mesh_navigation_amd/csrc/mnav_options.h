@@ -47,7 +47,8 @@
   X(schedule_chunk_rounds) /* fleet schedule: rounds enqueued between two looks of the host at the control record (default 8; the result does not depend on it) */ \
   X(schedule_clean_fill) /* fleet schedule: 1 = the tentative arrays are filled between the rounds, 0 = the claimants clean their own words in the commit pass (default 0; the result does not depend on it) */ \
   X(separation_cell_scale) /* fleet rollout: side of the separation check's grid cells in radii, 1 .. 4 (default 2; the result does not depend on it) */ \
-  X(separation_max_tests) /* fleet rollout: a check whose pair pass would perform more distance tests than this is skipped (default 2^32, provisional: DESIGN.md section 3.20) */
+  X(separation_max_tests) /* fleet rollout: a check whose pair pass would perform more distance tests than this is skipped (default 2^32, provisional: DESIGN.md section 3.20) */ \
+  X(ring_early_exit)     /* fleet rollout rings: 1 = a round of the doubling whose earlier rounds already cover the robots held returns at once, 0 (default, measured: DESIGN.md section 3.22) = every round runs (the result does not depend on it) */
 
 struct Options {
 #define X(name) double name = NAN;

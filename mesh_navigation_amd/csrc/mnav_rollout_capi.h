@@ -1,14 +1,17 @@
 // mnav_rollout_capi.h -- the C ABI of the device rollouts (include/mnav.h: mnav_follow_rollout, mnav_rollout_stats,
-// mnav_fleet_rollout, mnav_fleet_rollout_stats, mnav_fleet_rollout_yield, mnav_fleet_yield_stats) over the kernels of
-// mnav_rollout.h, mnav_fleet_rollout.h and mnav_fleet_yield.h.  Included by
+// mnav_fleet_rollout, mnav_fleet_rollout_stats, mnav_fleet_rollout_yield, mnav_fleet_yield_stats, mnav_fleet_rollout_rings,
+// mnav_fleet_ring_stats) over the kernels of mnav_rollout.h, mnav_fleet_rollout.h, mnav_fleet_yield.h and mnav_fleet_ring.h.  Included by
 // mnav.hip inside its extern "C" block, after mnav_follow_capi.h (the argument checks are the follower's) and
-// mnav_locate_capi.h (the index build is the lookup's own).  One driver, rollout_run, holds the call; the three entry points
+// mnav_locate_capi.h (the index build is the lookup's own).  One driver, rollout_run, holds the call; the four entry points
 // hand it one RolloutCall with their arguments and their own statistics record.  The device buffers are shared (a call uploads every input at
 // entry), the statistics are kept apart: a call of one entry point leaves what the other's *_stats tells alone.
 #pragma once
 
 static_assert(mnav_frol::kWaitingPresent == MNAV_SEP_WAITING_PRESENT && mnav_frol::kReachedPresent == MNAV_SEP_REACHED_PRESENT,
               "mnav_fleet_rollout.h restates the values of include/mnav.h");
+static_assert(mnav_frol::kRingRelease == MNAV_RING_RELEASE && mnav_frol::kWaitFree == MNAV_WAIT_FREE && mnav_frol::kWaitQueued == MNAV_WAIT_QUEUED &&
+              mnav_frol::kWaitParked == MNAV_WAIT_PARKED && mnav_frol::kWaitRingTail == MNAV_WAIT_RING_TAIL && mnav_frol::kWaitRingMember == MNAV_WAIT_RING_MEMBER,
+              "mnav_fleet_ring.h restates the values of include/mnav.h");
 
 // (the counter rows' message names the entry point, the others the rollout, as callers have seen them)
 static int rollout_reserve(mnav_ctx* ctx, const char* tag, size_t n, bool goals, size_t ticks, size_t trace_floats)
@@ -95,11 +98,43 @@ static int fleet_yield_reserve(mnav_ctx* ctx, size_t n, size_t checks)
   return 0;
 }
 
+// what the wait-for analysis needs beside the rule's buffers
+static int fleet_ring_reserve(mnav_ctx* ctx, size_t n, size_t checks)
+{
+  mnav_frol::RingState& W = ctx->ring;
+  const char* oom = "fleet rollout rings: out of device memory";
+  if (!W.have_ev) {
+    for (auto& e : W.ev) HIPCHK(hipEventCreate(e.out()));
+    W.have_ev = true;
+  }
+  if (n > W.cap) {
+    W.cap = 0;
+    if (alloc_group(W.blocker, 4 * n, W.jump0, 4 * n, W.jump1, 4 * n, W.key0, 8 * n, W.key1, 8 * n, W.mark, n, W.wait_class, n, W.anchor, 4 * n, W.ring_checks, 4 * n,
+                    W.first_ring_tick, 4 * n, W.parked_checks, 4 * n, W.released_checks, 4 * n) != hipSuccess) {
+      ctx->err = oom; return -1;
+    }
+    W.cap = n;
+  }
+  if (checks > W.chk_cap) {
+    W.chk_cap = 0;
+    if (W.rchk.alloc(sizeof(uint32_t) * mnav_frol::kRingCheckWords * checks) != hipSuccess) { ctx->err = oom; return -1; }
+    W.chk_cap = checks;
+  }
+  return 0;
+}
+
 // The optional last input of rollout_run: the right-of-way rule of mnav_fleet_rollout_yield.  config null: no rule, and then
 // every other pointer must be null; host pointers, each output may be null.
 struct YieldCall {
   const mnav_yield_config* config = nullptr; const uint32_t* priority = nullptr; const uint8_t* hold_in = nullptr; uint8_t* hold_out = nullptr;
   mnav_frol::YRows out = { nullptr, nullptr, nullptr, nullptr };
+};
+
+// ... and behind it the wait-for analysis of mnav_fleet_rollout_rings.  config null: no analysis, and then every output must be
+// null; host pointers, each output may be null.
+struct RingCall {
+  const mnav_ring_config* config = nullptr;
+  mnav_frol::RRows out = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
 };
 
 // One call of rollout_run, as its entry point fills it.  tag names the entry point in the messages that do, rec is the record
@@ -112,7 +147,7 @@ struct RolloutCall {
   const float* goal_pos; const float* goal_dir; const mnav_follow_config* config; const mnav_rollout_config* rollout;
   const uint32_t* start_tick; const mnav_separation_config* separation;
   struct { int32_t* status; uint32_t* ticks; float* pos; float* dir; uint32_t* face; double* travel; double* cost_integral; float* min_goal_dist; float* trace; } out;
-  mnav_frol::Rows sep_out; YieldCall yld;
+  mnav_frol::Rows sep_out; YieldCall yld; RingCall ring;
 };
 
 // The argument checks of a rollout beside the follower's, all on the host: -1 with ctx->err set, or 0.
@@ -176,6 +211,15 @@ static int rollout_run(mnav_ctx* ctx, const RolloutCall& A)
     if (A.yld.config->flags) { ctx->err = "fleet rollout yield: the flags of the yield config are reserved and must be 0"; return -1; }
     ahead_c2 = c * c;
   }
+  const bool rings = A.ring.config != nullptr;
+  if (!rings) {
+    if (A.ring.out.ring_checks || A.ring.out.first_ring_tick || A.ring.out.parked_checks || A.ring.out.released_checks || A.ring.out.wait_class || A.ring.out.anchor) {
+      ctx->err = "fleet rollout rings: a ring output without a ring config"; return -1;
+    }
+  } else {
+    if (!yielding) { ctx->err = "fleet rollout rings: a ring config without a yield config"; return -1; }
+    if (A.ring.config->flags & ~kRingKnownFlags) { ctx->err = "fleet rollout rings: unknown ring flag"; return -1; }
+  }
   const uint32_t checks = A.separation ? ticks / check_stride : 0, table = A.separation ? sep_table_size(n) : 0;
   const double max_tests_d = opt_set(ctx->opt.separation_max_tests) ? std::max(ctx->opt.separation_max_tests, 0.0) : kDefaultMaxTests;
   const unsigned long long max_tests = max_tests_d >= 18446744073709551615.0 ? ~0ull : (unsigned long long)max_tests_d;
@@ -183,10 +227,12 @@ static int rollout_run(mnav_ctx* ctx, const RolloutCall& A)
   cancel_reset(ctx);                                                  // as the plan calls do
   if (upload_walk_mesh(ctx)) return -1;
   if (staging_reserve(ctx, n, ctx->res.plans(), A.tag) || rollout_reserve(ctx, A.tag, n, A.goal_pos != nullptr, ticks, 3 * (size_t)n * rows) ||
-      fleet_rollout_reserve(ctx, n, A.start_tick != nullptr || yielding, A.separation != nullptr, table, checks) || (yielding && fleet_yield_reserve(ctx, n, checks))) return -1;
+      fleet_rollout_reserve(ctx, n, A.start_tick != nullptr || yielding, A.separation != nullptr, table, checks) || (yielding && fleet_yield_reserve(ctx, n, checks)) ||
+      (rings && fleet_ring_reserve(ctx, n, checks))) return -1;
   mnav_rol::Dev& R = ctx->rol;
   State& S = ctx->frol;
   YldState& Y = ctx->yld;
+  RingState& W = ctx->ring;
   mnav_fol::Staging& G = ctx->stage;
   mnav_ctx::RolloutRecord& rec = *A.rec;
   rec = {};
@@ -214,6 +260,7 @@ static int rollout_run(mnav_ctx* ctx, const RolloutCall& A)
   const uint32_t* d_start = A.start_tick || yielding ? S.start_tick.get() : nullptr;
   Sep Q{};
   Yld YQ{};
+  Ring WQ{};
   if (A.separation) {
     HIPCHK(hipMemsetAsync(S.near_checks, 0, 4 * (size_t)n, ctx->stream));                          // sep_row_start
     HIPCHK(hipMemsetAsync(S.max_partners, 0, 4 * (size_t)n, ctx->stream));
@@ -243,6 +290,18 @@ static int rollout_run(mnav_ctx* ctx, const RolloutCall& A)
     YQ.c2 = ahead_c2; YQ.dir = G.dir; YQ.priority = A.yld.priority ? Y.priority.get() : nullptr; YQ.hold = Y.hold; YQ.ychk = Y.ychk;
     YQ.rows = YRows{ Y.hold_checks, Y.held_ticks, Y.first_hold_tick, Y.first_hold_robot };
   }
+  if (rings) {
+    HIPCHK(hipMemsetAsync(W.wait_class, 0, n, ctx->stream));                                        // kWaitFree: no check ran yet
+    HIPCHK(hipMemsetAsync(W.anchor, 0xFF, 4 * (size_t)n, ctx->stream));
+    HIPCHK(hipMemsetAsync(W.ring_checks, 0, 4 * (size_t)n, ctx->stream));
+    HIPCHK(hipMemsetAsync(W.first_ring_tick, 0xFF, 4 * (size_t)n, ctx->stream));
+    HIPCHK(hipMemsetAsync(W.parked_checks, 0, 4 * (size_t)n, ctx->stream));
+    HIPCHK(hipMemsetAsync(W.released_checks, 0, 4 * (size_t)n, ctx->stream));
+    HIPCHK(hipMemsetAsync(W.rchk, 0, sizeof(uint32_t) * kRingCheckWords * (size_t)checks, ctx->stream));
+    WQ.flags = A.ring.config->flags; WQ.early = opt_on(ctx->opt.ring_early_exit); WQ.launched = ring_launches(n);
+    WQ.blocker = W.blocker; WQ.jump[0] = W.jump0; WQ.jump[1] = W.jump1; WQ.key[0] = W.key0; WQ.key[1] = W.key1; WQ.mark = W.mark; WQ.rchk = W.rchk;
+    WQ.rows = RRows{ W.ring_checks, W.first_ring_tick, W.parked_checks, W.released_checks, W.wait_class, W.anchor };
+  }
   mnav_fol::Config C;
   std::memcpy(&C, A.config, sizeof(C));
   const Params P{ A.rollout->dt, (float)A.rollout->dist_tolerance, (float)A.rollout->angle_tolerance, A.goal_pos != nullptr };
@@ -251,7 +310,7 @@ static int rollout_run(mnav_ctx* ctx, const RolloutCall& A)
   const uint32_t g_stay = (n + kStayBlock - 1) / kStayBlock, g_search = n < 2048u ? n : 2048u;
   const uint32_t g_all = (n + mnav_loc::kLocBlock - 1) / mnav_loc::kLocBlock, g_global = g_all < 1024u ? g_all : 1024u;
   const uint32_t g_sep = (n + kSepBlock - 1) / kSepBlock, g_clear = Q.tiles < 4096u ? Q.tiles : 4096u;
-  float ms_kernels = 0.f, ms_separation = 0.f, ms_pair = 0.f;
+  float ms_kernels = 0.f, ms_separation = 0.f, ms_pair = 0.f, ms_ring = 0.f;
   // one block: plain launches, no host look in between; then one synchronise
   const auto run_block = [&](uint32_t first, uint32_t nt) -> int {
     HIPCHK(hipEventRecord(G.ev[0], ctx->stream));
@@ -280,7 +339,16 @@ static int rollout_run(mnav_ctx* ctx, const RolloutCall& A)
       hipLaunchKernelGGL(k_sep_top, dim3(1), dim3(kSepBlock), 0, ctx->stream, Q);
       hipLaunchKernelGGL(k_sep_starts, dim3(Q.tiles), dim3(kSepBlock), 0, ctx->stream, Q);
       hipLaunchKernelGGL(k_sep_fill, dim3(g_sep), dim3(kSepBlock), 0, ctx->stream, Q, check);
-      if (yielding) {
+      if (rings) {                                                    // the pair pass that keeps the blockers, then the analysis
+        HIPCHK(hipEventRecord(Y.ev[2 * in_block], ctx->stream));
+        hipLaunchKernelGGL(k_ring_pair, dim3(g_sep), dim3(kSepBlock), 0, ctx->stream, Q, YQ, WQ, check, t + 1);
+        HIPCHK(hipEventRecord(Y.ev[2 * in_block + 1], ctx->stream));
+        HIPCHK(hipEventRecord(W.ev[2 * in_block], ctx->stream));
+        for (uint32_t k = 0; k < WQ.launched; ++k) hipLaunchKernelGGL(k_ring_double, dim3(g_sep), dim3(kSepBlock), 0, ctx->stream, WQ, n, YQ.ychk, check, k);
+        hipLaunchKernelGGL(k_ring_close, dim3(g_sep), dim3(kSepBlock), 0, ctx->stream, Q, WQ, YQ.ychk, check, t + 1);
+        hipLaunchKernelGGL(k_ring_rows, dim3(g_sep), dim3(kSepBlock), 0, ctx->stream, WQ, n, YQ.hold, check, t + 1);
+        HIPCHK(hipEventRecord(W.ev[2 * in_block + 1], ctx->stream));
+      } else if (yielding) {
         HIPCHK(hipEventRecord(Y.ev[2 * in_block], ctx->stream));
         hipLaunchKernelGGL(k_yld_pair, dim3(g_sep), dim3(kSepBlock), 0, ctx->stream, Q, YQ, check, t + 1);
         HIPCHK(hipEventRecord(Y.ev[2 * in_block + 1], ctx->stream));
@@ -294,6 +362,7 @@ static int rollout_run(mnav_ctx* ctx, const RolloutCall& A)
     ms_kernels += ev_ms(G.ev[0], G.ev[1]);
     for (uint32_t k = 0; k < in_block; ++k) ms_separation += ev_ms(S.ev[2 * k], S.ev[2 * k + 1]);
     if (yielding) for (uint32_t k = 0; k < in_block; ++k) ms_pair += ev_ms(Y.ev[2 * k], Y.ev[2 * k + 1]);
+    if (rings) for (uint32_t k = 0; k < in_block; ++k) ms_ring += ev_ms(W.ev[2 * k], W.ev[2 * k + 1]);
     return 0;
   };
   uint32_t done = 0;
@@ -334,6 +403,17 @@ static int rollout_run(mnav_ctx* ctx, const RolloutCall& A)
     if (A.yld.out.first_hold_tick) HIPCHK(hipMemcpyAsync(A.yld.out.first_hold_tick, Y.first_hold_tick, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     if (A.yld.out.first_hold_robot) HIPCHK(hipMemcpyAsync(A.yld.out.first_hold_robot, Y.first_hold_robot, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
   }
+  std::vector<uint32_t> rchk((size_t)kRingCheckWords * (rings ? checks_done : 0)), h_ring_checks;
+  if (rings) {
+    h_ring_checks.resize(n);                                          // the statistics read one of the ring rows' columns
+    if (checks_done) HIPCHK(hipMemcpyAsync(rchk.data(), W.rchk, sizeof(uint32_t) * rchk.size(), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(h_ring_checks.data(), W.ring_checks, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    if (A.ring.out.first_ring_tick) HIPCHK(hipMemcpyAsync(A.ring.out.first_ring_tick, W.first_ring_tick, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    if (A.ring.out.parked_checks) HIPCHK(hipMemcpyAsync(A.ring.out.parked_checks, W.parked_checks, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    if (A.ring.out.released_checks) HIPCHK(hipMemcpyAsync(A.ring.out.released_checks, W.released_checks, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    if (A.ring.out.wait_class) HIPCHK(hipMemcpyAsync(A.ring.out.wait_class, W.wait_class, n, hipMemcpyDeviceToHost, ctx->stream));
+    if (A.ring.out.anchor) HIPCHK(hipMemcpyAsync(A.ring.out.anchor, W.anchor, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  }
   HIPCHK(hipStreamSynchronize(ctx->stream));
   mnav_rol::rol_fold_counters(cnt.data(), done, n, rec.rol);
   if (A.separation) {
@@ -348,9 +428,15 @@ static int rollout_run(mnav_ctx* ctx, const RolloutCall& A)
     if (A.yld.out.held_ticks) std::memcpy(A.yld.out.held_ticks, h_held_ticks.data(), 4 * (size_t)n);
     if (A.yld.hold_out) std::memcpy(A.yld.hold_out, h_hold.data(), n);
   }
+  if (rings) {
+    ring_fold(chk.data(), rchk.data(), checks_done, check_stride, n, h_ring_checks.data(), rec.ring);
+    if (A.ring.out.ring_checks) std::memcpy(A.ring.out.ring_checks, h_ring_checks.data(), 4 * (size_t)n);
+  }
+  rec.ring.ms_ring = ms_ring; rec.ring.ms_separation = ms_separation; rec.ring.ms_kernels = ms_kernels;
   rec.rol.ms_kernels = ms_kernels; rec.sep.ms_separation = ms_separation;
   rec.rol.ms_total = (float)(1e-3 * (double)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count());
   rec.yld.ms_pair = ms_pair; rec.yld.ms_separation = ms_separation; rec.yld.ms_kernels = ms_kernels; rec.yld.ms_total = rec.rol.ms_total;
+  rec.ring.ms_total = rec.rol.ms_total;
   return rc ? rc : rec.sep.checks_skipped ? 2 : 0;
 }
 
@@ -362,7 +448,7 @@ int mnav_follow_rollout(mnav_ctx* ctx, uint32_t n, const float* pos, const float
   if (!ctx) return -1;
   return rollout_run(ctx, RolloutCall{ "rollout", &ctx->rol_rec, n, pos, dir, up, face_in, slots, seed_faces, goal_pos, goal_dir, config, rollout, nullptr, nullptr,
                                        { status_out, ticks_out, pos_out, dir_out, face_out, travel_out, cost_integral_out, min_goal_dist_out, trace_out },
-                                       mnav_frol::Rows{}, YieldCall{} });
+                                       mnav_frol::Rows{}, YieldCall{}, RingCall{} });
 }
 
 int mnav_fleet_rollout(mnav_ctx* ctx, uint32_t n, const float* pos, const float* dir, const float* up, const uint32_t* face_in, const uint32_t* slots,
@@ -376,7 +462,7 @@ int mnav_fleet_rollout(mnav_ctx* ctx, uint32_t n, const float* pos, const float*
   return rollout_run(ctx, RolloutCall{ "fleet rollout", &ctx->frol_rec, n, pos, dir, up, face_in, slots, seed_faces, goal_pos, goal_dir, config, rollout, start_tick,
                                        separation, { status_out, ticks_out, pos_out, dir_out, face_out, travel_out, cost_integral_out, min_goal_dist_out, trace_out },
                                        { near_checks_out, max_partners_out, first_near_tick_out, first_near_robot_out, min_sep2_out, min_sep_tick_out, min_sep_robot_out },
-                                       YieldCall{} });
+                                       YieldCall{}, RingCall{} });
 }
 
 int mnav_fleet_rollout_yield(mnav_ctx* ctx, uint32_t n, const float* pos, const float* dir, const float* up, const uint32_t* face_in, const uint32_t* slots,
@@ -392,7 +478,27 @@ int mnav_fleet_rollout_yield(mnav_ctx* ctx, uint32_t n, const float* pos, const 
   return rollout_run(ctx, RolloutCall{ "fleet rollout yield", &ctx->yld_rec, n, pos, dir, up, face_in, slots, seed_faces, goal_pos, goal_dir, config, rollout, start_tick,
                                        separation, { status_out, ticks_out, pos_out, dir_out, face_out, travel_out, cost_integral_out, min_goal_dist_out, trace_out },
                                        { near_checks_out, max_partners_out, first_near_tick_out, first_near_robot_out, min_sep2_out, min_sep_tick_out, min_sep_robot_out },
-                                       YieldCall{ yield, priority, hold_in, hold_out, { hold_checks_out, held_ticks_out, first_hold_tick_out, first_hold_robot_out } } });
+                                       YieldCall{ yield, priority, hold_in, hold_out, { hold_checks_out, held_ticks_out, first_hold_tick_out, first_hold_robot_out } },
+                                       RingCall{} });
+}
+
+int mnav_fleet_rollout_rings(mnav_ctx* ctx, uint32_t n, const float* pos, const float* dir, const float* up, const uint32_t* face_in, const uint32_t* slots,
+                             const uint32_t* seed_faces, const float* goal_pos, const float* goal_dir, const mnav_follow_config* config,
+                             const mnav_rollout_config* rollout, const uint32_t* start_tick, const mnav_separation_config* separation, int32_t* status_out,
+                             uint32_t* ticks_out, float* pos_out, float* dir_out, uint32_t* face_out, double* travel_out, double* cost_integral_out,
+                             float* min_goal_dist_out, float* trace_out, uint32_t* near_checks_out, uint32_t* max_partners_out, uint32_t* first_near_tick_out,
+                             uint32_t* first_near_robot_out, float* min_sep2_out, uint32_t* min_sep_tick_out, uint32_t* min_sep_robot_out,
+                             const mnav_yield_config* yield, const uint32_t* priority, const uint8_t* hold_in, uint8_t* hold_out, uint32_t* hold_checks_out,
+                             uint32_t* held_ticks_out, uint32_t* first_hold_tick_out, uint32_t* first_hold_robot_out, const mnav_ring_config* rings,
+                             uint8_t* wait_class_out, uint32_t* wait_anchor_out, uint32_t* ring_checks_out, uint32_t* first_ring_tick_out, uint32_t* parked_checks_out,
+                             uint32_t* released_checks_out)
+{
+  if (!ctx) return -1;
+  return rollout_run(ctx, RolloutCall{ "fleet rollout rings", &ctx->ring_rec, n, pos, dir, up, face_in, slots, seed_faces, goal_pos, goal_dir, config, rollout, start_tick,
+                                       separation, { status_out, ticks_out, pos_out, dir_out, face_out, travel_out, cost_integral_out, min_goal_dist_out, trace_out },
+                                       { near_checks_out, max_partners_out, first_near_tick_out, first_near_robot_out, min_sep2_out, min_sep_tick_out, min_sep_robot_out },
+                                       YieldCall{ yield, priority, hold_in, hold_out, { hold_checks_out, held_ticks_out, first_hold_tick_out, first_hold_robot_out } },
+                                       RingCall{ rings, { ring_checks_out, first_ring_tick_out, parked_checks_out, released_checks_out, wait_class_out, wait_anchor_out } } });
 }
 
 // the first eight values of both *_stats functions
@@ -454,6 +560,32 @@ int mnav_fleet_yield_stats(const mnav_ctx* ctx, uint32_t* robots_held, uint64_t*
   if (checks_skipped) *checks_skipped = S.checks_skipped;
   if (first_skipped_tick) *first_skipped_tick = S.first_skipped_tick;
   if (ms_pair) *ms_pair = S.ms_pair;
+  if (ms_separation) *ms_separation = S.ms_separation;
+  if (ms_kernels) *ms_kernels = S.ms_kernels;
+  if (ms_total) *ms_total = S.ms_total;
+  return 0;
+}
+
+int mnav_fleet_ring_stats(const mnav_ctx* ctx, uint32_t* robots_ring, uint64_t* rings, uint32_t* max_rings, uint32_t* max_rings_tick, uint64_t* releases,
+                          uint32_t* members_last, uint32_t* tails_last, uint32_t* parked_last, uint32_t* queued_last, uint32_t* rings_last, uint32_t* checks_run,
+                          uint32_t* checks_skipped, uint32_t* first_skipped_tick, float* ms_ring, float* ms_separation, float* ms_kernels, float* ms_total)
+{
+  if (!ctx) return -1;
+  const mnav_frol::RingStats& S = ctx->ring_rec.ring;
+  if (robots_ring) *robots_ring = S.robots_ring;
+  if (rings) *rings = S.rings;
+  if (max_rings) *max_rings = S.max_rings;
+  if (max_rings_tick) *max_rings_tick = S.max_rings_tick;
+  if (releases) *releases = S.releases;
+  if (members_last) *members_last = S.members_last;
+  if (tails_last) *tails_last = S.tails_last;
+  if (parked_last) *parked_last = S.parked_last;
+  if (queued_last) *queued_last = S.queued_last;
+  if (rings_last) *rings_last = S.rings_last;
+  if (checks_run) *checks_run = S.checks_run;
+  if (checks_skipped) *checks_skipped = S.checks_skipped;
+  if (first_skipped_tick) *first_skipped_tick = S.first_skipped_tick;
+  if (ms_ring) *ms_ring = S.ms_ring;
   if (ms_separation) *ms_separation = S.ms_separation;
   if (ms_kernels) *ms_kernels = S.ms_kernels;
   if (ms_total) *ms_total = S.ms_total;
