@@ -1259,6 +1259,12 @@ int mnav_get_timing(const mnav_ctx* ctx, mnav_stats* out);
  * had to fill the distance buffer before it could start.  The pairs are counted on this call, from the maps the pass left; all
  * three are 0 after a call that ran no finalize pass except filled_at_start.  Returns 0, or -1 (mnav_last_error). */
 int mnav_tb_finalize_stats(mnav_ctx* ctx, uint64_t* skipped_pairs, uint64_t* reset_pairs, uint32_t* filled_at_start);
+/* The counters of the last run of the tile-batch engine (all 0 before the first): iterations of the engine; work items (one tile
+ * with up to 64 plans of its bucket under k_tbv_solve, up to 16 under k_tb_solve_q); activations ((tile, plan) pairs solved);
+ * Gauss-Seidel sweeps, one per item and sweep -- sweeps / items is what the option tb_sweep_seq lowers; (tile, plan) pairs woken.
+ * Concurrent waves see each other's exports sooner or later, so iterations, items and activations of the same batch differ from
+ * run to run; the results never do.  Any pointer may be null.  Returns 0, or -1 without a context. */
+int mnav_tb_engine_stats(const mnav_ctx* ctx, uint32_t* iterations, uint64_t* items, uint64_t* activations, uint64_t* sweeps, uint64_t* wakes);
 /* Band width of the wavefront engine in potential units; <= 0 selects the default
  * (3 x mean finite edge weight for the Dijkstra band steps, 12 x for CVP, recomputed on every cost
  * upload).  Results do not depend on it. */

@@ -27,7 +27,7 @@ WALK_NO_FACE = -3           # mnav_fleet_walks: no face at the start
 SYMBOLS = [
     "mnav_create", "mnav_destroy", "mnav_last_error", "mnav_set_face_circulation", "mnav_upload_mesh", "mnav_upload_costs",
     "mnav_compute_edge_weights", "mnav_combine_costs", "mnav_plan_dijkstra", "mnav_plan_cvp", "mnav_plan_dijkstra_batch", "mnav_plan_cvp_batch",
-    "mnav_cancel", "mnav_get_stats", "mnav_get_timing", "mnav_tb_finalize_stats", "mnav_set_band_width", "mnav_set_dijkstra_engine", "mnav_device_output",
+    "mnav_cancel", "mnav_get_stats", "mnav_get_timing", "mnav_tb_finalize_stats", "mnav_tb_engine_stats", "mnav_set_band_width", "mnav_set_dijkstra_engine", "mnav_device_output",
     "mnav_algorithmic_bytes", "mnav_shard_setup", "mnav_shard_setup_partition", "mnav_shard_walk", "mnav_device_bytes", "mnav_shard_info", "mnav_shard_begin", "mnav_shard_rounds", "mnav_shard_apply", "mnav_shard_rounds_async", "mnav_shard_apply_async",
     "mnav_shard_finalize", "mnav_update_costs", "mnav_update_edge_weights", "mnav_download_costs", "mnav_set_resident_outputs", "mnav_download_output",
     "mnav_vector_at", "mnav_backtrack_cvp", "mnav_backtrack_cvp_batch", "mnav_layer_upload", "mnav_layer_steepness", "mnav_layer_inflation", "mnav_layer_download",
@@ -325,6 +325,8 @@ def load(path: str | None = None):
     L.mnav_get_timing.argtypes = [vp, C.POINTER(Stats)]
     L.mnav_tb_finalize_stats.restype = C.c_int
     L.mnav_tb_finalize_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(u32)]
+    L.mnav_tb_engine_stats.restype = C.c_int
+    L.mnav_tb_engine_stats.argtypes = [vp, C.POINTER(u32)] + [C.POINTER(C.c_uint64)] * 4
     L.mnav_set_band_width.restype = C.c_int
     L.mnav_set_band_width.argtypes = [vp, C.c_float]
     L.mnav_set_dijkstra_engine.restype = C.c_int
@@ -969,6 +971,15 @@ class MnavContext:
         if self._L.mnav_tb_finalize_stats(self._h, C.byref(sk), C.byref(rs), C.byref(fl)) != 0:
             raise RuntimeError(f"mnav_tb_finalize_stats failed: {self._err()}")
         return dict(skipped_pairs=int(sk.value), reset_pairs=int(rs.value), filled_at_start=bool(fl.value))
+
+    def tb_engine_stats(self) -> dict:
+        """Counters of the last tile-batch engine run (mnav_tb_engine_stats); sweeps_per_item is what `tb_sweep_seq` lowers."""
+        it = C.c_uint32(0)
+        items, acts, sweeps, wakes = (C.c_uint64(0) for _ in range(4))
+        if self._L.mnav_tb_engine_stats(self._h, C.byref(it), C.byref(items), C.byref(acts), C.byref(sweeps), C.byref(wakes)) != 0:
+            raise RuntimeError(f"mnav_tb_engine_stats failed: {self._err()}")
+        return dict(iterations=int(it.value), items=int(items.value), activations=int(acts.value), sweeps=int(sweeps.value), wakes=int(wakes.value),
+                    sweeps_per_item=(sweeps.value / items.value) if items.value else 0.0)
 
     def last_engine(self) -> str:
         """Engine / kernel of the last Dijkstra call, by name (mnav_last_engine)."""

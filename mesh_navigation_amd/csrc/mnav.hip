@@ -1944,6 +1944,18 @@ int mnav_tb_finalize_stats(mnav_ctx* ctx, uint64_t* skipped_pairs, uint64_t* res
   return 0;
 }
 
+int mnav_tb_engine_stats(const mnav_ctx* ctx, uint32_t* iterations, uint64_t* items, uint64_t* activations, uint64_t* sweeps, uint64_t* wakes)
+{
+  if (!ctx) return -1;
+  const tb::Ctl& K = ctx->tb.last;
+  if (iterations) *iterations = K.iters;
+  if (items) *items = K.items;
+  if (activations) *activations = K.acts;
+  if (sweeps) *sweeps = K.sweeps;
+  if (wakes) *wakes = K.wakes;
+  return 0;
+}
+
 int mnav_get_timing(const mnav_ctx* ctx, mnav_stats* out)
 {
   if (!ctx || !out) return -1;

@@ -25,6 +25,7 @@
   X(tb_no_prefill) X(tb_band_mult) X(tb_waves_per_cu)                                                                                    \
   X(tb_kernel)           /* tile-batch solve: 0 = k_tb_solve_q (16 plans per quarter of a wave, distances in LDS), 1 = k_tbv_solve (64 plans per wave, distances in registers); default: by the expected plans per tile */ \
   X(tb_sched_lds)        /* tile-batch schedule pass: 0 = every carried value goes to the global copies of the plans' minima; default: a workgroup reduces its tiles' values in LDS first, while the batch's plans fit there */ \
+  X(tb_sweep_seq)        /* tile-batch solve, k_tbv_solve: 1 (default) = the sweeps of an item run the orders its lanes voted for first, most votes first, then rotate on; 0 = the most voted order, then the rotation through the other three (the result does not depend on it) */ \
   X(tb_fin_keep)         /* tile-batch finalize pass, what it keeps for the next call: bit 0 = it skips the stores of a (tile, plan) that is unreached again, bit 1 = it resets the distance buffer itself instead of a fill (default 1: measured, the reset gains no time and frees the second distance buffer; 3: both; 0: neither; the result does not depend on it) */ \
   X(tb_fin_cnt8)         /* tile-batch finalize pass, settled vertices per plan: 1 (default, measured: DESIGN.md section 3.1) = a byte per (tile, plan), stored 64 at a time and summed by a kernel behind the pass (one byte per pair of device memory, from the first such pass on); 0 = one atomicAdd per reached pair; the result does not depend on it */ \
   X(async_wg_per_cu) X(async_wg_per_plan) X(async_max_s)                                                                          \

@@ -65,6 +65,7 @@ struct Args {
   unsigned long long* wstat; uint32_t wstat_slots;                  // statistics per persistent wave {items, activations, sweeps, wakes}: k_tb_stats sums them
   uint32_t item_plans;                                               // plans per work item: 16 (a quarter of a wave, k_tb_solve_q) or 64 (a wave, k_tbv_solve)
   uint32_t sched_lds, min_copies;                                    // k_tb_sched: 1 = carried minima meet in LDS first; the arrays of mcarry in use (k_tb_plan folds them)
+  uint32_t sweep_seq;                                                // k_tbv_solve: 1 = the sweeps run the voted orders first (mnav_tbv_seq.h), 0 = the most voted order, then the rotation
 };
 
 __device__ __forceinline__ size_t slot_addr(const uint2 va, uint32_t NP, uint32_t p)

@@ -339,6 +339,7 @@ int run_dijkstra_tb(mnav_ctx* ctx, uint32_t n, const std::vector<PlanIn>& in, do
   // the schedule pass reduces the carried minima per workgroup in LDS while the plans' words fit there (mnav_tb.h)
   A.sched_lds = (tb_sched_lds_fits(n) && !(opt_set(ctx->opt.tb_sched_lds) && !opt_on(ctx->opt.tb_sched_lds))) ? 1u : 0u;
   A.min_copies = A.sched_lds ? kTbMinCopiesLds : kTbMinCopies;
+  A.sweep_seq = opt_u32(ctx->opt.tb_sweep_seq, 1u) != 0u ? 1u : 0u;
   {
     const float band_mult = (S.kernel == 1 && density < 40.0) ? 4.0f : S.band_mult;
     float band = (ctx->delta_auto / 3.0f) * std::sqrt((float)S.T) * band_mult;   // potential across one tile

@@ -22,6 +22,7 @@
 // itself is dijkstra_mesh_planner.cpp:331 (one float32 add per edge, minimum over the sources): same arithmetic, same fixed point
 // as k_tb_solve_q and every other engine, bit for bit.
 #pragma once
+#include "mnav_tbv_seq.h"
 
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Winline-asm"     // (the clobber list names v255 on purpose: the kernel's register count must cover the window)
@@ -125,26 +126,48 @@ __device__ __forceinline__ uint32_t win_read(uint32_t row)
   "Ltbv_pc" #tag "_%=:\n\t"                                                                                            \
   "v_mov_b32 v66, v62\n\t"                                                                                             \
   "Ltbv_pn" #tag "_%=:\n\t"
-// the chunk under the vector load cursor (byte offset s68 from the pass's first chunk) into ring slot `b`; cursor + 1 chunk, cyclic
-#define TBV_LOAD(b)                                                                                                    \
+// The two load cursors.  A pass reads "orders" of s74 chunks each (s75 bytes): the sweeps the four orders of the tile, in the
+// sequence s69 (mnav_tbv_seq.h: sixteen 2-bit entries); pre and post their one run of chunks, as the sequence 0, 0, 0, ...  A cursor
+// is {byte offset from the pass's first chunk, end of the order it is in, index of that order's entry in the sequence}; each cursor
+// walks the sequence for itself (the vector cursor is four chunks ahead of the execution, the scalar one a chunk).  On the common
+// path a cursor costs what the cyclic one did: add, compare, branch not taken.  At the end of an order the fix-up (out of line,
+// behind the loop) steps to the next entry -- past entry 15 back by 4: from entry 8 on the sequence repeats with period 4 -- and
+// to chunk 0 of its order.  Every address is order * s75 + (0 .. s75 - 0x100): inside the pass's chunks whatever the sequence holds
+// (tests/tbv_cursor_main.cpp walks the same state machine on the host).
+// the chunk under the vector cursor (s68, end s76, entry s79) into ring slot `b`
+#define TBV_LOAD(b, tag)                                                                                               \
   "s_add_u32 s86, s72, s68\n\t"  "s_addc_u32 s87, s73, 0\n\t"                                                          \
   "global_load_dwordx4 v[" #b ":" #b "+3], v64, s[86:87]\n\t"                                                          \
-  "s_add_u32 s68, s68, 0x100\n\t"  "s_cmp_eq_u32 s68, s75\n\t"  "s_cselect_b32 s68, 0, s68\n\t"
-// the index dwords of the chunk under the scalar cursor (s78) into the SGPR set that starts at `S`; cursor + 1 chunk, cyclic
+  "s_add_u32 s68, s68, 0x100\n\t"  "s_cmp_eq_u32 s68, s76\n\t"  "s_cbranch_scc1 Ltbv_vf" #tag "_%=\n\t"                \
+  "Ltbv_vr" #tag "_%=:\n\t"
+// the index dwords of the chunk under the scalar cursor (s78, end s77, entry s90) into the SGPR set that starts at `S`
 // (tried instead: the index dwords out of the ring registers by v_readlane, no scalar loads -- four more vector instructions per
 //  block: 105 instead of 88 cycles per block and SIMD on its own, 128 instead of 123.5 ms per 7168-plan engine run)
-#define TBV_SLOAD(S)                                                                                                   \
+#define TBV_SLOAD(S, tag)                                                                                              \
   "s_load_dwordx16 s[" #S ":" #S "+15], s[72:73], s78\n\t"                                                             \
-  "s_add_u32 s78, s78, 0x100\n\t"  "s_cmp_eq_u32 s78, s75\n\t"  "s_cselect_b32 s78, 0, s78\n\t"
+  "s_add_u32 s78, s78, 0x100\n\t"  "s_cmp_eq_u32 s78, s77\n\t"  "s_cbranch_scc1 Ltbv_sf" #tag "_%=\n\t"                \
+  "Ltbv_sr" #tag "_%=:\n\t"
+// the fix-ups: cursor {POS, END, IDX} to chunk 0 of the order of the sequence's next entry (s86: free between two vector loads)
+#define TBV_CURSOR_NEXT(POS, END, IDX)                                                                                 \
+  "s_add_u32 " IDX ", " IDX ", 1\n\t"  "s_cmp_gt_u32 " IDX ", 15\n\t"  "s_cselect_b32 s86, 4, 0\n\t"  "s_sub_u32 " IDX ", " IDX ", s86\n\t" \
+  "s_lshl_b32 s86, " IDX ", 1\n\t"  "s_lshr_b32 s86, s69, s86\n\t"  "s_and_b32 s86, s86, 3\n\t"                        \
+  "s_mul_i32 " POS ", s86, s75\n\t"  "s_add_u32 " END ", " POS ", s75\n\t"
+#define TBV_LOAD_FIX(tag)  "Ltbv_vf" #tag "_%=:\n\t" TBV_CURSOR_NEXT("s68", "s76", "s79") "s_branch Ltbv_vr" #tag "_%=\n\t"
+#define TBV_SLOAD_FIX(tag) "Ltbv_sf" #tag "_%=:\n\t" TBV_CURSOR_NEXT("s78", "s77", "s90") "s_branch Ltbv_sr" #tag "_%=\n\t"
+// both cursors to chunk 0 of the sequence's entry 0 (s74 = chunks per order, s69 = the sequence)
+#define TBV_CURSORS_INIT                                                                                               \
+  "s_lshl_b32 s75, s74, 8\n\t"                                                                                         \
+  "s_and_b32 s68, s69, 3\n\t"  "s_mul_i32 s68, s68, s75\n\t"  "s_add_u32 s76, s68, s75\n\t"  "s_mov_b32 s79, 0\n\t"      \
+  "s_mov_b32 s78, s68\n\t"  "s_mov_b32 s77, s76\n\t"  "s_mov_b32 s90, 0\n\t"
 // one chunk: its weights in ring slot b, its indices in set SA; the next chunk's indices go to set SB.  END: what follows the chunk
 #define TBV_CHUNK(BLOCK, b, SA, SB, tag, END)                                                                          \
   "s_waitcnt vmcnt(3) lgkmcnt(0)\n\t"                                                                                  \
-  TBV_SLOAD(SB)                                                                                                        \
+  TBV_SLOAD(SB, tag)                                                                                                   \
   "s_set_gpr_idx_on s74, gpr_idx(SRC1)\n\t"                                                                            \
   BLOCK(b, SA, SA + 4, SA + 8, SA + 12, tag##0)  BLOCK(b + 1, SA + 1, SA + 5, SA + 9, SA + 13, tag##1)                 \
   BLOCK(b + 2, SA + 2, SA + 6, SA + 10, SA + 14, tag##2)  BLOCK(b + 3, SA + 3, SA + 7, SA + 11, SA + 15, tag##3)       \
   "s_set_gpr_idx_off\n\t"                                                                                              \
-  TBV_LOAD(b)                                                                                                          \
+  TBV_LOAD(b, tag)                                                                                                     \
   "s_sub_u32 s80, s80, 1\n\t"                                                                                          \
   "s_cmp_lg_u32 s80, 0\n\t"                                                                                            \
   "s_cbranch_scc1 Ltbv_nx" #tag "_%=\n\t"                                                                              \
@@ -163,14 +186,17 @@ __device__ __forceinline__ uint32_t win_read(uint32_t row)
   "s_mov_b64 s[70:71], 0\n\t"
 #define TBV_END_PASS "s_branch Ltbv_done_%=\n\t"
 #define TBV_LOOP(BLOCK, END)                                                                                           \
-  TBV_LOAD(40) TBV_LOAD(44) TBV_LOAD(48) TBV_LOAD(52)                                                                  \
-  TBV_SLOAD(36)                                                                                                        \
+  TBV_LOAD(40, p0) TBV_LOAD(44, p1) TBV_LOAD(48, p2) TBV_LOAD(52, p3)                                                  \
+  TBV_SLOAD(36, p0)                                                                                                    \
   "Ltbv_top_%=:\n\t"                                                                                                   \
   TBV_CHUNK(BLOCK, 40, 36, 52, c0, END) TBV_CHUNK(BLOCK, 44, 52, 36, c1, END) TBV_CHUNK(BLOCK, 48, 36, 52, c2, END) TBV_CHUNK(BLOCK, 52, 52, 36, c3, END) \
-  "s_branch Ltbv_top_%=\n\t"
+  "s_branch Ltbv_top_%=\n\t"                                                                                          \
+  TBV_LOAD_FIX(p0) TBV_LOAD_FIX(p1) TBV_LOAD_FIX(p2) TBV_LOAD_FIX(p3) TBV_SLOAD_FIX(p0)                                \
+  TBV_LOAD_FIX(c0) TBV_LOAD_FIX(c1) TBV_LOAD_FIX(c2) TBV_LOAD_FIX(c3)                                                  \
+  TBV_SLOAD_FIX(c0) TBV_SLOAD_FIX(c1) TBV_SLOAD_FIX(c2) TBV_SLOAD_FIX(c3)
 #define TBV_CLOBBERS "memory", "vcc", "scc", "m0", "s36", "s37", "s38", "s39", "s40", "s41", "s42", "s43", "s44", "s45", "s46", "s47", "s48", "s49", "s50", "s51", \
-  "s52", "s53", "s54", "s55", "s56", "s57", "s58", "s59", "s60", "s61", "s62", "s63", "s64", "s65", "s66", "s67", "s68", "s70", "s71", "s72", "s73", "s74", "s75", \
-  "s78", "s80", "s81", "s82", "s83", "s84", "s85", "s86", "s87", "s88", "s89", "v40", "v68", "v255"
+  "s52", "s53", "s54", "s55", "s56", "s57", "s58", "s59", "s60", "s61", "s62", "s63", "s64", "s65", "s66", "s67", "s68", "s69", "s70", "s71", "s72", "s73", "s74", "s75", \
+  "s76", "s77", "s78", "s79", "s80", "s81", "s82", "s83", "s84", "s85", "s86", "s87", "s88", "s89", "s90", "v40", "v68", "v255"
 
 struct Uni { uint32_t lo, hi, nch; };   // a stream's first chunk (address) and its chunk count, made uniform for the "s" operands
 __device__ __forceinline__ Uni uni(const uint32_t* first, uint32_t nch)
@@ -180,28 +206,28 @@ __device__ __forceinline__ Uni uni(const uint32_t* first, uint32_t nch)
   return Uni{ tb::rfl((uint32_t)a), tb::rfl((uint32_t)(a >> 32)), tb::rfl(nch) };
 }
 
-// The Gauss-Seidel sweeps of one activation over the four orders' chunks (order k at sweep0 + k * nch chunks), starting with
-// `first_order`, until a sweep changes nothing in any lane.  Returns the number of sweeps; `overrun` when `cap` did not suffice.
+// The Gauss-Seidel sweeps of one activation over the four orders' chunks (order k at sweep0 + k * nch chunks), in the orders of
+// the sequence `seq` (mnav_tbv_seq.h), until a sweep changes nothing in any lane -- a sweep of any order that changes nothing
+// proves the tile-local fixed point, the four orders hold the same edges: the sequence decides how many sweeps run, never the
+// bits they leave.  Returns the number of sweeps; `overrun` when `cap` did not suffice.
 // `force` != 0: every sweep counts as "changed" (timing runs: exactly `cap` sweeps).  nch >= 1.  `lowered`: the lanes in which
 // some sweep lowered some row.
-__device__ __forceinline__ uint32_t tbv_sweeps(const uint32_t* sweep0, uint32_t nch, uint32_t first_order, uint32_t cap, uint32_t lane_off,
+__device__ __forceinline__ uint32_t tbv_sweeps(const uint32_t* sweep0, uint32_t nch, uint32_t seq, uint32_t cap, uint32_t lane_off,
                                                uint32_t force, bool& overrun, unsigned long long& lowered)
 {
   uint32_t sweeps, ovr, low_lo, low_hi;
   const Uni u = uni(sweep0, nch);
-  first_order = tb::rfl(first_order); cap = tb::rfl(cap); force = tb::rfl(force);
+  seq = tb::rfl(seq); cap = tb::rfl(cap); force = tb::rfl(force);
   asm volatile(
       "v_mov_b32 v64, %[off]\n\t"
       "s_mov_b32 s72, %[stlo]\n\t"
       "s_mov_b32 s73, %[sthi]\n\t"
       "s_mov_b32 s74, %[nch]\n\t"
-      "s_lshl_b32 s75, s74, 10\n\t"                                   // bytes of the four orders
+      "s_mov_b32 s69, %[seq]\n\t"
+      TBV_CURSORS_INIT                                                // both cursors start at chunk 0 of the sequence's first order
       "s_mov_b32 s81, %[cap]\n\t"
       "s_mov_b32 s82, %[force]\n\t"
       "s_mov_b32 s83, %[force]\n\t"
-      "s_lshl_b32 s68, s74, 8\n\t"
-      "s_mul_i32 s68, s68, %[ord]\n\t"                               // both cursors start at the first order's chunk 0
-      "s_mov_b32 s78, s68\n\t"
       "s_mov_b32 s80, s74\n\t"
       "s_mov_b32 s84, 0\n\t"
       "s_mov_b64 s[70:71], 0\n\t"
@@ -218,7 +244,7 @@ __device__ __forceinline__ uint32_t tbv_sweeps(const uint32_t* sweep0, uint32_t 
       "s_mov_b32 %[lhi], s89\n\t"
       "s_waitcnt vmcnt(0) lgkmcnt(0)\n\t"                              // the speculative loads of the next sweep land in the ring / the index set: nothing may follow them
       : [sw] "=s"(sweeps), [ovr] "=s"(ovr), [llo] "=s"(low_lo), [lhi] "=s"(low_hi)
-      : [stlo] "s"(u.lo), [sthi] "s"(u.hi), [nch] "s"(u.nch), [ord] "s"(first_order), [cap] "s"(cap), [off] "v"(lane_off), [force] "s"(force)
+      : [stlo] "s"(u.lo), [sthi] "s"(u.hi), [nch] "s"(u.nch), [seq] "s"(seq), [cap] "s"(cap), [off] "v"(lane_off), [force] "s"(force)
       : TBV_CLOBBERS);
   overrun = ovr != 0u;
   lowered = ((unsigned long long)low_hi << 32) | low_lo;
@@ -238,9 +264,8 @@ __device__ __forceinline__ void tbv_pre(const uint32_t* pre0, uint32_t nch, uint
       "s_mov_b32 s72, %[stlo]\n\t"
       "s_mov_b32 s73, %[sthi]\n\t"
       "s_mov_b32 s74, %[nch]\n\t"
-      "s_lshl_b32 s75, s74, 8\n\t"
-      "s_mov_b32 s68, 0\n\t"
-      "s_mov_b32 s78, 0\n\t"
+      "s_mov_b32 s69, 0\n\t"                                           // one "order": the pass's own chunks, again and again
+      TBV_CURSORS_INIT
       "s_mov_b32 s80, s74\n\t"
       TBV_LOOP(TBV_BLOCK_PRE, TBV_END_PASS)
       "Ltbv_done_%=:\n\t"
@@ -266,9 +291,8 @@ __device__ __forceinline__ void tbv_post(const uint32_t* post0, uint32_t nch, ui
       "s_mov_b32 s72, %[stlo]\n\t"
       "s_mov_b32 s73, %[sthi]\n\t"
       "s_mov_b32 s74, %[nch]\n\t"
-      "s_lshl_b32 s75, s74, 8\n\t"
-      "s_mov_b32 s68, 0\n\t"
-      "s_mov_b32 s78, 0\n\t"
+      "s_mov_b32 s69, 0\n\t"                                           // one "order": the pass's own chunks, again and again
+      TBV_CURSORS_INIT
       "s_mov_b32 s80, s74\n\t"
       TBV_LOOP(TBV_BLOCK_POST, TBV_END_PASS)
       "Ltbv_done_%=:\n\t"
@@ -339,20 +363,22 @@ void k_tbv_solve(tb::Args A, const uint32_t* __restrict__ vtile, const uint32_t*
     u32x2 item_n = { 0u, 0u };
     if (it_n < n_items) item_n = ((MNAV_GLOBAL const u32x2*)as_global(A.items))[it_n];   // in flight during the passes
     TB_STAMP(1);
-    // ---- ghosts -> owned (the ghosts are constant during the activation); the order most lanes ask for starts the sweeps
-    uint32_t first_order = 0;
+    // ---- ghosts -> owned (the ghosts are constant during the activation).  The lanes vote for the order their wave enters with:
+    // the sweeps run the voted orders first, most votes first, and rotate on from the last of them (mnav_tbv_seq.h).  Measured on
+    // the CPU model: 3.5 instead of 3.9 sweeps per item against "the winner, then the rotation" (A.sweep_seq = 0),
+    // which runs orders nobody asked for before the ones the other lanes need.
+    uint32_t seq = tbv_seq::tbv_seq_rotation(0u);
     bool changed = false;                                              // this lane: a ghost or a sweep lowered one of its rows
     if (pre_chunks) {
       uint32_t mn, gord;
       tbv::tbv_pre(vstream + (size_t)pre_off * kTbChunk, pre_chunks, lane_off, mn, gord);
       changed = mn != kTbInfBits;
       const bool votes = active && changed;
-      uint32_t bestc = 0;
+      uint32_t cn[4];
 #pragma unroll
-      for (uint32_t o = 0; o < 4; ++o) {
-        const uint32_t cn = (uint32_t)__popcll(__ballot(votes && (gord & 3u) == o));
-        if (cn > bestc) { bestc = cn; first_order = o; }
-      }
+      for (uint32_t o = 0; o < 4; ++o) cn[o] = (uint32_t)__popcll(__ballot(votes && (gord & 3u) == o));
+      seq = tbv_seq::tbv_seq_build(cn[0], cn[1], cn[2], cn[3]);
+      if (!A.sweep_seq) seq = tbv_seq::tbv_seq_rotation(seq & 3u);
     }
     TB_STAMP(2);
     // ---- Gauss-Seidel sweeps to the tile-local fixed point of every lane
@@ -360,7 +386,7 @@ void k_tbv_solve(tb::Args A, const uint32_t* __restrict__ vtile, const uint32_t*
     if (sweep_chunks) {
       bool overrun;
       unsigned long long lowered;
-      sweep = tbv::tbv_sweeps(vstream + (size_t)sweep_off * kTbChunk, sweep_chunks, first_order, 16u * T, lane_off, 0u, overrun, lowered);
+      sweep = tbv::tbv_sweeps(vstream + (size_t)sweep_off * kTbChunk, sweep_chunks, seq, 16u * T, lane_off, 0u, overrun, lowered);
       if (overrun && lane == 0) A.ctl->err = 1u;
       changed = changed || ((lowered >> lane) & 1ull);                 // (the wave source's tile: lowered by no ghost, yet its rows move)
     }
@@ -450,10 +476,10 @@ void k_tbv_solve(tb::Args A, const uint32_t* __restrict__ vtile, const uint32_t*
   }
 }
 
-// Test / timing entry of the sweep routine on its own (mnav_debug_tbv_sweeps): every wave loads ITS owned rows [row][lane] from
+// Test / timing entry of the sweep routine on its own (mnav_debug_tbv_sweeps, mnav_debug_tbv_sweeps_seq): every wave loads ITS owned rows [row][lane] from
 // `img`, runs the sweeps over the one stream and stores the rows back.
 __global__ __launch_bounds__(64) TBV_COMPILER_VGPRS
-void k_tbv_micro(const uint32_t* __restrict__ stream, uint32_t nch, uint32_t first_order, uint32_t cap, uint32_t force, uint32_t reps,
+void k_tbv_micro(const uint32_t* __restrict__ stream, uint32_t nch, uint32_t seq, uint32_t cap, uint32_t force, uint32_t reps,
                  uint32_t* __restrict__ img, uint32_t* __restrict__ out)
 {
   const int lane = threadIdx.x;
@@ -464,7 +490,7 @@ void k_tbv_micro(const uint32_t* __restrict__ stream, uint32_t nch, uint32_t fir
   for (uint32_t k = 0; k < reps; ++k) {
     bool ovr;
     unsigned long long low;
-    total += tbv::tbv_sweeps(stream, nch, first_order, cap, 16u * ((uint32_t)lane & 15u), force ? ~0u : 0u, ovr, low);
+    total += tbv::tbv_sweeps(stream, nch, seq, cap, 16u * ((uint32_t)lane & 15u), force ? ~0u : 0u, ovr, low);
     over |= ovr ? 1u : 0u;
   }
   tbv::static_for<0, tbv::kRows>([&](auto r) { constexpr int R = decltype(r)::value; my[R * 64] = tbv::img_get<R>(); });
@@ -473,9 +499,11 @@ void k_tbv_micro(const uint32_t* __restrict__ stream, uint32_t nch, uint32_t fir
 
 }  // namespace
 
-extern "C" int mnav_debug_tbv_sweeps(const uint32_t* stream_host, uint32_t nch, uint32_t first_order, uint32_t cap, uint32_t force, uint32_t reps,
-                                     uint32_t waves, uint32_t* img_host, uint32_t* out_host, float* ms_out)
+// the sweeps in the orders of the packed sequence `seq` (mnav_tbv_seq.h)
+extern "C" int mnav_debug_tbv_sweeps_seq(const uint32_t* stream_host, uint32_t nch, uint32_t seq, uint32_t cap, uint32_t force, uint32_t reps,
+                                         uint32_t waves, uint32_t* img_host, uint32_t* out_host, float* ms_out)
 {
+  if (nch < 1u || !waves) return -1;
   DevBuf<uint32_t> d_s, d_i, d_o;
   const size_t ns = (size_t)4 * nch * 64 + 8 * 64, ni = (size_t)waves * tbv::kRows * 64;
   if (d_s.alloc(4 * ns) != hipSuccess || d_i.alloc(4 * ni) != hipSuccess || d_o.alloc(8 * (size_t)waves) != hipSuccess) return -1;
@@ -485,7 +513,7 @@ extern "C" int mnav_debug_tbv_sweeps(const uint32_t* stream_host, uint32_t nch, 
   Event e0, e1;
   (void)hipEventCreate(e0.out()); (void)hipEventCreate(e1.out());
   (void)hipEventRecord(e0, 0);
-  hipLaunchKernelGGL(k_tbv_micro, dim3(waves), dim3(64), 0, 0, d_s, nch, first_order, cap, force, reps, d_i, d_o);
+  hipLaunchKernelGGL(k_tbv_micro, dim3(waves), dim3(64), 0, 0, d_s, nch, seq, cap, force, reps, d_i, d_o);
   (void)hipEventRecord(e1, 0);
   const hipError_t e = hipDeviceSynchronize();
   float ms = 0.f;
@@ -494,5 +522,12 @@ extern "C" int mnav_debug_tbv_sweeps(const uint32_t* stream_host, uint32_t nch, 
   (void)hipMemcpy(img_host, d_i, 4 * ni, hipMemcpyDeviceToHost);
   (void)hipMemcpy(out_host, d_o, 8 * (size_t)waves, hipMemcpyDeviceToHost);
   return e == hipSuccess ? 0 : -2;
+}
+
+// the sweeps from order `first_order` on, then the rotation
+extern "C" int mnav_debug_tbv_sweeps(const uint32_t* stream_host, uint32_t nch, uint32_t first_order, uint32_t cap, uint32_t force, uint32_t reps,
+                                     uint32_t waves, uint32_t* img_host, uint32_t* out_host, float* ms_out)
+{
+  return mnav_debug_tbv_sweeps_seq(stream_host, nch, tbv_seq::tbv_seq_rotation(first_order), cap, force, reps, waves, img_host, out_host, ms_out);
 }
 #pragma clang diagnostic pop

@@ -1,5 +1,8 @@
 """The register-resident Gauss-Seidel sweep routine (mnav_tbv.h, tbv_sweeps) on its own: (1) against a numpy restatement of the
-same stream on random images, bit for bit; (2) timing: cycles per block and SIMD at full residency.
+same stream on random images, bit for bit; (2) timing: cycles per block and SIMD at full residency, forced sweeps -- in the rotation
+from order 0 (mnav_debug_tbv_sweeps) and in a sequence whose cursors jump between the orders (mnav_debug_tbv_sweeps_seq: 3, 1, then
+the rotation from 2).  Both must give the same figure: the cursors' end-of-order fix-up is off the common path.
+(Parity of the sequences: tests/test_gpu_tbv_seq.py, on streams whose orders hold the same blocks.)
 
     python tools/gpu_tbv_micro.py
 """
@@ -67,6 +70,9 @@ def main():
     fn = L.mnav_debug_tbv_sweeps
     fn.restype = C.c_int
     fn.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+    fn_seq = L.mnav_debug_tbv_sweeps_seq
+    fn_seq.restype, fn_seq.argtypes = C.c_int, fn.argtypes
+    seq = sum(o << (2 * k) for k, o in enumerate([3, 1] + [(2 + k) & 3 for k in range(14)]))
     rng = np.random.default_rng(7)
     out = {}
     # ---- (1) parity
@@ -95,6 +101,9 @@ def main():
         clk = 2.4e9
         out[f"timing_{waves}_waves"] = dict(ms=ms.value, blocks=blocks, ns_per_block_per_simd=ms.value * 1e6 / (blocks / 1024.0),
                                             cycles_per_block_per_simd_at_2p4GHz=ms.value * 1e-3 * clk / (blocks / 1024.0), sweeps_ok=bool((res2[:, 0] == reps * cap).all()))
+        rc = fn_seq(words.ctypes.data, nch, seq, cap, 1, reps, waves, img2.ctypes.data, res2.ctypes.data, C.byref(ms))
+        out[f"timing_seq_{waves}_waves"] = dict(ms=ms.value, blocks=blocks, ns_per_block_per_simd=ms.value * 1e6 / (blocks / 1024.0),
+                                                cycles_per_block_per_simd_at_2p4GHz=ms.value * 1e-3 * clk / (blocks / 1024.0), sweeps_ok=bool((res2[:, 0] == reps * cap).all()))
     print(json.dumps(out))
 
 
