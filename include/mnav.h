@@ -839,6 +839,68 @@ int mnav_fleet_ring_stats(const mnav_ctx* ctx, uint32_t* robots_ring, uint64_t* 
                           uint32_t* rings_last, uint32_t* checks_run, uint32_t* checks_skipped, uint32_t* first_skipped_tick,
                           float* ms_ring, float* ms_separation, float* ms_kernels, float* ms_total);
 
+/* -- sampled rollouts: K candidate controls per robot, scored on the device ----------------------------
+ * What a local planner asks at every control tick -- of K ways to steer for the next `ticks` ticks, which one ends lowest on
+ * the potential field, at the least cost, without leaving the mesh or crossing a lethal region (DWA or MPPI over the
+ * planner's own field) -- answered over the resident fields.  The robots go up as for mnav_follow_rollout, with a table
+ * of n_candidates candidates shared by all robots; the device expands them into n * K rows (row i * K + k: robot i under
+ * candidate k), runs every row for rollout->ticks ticks, scores every row and picks per robot.  Only the picks come down,
+ * and the per-row outputs a caller asks for: nothing V-sized crosses PCIe. */
+typedef struct mnav_sample_config {
+  double   w_potential;   /* weights of J, each finite and >= 0 */
+  double   w_cost;
+  double   w_time;
+  double   lethal_cost;   /* used as (float)lethal_cost; not NaN; +inf: only a NaN cost is lethal */
+  uint32_t flags;         /* reserved, must be 0 */
+} mnav_sample_config;
+#define MNAV_SAMPLE_CONFIG_DEFAULTS { 1.0, 0.0, 0.0, 1.0, 0u }
+/* candidates: 4 doubles per candidate, lin_gain, lin_bias, ang_gain, ang_bias.  Gain 0 is a constant arc (DWA), (1, 0, 1, 0)
+ * is the follower itself, gain 1 with an angular bias is "follow the field but keep left".
+ * Every row starts as a robot of mnav_follow_rollout, with pot = +inf, lethal = 0 and cmd0 = (0, 0).  ONE TICK OF A RUNNING
+ * ROW is steps 1 to 6 of mnav_follow_rollout, same types and order, no contraction, with three differences:
+ *   a  POTENTIAL AND LETHAL FLAG.  After step 3 (R is OK or NO_FIELD; the face and R.bary are known):
+ *        pot = d[v0]*b0 + d[v1]*b1 + d[v2]*b2 in float, left to right (the form of cost_out of mnav_follow_batch), d the
+ *        slot's resident potential -- bit for bit what mnav_download_output(slot, 0) returns --, v0..2 the face's vertices in
+ *        stored order; and when R is OK: lethal |= !(R.cost < (float)lethal_cost), so a NaN cost counts as lethal
+ *   b  COMMAND.  Step 6 runs under u in place of R.lin, and the same for ang:
+ *        u = gain * R.lin; if (bias != 0) u += bias; u = u < max_lin_velocity ? u : max_lin_velocity
+ *        (max_ang_velocity for ang: the saturation of the follower, idempotent on its own command).  A zero bias is not
+ *        added -- x + 0.0 would turn -0 into +0 --, so (1, 0, 1, 0) passes R.lin and R.ang through bit for bit.  The first
+ *        tick of a row that reaches step 6 records cmd0 = (u_lin, u_ang)
+ *   c  END OF THE CALL.  J = w_potential * (double)pot + w_cost * cost_integral + w_time * ((double)ticks_run * dt), in
+ *        double, left to right.  A row is FEASIBLE iff its status is RUNNING or REACHED, it is not lethal and J is finite
+ *        (an infinite or NaN potential makes J non-finite; a row that never reached step 3 keeps pot = +inf)
+ * pot is the potential where the row's LAST tick found it, that is before that tick's step: a caller who wants the
+ * potential one step further asks for one more tick.
+ * THE PICK, per robot: the feasible row with the smallest (J, k) -- J compared with <, ties to the smallest k, -0 ties with
+ * +0.  best_k_out[i] = that k (MNAV_NONE: no row is feasible), best_score_out[i] = its J (+inf), best_cmd_out[2 i], [2 i + 1] =
+ * its cmd0 (zeros), n_feasible_out[i] = the robot's feasible rows.  Optional per-row outputs, n * K each, row-major as above
+ * (any may be NULL, and is then not downloaded): status, ticks, score J, potential, lethal flag (0 / 1), cost integral,
+ * travel, end position (3 floats).  The pick is built from compares, counts and minima only: the same bits on every run.
+ * mnav_cancel is honoured between blocks of at most 256 ticks, as in the rollouts, but the flag is NOT cleared at entry: a
+ * cancel that arrived before the call ends it before its first tick (the statistics are then all 0).  A cancelled call
+ * returns 1, writes no output and takes the flag down.
+ * Returns 0, 1 when cancelled, or -1 with mnav_last_error set and NOTHING touched (every refusal comes before the first
+ * device call): every refusal of mnav_follow_rollout, a non-zero trace_stride, n_candidates = 0 or a NULL table, a gain or
+ * bias that is not finite, a weight that is negative or not finite, a NaN lethal_cost, non-zero flags, a NULL sample,
+ * n * n_candidates above 2^28, a slot whose potential is not resident, a table whose largest |ang_gain| * |max_ang_velocity| *
+ * max(1, |ang_vel_factor|) + |ang_bias|, times dt, reaches 100 rad.  n = 0 does nothing.  The call changes no plan output, no
+ * layer and no statistic or record of another entry point (mnav_rollout_stats and the mnav_fleet_*_stats keep their values);
+ * it builds the lookup index as mnav_follow_rollout does.  About 100 bytes per row stay resident.  DESIGN.md section 3.23. */
+int mnav_follow_sample(mnav_ctx* ctx, uint32_t n, const float* pos, const float* dir, const float* up, const uint32_t* face_in,
+                       const uint32_t* slots, const uint32_t* seed_faces, const float* goal_pos, const float* goal_dir,
+                       const mnav_follow_config* config, const mnav_rollout_config* rollout, uint32_t n_candidates,
+                       const double* candidates, const mnav_sample_config* sample, uint32_t* best_k_out, double* best_score_out,
+                       double* best_cmd_out, uint32_t* n_feasible_out, int32_t* status_out, uint32_t* ticks_out, double* score_out,
+                       float* potential_out, uint8_t* lethal_out, double* cost_integral_out, double* travel_out, float* pos_out);
+/* The last mnav_follow_sample: status_counts[4] = rows per final status, lethal and feasible rows, robots without a pick, the
+ * row-ticks run and how they were resolved (stayed, neighbour, global: as mnav_rollout_stats), built_index, device
+ * milliseconds of the expand kernel, of the score and pick kernels, of all kernels, and host milliseconds of the whole
+ * call.  After a cancelled call the three pick counts are 0.  Any pointer may be NULL. */
+int mnav_sample_stats(const mnav_ctx* ctx, uint32_t* status_counts, uint32_t* lethal_rows, uint32_t* feasible_rows,
+                      uint32_t* robots_without_pick, uint64_t* row_ticks, uint64_t* stayed, uint64_t* neighbour, uint64_t* global,
+                      uint32_t* built_index, float* ms_expand, float* ms_pick, float* ms_kernels, float* ms_total);
+
 /* -- fleet paths and walks: many robots per resident field ---------------------------------------------
  * A Dijkstra call returns one vertex path per plan, from the plan's seed (the goal) to its one target.  The field is seeded
  * at the goal, so it already holds the path of every robot inside it: mnav_fleet_paths hands Move Base Flex's setPlan a

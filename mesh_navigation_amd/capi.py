@@ -38,6 +38,7 @@ SYMBOLS = [
     "mnav_locate", "mnav_locate_stats", "mnav_plan_dijkstra_batch_at", "mnav_plan_cvp_batch_at",
     "mnav_follow_batch", "mnav_follow_stats", "mnav_follow_rollout", "mnav_rollout_stats", "mnav_fleet_rollout", "mnav_fleet_rollout_stats",
     "mnav_fleet_rollout_yield", "mnav_fleet_yield_stats", "mnav_fleet_rollout_rings", "mnav_fleet_ring_stats",
+    "mnav_follow_sample", "mnav_sample_stats",
     "mnav_map_configure", "mnav_map_compute", "mnav_map_layer_changed", "mnav_map_update_layer", "mnav_map_obstacle", "mnav_map_stats",
     "mnav_replan_dijkstra_batch", "mnav_replan_plans", "mnav_replan_stats", "mnav_replan_dijkstra_each", "mnav_replan_each_stats",
     "mnav_replan_warm_stats",
@@ -145,6 +146,20 @@ class RingConfig(C.Structure):
 
 RING_RELEASE = 1
 WAIT_FREE, WAIT_QUEUED, WAIT_PARKED, WAIT_RING_TAIL, WAIT_RING_MEMBER = 0, 1, 2, 3, 4
+
+
+class SampleConfig(C.Structure):
+    """mnav_sample_config (include/mnav.h): the weights of a candidate row's score J (potential, cost integral, time), the
+    vertex cost from which a row counts as lethal, and the reserved flags (0)."""
+    _fields_ = [("w_potential", C.c_double), ("w_cost", C.c_double), ("w_time", C.c_double), ("lethal_cost", C.c_double), ("flags", C.c_uint32)]
+    DEFAULTS = dict(w_potential=1.0, w_cost=0.0, w_time=0.0, lethal_cost=1.0, flags=0)
+
+    def __init__(self, **kw):
+        super().__init__(**{**self.DEFAULTS, **kw})
+
+
+SAMPLE_PICKS = ("best_k", "best_score", "best_cmd", "n_feasible")
+SAMPLE_ROWS = ("status", "ticks", "score", "potential", "lethal", "cost_integral", "travel", "pos")
 
 
 class MapNode(C.Structure):
@@ -291,6 +306,10 @@ def load(path: str | None = None):
     L.mnav_fleet_rollout_rings.argtypes = L.mnav_fleet_rollout_yield.argtypes + [C.POINTER(RingConfig)] + [vp] * 6
     L.mnav_fleet_ring_stats.restype = C.c_int
     L.mnav_fleet_ring_stats.argtypes = [vp] + [vp] * 17
+    L.mnav_follow_sample.restype = C.c_int
+    L.mnav_follow_sample.argtypes = [vp, u32] + [vp] * 8 + [C.POINTER(FollowConfig), C.POINTER(RolloutConfig), u32, vp, C.POINTER(SampleConfig)] + [vp] * 12
+    L.mnav_sample_stats.restype = C.c_int
+    L.mnav_sample_stats.argtypes = [vp, C.POINTER(u32 * 4)] + [C.POINTER(u32)] * 3 + [C.POINTER(C.c_uint64)] * 4 + [C.POINTER(u32)] + [C.POINTER(C.c_float)] * 4
     L.mnav_rollout_stats.restype = C.c_int
     L.mnav_rollout_stats.argtypes = [vp, C.POINTER(u32 * 4)] + [C.POINTER(C.c_uint64)] * 4 + [C.POINTER(u32)] + [C.POINTER(C.c_float)] * 2
     L.mnav_map_configure.restype = C.c_int
@@ -1611,6 +1630,53 @@ class MnavContext:
         names = ("robot_ticks", "stayed", "neighbour", "global")
         return dict(running=sc[0], reached=sc[1], out_of_map=sc[2], no_field=sc[3], **{k: x.value for k, x in zip(names, v)},
                     built_index=b.value, ms_kernels=mk.value, ms_total=mt.value)
+
+    def follow_sample(self, pos, direction, up, face_in, slots, candidates, seed_faces=None, goal_pos=None, goal_dir=None, config: FollowConfig | None = None,
+                      rollout: RolloutConfig | None = None, sample: SampleConfig | None = None, outputs=None) -> dict:
+        """K candidate controls per robot, rolled out for rollout.ticks ticks, scored on the resident potential and picked
+        per robot on the device (mnav_follow_sample, include/mnav.h).  The per-robot arrays are those of rollout();
+        candidates: (K, 4) doubles, lin_gain, lin_bias, ang_gain, ang_bias.  Returns a dict: the picks best_k (NONE: no
+        feasible row), best_score, best_cmd (n, 2), n_feasible; the per-row outputs SAMPLE_ROWS, each (n, K) (pos: (n, K, 3)),
+        or None where `outputs` (names; default: all) leaves one out; and `cancelled`."""
+        p, d, u = (_f32(a).reshape(-1, 3) for a in (pos, direction, up))
+        fi, sl = _u32(face_in).reshape(-1), _u32(slots).reshape(-1)
+        n = int(p.shape[0])
+        if not (d.shape[0] == u.shape[0] == fi.shape[0] == sl.shape[0] == n):
+            raise ValueError("follow_sample: the per-robot arrays differ in length")
+        sf = None if seed_faces is None else _u32(seed_faces).reshape(-1)
+        if sf is not None and sf.shape[0] != n:
+            raise ValueError("follow_sample: seed_faces needs one entry per robot")
+        gp = None if goal_pos is None else _f32(goal_pos).reshape(-1, 3)
+        gd = None if goal_dir is None else _f32(goal_dir).reshape(-1, 3)
+        if any(g is not None and g.shape[0] != n for g in (gp, gd)):
+            raise ValueError("follow_sample: goal_pos / goal_dir need one row per robot")
+        tab = np.ascontiguousarray(candidates, np.float64).reshape(-1, 4)
+        K = int(tab.shape[0])
+        cfg = config if config is not None else FollowConfig()
+        ro = rollout if rollout is not None else RolloutConfig()
+        sa = sample if sample is not None else SampleConfig()
+        shapes = dict(best_k=((n,), np.uint32), best_score=((n,), np.float64), best_cmd=((n, 2), np.float64), n_feasible=((n,), np.uint32),
+                      status=((n, K), np.int32), ticks=((n, K), np.uint32), score=((n, K), np.float64), potential=((n, K), np.float32),
+                      lethal=((n, K), np.uint8), cost_integral=((n, K), np.float64), travel=((n, K), np.float64), pos=((n, K, 3), np.float32))
+        want = set(shapes) if outputs is None else set(outputs)
+        o = {k: (np.zeros(*shapes[k]) if k in want else None) for k in shapes}
+        rc = self._L.mnav_follow_sample(self._h, n, _p(p), _p(d), _p(u), _p(fi), _p(sl), _p(sf), _p(gp), _p(gd), C.byref(cfg), C.byref(ro), K, _p(tab) if K else None,
+                                        C.byref(sa), *[_p(o[k]) for k in SAMPLE_PICKS + SAMPLE_ROWS])
+        if rc < 0:
+            raise RuntimeError(f"mnav_follow_sample failed: {self._err()}")
+        return dict(o, cancelled=rc == 1)
+
+    def sample_stats(self) -> dict:
+        sc = (C.c_uint32 * 4)()
+        c = [C.c_uint32() for _ in range(3)]
+        v = [C.c_uint64() for _ in range(4)]
+        b = C.c_uint32()
+        ms = [C.c_float() for _ in range(4)]
+        self._L.mnav_sample_stats(self._h, C.byref(sc), *[C.byref(x) for x in c], *[C.byref(x) for x in v], C.byref(b), *[C.byref(x) for x in ms])
+        return dict(running=sc[0], reached=sc[1], out_of_map=sc[2], no_field=sc[3],
+                    **{k: x.value for k, x in zip(("lethal_rows", "feasible_rows", "robots_without_pick"), c)},
+                    **{k: x.value for k, x in zip(("row_ticks", "stayed", "neighbour", "global"), v)}, built_index=b.value,
+                    **{k: x.value for k, x in zip(("ms_expand", "ms_pick", "ms_kernels", "ms_total"), ms)})
 
     def fleet_rollout(self, pos, direction, up, face_in, slots, seed_faces=None, goal_pos=None, goal_dir=None, config: FollowConfig | None = None,
                       rollout: RolloutConfig | None = None, start_tick=None, separation: SeparationConfig | None = None, outputs=None) -> FleetRolloutOut:

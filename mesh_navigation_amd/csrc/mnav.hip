@@ -88,6 +88,7 @@ constexpr int kChunk = 96;  // step launches per graph replay; multiple of 6 (sl
 #include "mnav_fleet_rollout.h"   // fleet rollouts: a departure tick per robot and the separation check between robots (mnav_frol::)
 #include "mnav_fleet_yield.h"     // ... in which robots yield: the right-of-way rule inside the check's pair pass, held robots without a tick (mnav_frol::)
 #include "mnav_fleet_ring.h"      // ... and learn why they are held: the wait-for analysis behind the pair pass, the release of rings (mnav_frol::)
+#include "mnav_sample.h"     // sampled rollouts: K candidate controls per robot, scored on the potential and picked on the device (mnav_smp::)
 #include "mnav_replan.h"     // replan on a resident potential: rewind level from the change log, rewind with the tiles' wake-up words (k_replan_*)
 #include "mnav_replan_each.h"  // the per-plan replan: class of every plan, ordered lists, compacted records (k_replan_classify, k_replan_gather)
 #include "mnav_tb_warm.h"    // warm start of the tile-batch engine from rewound fields: every slice and pending word of a sub-batch (k_tb_warm)
@@ -250,6 +251,7 @@ struct mnav_ctx {
   RolloutRecord rol_rec, frol_rec, yld_rec, ring_rec;              // mnav_follow_rollout, mnav_fleet_rollout, mnav_fleet_rollout_yield, mnav_fleet_rollout_rings: kept apart
   mnav_frol::YldState yld;                                         // yielding fleet rollout: hold flags, priorities, yield rows and check rows, the pair passes' event pairs
   mnav_frol::RingState ring;                                       // wait-for analysis: blockers, the doubling's buffers, marks, ring rows and check rows, its event pairs
+  mnav_smp::Dev smp; mnav_smp::Stats smp_rec;                      // sampled rollouts: the uploaded robots, the rows' pot / lethal / cmd0 / score, the picks; the last call's record
   mnav_chg::Scratch chg;                                           // obstacle / clearance / border layers: change list and counters of the last call
   mnav_map::State map;                                             // resident layer graph (mnav_map_*): nodes, tables, change lists of the last update
   uint32_t infl_steps = 0, infl_bands = 0; uint64_t infl_evals = 0; float infl_ms = 0.f, infl_ms_wave = 0.f;   // last inflation wave
@@ -1879,6 +1881,7 @@ uint32_t mnav_plan_cvp_batch(mnav_ctx* ctx, uint32_t n, const float* seed_pos, c
 #include "mnav_locate_capi.h"     // mnav_locate, mnav_locate_stats, mnav_plan_dijkstra_batch_at, mnav_plan_cvp_batch_at
 #include "mnav_follow_capi.h"     // mnav_follow_batch, mnav_follow_stats
 #include "mnav_rollout_capi.h"    // mnav_follow_rollout, mnav_rollout_stats, mnav_fleet_rollout, mnav_fleet_rollout_stats, mnav_fleet_rollout_yield, mnav_fleet_yield_stats, mnav_fleet_rollout_rings, mnav_fleet_ring_stats
+#include "mnav_sample_capi.h"     // mnav_follow_sample, mnav_sample_stats
 #include "mnav_graph_capi.h"      // mnav_map_configure / _compute / _layer_changed / _update_layer / _obstacle / _stats
 #include "mnav_replan_capi.h"     // mnav_replan_dijkstra_batch, mnav_replan_stats
 #include "mnav_replan_each_capi.h"   // mnav_replan_dijkstra_each, mnav_replan_each_stats

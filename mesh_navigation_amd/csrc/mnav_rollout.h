@@ -56,29 +56,42 @@ MNAV_HD State rol_start(W3 pos, W3 dir, W3 up, uint32_t face)
   return S;
 }
 
-// steps 2 to 6 (and the count of step 1) for a RUNNING robot whose tick gave R
-MNAV_HD void rol_after_tick(State& S, const mnav_fol::Result& R, const Params& P, W3 goal_pos, W3 goal_dir)
+// steps 2 to 5 (and the count of step 1) for a RUNNING robot whose tick gave R; false: the robot stopped
+MNAV_HD bool rol_arrive(State& S, const mnav_fol::Result& R, const Params& P, W3 goal_pos, W3 goal_dir)
 {
   S.ticks += 1;
-  if (R.code == mnav_fol::kOutOfMap) { S.status = kOutOfMap; S.face = kNone; return; }
+  if (R.code == mnav_fol::kOutOfMap) { S.status = kOutOfMap; S.face = kNone; return false; }
   S.pos = R.pos; S.face = R.face;
   if (P.have_goal) {
     const float gd = mnav::w3_length(mnav::w3_sub(goal_pos, S.pos));                                // :175
     const float ang = mnav::acosf_ref(mnav::w3_dot(goal_dir, S.dir));                              // :176
     S.min_goal_dist = gd < S.min_goal_dist ? gd : S.min_goal_dist;
-    if (gd <= P.dist_tolerance && ang <= P.angle_tolerance) { S.status = kReached; return; }       // :177
+    if (gd <= P.dist_tolerance && ang <= P.angle_tolerance) { S.status = kReached; return false; } // :177
   }
-  if (R.code == mnav_fol::kNoField) { S.status = kNoField; return; }
-  const double step = R.lin * P.dt;
+  if (R.code == mnav_fol::kNoField) { S.status = kNoField; return false; }
+  return true;
+}
+
+// step 6 under the command (lin, ang) at the tick's cost; the rollouts pass the follower's own command, mnav_sample.h a
+// candidate's
+MNAV_HD void rol_step(State& S, double lin, double ang, float cost, const Params& P)
+{
+  const double step = lin * P.dt;
   S.travel += step;
-  S.cost_integral += (double)R.cost * P.dt;
+  S.cost_integral += (double)cost * P.dt;
   S.pos = mnav::w3((float)((double)S.pos.x + (double)S.dir.x * step), (float)((double)S.pos.y + (double)S.dir.y * step),
                    (float)((double)S.pos.z + (double)S.dir.z * step));
-  const float th = (float)(R.ang * P.dt);
+  const float th = (float)(ang * P.dt);
   const float c = mnav::cosf_ref(th), s = mnav::sinf_ref(th);
   const W3 k = mnav::w3_cross(S.up, S.dir);
   const float h = mnav::w3_dot(S.up, S.dir) * (1.0f - c);
   S.dir = mnav::w3_normalized(mnav::w3_add(mnav::w3_add(mnav::w3_scale(S.dir, c), mnav::w3_scale(k, s)), mnav::w3_scale(S.up, h)));
+}
+
+// steps 2 to 6 (and the count of step 1) for a RUNNING robot whose tick gave R
+MNAV_HD void rol_after_tick(State& S, const mnav_fol::Result& R, const Params& P, W3 goal_pos, W3 goal_dir)
+{
+  if (rol_arrive(S, R, P, goal_pos, goal_dir)) rol_step(S, R.lin, R.ang, R.cost, P);
 }
 
 #if !defined(__HIP_DEVICE_COMPILE__)
